@@ -102,6 +102,28 @@ def blas_baseline(q_host, db_host, S):
     return time.perf_counter() - t0, top1, nthr
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(d, **arrays):
+    """--dump-outputs: what the timed path handed its caller in the last timed step, one float64 DIR/<name>.npy per array (DB row
+    indices are exact in float64).  The inputs are seeded, so two builds run with the same arguments can be compared file for file.
+    All arrays share their first axis (one row per query); above DUMP_LIMIT_BYTES a fixed, seeded sample of rows is kept, and the
+    query numbers of that sample go to DIR/rows.npy."""
+    import numpy as np
+    out = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    m = len(next(iter(out.values())))
+    row_bytes = sum(a.nbytes for a in out.values()) // max(m, 1)
+    budget = DUMP_LIMIT_BYTES - 4096                     # room for the .npy headers
+    if row_bytes * m > budget:
+        rows = np.sort(np.random.default_rng(0).choice(m, budget // (row_bytes + 8), replace=False))
+        out = {k: a[rows] for k, a in out.items()}
+        out["rows"] = rows.astype(np.float64)
+    os.makedirs(d, exist_ok=True)
+    for k, a in out.items():
+        np.save(os.path.join(d, k + ".npy"), a)
+
+
 def self_launch(args):
     """`python bench.py --gpus N` with N > 1 and no launcher around it: start the N ranks here (torch.distributed.run, one rank per GPU,
     rendezvous on 127.0.0.1 at a free port) with the same command line.  The ranks inherit stdout / stderr, so rank 0's single JSON line is
@@ -140,6 +162,8 @@ def via_group(args):
     for _ in range(args.steps):
         idx, sc = g.match_topk(q, 0, 2.0, 1)
     dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, idx=idx, score=sc)
     g.set_timing(True)                                             # one more step with events between the phases on every shard's stream
     g.match_topk(q, 0, 2.0, 1)
     per_rank = []
@@ -596,7 +620,11 @@ def main():
     ap.add_argument("--no-extra", action="store_true", help="skip the secondary workloads reported under `extra`")
     ap.add_argument("--no-kitti-shape", action="store_true", help="skip extra.kitti_shape (its drive sampler is ~70 000 torch launches: slow under rocprofv3 --pmc)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (gloo: several ranks on ONE GPU, tests only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the top-k indices and scores of the last timed step to DIR/idx.npy and DIR/score.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.via_group:
         return via_group(args)
@@ -672,6 +700,8 @@ def main():
         idx, score = step(evs[i])
     barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:   # now: the calls below reuse the matcher's output buffers
+        dump_outputs(args.dump_outputs, idx=idx.cpu().numpy(), score=score.cpu().numpy())
     kern_ms = [ev.elapsed_ms(a, b) for a, b in evs]
     # one more step, outside the timed region, with an event after every phase of the protocol on the stream everything runs on (the
     # library's kernels, torch's copies and RCCL's all-gathers share it): per-rank phase times, gathered to rank 0 below
