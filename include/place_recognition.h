@@ -170,6 +170,14 @@ int pr_match_topk_fused(pr_ctx* ctx, const double* sc1, const double* m2dp1, int
                         int32_t n, int32_t mask_width, double p_weight, int32_t k, int32_t* idx, float* score);
 int pr_match_topk_fused_f64(pr_ctx* ctx, const double* sc1, const double* m2dp1, int32_t m, const double* sc2, const double* m2dp2,
                             int32_t n, int32_t mask_width, double p_weight, int32_t k, int32_t* idx, double* score);
+/* Host forms of pr_align_pairs_dev / pr_delight_align_pairs_dev (the variants of processSC.m:22-33, processM2DP.m:12-22,
+ * processDELIGHT.m:7-37 that match() keeps only the minimum of): idx [m][k] as pr_match_topk returns it (-1 or a row of h2).  Only the
+ * DB rows idx references are uploaded (at most m k distinct ones): the cost does not grow with n.  variant / dist [m][k][2]: SC structure,
+ * intensity; M2DP count, intensity; DELIGHT the result in [0], -1 / NaN in [1].  The fused form: [m][k][4] in p5 channel order. */
+int pr_match_align(pr_ctx* ctx, int type, const double* h1, int32_t m, const double* h2, int32_t n, int32_t k, const int32_t* idx,
+                   int32_t* variant, double* dist);
+int pr_match_align_fused(pr_ctx* ctx, const double* sc1, const double* m2dp1, int32_t m, const double* sc2, const double* m2dp2,
+                         int32_t n, int32_t k, const int32_t* idx, int32_t* variant, double* dist);
 int pr_fuse_select2_dev(pr_ctx* ctx, const float* d_p, const float* d_i, const float* e_p, const float* e_i, int32_t m, int32_t n,
                         const double* mom_all, const double* mom2_all, int32_t G, int32_t q_row0, int32_t db_row0,
                         int32_t mask_width, double p_weight, int32_t k, int32_t* idx, float* score);
@@ -327,6 +335,28 @@ int pr_widen_scores_dev(pr_ctx* ctx, const float* score32, int64_t count, double
  * result, not an error).  G <= 64, k <= 128. */
 int pr_merge_topk_dev(pr_ctx* ctx, const int32_t* idx_all, const double* score_all, int32_t G, int32_t m, int32_t k,
                       int32_t* idx, double* score);
+/* Alignment of matched pairs: which variant of the query lines up best with its DB entry.  The reference computes the distance of every
+ * variant and keeps only the minimum (processSC.m:22-33 with permute_sc :37-45, processM2DP.m:12-22, processDELIGHT.m:7-37); these calls
+ * also return its position, in fp64 from the RAW signatures and in the reference's own formulation (the arithmetic of pr_rerank_dev:
+ * the distance returned is, bit for bit, the channel distance pr_rerank_partial_dev writes into p5).  Variants, 0-based:
+ *   SC      v = 2 s + r, s = 0..59 the sector shift, r the mirror flag: row v + 1 of sig_i (processSC.m:24-27) = permute_sc(hist, i, s + 1, r)
+ *           - the entry's sector c against the query's sector (s + c) % 60 (r = 0) or (s - c) % 60 (r = 1)
+ *   M2DP    v = 4 a + b, a the query's variant row and b the entry's (the 4 x 4 block of processM2DP.m:18, rows in test_m2dp.cpp:44-68 order)
+ *   DELIGHT v = k, the row of Mut (processDELIGHT.m:2-5)
+ * Ties go to the lowest variant (DELIGHT: the reference's strict `min_dist > ts`).  No variant: -1 with distance NaN for a zero-norm SC row
+ * (processSC.m:16,19: every variant is NaN), +Inf for a DELIGHT pair without an occupied bin (the reference's untouched min_dist = Inf).
+ * A pair whose idx is -1 or outside this shard's rows [db_row0, db_row0 + n_local) gets -1 / NaN: with the DB row-sharded, exactly one
+ * shard fills each pair, and the shards' results combine by an element-wise max of the variants (fmax of the distances).
+ * Stream-ordered on the context's stream, no allocation, no host synchronisation (can be captured in a hipGraph).
+ * q_* / db_*: DEVICE raw signatures exactly as pr_rerank_dev takes them ([m][2400] / [n_local][2400], [4 m][384] / [4 n_local][384];
+ * dtype PR_F64 | PR_F32); either descriptor pair may be NULL (its slots are -1 / NaN).  idx: DEVICE [m][k] GLOBAL DB rows, -1 = none.
+ * variant / dist: DEVICE [m][k][4], slots in p5 channel order (SC structure, SC intensity, M2DP count, M2DP intensity). */
+int pr_align_pairs_dev(pr_ctx* ctx, const void* q_sc, const void* db_sc, int sc_dtype, const void* q_m2, const void* db_m2, int m2_dtype,
+                       int32_t m, int32_t n_local, int32_t db_row0, int32_t k, const int32_t* idx, int32_t* variant, double* dist);
+/* The same for DELIGHT (processDELIGHT.m:7-37: chi-square over the bins with A + B > 0, mean over those bins, minimum over the 4
+ * permutations): q DEVICE [16 m][256], db DEVICE [16 n_local][256]; variant / dist DEVICE [m][k]. */
+int pr_delight_align_pairs_dev(pr_ctx* ctx, const void* q, const void* db, int dtype, int32_t m, int32_t n_local, int32_t db_row0, int32_t k,
+                               const int32_t* idx, int32_t* variant, double* dist);
 
 /* ---- the database row-sharded over several GPUs of one node (the reference is single-device MATLAB,
  * match_signatures/run_test.m:25-57 - this is that computation with hist2 split by rows) ---------------------------------------
@@ -393,6 +423,15 @@ int pr_delight_generate_frames_dev(pr_ctx* ctx, const double* xyz, const float* 
                                    const double* frames, double* out);
 
 /* ---- host-side rows a1/a2 (CPU in the reference too; no device, no context) ---------------------------- */
+/* Relative pose of an SC match (no reference counterpart: the reference keeps no variant, processSC.m:31): from the two clouds' PCA
+ * frames (utils/pts_align.h:7-46, the [16]-double layout pr_cloud_frames_dev writes) and the SC variant v = 2 s + r of the pair
+ * (pr_align_pairs_dev, structure channel), T [c][3][4] = [R | t] maps points of the QUERY's camera frame into the DB entry's camera frame.
+ * With D = 2 pi / 60 (SC.cpp:33-38): r = 0 turns the aligned y'z' plane by -s D, r = 1 reflects it with B = [[cos f, sin f], [sin f, -cos f]],
+ * f = (s + 1) D; the height axis x' gets the sign sigma = det(E_db) det(E_q) det(B); R = E_db diag(sigma, B) E_q^T, t = mu_db - R mu_q
+ * (DESIGN.md "Alignment").  An initial guess for ICP: the yaw is known to about half a sector (3 deg) where PCA's in-plane axes are
+ * ambiguous, the translation is the alignment of the centroids.  PR_EINVAL (text: pr_last_error(NULL)) for a variant outside [0, 120) or
+ * a frame of fewer than 3 points (slot 13). */
+int pr_sc_relative_pose(const double* frames_q, const double* frames_db, const int32_t* variant, int32_t c, double* T);
 
 /* Replaces pts_preprocess(poses_file, pts_file, incoming_id_file, lidarRange, clouds, polar_filter)
  * (utils/pts_preprocess.h:169-232, records PosesPts.h:5-40): sliding world-point window per pose, camera-frame

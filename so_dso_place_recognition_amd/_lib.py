@@ -50,6 +50,11 @@ SYMBOLS = {
     "pr_order_exact_merge_dev": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     "pr_widen_scores_dev": (C.c_int, [_vp, _vp, C.c_int64, _vp]),
     "pr_merge_topk_dev": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp]),
+    "pr_align_pairs_dev": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "pr_delight_align_pairs_dev": (C.c_int, [_vp, _vp, _vp, C.c_int, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "pr_match_align": (C.c_int, [_vp, C.c_int, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp]),
+    "pr_match_align_fused": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp]),
+    "pr_sc_relative_pose": (C.c_int, [_vp, _vp, _vp, _i32, _vp]),
     "pr_group_create": (C.c_int, [_vp, _i32, C.POINTER(_vp)]),
     "pr_group_destroy": (None, [_vp]),
     "pr_group_last_error": (C.c_char_p, [_vp]),

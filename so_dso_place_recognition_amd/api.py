@@ -422,6 +422,83 @@ def match_topk_fused(sc1, m2dp1, sc2, m2dp2, mask_width=0, p_weight=2.0, k=1, ct
     return idx, sc
 
 
+def match_align(type_, hist1, hist2, idx, ctx: Context | None = None):
+    """The best-aligning variant of every matched pair (pr_match_align): idx [m,k] as match_topk returns it (-1 = none).  Returns
+    (variant int32 [m,k,2], dist float64 [m,k,2]) per channel - SC: structure, intensity, v = 2 * shift + mirror; M2DP: count, intensity,
+    v = 4 * query row + DB row; DELIGHT: [..., 0] the octant permutation, [..., 1] = -1 / NaN.  -1 / NaN where there is no variant."""
+    ctx = ctx or default_context()
+    t = {"sc": TYPE_SC, "m2dp": TYPE_M2DP, "delight": TYPE_DELIGHT}.get(type_, type_)
+    if t not in (TYPE_SC, TYPE_M2DP, TYPE_DELIGHT):
+        raise ValueError("alignment needs type 'sc', 'm2dp' or 'delight' (gist / bow have no variants)")
+    div, width = {TYPE_SC: (1, 2400), TYPE_M2DP: (4, 384), TYPE_DELIGHT: (16, 256)}[t]
+    h1 = np.ascontiguousarray(hist1, np.float64)
+    h2 = np.ascontiguousarray(hist2, np.float64)
+    if h1.ndim != 2 or h2.ndim != 2 or h1.shape[1] != width or h2.shape[1] != width or h1.shape[0] % div or h2.shape[0] % div:
+        raise ValueError(f"expected [{div}*m, {width}] and [{div}*n, {width}] signature matrices")
+    m, n = h1.shape[0] // div, h2.shape[0] // div
+    ix = np.ascontiguousarray(idx, np.int32)
+    if ix.ndim != 2 or ix.shape[0] != m:
+        raise ValueError("idx must be [m, k]")
+    k = ix.shape[1]
+    var = np.empty((m, k, 2), np.int32); dist = np.empty((m, k, 2), np.float64)
+    ctx.check(ctx.lib.pr_match_align(ctx.h, t, _ptr(h1), m, _ptr(h2), n, k, _ptr(ix), _ptr(var), _ptr(dist)))
+    return var, dist
+
+
+def match_align_fused(sc1, m2dp1, sc2, m2dp2, idx, ctx: Context | None = None):
+    """match_align for the pairs of match_topk_fused (pr_match_align_fused) -> (variant int32 [m,k,4], dist float64 [m,k,4]): SC structure,
+    SC intensity, M2DP count, M2DP intensity."""
+    ctx = ctx or default_context()
+    a1 = np.ascontiguousarray(sc1, np.float64); a2 = np.ascontiguousarray(sc2, np.float64)
+    b1 = np.ascontiguousarray(m2dp1, np.float64); b2 = np.ascontiguousarray(m2dp2, np.float64)
+    m, n = a1.shape[0], a2.shape[0]
+    if b1.shape != (4 * m, 384) or b2.shape != (4 * n, 384) or a1.shape[1] != 2400 or a2.shape[1] != 2400:
+        raise ValueError("need SC [m, 2400] and M2DP [4 m, 384] signatures of the same m (n) places")
+    ix = np.ascontiguousarray(idx, np.int32)
+    if ix.ndim != 2 or ix.shape[0] != m:
+        raise ValueError("idx must be [m, k]")
+    k = ix.shape[1]
+    var = np.empty((m, k, 4), np.int32); dist = np.empty((m, k, 4), np.float64)
+    ctx.check(ctx.lib.pr_match_align_fused(ctx.h, _ptr(a1), _ptr(b1), m, _ptr(a2), _ptr(b2), n, k, _ptr(ix), _ptr(var), _ptr(dist)))
+    return var, dist
+
+
+def cloud_frames(xyz, inten, offs, ctx: Context | None = None) -> np.ndarray:
+    """PCA frames of clouds in CSR layout (pr_cloud_frames_dev: utils/pts_align.h:7-46 on the GPU) -> host float64 [N, 16]: mean[3], the
+    eigenvectors by ascending eigenvalue [3][3], 0, point count, and with intensities the cloud's float average and 1.0 (else 0, 0).
+    Numpy arrays or device tensors; the clouds go through device memory of the context's GPU."""
+    import torch
+    ctx = ctx or default_context()
+    dev = torch.device("cuda", ctx.device)
+    x = torch.as_tensor(xyz, dtype=torch.float64).to(dev).contiguous()
+    o = torch.as_tensor(offs, dtype=torch.int64).to(dev).contiguous()
+    it = None if inten is None else torch.as_tensor(inten, dtype=torch.float32).to(dev).contiguous()
+    N = o.numel() - 1
+    fr = torch.empty((max(N, 0), 16), dtype=torch.float64, device=dev)
+    torch.cuda.synchronize(dev)                       # the uploads (torch's stream) before the library's stream reads them
+    ctx.check(ctx.lib.pr_cloud_frames_dev(ctx.h, C.c_void_p(x.data_ptr()), None if it is None else C.c_void_p(it.data_ptr()),
+                                          C.c_void_p(o.data_ptr()), N, C.c_void_p(fr.data_ptr())))
+    ctx.sync()
+    return fr.cpu().numpy()
+
+
+def sc_relative_pose(frames_q, frames_db, variant) -> np.ndarray:
+    """[R | t] float64 [c, 3, 4] mapping query-camera-frame points into the DB entry's camera frame, from the two clouds' frames
+    ([c, 16] as cloud_frames returns them) and the SC structure-channel variant of the pair ([c], match_align / Matcher.align):
+    pr_sc_relative_pose, host only.  An initial guess for ICP (DESIGN.md "Alignment")."""
+    fq = np.ascontiguousarray(frames_q, np.float64).reshape(-1, 16)
+    fd = np.ascontiguousarray(frames_db, np.float64).reshape(-1, 16)
+    v = np.ascontiguousarray(variant, np.int32).reshape(-1)
+    if fq.shape[0] != v.shape[0] or fd.shape[0] != v.shape[0]:
+        raise ValueError("frames_q, frames_db and variant must describe the same pairs")
+    T = np.empty((v.shape[0], 3, 4), np.float64)
+    lib = _lib.load()
+    rc = lib.pr_sc_relative_pose(_ptr(fq), _ptr(fd), _ptr(v), v.shape[0], _ptr(T))
+    if rc != 0:
+        raise PRError(rc, lib.pr_last_error(None).decode())
+    return T
+
+
 def run_test(type_, hist1, hist2, gt1=None, gt2=None, loop_diff=None, mask_width=0, ctx: Context | None = None):
     """run_test.m:1.  Without ground truth: returns (diff_v, diff_idx) of run_test.m:57 (0-based indices).
     With gt1/gt2/loop_diff: returns (AUC, top_recall, lp_detected) through eval.precision_recall; the sweep ranks the QUERIES by their

@@ -12,6 +12,10 @@
 //                                     mask of run_test.m:47-53 restricted to the past), then joins the database - resident on the GPU and grown IN
 //                                     PLACE (pr_group_set_database_growable / pr_group_append_database), one pr_group_match_topk per keyframe.
 //                                     Rows with fewer than two candidates come out as -1 NaN.  sc | m2dp; --devices optional (default: device 0)
+//   [--align_out F]                   the best-aligning variant of every returned pair (pr_match_align, one device whatever --devices; with --online
+//                                     the indices are rows of hist1): one line per query, K groups "v_ch0 v_ch1", -1 where there is none.  SC: structure,
+//                                     intensity, v = 2 shift + mirror (processSC.m:24-27); M2DP: count, intensity, v = 4 a + b (processM2DP.m:18);
+//                                     DELIGHT: the octant permutation (processDELIGHT.m:2-5) and -1.  sc | m2dp | delight
 // Output: one line per query: K pairs "index score" (0-based indices unless --one_based 1), and the reference's
 // console lines `type` / `tm` (ms per query, run_test.m:42-44).  Scores are doubles, as MATLAB holds them.
 #include <chrono>
@@ -26,11 +30,14 @@ int main(int argc, char** argv) {
   std::string type, h1f, h2f, outf;
   if (!prm.get("type", type) || !prm.get("hist1", h1f) || !prm.get("hist2", h2f) || !prm.get("out", outf) ||
       (type != "sc" && type != "m2dp" && type != "delight" && type != "gist" && type != "bow")) {
-    printf("usage: match_signatures --type sc|m2dp|delight|gist|bow --hist1 F --hist2 F [--mask_width W] [--p_weight 2] [--topk K] [--one_based 0|1] --out F\n");
+    printf("usage: match_signatures --type sc|m2dp|delight|gist|bow --hist1 F --hist2 F [--mask_width W] [--p_weight 2] [--topk K] [--one_based 0|1] --out F [--align_out F]\n");
     return 1;
   }
   const int t = type == "sc" ? PR_TYPE_SC : type == "m2dp" ? PR_TYPE_M2DP : type == "delight" ? PR_TYPE_DELIGHT : type == "gist" ? PR_TYPE_GIST : PR_TYPE_BOW;
   const bool cols_type = t == PR_TYPE_GIST || t == PR_TYPE_BOW;        // no fixed signature length
+  std::string alignf;
+  const bool want_align = prm.get("align_out", alignf);
+  if (want_align && cols_type) { fprintf(stderr, "--align_out needs --type sc|m2dp|delight (gist / bow signatures have no variants)\n"); return 1; }
   const int div = t == PR_TYPE_SC ? 1 : t == PR_TYPE_M2DP ? 4 : t == PR_TYPE_DELIGHT ? 16 : t == PR_TYPE_BOW ? 2 : 1;
   int64_t width = t == PR_TYPE_SC ? PR_SC_SIG_LEN : (t == PR_TYPE_M2DP ? PR_M2DP_SIG_LEN : PR_DELIGHT_SIG_LEN);
   double *h1 = nullptr, *h2 = nullptr;
@@ -128,6 +135,21 @@ int main(int argc, char** argv) {
                             nullptr, &nd) != PR_OK) { fprintf(stderr, "%s\n", pr_host_last_error()); pr_destroy(ctx); return 4; }
     printf("AUC = %.9g\ntop_recall = %.9g\nlp_detected = %d\n", auc, tr, nd);
     pr_free(g1); pr_free(g2);
+  }
+  if (want_align) {   // the variants of the returned pairs, on one device (the online form matched hist1 against its own earlier rows)
+    if (!ctx && pr_create(dev_ids.empty() ? (int)prm.num("device", 0) : dev_ids[0], &ctx) != PR_OK) { fprintf(stderr, "%s\n", pr_last_error(nullptr)); return 3; }
+    std::vector<int32_t> var((size_t)m * k * 2);
+    std::vector<double> vd((size_t)m * k * 2);
+    if (pr_match_align(ctx, t, h1, m, online ? h1 : h2, online ? m : n, k, idx.data(), var.data(), vd.data()) != PR_OK) {
+      fprintf(stderr, "alignment failed: %s\n", pr_last_error(ctx)); pr_destroy(ctx); return 4;
+    }
+    FILE* fa = fopen(alignf.c_str(), "w");
+    if (!fa) { fprintf(stderr, "cannot write %s\n", alignf.c_str()); pr_destroy(ctx); return 5; }
+    for (int32_t i = 0; i < m; i++) {
+      for (int32_t j = 0; j < k; j++) fprintf(fa, "%s%d %d", j ? " " : "", var[((size_t)i * k + j) * 2], var[((size_t)i * k + j) * 2 + 1]);
+      fputc('\n', fa);
+    }
+    fclose(fa);
   }
   FILE* f = fopen(outf.c_str(), "w");
   if (!f) { fprintf(stderr, "cannot write %s\n", outf.c_str()); pr_destroy(ctx); return 5; }

@@ -193,6 +193,12 @@ void launch_rerank_finish(hipStream_t st, const int32_t* cand_idx, const double*
 void launch_widen(hipStream_t st, const float* a, long long n, double* b);
 void launch_merge_topk(hipStream_t st, const int32_t* idx_all, const double* score_all, int G, int m, int k, int32_t* idx, double* score);
 
+// align.hip — the argmin variant of a (query, DB entry) pair per channel (processSC.m:22-33, processM2DP.m:12-22, processDELIGHT.m:7-37)
+void launch_align(hipStream_t st, const void* q_sc, const void* db_sc, int sc_dt, const void* q_m2, const void* db_m2, int m2_dt, int m,
+                  int n_local, int db_row0, int k, const int32_t* idx, int32_t* variant /* [m][k][4] */, double* dist /* [m][k][4] */);
+void launch_delight_align(hipStream_t st, const void* q, const void* db, int dt, int m, int n_local, int db_row0, int k, const int32_t* idx,
+                          int32_t* variant /* [m][k] */, double* dist /* [m][k] */);
+
 // sc_gen.hip / m2dp_gen.hip — pts_align.h:7-46 + SC.cpp:12-76 / M2DP.cpp:38-109 (+ test_m2dp.cpp:44-68)
 void launch_ave_chain(hipStream_t st, const float* inten, const int64_t* offs, int N, float* ave /* [N] or NULL */,
                       double* frames = nullptr /* non-NULL: also frames[c][14] = the average, [15] = 1 (frames.hpp) */);

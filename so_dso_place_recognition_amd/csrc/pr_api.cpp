@@ -1194,6 +1194,34 @@ int pr_merge_topk_dev(pr_ctx* ctx, const int32_t* idx_all, const double* score_a
   return PR_OK;
 }
 
+int pr_align_pairs_dev(pr_ctx* ctx, const void* q_sc, const void* db_sc, int sc_dtype, const void* q_m2, const void* db_m2, int m2_dtype,
+                       int32_t m, int32_t n_local, int32_t db_row0, int32_t k, const int32_t* idx, int32_t* variant, double* dist) {
+  if (!ctx) return PR_EINVAL;
+  const bool sc = q_sc || db_sc, m2 = q_m2 || db_m2;
+  if ((!sc && !m2) || (sc && (!q_sc || !db_sc)) || (m2 && (!q_m2 || !db_m2)) || !idx || !variant || !dist || m < 0 || n_local < 0 ||
+      db_row0 < 0 || k < 1 || (int64_t)m * k * 4 > INT32_MAX || (sc && sc_dtype != PR_F64 && sc_dtype != PR_F32) ||
+      (m2 && m2_dtype != PR_F64 && m2_dtype != PR_F32))
+    PR_FAIL(ctx, PR_EINVAL, "pr_align_pairs_dev: bad arguments (m=%d, n_local=%d, db_row0=%d, k=%d)", m, n_local, db_row0, k);
+  if (m == 0) return PR_OK;
+  if (int rc = set_device(ctx)) return rc;
+  pr::launch_align(ctx->stream, q_sc, db_sc, sc_dtype, q_m2, db_m2, m2_dtype, m, n_local, db_row0, k, idx, variant, dist);
+  PR_HIP(ctx, hipGetLastError());
+  return PR_OK;
+}
+
+int pr_delight_align_pairs_dev(pr_ctx* ctx, const void* q, const void* db, int dtype, int32_t m, int32_t n_local, int32_t db_row0, int32_t k,
+                               const int32_t* idx, int32_t* variant, double* dist) {
+  if (!ctx) return PR_EINVAL;
+  if (!q || !db || !idx || !variant || !dist || m < 0 || n_local < 0 || db_row0 < 0 || k < 1 || (int64_t)m * k > INT32_MAX ||
+      (dtype != PR_F64 && dtype != PR_F32))
+    PR_FAIL(ctx, PR_EINVAL, "pr_delight_align_pairs_dev: bad arguments (m=%d, n_local=%d, db_row0=%d, k=%d)", m, n_local, db_row0, k);
+  if (m == 0) return PR_OK;
+  if (int rc = set_device(ctx)) return rc;
+  pr::launch_delight_align(ctx->stream, q, db, dtype, m, n_local, db_row0, k, idx, variant, dist);
+  PR_HIP(ctx, hipGetLastError());
+  return PR_OK;
+}
+
 // ------------------------------------------------------------------------------------------- host-buffer path
 
 
@@ -1498,6 +1526,99 @@ int pr_match_topk_fused(pr_ctx* ctx, const double* sc1, const double* m2dp1, int
 int pr_match_topk_fused_f64(pr_ctx* ctx, const double* sc1, const double* m2dp1, int32_t m, const double* sc2, const double* m2dp2,
                             int32_t n, int32_t mask_width, double p_weight, int32_t k, int32_t* idx, double* score) {
   return fused_host(ctx, sc1, m2dp1, m, sc2, m2dp2, n, mask_width, p_weight, k, idx, nullptr, score);
+}
+
+// pr_match_align / pr_match_align_fused.  type: PR_TYPE_SC | PR_TYPE_M2DP | PR_TYPE_DELIGHT with h1 = a1, h2 = a2, or -1 = fused (a: SC,
+// b: M2DP).  Only the DB rows that idx references go to the device - at most m * k distinct ones, renumbered in ascending order - so the
+// cost does not grow with n; the device forms then run on that compacted shard.  var_out / dist_out: [m][k][S], S = 4 (fused) or 2.
+static int align_host(pr_ctx* ctx, const char* who, int type, const double* a1, const double* b1, int32_t m, const double* a2, const double* b2,
+                      int32_t n, int32_t k, const int32_t* idx, int32_t* var_out, double* dist_out) {
+  if (!ctx) return PR_EINVAL;
+  const bool fused = type < 0;
+  if (!fused && type != PR_TYPE_SC && type != PR_TYPE_M2DP && type != PR_TYPE_DELIGHT) PR_FAIL(ctx, PR_EINVAL, "%s: type must be SC, M2DP or DELIGHT", who);
+  if (m < 0 || n < 0 || k < 1 || (int64_t)m * k * 4 > INT32_MAX || (m > 0 && (!idx || !var_out || !dist_out || !a1 || (fused && !b1))))
+    PR_FAIL(ctx, PR_EINVAL, "%s: bad arguments (m=%d, n=%d, k=%d)", who, m, n, k);
+  const size_t mk = (size_t)m * k;
+  std::vector<int32_t> rows;
+  rows.reserve(mk);
+  for (size_t i = 0; i < mk; i++) {
+    if (idx[i] < -1 || idx[i] >= n) PR_FAIL(ctx, PR_EINVAL, "%s: idx[%zu] = %d is outside [-1, %d)", who, i, idx[i], n);
+    if (idx[i] >= 0) rows.push_back(idx[i]);
+  }
+  std::sort(rows.begin(), rows.end());
+  rows.erase(std::unique(rows.begin(), rows.end()), rows.end());
+  const int S = fused ? 4 : 2;
+  if (rows.empty()) {                                            // nothing referenced: every pair is "no candidate"
+    for (size_t i = 0; i < mk * S; i++) { var_out[i] = -1; dist_out[i] = NAN; }
+    return PR_OK;
+  }
+  if (!a2 || (fused && !b2)) PR_FAIL(ctx, PR_EINVAL, "%s: the DB signatures are NULL", who);
+  std::vector<int32_t> lidx(mk);
+  for (size_t i = 0; i < mk; i++)
+    lidx[i] = idx[i] < 0 ? -1 : (int32_t)(std::lower_bound(rows.begin(), rows.end(), idx[i]) - rows.begin());
+  if (int rc = set_device(ctx)) return rc;
+  const int32_t u = (int32_t)rows.size();
+  // the descriptor types of the call: {rows per signature, doubles per row, query signatures, DB signatures}
+  struct Part { size_t rows_per, cols; const double* q; const double* db; };
+  std::vector<Part> parts;
+  if (fused) parts = {{1, PR_SC_SIG_LEN, a1, a2}, {4, PR_M2DP_SIG_LEN, b1, b2}};
+  else if (type == PR_TYPE_SC) parts = {{1, PR_SC_SIG_LEN, a1, a2}};
+  else if (type == PR_TYPE_M2DP) parts = {{4, PR_M2DP_SIG_LEN, a1, a2}};
+  else parts = {{16, PR_DELIGHT_SIG_LEN, a1, a2}};
+  DevScope scope_(ctx);
+  DevBuf dq[2], ddb[2], didx, dvar, ddist;
+  const size_t slots = type == PR_TYPE_DELIGHT ? 1 : 4;          // of the device form's output
+  std::vector<double> gathered;
+  for (size_t p = 0; p < parts.size(); p++) {
+    const Part& P = parts[p];
+    const size_t sig = P.rows_per * P.cols;                      // doubles per signature
+    gathered.resize((size_t)u * sig);
+    for (int32_t r = 0; r < u; r++) std::memcpy(gathered.data() + (size_t)r * sig, P.db + (size_t)rows[r] * sig, sig * 8);
+    PR_HIP(ctx, dq[p].alloc((size_t)m * sig * 8));
+    PR_HIP(ctx, ddb[p].alloc((size_t)u * sig * 8));
+    PR_HIP(ctx, hipMemcpyAsync(dq[p].p, P.q, (size_t)m * sig * 8, hipMemcpyHostToDevice, ctx->stream));
+    PR_HIP(ctx, hipMemcpyAsync(ddb[p].p, gathered.data(), (size_t)u * sig * 8, hipMemcpyHostToDevice, ctx->stream));
+    PR_HIP(ctx, hipStreamSynchronize(ctx->stream));              // (`gathered` is reused by the next part)
+  }
+  PR_HIP(ctx, didx.alloc(mk * 4));
+  PR_HIP(ctx, dvar.alloc(mk * slots * 4));
+  PR_HIP(ctx, ddist.alloc(mk * slots * 8));
+  PR_HIP(ctx, hipMemcpyAsync(didx.p, lidx.data(), mk * 4, hipMemcpyHostToDevice, ctx->stream));
+  int rc;
+  if (type == PR_TYPE_DELIGHT)
+    rc = pr_delight_align_pairs_dev(ctx, dq[0].p, ddb[0].p, PR_F64, m, u, 0, k, didx.as<int32_t>(), dvar.as<int32_t>(), ddist.as<double>());
+  else if (fused)
+    rc = pr_align_pairs_dev(ctx, dq[0].p, ddb[0].p, PR_F64, dq[1].p, ddb[1].p, PR_F64, m, u, 0, k, didx.as<int32_t>(), dvar.as<int32_t>(),
+                            ddist.as<double>());
+  else {
+    const bool sc = type == PR_TYPE_SC;
+    rc = pr_align_pairs_dev(ctx, sc ? dq[0].p : nullptr, sc ? ddb[0].p : nullptr, PR_F64, sc ? nullptr : dq[0].p, sc ? nullptr : ddb[0].p, PR_F64,
+                            m, u, 0, k, didx.as<int32_t>(), dvar.as<int32_t>(), ddist.as<double>());
+  }
+  if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+  std::vector<int32_t> hv(mk * slots);
+  std::vector<double> hd(mk * slots);
+  PR_HIP(ctx, hipMemcpyAsync(hv.data(), dvar.p, mk * slots * 4, hipMemcpyDeviceToHost, ctx->stream));
+  PR_HIP(ctx, hipMemcpyAsync(hd.data(), ddist.p, mk * slots * 8, hipMemcpyDeviceToHost, ctx->stream));
+  PR_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  const size_t first = type == PR_TYPE_M2DP ? 2 : 0;             // the device form's slots this call returns
+  for (size_t i = 0; i < mk; i++)
+    for (int s = 0; s < S; s++) {
+      const bool have = type != PR_TYPE_DELIGHT || s == 0;
+      var_out[i * S + s] = have ? hv[i * slots + first + s] : -1;
+      dist_out[i * S + s] = have ? hd[i * slots + first + s] : NAN;
+    }
+  return PR_OK;
+}
+
+int pr_match_align(pr_ctx* ctx, int type, const double* h1, int32_t m, const double* h2, int32_t n, int32_t k, const int32_t* idx,
+                   int32_t* variant, double* dist) {
+  return align_host(ctx, "pr_match_align", type, h1, nullptr, m, h2, nullptr, n, k, idx, variant, dist);
+}
+
+int pr_match_align_fused(pr_ctx* ctx, const double* sc1, const double* m2dp1, int32_t m, const double* sc2, const double* m2dp2, int32_t n,
+                         int32_t k, const int32_t* idx, int32_t* variant, double* dist) {
+  return align_host(ctx, "pr_match_align_fused", -1, sc1, m2dp1, m, sc2, m2dp2, n, k, idx, variant, dist);
 }
 
 // GIST / BoW (run_test.m:32-35): one distance matrix from raw f64 rows of `cols` columns, no packing, no fusion
@@ -1863,6 +1984,50 @@ int pr_generate_clouds(pr_ctx* ctx, int type, const pr_clouds* c, double max_rho
   if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
   PR_HIP(ctx, hipMemcpyAsync(out, dout.p, (size_t)N * rowlen * 8, hipMemcpyDeviceToHost, ctx->stream));
   PR_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return PR_OK;
+}
+
+// SC relative pose from the two clouds' PCA frames and the winning SC variant v = 2 s + r (DESIGN.md "Alignment").  The sector of an
+// aligned point is floor((atan2(z', y') + pi) / D), D = 2 pi / 60 (SC.cpp:33-38), aligned p' = E^T (p - mu), E = [v0 v1 v2].
+//   r = 0: the entry's sector c matched the query's sector c + s: d'_yz = Rot(-s D) q'_yz
+//   r = 1: the entry's sector c matched the query's sector s - c: d'_yz = B q'_yz, B = [[cos f, sin f], [sin f, -cos f]], f = (s + 1) D
+//          (the reflection that maps the query's sector centres onto the entry's)
+// The height axis x' has no sign in either channel (max - min height, intensity); sigma = det(E_db) det(E_q) det(B) makes R proper.
+// S = diag(sigma, B), R = E_db S E_q^T, t = mu_db - R mu_q.  An initial guess (yaw to half a sector, translation = centroid alignment).
+int pr_sc_relative_pose(const double* frames_q, const double* frames_db, const int32_t* variant, int32_t c, double* T) {
+  if (c < 0 || (c > 0 && (!frames_q || !frames_db || !variant || !T))) PR_FAIL((pr_ctx*)nullptr, PR_EINVAL, "pr_sc_relative_pose: bad arguments (c=%d)", c);
+  for (int32_t i = 0; i < c; i++) {
+    if (variant[i] < 0 || variant[i] >= 120)
+      PR_FAIL((pr_ctx*)nullptr, PR_EINVAL, "pr_sc_relative_pose: variant[%d] = %d is outside [0, 120)", i, variant[i]);
+    if (!(frames_q[16 * (size_t)i + 13] >= 3) || !(frames_db[16 * (size_t)i + 13] >= 3))
+      PR_FAIL((pr_ctx*)nullptr, PR_EINVAL, "pr_sc_relative_pose: frame %d has fewer than 3 points (slot 13)", i);
+  }
+  const double D = 2.0 * M_PI / 60.0;
+  for (int32_t i = 0; i < c; i++) {
+    const double* fq = frames_q + 16 * (size_t)i;
+    const double* fd = frames_db + 16 * (size_t)i;
+    const int s = variant[i] >> 1, r = variant[i] & 1;
+    double Eq[3][3], Ed[3][3];                                   // [component][eigenvector]
+    for (int j = 0; j < 3; j++)
+      for (int e = 0; e < 3; e++) { Eq[j][e] = fq[3 + 3 * e + j]; Ed[j][e] = fd[3 + 3 * e + j]; }
+    auto det3 = [](const double (&M)[3][3]) {
+      return M[0][0] * (M[1][1] * M[2][2] - M[1][2] * M[2][1]) - M[0][1] * (M[1][0] * M[2][2] - M[1][2] * M[2][0]) +
+             M[0][2] * (M[1][0] * M[2][1] - M[1][1] * M[2][0]);
+    };
+    const double a = r ? (s + 1) * D : s * D, ca = std::cos(a), sa = std::sin(a);
+    const double sigma = det3(Ed) * det3(Eq) * (r ? -1.0 : 1.0) < 0 ? -1.0 : 1.0;
+    const double S[3][3] = {{sigma, 0, 0}, {0, ca, sa}, {0, r ? sa : -sa, r ? -ca : ca}};
+    double ES[3][3], R[3][3];
+    for (int j = 0; j < 3; j++)
+      for (int e = 0; e < 3; e++) ES[j][e] = Ed[j][0] * S[0][e] + Ed[j][1] * S[1][e] + Ed[j][2] * S[2][e];
+    for (int j = 0; j < 3; j++)
+      for (int e = 0; e < 3; e++) R[j][e] = ES[j][0] * Eq[e][0] + ES[j][1] * Eq[e][1] + ES[j][2] * Eq[e][2];   // E_db S E_q^T
+    double* o = T + 12 * (size_t)i;
+    for (int j = 0; j < 3; j++) {
+      for (int e = 0; e < 3; e++) o[4 * j + e] = R[j][e];
+      o[4 * j + 3] = fd[j] - (R[j][0] * fq[0] + R[j][1] * fq[1] + R[j][2] * fq[2]);
+    }
+  }
   return PR_OK;
 }
 

@@ -1,6 +1,7 @@
-// rerank_common.hpp - device helpers shared by rerank.hip (fp64 re-evaluation of the selection's survivors) and exact_row.hip (the
-// flagged queries' exact rows): the reference's pair distances in fp64 (processSC.m:15-33, processM2DP.m:12-22), Chan combination of
-// the shards' moments, the (score, index) order of run_test.m:57, and the flagged-query list of a call.
+// rerank_common.hpp - device helpers shared by rerank.hip (fp64 re-evaluation of the selection's survivors), exact_row.hip (the
+// flagged queries' exact rows) and align.hip (the best-aligning variant of a pair): the reference's pair distances in fp64
+// (processSC.m:15-33, processM2DP.m:12-22), Chan combination of the shards' moments, the (score, index) order of run_test.m:57, and the
+// flagged-query list of a call.
 #pragma once
 #include "kernels.hpp"
 
@@ -36,13 +37,40 @@ __device__ __forceinline__ double block_min256(double v, double* red, int tid) {
   return r;
 }
 
+// The minimum AND its position over the 256 threads: (value, index) pairs ordered NaN last, then by value, ties -> lower index (the order
+// is total for distinct indices, so both partners of an xor exchange keep the same pair).  *iout = -1 when every value is NaN.  ired: LDS [4].
+__device__ __forceinline__ bool arg_before(double av, int ai, double bv, int bi) {
+  const bool an = av != av, bn = bv != bv;
+  if (an != bn) return bn;
+  return (!an && av < bv) || ((an || av == bv) && ai < bi);
+}
+__device__ __forceinline__ double block_argmin256(double v, int i, double* red, int* ired, int tid, int* iout) {
+#pragma unroll
+  for (int s = 32; s > 0; s >>= 1) {
+    const double ov = __shfl_xor(v, s, 64);
+    const int oi = __shfl_xor(i, s, 64);
+    if (arg_before(ov, oi, v, i)) { v = ov; i = oi; }
+  }
+  if ((tid & 63) == 0) { red[tid >> 6] = v; ired[tid >> 6] = i; }
+  __syncthreads();
+  v = red[0]; i = ired[0];
+  for (int w = 1; w < 4; w++)
+    if (arg_before(red[w], ired[w], v, i)) { v = red[w]; i = ired[w]; }
+  __syncthreads();
+  *iout = (v != v) ? -1 : i;
+  return v;
+}
+
 // processSC.m:15-33 for one channel of one pair, fp64.  buf: 60 x 21 (query, padded sector stride) + 1200 (entry) doubles.
 // Thread = (ring r, block of 5 consecutive shifts): it walks the 60 sectors of the entry once and keeps the 5 forward and
 // 5 mirrored variants of its shifts in registers - a sliding window over the query's ring column, so every step costs three
 // LDS reads (entry value, one new query value per direction) for ten multiply-adds; the first version read two operands
 // per multiply-add and was LDS-bound at 3.2 ms per 4096 x 9 pairs.
+// ARG: also the variant of the minimum into *arg (ired: LDS [4]) - variant v = 2 s + r is row v + 1 of sig_i (processSC.m:24-27), i.e.
+// permute_sc(hist, i, s + 1, r): the entry's sector c against the query's sector (s + c) % 60 (r = 0) or (s - c) % 60 (r = 1).
+template <bool ARG = false>
 __device__ double sc_pair_exact(const void* qsig, int qdt, size_t qoff, const void* dsig, int ddt, size_t doff,
-                                double* buf /*60*21 + 1200*/, double* red, int tid) {
+                                double* buf /*60*21 + 1200*/, double* red, int tid, int* ired = nullptr, int* arg = nullptr) {
   double* qs = buf;
   double* ds = buf + 60 * 21;
   double pq = 0.0, pd = 0.0;
@@ -102,13 +130,16 @@ __device__ double sc_pair_exact(const void* qsig, int qdt, size_t qoff, const vo
     for (int q = 0; q < 20; q++) dot += buf[tid * 20 + q];
     diff = (1.0 - dot) / 2.0;                                    // processSC.m:30
   }
+  if constexpr (ARG) return block_argmin256(diff, tid, red, ired, tid, arg);   // (diff of thread tid < 120 = variant tid)
   const double best = block_min256(diff, red, tid);              // processSC.m:31 (its barriers also free buf for the next channel)
   return best;
 }
 
 // processM2DP.m:12-22 for one channel of one pair: rows [4][384], channel columns [192 ch, 192 ch + 192)
+// ARG: also the variant of the minimum into *arg - v = 4 a + b, a the query's variant row, b the entry's (test_m2dp.cpp:44-68 row order)
+template <bool ARG = false>
 __device__ double m2dp_pair_exact(const void* qsig, int qdt, size_t qoff, const void* dsig, int ddt, size_t doff, int ch,
-                                  double* red, int tid) {
+                                  double* red, int tid, int* ired = nullptr, int* arg = nullptr) {
   // thread = (a, b, part of 16 x 12 columns)
   const int ab = tid >> 4, part = tid & 15, a = ab >> 2, b = ab & 3;
   double s = 0.0;
@@ -123,6 +154,7 @@ __device__ double m2dp_pair_exact(const void* qsig, int qdt, size_t qoff, const 
     diff = (1.0 - dot) / 2.0;                                   // processM2DP.m:15
   }
   __syncthreads();
+  if constexpr (ARG) return block_argmin256(diff, ab, red, ired, tid, arg);
   return block_min256(diff, red, tid);                          // processM2DP.m:19
 }
 

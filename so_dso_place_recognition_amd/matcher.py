@@ -392,6 +392,38 @@ class Matcher(_Base):
                 mark("exact rows (one shard)")
         return idx, score
 
+    def align(self, idx: torch.Tensor, db_row0: int = 0):
+        """The best-aligning variant of every pair (query of the last match(), DB row idx[q, j]) -> (variant int32 [m,k,2], dist float64
+        [m,k,2]) device tensors, per channel (SC: structure, intensity, v = 2 * shift + mirror; M2DP: count, intensity, v = 4 * query row +
+        DB row; DELIGHT: [..., 0] the octant permutation, [..., 1] = -1 / NaN), from the raw rows in fp64 (pr_align_pairs_dev /
+        pr_delight_align_pairs_dev: the variant arithmetic of the re-evaluation, whatever the matcher's arithmetic; a growing DB included).
+        idx: GLOBAL DB rows [m,k] as match() returns them; db_row0: the first global row of this matcher's shard.  Entries outside
+        [db_row0, db_row0 + n) come back -1 / NaN, so with the DB row-sharded exactly one shard fills each pair: combine the shards'
+        results with torch.maximum on the variants (torch.fmax on the distances).  Stream-ordered, no host synchronisation."""
+        assert self.db_sig is not None and getattr(self, "_q_sig", None) is not None, "match() first"
+        assert self._q_sig.dtype == self.db_sig.dtype
+        idx = idx.to(torch.int32).contiguous()
+        m, k = idx.shape
+        assert m == self._m
+        raw = (_dptr(self._q_sig), _dptr(self.db_sig), _torch_dt(self.db_sig))
+        if self.plain:
+            v1 = torch.empty((m, k), dtype=torch.int32, device=self.dev)
+            d1 = torch.empty((m, k), dtype=torch.float64, device=self.dev)
+            self._enter()
+            self.ctx.check(self.lib.pr_delight_align_pairs_dev(self.ctx.h, *raw, m, self.n, int(db_row0), k, _dptr(idx), _dptr(v1), _dptr(d1)))
+            self._leave()
+            return (torch.stack([v1, torch.full_like(v1, -1)], -1), torch.stack([d1, torch.full_like(d1, float("nan"))], -1))
+        var = torch.empty((m, k, 4), dtype=torch.int32, device=self.dev)
+        dist = torch.empty((m, k, 4), dtype=torch.float64, device=self.dev)
+        sc = self.type == _lib.TYPE_SC
+        none = (None, None, 0)
+        self._enter()
+        self.ctx.check(self.lib.pr_align_pairs_dev(self.ctx.h, *(raw if sc else none), *(none if sc else raw), m, self.n, int(db_row0), k,
+                                                   _dptr(idx), _dptr(var), _dptr(dist)))
+        self._leave()
+        c0 = 0 if sc else 2
+        return var[..., c0:c0 + 2], dist[..., c0:c0 + 2]
+
     def flagged_count(self) -> int:
         """Queries the last match(..., exact_order=False) of ONE rank left flagged by the order / containment checks (the ones the default
         match() answers from their exact rows).  Synchronises (pr_order_flagged_count); 0 once a resolving call has taken the flags."""
@@ -585,6 +617,20 @@ class FusedMatcher(_Base):
         elif resolve is not None and G == 1:
             self._resolve_order(self._raw6(), self._m1, self._m2, self.sc._m, self.sc.n, q_row0, mask_width, p_weight, k, idx, score, exact_order)
         return idx, score
+
+    def align(self, idx: torch.Tensor, db_row0: int = 0):
+        """Matcher.align for the pairs of the last match() -> (variant int32 [m,k,4], dist float64 [m,k,4]): SC structure, SC intensity,
+        M2DP count, M2DP intensity (pr_align_pairs_dev with both descriptor types).  Sharding as Matcher.align."""
+        assert self.sc.db_sig is not None and getattr(self.sc, "_q_sig", None) is not None, "match() first"
+        idx = idx.to(torch.int32).contiguous()
+        m, k = idx.shape
+        assert m == self.sc._m
+        var = torch.empty((m, k, 4), dtype=torch.int32, device=self.dev)
+        dist = torch.empty((m, k, 4), dtype=torch.float64, device=self.dev)
+        self._enter()
+        self.ctx.check(self.lib.pr_align_pairs_dev(self.ctx.h, *self._raw6(), m, self.sc.n, int(db_row0), k, _dptr(idx), _dptr(var), _dptr(dist)))
+        self._leave()
+        return var, dist
 
     take_warnings = Matcher.take_warnings
     flagged_count = Matcher.flagged_count
