@@ -24,7 +24,7 @@ typedef struct pr_clouds pr_clouds;
 enum { PR_OK = 0, PR_EINVAL = -1, PR_ENOMEM = -2, PR_EHIP = -3, PR_EIO = -4, PR_ENAN = -5 };
 enum { PR_TYPE_SC = 0, PR_TYPE_M2DP = 1, PR_TYPE_DELIGHT = 2, PR_TYPE_GIST = 3, PR_TYPE_BOW = 4 };   /* run_test.m:26-36 `type` */
 enum { PR_ROLE_QUERY = 0, PR_ROLE_DB = 1 };         /* hist1 / hist2 of run_test.m:1 */
-enum { PR_F64 = 0, PR_F32 = 1 };
+enum { PR_F64 = 0, PR_F32 = 1, PR_U8 = 2 };   /* PR_U8: 8-bit images (pr_gist_generate*) */
 enum { PR_HOST = 0, PR_DEVICE = 1 };
 /* arithmetic of the SC and M2DP matchers (processSC.m:22-33, processM2DP.m:12-22 on the GPU): split-f16 (fp32 operands carried
  * as f16 hi + lo, three f16 MFMAs per product, fp32 accumulate; default, 2-3x faster, same 1e-7 error as fp32), plain fp32 MFMA, or
@@ -125,6 +125,20 @@ int pr_m2dp_svd_rows(pr_ctx* ctx, int32_t* rows, int32_t cap, int32_t* count);
 /* Replaces DELIGHT::getSignature looped as in DELIGHT/test_delight.cpp:41-56 (DELIGHT/DELIGHT.h:11-18, DELIGHT.cpp:8-24;
  * PCA alignment inside).  out[16N][256]: 16 intensity histograms per cloud. */
 int pr_delight_generate(pr_ctx* ctx, const double* xyz, const float* inten, const int64_t* offs, int32_t N, double* out);
+
+/* Replaces GIST::extract looped as in GIST/src/test_gist.cpp:57-96 (gist.cpp:54-94 -> libgist.cpp:914-951, bw_gist_scaletab, grayscale):
+ * img [N][256][256] row-major, dtype PR_U8 (mono8, as cv_bridge gives it) or PR_F32.  Images must be 256 x 256: GIST::extract resizes
+ * (INTER_LANCZOS4) and centre-crops other sizes first (gist.cpp:62-75), which the caller does; otherwise PR_EINVAL.
+ * nblocks 1..16, n_scale 1..8, orients[n_scale] 1..32 each; the reference's defaults are 4, 4, {8, 8, 8, 8} (test_gist.cpp:57).
+ * out [N][pr_gist_signature_size()] float: per filter (scale-major), the nblocks x nblocks block means, res[k * nblocks + l] with k the
+ * x (column) block (libgist.cpp:600-629).  A descriptor with a NaN or Inf makes the host form return PR_ENAN (the reference returns NULL,
+ * libgist.cpp:936-945); the device form (img, out device pointers) leaves such a row as NaN, is stream-ordered without host waits, and after
+ * its first call with a parameter set and batch size allocates nothing (graph-capturable). */
+int pr_gist_signature_size(int32_t nblocks, int32_t n_scale, const int32_t* orients);
+int pr_gist_generate(pr_ctx* ctx, const void* img, int dtype, int32_t N, int32_t height, int32_t width, int32_t nblocks, int32_t n_scale,
+                     const int32_t* orients, float* out);
+int pr_gist_generate_dev(pr_ctx* ctx, const void* img, int dtype, int32_t N, int32_t height, int32_t width, int32_t nblocks,
+                         int32_t n_scale, const int32_t* orients, float* out);
 
 /* Replaces processDELIGHT(hist1, hist2) (match_signatures/processDELIGHT.m:1-38).  h1[16m][256], h2[16n][256];
  * dist: host f32 [m][n] (chi-square, min over the 4 octant permutations; +Inf when no bin is occupied). */

@@ -15,6 +15,7 @@ NAN_EXCLUDE, NAN_FAIL = 0, 1
 WARN_NAN_ROWS, WARN_M2DP_SVD, WARN_F16_FALLBACK, WARN_ORDER_RESOLVED, WARN_ORDER_UNRESOLVED = 1, 2, 4, 8, 16
 ROLE_QUERY, ROLE_DB = 0, 1
 F64, F32 = 0, 1
+U8 = 2              # 8-bit images (pr_gist_generate*)
 HOST, DEVICE = 0, 1
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -82,6 +83,9 @@ SYMBOLS = {
     "pr_m2dp_generate": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _dbl, _vp]),
     "pr_m2dp_svd_rows": (C.c_int, [_vp, _vp, _i32, _vp]),
     "pr_delight_generate": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _vp]),
+    "pr_gist_signature_size": (C.c_int, [_i32, _i32, _vp]),
+    "pr_gist_generate": (C.c_int, [_vp, _vp, C.c_int, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "pr_gist_generate_dev": (C.c_int, [_vp, _vp, C.c_int, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "pr_delight_distance": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _vp]),
     "pr_gist_distance": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _i32, _vp]),
     "pr_bow_distance": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _i32, _vp]),

@@ -2,6 +2,7 @@
 
 Same names, argument meaning and error behaviour as the reference:
   SC / M2DP classes            SC/SC.h:10-23, M2DP/M2DP.h:12-30  (getSignatureSize / getSignature)
+  GIST class, gist_generate    GIST/include/gist.h, gist.cpp:54-94  (getSignatureSize / extract)
   processSC / processM2DP      match_signatures/processSC.m:1, processM2DP.m:1
   run_test                     match_signatures/run_test.m:1  (fusion, mask, top-1; PR/AUC evaluation in eval.py)
 Arrays are numpy on the host; the device-resident path used by bench.py / dist.py is `Matcher`.
@@ -10,12 +11,22 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from typing import NamedTuple
 
 import numpy as np
 
 from . import _lib
 from ._lib import PRError, TYPE_BOW, TYPE_DELIGHT, TYPE_GIST, TYPE_M2DP, TYPE_SC  # noqa: F401
 
+
+class GISTParams(NamedTuple):
+    """cls::GISTParams (GIST/include/gist.h): use_color, width, height, blocks, scale, orients."""
+    use_color: bool = False
+    width: int = 256
+    height: int = 256
+    blocks: int = 4
+    scale: int = 4
+    orients: tuple = (8, 8, 8, 8)
 
 def _ptr(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
@@ -270,6 +281,83 @@ def delight_generate(xyz, inten, offs, ctx: Context | None = None) -> np.ndarray
     return out
 
 
+def gist_signature_size(nblocks: int = 4, orients=(8, 8, 8, 8)) -> int:
+    """nblocks^2 x sum(orients) (GIST::setParams, gist.cpp:40-50, grayscale)."""
+    o = np.ascontiguousarray(orients, np.int32)
+    rc = _lib.load().pr_gist_signature_size(int(nblocks), len(o), _ptr(o))
+    if rc < 0:
+        raise ValueError(f"invalid GIST parameters: nblocks={nblocks}, orients={tuple(orients)}")
+    return rc
+
+
+def _gist_images(images, where: str):
+    if images.ndim == 2:
+        images = images[None]
+    if images.ndim != 3:
+        raise ValueError(f"expected [N, 256, 256] images ({where})")
+    return images
+
+
+def gist_generate(images, nblocks: int = 4, orients=(8, 8, 8, 8), ctx: Context | None = None) -> np.ndarray:
+    """GIST::extract (gist.cpp:54-94) of 256 x 256 grayscale images, uint8 (mono8) or float32, [N, 256, 256] or one [256, 256]
+    -> float32 [N, nblocks^2 sum(orients)].  Other sizes raise PRError (PR_EINVAL): resize and crop them first.
+    A descriptor with a NaN / Inf raises PRError (PR_ENAN), as the reference returns NULL for it."""
+    ctx = ctx or default_context()
+    img = np.asarray(images)
+    dtype = _lib.U8 if img.dtype == np.uint8 else _lib.F32
+    img = _gist_images(np.ascontiguousarray(img, np.uint8 if dtype == _lib.U8 else np.float32), "gist_generate")
+    o = np.ascontiguousarray(orients, np.int32)
+    N, H, W = img.shape
+    out = np.empty((N, gist_signature_size(nblocks, orients)), np.float32)
+    ctx.check(ctx.lib.pr_gist_generate(ctx.h, _ptr(img), dtype, N, H, W, int(nblocks), len(o), _ptr(o), _ptr(out)))
+    return out
+
+
+def gist_generate_torch(images, nblocks: int = 4, orients=(8, 8, 8, 8), ctx: Context | None = None, out=None):
+    """Device form (pr_gist_generate_dev) for images already on the GPU: a torch uint8 / float32 tensor [N, 256, 256] (or [256, 256])
+    -> float32 tensor [N, D] on the same device (or `out`, preallocated).  No host wait, and after the first call with these parameters
+    and a batch at least this size nothing is allocated by the library (graph-capturable with a preallocated `out`).  A row whose
+    descriptor is not finite is left as NaN.
+    ctx given: the kernels run on ctx's stream and the caller orders it with the tensors' producers and consumers (e.g. a context created
+    on the stream the work runs on).  ctx None: one library context per device, on a stream of its own, joined to torch's current stream
+    by stream waits on both sides (no host wait); the tensors are marked as used on that stream for torch's caching allocator."""
+    import torch
+    if images.dtype not in (torch.uint8, torch.float32) or not images.is_cuda:
+        raise ValueError("gist_generate_torch: expected a CUDA tensor of dtype uint8 or float32")
+    img = _gist_images(images.contiguous(), "gist_generate_torch")
+    o = np.ascontiguousarray(orients, np.int32)
+    N, H, W = img.shape
+    D = gist_signature_size(nblocks, orients)
+    if out is None:
+        out = torch.empty((N, D), dtype=torch.float32, device=img.device)
+    elif out.shape != (N, D) or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError(f"gist_generate_torch: out must be a contiguous float32 tensor [{N}, {D}]")
+    dtype = _lib.U8 if img.dtype == torch.uint8 else _lib.F32
+    lib_stream = cur = None
+    if ctx is None:
+        ctx, lib_stream = _torch_default_context(img.device.index or 0)
+        cur = torch.cuda.current_stream(img.device)
+        lib_stream.wait_stream(cur)                # the images (and out) are ready on torch's stream before the library reads / writes them
+    ctx.check(ctx.lib.pr_gist_generate_dev(ctx.h, C.c_void_p(img.data_ptr()), dtype, N, H, W, int(nblocks), len(o), _ptr(o),
+                                           C.c_void_p(out.data_ptr())))
+    if lib_stream is not None:
+        cur.wait_stream(lib_stream)                # torch's later work sees the rows
+        img.record_stream(lib_stream)
+        out.record_stream(lib_stream)
+    return out
+
+
+_torch_ctx = {}      # device -> (Context on its own stream, that stream as a torch.cuda.ExternalStream): one per device, for the process
+
+
+def _torch_default_context(device: int):
+    import torch
+    if device not in _torch_ctx:
+        c = Context(device)
+        _torch_ctx[device] = (c, torch.cuda.ExternalStream(c.stream, device=device))
+    return _torch_ctx[device]
+
+
 class DELIGHT:
     """DELIGHT/DELIGHT.h:11-18."""
 
@@ -315,6 +403,27 @@ class M2DP:
     def getSignatures(self, pts, intensity):
         xyz, it, offs = _csr([(pts, intensity)])
         return m2dp_generate(xyz, it, offs, self.max_rho, self.ctx)
+
+
+class GIST:
+    """cls::GIST (GIST/include/gist.h, gist.cpp:40-94), grayscale.  params: a GISTParams or None for test_gist.cpp:57's
+    DEFAULT_PARAMS{false, 256, 256, 4, 4, {8, 8, 8, 8}}."""
+
+    def __init__(self, params=None, ctx: Context | None = None):
+        self.params = params if params is not None else GISTParams()
+        p = self.params
+        if p.use_color:
+            raise ValueError("GIST: colour GIST is not supported (test_gist uses use_color = false)")
+        if (p.width, p.height) != (256, 256) or p.scale != len(p.orients):
+            raise ValueError("GIST: width = height = 256 and scale = len(orients) are supported")
+        self.ctx = ctx
+
+    def getSignatureSize(self) -> int:
+        return gist_signature_size(self.params.blocks, self.params.orients)
+
+    def extract(self, img) -> np.ndarray:
+        """One 256 x 256 image (uint8 or float32) -> float32 [getSignatureSize()] (the resize / crop of extract is the caller's)."""
+        return gist_generate(np.asarray(img)[None], self.params.blocks, self.params.orients, self.ctx)[0]
 
 
 def _distance(fn_name, div, width, hist1, hist2, ctx):

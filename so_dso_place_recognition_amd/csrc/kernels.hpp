@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+struct pr_ctx;
+
 namespace pr {
 
 // ------------------------------------------------------------------ packed layouts
@@ -236,6 +238,20 @@ void launch_delight_gen(hipStream_t st, const double* xyz, const float* inten, c
                         const double* frames, double* out);
 void launch_delight_pack(hipStream_t st, const void* sig, int dtype, int sigs, float* packed, unsigned* mask);
 void launch_delight_match(hipStream_t st, const float* q, int m, const float* db, const unsigned* dbmask, int n, float* dist);
+// gist_gen.hip — libgist.cpp:914-951 (bw_gist_scaletab) for 256 x 256 images: n images (u8 or f32, [n][256][256]) -> out [n][nf nb^2].
+// circ: [GIST_LD][GIST_LD] whitening circulant (266 x 266 valid), gabor: [nf][256][256], tw: W256^m (m < 256, forward sign);
+// scratch: gist_scratch_floats(chunk >= n, nf, nb) floats.  Stream-ordered, allocates nothing.
+constexpr int GIST_LD = 272;      // row stride of the padded 266 x 266 planes
+constexpr int GIST_PAIRS = 128;   // (image, filter) pairs per Gabor launch: their 256 x 256 c64 intermediates (64 MiB) stay cache-resident
+size_t gist_scratch_floats(int chunk, int nf, int nb);
+void launch_gist(hipStream_t st, const void* img, bool u8, int n, int nb, int nf, const float* circ, const float* gabor,
+                 const float2* tw, float* scratch, float* out);
+void gist_release(void* state);                 // gist.cpp: frees a context's GIST tables and scratch (pr_destroy, streams idle)
+// pr_api.cpp: what gist.cpp needs of a context
+hipStream_t ctx_stream(pr_ctx* ctx);
+int ctx_device(pr_ctx* ctx);
+void ctx_set_error(pr_ctx* ctx, const char* msg);
+void*& ctx_gist(pr_ctx* ctx);
 
 // prestage.hip — utils/pts_preprocess.h:135-232 on the GPU (see the file header); all pointers are device pointers
 int64_t prestage_cells(double range, int polar);          // dense cell-table length per pose

@@ -68,6 +68,7 @@ struct pr_ctx {
   bool timing = false;           // pr_set_kernel_timing: events around the launches of pr_distances_dev
   hipEvent_t ev_t[4] = {nullptr, nullptr, nullptr, nullptr};
   int timing_valid = 0;          // 0: nothing recorded; 1: ev_t[0], ev_t[3] only (one launch); 3: all four (channel 0 | channel 1 split | channel 1 single)
+  void* gist = nullptr;          // GIST filter tables per parameter set and grow-only scratch (gist.cpp)
 };
 
 struct pr_sigset {
@@ -355,6 +356,7 @@ void pr_destroy(pr_ctx* ctx) {
   if (ctx->d_cst) (void)hipFree(ctx->d_cst);
   if (ctx->d_cst_h) (void)hipFree(ctx->d_cst_h);
   if (ctx->d_planes) (void)hipFree(ctx->d_planes);
+  pr::gist_release(ctx->gist);
   delete ctx;
 }
 
@@ -2032,3 +2034,11 @@ int pr_sc_relative_pose(const double* frames_q, const double* frames_db, const i
 }
 
 }  // extern "C"
+
+// what gist.cpp needs of a context (pr_ctx is private to this file)
+namespace pr {
+hipStream_t ctx_stream(pr_ctx* ctx) { return ctx->stream; }
+int ctx_device(pr_ctx* ctx) { return ctx->device; }
+void ctx_set_error(pr_ctx* ctx, const char* msg) { if (ctx) ctx->err = msg; else g_err = msg; }
+void*& ctx_gist(pr_ctx* ctx) { return ctx->gist; }
+}  // namespace pr

@@ -2,8 +2,9 @@
 # The reference's batch driver, generate_signatures/test.bash:4-22 + launch/lidar.launch:13-21, for the MI355X executables:
 # every KITTI / RobotCar sequence x every lidar descriptor (delight, m2dp, sc), each run with the parameters lidar.launch sets
 # (poses_history_file, pts_history_file, <method>_file, incoming_id_file, lidarRange = 45.0) under
-# <results>/<dataset>/<seq>/.  The reference's gist.launch / bow.launch lines (image descriptors) have no counterpart here:
-# SURVEY.md §8 scopes the generators to the lidar path; their matchers are in match_signatures --type gist|bow.
+# <results>/<dataset>/<seq>/.  The reference's gist.launch / bow.launch lines (image descriptors) read a ROS bag and are not run here:
+# bin/test_gist is the GIST generator's drop-in, fed by a list of PGM frames (_images:=) instead of the bag;
+# there is no BoW generator.  Both matchers are in match_signatures --type gist|bow.
 #
 # usage: tools/test.bash [results_dir] [extra test_<method> arguments, e.g. _device:=1 or _gpu_prestage:=0]
 #   results_dir defaults to ./results (the layout of place_recognition/results in the reference)
