@@ -9,6 +9,7 @@
 #include <cstring>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/place_recognition.h"
@@ -128,6 +129,18 @@ struct DevBuf {
   hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
   template <typename T> T* as() { return static_cast<T*>(p); }
 };
+// a signature set of a host-buffer call (pr_sigset_destroy waits for the context's stream)
+struct SigSet {
+  pr_ctx* ctx = nullptr;
+  pr_sigset* s = nullptr;
+  int create(pr_ctx* c, int type, int role, int32_t max_sigs) { ctx = c; return pr_sigset_create(c, type, role, max_sigs, &s); }
+  ~SigSet() { pr_sigset_destroy(ctx, s); }
+};
+
+// doubles per signature of descriptor type t: SC one row, M2DP 4 rows, DELIGHT 16 histograms
+size_t sig_doubles(int t) {
+  return t == PR_TYPE_SC ? PR_SC_SIG_LEN : t == PR_TYPE_M2DP ? (size_t)4 * PR_M2DP_SIG_LEN : (size_t)16 * PR_DELIGHT_SIG_LEN;
+}
 
 int set_device(pr_ctx* ctx) {
   PR_HIP(ctx, hipSetDevice(ctx->device));
@@ -647,15 +660,13 @@ int pr_sigset_pack(pr_ctx* ctx, pr_sigset* s, const void* sig, int dtype, int wh
       (where != PR_HOST && where != PR_DEVICE))
     PR_FAIL(ctx, PR_EINVAL, "pr_sigset_pack: bad arguments (n_sigs=%d, capacity=%d)", n_sigs, s->max_sigs);
   if (int rc = set_device(ctx)) return rc;
-  const size_t rows = (s->type == PR_TYPE_SC) ? (size_t)n_sigs : (s->type == PR_TYPE_M2DP ? (size_t)4 * n_sigs : (size_t)16 * n_sigs);
-  const size_t cols = (s->type == PR_TYPE_SC) ? PR_SC_SIG_LEN : (s->type == PR_TYPE_M2DP ? PR_M2DP_SIG_LEN : PR_DELIGHT_SIG_LEN);
-  const size_t esz = (dtype == PR_F64) ? 8 : 4;
+  const size_t bytes = (size_t)n_sigs * sig_doubles(s->type) * ((dtype == PR_F64) ? 8 : 4);
   DevScope scope_(ctx);
   DevBuf stage;
   const void* dsig = sig;
   if (where == PR_HOST && n_sigs > 0) {
-    PR_HIP(ctx, stage.alloc(rows * cols * esz));
-    PR_HIP(ctx, hipMemcpyAsync(stage.p, sig, rows * cols * esz, hipMemcpyHostToDevice, ctx->stream));
+    PR_HIP(ctx, stage.alloc(bytes));
+    PR_HIP(ctx, hipMemcpyAsync(stage.p, sig, bytes, hipMemcpyHostToDevice, ctx->stream));
     dsig = stage.p;
   }
   // the channel stride must match the matcher's view of THIS count (not the capacity)
@@ -724,14 +735,13 @@ int pr_sigset_append(pr_ctx* ctx, pr_sigset* s, const void* sig, int dtype, int 
   if ((int64_t)s->count + n_new > s->max_sigs) PR_FAIL(ctx, PR_EINVAL, "pr_sigset_append: %d + %d rows exceed the capacity %d", s->count, n_new, s->max_sigs);
   if (n_new == 0) return PR_OK;
   if (int rc = set_device(ctx)) return rc;
-  const size_t rows = s->type == PR_TYPE_SC ? (size_t)n_new : (size_t)4 * n_new, cols = s->type == PR_TYPE_SC ? PR_SC_SIG_LEN : PR_M2DP_SIG_LEN;
-  const size_t esz = dtype == PR_F64 ? 8 : 4;
+  const size_t bytes = (size_t)n_new * sig_doubles(s->type) * (dtype == PR_F64 ? 8 : 4);
   DevScope scope_(ctx);
   DevBuf stage;
   const void* dsig = sig;
   if (where == PR_HOST) {
-    PR_HIP(ctx, stage.alloc(rows * cols * esz));
-    PR_HIP(ctx, hipMemcpyAsync(stage.p, sig, rows * cols * esz, hipMemcpyHostToDevice, ctx->stream));
+    PR_HIP(ctx, stage.alloc(bytes));
+    PR_HIP(ctx, hipMemcpyAsync(stage.p, sig, bytes, hipMemcpyHostToDevice, ctx->stream));
     dsig = stage.p;
   }
   if (s->type == PR_TYPE_SC)       // the row-wise pack kernel: bit for bit the rows a pack of the whole set writes; statistics folded in, not restarted
@@ -879,6 +889,27 @@ int pr_fuse_select_f64_dev(pr_ctx* ctx, const float* d_p, const float* d_i, int3
                            int32_t* idx, float* score, double* score64) {
   if (!score64) return PR_EINVAL;
   return fuse_select_impl(ctx, d_p, d_i, m, n, mom_all, G, q_row0, db_row0, mask_width, p_weight, k, idx, score, score64);
+}
+
+static int fuse_select2_impl(pr_ctx* ctx, const float* d_p, const float* d_i, const float* e_p, const float* e_i, int32_t m, int32_t n,
+                             const double* mom_all, const double* mom2_all, int32_t G, int32_t q_row0, int32_t db_row0,
+                             int32_t mask_width, double p_weight, int32_t k, int32_t* idx, float* score, double* score64) {
+  if (!ctx || !d_p || !d_i || !e_p || !e_i || !mom_all || !mom2_all || !idx || !score || m < 0 || n < 1 || G < 1 || k < 1) return PR_EINVAL;
+  if (int rc = set_device(ctx)) return rc;
+  pr::launch_fuse_select(ctx->stream, d_p, d_i, m, n, mom_all, G, q_row0, db_row0, mask_width, p_weight, k, idx, score, e_p, e_i, mom2_all, ctx->sel_scratch, score64);
+  PR_HIP(ctx, hipGetLastError());
+  return PR_OK;
+}
+int pr_fuse_select2_dev(pr_ctx* ctx, const float* d_p, const float* d_i, const float* e_p, const float* e_i, int32_t m, int32_t n,
+                        const double* mom_all, const double* mom2_all, int32_t G, int32_t q_row0, int32_t db_row0,
+                        int32_t mask_width, double p_weight, int32_t k, int32_t* idx, float* score) {
+  return fuse_select2_impl(ctx, d_p, d_i, e_p, e_i, m, n, mom_all, mom2_all, G, q_row0, db_row0, mask_width, p_weight, k, idx, score, nullptr);
+}
+int pr_fuse_select2_f64_dev(pr_ctx* ctx, const float* d_p, const float* d_i, const float* e_p, const float* e_i, int32_t m, int32_t n,
+                            const double* mom_all, const double* mom2_all, int32_t G, int32_t q_row0, int32_t db_row0,
+                            int32_t mask_width, double p_weight, int32_t k, int32_t* idx, float* score, double* score64) {
+  if (!score64) return PR_EINVAL;
+  return fuse_select2_impl(ctx, d_p, d_i, e_p, e_i, m, n, mom_all, mom2_all, G, q_row0, db_row0, mask_width, p_weight, k, idx, score, score64);
 }
 
 // survivors of the all-pairs selection that the fp64 re-evaluation looks at: k + 8 (fp32-grade passes), k + 56 in the single-product
@@ -1225,309 +1256,290 @@ int pr_delight_align_pairs_dev(pr_ctx* ctx, const void* q, const void* db, int d
 }
 
 // ------------------------------------------------------------------------------------------- host-buffer path
+}  // extern "C"
 
+namespace {
 
-// PR_SC_ARITH_F16, host calls: margin check of the re-evaluated top-k; the flagged queries are matched again in split-f16 against the whole
-// DB (whose raw signatures are still on the device) and their rows of dcand / dsc64 overwritten.  hq_*: HOST query signatures, ddb_*: DEVICE
-// raw DB signatures (f64), either descriptor type may be absent; mom_*: the f16 pass moments [m][2][3]; cand_sc: its candidate scores.
-static int f16_fallback(pr_ctx* ctx, const double* hq_sc, const double* hq_m2, const void* ddb_sc, const void* ddb_m2, int32_t m, int32_t n,
-                        int32_t mask_width, double p_weight, int32_t k, const double* mom_sc, const double* mom_m2, int32_t kin,
-                        const double* cand_sc, int32_t* dcand, double* dsc64) {
-  DevScope scope_(ctx);
-  DevBuf dflags, dcount;
-  if (dflags.alloc((size_t)m * 4) != hipSuccess || dcount.alloc(4) != hipSuccess) PR_FAIL(ctx, PR_ENOMEM, "out of device memory");
-  if (int rc = pr_f16_margin_dev(ctx, mom_sc, mom_m2, m, 1, p_weight, kin, cand_sc, k, dsc64, dflags.as<int32_t>(), dcount.as<int32_t>())) return rc;
+enum { CREATE, UPLOAD, PACK, DISTANCES, MOMENTS };   // the steps of one descriptor type from host rows to row moments
+
+// one descriptor type of a host-buffer call.  db: its raw DB rows on the device - rdb, or those of the call the F16 fallback repairs
+struct Desc {
+  int type = -1;                                 // PR_TYPE_*, -1: absent
+  const double *hq = nullptr, *hdb = nullptr;    // host query / DB rows (hdb = nullptr: db is set already)
+  const void* db = nullptr;
+  SigSet sq, sdb;
+  DevBuf rq, rdb, dp, di, mom;                   // raw f64 rows (the fp64 re-evaluation reads them), [m][n] distances (DELIGHT: dp), [m][2][3] moments
+  int step(pr_ctx* ctx, int s, int32_t m, int32_t n) {   // one step over m query and n DB rows
+    const size_t sig = sig_doubles(type);
+    switch (s) {
+      case CREATE:
+        if (int rc = sq.create(ctx, type, PR_ROLE_QUERY, m)) return rc;
+        return sdb.create(ctx, type, PR_ROLE_DB, n);
+      case UPLOAD:
+        PR_HIP(ctx, rq.alloc((size_t)m * sig * 8));
+        PR_HIP(ctx, hipMemcpyAsync(rq.p, hq, (size_t)m * sig * 8, hipMemcpyHostToDevice, ctx->stream));
+        if (!hdb) return PR_OK;
+        PR_HIP(ctx, rdb.alloc((size_t)n * sig * 8));
+        PR_HIP(ctx, hipMemcpyAsync(rdb.p, hdb, (size_t)n * sig * 8, hipMemcpyHostToDevice, ctx->stream));
+        db = rdb.p;
+        return PR_OK;
+      case PACK:
+        if (int rc = pr_sigset_pack(ctx, sq.s, rq.p, PR_F64, PR_DEVICE, m)) return rc;
+        return pr_sigset_pack(ctx, sdb.s, db, PR_F64, PR_DEVICE, n);
+      case DISTANCES:
+        PR_HIP(ctx, dp.alloc((size_t)m * n * 4));
+        if (type != PR_TYPE_DELIGHT) PR_HIP(ctx, di.alloc((size_t)m * n * 4));
+        return pr_distances_dev(ctx, sq.s, sdb.s, dp.as<float>(), di.as<float>());
+    }
+    PR_HIP(ctx, mom.alloc((size_t)m * 6 * 8));
+    return pr_row_moments_dev(ctx, dp.as<float>(), di.as<float>(), m, n, mom.as<double>());
+  }
+};
+
+// the descriptor types of a call: SC (t[0]), M2DP (t[1]) or both; DELIGHT alone in t[0]
+struct Types {
+  Desc t[2];
+  Desc& add(int type, const double* hq, const double* hdb) {
+    Desc& d = t[type == PR_TYPE_M2DP ? 1 : 0];
+    d.type = type; d.hq = hq; d.hdb = hdb;
+    return d;
+  }
+  int prepare(pr_ctx* ctx, int32_t m, int32_t n, int last) {   // the steps up to `last`, each across the types before the next
+    for (int s = CREATE; s <= last; s++)
+      for (Desc& d : t)
+        if (int rc = d.type < 0 ? PR_OK : d.step(ctx, s, m, n)) return rc;
+    return PR_OK;
+  }
+  double* mom(int i, int32_t i0) { return t[i].type < 0 ? nullptr : t[i].mom.as<double>() + (size_t)i0 * 6; }
+  // f(ctx, q_sc, db_sc, PR_F64, q_m2, db_m2, PR_F64, mom_sc, mom_m2, rest...) for the query rows from i0 on, nullptr for an absent type
+  template <typename F, typename... R> int dev(F f, pr_ctx* ctx, int32_t i0, R... rest) {
+    const void* q[2] = {nullptr, nullptr};
+    for (int i = 0; i < 2; i++)
+      if (t[i].type >= 0) q[i] = t[i].rq.as<double>() + (size_t)i0 * sig_doubles(t[i].type);
+    return f(ctx, q[0], t[0].db, PR_F64, q[1], t[1].db, PR_F64, mom(0, i0), mom(1, i0), rest...);
+  }
+};
+
+// scratch of the top-k core for up to `rows` queries: the selection's [rows][width] survivors (indices, fp32 scores, the same as doubles:
+// the re-evaluation skips candidates that cannot reach the top-k) and the re-evaluated [rows][k] top-k
+struct TopkBufs {
+  DevBuf idx, sc, sw, kidx, ksc;
+  int alloc(pr_ctx* ctx, size_t rows, int width, int k) {
+    PR_HIP(ctx, idx.alloc(rows * width * 4));
+    PR_HIP(ctx, sc.alloc(rows * width * 4));
+    PR_HIP(ctx, sw.alloc(rows * width * 8));
+    PR_HIP(ctx, kidx.alloc(rows * k * 4));
+    PR_HIP(ctx, ksc.alloc(rows * k * 8));
+    return PR_OK;
+  }
+};
+
+struct ArithScope {   // the context's arithmetic switched for a scope, restored on every way out
+  pr_ctx* ctx;
+  int prev;
+  ArithScope(pr_ctx* c, int mode) : ctx(c), prev(c->sc_mode) { c->sc_mode = mode; }
+  ~ArithScope() { ctx->sc_mode = prev; }
+};
+
+template <typename I, typename S> int no_candidate(size_t count, I* idx, S* score) {   // every entry "no candidate"
+  for (size_t i = 0; i < count; i++) { idx[i] = -1; score[i] = NAN; }
+  return PR_OK;
+}
+
+// the top-k to the host: the scores straight into the caller's buffer when it has the device's precision D, else through a vector converted
+// on the host (re-evaluated f64 scores to pr_match_topk's f32, DELIGHT's f32 selection to the _f64 form's)
+template <typename D, typename H> int download_topk(pr_ctx* ctx, const int32_t* didx, const D* dscore, size_t count, int32_t* idx, H* score) {
+  constexpr bool direct = std::is_same<D, H>::value;
+  std::vector<D> tmp(direct ? 0 : count);
+  hipError_t e = hipMemcpyAsync(idx, didx, count * 4, hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(direct ? (void*)score : (void*)tmp.data(), dscore, count * sizeof(D), hipMemcpyDeviceToHost, ctx->stream);
+  if (e != hipSuccess) {                                         // (a queued copy may target tmp)
+    (void)hipStreamSynchronize(ctx->stream);
+    PR_FAIL(ctx, PR_EHIP, "top-k download failed: %s", hipGetErrorString(e));
+  }
+  if (int rc = pr_sync(ctx)) return rc;
+  for (size_t i = 0; i < tmp.size(); i++) score[i] = (H)tmp[i];
+  return PR_OK;
+}
+
+// one fp32 distance matrix (DELIGHT, GIST, BoW; run_test.m:26-36): the selection's top-k as it stands - no moments, no fusion, nothing to
+// re-evaluate (p_weight does not enter without a second matrix)
+template <typename H>
+int plain_topk(pr_ctx* ctx, const float* dist, int32_t m, int32_t n, int32_t mask_width, double p_weight, int32_t k, int32_t* idx, H* score) {
+  DevBuf didx, dsc;
+  PR_HIP(ctx, didx.alloc((size_t)m * k * 4));
+  PR_HIP(ctx, dsc.alloc((size_t)m * k * 4));
+  if (int rc = pr_fuse_select_dev(ctx, dist, nullptr, m, n, nullptr, 1, 0, 0, mask_width, p_weight, k, didx.as<int32_t>(), dsc.as<float>())) return rc;
+  return download_topk(ctx, didx.as<int32_t>(), dsc.as<float>(), (size_t)m * k, idx, score);
+}
+
+// select -> widen -> rerank -> order-resolve over the query rows [i0, i0 + len) of T's matrices (q_row0: the first one's row number, which
+// only the mask reads), as wide as the context's arithmetic wants; the top-k goes to b.kidx / b.ksc.  Queries whose re-evaluated order hangs
+// on the pass's sigmas get their row statistics in fp64 - in PR_SC_ARITH_F16 the margin check takes the flags instead (f16_fallback).
+int topk_core(pr_ctx* ctx, Types& T, int32_t i0, int32_t len, int32_t n, int32_t q_row0, int32_t mask_width, double p_weight, int32_t k,
+              TopkBufs& b) {
+  const int kin = rerank_width(k, ctx->sc_mode);
+  const size_t o = (size_t)i0 * n;
+  Desc &sc = T.t[0], &m2 = T.t[1], &one = sc.type >= 0 ? sc : m2;
+  int rc = sc.type >= 0 && m2.type >= 0
+      ? pr_fuse_select2_dev(ctx, sc.dp.as<float>() + o, sc.di.as<float>() + o, m2.dp.as<float>() + o, m2.di.as<float>() + o, len, n, T.mom(0, i0),
+                            T.mom(1, i0), 1, q_row0, 0, mask_width, p_weight, kin, b.idx.as<int32_t>(), b.sc.as<float>())
+      : pr_fuse_select_dev(ctx, one.dp.as<float>() + o, one.di.as<float>() + o, len, n, one.mom.as<double>() + (size_t)i0 * 6, 1, q_row0, 0,
+                           mask_width, p_weight, kin, b.idx.as<int32_t>(), b.sc.as<float>());
+  if (rc) return rc;
+  if ((rc = pr_widen_scores_dev(ctx, b.sc.as<float>(), (int64_t)len * kin, b.sw.as<double>()))) return rc;
+  if ((rc = T.dev(pr_rerank_dev, ctx, i0, len, n, 1, q_row0, 0, mask_width, p_weight, kin, b.idx.as<int32_t>(), b.sw.as<double>(), k,
+                  b.kidx.as<int32_t>(), b.ksc.as<double>())))
+    return rc;
+  if (ctx->sc_mode == PR_SC_ARITH_F16) return PR_OK;
+  return T.dev(pr_order_resolve_dev, ctx, i0, len, n, q_row0, mask_width, p_weight, k, b.kidx.as<int32_t>(), b.ksc.as<double>(), nullptr);
+}
+
+// PR_SC_ARITH_F16: margin check of the re-evaluated top-k in `top`; the flagged queries are matched again in split-f16 against the whole DB
+// (whose raw rows T still holds on the device) and their rows of the top-k overwritten.
+int f16_fallback(pr_ctx* ctx, Types& T, int32_t m, int32_t n, int32_t mask_width, double p_weight, int32_t k, TopkBufs& top) {
+  // (the host ends of the async copies come first: on an error return the DevBufs' destructors idle the streams before these go)
   int32_t cnt = 0;
+  std::vector<int32_t> fl(m), F;                                 // the flags, the flagged rows (ascending)
+  std::vector<double> rows[2];
+  DevBuf dflags, dcount;
+  PR_HIP(ctx, dflags.alloc((size_t)m * 4));
+  PR_HIP(ctx, dcount.alloc(4));
+  if (int rc = pr_f16_margin_dev(ctx, T.mom(0, 0), T.mom(1, 0), m, 1, p_weight, rerank_width(k, ctx->sc_mode), top.sw.as<double>(), k,
+                                 top.ksc.as<double>(), dflags.as<int32_t>(), dcount.as<int32_t>()))
+    return rc;
   PR_HIP(ctx, hipMemcpyAsync(&cnt, dcount.p, 4, hipMemcpyDeviceToHost, ctx->stream));
   PR_HIP(ctx, hipStreamSynchronize(ctx->stream));
   if (cnt == 0) return PR_OK;
-  std::vector<int32_t> fl(m), F;
-  PR_HIP(ctx, hipMemcpy(fl.data(), dflags.p, (size_t)m * 4, hipMemcpyDeviceToHost));
+  PR_HIP(ctx, hipMemcpyAsync(fl.data(), dflags.p, (size_t)m * 4, hipMemcpyDeviceToHost, ctx->stream));
+  PR_HIP(ctx, hipStreamSynchronize(ctx->stream));
   for (int32_t q = 0; q < m; q++) if (fl[q]) F.push_back(q);
   const int32_t mf = (int32_t)F.size();
   ctx->warnings |= PR_WARN_F16_FALLBACK;
-  const int kin2 = rerank_width(k, PR_SC_ARITH_F16X2);
-  pr_sigset* ss[4] = {nullptr, nullptr, nullptr, nullptr};   // SC query, SC db, M2DP query, M2DP db
-  DevBuf rq[2], d[4], mo[2], didx, dsc, dsw;
-  int rc = PR_OK;
-  ctx->sc_mode = PR_SC_ARITH_F16X2;
-  do {
-    const size_t mn = (size_t)mf * n;
-    for (int t = 0; t < 2 && rc == PR_OK; t++) {                // t = 0: SC, 1: M2DP
-      const double* hq = t ? hq_m2 : hq_sc;
-      const void* ddb = t ? ddb_m2 : ddb_sc;
-      if (!hq) continue;
-      const size_t rowlen = t ? 4 * 384 : 2400;
-      std::vector<double> g((size_t)mf * rowlen);
-      for (int32_t i = 0; i < mf; i++) memcpy(g.data() + (size_t)i * rowlen, hq + (size_t)F[i] * rowlen, rowlen * 8);
-      if (rq[t].alloc(g.size() * 8) != hipSuccess || d[2 * t].alloc(mn * 4) != hipSuccess || d[2 * t + 1].alloc(mn * 4) != hipSuccess ||
-          mo[t].alloc((size_t)mf * 6 * 8) != hipSuccess) { ctx->err = "out of device memory (f16 fallback)"; rc = PR_ENOMEM; break; }
-      if (hipMemcpy(rq[t].p, g.data(), g.size() * 8, hipMemcpyHostToDevice) != hipSuccess) { ctx->err = "H2D copy failed"; rc = PR_EHIP; break; }
-      if ((rc = pr_sigset_create(ctx, t ? PR_TYPE_M2DP : PR_TYPE_SC, PR_ROLE_QUERY, mf, &ss[2 * t])) ||
-          (rc = pr_sigset_create(ctx, t ? PR_TYPE_M2DP : PR_TYPE_SC, PR_ROLE_DB, n, &ss[2 * t + 1])) ||
-          (rc = pr_sigset_pack(ctx, ss[2 * t], rq[t].p, PR_F64, PR_DEVICE, mf)) || (rc = pr_sigset_pack(ctx, ss[2 * t + 1], ddb, PR_F64, PR_DEVICE, n)) ||
-          (rc = pr_distances_dev(ctx, ss[2 * t], ss[2 * t + 1], d[2 * t].as<float>(), d[2 * t + 1].as<float>())) ||
-          (rc = pr_row_moments_dev(ctx, d[2 * t].as<float>(), d[2 * t + 1].as<float>(), mf, n, mo[t].as<double>()))) break;
+  ArithScope split_(ctx, PR_SC_ARITH_F16X2);
+  Types R;                                                       // the flagged rows against T's DB rows, scored type by type
+  for (int i = 0; i < 2; i++) {
+    if (T.t[i].type < 0) continue;
+    const size_t sig = sig_doubles(T.t[i].type);
+    rows[i].resize((size_t)mf * sig);
+    for (int32_t r = 0; r < mf; r++) memcpy(rows[i].data() + (size_t)r * sig, T.t[i].hq + (size_t)F[r] * sig, sig * 8);
+    Desc& d = R.add(T.t[i].type, rows[i].data(), nullptr);
+    d.db = T.t[i].db;
+    for (int s = CREATE; s <= MOMENTS; s++)
+      if (int rc = d.step(ctx, s, mf, n)) return rc;
+  }
+  // the flagged queries in RUNS: a query's own row number only enters through the mask (run_test.m:47-53), so without a mask the whole list
+  // is one batch, and with one every maximal run of consecutive row numbers is (a vehicle standing still flags its frames in a row) - one
+  // selection, one re-evaluation and one order resolution per run instead of per query (round 6; until then one query at a time, each
+  // with its own host synchronisation in pr_order_resolve_dev)
+  std::vector<int32_t> run_end;                                  // run r = list positions [run_end[r - 1], run_end[r])
+  for (int32_t i = 1; i <= mf; i++)
+    if (i == mf || (mask_width > 0 && F[i] != F[i - 1] + 1)) run_end.push_back(i);
+  int32_t longest = 0;
+  for (size_t r = 0, a0 = 0; r < run_end.size(); a0 = run_end[r++]) longest = std::max<int32_t>(longest, run_end[r] - (int32_t)a0);
+  TopkBufs b;                                                    // (a run's top-k: the list is ascending, not contiguous, without a mask)
+  if (int rc = b.alloc(ctx, longest, rerank_width(k, ctx->sc_mode), k)) return rc;
+  for (size_t r = 0, a0 = 0; r < run_end.size(); a0 = run_end[r++]) {
+    const int32_t i0 = (int32_t)a0, len = run_end[r] - i0;
+    if (int rc = topk_core(ctx, R, i0, len, n, mask_width > 0 ? F[i0] : 0, mask_width, p_weight, k, b)) return rc;   // (row numbers: the mask's)
+    for (int32_t i = 0; i < len;) {                              // -> the flagged queries' rows, one copy per stretch of consecutive rows
+      int32_t j = i + 1;
+      while (j < len && F[i0 + j] == F[i0 + j - 1] + 1) j++;
+      const size_t to = (size_t)F[i0 + i] * k, from = (size_t)i * k, nk = (size_t)(j - i) * k;
+      PR_HIP(ctx, hipMemcpyAsync(top.kidx.as<int32_t>() + to, b.kidx.as<int32_t>() + from, nk * 4, hipMemcpyDeviceToDevice, ctx->stream));
+      PR_HIP(ctx, hipMemcpyAsync(top.ksc.as<double>() + to, b.ksc.as<double>() + from, nk * 8, hipMemcpyDeviceToDevice, ctx->stream));
+      i = j;
     }
-    if (rc) break;
-    // the flagged queries in RUNS: a query's own row number only enters through the mask (run_test.m:47-53), so without a mask the whole list
-    // is one batch, and with one every maximal run of consecutive row numbers is (a vehicle standing still flags its frames in a row) - one
-    // selection, one re-evaluation and one order resolution per run instead of per query (round 6; until then one query at a time, each
-    // with its own host synchronisation in pr_order_resolve_dev)
-    std::vector<int32_t> run_end;                                // run r = list positions [run_end[r - 1], run_end[r])
-    for (int32_t i = 1; i <= mf; i++)
-      if (i == mf || (mask_width > 0 && F[i] != F[i - 1] + 1)) run_end.push_back(i);
-    int32_t longest = 0;
-    for (size_t r = 0, a0 = 0; r < run_end.size(); a0 = run_end[r++]) longest = std::max<int32_t>(longest, run_end[r] - (int32_t)a0);
-    DevBuf oidx, osc;                                            // a run's results [len][k] (the list is ascending, not contiguous, without a mask)
-    if (didx.alloc((size_t)longest * kin2 * 4) != hipSuccess || dsc.alloc((size_t)longest * kin2 * 4) != hipSuccess ||
-        dsw.alloc((size_t)longest * kin2 * 8) != hipSuccess || oidx.alloc((size_t)longest * k * 4) != hipSuccess ||
-        osc.alloc((size_t)longest * k * 8) != hipSuccess) { ctx->err = "out of device memory"; rc = PR_ENOMEM; break; }
-    const bool both = hq_sc && hq_m2;
-    for (size_t r = 0, a0 = 0; r < run_end.size() && rc == PR_OK; a0 = run_end[r++]) {
-      const int32_t i0 = (int32_t)a0, len = run_end[r] - i0;
-      const size_t o = (size_t)i0 * n;
-      const int32_t q0 = mask_width > 0 ? F[i0] : 0;             // (without a mask the row numbers are not read)
-      if (both)
-        rc = pr_fuse_select2_dev(ctx, d[0].as<float>() + o, d[1].as<float>() + o, d[2].as<float>() + o, d[3].as<float>() + o, len, n,
-                                 mo[0].as<double>() + (size_t)i0 * 6, mo[1].as<double>() + (size_t)i0 * 6, 1, q0, 0, mask_width, p_weight, kin2,
-                                 didx.as<int32_t>(), dsc.as<float>());
-      else {
-        const int t = hq_sc ? 0 : 1;
-        rc = pr_fuse_select_dev(ctx, d[2 * t].as<float>() + o, d[2 * t + 1].as<float>() + o, len, n, mo[t].as<double>() + (size_t)i0 * 6, 1, q0, 0,
-                                mask_width, p_weight, kin2, didx.as<int32_t>(), dsc.as<float>());
-      }
-      if (rc || (rc = pr_widen_scores_dev(ctx, dsc.as<float>(), (int64_t)len * kin2, dsw.as<double>()))) break;
-      rc = pr_rerank_dev(ctx, hq_sc ? rq[0].as<double>() + (size_t)i0 * 2400 : nullptr, hq_sc ? ddb_sc : nullptr, PR_F64,
-                         hq_m2 ? rq[1].as<double>() + (size_t)i0 * 4 * 384 : nullptr, hq_m2 ? ddb_m2 : nullptr, PR_F64,
-                         hq_sc ? mo[0].as<double>() + (size_t)i0 * 6 : nullptr, hq_m2 ? mo[1].as<double>() + (size_t)i0 * 6 : nullptr, len, n, 1, q0, 0,
-                         mask_width, p_weight, kin2, didx.as<int32_t>(), dsw.as<double>(), k, oidx.as<int32_t>(), osc.as<double>());
-      if (rc == PR_OK)                                            // (the split pass's own order check: exact row statistics if it fails)
-        rc = pr_order_resolve_dev(ctx, hq_sc ? rq[0].as<double>() + (size_t)i0 * 2400 : nullptr, hq_sc ? ddb_sc : nullptr, PR_F64,
-                                  hq_m2 ? rq[1].as<double>() + (size_t)i0 * 4 * 384 : nullptr, hq_m2 ? ddb_m2 : nullptr, PR_F64,
-                                  hq_sc ? mo[0].as<double>() + (size_t)i0 * 6 : nullptr, hq_m2 ? mo[1].as<double>() + (size_t)i0 * 6 : nullptr, len, n, q0,
-                                  mask_width, p_weight, k, oidx.as<int32_t>(), osc.as<double>(), nullptr);
-      for (int32_t i = 0; i < len && rc == PR_OK; ) {            // results -> the flagged queries' rows of dcand / dsc64, one copy per stretch of consecutive rows
-        int32_t j = i + 1;
-        while (j < len && F[i0 + j] == F[i0 + j - 1] + 1) j++;
-        if (hipMemcpyAsync(dcand + (size_t)F[i0 + i] * k, oidx.as<int32_t>() + (size_t)i * k, (size_t)(j - i) * k * 4, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess ||
-            hipMemcpyAsync(dsc64 + (size_t)F[i0 + i] * k, osc.as<double>() + (size_t)i * k, (size_t)(j - i) * k * 8, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess) {
-          ctx->err = "f16 fallback: device copy failed"; rc = PR_EHIP;
-        }
-        i = j;
-      }
-    }
-    if (rc == PR_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) { ctx->err = "f16 fallback failed"; rc = PR_EHIP; }
-  } while (0);
-  if (rc != PR_OK) (void)hipStreamSynchronize(ctx->stream);
-  for (auto* q : ss) pr_sigset_destroy(ctx, q);
-  ctx->sc_mode = PR_SC_ARITH_F16;
-  return rc;
+  }
+  PR_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return PR_OK;
 }
 
-// score32 / score64: exactly one is non-null
-static int distance_host(pr_ctx* ctx, int type, const double* h1, int32_t m, const double* h2, int32_t n,
-                         float* out_p, float* out_i, int32_t mask_width, double p_weight, int32_t k, int32_t* idx,
-                         float* score32, double* score64, bool want_topk) {
+// pr_match_topk* (type: PR_TYPE_SC | PR_TYPE_M2DP | PR_TYPE_DELIGHT, rows a1 / a2) and pr_match_topk_fused* (type -1: SC a1 / a2, M2DP
+// b1 / b2).  SC, M2DP and the fused pair: every type's steps up to the row moments, the core over all m rows and, in PR_SC_ARITH_F16, the
+// margin check with the split-f16 fallback; DELIGHT: one plain matrix.
+template <typename H>
+int topk_host(pr_ctx* ctx, const char* who, int type, const double* a1, const double* b1, int32_t m, const double* a2, const double* b2,
+              int32_t n, int32_t mask_width, double p_weight, int32_t k, int32_t* idx, H* score) {
   if (!ctx) return PR_EINVAL;
-  if (m < 0 || n < 0 || (m > 0 && !h1) || (n > 0 && !h2)) PR_FAIL(ctx, PR_EINVAL, "bad signature buffers (m=%d, n=%d)", m, n);
-  const bool plain = (type == PR_TYPE_DELIGHT);
-  if (want_topk && (k < 1 || (!plain && k > 120) || !idx || (!score32 && !score64)))   // (k + 8 candidates of the re-evaluation <= 128; DELIGHT has none)
-    PR_FAIL(ctx, PR_EINVAL, "pr_match_topk needs 1 <= k <= 120 (SC, M2DP) and output buffers");
-  if (want_topk && n == 0) {   // nothing to match against: every query row is "no candidate"
-    for (size_t i = 0; i < (size_t)m * k; i++) { idx[i] = -1; if (score32) score32[i] = NAN; else score64[i] = NAN; }
-    return PR_OK;
+  const bool fused = type < 0, plain = type == PR_TYPE_DELIGHT;
+  if (fused && (m < 0 || n < 2 || k < 1 || k > 120 || !idx || !score || (m > 0 && (!a1 || !b1)) || !a2 || !b2))
+    PR_FAIL(ctx, PR_EINVAL, "%s: bad arguments (m=%d, n=%d, k=%d)", who, m, n, k);
+  if (!fused) {
+    if (type != PR_TYPE_SC && type != PR_TYPE_M2DP && !plain) PR_FAIL(ctx, PR_EINVAL, "%s: unknown type %d", who, type);
+    if (!score) PR_FAIL(ctx, PR_EINVAL, "%s: score is NULL", who);
+    if (m < 0 || n < 0 || (m > 0 && !a1) || (n > 0 && !a2)) PR_FAIL(ctx, PR_EINVAL, "%s: bad signature buffers (m=%d, n=%d)", who, m, n);
+    if (k < 1 || (!plain && k > 120) || !idx)                   // (k + 8 candidates of the re-evaluation <= 128; DELIGHT has none)
+      PR_FAIL(ctx, PR_EINVAL, "%s needs 1 <= k <= 120 (SC, M2DP) and output buffers", who);
+    if (n == 0) return no_candidate((size_t)m * k, idx, score);
+    if (!plain && n < 2) PR_FAIL(ctx, PR_EINVAL, "%s needs n >= 2 (N-1 standard deviation)", who);
   }
-  if (want_topk && n < 2 && !plain)
-    PR_FAIL(ctx, PR_EINVAL, "pr_match_topk needs n >= 2 (N-1 standard deviation)");
+  if (m == 0) return PR_OK;
+  if (int rc = set_device(ctx)) return rc;
+  DevScope scope_(ctx);
+  Types T;
+  T.add(fused ? PR_TYPE_SC : type, a1, a2);
+  if (fused) T.add(PR_TYPE_M2DP, b1, b2);
+  if (int rc = T.prepare(ctx, m, n, plain ? DISTANCES : MOMENTS)) return rc;
+  if (plain) return plain_topk(ctx, T.t[0].dp.as<float>(), m, n, mask_width, p_weight, k, idx, score);
+  TopkBufs top;
+  if (int rc = top.alloc(ctx, m, rerank_width(k, ctx->sc_mode), k)) return rc;
+  if (int rc = topk_core(ctx, T, 0, m, n, 0, mask_width, p_weight, k, top)) return rc;
+  if (ctx->sc_mode == PR_SC_ARITH_F16)
+    if (int rc = f16_fallback(ctx, T, m, n, mask_width, p_weight, k, top)) return rc;
+  return download_topk(ctx, top.kidx.as<int32_t>(), top.ksc.as<double>(), (size_t)m * k, idx, score);
+}
+
+// pr_sc / m2dp / delight_distance: the distance matrices of one descriptor type
+int distance_host(pr_ctx* ctx, const char* who, int type, const double* h1, int32_t m, const double* h2, int32_t n, float* out_p, float* out_i) {
+  if (!ctx) return PR_EINVAL;
+  if (m < 0 || n < 0 || (m > 0 && !h1) || (n > 0 && !h2)) PR_FAIL(ctx, PR_EINVAL, "%s: bad signature buffers (m=%d, n=%d)", who, m, n);
   if (m == 0 || n == 0) return PR_OK;
   if (int rc = set_device(ctx)) return rc;
-  const size_t rows_per = (type == PR_TYPE_SC) ? 1 : (type == PR_TYPE_M2DP ? 4 : 16);
-  const size_t cols = (type == PR_TYPE_SC) ? PR_SC_SIG_LEN : (type == PR_TYPE_M2DP ? PR_M2DP_SIG_LEN : PR_DELIGHT_SIG_LEN);
-  pr_sigset *q = nullptr, *d = nullptr;
-  int rc = pr_sigset_create(ctx, type, PR_ROLE_QUERY, m, &q);
-  if (rc == PR_OK) rc = pr_sigset_create(ctx, type, PR_ROLE_DB, n, &d);
   DevScope scope_(ctx);
-  DevBuf raw1, raw2, dp, di, mom, didx, dsc, dsc64, dcand;
-  do {
-    if (rc) break;
-    // the raw signatures stay on the device for the fp64 re-evaluation of the selection's survivors
-    const size_t b1 = (size_t)m * rows_per * cols * 8, b2 = (size_t)n * rows_per * cols * 8;
-    if (raw1.alloc(b1) != hipSuccess || raw2.alloc(b2) != hipSuccess) { ctx->err = "out of device memory for the signatures"; rc = PR_ENOMEM; break; }
-    if (hipMemcpyAsync(raw1.p, h1, b1, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
-        hipMemcpyAsync(raw2.p, h2, b2, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) { ctx->err = "H2D copy failed"; rc = PR_EHIP; break; }
-    if ((rc = pr_sigset_pack(ctx, q, raw1.p, PR_F64, PR_DEVICE, m))) break;
-    if ((rc = pr_sigset_pack(ctx, d, raw2.p, PR_F64, PR_DEVICE, n))) break;
-    const size_t mn = (size_t)m * n;
-    if (dp.alloc(mn * 4) != hipSuccess || (!plain && di.alloc(mn * 4) != hipSuccess)) { ctx->err = "out of device memory for the m x n distance matrices"; rc = PR_ENOMEM; break; }
-    if ((rc = pr_distances_dev(ctx, q, d, dp.as<float>(), plain ? nullptr : di.as<float>()))) break;
-    if (want_topk) {
-      const int kin = plain ? k : rerank_width(k, ctx->sc_mode);
-      if (mom.alloc((size_t)m * 6 * 8) != hipSuccess || didx.alloc((size_t)m * kin * 4) != hipSuccess ||
-          dsc.alloc((size_t)m * kin * 4) != hipSuccess || dsc64.alloc((size_t)m * k * 8) != hipSuccess ||
-          dcand.alloc((size_t)m * k * 4) != hipSuccess) { ctx->err = "out of device memory"; rc = PR_ENOMEM; break; }
-      if (!plain && (rc = pr_row_moments_dev(ctx, dp.as<float>(), di.as<float>(), m, n, mom.as<double>()))) break;
-      if ((rc = pr_fuse_select_dev(ctx, dp.as<float>(), plain ? nullptr : di.as<float>(), m, n, mom.as<double>(), 1, 0, 0, mask_width,
-                                   p_weight, kin, didx.as<int32_t>(), dsc.as<float>()))) break;
-      std::vector<float> tmp;
-      if (plain) {   // DELIGHT: a single fp32 chi-square matrix, no fusion (run_test.m:26-36) - nothing to re-evaluate
-        if (score64) tmp.resize((size_t)m * k);
-        if (hipMemcpyAsync(idx, didx.p, (size_t)m * k * 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-            hipMemcpyAsync(score32 ? score32 : tmp.data(), dsc.p, (size_t)m * k * 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) { ctx->err = "D2H copy failed"; rc = PR_EHIP; break; }
-        if ((rc = pr_sync(ctx))) break;
-        if (score64) for (size_t i = 0; i < tmp.size(); i++) score64[i] = (double)tmp[i];
-        break;
-      }
-      const bool sc = type == PR_TYPE_SC;
-      DevBuf dsw;   // the fp32-pass scores as doubles: the re-evaluation skips candidates that cannot reach the top-k
-      if (dsw.alloc((size_t)m * kin * 8) != hipSuccess) { ctx->err = "out of device memory"; rc = PR_ENOMEM; break; }
-      if ((rc = pr_widen_scores_dev(ctx, dsc.as<float>(), (int64_t)m * kin, dsw.as<double>()))) break;
-      if ((rc = pr_rerank_dev(ctx, sc ? raw1.p : nullptr, sc ? raw2.p : nullptr, PR_F64, sc ? nullptr : raw1.p, sc ? nullptr : raw2.p, PR_F64,
-                              sc ? mom.as<double>() : nullptr, sc ? nullptr : mom.as<double>(), m, n, 1, 0, 0, mask_width, p_weight, kin,
-                              didx.as<int32_t>(), dsw.as<double>(), k, dcand.as<int32_t>(), dsc64.as<double>()))) break;
-      std::vector<double> t64;
-      if (score32) t64.resize((size_t)m * k);
-      // queries whose re-evaluated order hangs on the fp32 pass's sigmas get their row statistics in fp64 (PR_SC_ARITH_F16: the margin
-      // check below takes the flags instead and sends them to the split pass, which resolves its own)
-      if (ctx->sc_mode != PR_SC_ARITH_F16 &&
-          (rc = pr_order_resolve_dev(ctx, sc ? raw1.p : nullptr, sc ? raw2.p : nullptr, PR_F64, sc ? nullptr : raw1.p, sc ? nullptr : raw2.p, PR_F64,
-                                     sc ? mom.as<double>() : nullptr, sc ? nullptr : mom.as<double>(), m, n, 0, mask_width, p_weight, k,
-                                     dcand.as<int32_t>(), dsc64.as<double>(), nullptr))) break;
-      if (ctx->sc_mode == PR_SC_ARITH_F16 &&
-          (rc = f16_fallback(ctx, sc ? h1 : nullptr, sc ? nullptr : h1, sc ? raw2.p : nullptr, sc ? nullptr : raw2.p, m, n, mask_width, p_weight, k,
-                             sc ? mom.as<double>() : nullptr, sc ? nullptr : mom.as<double>(), kin, dsw.as<double>(), dcand.as<int32_t>(),
-                             dsc64.as<double>()))) break;
-      if (hipMemcpyAsync(idx, dcand.p, (size_t)m * k * 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-          hipMemcpyAsync(score64 ? score64 : t64.data(), dsc64.p, (size_t)m * k * 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) { ctx->err = "D2H copy failed"; rc = PR_EHIP; break; }
-      if ((rc = pr_sync(ctx))) break;
-      if (score32) for (size_t i = 0; i < t64.size(); i++) score32[i] = (float)t64[i];
-      break;
-    }
-    if (out_p && hipMemcpyAsync(out_p, dp.p, mn * 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) { ctx->err = "D2H copy failed"; rc = PR_EHIP; break; }
-    if (out_i && !plain && hipMemcpyAsync(out_i, di.p, mn * 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) { ctx->err = "D2H copy failed"; rc = PR_EHIP; break; }
-    rc = pr_sync(ctx);
-  } while (0);
-  if (rc != PR_OK) (void)hipStreamSynchronize(ctx->stream);
-  pr_sigset_destroy(ctx, q);
-  pr_sigset_destroy(ctx, d);
-  return rc;
+  Types T;
+  Desc& d = T.add(type, h1, h2);
+  if (int rc = T.prepare(ctx, m, n, DISTANCES)) return rc;
+  if (out_p) PR_HIP(ctx, hipMemcpyAsync(out_p, d.dp.p, (size_t)m * n * 4, hipMemcpyDeviceToHost, ctx->stream));
+  if (out_i && d.di.p) PR_HIP(ctx, hipMemcpyAsync(out_i, d.di.p, (size_t)m * n * 4, hipMemcpyDeviceToHost, ctx->stream));
+  return pr_sync(ctx);
 }
 
+}  // namespace
+
+extern "C" {
+
 int pr_sc_distance(pr_ctx* ctx, const double* h1, int32_t m, const double* h2, int32_t n, float* d_struct, float* d_int) {
-  return distance_host(ctx, PR_TYPE_SC, h1, m, h2, n, d_struct, d_int, 0, 0, 0, nullptr, nullptr, nullptr, false);
+  return distance_host(ctx, "pr_sc_distance", PR_TYPE_SC, h1, m, h2, n, d_struct, d_int);
 }
 
 int pr_m2dp_distance(pr_ctx* ctx, const double* h1, int32_t m, const double* h2, int32_t n, float* d_cnt, float* d_int) {
-  return distance_host(ctx, PR_TYPE_M2DP, h1, m, h2, n, d_cnt, d_int, 0, 0, 0, nullptr, nullptr, nullptr, false);
+  return distance_host(ctx, "pr_m2dp_distance", PR_TYPE_M2DP, h1, m, h2, n, d_cnt, d_int);
 }
 
 int pr_delight_distance(pr_ctx* ctx, const double* h1, int32_t m, const double* h2, int32_t n, float* dist) {
-  return distance_host(ctx, PR_TYPE_DELIGHT, h1, m, h2, n, dist, nullptr, 0, 0, 0, nullptr, nullptr, nullptr, false);
+  return distance_host(ctx, "pr_delight_distance", PR_TYPE_DELIGHT, h1, m, h2, n, dist, nullptr);
 }
 
 int pr_match_topk(pr_ctx* ctx, int type, const double* h1, int32_t m, const double* h2, int32_t n, int32_t mask_width,
                   double p_weight, int32_t k, int32_t* idx, float* score) {
-  if (!ctx) return PR_EINVAL;
-  if (type != PR_TYPE_SC && type != PR_TYPE_M2DP && type != PR_TYPE_DELIGHT) PR_FAIL(ctx, PR_EINVAL, "pr_match_topk: unknown type %d", type);
-  if (!score) PR_FAIL(ctx, PR_EINVAL, "pr_match_topk: score is NULL");
-  return distance_host(ctx, type, h1, m, h2, n, nullptr, nullptr, mask_width, p_weight, k, idx, score, nullptr, true);
+  return topk_host(ctx, "pr_match_topk", type, h1, nullptr, m, h2, nullptr, n, mask_width, p_weight, k, idx, score);
 }
 
 int pr_match_topk_f64(pr_ctx* ctx, int type, const double* h1, int32_t m, const double* h2, int32_t n, int32_t mask_width,
                       double p_weight, int32_t k, int32_t* idx, double* score) {
-  if (!ctx) return PR_EINVAL;
-  if (type != PR_TYPE_SC && type != PR_TYPE_M2DP && type != PR_TYPE_DELIGHT) PR_FAIL(ctx, PR_EINVAL, "pr_match_topk_f64: unknown type %d", type);
-  if (!score) PR_FAIL(ctx, PR_EINVAL, "pr_match_topk_f64: score is NULL");
-  return distance_host(ctx, type, h1, m, h2, n, nullptr, nullptr, mask_width, p_weight, k, idx, nullptr, score, true);
-}
-
-static int fuse_select2_impl(pr_ctx* ctx, const float* d_p, const float* d_i, const float* e_p, const float* e_i, int32_t m, int32_t n,
-                             const double* mom_all, const double* mom2_all, int32_t G, int32_t q_row0, int32_t db_row0,
-                             int32_t mask_width, double p_weight, int32_t k, int32_t* idx, float* score, double* score64) {
-  if (!ctx || !d_p || !d_i || !e_p || !e_i || !mom_all || !mom2_all || !idx || !score || m < 0 || n < 1 || G < 1 || k < 1) return PR_EINVAL;
-  if (int rc = set_device(ctx)) return rc;
-  pr::launch_fuse_select(ctx->stream, d_p, d_i, m, n, mom_all, G, q_row0, db_row0, mask_width, p_weight, k, idx, score, e_p, e_i, mom2_all, ctx->sel_scratch, score64);
-  PR_HIP(ctx, hipGetLastError());
-  return PR_OK;
-}
-int pr_fuse_select2_dev(pr_ctx* ctx, const float* d_p, const float* d_i, const float* e_p, const float* e_i, int32_t m, int32_t n,
-                        const double* mom_all, const double* mom2_all, int32_t G, int32_t q_row0, int32_t db_row0,
-                        int32_t mask_width, double p_weight, int32_t k, int32_t* idx, float* score) {
-  return fuse_select2_impl(ctx, d_p, d_i, e_p, e_i, m, n, mom_all, mom2_all, G, q_row0, db_row0, mask_width, p_weight, k, idx, score, nullptr);
-}
-int pr_fuse_select2_f64_dev(pr_ctx* ctx, const float* d_p, const float* d_i, const float* e_p, const float* e_i, int32_t m, int32_t n,
-                            const double* mom_all, const double* mom2_all, int32_t G, int32_t q_row0, int32_t db_row0,
-                            int32_t mask_width, double p_weight, int32_t k, int32_t* idx, float* score, double* score64) {
-  if (!score64) return PR_EINVAL;
-  return fuse_select2_impl(ctx, d_p, d_i, e_p, e_i, m, n, mom_all, mom2_all, G, q_row0, db_row0, mask_width, p_weight, k, idx, score, score64);
+  return topk_host(ctx, "pr_match_topk_f64", type, h1, nullptr, m, h2, nullptr, n, mask_width, p_weight, k, idx, score);
 }
 
 // BASELINE.json config 5: SC and M2DP signatures of the same places scored together (build-defined)
-static int fused_host(pr_ctx* ctx, const double* sc1, const double* m2dp1, int32_t m, const double* sc2, const double* m2dp2,
-                      int32_t n, int32_t mask_width, double p_weight, int32_t k, int32_t* idx, float* score32, double* score64) {
-  if (!ctx) return PR_EINVAL;
-  if (m < 0 || n < 2 || k < 1 || k > 120 || !idx || (!score32 && !score64) || (m > 0 && (!sc1 || !m2dp1)) || !sc2 || !m2dp2)
-    PR_FAIL(ctx, PR_EINVAL, "pr_match_topk_fused: bad arguments (m=%d, n=%d, k=%d)", m, n, k);
-  if (m == 0) return PR_OK;
-  if (int rc = set_device(ctx)) return rc;
-  pr_sigset* ss[4] = {nullptr, nullptr, nullptr, nullptr};   // SC query, SC db, M2DP query, M2DP db
-  DevScope scope_(ctx);
-  DevBuf raw[4], d[4], mom[2], didx, dsc, dcand, dsc64, dsw;
-  const void* host[4] = {sc1, sc2, m2dp1, m2dp2};
-  const size_t bytes[4] = {(size_t)m * 2400 * 8, (size_t)n * 2400 * 8, (size_t)m * 4 * 384 * 8, (size_t)n * 4 * 384 * 8};
-  const int kin = rerank_width(k, ctx->sc_mode);
-  int rc = PR_OK;
-  do {
-    if ((rc = pr_sigset_create(ctx, PR_TYPE_SC, PR_ROLE_QUERY, m, &ss[0])) || (rc = pr_sigset_create(ctx, PR_TYPE_SC, PR_ROLE_DB, n, &ss[1])) ||
-        (rc = pr_sigset_create(ctx, PR_TYPE_M2DP, PR_ROLE_QUERY, m, &ss[2])) || (rc = pr_sigset_create(ctx, PR_TYPE_M2DP, PR_ROLE_DB, n, &ss[3]))) break;
-    bool ok = true;
-    for (int i = 0; i < 4; i++)
-      ok = ok && raw[i].alloc(bytes[i]) == hipSuccess &&
-           hipMemcpyAsync(raw[i].p, host[i], bytes[i], hipMemcpyHostToDevice, ctx->stream) == hipSuccess;
-    if (!ok) { ctx->err = "out of device memory for the signatures"; rc = PR_ENOMEM; break; }
-    if ((rc = pr_sigset_pack(ctx, ss[0], raw[0].p, PR_F64, PR_DEVICE, m)) || (rc = pr_sigset_pack(ctx, ss[1], raw[1].p, PR_F64, PR_DEVICE, n)) ||
-        (rc = pr_sigset_pack(ctx, ss[2], raw[2].p, PR_F64, PR_DEVICE, m)) || (rc = pr_sigset_pack(ctx, ss[3], raw[3].p, PR_F64, PR_DEVICE, n))) break;
-    const size_t mn = (size_t)m * n;
-    for (auto& b : d) ok = ok && b.alloc(mn * 4) == hipSuccess;
-    ok = ok && mom[0].alloc((size_t)m * 6 * 8) == hipSuccess && mom[1].alloc((size_t)m * 6 * 8) == hipSuccess &&
-         didx.alloc((size_t)m * kin * 4) == hipSuccess && dsc.alloc((size_t)m * kin * 4) == hipSuccess &&
-         dcand.alloc((size_t)m * k * 4) == hipSuccess && dsc64.alloc((size_t)m * k * 8) == hipSuccess && dsw.alloc((size_t)m * kin * 8) == hipSuccess;
-    if (!ok) { ctx->err = "out of device memory for the four m x n distance matrices"; rc = PR_ENOMEM; break; }
-    if ((rc = pr_distances_dev(ctx, ss[0], ss[1], d[0].as<float>(), d[1].as<float>())) ||
-        (rc = pr_distances_dev(ctx, ss[2], ss[3], d[2].as<float>(), d[3].as<float>())) ||
-        (rc = pr_row_moments_dev(ctx, d[0].as<float>(), d[1].as<float>(), m, n, mom[0].as<double>())) ||
-        (rc = pr_row_moments_dev(ctx, d[2].as<float>(), d[3].as<float>(), m, n, mom[1].as<double>())) ||
-        (rc = pr_fuse_select2_dev(ctx, d[0].as<float>(), d[1].as<float>(), d[2].as<float>(), d[3].as<float>(), m, n, mom[0].as<double>(),
-                                  mom[1].as<double>(), 1, 0, 0, mask_width, p_weight, kin, didx.as<int32_t>(), dsc.as<float>())) ||
-        (rc = pr_widen_scores_dev(ctx, dsc.as<float>(), (int64_t)m * kin, dsw.as<double>())) ||
-        (rc = pr_rerank_dev(ctx, raw[0].p, raw[1].p, PR_F64, raw[2].p, raw[3].p, PR_F64, mom[0].as<double>(), mom[1].as<double>(), m, n, 1,
-                            0, 0, mask_width, p_weight, kin, didx.as<int32_t>(), dsw.as<double>(), k, dcand.as<int32_t>(), dsc64.as<double>()))) break;
-    std::vector<double> t64;
-    if (score32) t64.resize((size_t)m * k);
-    if (ctx->sc_mode != PR_SC_ARITH_F16 &&
-        (rc = pr_order_resolve_dev(ctx, raw[0].p, raw[1].p, PR_F64, raw[2].p, raw[3].p, PR_F64, mom[0].as<double>(), mom[1].as<double>(), m, n, 0,
-                                   mask_width, p_weight, k, dcand.as<int32_t>(), dsc64.as<double>(), nullptr))) break;
-    if (ctx->sc_mode == PR_SC_ARITH_F16 &&
-        (rc = f16_fallback(ctx, sc1, m2dp1, raw[1].p, raw[3].p, m, n, mask_width, p_weight, k, mom[0].as<double>(), mom[1].as<double>(), kin,
-                           dsw.as<double>(), dcand.as<int32_t>(), dsc64.as<double>()))) break;
-    if (hipMemcpyAsync(idx, dcand.p, (size_t)m * k * 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-        hipMemcpyAsync(score64 ? score64 : t64.data(), dsc64.p, (size_t)m * k * 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) { ctx->err = "D2H copy failed"; rc = PR_EHIP; break; }
-    if ((rc = pr_sync(ctx))) break;
-    if (score32) for (size_t i = 0; i < t64.size(); i++) score32[i] = (float)t64[i];
-  } while (0);
-  if (rc != PR_OK) (void)hipStreamSynchronize(ctx->stream);
-  for (auto* q : ss) pr_sigset_destroy(ctx, q);
-  return rc;
-}
-
 int pr_match_topk_fused(pr_ctx* ctx, const double* sc1, const double* m2dp1, int32_t m, const double* sc2, const double* m2dp2,
                         int32_t n, int32_t mask_width, double p_weight, int32_t k, int32_t* idx, float* score) {
-  return fused_host(ctx, sc1, m2dp1, m, sc2, m2dp2, n, mask_width, p_weight, k, idx, score, nullptr);
+  return topk_host(ctx, "pr_match_topk_fused", -1, sc1, m2dp1, m, sc2, m2dp2, n, mask_width, p_weight, k, idx, score);
 }
 
 int pr_match_topk_fused_f64(pr_ctx* ctx, const double* sc1, const double* m2dp1, int32_t m, const double* sc2, const double* m2dp2,
                             int32_t n, int32_t mask_width, double p_weight, int32_t k, int32_t* idx, double* score) {
-  return fused_host(ctx, sc1, m2dp1, m, sc2, m2dp2, n, mask_width, p_weight, k, idx, nullptr, score);
+  return topk_host(ctx, "pr_match_topk_fused_f64", -1, sc1, m2dp1, m, sc2, m2dp2, n, mask_width, p_weight, k, idx, score);
 }
 
 // pr_match_align / pr_match_align_fused.  type: PR_TYPE_SC | PR_TYPE_M2DP | PR_TYPE_DELIGHT with h1 = a1, h2 = a2, or -1 = fused (a: SC,
@@ -1550,30 +1562,27 @@ static int align_host(pr_ctx* ctx, const char* who, int type, const double* a1, 
   std::sort(rows.begin(), rows.end());
   rows.erase(std::unique(rows.begin(), rows.end()), rows.end());
   const int S = fused ? 4 : 2;
-  if (rows.empty()) {                                            // nothing referenced: every pair is "no candidate"
-    for (size_t i = 0; i < mk * S; i++) { var_out[i] = -1; dist_out[i] = NAN; }
-    return PR_OK;
-  }
+  if (rows.empty()) return no_candidate(mk * S, var_out, dist_out);   // nothing referenced: every pair is "no candidate"
   if (!a2 || (fused && !b2)) PR_FAIL(ctx, PR_EINVAL, "%s: the DB signatures are NULL", who);
   std::vector<int32_t> lidx(mk);
   for (size_t i = 0; i < mk; i++)
     lidx[i] = idx[i] < 0 ? -1 : (int32_t)(std::lower_bound(rows.begin(), rows.end(), idx[i]) - rows.begin());
   if (int rc = set_device(ctx)) return rc;
   const int32_t u = (int32_t)rows.size();
-  // the descriptor types of the call: {rows per signature, doubles per row, query signatures, DB signatures}
-  struct Part { size_t rows_per, cols; const double* q; const double* db; };
-  std::vector<Part> parts;
-  if (fused) parts = {{1, PR_SC_SIG_LEN, a1, a2}, {4, PR_M2DP_SIG_LEN, b1, b2}};
-  else if (type == PR_TYPE_SC) parts = {{1, PR_SC_SIG_LEN, a1, a2}};
-  else if (type == PR_TYPE_M2DP) parts = {{4, PR_M2DP_SIG_LEN, a1, a2}};
-  else parts = {{16, PR_DELIGHT_SIG_LEN, a1, a2}};
+  // the descriptor types of the call by slot of the device form (SC or DELIGHT: 0, M2DP: 1): {type, query signatures, DB signatures}
+  struct Part { int type; const double* q; const double* db; } parts[2] = {{-1, nullptr, nullptr}, {-1, nullptr, nullptr}};
+  if (fused) { parts[0] = {PR_TYPE_SC, a1, a2}; parts[1] = {PR_TYPE_M2DP, b1, b2}; }
+  else parts[type == PR_TYPE_M2DP ? 1 : 0] = {type, a1, a2};
+  const size_t slots = type == PR_TYPE_DELIGHT ? 1 : 4;          // of the device form's output
+  // (host ends of the async copies come first: on an error return the DevBufs' destructors idle the streams before these go)
+  std::vector<double> gathered, hd(mk * slots);
+  std::vector<int32_t> hv(mk * slots);
   DevScope scope_(ctx);
   DevBuf dq[2], ddb[2], didx, dvar, ddist;
-  const size_t slots = type == PR_TYPE_DELIGHT ? 1 : 4;          // of the device form's output
-  std::vector<double> gathered;
-  for (size_t p = 0; p < parts.size(); p++) {
+  for (int p = 0; p < 2; p++) {
     const Part& P = parts[p];
-    const size_t sig = P.rows_per * P.cols;                      // doubles per signature
+    if (P.type < 0) continue;
+    const size_t sig = sig_doubles(P.type);
     gathered.resize((size_t)u * sig);
     for (int32_t r = 0; r < u; r++) std::memcpy(gathered.data() + (size_t)r * sig, P.db + (size_t)rows[r] * sig, sig * 8);
     PR_HIP(ctx, dq[p].alloc((size_t)m * sig * 8));
@@ -1586,20 +1595,11 @@ static int align_host(pr_ctx* ctx, const char* who, int type, const double* a1, 
   PR_HIP(ctx, dvar.alloc(mk * slots * 4));
   PR_HIP(ctx, ddist.alloc(mk * slots * 8));
   PR_HIP(ctx, hipMemcpyAsync(didx.p, lidx.data(), mk * 4, hipMemcpyHostToDevice, ctx->stream));
-  int rc;
-  if (type == PR_TYPE_DELIGHT)
-    rc = pr_delight_align_pairs_dev(ctx, dq[0].p, ddb[0].p, PR_F64, m, u, 0, k, didx.as<int32_t>(), dvar.as<int32_t>(), ddist.as<double>());
-  else if (fused)
-    rc = pr_align_pairs_dev(ctx, dq[0].p, ddb[0].p, PR_F64, dq[1].p, ddb[1].p, PR_F64, m, u, 0, k, didx.as<int32_t>(), dvar.as<int32_t>(),
-                            ddist.as<double>());
-  else {
-    const bool sc = type == PR_TYPE_SC;
-    rc = pr_align_pairs_dev(ctx, sc ? dq[0].p : nullptr, sc ? ddb[0].p : nullptr, PR_F64, sc ? nullptr : dq[0].p, sc ? nullptr : ddb[0].p, PR_F64,
-                            m, u, 0, k, didx.as<int32_t>(), dvar.as<int32_t>(), ddist.as<double>());
-  }
-  if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
-  std::vector<int32_t> hv(mk * slots);
-  std::vector<double> hd(mk * slots);
+  if (int rc = type == PR_TYPE_DELIGHT
+                   ? pr_delight_align_pairs_dev(ctx, dq[0].p, ddb[0].p, PR_F64, m, u, 0, k, didx.as<int32_t>(), dvar.as<int32_t>(), ddist.as<double>())
+                   : pr_align_pairs_dev(ctx, dq[0].p, ddb[0].p, PR_F64, dq[1].p, ddb[1].p, PR_F64, m, u, 0, k, didx.as<int32_t>(),
+                                        dvar.as<int32_t>(), ddist.as<double>()))
+    return rc;
   PR_HIP(ctx, hipMemcpyAsync(hv.data(), dvar.p, mk * slots * 4, hipMemcpyDeviceToHost, ctx->stream));
   PR_HIP(ctx, hipMemcpyAsync(hd.data(), ddist.p, mk * slots * 8, hipMemcpyDeviceToHost, ctx->stream));
   PR_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -1632,33 +1632,22 @@ static int plain_cols_host(pr_ctx* ctx, int type, const double* h1, int32_t m, c
     PR_FAIL(ctx, PR_EINVAL, "bad signature buffers (m=%d, n=%d, cols=%d)", m, n, cols);
   if (type == PR_TYPE_BOW && (size_t)cols * 16 > 160 * 1024) PR_FAIL(ctx, PR_EINVAL, "BoW rows of %d columns do not fit the LDS", cols);
   if (want_topk && (k < 1 || !idx || !score)) PR_FAIL(ctx, PR_EINVAL, "top-k needs k >= 1 and output buffers");
-  if (want_topk && n == 0) { for (size_t i = 0; i < (size_t)m * k; i++) { idx[i] = -1; score[i] = NAN; } return PR_OK; }
+  if (want_topk && n == 0) return no_candidate((size_t)m * k, idx, score);
   if (m == 0 || n == 0) return PR_OK;
   if (int rc = set_device(ctx)) return rc;
   const size_t rows1 = (type == PR_TYPE_BOW ? 2 : 1) * (size_t)m, rows2 = (type == PR_TYPE_BOW ? 2 : 1) * (size_t)n;
-  const size_t mn = (size_t)m * n;
   DevScope scope_(ctx);
-  DevBuf d1, d2, dd, didx, dsc;
-  if (d1.alloc(rows1 * cols * 8) != hipSuccess || d2.alloc(rows2 * cols * 8) != hipSuccess || dd.alloc(mn * 4) != hipSuccess)
+  DevBuf d1, d2, dd;
+  if (d1.alloc(rows1 * cols * 8) != hipSuccess || d2.alloc(rows2 * cols * 8) != hipSuccess || dd.alloc((size_t)m * n * 4) != hipSuccess)
     PR_FAIL(ctx, PR_ENOMEM, "out of device memory for %d x %d %s signatures", m, n, type == PR_TYPE_BOW ? "BoW" : "GIST");
-  int rc = PR_OK;
-  do {
-    if (hipMemcpyAsync(d1.p, h1, rows1 * cols * 8, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
-        hipMemcpyAsync(d2.p, h2, rows2 * cols * 8, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) { ctx->err = "H2D copy failed"; rc = PR_EHIP; break; }
-    if (type == PR_TYPE_GIST) pr::launch_gist_distance(ctx->stream, d1.as<double>(), m, d2.as<double>(), n, cols, dd.as<float>());
-    else pr::launch_bow_distance(ctx->stream, d1.as<double>(), m, d2.as<double>(), n, cols, dd.as<float>());
-    if (hipGetLastError() != hipSuccess) { ctx->err = "kernel launch failed"; rc = PR_EHIP; break; }
-    if (want_topk) {
-      if (didx.alloc((size_t)m * k * 4) != hipSuccess || dsc.alloc((size_t)m * k * 4) != hipSuccess) { ctx->err = "out of device memory"; rc = PR_ENOMEM; break; }
-      if ((rc = pr_fuse_select_dev(ctx, dd.as<float>(), nullptr, m, n, nullptr, 1, 0, 0, mask_width, 0.0, k, didx.as<int32_t>(), dsc.as<float>()))) break;
-      if (hipMemcpyAsync(idx, didx.p, (size_t)m * k * 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-          hipMemcpyAsync(score, dsc.p, (size_t)m * k * 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) { ctx->err = "D2H copy failed"; rc = PR_EHIP; break; }
-    }
-    if (out && hipMemcpyAsync(out, dd.p, mn * 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) { ctx->err = "D2H copy failed"; rc = PR_EHIP; break; }
-    rc = pr_sync(ctx);
-  } while (0);
-  if (rc != PR_OK) (void)hipStreamSynchronize(ctx->stream);
-  return rc;
+  PR_HIP(ctx, hipMemcpyAsync(d1.p, h1, rows1 * cols * 8, hipMemcpyHostToDevice, ctx->stream));
+  PR_HIP(ctx, hipMemcpyAsync(d2.p, h2, rows2 * cols * 8, hipMemcpyHostToDevice, ctx->stream));
+  if (type == PR_TYPE_GIST) pr::launch_gist_distance(ctx->stream, d1.as<double>(), m, d2.as<double>(), n, cols, dd.as<float>());
+  else pr::launch_bow_distance(ctx->stream, d1.as<double>(), m, d2.as<double>(), n, cols, dd.as<float>());
+  PR_HIP(ctx, hipGetLastError());
+  if (want_topk) return plain_topk(ctx, dd.as<float>(), m, n, mask_width, 0.0, k, idx, score);
+  if (out) PR_HIP(ctx, hipMemcpyAsync(out, dd.p, (size_t)m * n * 4, hipMemcpyDeviceToHost, ctx->stream));
+  return pr_sync(ctx);
 }
 
 int pr_gist_distance(pr_ctx* ctx, const double* h1, int32_t m, const double* h2, int32_t n, int32_t cols, float* dist) {
@@ -1928,7 +1917,7 @@ static int generate_host(pr_ctx* ctx, int type, const double* xyz, const float* 
   const size_t T = (size_t)offs[N];
   if (T > 0 && (!xyz || !inten)) PR_FAIL(ctx, PR_EINVAL, "generate: xyz/inten are NULL");
   if (int rc = set_device(ctx)) return rc;
-  const size_t rowlen = (type == PR_TYPE_SC) ? PR_SC_SIG_LEN : (type == PR_TYPE_M2DP ? (size_t)4 * PR_M2DP_SIG_LEN : (size_t)16 * PR_DELIGHT_SIG_LEN);
+  const size_t rowlen = sig_doubles(type);
   DevScope scope_(ctx);
   DevBuf dx, di, dof, dout;
   PR_HIP(ctx, dx.alloc(T * 24));
@@ -1972,7 +1961,7 @@ int pr_generate_clouds(pr_ctx* ctx, int type, const pr_clouds* c, double max_rho
     return generate_host(ctx, type, c->xyz.data(), c->inten.data(), c->offs.data(), N, max_rho, out);
   if (N > 0 && !out) PR_FAIL(ctx, PR_EINVAL, "pr_generate_clouds: out is NULL");
   if (int rc = set_device(ctx)) return rc;
-  const size_t rowlen = (type == PR_TYPE_SC) ? PR_SC_SIG_LEN : (type == PR_TYPE_M2DP ? (size_t)4 * PR_M2DP_SIG_LEN : (size_t)16 * PR_DELIGHT_SIG_LEN);
+  const size_t rowlen = sig_doubles(type);
   DevScope scope_(ctx);
   DevBuf dout;
   PR_HIP(ctx, dout.alloc((size_t)N * rowlen * 8));

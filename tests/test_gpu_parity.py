@@ -167,6 +167,13 @@ def test_match_topk_vs_oracle(api, type_, mask, k):
     assert np.array_equal(gidx, oidx)                       # bit-exact indices
     rc, odp, odi = oracle_lib.sc_distance(q, db) if type_ == "sc" else oracle_lib.m2dp_distance(q, db)
     assert gsc.dtype == np.float64 and (np.abs(gsc - osc) <= helpers.score_tol(osc, helpers.row_sigmas(odp, odi))).all()   # helpers.score_tol: the bound and where it comes from
+    # the fp32-score form on the same inputs: the same indices, the f64 form's scores rounded to float32
+    ctx = api.default_context()
+    div = 1 if type_ == "sc" else 4
+    idx32 = np.empty_like(gidx); sc32 = np.empty(gidx.shape, np.float32)
+    ctx.check(ctx.lib.pr_match_topk(ctx.h, t, api._ptr(q), q.shape[0] // div, api._ptr(db), db.shape[0] // div, mask, 2.0, k,
+                                    api._ptr(idx32), api._ptr(sc32)))
+    assert np.array_equal(idx32, gidx) and np.array_equal(sc32, gsc.astype(np.float32), equal_nan=True)
 
 
 def test_match_planted_and_ties(api, golden_dir):
@@ -547,6 +554,12 @@ def test_fused_sc_m2dp_scoring_vs_oracle(api):
     idx, sc = api.match_topk_fused(sq, mq, sdb, mdb, mask_width=3, p_weight=2.0, k=3)
     sg = [helpers.row_sigmas(*oracle_lib.sc_distance(sq, sdb)[1:]), helpers.row_sigmas(*oracle_lib.m2dp_distance(mq, mdb)[1:])]
     assert np.array_equal(idx, oidx) and (np.abs(sc - osc) <= helpers.score_tol(osc, sg[0]) + helpers.score_tol(osc, sg[1])).all()
+    # the fp32-score form on the same inputs: the same indices, the f64 form's scores rounded to float32
+    ctx = api.default_context()
+    idx32 = np.empty_like(idx); sc32 = np.empty(idx.shape, np.float32)
+    ctx.check(ctx.lib.pr_match_topk_fused(ctx.h, api._ptr(sq), api._ptr(mq), m, api._ptr(sdb), api._ptr(mdb), n, 3, 2.0, 3,
+                                          api._ptr(idx32), api._ptr(sc32)))
+    assert np.array_equal(idx32, idx) and np.array_equal(sc32, sc.astype(np.float32), equal_nan=True)
     # one channel pair switched off (identical rows give z = NaN there) is not the point; agreement of SC-only with the fused
     # top-1 on queries planted in BOTH databases at the same index is
     same = planted == planted2
