@@ -20,6 +20,7 @@ extern "C" {
 typedef struct pr_ctx pr_ctx;
 typedef struct pr_sigset pr_sigset;
 typedef struct pr_clouds pr_clouds;
+typedef struct pr_bow_vocab pr_bow_vocab;
 
 enum { PR_OK = 0, PR_EINVAL = -1, PR_ENOMEM = -2, PR_EHIP = -3, PR_EIO = -4, PR_ENAN = -5 };
 enum { PR_TYPE_SC = 0, PR_TYPE_M2DP = 1, PR_TYPE_DELIGHT = 2, PR_TYPE_GIST = 3, PR_TYPE_BOW = 4 };   /* run_test.m:26-36 `type` */
@@ -51,7 +52,7 @@ enum { PR_SC_ARITH_F16X2 = 0, PR_SC_ARITH_F32 = 1, PR_SC_ARITH_F16 = 2 };
  * PR_NAN_EXCLUDE (default) does exactly that and reports PR_WARN_NAN_ROWS; PR_NAN_FAIL turns it into the error PR_ENAN at pr_sync. */
 enum { PR_NAN_EXCLUDE = 0, PR_NAN_FAIL = 1 };
 enum { PR_WARN_NAN_ROWS = 1, PR_WARN_M2DP_SVD = 2, PR_WARN_F16_FALLBACK = 4, PR_WARN_ORDER_RESOLVED = 8,
-       PR_WARN_ORDER_UNRESOLVED = 16 };   /* bits of pr_take_warnings; ORDER_RESOLVED: a query was answered from its exact fp64 row (order or containment
+       PR_WARN_ORDER_UNRESOLVED = 16, PR_WARN_BOW_TRUNCATED = 32 };   /* bits of pr_take_warnings; ORDER_RESOLVED: a query was answered from its exact fp64 row (order or containment
                                             check, below); the last one: a caller of the sharded per-pass form stopped (last_pass != 0) with flagged queries left -
                                             those keep the answer of the re-evaluated candidate list.  The library's own calls, stream-ordered or not, run every pass */
 
@@ -139,6 +140,35 @@ int pr_gist_generate(pr_ctx* ctx, const void* img, int dtype, int32_t N, int32_t
                      const int32_t* orients, float* out);
 int pr_gist_generate_dev(pr_ctx* ctx, const void* img, int dtype, int32_t N, int32_t height, int32_t width, int32_t nblocks,
                          int32_t n_scale, const int32_t* orients, float* out);
+
+/* DBoW2 vocabulary of ORB descriptors (ORB_SLAM2::ORBVocabulary = TemplatedVocabulary<FORB::TDescriptor, FORB>), independent of any
+ * context.  pr_bow_vocab_load reads ORBvoc-style text (TemplatedVocabulary.h:1338-1424, loadFromTextFile: a header `k L scoring weighting`,
+ * then one node per line `parent isLeaf d0 .. d31 weight`, node id = line position, root = node 0 without a line) or the binary side-car of
+ * pr_bow_vocab_save_bin, told apart by its magic.  Empty lines are skipped (the reference appends a node with undefined bytes for them).
+ * PR_EINVAL (message in pr_host_last_error) for a header outside 0 <= k <= 20, 1 <= L <= 10, scoring 0..5, weighting 0..3, or a line with
+ * fewer than 35 tokens, a non-numeric token, a non-finite weight or parent >= its own id.  Node arrays cover the root at index 0 (export
+ * writes -1 / 0 / zeros / 0 for it, create ignores it): parent [n_nodes] i32, is_leaf [n_nodes] u8 (> 0: a word, ids in node order),
+ * desc [n_nodes][32] u8, weight [n_nodes] f64.  info: [k, L, scoring, weighting]. */
+int pr_bow_vocab_load(const char* path, pr_bow_vocab** out);
+int pr_bow_vocab_save_bin(const pr_bow_vocab* v, const char* path);
+int pr_bow_vocab_create(int32_t k, int32_t L, int32_t scoring, int32_t weighting, int64_t n_nodes, const int32_t* parent,
+                        const uint8_t* is_leaf, const uint8_t* desc, const double* weight, pr_bow_vocab** out);
+int pr_bow_vocab_info(const pr_bow_vocab* v, int32_t* info, int64_t* n_nodes, int64_t* n_words);
+int pr_bow_vocab_export(const pr_bow_vocab* v, int32_t* parent, uint8_t* is_leaf, uint8_t* desc, double* weight);
+void pr_bow_vocab_destroy(pr_bow_vocab* v);
+
+/* Replaces ORBVocabulary::transform looped as in BoW/test_bow.cpp:127-135 (TemplatedVocabulary.h:1127-1260; the FeatureVector is not
+ * produced).  desc [offs[N]][32] u8 ORB descriptors (the rows of ORBextractor's cv::Mat), offs [N+1] i64 (CSR, offs[0] = 0).
+ * out [2N][cols] f64 in pr_bow_distance's layout: per image a row of word ids in ascending order and a row of their values, both padded
+ * with -1.  n_words [N] (optional): each image's distinct-word count.  The host form returns PR_EINVAL naming the first image with more
+ * than cols words.  The device form (desc, offs, out, n_words, feat_words device pointers; n_desc = offs[N]) is stream-ordered without host
+ * waits and, after its first call with this vocabulary and at least this many descriptors, allocates nothing (graph-capturable); a row
+ * with more than cols words keeps its first cols and raises PR_WARN_BOW_TRUNCATED, n_words still holds the true count.  feat_words
+ * [n_desc] (optional): each descriptor's word id (-1 for every descriptor when the vocabulary has no words). */
+int pr_bow_generate(pr_ctx* ctx, const pr_bow_vocab* vocab, const uint8_t* desc, const int64_t* offs, int32_t N, int32_t cols,
+                    double* out, int32_t* n_words);
+int pr_bow_generate_dev(pr_ctx* ctx, const pr_bow_vocab* vocab, const uint8_t* desc, int64_t n_desc, const int64_t* offs, int32_t N,
+                        int32_t cols, double* out, int32_t* n_words, int32_t* feat_words);
 
 /* Replaces processDELIGHT(hist1, hist2) (match_signatures/processDELIGHT.m:1-38).  h1[16m][256], h2[16n][256];
  * dist: host f32 [m][n] (chi-square, min over the 4 octant permutations; +Inf when no bin is occupied). */

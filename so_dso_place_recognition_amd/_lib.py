@@ -13,6 +13,7 @@ TYPE_SC, TYPE_M2DP, TYPE_DELIGHT, TYPE_GIST, TYPE_BOW = 0, 1, 2, 3, 4
 SC_ARITH_F16X2, SC_ARITH_F32, SC_ARITH_F16 = 0, 1, 2
 NAN_EXCLUDE, NAN_FAIL = 0, 1
 WARN_NAN_ROWS, WARN_M2DP_SVD, WARN_F16_FALLBACK, WARN_ORDER_RESOLVED, WARN_ORDER_UNRESOLVED = 1, 2, 4, 8, 16
+WARN_BOW_TRUNCATED = 32
 ROLE_QUERY, ROLE_DB = 0, 1
 F64, F32 = 0, 1
 U8 = 2              # 8-bit images (pr_gist_generate*)
@@ -86,6 +87,14 @@ SYMBOLS = {
     "pr_gist_signature_size": (C.c_int, [_i32, _i32, _vp]),
     "pr_gist_generate": (C.c_int, [_vp, _vp, C.c_int, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "pr_gist_generate_dev": (C.c_int, [_vp, _vp, C.c_int, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "pr_bow_vocab_load": (C.c_int, [C.c_char_p, C.POINTER(_vp)]),
+    "pr_bow_vocab_save_bin": (C.c_int, [_vp, C.c_char_p]),
+    "pr_bow_vocab_create": (C.c_int, [_i32, _i32, _i32, _i32, C.c_int64, _vp, _vp, _vp, _vp, C.POINTER(_vp)]),
+    "pr_bow_vocab_info": (C.c_int, [_vp, _vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "pr_bow_vocab_export": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    "pr_bow_vocab_destroy": (None, [_vp]),
+    "pr_bow_generate": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp]),
+    "pr_bow_generate_dev": (C.c_int, [_vp, _vp, _vp, C.c_int64, _vp, _i32, _i32, _vp, _vp, _vp]),
     "pr_delight_distance": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _vp]),
     "pr_gist_distance": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _i32, _vp]),
     "pr_bow_distance": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _i32, _vp]),

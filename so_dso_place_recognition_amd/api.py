@@ -3,6 +3,7 @@
 Same names, argument meaning and error behaviour as the reference:
   SC / M2DP classes            SC/SC.h:10-23, M2DP/M2DP.h:12-30  (getSignatureSize / getSignature)
   GIST class, gist_generate    GIST/include/gist.h, gist.cpp:54-94  (getSignatureSize / extract)
+  ORBVocabulary, bow_generate  BoW/ORBVocabulary.h, DBoW2 TemplatedVocabulary.h (loadFromTextFile / transform), test_bow.cpp:127-163
   processSC / processM2DP      match_signatures/processSC.m:1, processM2DP.m:1
   run_test                     match_signatures/run_test.m:1  (fusion, mask, top-1; PR/AUC evaluation in eval.py)
 Arrays are numpy on the host; the device-resident path used by bench.py / dist.py is `Matcher`.
@@ -356,6 +357,170 @@ def _torch_default_context(device: int):
         c = Context(device)
         _torch_ctx[device] = (c, torch.cuda.ExternalStream(c.stream, device=device))
     return _torch_ctx[device]
+
+
+class ORBVocabulary:
+    """ORB_SLAM2::ORBVocabulary (DBoW2 TemplatedVocabulary<FORB::TDescriptor, FORB>): the vocabulary tree, held by the library
+    (pr_bow_vocab, no device needed until transform).  Scoring / weighting values as DBoW2's enums: scoring L1_NORM, L2_NORM, CHI_SQUARE,
+    KL, BHATTACHARYYA, DOT_PRODUCT = 0..5; weighting TF_IDF, TF, IDF, BINARY = 0..3."""
+
+    def __init__(self, path: str | None = None):
+        self.lib = _lib.load()
+        self.h = None
+        if path is not None:
+            self.loadFromTextFile(path)
+
+    def _own(self, h):
+        self.close()
+        self.h = h
+
+    def loadFromTextFile(self, path: str) -> bool:
+        """ORBvoc-style text (TemplatedVocabulary.h:1338-1424) or the binary side-car of save(); raises PRError (PR_EINVAL / PR_EIO)
+        where the reference would fail or read out of bounds."""
+        h = C.c_void_p()
+        rc = self.lib.pr_bow_vocab_load(os.fsencode(path), C.byref(h))
+        if rc != 0:
+            raise PRError(rc, self.lib.pr_host_last_error().decode())
+        self._own(h)
+        return True
+
+    @classmethod
+    def from_arrays(cls, k, L, scoring, weighting, parent, is_leaf, desc, weight):
+        """Node arrays with the root at index 0 (its entries ignored): parent int32 [n] (< own index), is_leaf [n] (> 0: a word),
+        desc uint8 [n, 32], weight float64 [n]."""
+        parent = np.ascontiguousarray(parent, np.int32)
+        n = parent.shape[0]
+        is_leaf = np.ascontiguousarray(is_leaf, np.uint8)
+        desc = np.ascontiguousarray(desc, np.uint8)
+        weight = np.ascontiguousarray(weight, np.float64)
+        if is_leaf.shape != (n,) or desc.shape != (n, 32) or weight.shape != (n,):
+            raise ValueError("from_arrays: parent [n], is_leaf [n], desc [n, 32], weight [n]")
+        v = cls()
+        h = C.c_void_p()
+        rc = v.lib.pr_bow_vocab_create(int(k), int(L), int(scoring), int(weighting), n, _ptr(parent), _ptr(is_leaf), _ptr(desc),
+                                       _ptr(weight), C.byref(h))
+        if rc != 0:
+            raise PRError(rc, v.lib.pr_host_last_error().decode())
+        v._own(h)
+        return v
+
+    def save(self, path: str):
+        """The binary side-car (loads ~100x faster than the text)."""
+        rc = self.lib.pr_bow_vocab_save_bin(self._handle(), os.fsencode(path))
+        if rc != 0:
+            raise PRError(rc, self.lib.pr_host_last_error().decode())
+
+    def _handle(self):
+        if not self.h:
+            raise ValueError("ORBVocabulary: nothing loaded")
+        return self.h
+
+    def info(self):
+        """dict of k, L, scoring, weighting, nodes (the root included), words."""
+        i = np.zeros(4, np.int32)
+        nn, nw = C.c_int64(), C.c_int64()
+        self.lib.pr_bow_vocab_info(self._handle(), _ptr(i), C.byref(nn), C.byref(nw))
+        return {"k": int(i[0]), "L": int(i[1]), "scoring": int(i[2]), "weighting": int(i[3]), "nodes": nn.value, "words": nw.value}
+
+    def size(self) -> int:
+        return self.info()["words"]
+
+    def empty(self) -> bool:
+        return self.size() == 0
+
+    def arrays(self):
+        """(parent, is_leaf, desc, weight) as from_arrays takes them (pr_bow_vocab_export)."""
+        n = self.info()["nodes"]
+        parent, is_leaf = np.empty(n, np.int32), np.empty(n, np.uint8)
+        desc, weight = np.empty((n, 32), np.uint8), np.empty(n, np.float64)
+        self.lib.pr_bow_vocab_export(self._handle(), _ptr(parent), _ptr(is_leaf), _ptr(desc), _ptr(weight))
+        return parent, is_leaf, desc, weight
+
+    def transform(self, descriptors, ctx: Context | None = None):
+        """BowVector of one image's ORB descriptors (uint8 [n, 32]): (word ids int64 ascending, values float64)."""
+        d = np.ascontiguousarray(descriptors, np.uint8).reshape(-1, 32)
+        out, nw = bow_generate((d, np.array([0, d.shape[0]], np.int64)), self, cols=max(d.shape[0], 1), ctx=ctx, return_counts=True)
+        return out[0, :nw[0]].astype(np.int64), out[1, :nw[0]].copy()
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.pr_bow_vocab_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _bow_csr(descriptors):
+    if isinstance(descriptors, tuple):
+        desc, offs = descriptors
+        desc = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+        offs = np.ascontiguousarray(offs, np.int64)
+    else:
+        parts = [np.ascontiguousarray(d, np.uint8).reshape(-1, 32) for d in descriptors]
+        offs = np.zeros(len(parts) + 1, np.int64)
+        offs[1:] = np.cumsum([p.shape[0] for p in parts])
+        desc = np.concatenate(parts) if parts else np.zeros((0, 32), np.uint8)
+    if offs.ndim != 1 or offs.shape[0] < 1 or offs[0] != 0 or offs[-1] != desc.shape[0]:
+        raise ValueError("bow_generate: offs must run from 0 to the descriptor count")
+    return desc, offs
+
+
+def bow_generate(descriptors, vocab: ORBVocabulary, cols: int = 4000, ctx: Context | None = None, return_counts: bool = False):
+    """ORBVocabulary::transform of each image (test_bow.cpp:127-135) -> float64 [2N, cols] as test_bow writes history_bow.txt and
+    processBoW reads it: per image a row of word ids (ascending) and a row of values, padded with -1.  descriptors: a list of uint8
+    [n_i, 32] arrays, or (desc [F, 32], offs [N + 1]).  An image with more than cols words raises PRError (PR_EINVAL).
+    return_counts: also return each image's distinct-word count (int32 [N])."""
+    ctx = ctx or default_context()
+    desc, offs = _bow_csr(descriptors)
+    N = offs.shape[0] - 1
+    out = np.empty((2 * N, int(cols)), np.float64)
+    nw = np.empty(N, np.int32)
+    ctx.check(ctx.lib.pr_bow_generate(ctx.h, vocab._handle(), _ptr(desc), _ptr(offs), N, int(cols), _ptr(out), _ptr(nw)))
+    return (out, nw) if return_counts else out
+
+
+def bow_generate_torch(desc, offs, vocab: ORBVocabulary, cols: int = 4000, ctx: Context | None = None, out=None, n_words=None,
+                       feature_words=None):
+    """Device form (pr_bow_generate_dev): desc a CUDA uint8 tensor [F, 32], offs a CUDA int64 tensor [N + 1] -> float64 tensor [2N, cols]
+    (or `out`).  n_words (int32 [N]) and feature_words (int32 [F], each descriptor's word id) are optional outputs.  No host wait; after
+    the first call with this vocabulary and at least F descriptors the library allocates nothing (graph-capturable with preallocated
+    outputs).  A row with more than cols words keeps its first cols and raises _lib.WARN_BOW_TRUNCATED (Context.take_warnings).
+    ctx as in gist_generate_torch: None joins a per-device library context to torch's current stream."""
+    import torch
+    if desc.dtype != torch.uint8 or not desc.is_cuda or offs.dtype != torch.int64 or not offs.is_cuda:
+        raise ValueError("bow_generate_torch: expected CUDA tensors desc uint8 [F, 32] and offs int64 [N + 1]")
+    desc = desc.contiguous().reshape(-1, 32)
+    offs = offs.contiguous()
+    F, N = desc.shape[0], offs.shape[0] - 1
+    if N < 0:
+        raise ValueError("bow_generate_torch: offs needs N + 1 entries")
+    if out is None:
+        out = torch.empty((2 * N, int(cols)), dtype=torch.float64, device=desc.device)
+    elif out.shape != (2 * N, cols) or out.dtype != torch.float64 or not out.is_contiguous():
+        raise ValueError(f"bow_generate_torch: out must be a contiguous float64 tensor [{2 * N}, {cols}]")
+    for name, t, n in (("n_words", n_words, N), ("feature_words", feature_words, F)):
+        if t is not None and (t.shape != (n,) or t.dtype != torch.int32 or not t.is_contiguous()):
+            raise ValueError(f"bow_generate_torch: {name} must be a contiguous int32 tensor [{n}]")
+    lib_stream = cur = None
+    if ctx is None:
+        ctx, lib_stream = _torch_default_context(desc.device.index or 0)
+        cur = torch.cuda.current_stream(desc.device)
+        lib_stream.wait_stream(cur)
+
+    def dp(t):
+        return C.c_void_p(t.data_ptr()) if t is not None else None
+    ctx.check(ctx.lib.pr_bow_generate_dev(ctx.h, vocab._handle(), dp(desc), F, dp(offs), N, int(cols), dp(out), dp(n_words),
+                                          dp(feature_words)))
+    if lib_stream is not None:
+        cur.wait_stream(lib_stream)
+        for t in (desc, offs, out, n_words, feature_words):
+            if t is not None:
+                t.record_stream(lib_stream)
+    return out
 
 
 class DELIGHT:

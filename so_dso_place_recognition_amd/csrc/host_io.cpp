@@ -91,6 +91,10 @@ inline int fmt_g(char* b, size_t n, double v) { return (int)(std::to_chars(b, b 
 
 }  // namespace
 
+namespace pr {
+void host_set_error(const std::string& msg) { g_io_err = msg; }   // bow.cpp: errors of the context-free vocabulary calls
+}  // namespace pr
+
 extern "C" {
 
 const char* pr_host_last_error(void) { return g_io_err.c_str(); }

@@ -247,11 +247,28 @@ size_t gist_scratch_floats(int chunk, int nf, int nb);
 void launch_gist(hipStream_t st, const void* img, bool u8, int n, int nb, int nf, const float* circ, const float* gabor,
                  const float2* tw, float* scratch, float* out);
 void gist_release(void* state);                 // gist.cpp: frees a context's GIST tables and scratch (pr_destroy, streams idle)
-// pr_api.cpp: what gist.cpp needs of a context
+// bow_gen.hip — TemplatedVocabulary::transform (TemplatedVocabulary.h:1127-1260) over a vocabulary tree in BFS order: node b's children
+// are child[b].x .. child[b].x + child[b].y - 1 (contiguous, file order), desc [nodes][32 B], word / weight of each node.
+//   launch_bow_descend: feature f of n_desc -> node[f] (the childless node its descent ends on), lanes per feature 1..16 (a power of 2);
+//                       feat_words (or null) [f] = word[node[f]]
+//   launch_bow_aggregate: per image (offs clamped into [0, n_desc]) the BowVector of the reference's order, written as ids / values rows
+//                       of out [2N][cols]; n_words (or null) [i] = distinct words; flags[0] = 1 when one has more than cols.
+//   scratch: wgt [n_desc] f64 (set by aggregate's fill), vals [n_desc] f64, gkeys [2 n_desc] u64 (images of more than BOW_LDS_KEYS descriptors).
+constexpr int BOW_LDS_KEYS = 8192;
+void launch_bow_descend(hipStream_t st, const uint8_t* desc, int64_t n_desc, const uint4* vdesc, const int2* child, const int* word,
+                        int lanes, int* node, int* feat_words);
+void launch_bow_aggregate(hipStream_t st, const int64_t* offs, int N, int64_t n_desc, const int* node, const int* word, const double* weight,
+                          int weighting, int scoring, int cols, double* wgt, double* vals, unsigned long long* gkeys, double* out,
+                          int* n_words, int* flags);   // node null: a vocabulary without words, every row empty
+void launch_bow_fill_words(hipStream_t st, int* feat_words, int64_t n, int v);
+void bow_release(void* state);                  // bow.cpp: frees a context's device vocabularies and scratch (pr_destroy, streams idle)
+// pr_api.cpp: what gist.cpp and bow.cpp need of a context
 hipStream_t ctx_stream(pr_ctx* ctx);
 int ctx_device(pr_ctx* ctx);
 void ctx_set_error(pr_ctx* ctx, const char* msg);
 void*& ctx_gist(pr_ctx* ctx);
+void*& ctx_bow(pr_ctx* ctx);
+int* ctx_bow_flag(pr_ctx* ctx);                 // [1] device word: a BoW row was truncated (PR_WARN_BOW_TRUNCATED at pr_take_warnings)
 
 // prestage.hip — utils/pts_preprocess.h:135-232 on the GPU (see the file header); all pointers are device pointers
 int64_t prestage_cells(double range, int polar);          // dense cell-table length per pose

@@ -37,7 +37,7 @@ struct pr_ctx {
   hipEvent_t ev_m2[4] = {nullptr, nullptr, nullptr, nullptr};   // M2DP generation: two batches in flight (binning | singular pairs), launch_m2dp_bin_svd
   std::string err;
   int* d_svd_rows = nullptr;     // [1 + M2DP_SVD_ROWS_CAP] rows of the last pr_m2dp_generate* call whose leading singular pair did not converge
-  int* d_flags = nullptr;        // [4] deferred bits: [0] zero-norm row at pack time, [1] M2DP singular pair not converged, [2] a query was answered with fp64 row statistics, [3] more flagged queries than one stream-ordered pass resolves
+  int* d_flags = nullptr;        // [4] deferred bits: [0] zero-norm row at pack time, [1] M2DP singular pair not converged, [2] a query was answered with fp64 row statistics, [3] more flagged queries than one stream-ordered pass resolves; [5] a BoW row was truncated
   bool sc_online_h = false;      // PR_SC_ONLINE=h: calls of up to 8 queries through sc_match_h.hip's one-group form (the default until round 5)
   double* d_twiddle = nullptr;   // cos[60], sin[60] of 2*pi*t/60
   float* d_cst = nullptr;        // SC stage-2 constants [31][2][64]
@@ -70,6 +70,7 @@ struct pr_ctx {
   hipEvent_t ev_t[4] = {nullptr, nullptr, nullptr, nullptr};
   int timing_valid = 0;          // 0: nothing recorded; 1: ev_t[0], ev_t[3] only (one launch); 3: all four (channel 0 | channel 1 split | channel 1 single)
   void* gist = nullptr;          // GIST filter tables per parameter set and grow-only scratch (gist.cpp)
+  void* bow = nullptr;           // BoW device vocabularies and grow-only scratch (bow.cpp)
 };
 
 struct pr_sigset {
@@ -170,10 +171,14 @@ size_t sigset_floats(int type, int role, int32_t max_sigs, int* groups, int sc_m
 }
 
 int check_flags(pr_ctx* ctx) {
-  int h[4];
+  int h[6];                      // h[4] is not a deferred bit (ScBin::viol) and stays as it is
   PR_HIP(ctx, hipMemcpyAsync(h, ctx->d_flags, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
   PR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (h[0] || h[1] || h[2] || h[3]) PR_HIP(ctx, hipMemsetAsync(ctx->d_flags, 0, sizeof h, ctx->stream));
+  if (h[0] || h[1] || h[2] || h[3]) PR_HIP(ctx, hipMemsetAsync(ctx->d_flags, 0, 4 * sizeof(int), ctx->stream));
+  if (h[5]) {
+    PR_HIP(ctx, hipMemsetAsync(ctx->d_flags + 5, 0, sizeof(int), ctx->stream));
+    ctx->warnings |= PR_WARN_BOW_TRUNCATED;
+  }
   if (h[1]) ctx->warnings |= PR_WARN_M2DP_SVD;
   if (h[2]) ctx->warnings |= PR_WARN_ORDER_RESOLVED;
   if (h[3]) ctx->warnings |= PR_WARN_ORDER_UNRESOLVED;
@@ -370,6 +375,7 @@ void pr_destroy(pr_ctx* ctx) {
   if (ctx->d_cst_h) (void)hipFree(ctx->d_cst_h);
   if (ctx->d_planes) (void)hipFree(ctx->d_planes);
   pr::gist_release(ctx->gist);
+  pr::bow_release(ctx->bow);
   delete ctx;
 }
 
@@ -2024,10 +2030,12 @@ int pr_sc_relative_pose(const double* frames_q, const double* frames_db, const i
 
 }  // extern "C"
 
-// what gist.cpp needs of a context (pr_ctx is private to this file)
+// what gist.cpp and bow.cpp need of a context (pr_ctx is private to this file)
 namespace pr {
 hipStream_t ctx_stream(pr_ctx* ctx) { return ctx->stream; }
 int ctx_device(pr_ctx* ctx) { return ctx->device; }
 void ctx_set_error(pr_ctx* ctx, const char* msg) { if (ctx) ctx->err = msg; else g_err = msg; }
 void*& ctx_gist(pr_ctx* ctx) { return ctx->gist; }
+void*& ctx_bow(pr_ctx* ctx) { return ctx->bow; }
+int* ctx_bow_flag(pr_ctx* ctx) { return ctx->d_flags + 5; }
 }  // namespace pr

@@ -336,3 +336,63 @@ def drive_clouds_torch(frames=2000, per_cloud=6000, seed=5, stops=(), device="cu
         xyz.append(cam); inten.append(it.to(torch.float32)); offs.append(offs[-1] + cam.shape[0])
     res = (torch.cat(xyz).cpu().numpy(), torch.cat(inten).cpu().numpy(), np.array(offs, np.int64), lap)
     return res + (np.array(poss),) if positions else res
+
+
+# ----------------------------------------------------------------------------- BoW vocabularies and ORB descriptor sets
+def _flip_bits(rng, desc, p):
+    """desc uint8 [n, 32] with each of its 256 bits flipped with probability p."""
+    out = np.empty_like(desc)
+    for c0 in range(0, desc.shape[0], 1 << 16):
+        d = desc[c0:c0 + (1 << 16)]
+        flips = rng.random((d.shape[0], 256)) < p
+        out[c0:c0 + d.shape[0]] = d ^ np.packbits(flips, axis=1)
+    return out
+
+
+def bow_vocabulary(seed: int, k: int = 10, L: int = 6, stop_frac: float = 0.0):
+    """A complete k-ary DBoW2 tree of depth L as node arrays (parent, is_leaf, desc, weight) for api.ORBVocabulary.from_arrays: node 0 is
+    the root, nodes in level order (sum of k^l nodes, 1 111 111 for k = 10, L = 6).  A child's descriptor is its parent's with each bit
+    flipped with probability 0.5^l at level l (random at level 1), so a descriptor near a leaf descends to that leaf.  Leaves are the
+    words, weights (idf-like) uniform in [0.5, 5), a `stop_frac` share of them 0 (stopped words); inner nodes weigh 0."""
+    rng = np.random.default_rng(seed)
+    sizes = [k ** l for l in range(L + 1)]
+    n = sum(sizes)
+    parent = np.full(n, -1, np.int32)
+    desc = np.zeros((n, 32), np.uint8)
+    desc[0] = rng.integers(0, 256, 32, dtype=np.uint8)
+    start = 0
+    for l in range(1, L + 1):
+        p0, c0 = start, start + sizes[l - 1]
+        idx = np.arange(sizes[l])
+        parent[c0:c0 + sizes[l]] = p0 + idx // k
+        desc[c0:c0 + sizes[l]] = _flip_bits(rng, desc[p0 + idx // k], 0.5 ** l)
+        start = c0
+    is_leaf = np.zeros(n, np.uint8)
+    is_leaf[start:] = 1
+    weight = np.zeros(n, np.float64)
+    weight[start:] = rng.uniform(0.5, 5.0, sizes[L])
+    weight[start:][rng.random(sizes[L]) < stop_frac] = 0.0
+    return parent, is_leaf, desc, weight
+
+
+def bow_drive(seed: int, anchors, n_first: int, revisits, per_image: int = 300, share: float = 0.8, flips: float = 0.01):
+    """ORB descriptor sets of a drive: frames 0 .. n_first-1 see distinct places, then frame n_first + j revisits the place of frame
+    revisits[j].  A place holds per_image descriptors near random rows of `anchors` (uint8 [A, 32], e.g. a vocabulary's leaves); a frame
+    shows each with bit-flip probability `flips`, and a revisit keeps `share` of them (a random subset) and adds fresh ones.
+    Returns (desc uint8 [F, 32], offs int64 [N + 1], planted int64 [N]: the first visit of a revisit frame, -1 for the others)."""
+    rng = np.random.default_rng(seed)
+    anchors = np.asarray(anchors, np.uint8)
+    pools = [_flip_bits(rng, anchors[rng.integers(0, len(anchors), per_image)], 0.02) for _ in range(n_first)]
+    frames, planted = [], []
+    for f in range(n_first):
+        frames.append(_flip_bits(rng, pools[f], flips))
+        planted.append(-1)
+    for r in revisits:
+        keep = rng.permutation(per_image)[:int(round(share * per_image))]
+        fresh = _flip_bits(rng, anchors[rng.integers(0, len(anchors), per_image - len(keep))], 0.02)
+        d = np.concatenate([_flip_bits(rng, pools[r][keep], flips), fresh])
+        frames.append(d[rng.permutation(len(d))])
+        planted.append(int(r))
+    offs = np.zeros(len(frames) + 1, np.int64)
+    offs[1:] = np.cumsum([len(d) for d in frames])
+    return np.concatenate(frames), offs, np.array(planted, np.int64)

@@ -4,7 +4,8 @@
 # (poses_history_file, pts_history_file, <method>_file, incoming_id_file, lidarRange = 45.0) under
 # <results>/<dataset>/<seq>/.  The reference's gist.launch / bow.launch lines (image descriptors) read a ROS bag and are not run here:
 # bin/test_gist is the GIST generator's drop-in, fed by a list of PGM frames (_images:=) instead of the bag;
-# there is no BoW generator.  Both matchers are in match_signatures --type gist|bow.
+# bin/test_bow is the BoW generator's, fed by a list of ORB descriptor files (_descriptors:=).  Both matchers are in
+# match_signatures --type gist|bow.
 #
 # usage: tools/test.bash [results_dir] [extra test_<method> arguments, e.g. _device:=1 or _gpu_prestage:=0]
 #   results_dir defaults to ./results (the layout of place_recognition/results in the reference)
