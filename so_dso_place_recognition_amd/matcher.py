@@ -47,13 +47,17 @@ def _dptr(t: torch.Tensor | None):
     return C.c_void_p(t.data_ptr())
 
 
-def _dptr_mom(mt, sc: bool):
-    """The combined moments tensor of a Matcher as the (mom_sc | mom_m2) argument it belongs to (the other one is None)."""
-    return mt._mom_all if (mt.type == _lib.TYPE_SC) == sc else None
-
-
 def _torch_dt(t: torch.Tensor) -> int:
     return {torch.float64: _lib.F64, torch.float32: _lib.F32}[t.dtype]
+
+
+def _raw_rows(d) -> tuple:
+    """(queries, DB, dtype) of a descriptor store: the raw rows of its last local_phase1() / its DB shard (the fp64 kernels read them)."""
+    assert d._q_sig.dtype == d.db_sig.dtype
+    return _dptr(d._q_sig), _dptr(d.db_sig), _torch_dt(d.db_sig)
+
+
+_NO_ROWS = (None, None, 0)
 
 
 def _stream_context(device: int, **kw) -> Context:
@@ -61,8 +65,18 @@ def _stream_context(device: int, **kw) -> Context:
     return Context(device, stream=int(torch.cuda.current_stream(device).cuda_stream), **kw)
 
 
+RESOLVE_SLOTS = 64      # flagged queries one pass of the exact-row resolution serves (kernels.hpp)
+
+
 class _Base:
+    """The device-resident protocol, written once over the matcher's descriptor stores `descs`: (self,) for a Matcher, (sc, m2) for a
+    FusedMatcher.  Every store holds its raw rows (_q_sig, db_sig), its distance matrices (_bufs) and, after local_select(), its part of
+    the moments of all shards (_mom [G, m, 2, 3]); the matcher itself holds _m / n (queries of the last local_phase1(), DB rows of this
+    shard) and, in its own _bufs, the call's candidate lists and results."""
     resolved = None       # queries the last single-shard match() of more than 64 queries answered from their exact rows (it reads the count back)
+    plain = False         # True for DELIGHT (Matcher): one distance matrix, no z-score fusion
+    _raw = None           # the capacity-sized raw DB of reserve_database()
+    _twin = None          # the split-f16 twin of the f16 arithmetic (_split_twin)
 
     def _init_ctx(self, ctx, device):
         if device is None:
@@ -71,6 +85,13 @@ class _Base:
         self.dev = torch.device("cuda", self.ctx.device)
         self.lib = self.ctx.lib
         self._lib_stream = None if self.ctx.stream == 0 else torch.cuda.ExternalStream(self.ctx.stream, device=self.dev)
+        self._bufs = {}
+        self._flat = {}
+
+    def close(self):
+        if self._twin is not None:
+            self._twin.close()
+            self._twin = None
 
     # The library's kernels run on self.ctx.stream; torch work (casts, zero_(), all_gather_into_tensor, output allocations) runs on torch's
     # CURRENT stream, which may differ from the one the context was created on (`with torch.cuda.stream(s)`, DDP side streams).  The two
@@ -94,6 +115,42 @@ class _Base:
         else:
             self.ctx.sync()
 
+    def _buf(self, name, shape, dtype):
+        """The call's working tensors, kept between calls.  A shape that grows a little per call (a DB that gains a row per keyframe: the
+        [m, n] distance matrices) is served as a view of flat storage with an eighth of headroom instead of a new allocation per call."""
+        t = self._bufs.get(name)
+        if t is None or tuple(t.shape) != tuple(shape) or t.dtype != dtype:
+            need = 1
+            for d in shape:
+                need *= int(d)
+            flat = self._flat.get(name)
+            if flat is None or flat.dtype != dtype or flat.numel() < need:
+                flat = torch.empty(need + (need >> 3 if self._raw is not None else 0), dtype=dtype, device=self.dev)
+                self._flat[name] = flat
+            t = flat[:need].view(shape)
+            self._bufs[name] = t
+        return t
+
+    # ---- the library's argument slots (the C++ Types::dev): one SC and one M2DP slot, None / (None, None, 0) for a type the matcher lacks
+    def _slots(self):
+        sc = m2 = None
+        for d in self.descs:
+            if d.type == _lib.TYPE_SC:
+                sc = d
+            elif d.type == _lib.TYPE_M2DP:
+                m2 = d
+        return sc, m2
+
+    def _raw6(self) -> tuple:
+        """(q_sc, db_sc, dt_sc, q_m2, db_m2, dt_m2)"""
+        sc, m2 = self._slots()
+        return (*(_NO_ROWS if sc is None else _raw_rows(sc)), *(_NO_ROWS if m2 is None else _raw_rows(m2)))
+
+    def _moms(self) -> tuple:
+        """(mom_sc, mom_m2): the moments of all shards the last local_select() was given."""
+        sc, m2 = self._slots()
+        return None if sc is None else sc._mom, None if m2 is None else m2._mom
+
     # ---- PR_SC_ARITH_F16 (single f16 product per term): exact indices need a margin check of the candidate list and, for the
     # queries that fail it, a second pass in split-f16 (include/place_recognition.h)
     @property
@@ -111,35 +168,6 @@ class _Base:
         self._leave()
         self.f16_flags, self.f16_count = flags, count
         return flags, count
-
-    def _resolve_order(self, raw6, mom_sc, mom_m2, m, n, q_row0, mask_width, p_weight, k, idx, score, exact_order=True):
-        """After a single-shard pr_rerank_dev: queries whose re-evaluated order hangs on the fp32 pass's sigmas, or whose candidate list does
-        not provably hold the top-k, are answered from their exact fp64 rows; idx / score (and the moments rows) are patched in place.
-        One pass takes RESOLVE_SLOTS flagged queries.  Calls of up to that many queries (and exact_order == "async"): pr_order_resolve_async_dev,
-        ceil(m / 64) stream-ordered passes without host synchronisation - all flagged queries, empty passes leave at once
-        (PR_WARN_ORDER_RESOLVED at ctx.take_warnings() tells whether it happened).  Larger calls: pr_order_resolve_dev - reads the number of
-        flagged queries back (ONE synchronisation of the stream per call) and runs as many passes as it takes."""
-        self._enter()
-        if m <= RESOLVE_SLOTS or exact_order == "async":
-            self.ctx.check(self.lib.pr_order_resolve_async_dev(self.ctx.h, *raw6, _dptr(mom_sc), _dptr(mom_m2), m, n, int(q_row0), int(mask_width),
-                                                               float(p_weight), int(k), _dptr(idx), _dptr(score)))
-        else:
-            cnt = C.c_int32(0)
-            self.ctx.check(self.lib.pr_order_resolve_dev(self.ctx.h, *raw6, _dptr(mom_sc), _dptr(mom_m2), m, n, int(q_row0), int(mask_width),
-                                                         float(p_weight), int(k), _dptr(idx), _dptr(score), C.byref(cnt)))
-            self.resolved = int(cnt.value)
-        self._leave()
-
-    def _exact_passes(self, m, exact_order=True):
-        """Passes of RESOLVE_SLOTS flagged queries step 7 of the sharded protocol needs (the same number on every rank: the flags are a
-        function of the gathered evaluations).  Up to RESOLVE_SLOTS queries: one, unconditionally and without synchronisation; exact_order ==
-        "async" (a captured graph): ceil(m / 64), every one of them with its two all-gathers, whatever was flagged - empty passes leave at once;
-        otherwise the flagged count is read back (one synchronisation) - none flagged, no pass and no all-gather."""
-        if m <= RESOLVE_SLOTS:
-            return 1
-        if exact_order == "async":
-            return (m + RESOLVE_SLOTS - 1) // RESOLVE_SLOTS
-        return (self.flagged_count() + RESOLVE_SLOTS - 1) // RESOLVE_SLOTS
 
     def _fallback_rows(self, run_rows, idx, score, mask_width, q_row0):
         """Recomputes the flagged queries through `run_rows(rows tensor, q_row0 or None)` (a split-f16 matcher over the same DB) and
@@ -159,6 +187,239 @@ class _Base:
                 idx[r], score[r] = i2[0], s2[0]
         return idx, score
 
+    def _split_twin(self):
+        """The same matcher in split-f16 over the same (already resident) raw DB, created and packed on first use."""
+        db = self.descs[0].db_sig
+        if self._twin is None or self._twin_of is not db:
+            if self._twin is not None:
+                self._twin.close()
+            tw = type(self)(*self._spec, ctx=Context(self.ctx.device, sc_arith="f16x2", stream=self.ctx.stream))
+            tw.pack_database(*(d.db_sig for d in self.descs))
+            self._twin, self._twin_of = tw, db
+        return self._twin
+
+    # ---- the protocol (module docstring): phase 1 is the subclass's, everything after it is written here once
+    def local_select(self, mom_all: torch.Tensor, G: int, mask_width, p_weight, k, db_row0, q_row0):
+        """fp32 selection of this shard's k + 8 best with the moments of all shards -> (idx_in i32 [m,kin], score f64 [m,kin])."""
+        m, n = self._m, self.n
+        stores = self.descs
+        if len(stores) == 1:          # one descriptor type: its moments [G, m, 2, 3] as they are
+            stores[0]._mom = mom_all.contiguous()
+            select = self.lib.pr_fuse_select_f64_dev
+        else:                         # SC + M2DP: [G, m, 4, 3] split per type
+            for d, t in zip(stores, mom_all.reshape(G, m, 4, 3).split(2, dim=2)):
+                d._mom = t.contiguous()
+            select = self.lib.pr_fuse_select2_f64_dev
+        self._args = (G, q_row0, db_row0, int(mask_width), float(p_weight))
+        kin = k if self.plain else int(self.lib.pr_rerank_width(self.ctx.h, int(k)))
+        idx_in = self._buf("idx_in", (m, kin), torch.int32)
+        sc32 = self._buf("sc32", (m, kin), torch.float32)
+        sc64 = self._buf("sc64", (m, kin), torch.float64)
+        dists = [_dptr(t) for d in stores for t in (d._bufs["d_p"], d._bufs.get("d_i"))]
+        self._enter()
+        self.ctx.check(select(self.ctx.h, *dists, m, n, *[_dptr(d._mom) for d in stores], G, q_row0, db_row0, int(mask_width), float(p_weight),
+                              int(kin), _dptr(idx_in), _dptr(sc32), _dptr(sc64)))
+        self._leave()
+        return idx_in, sc64
+
+    def local_rerank(self, cand_idx: torch.Tensor, k: int, partial: bool, cand_sc: torch.Tensor = None):
+        """fp64 re-evaluation of the candidates [m,kin]: partial=False -> (idx [m,k], score [m,k]) (all candidates are this
+        shard's: the one-rank path); partial=True -> scores [m,kin], NaN for candidates outside this shard.  cand_sc: the
+        candidates' fp32-pass scores as f64 [m,kin] (ascending) - candidates that cannot reach the top-k are then not evaluated."""
+        m, n = self._m, self.n
+        G, q_row0, db_row0, mask_width, p_weight = self._args
+        kin = cand_idx.shape[1]
+        cand_idx = cand_idx.contiguous()
+        cand_sc = None if cand_sc is None else cand_sc.contiguous()
+        self._last_cand = (cand_idx, cand_sc)
+        rows = (*self._raw6(), *map(_dptr, self._moms()))
+        self._enter()
+        if partial:
+            part = self._buf("part", (m, 5, kin), torch.float64)           # the shard's p5 block (include/place_recognition.h)
+            self.ctx.check(self.lib.pr_rerank_partial_dev(self.ctx.h, *rows, m, n, G, q_row0, db_row0, mask_width, p_weight, kin, _dptr(cand_idx),
+                                                          _dptr(cand_sc), int(k), _dptr(part)))
+            self._leave()
+            return part
+        idx = self._buf("idx", (m, k), torch.int32)
+        score = self._buf("score", (m, k), torch.float64)
+        self.ctx.check(self.lib.pr_rerank_dev(self.ctx.h, *rows, m, n, G, q_row0, db_row0, mask_width, p_weight, kin, _dptr(cand_idx),
+                                              _dptr(cand_sc), int(k), _dptr(idx), _dptr(score)))
+        self._leave()
+        return idx, score
+
+    def local_phase2(self, mom_all: torch.Tensor, G: int, mask_width, p_weight, k, db_row0, q_row0):
+        """Selection + re-evaluation of this shard alone -> its own top-k (what rank g would answer by itself)."""
+        idx_in, sc = self.local_select(mom_all, G, mask_width, p_weight, k, db_row0, q_row0)
+        if self.plain:
+            return idx_in, sc
+        return self.local_rerank(idx_in, k, partial=False, cand_sc=sc)
+
+    def merge(self, idx_all: torch.Tensor, sc_all: torch.Tensor, k: int):
+        """pr_merge_topk_dev on [G, m, k] device tensors."""
+        G, m, kk = idx_all.shape
+        assert kk == k
+        idx = torch.empty((m, k), dtype=torch.int32, device=idx_all.device)
+        score = torch.empty((m, k), dtype=torch.float64, device=idx_all.device)
+        self._enter()
+        self.ctx.check(self.lib.pr_merge_topk_dev(self.ctx.h, _dptr(idx_all.contiguous()), _dptr(sc_all.contiguous()), G, m, k, _dptr(idx),
+                                                  _dptr(score)))
+        self._leave()
+        return idx, score
+
+    def finish(self, cand_idx: torch.Tensor, cand_sc: torch.Tensor | None, part_all: torch.Tensor, k: int):
+        """pr_rerank_finish_dev: candidates [m, kin] (+ their merged pass scores) + the shards' p5 blocks [G, m, 5, kin] -> (idx [m,k], score [m,k]);
+        the order and containment checks of the result (under the statistics of the last local_select()) stay in the context:
+        pr_f16_margin_dev (PR_SC_ARITH_F16) or exact_moments() / exact_select() / exact_merge() take them."""
+        G, m, five, kin = part_all.shape
+        assert five == 5
+        idx = torch.empty((m, k), dtype=torch.int32, device=cand_idx.device)
+        score = torch.empty((m, k), dtype=torch.float64, device=cand_idx.device)
+        cand_idx = cand_idx.contiguous()
+        cand_sc = None if cand_sc is None else cand_sc.contiguous()
+        part_all = part_all.contiguous()
+        self._enter()
+        self.ctx.check(self.lib.pr_rerank_finish_dev(self.ctx.h, *map(_dptr, self._moms()), int(self._args[0]), _dptr(cand_idx), _dptr(cand_sc),
+                                                     _dptr(part_all), G, m, kin, k, float(self._args[4]), _dptr(idx), _dptr(score)))
+        self._leave()
+        return idx, score
+
+    def exact_moments(self, offset: int = 0, last: bool = True):
+        """Step 7, first local part: this shard's exact rows of flagged queries offset .. offset + 63 of the last finish() (kept in the
+        context) and their moments -> [m, 4, 3] f64.  last: no pass follows (flagged queries behind it raise WARN_ORDER_UNRESOLVED)."""
+        m, n = self._m, self.n
+        raw6 = self._raw6()
+        exact = torch.empty((m, 4, 3), dtype=torch.float64, device=self.dev)
+        self._enter()
+        self.ctx.check(self.lib.pr_order_exact_moments_dev(self.ctx.h, *raw6, *map(_dptr, self._moms()), int(self._args[0]), m, n, int(offset),
+                                                           int(bool(last)), _dptr(exact)))
+        self._leave()
+        return exact
+
+    def exact_select(self, exact_all: torch.Tensor, k: int, offset: int = 0):
+        """Step 7, second local part: this shard's k best of the flagged queries' exact rows under the statistics of all shards
+        -> [64, 2, k] f64 (scores | global indices)."""
+        m, n = self._m, self.n
+        _, q_row0, db_row0, mask_width, p_weight = self._args
+        mom_sc, mom_m2 = self._moms()
+        G = exact_all.shape[0]
+        exact_all = exact_all.contiguous()
+        sel = torch.empty((RESOLVE_SLOTS, 2, k), dtype=torch.float64, device=self.dev)
+        self._enter()
+        self.ctx.check(self.lib.pr_order_exact_select_dev(self.ctx.h, _dptr(exact_all), G, m, n, int(q_row0), int(db_row0), int(mask_width),
+                                                          float(p_weight), int(mom_sc is not None), int(mom_m2 is not None), int(k), int(offset),
+                                                          _dptr(sel)))
+        self._leave()
+        return sel
+
+    def exact_merge(self, sel_all: torch.Tensor, k: int, idx: torch.Tensor, score: torch.Tensor, offset: int = 0):
+        G = sel_all.shape[0]
+        sel_all = sel_all.contiguous()
+        self._enter()
+        self.ctx.check(self.lib.pr_order_exact_merge_dev(self.ctx.h, _dptr(sel_all), G, self._m, int(k), int(offset), _dptr(idx), _dptr(score)))
+        self._leave()
+        return idx, score
+
+    def _exact_passes(self, exact_order=True):
+        """Passes of RESOLVE_SLOTS flagged queries step 7 of the sharded protocol needs (the same number on every rank: the flags are a
+        function of the gathered evaluations).  Up to RESOLVE_SLOTS queries: one, unconditionally and without synchronisation; exact_order ==
+        "async" (a captured graph): ceil(m / 64), every one of them with its two all-gathers, whatever was flagged - empty passes leave at once;
+        otherwise the flagged count is read back (one synchronisation) - none flagged, no pass and no all-gather."""
+        m = self._m
+        if m <= RESOLVE_SLOTS:
+            return 1
+        if exact_order == "async":
+            return (m + RESOLVE_SLOTS - 1) // RESOLVE_SLOTS
+        return (self.flagged_count() + RESOLVE_SLOTS - 1) // RESOLVE_SLOTS
+
+    def _resolve_order(self, k, idx, score, exact_order=True):
+        """After a single-shard pr_rerank_dev: queries whose re-evaluated order hangs on the fp32 pass's sigmas, or whose candidate list does
+        not provably hold the top-k, are answered from their exact fp64 rows; idx / score (and the moments rows) are patched in place.
+        One pass takes RESOLVE_SLOTS flagged queries.  Calls of up to that many queries (and exact_order == "async"): pr_order_resolve_async_dev,
+        ceil(m / 64) stream-ordered passes without host synchronisation - all flagged queries, empty passes leave at once
+        (PR_WARN_ORDER_RESOLVED at ctx.take_warnings() tells whether it happened).  Larger calls: pr_order_resolve_dev - reads the number of
+        flagged queries back (ONE synchronisation of the stream per call) and runs as many passes as it takes."""
+        m, n = self._m, self.n
+        _, q_row0, _, mask_width, p_weight = self._args
+        args = (self.ctx.h, *self._raw6(), *map(_dptr, self._moms()), m, n, int(q_row0), int(mask_width), float(p_weight), int(k), _dptr(idx),
+                _dptr(score))
+        self._enter()
+        if m <= RESOLVE_SLOTS or exact_order == "async":
+            self.ctx.check(self.lib.pr_order_resolve_async_dev(*args))
+        else:
+            cnt = C.c_int32(0)
+            self.ctx.check(self.lib.pr_order_resolve_dev(*args, C.byref(cnt)))
+            self.resolved = int(cnt.value)
+        self._leave()
+
+    def _match(self, queries: tuple, mask_width, p_weight, k, db_row0, q_row0, group, force_exchange, f16_fallback, exact_order, mark):
+        """match() with the query rows of every store (queries: one tensor per store, in the order of descs)."""
+        G = _world(group)
+        f16 = self.f16 and not self.plain
+        resolve = ((self.exact_moments, self.exact_select, self.exact_merge, lambda: self._exact_passes(exact_order))
+                   if (exact_order and not self.plain and not f16) else None)
+        post = (lambda cand_sc, idx, score: self._margin(*self._moms(), self._args[0], p_weight, cand_sc, k, score)) if f16 else None
+        idx, score = sharded_topk(lambda: self.local_phase1(*queries),
+                                  lambda mom_all, G_: self.local_select(mom_all, G_, mask_width, p_weight, k, db_row0, q_row0),
+                                  k, group if (G > 1 or force_exchange) else None, G, merge=self.merge, force_exchange=force_exchange,
+                                  rerank=None if self.plain else self.local_rerank, finish=self.finish, post=post, resolve=resolve, mark=mark)
+        if f16 and f16_fallback:
+            def run_rows(rows, qr0):
+                fb = self._split_twin()
+                qsel = [q.view(-1, d.rows_per_sig, d.sig_len)[rows].reshape(-1, d.sig_len).contiguous()   # M2DP: 4 rows per query
+                        for d, q in zip(self.descs, queries)]
+                return fb._match(qsel, mask_width, p_weight, k, db_row0, q_row0 if qr0 is None else qr0, group, force_exchange, True, exact_order,
+                                 None)
+            idx, score = self._fallback_rows(run_rows, idx, score, mask_width, q_row0)
+        elif resolve is not None and G == 1 and not force_exchange:
+            self._resolve_order(k, idx, score, exact_order)
+            if mark is not None:
+                mark("exact rows (one shard)")
+        return idx, score
+
+    def align(self, idx: torch.Tensor, db_row0: int = 0):
+        """The best-aligning variant of every pair (query of the last match(), DB row idx[q, j]) -> (variant int32 [m,k,2], dist float64
+        [m,k,2]) device tensors, per channel (SC: structure, intensity, v = 2 * shift + mirror; M2DP: count, intensity, v = 4 * query row +
+        DB row; DELIGHT: [..., 0] the octant permutation, [..., 1] = -1 / NaN), from the raw rows in fp64 (pr_align_pairs_dev /
+        pr_delight_align_pairs_dev: the variant arithmetic of the re-evaluation, whatever the matcher's arithmetic; a growing DB included).
+        A FusedMatcher returns [m,k,4]: SC structure, SC intensity, M2DP count, M2DP intensity.
+        idx: GLOBAL DB rows [m,k] as match() returns them; db_row0: the first global row of this matcher's shard.  Entries outside
+        [db_row0, db_row0 + n) come back -1 / NaN, so with the DB row-sharded exactly one shard fills each pair: combine the shards'
+        results with torch.maximum on the variants (torch.fmax on the distances).  Stream-ordered, no host synchronisation."""
+        assert all(d.db_sig is not None and d._q_sig is not None for d in self.descs), "match() first"
+        idx = idx.to(torch.int32).contiguous()
+        m, k = idx.shape
+        assert m == self._m
+        if self.plain:
+            raw = _raw_rows(self)
+            v1 = torch.empty((m, k), dtype=torch.int32, device=self.dev)
+            d1 = torch.empty((m, k), dtype=torch.float64, device=self.dev)
+            self._enter()
+            self.ctx.check(self.lib.pr_delight_align_pairs_dev(self.ctx.h, *raw, m, self.n, int(db_row0), k, _dptr(idx), _dptr(v1), _dptr(d1)))
+            self._leave()
+            return (torch.stack([v1, torch.full_like(v1, -1)], -1), torch.stack([d1, torch.full_like(d1, float("nan"))], -1))
+        raw6 = self._raw6()
+        var = torch.empty((m, k, 4), dtype=torch.int32, device=self.dev)
+        dist = torch.empty((m, k, 4), dtype=torch.float64, device=self.dev)
+        self._enter()
+        self.ctx.check(self.lib.pr_align_pairs_dev(self.ctx.h, *raw6, m, self.n, int(db_row0), k, _dptr(idx), _dptr(var), _dptr(dist)))
+        self._leave()
+        ch = slice(0 if raw6[0] is not None else 2, 4 if raw6[3] is not None else 2)     # the channels of the matcher's descriptor types
+        return var[..., ch], dist[..., ch]
+
+    def flagged_count(self) -> int:
+        """Queries the last match(..., exact_order=False) of ONE rank left flagged by the order / containment checks (the ones the default
+        match() answers from their exact rows).  Synchronises (pr_order_flagged_count); 0 once a resolving call has taken the flags."""
+        cnt = C.c_int32(0)
+        self._enter()
+        self.ctx.check(self.lib.pr_order_flagged_count(self.ctx.h, int(self._m), C.byref(cnt)))
+        self._leave()
+        return int(cnt.value)
+
+    def take_warnings(self) -> int:
+        """PR_WARN_* bits of the context since the last call (synchronises its stream): WARN_ORDER_RESOLVED after a match() whose order
+        needed fp64 row statistics (WARN_ORDER_UNRESOLVED: only when exact_moments(.., last=True) was called with flagged queries left)."""
+        return self.ctx.take_warnings()
+
 
 class Matcher(_Base):
     def __init__(self, type_: str, max_queries: int, max_db: int, ctx: Context | None = None, device: int | None = None):
@@ -166,7 +427,7 @@ class Matcher(_Base):
         self.rows_per_sig, self.sig_len = {_lib.TYPE_SC: (1, 2400), _lib.TYPE_M2DP: (4, 384), _lib.TYPE_DELIGHT: (16, 256)}[self.type]
         self.plain = self.type == _lib.TYPE_DELIGHT      # one distance matrix, no z-score fusion (run_test.m:26-36)
         self._init_ctx(ctx, device)
-        self._max_q, self._max_db = max_queries, max_db
+        self._spec = (type_, max_queries, max_db)
         self.q = C.c_void_p()
         self.db = C.c_void_p()
         self.ctx.check(self.lib.pr_sigset_create(self.ctx.h, self.type, _lib.ROLE_QUERY, max_queries, C.byref(self.q)))
@@ -174,35 +435,20 @@ class Matcher(_Base):
         self.max_queries, self.max_db = max_queries, max_db
         self.n = 0
         self.db_sig = None             # the raw DB shard (the fp64 re-evaluation reads it)
-        self._bufs = {}
-        self._flat = {}
+        self._q_sig = None             # the raw queries of the last local_phase1()
         self.pre_distances = None      # optional callables (e.g. HIP event records) around the distance launch
         self.post_distances = None
 
+    @property
+    def descs(self):                   # (a property: an attribute holding self would make every matcher a reference cycle)
+        return (self,)
+
     def close(self):
-        if getattr(self, "_twin", None) is not None:
-            self._twin.close()
-            self._twin = None
+        super().close()
         if self.q:
             self.lib.pr_sigset_destroy(self.ctx.h, self.q)
             self.lib.pr_sigset_destroy(self.ctx.h, self.db)
             self.q = self.db = None
-
-    def _buf(self, name, shape, dtype):
-        """The call's working tensors, kept between calls.  A shape that grows a little per call (a DB that gains a row per keyframe: the
-        [m, n] distance matrices) is served as a view of flat storage with an eighth of headroom instead of a new allocation per call."""
-        t = self._bufs.get(name)
-        if t is None or tuple(t.shape) != tuple(shape) or t.dtype != dtype:
-            need = 1
-            for d in shape:
-                need *= int(d)
-            flat = self._flat.get(name)
-            if flat is None or flat.dtype != dtype or flat.numel() < need:
-                flat = torch.empty(need + (need >> 3 if getattr(self, "_raw", None) is not None else 0), dtype=dtype, device=self.dev)
-                self._flat[name] = flat
-            t = flat[:need].view(shape)
-            self._bufs[name] = t
-        return t
 
     def _pack(self, handle, sig: torch.Tensor):
         assert sig.is_cuda and sig.is_contiguous() and sig.dim() == 2 and sig.shape[1] == self.sig_len
@@ -226,7 +472,7 @@ class Matcher(_Base):
         assert self.type in (_lib.TYPE_SC, _lib.TYPE_M2DP)
         self._enter()
         self.ctx.check(self.lib.pr_sigset_reserve(self.ctx.h, self.db))
-        self._raw = torch.empty((self._max_db * self.rows_per_sig, self.sig_len), dtype=torch.float64, device=self.dev)
+        self._raw = torch.empty((self.max_db * self.rows_per_sig, self.sig_len), dtype=torch.float64, device=self.dev)
         self.n = 0
         if sig is not None and sig.shape[0]:
             assert sig.dtype == torch.float64
@@ -239,10 +485,10 @@ class Matcher(_Base):
     def append_database(self, sig: torch.Tensor):
         """Rows [n, n + n_new) of the growing DB: the raw rows into the matcher's buffer, their operand rows into the image
         (pr_sigset_append: one kernel, bit for bit what a pack of all rows would write there)."""
-        assert getattr(self, "_raw", None) is not None, "reserve_database() first"
+        assert self._raw is not None, "reserve_database() first"
         assert sig.is_cuda and sig.dim() == 2 and sig.shape[1] == self.sig_len and sig.dtype == torch.float64 and sig.shape[0] % self.rows_per_sig == 0
         k, r0 = sig.shape[0] // self.rows_per_sig, self.n * self.rows_per_sig
-        assert self.n + k <= self._max_db
+        assert self.n + k <= self.max_db
         dst = self._raw[r0:r0 + sig.shape[0]]
         dst.copy_(sig)
         self._enter()                                              # (the copy above is torch's: ordered in front of the library's kernel)
@@ -273,90 +519,6 @@ class Matcher(_Base):
             self._leave()
         return mom
 
-    def _kin(self, k):
-        return k if self.plain else int(self.lib.pr_rerank_width(self.ctx.h, int(k)))
-
-    def local_select(self, mom_all: torch.Tensor, G: int, mask_width, p_weight, k, db_row0, q_row0):
-        """fp32 selection of this shard's k + 8 best with the moments of all shards -> (idx_in i32 [m,kin], score f64 [m,kin])."""
-        m, n = self._m, self.n
-        d_p, d_i = self._bufs["d_p"], self._bufs.get("d_i")
-        kin = self._kin(k)
-        idx_in = self._buf("idx_in", (m, kin), torch.int32)
-        sc32 = self._buf("sc32", (m, kin), torch.float32)
-        sc64 = self._buf("sc64", (m, kin), torch.float64)
-        self._mom_all = mom_all.contiguous()
-        self._args = (G, q_row0, db_row0, int(mask_width), float(p_weight))
-        self._enter()
-        self.ctx.check(self.lib.pr_fuse_select_f64_dev(self.ctx.h, _dptr(d_p), None if self.plain else _dptr(d_i), m, n, _dptr(self._mom_all), G,
-                                                       q_row0, db_row0, int(mask_width), float(p_weight), int(kin), _dptr(idx_in), _dptr(sc32),
-                                                       _dptr(sc64)))
-        self._leave()
-        return idx_in, sc64
-
-    def _raw_args(self):
-        sc = self.type == _lib.TYPE_SC
-        assert self._q_sig.dtype == self.db_sig.dtype
-        raw = (_dptr(self._q_sig), _dptr(self.db_sig), _torch_dt(self.db_sig))
-        none = (None, None, 0)
-        return (*(raw if sc else none), *(none if sc else raw), _dptr(self._mom_all) if sc else None, None if sc else _dptr(self._mom_all))
-
-    def local_rerank(self, cand_idx: torch.Tensor, k: int, partial: bool, cand_sc: torch.Tensor = None):
-        """fp64 re-evaluation of the candidates [m,kin]: partial=False -> (idx [m,k], score [m,k]) (all candidates are this
-        shard's: the one-rank path); partial=True -> scores [m,kin], NaN for candidates outside this shard.  cand_sc: the
-        candidates' fp32-pass scores as f64 [m,kin] (ascending) - candidates that cannot reach the top-k are then not evaluated."""
-        m, n = self._m, self.n
-        G, q_row0, db_row0, mask_width, p_weight = self._args
-        kin = cand_idx.shape[1]
-        cand_idx = cand_idx.contiguous()
-        cand_sc = None if cand_sc is None else cand_sc.contiguous()
-        csc = None if cand_sc is None else _dptr(cand_sc)
-        self._last_cand = (cand_idx, cand_sc)
-        self._enter()
-        if partial:
-            part = self._buf("part", (m, 5, kin), torch.float64)           # the shard's p5 block (include/place_recognition.h)
-            self.ctx.check(self.lib.pr_rerank_partial_dev(self.ctx.h, *self._raw_args(), m, n, G, q_row0, db_row0, mask_width, p_weight, kin,
-                                                          _dptr(cand_idx), csc, int(k), _dptr(part)))
-            self._leave()
-            return part
-        idx = self._buf("idx", (m, k), torch.int32)
-        score = self._buf("score", (m, k), torch.float64)
-        self.ctx.check(self.lib.pr_rerank_dev(self.ctx.h, *self._raw_args(), m, n, G, q_row0, db_row0, mask_width, p_weight, kin,
-                                              _dptr(cand_idx), csc, int(k), _dptr(idx), _dptr(score)))
-        self._leave()
-        return idx, score
-
-    def _moms(self):
-        sc = self.type == _lib.TYPE_SC
-        return (self._mom_all if sc else None, None if sc else self._mom_all)
-
-    def finish(self, cand_idx: torch.Tensor, cand_sc: torch.Tensor, part_all: torch.Tensor, k: int):
-        return _finish_dev(self, cand_idx, cand_sc, part_all, k, (*self._moms(), self._args[0]), self._args[4])
-
-    def exact_moments(self, offset: int = 0, last: bool = True):
-        """Step 7, first local part: this shard's exact rows of flagged queries offset .. offset + 63 of the last finish() (kept in the
-        context) and their moments -> [m, 4, 3] f64.  last: no pass follows (flagged queries behind it raise WARN_ORDER_UNRESOLVED)."""
-        return _exact_moments_dev(self, self._raw_args()[:6], *self._moms(), self._args[0], self._m, self.n, offset, last)
-
-    def exact_select(self, exact_all: torch.Tensor, k: int, offset: int = 0):
-        """Step 7, second local part: this shard's k best of the flagged queries' exact rows under the statistics of all shards
-        -> [64, 2, k] f64 (scores | global indices)."""
-        sc = self.type == _lib.TYPE_SC
-        G, q_row0, db_row0, mask_width, p_weight = self._args
-        return _exact_select_dev(self, exact_all, self._m, self.n, q_row0, db_row0, mask_width, p_weight, sc, not sc, k, offset)
-
-    def exact_merge(self, sel_all: torch.Tensor, k: int, idx: torch.Tensor, score: torch.Tensor, offset: int = 0):
-        return _exact_merge_dev(self, sel_all, self._m, k, idx, score, offset)
-
-    def local_phase2(self, mom_all: torch.Tensor, G: int, mask_width, p_weight, k, db_row0, q_row0):
-        """Selection + re-evaluation of this shard alone -> its own top-k (what rank g would answer by itself)."""
-        idx_in, sc = self.local_select(mom_all, G, mask_width, p_weight, k, db_row0, q_row0)
-        if self.plain:
-            return idx_in, sc
-        return self.local_rerank(idx_in, k, partial=False, cand_sc=sc)
-
-    def merge(self, idx_all: torch.Tensor, sc_all: torch.Tensor, k: int):
-        return _merge_dev(self, idx_all, sc_all, k)
-
     def match(self, queries: torch.Tensor, mask_width: int = 0, p_weight: float = 2.0, k: int = 1,
               db_row0: int = 0, q_row0: int = 0, group=None, force_exchange: bool = False, f16_fallback: bool = True,
               exact_order: bool = True, mark=None):
@@ -369,85 +531,7 @@ class Matcher(_Base):
         number of flagged queries back (one synchronisation) and runs the passes it takes.  "async": ceil(m / 64) such passes chained on the
         stream whatever was flagged (no read-back: what a captured graph of a large call uses; empty passes leave at once);
         False skips the resolution (the answer of the re-evaluated candidate list; the flags are simply dropped)."""
-        G = _world(group)
-        f16 = self.f16 and not self.plain
-        resolve = ((self.exact_moments, self.exact_select, self.exact_merge, lambda: self._exact_passes(self._m, exact_order))
-                   if (exact_order and not self.plain and not f16) else None)
-        post = (lambda cand_sc, idx, score: self._margin(_dptr_mom(self, True), _dptr_mom(self, False), self._args[0], p_weight, cand_sc, k,
-                                                          score)) if f16 else None
-        idx, score = sharded_topk(lambda: self.local_phase1(queries),
-                                  lambda mom_all, G_: self.local_select(mom_all, G_, mask_width, p_weight, k, db_row0, q_row0),
-                                  k, group if (G > 1 or force_exchange) else None, G, merge=self.merge, force_exchange=force_exchange,
-                                  rerank=None if self.plain else self.local_rerank, finish=self.finish, post=post, resolve=resolve, mark=mark)
-        if f16 and f16_fallback:
-            def run_rows(rows, qr0):
-                fb = self._split_twin()
-                qsel = queries.view(-1, self.rows_per_sig, self.sig_len)[rows].reshape(-1, self.sig_len).contiguous()   # M2DP: 4 rows per query
-                return fb.match(qsel, mask_width, p_weight, k, db_row0, q_row0 if qr0 is None else qr0, group, force_exchange,
-                                exact_order=exact_order)
-            idx, score = self._fallback_rows(run_rows, idx, score, mask_width, q_row0)
-        elif resolve is not None and G == 1 and not force_exchange:
-            self._resolve_order(self._raw_args()[:6], *self._moms(), self._m, self.n, q_row0, mask_width, p_weight, k, idx, score, exact_order)
-            if mark is not None:
-                mark("exact rows (one shard)")
-        return idx, score
-
-    def align(self, idx: torch.Tensor, db_row0: int = 0):
-        """The best-aligning variant of every pair (query of the last match(), DB row idx[q, j]) -> (variant int32 [m,k,2], dist float64
-        [m,k,2]) device tensors, per channel (SC: structure, intensity, v = 2 * shift + mirror; M2DP: count, intensity, v = 4 * query row +
-        DB row; DELIGHT: [..., 0] the octant permutation, [..., 1] = -1 / NaN), from the raw rows in fp64 (pr_align_pairs_dev /
-        pr_delight_align_pairs_dev: the variant arithmetic of the re-evaluation, whatever the matcher's arithmetic; a growing DB included).
-        idx: GLOBAL DB rows [m,k] as match() returns them; db_row0: the first global row of this matcher's shard.  Entries outside
-        [db_row0, db_row0 + n) come back -1 / NaN, so with the DB row-sharded exactly one shard fills each pair: combine the shards'
-        results with torch.maximum on the variants (torch.fmax on the distances).  Stream-ordered, no host synchronisation."""
-        assert self.db_sig is not None and getattr(self, "_q_sig", None) is not None, "match() first"
-        assert self._q_sig.dtype == self.db_sig.dtype
-        idx = idx.to(torch.int32).contiguous()
-        m, k = idx.shape
-        assert m == self._m
-        raw = (_dptr(self._q_sig), _dptr(self.db_sig), _torch_dt(self.db_sig))
-        if self.plain:
-            v1 = torch.empty((m, k), dtype=torch.int32, device=self.dev)
-            d1 = torch.empty((m, k), dtype=torch.float64, device=self.dev)
-            self._enter()
-            self.ctx.check(self.lib.pr_delight_align_pairs_dev(self.ctx.h, *raw, m, self.n, int(db_row0), k, _dptr(idx), _dptr(v1), _dptr(d1)))
-            self._leave()
-            return (torch.stack([v1, torch.full_like(v1, -1)], -1), torch.stack([d1, torch.full_like(d1, float("nan"))], -1))
-        var = torch.empty((m, k, 4), dtype=torch.int32, device=self.dev)
-        dist = torch.empty((m, k, 4), dtype=torch.float64, device=self.dev)
-        sc = self.type == _lib.TYPE_SC
-        none = (None, None, 0)
-        self._enter()
-        self.ctx.check(self.lib.pr_align_pairs_dev(self.ctx.h, *(raw if sc else none), *(none if sc else raw), m, self.n, int(db_row0), k,
-                                                   _dptr(idx), _dptr(var), _dptr(dist)))
-        self._leave()
-        c0 = 0 if sc else 2
-        return var[..., c0:c0 + 2], dist[..., c0:c0 + 2]
-
-    def flagged_count(self) -> int:
-        """Queries the last match(..., exact_order=False) of ONE rank left flagged by the order / containment checks (the ones the default
-        match() answers from their exact rows).  Synchronises (pr_order_flagged_count); 0 once a resolving call has taken the flags."""
-        cnt = C.c_int32(0)
-        self._enter()
-        self.ctx.check(self.lib.pr_order_flagged_count(self.ctx.h, int(self._m if hasattr(self, "_m") else self.sc._m), C.byref(cnt)))
-        self._leave()
-        return int(cnt.value)
-
-    def take_warnings(self) -> int:
-        """PR_WARN_* bits of the context since the last call (synchronises its stream): WARN_ORDER_RESOLVED after a match() whose order
-        needed fp64 row statistics (WARN_ORDER_UNRESOLVED: only when exact_moments(.., last=True) was called with flagged queries left)."""
-        return self.ctx.take_warnings()
-
-    def _split_twin(self):
-        """The same matcher in split-f16 over the same (already resident) raw DB, created and packed on first use."""
-        if getattr(self, "_twin", None) is None or self._twin_of is not self.db_sig:
-            if getattr(self, "_twin", None) is not None:
-                self._twin.close()
-            tw = Matcher({_lib.TYPE_SC: "sc", _lib.TYPE_M2DP: "m2dp"}[self.type], self._max_q, self._max_db,
-                         ctx=Context(self.ctx.device, sc_arith="f16x2", stream=self.ctx.stream))
-            tw.pack_database(self.db_sig)
-            self._twin, self._twin_of = tw, self.db_sig
-        return self._twin
+        return self._match((queries,), mask_width, p_weight, k, db_row0, q_row0, group, force_exchange, f16_fallback, exact_order, mark)
 
     def distances(self):
         """The last distance matrices (device, float32 [m, n_local])."""
@@ -509,140 +593,30 @@ class FusedMatcher(_Base):
 
     def __init__(self, max_queries: int, max_db: int, ctx: Context | None = None, device: int | None = None):
         self._init_ctx(ctx, device)
+        self._spec = (max_queries, max_db)
         self.sc = Matcher("sc", max_queries, max_db, self.ctx)
         self.m2 = Matcher("m2dp", max_queries, max_db, self.ctx)
-        self._bufs = {}
-        self._flat = {}
-
-    _buf = Matcher._buf
+        self.descs = (self.sc, self.m2)
 
     def close(self):
-        if getattr(self, "_twin", None) is not None:
-            self._twin.close()
-            self._twin = None
+        super().close()
         self.sc.close(); self.m2.close()
 
     def pack_database(self, sc_sig: torch.Tensor, m2dp_sig: torch.Tensor):
         self.sc.pack_database(sc_sig); self.m2.pack_database(m2dp_sig)
         assert self.sc.n == self.m2.n, "the two databases must describe the same places"
+        self.n = self.sc.n
 
     def local_phase1(self, sc_queries, m2dp_queries):
         a = self.sc.local_phase1(sc_queries)
         b = self.m2.local_phase1(m2dp_queries)
         assert self.sc._m == self.m2._m
+        self._m = self.sc._m
         return torch.cat([a, b], dim=1)                                    # [m, 4, 3]
-
-    def local_select(self, mom_all, G, mask_width, p_weight, k, db_row0, q_row0):
-        m, n = self.sc._m, self.sc.n
-        lib, h = self.lib, self.ctx.h
-        mom_all = mom_all.reshape(G, m, 4, 3)
-        self._m1, self._m2 = mom_all[:, :, :2].contiguous(), mom_all[:, :, 2:].contiguous()
-        self._args = (G, q_row0, db_row0, int(mask_width), float(p_weight))
-        d = [self.sc._bufs["d_p"], self.sc._bufs["d_i"], self.m2._bufs["d_p"], self.m2._bufs["d_i"]]
-        kin = int(self.lib.pr_rerank_width(self.ctx.h, int(k)))
-        idx_in = self._buf("idx_in", (m, kin), torch.int32)
-        sc32 = self._buf("sc32", (m, kin), torch.float32)
-        sc64 = self._buf("sc64", (m, kin), torch.float64)
-        self._enter()
-        self.ctx.check(lib.pr_fuse_select2_f64_dev(h, _dptr(d[0]), _dptr(d[1]), _dptr(d[2]), _dptr(d[3]), m, n, _dptr(self._m1), _dptr(self._m2), G,
-                                                   q_row0, db_row0, int(mask_width), float(p_weight), int(kin), _dptr(idx_in), _dptr(sc32),
-                                                   _dptr(sc64)))
-        self._leave()
-        return idx_in, sc64
-
-    def local_rerank(self, cand_idx, k, partial, cand_sc=None):
-        m, n = self.sc._m, self.sc.n
-        G, q_row0, db_row0, mask_width, p_weight = self._args
-        kin = cand_idx.shape[1]
-        cand_idx = cand_idx.contiguous()
-        raw = (_dptr(self.sc._q_sig), _dptr(self.sc.db_sig), _torch_dt(self.sc.db_sig), _dptr(self.m2._q_sig), _dptr(self.m2.db_sig),
-               _torch_dt(self.m2.db_sig), _dptr(self._m1), _dptr(self._m2))
-        cand_sc = None if cand_sc is None else cand_sc.contiguous()
-        csc = None if cand_sc is None else _dptr(cand_sc)
-        self._last_cand = (cand_idx, cand_sc)
-        self._enter()
-        if partial:
-            part = self._buf("part", (m, 5, kin), torch.float64)
-            self.ctx.check(self.lib.pr_rerank_partial_dev(self.ctx.h, *raw, m, n, G, q_row0, db_row0, mask_width, p_weight, kin, _dptr(cand_idx),
-                                                          csc, int(k), _dptr(part)))
-            self._leave()
-            return part
-        idx = self._buf("idx", (m, k), torch.int32)
-        score = self._buf("score", (m, k), torch.float64)
-        self.ctx.check(self.lib.pr_rerank_dev(self.ctx.h, *raw, m, n, G, q_row0, db_row0, mask_width, p_weight, kin, _dptr(cand_idx), csc, int(k),
-                                              _dptr(idx), _dptr(score)))
-        self._leave()
-        return idx, score
-
-    def finish(self, cand_idx, cand_sc, part_all, k):
-        return _finish_dev(self, cand_idx, cand_sc, part_all, k, (self._m1, self._m2, self._args[0]), self._args[4])
-
-    def _raw6(self):
-        return (_dptr(self.sc._q_sig), _dptr(self.sc.db_sig), _torch_dt(self.sc.db_sig), _dptr(self.m2._q_sig), _dptr(self.m2.db_sig),
-                _torch_dt(self.m2.db_sig))
-
-    def exact_moments(self, offset=0, last=True):
-        return _exact_moments_dev(self, self._raw6(), self._m1, self._m2, self._args[0], self.sc._m, self.sc.n, offset, last)
-
-    def exact_select(self, exact_all, k, offset=0):
-        G, q_row0, db_row0, mask_width, p_weight = self._args
-        return _exact_select_dev(self, exact_all, self.sc._m, self.sc.n, q_row0, db_row0, mask_width, p_weight, True, True, k, offset)
-
-    def exact_merge(self, sel_all, k, idx, score, offset=0):
-        return _exact_merge_dev(self, sel_all, self.sc._m, k, idx, score, offset)
-
-    def local_phase2(self, mom_all, G, mask_width, p_weight, k, db_row0, q_row0):
-        idx_in, sc = self.local_select(mom_all, G, mask_width, p_weight, k, db_row0, q_row0)
-        return self.local_rerank(idx_in, k, partial=False, cand_sc=sc)
-
-    def merge(self, idx_all, sc_all, k):
-        return _merge_dev(self, idx_all, sc_all, k)
 
     def match(self, sc_queries: torch.Tensor, m2dp_queries: torch.Tensor, mask_width: int = 0, p_weight: float = 2.0, k: int = 1,
               db_row0: int = 0, q_row0: int = 0, group=None, f16_fallback: bool = True, exact_order: bool = True):
-        G = _world(group)
-        post = (lambda cand_sc, idx, score: self._margin(self._m1, self._m2, self._args[0], p_weight, cand_sc, k, score)) if self.f16 else None
-        resolve = ((self.exact_moments, self.exact_select, self.exact_merge, lambda: self._exact_passes(self.sc._m, exact_order))
-                   if (exact_order and not self.f16) else None)
-        idx, score = sharded_topk(lambda: self.local_phase1(sc_queries, m2dp_queries),
-                                  lambda mom_all, G_: self.local_select(mom_all, G_, mask_width, p_weight, k, db_row0, q_row0),
-                                  k, group if G > 1 else None, G, merge=self.merge, rerank=self.local_rerank, finish=self.finish, post=post,
-                                  resolve=resolve)
-        if self.f16 and f16_fallback:
-            def run_rows(rows, qr0):
-                fb = self._split_twin()
-                return fb.match(sc_queries[rows].contiguous(), m2dp_queries.view(-1, 4, 384)[rows].reshape(-1, 384).contiguous(), mask_width,
-                                p_weight, k, db_row0, q_row0 if qr0 is None else qr0, group, exact_order=exact_order)
-            idx, score = self._fallback_rows(run_rows, idx, score, mask_width, q_row0)
-        elif resolve is not None and G == 1:
-            self._resolve_order(self._raw6(), self._m1, self._m2, self.sc._m, self.sc.n, q_row0, mask_width, p_weight, k, idx, score, exact_order)
-        return idx, score
-
-    def align(self, idx: torch.Tensor, db_row0: int = 0):
-        """Matcher.align for the pairs of the last match() -> (variant int32 [m,k,4], dist float64 [m,k,4]): SC structure, SC intensity,
-        M2DP count, M2DP intensity (pr_align_pairs_dev with both descriptor types).  Sharding as Matcher.align."""
-        assert self.sc.db_sig is not None and getattr(self.sc, "_q_sig", None) is not None, "match() first"
-        idx = idx.to(torch.int32).contiguous()
-        m, k = idx.shape
-        assert m == self.sc._m
-        var = torch.empty((m, k, 4), dtype=torch.int32, device=self.dev)
-        dist = torch.empty((m, k, 4), dtype=torch.float64, device=self.dev)
-        self._enter()
-        self.ctx.check(self.lib.pr_align_pairs_dev(self.ctx.h, *self._raw6(), m, self.sc.n, int(db_row0), k, _dptr(idx), _dptr(var), _dptr(dist)))
-        self._leave()
-        return var, dist
-
-    take_warnings = Matcher.take_warnings
-    flagged_count = Matcher.flagged_count
-
-    def _split_twin(self):
-        if getattr(self, "_twin", None) is None or self._twin_of is not self.sc.db_sig:
-            if getattr(self, "_twin", None) is not None:
-                self._twin.close()
-            tw = FusedMatcher(self.sc._max_q, self.sc._max_db, ctx=Context(self.ctx.device, sc_arith="f16x2", stream=self.ctx.stream))
-            tw.pack_database(self.sc.db_sig, self.m2.db_sig)
-            self._twin, self._twin_of = tw, self.sc.db_sig
-        return self._twin
+        return self._match((sc_queries, m2dp_queries), mask_width, p_weight, k, db_row0, q_row0, group, False, f16_fallback, exact_order, None)
 
 
 def _world(group) -> int:
@@ -650,75 +624,11 @@ def _world(group) -> int:
     return dist.get_world_size(group) if (group is not None or (dist.is_available() and dist.is_initialized())) else 1
 
 
-def _merge_dev(owner, idx_all: torch.Tensor, sc_all: torch.Tensor, k: int):
-    """pr_merge_topk_dev on [G, m, k] device tensors."""
-    G, m, kk = idx_all.shape
-    assert kk == k
-    idx = torch.empty((m, k), dtype=torch.int32, device=idx_all.device)
-    score = torch.empty((m, k), dtype=torch.float64, device=idx_all.device)
-    owner._enter()
-    owner.ctx.check(owner.lib.pr_merge_topk_dev(owner.ctx.h, _dptr(idx_all.contiguous()), _dptr(sc_all.contiguous()), G, m, k,
-                                                _dptr(idx), _dptr(score)))
-    owner._leave()
-    return idx, score
-
-
-def _finish_dev(owner, cand_idx: torch.Tensor, cand_sc: torch.Tensor | None, part_all: torch.Tensor, k: int, moms, p_weight: float):
-    """pr_rerank_finish_dev: candidates [m, kin] (+ their merged pass scores) + the shards' p5 blocks [G, m, 5, kin] -> (idx [m,k], score [m,k]);
-    the order and containment checks of the result (statistics moms = (mom_sc | None, mom_m2 | None, shards in them)) stay in the context:
-    pr_f16_margin_dev (PR_SC_ARITH_F16) or exact_moments() / exact_select() / exact_merge() take them."""
-    G, m, five, kin = part_all.shape
-    assert five == 5
-    idx = torch.empty((m, k), dtype=torch.int32, device=cand_idx.device)
-    score = torch.empty((m, k), dtype=torch.float64, device=cand_idx.device)
-    cand_idx = cand_idx.contiguous()
-    cand_sc = None if cand_sc is None else cand_sc.contiguous()
-    part_all = part_all.contiguous()
-    mom_sc, mom_m2, g_mom = moms
-    owner._enter()
-    owner.ctx.check(owner.lib.pr_rerank_finish_dev(owner.ctx.h, _dptr(mom_sc), _dptr(mom_m2), int(g_mom), _dptr(cand_idx), _dptr(cand_sc),
-                                                   _dptr(part_all), G, m, kin, k, float(p_weight), _dptr(idx), _dptr(score)))
-    owner._leave()
-    return idx, score
-
-
-RESOLVE_SLOTS = 64      # flagged queries one pass of the exact-row resolution serves (kernels.hpp)
-
-
-def _exact_moments_dev(owner, raw6, mom_sc, mom_m2, g_mom: int, m: int, n_local: int, offset: int = 0, last: bool = True):
-    exact = torch.empty((m, 4, 3), dtype=torch.float64, device=owner.dev)
-    owner._enter()
-    owner.ctx.check(owner.lib.pr_order_exact_moments_dev(owner.ctx.h, *raw6, _dptr(mom_sc), _dptr(mom_m2), int(g_mom), m, n_local, int(offset),
-                                                         int(bool(last)), _dptr(exact)))
-    owner._leave()
-    return exact
-
-
-def _exact_select_dev(owner, exact_all: torch.Tensor, m: int, n_local: int, q_row0: int, db_row0: int, mask_width: int, p_weight: float,
-                      has_sc: bool, has_m2: bool, k: int, offset: int = 0):
-    G = exact_all.shape[0]
-    exact_all = exact_all.contiguous()
-    sel = torch.empty((RESOLVE_SLOTS, 2, k), dtype=torch.float64, device=owner.dev)
-    owner._enter()
-    owner.ctx.check(owner.lib.pr_order_exact_select_dev(owner.ctx.h, _dptr(exact_all), G, m, n_local, int(q_row0), int(db_row0), int(mask_width),
-                                                        float(p_weight), int(has_sc), int(has_m2), int(k), int(offset), _dptr(sel)))
-    owner._leave()
-    return sel
-
-
-def _exact_merge_dev(owner, sel_all: torch.Tensor, m: int, k: int, idx, score, offset: int = 0):
-    G = sel_all.shape[0]
-    sel_all = sel_all.contiguous()
-    owner._enter()
-    owner.ctx.check(owner.lib.pr_order_exact_merge_dev(owner.ctx.h, _dptr(sel_all), G, m, int(k), int(offset), _dptr(idx), _dptr(score)))
-    owner._leave()
-    return idx, score
-
-
 def sharded_topk(local_moments, local_select, k: int, group, G: int, merge=None, force_exchange: bool = False, rerank=None, finish=None,
                  post=None, resolve=None, mark=None):
     """The exchange protocol of SURVEY.md §8-e around two local callables (HIP in production; a numpy stand-in in
     the gloo CPU tests): moments -> all_gather -> select with the moments of all shards -> all_gather -> merge.
+    resolve (optional, step 7): (moments(offset, last), select(exact_all, k, offset), merge(sel_all, k, idx, score, offset), passes()).
     mark (optional): called with a phase name after every phase of the protocol has been ENQUEUED (bench.py records an event on the
     stream there: the per-rank phase times of a step)."""
     import torch.distributed as dist
@@ -763,20 +673,20 @@ def sharded_topk(local_moments, local_select, k: int, group, G: int, merge=None,
     idx, score = finish(cand_idx, cand_sc, part_all, k)
     mark("finish+checks")
     if resolve is not None:                              # step 7: the flagged queries from their exact rows (moments, per-shard k best, merge),
-        passes = resolve[3]() if len(resolve) > 3 else 1   # 64 per pass; the same number of passes on every rank
-        if len(resolve) > 3:
-            mark("flagged count")                        # (calls above 64 queries: one read-back of the count; none flagged - no pass)
-        for p in range(passes):
+        exact_moments, exact_select, exact_merge, passes = resolve
+        n_pass = passes()                                # 64 per pass; the same number of passes on every rank
+        mark("flagged count")                            # (calls above 64 queries: one read-back of the count; none flagged - no pass)
+        for p in range(n_pass):
             off = p * RESOLVE_SLOTS
-            ex = resolve[0](off, p == passes - 1) if len(resolve) > 3 else (resolve[0](off) if p else resolve[0]())
+            ex = exact_moments(off, p == n_pass - 1)
             mark("exact rows")
             exact_all = gather(ex)
             mark("all_gather D (exact moments)")
-            sel = resolve[1](exact_all, k, off) if p else resolve[1](exact_all, k)
+            sel = exact_select(exact_all, k, off)
             mark("exact select")
             sel_all = gather(sel)
             mark("all_gather E (exact lists)")
-            idx, score = resolve[2](sel_all, k, idx, score, off) if p else resolve[2](sel_all, k, idx, score)
+            idx, score = exact_merge(sel_all, k, idx, score, off)
             mark("exact merge")
     if post is not None:
         post(cand_sc, idx, score)

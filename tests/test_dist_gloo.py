@@ -66,22 +66,22 @@ def _worker(rank, world, port, n, m, k, mask, q):
         sc_ = np.nanmax(np.where(np.isnan(pa[:, :, 0]), -np.inf, pa[:, :, 0]), axis=0)
         return cand_idx[:, :kk].clone(), torch.from_numpy(sc_[:, :kk].copy())
 
-    def exact():
+    def exact(off, last):
         return torch.full((m, 4, 3), float(rank + 1), dtype=torch.float64)
 
-    def select(exact_all, kk):                                 # this rank's k best of the flagged queries' exact rows: [64, 2, k]
+    def select(exact_all, kk, off):                            # this rank's k best of the flagged queries' exact rows: [64, 2, k]
         seen["exact"] = exact_all.numpy().copy()
         return torch.full((64, 2, kk), float(10 * (rank + 1)), dtype=torch.float64)
 
-    def merge(sel_all, kk, i_, s_):
+    def merge(sel_all, kk, i_, s_, off):
         seen["sel"] = sel_all.numpy().copy()
         return i_, s_
 
-    idx2, sc2 = sharded_topk(local_moments, local_select, k, None, world, rerank=rerank, finish=finish, resolve=(exact, select, merge))
+    idx2, sc2 = sharded_topk(local_moments, local_select, k, None, world, rerank=rerank, finish=finish, resolve=(exact, select, merge, lambda: 1))
     assert seen["exact"].shape == (world, m, 4, 3) and all((seen["exact"][g] == g + 1).all() for g in range(world))
     assert seen["sel"].shape == (world, 64, 2, k) and all((seen["sel"][g] == 10 * (g + 1)).all() for g in range(world))
     assert torch.equal(idx2, idx) and np.abs(sc2.numpy() - sc.numpy()).max() == 0.0
-    # the Matcher's form of step 7: a fourth entry gives the number of passes (a stream-ordered call: ceil(m / 64), whatever is flagged); every
+    # several passes of step 7 (the fourth entry gives their number; a stream-ordered call: ceil(m / 64), whatever is flagged); every
     # pass runs both exchanges with its offset, and only the LAST one is declared last (what may raise PR_WARN_ORDER_UNRESOLVED in the library)
     calls = []
 
@@ -109,7 +109,7 @@ def _worker(rank, world, port, n, m, k, mask, q):
 
 
 @pytest.mark.parametrize("mask,k", [(0, 1), (4, 3)])
-def test_sharded_topk_matches_unsharded_oracle(mask, k):
+def test_sharded_topk_with_one_resolve_convention_matches_unsharded_oracle(mask, k):
     import oracle_lib
     from so_dso_place_recognition_amd import synth
     n, m, world = 90, 12, 2

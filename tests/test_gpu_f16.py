@@ -198,10 +198,10 @@ def test_f16_config5_fused_1m_db_in_8_shards(api):
         mt.close()
 
 
-def test_merge_topk_has_no_cap_on_shards_times_width(api):
+def test_matcher_merge_has_no_cap_on_shards_times_width(api):
     """pr_merge_topk_dev is a G-way merge of ascending lists: 8 shards x 58 candidates (464 entries per query; the first version selected
     over a gathered array of at most 128) against the torch restatement, with missing entries at the end of one shard's lists."""
-    from so_dso_place_recognition_amd.matcher import Matcher, _merge_dev, merge_topk
+    from so_dso_place_recognition_amd.matcher import Matcher, merge_topk
     G, m, k = 8, 64, 58
     g = torch.Generator().manual_seed(1)
     sc = torch.sort(torch.randn(G, m, k, generator=g, dtype=torch.float64), dim=2).values
@@ -213,7 +213,7 @@ def test_merge_topk_has_no_cap_on_shards_times_width(api):
     ri, rs = merge_topk(idx, sc, k)
     mt = Matcher("sc", 8, 16)
     for kk in (k, 9):
-        di, ds = _merge_dev(mt, idx[:, :, :kk].contiguous().cuda(), sc[:, :, :kk].contiguous().cuda(), kk)
+        di, ds = mt.merge(idx[:, :, :kk].contiguous().cuda(), sc[:, :, :kk].contiguous().cuda(), kk)
         ri, rs = merge_topk(idx[:, :, :kk].contiguous(), sc[:, :, :kk].contiguous(), kk)
         assert torch.equal(di.cpu(), ri) and torch.equal(ds.cpu(), rs)
     mt.close()

@@ -45,9 +45,6 @@ for it in range(4):
     sel = timed("select", lambda: mt.local_select(mom.unsqueeze(0), 1, 0, 2.0, a.k, 0, 0), acc)
     idx, sc = timed("re-evaluation", lambda: mt.local_rerank(sel[0], a.k, False, sel[1]), acc)
     if mt.f16:
-        if a.fused:
-            timed("margin", lambda: mt._margin(mt._m1, mt._m2, 1, 2.0, sel[1], a.k, sc), acc)
-        else:
-            timed("margin", lambda: mt._margin(mt._mom_all, None, 1, 2.0, sel[1], a.k, sc), acc)
+        timed("margin", lambda: mt._margin(*mt._moms(), 1, 2.0, sel[1], a.k, sc), acc)
 print(a.arith, "fused" if a.fused else "sc", "kin", sel[0].shape[1], {k: round(float(np.mean(v[1:])), 3) for k, v in acc.items()},
       "planted", int((idx.cpu().numpy()[:, 0] == planted).sum()))
