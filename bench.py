@@ -10,6 +10,9 @@ One step = the whole match path on inputs already resident in HBM as f64 signatu
 i.e. run_test.m:25-57.  With N > 1 GPUs the SAME 100k DB is row-sharded over the ranks (strong scaling,
 SURVEY.md §8-e); queries are replicated.  value = queries of all steps / max-over-ranks wall time.
 
+A plain run does only what `value` needs: it sets up, warms up, times the steps, writes --dump-outputs and prints the JSON line.
+Everything below (all outside the timed region) runs with --full only.
+
 `extra` (outside the timed region, N = 1 only): the secondary workloads of BASELINE.json measured in the same run - M2DP matching
 over a 50k-signature DB (config 3), SC generation from 50 000-point clouds (config 2), and the fp32-MFMA arithmetic of the SC matcher.
 
@@ -164,25 +167,28 @@ def via_group(args):
     dt = time.perf_counter() - t0
     if args.dump_outputs:
         dump_outputs(args.dump_outputs, idx=idx, score=sc)
-    g.set_timing(True)                                             # one more step with events between the phases on every shard's stream
-    g.match_topk(q, 0, 2.0, 1)
-    per_rank = []
-    for r, ph in enumerate(g.last_timing()):
-        coll_ms = sum(v for kk, v in ph.items() if kk.startswith("all_gather"))
-        rows = n * (r + 1) // args.gpus - n * r // args.gpus
-        per_rank.append({"rank": r, "db_rows": rows, "shard_fraction": rows / n, "phases_ms": ph, "collective_ms": coll_ms,
-                         "compute_ms": sum(ph.values()) - coll_ms, "matcher_ns_per_pair": 1e6 * ph["distances"] / (m * rows)})
-    g.set_timing(False)
-    print(json.dumps({"metric": "queries/sec over 100k-signature DB (SC 20x60, z-score fusion, top-1), through pr_group (C ABI, host query buffers)",
-                      "value": m * args.steps / dt, "unit": "queries/s", "n_gpus": args.gpus, "steps": args.steps, "warmup": args.warmup,
-                      "ms_per_step": 1e3 * dt / args.steps, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
-                      "dtype": "f16x2 (fp32 carried as f16 hi + lo, fp32 accumulate)", "data": "synthetic",
-                      "collective": {"backend": "rccl (in-process, ncclCommInitAll)" if g.uses_rccl else "device copies", "world": args.gpus,
-                                     "rccl_ranks_seen": g.rccl_ranks, "exchange_selftest": "passed at pr_group_create" if args.gpus > 1 else None},
-                      "per_rank": per_rank, "flagged_queries_last_step": g.last_flagged,
-                      "config": {"workload": "sc_match_100k", "db_signatures": n, "queries_per_step": m, "via": "pr_group_match_topk",
-                                 "uses_rccl": g.uses_rccl, "note": "DB packed once (pr_group_set_database); queries host -> every GPU per step"},
-                      "parity": {"planted_top1_correct": int((idx[:, 0] == planted).sum()), "queries": m}}), flush=True)
+    out = {"metric": "queries/sec over 100k-signature DB (SC 20x60, z-score fusion, top-1), through pr_group (C ABI, host query buffers)",
+           "value": m * args.steps / dt, "unit": "queries/s", "n_gpus": args.gpus, "steps": args.steps, "warmup": args.warmup,
+           "ms_per_step": 1e3 * dt / args.steps, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
+           "dtype": "f16x2 (fp32 carried as f16 hi + lo, fp32 accumulate)", "data": "synthetic"}
+    if args.full:
+        g.set_timing(True)                                         # one more step with events between the phases on every shard's stream
+        g.match_topk(q, 0, 2.0, 1)
+        per_rank = []
+        for r, ph in enumerate(g.last_timing()):
+            coll_ms = sum(v for kk, v in ph.items() if kk.startswith("all_gather"))
+            rows = n * (r + 1) // args.gpus - n * r // args.gpus
+            per_rank.append({"rank": r, "db_rows": rows, "shard_fraction": rows / n, "phases_ms": ph, "collective_ms": coll_ms,
+                             "compute_ms": sum(ph.values()) - coll_ms, "matcher_ns_per_pair": 1e6 * ph["distances"] / (m * rows)})
+        g.set_timing(False)
+        out.update({"collective": {"backend": "rccl (in-process, ncclCommInitAll)" if g.uses_rccl else "device copies", "world": args.gpus,
+                                   "rccl_ranks_seen": g.rccl_ranks, "exchange_selftest": "passed at pr_group_create" if args.gpus > 1 else None},
+                    "per_rank": per_rank, "flagged_queries_last_step": g.last_flagged})
+    out["config"] = {"workload": "sc_match_100k", "db_signatures": n, "queries_per_step": m, "via": "pr_group_match_topk",
+                     "uses_rccl": g.uses_rccl, "note": "DB packed once (pr_group_set_database); queries host -> every GPU per step"}
+    if args.full:
+        out["parity"] = {"planted_top1_correct": int((idx[:, 0] == planted).sum()), "queries": m}
+    print(json.dumps(out), flush=True)
     g.close()
 
 
@@ -609,16 +615,19 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--db", type=int, default=100_000, help="total DB signatures (sharded over the ranks)")
     ap.add_argument("--queries", type=int, default=4096)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check what the headline figure does not need: roofline, parity, collective, "
+                         "per_rank, cpu_baseline and extra (a plain run sets up, warms up, times the steps, dumps and prints the line)")
     ap.add_argument("--cpu-sample", type=int, default=-1, help="queries for the CPU baseline (-1: one per host core, <= 64)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline and the oracle's entries of parity")
     ap.add_argument("--sc-arith", default=None, choices=["f16x2", "f32", "f16"],
                     help="SC matcher arithmetic (default: the library's, split-f16 MFMA; f32 = the fp32-MFMA kernel; f16 = one f16 product per term)")
     ap.add_argument("--via-group", action="store_true",
                     help="ONE process drives --gpus GPUs through pr_group (C ABI, in-process RCCL) instead of one torch.distributed rank per GPU")
     ap.add_argument("--force-exchange", action="store_true",
                     help="N = 1 only: run the two all-gathers (RCCL, one-rank group) and the device merge of the sharded protocol anyway")
-    ap.add_argument("--no-extra", action="store_true", help="skip the secondary workloads reported under `extra`")
-    ap.add_argument("--no-kitti-shape", action="store_true", help="skip extra.kitti_shape (its drive sampler is ~70 000 torch launches: slow under rocprofv3 --pmc)")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the secondary workloads reported under `extra`")
+    ap.add_argument("--no-kitti-shape", action="store_true", help="with --full: skip extra.kitti_shape (its drive sampler is ~70 000 torch launches: slow under rocprofv3 --pmc)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (gloo: several ranks on ONE GPU, tests only)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write the top-k indices and scores of the last timed step to DIR/idx.npy and DIR/score.npy (float64)")
@@ -663,7 +672,7 @@ def main():
     lo, hi = (n * rank) // world, (n * (rank + 1)) // world          # this rank's DB rows
     t0 = time.time()
     db = synth.sc_database_torch(45, hi - lo, first=lo, device=dev)   # f64 [n_local, 2400] drawn in HBM (== synth.sc_database bit for bit)
-    db_host = db.cpu().numpy() if (rank == 0 and world == 1 and not args.no_cpu_baseline) else None
+    db_host = db.cpu().numpy() if (args.full and rank == 0 and world == 1 and not args.no_cpu_baseline) else None
     q_host, planted = synth.sc_queries(46, np.empty((0, 2400)), m, db_first=0, n_global=n, db_seed=45)
     q = torch.from_numpy(q_host).to(dev)                              # f64 [m, 2400]
     gen_s = time.time() - t0
@@ -702,137 +711,146 @@ def main():
     dt = time.perf_counter() - t0
     if args.dump_outputs and rank == 0:   # now: the calls below reuse the matcher's output buffers
         dump_outputs(args.dump_outputs, idx=idx.cpu().numpy(), score=score.cpu().numpy())
-    kern_ms = [ev.elapsed_ms(a, b) for a, b in evs]
-    # one more step, outside the timed region, with an event after every phase of the protocol on the stream everything runs on (the
-    # library's kernels, torch's copies and RCCL's all-gathers share it): per-rank phase times, gathered to rank 0 below
-    marks = []
-
-    def mark(name):
-        e = ev.create()
-        ev.record(e, stream)
-        marks.append((name, e))
-    barrier()
-    mark("start")
-    mt.pack_database(db)
-    mark("pack(db)")
-    mt.match(q, 0, 2.0, 1, db_row0=lo, force_exchange=args.force_exchange, mark=mark)
-    mark("end")
-    torch.cuda.synchronize()
-    phases = {}
-    for (_, a), (name, b_) in zip(marks[:-1], marks[1:]):
-        phases[name] = phases.get(name, 0.0) + ev.elapsed_ms(a, b_)
-    coll_ms = sum(v for kk, v in phases.items() if kk.startswith("all_gather"))
-    mine_rank = {"rank": rank, "db_rows": hi - lo, "shard_fraction": (hi - lo) / n, "phases_ms": phases, "collective_ms": coll_ms,
-                 "compute_ms": sum(phases.values()) - coll_ms, "step_ms": ev.elapsed_ms(marks[0][1], marks[-1][1]),
-                 "matcher_ns_per_pair": 1e6 * float(np.mean(kern_ms)) / (m * (hi - lo))}
-    flagged = None
-    if world == 1 and not args.force_exchange and arith != "f16":   # how many queries of a step the order / containment checks hand to the exact rows
-        mt.match(q, 0, 2.0, 1, db_row0=lo, exact_order=False)
-        flagged = mt.flagged_count()
-    per_rank = [mine_rank]
-    if world > 1:
-        per_rank = [None] * world
-        dist.all_gather_object(per_rank, mine_rank)
-    # per-launch times of the matcher (pr_set_kernel_timing: the library's own events between its launches), outside the timed region
-    launch_ms = None
-    if arith == "f16x2":
-        mt.ctx.kernel_timing(True)
-        acc = []
-        for _ in range(min(5, max(2, args.steps))):
-            step(None)
-            acc.append(mt.ctx.last_distance_timing())
-        mt.ctx.kernel_timing(False)
-        launch_ms = [float(np.mean([a[i] for a in acc])) for i in range(3)]
-        st_bin = C.c_int32(0)
-        mt.ctx.check(mt.lib.pr_sc_binary_state(mt.ctx.h, mt.q, mt.db, C.byref(st_bin)))
     if world > 1:
         tt = torch.tensor([dt], dtype=torch.float64, device=dev if args.backend == "nccl" else "cpu")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
+    # whether the steps took the binary path for the intensity channel: read from the packed sets' statistics, no launch
+    st_bin = None
+    if arith == "f16x2":
+        st_bin = C.c_int32(0)
+        mt.ctx.check(mt.lib.pr_sc_binary_state(mt.ctx.h, mt.q, mt.db, C.byref(st_bin)))
+        st_bin = st_bin.value
+    binary_path = st_bin == 1 and os.environ.get("PR_SC_KERNEL") != "h"     # (PR_SC_KERNEL=h: sc_match_h_kernel has no binary path)
 
-    idx_h = idx.cpu().numpy()[:, 0]
-    score_h = score.cpu().numpy()[:, 0]
-    planted_ok = int((idx_h == planted).sum())
-    # what the communicator itself says (not argv): every rank contributes its rank through the group's own all-gather
-    coll = {"backend": None, "world": 1, "rccl_ranks_seen": 0}
-    if dist.is_available() and dist.is_initialized():
-        on_dev = dist.get_backend() == "nccl"
-        mine = torch.tensor([rank], dtype=torch.int32, device=dev if on_dev else "cpu")
-        seen = torch.empty((dist.get_world_size(),), dtype=torch.int32, device=mine.device)
-        dist.all_gather_into_tensor(seen, mine)
-        coll = {"backend": "nccl (RCCL %s)" % ".".join(map(str, torch.cuda.nccl.version())) if on_dev else dist.get_backend(),
-                "world": dist.get_world_size(), "rccl_ranks_seen": len(set(seen.cpu().tolist())) if on_dev else 0}
+    if args.full:
+        kern_ms = [ev.elapsed_ms(a, b) for a, b in evs]
+        # one more step, outside the timed region, with an event after every phase of the protocol on the stream everything runs on (the
+        # library's kernels, torch's copies and RCCL's all-gathers share it): per-rank phase times, gathered to rank 0 below
+        marks = []
+
+        def mark(name):
+            e = ev.create()
+            ev.record(e, stream)
+            marks.append((name, e))
+        barrier()
+        mark("start")
+        mt.pack_database(db)
+        mark("pack(db)")
+        mt.match(q, 0, 2.0, 1, db_row0=lo, force_exchange=args.force_exchange, mark=mark)
+        mark("end")
+        torch.cuda.synchronize()
+        phases = {}
+        for (_, a), (name, b_) in zip(marks[:-1], marks[1:]):
+            phases[name] = phases.get(name, 0.0) + ev.elapsed_ms(a, b_)
+        coll_ms = sum(v for kk, v in phases.items() if kk.startswith("all_gather"))
+        mine_rank = {"rank": rank, "db_rows": hi - lo, "shard_fraction": (hi - lo) / n, "phases_ms": phases, "collective_ms": coll_ms,
+                     "compute_ms": sum(phases.values()) - coll_ms, "step_ms": ev.elapsed_ms(marks[0][1], marks[-1][1]),
+                     "matcher_ns_per_pair": 1e6 * float(np.mean(kern_ms)) / (m * (hi - lo))}
+        flagged = None
+        if world == 1 and not args.force_exchange and arith != "f16":   # how many queries of a step the order / containment checks hand to the exact rows
+            mt.match(q, 0, 2.0, 1, db_row0=lo, exact_order=False)
+            flagged = mt.flagged_count()
+        per_rank = [mine_rank]
+        if world > 1:
+            per_rank = [None] * world
+            dist.all_gather_object(per_rank, mine_rank)
+        # per-launch times of the matcher (pr_set_kernel_timing: the library's own events between its launches), outside the timed region
+        launch_ms = None
+        if arith == "f16x2":
+            mt.ctx.kernel_timing(True)
+            acc = []
+            for _ in range(min(5, max(2, args.steps))):
+                step(None)
+                acc.append(mt.ctx.last_distance_timing())
+            mt.ctx.kernel_timing(False)
+            launch_ms = [float(np.mean([a[i] for a in acc])) for i in range(3)]
+
+        idx_h = idx.cpu().numpy()[:, 0]
+        score_h = score.cpu().numpy()[:, 0]
+        planted_ok = int((idx_h == planted).sum())
+        # what the communicator itself says (not argv): every rank contributes its rank through the group's own all-gather
+        coll = {"backend": None, "world": 1, "rccl_ranks_seen": 0}
+        if dist.is_available() and dist.is_initialized():
+            on_dev = dist.get_backend() == "nccl"
+            mine = torch.tensor([rank], dtype=torch.int32, device=dev if on_dev else "cpu")
+            seen = torch.empty((dist.get_world_size(),), dtype=torch.int32, device=mine.device)
+            dist.all_gather_into_tensor(seen, mine)
+            coll = {"backend": "nccl (RCCL %s)" % ".".join(map(str, torch.cuda.nccl.version())) if on_dev else dist.get_backend(),
+                    "world": dist.get_world_size(), "rccl_ranks_seen": len(set(seen.cpu().tolist())) if on_dev else 0}
 
     if rank == 0:
-        qps = m * args.steps / dt
-        kms = float(np.mean(kern_ms))
-        pairs = m * (hi - lo)
-        f16 = arith in ("f16x2", "f16")
-        kname = {"h": "sc_match_h_kernel"}.get(os.environ.get("PR_SC_KERNEL", "e"), "sc_match_e_kernel") if f16 else "sc_match_kernel"
-        if arith == "f16":
-            kname = "sc_match_e_kernel<single product>"
-        fpp, peak = (FLOP_PER_PAIR_F16X2 if arith == "f16x2" else FLOP_PER_PAIR, MFMA_F16_PEAK_TFLOPS) if f16 else (FLOP_PER_PAIR, MFMA_F32_PEAK_TFLOPS)
-        kms_all = kms
-        launches = None
-        binary = launch_ms is not None and launch_ms[1] + launch_ms[2] > 0
-        if binary:     # three launches: structure channel in split-f16 | intensity channel with one product per term + rounding | the same in split-f16
-            # (one of the last two has left at once: the gate of DESIGN.md §4.0b).  The dominant kernel is the first one: one channel's FLOPs.
-            fast = launch_ms[1] > launch_ms[2]
-            kname = "sc_match_e_kernel<split-f16>, structure channel"
-            fpp, kms = FLOP_PER_PAIR_F16X2 // 2, launch_ms[0]
-            launches = [{"kernel": kname, "ms": launch_ms[0], "flop_per_pair": fpp, "frac": pairs * fpp / (launch_ms[0] * 1e-3) / 1e12 / peak},
-                        {"kernel": "sc_match_e_kernel<single product on the hi halves + integer rounding>, intensity channel (binary)", "ms": launch_ms[1],
-                         "flop_per_pair": FLOP_PER_PAIR // 2, "frac": (pairs * (FLOP_PER_PAIR // 2) / (launch_ms[1] * 1e-3) / 1e12 / peak) if fast else None},
-                        {"kernel": "sc_match_e_kernel<split-f16>, intensity channel", "ms": launch_ms[2], "flop_per_pair": FLOP_PER_PAIR_F16X2 // 2,
-                         "frac": None if fast else pairs * (FLOP_PER_PAIR_F16X2 // 2) / (launch_ms[2] * 1e-3) / 1e12 / peak}]
-        ach = pairs * fpp / (kms * 1e-3) / 1e12
-        traffic = None   # HBM bytes per launch from the committed PMC passes (FETCH_SIZE x2 on gfx950 + WRITE_SIZE)
-        traffic_file = None
-        for cand in (("r06_traffic.json", "r05_traffic.json", "r04b_traffic.json") if binary else ("r04_traffic.json", "r03_traffic.json")):   # the newest committed PMC passes of this command
-            try:
-                tr = json.load(open(os.path.join(ROOT, "profiles", cand)))
-                if tr["workload"] == {"db": n, "queries": m, "n_gpus": world}:
-                    traffic = next(v["hbm_bytes_per_launch"] for kk, v in tr.items() if kk.startswith(kname.split("<")[0]) and (arith != "f16") == ("<false" not in kk)
-                                   and (not binary or v.get("launch") == "structure channel"))
-                    traffic_file = cand
-                    break
-            except Exception:
-                pass
         out = {
             "metric": "queries/sec over 100k-signature DB (SC 20x60, z-score fusion, top-1)",
-            "value": qps, "unit": "queries/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "value": m * args.steps / dt, "unit": "queries/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": 1e3 * dt / args.steps, "ms_per_query": 1e3 * dt / (args.steps * m),
             "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
-            "dtype": {"f16x2": "f16x2 (fp32 carried as f16 hi + lo, fp32 accumulate)" + ("; binary intensity channel: one f16 product per term, rounded to its exact integer count" if binary and fast else ""),
+            "dtype": {"f16x2": "f16x2 (fp32 carried as f16 hi + lo, fp32 accumulate)" + ("; binary intensity channel: one f16 product per term, rounded to its exact integer count" if binary_path else ""),
                       "f16": "f16 (one f16 per value, fp32 accumulate; exact top-k through fp64 re-evaluation)"}.get(arith, "f32"),
             "data": "synthetic",
             "config": {"workload": "sc_match_100k", "db_signatures": n, "queries_per_step": m, "descriptor": "SC 20x60 x 2 channels",
                        "mask_width": 0, "p_weight": 2.0, "k": 1, "db_rows_per_gpu": hi - lo,
                        "step": "pack(q)+pack(db)+distances+moments+select(k+8)+fp64 re-evaluation+order / containment checks+exact fp64 rows of flagged queries"
                                + ("+4 all_gathers+merge" if (world > 1 or args.force_exchange) else "")},
-            "roofline": {"kernel": kname, "bound": "mfma", "achieved": ach, "peak": peak,
-                         "unit": "TFLOP/s", "frac": ach / peak, "traffic": traffic,
-                         "traffic_source": (f"profiles/{traffic_file}: rocprofv3 --pmc FETCH_SIZE (x2 on gfx950) + WRITE_SIZE passes of this command, per launch "
-                                            "(a committed measurement of one box, not a live counter)" if traffic is not None else None),
-                         "flop_per_pair": fpp, "pairs_per_launch": pairs, "ms_per_launch": kms,
-                         "matcher_ms_per_step": kms_all, "launches": launches,
-                         "binary_channel_state": (int(st_bin.value) if launch_ms is not None else None),
-                         # a loop of nothing but f16 MFMAs on split-f16-like operands sustains 0.66 - 0.68 of `peak` on this chip (it clocks against its
-                         # power limit; zeros reach 0.98): tools/ubench/mfma_power.hip, profiles/r06_mfma_power_box{A,B}.txt (committed, not live)
-                         "sustained_mfma_ceiling_frac_of_peak": 0.67 if f16 else None,
-                         "frac_of_sustained_mfma_ceiling": (ach / peak / 0.67) if f16 else None,
-                         # the same launch priced as the fp32 formulation it replaces (what an fp32-MFMA kernel would need)
-                         "fp32_formulation_tflops": pairs * FLOP_PER_PAIR / (kms_all * 1e-3) / 1e12,
-                         "fp32_formulation_frac_of_157.3": pairs * FLOP_PER_PAIR / (kms_all * 1e-3) / 1e12 / MFMA_F32_PEAK_TFLOPS,
-                         "dense_equivalent_tflops": pairs * 576000 / (kms_all * 1e-3) / 1e12},
-            "parity": {"planted_top1_correct": planted_ok, "queries": m, "queries_flagged_for_exact_rows": flagged},
-            "collective": coll,
-            # one instrumented step per rank (outside the timed region): where a step's time goes on every GPU - compute scales with
-            # shard_fraction (compare matcher_ns_per_pair with the N = 1 line: the kernel's efficiency at the shard's size), the all-gathers do not
-            "per_rank": per_rank,
-            "setup_s": gen_s,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full:
+            kms = float(np.mean(kern_ms))
+            pairs = m * (hi - lo)
+            f16 = arith in ("f16x2", "f16")
+            kname = {"h": "sc_match_h_kernel"}.get(os.environ.get("PR_SC_KERNEL", "e"), "sc_match_e_kernel") if f16 else "sc_match_kernel"
+            if arith == "f16":
+                kname = "sc_match_e_kernel<single product>"
+            fpp, peak = (FLOP_PER_PAIR_F16X2 if arith == "f16x2" else FLOP_PER_PAIR, MFMA_F16_PEAK_TFLOPS) if f16 else (FLOP_PER_PAIR, MFMA_F32_PEAK_TFLOPS)
+            kms_all = kms
+            launches = None
+            binary = launch_ms is not None and launch_ms[1] + launch_ms[2] > 0
+            if binary:     # three launches: structure channel in split-f16 | intensity channel with one product per term + rounding | the same in split-f16
+                # (one of the last two has left at once: the gate of DESIGN.md §4.0b).  The dominant kernel is the first one: one channel's FLOPs.
+                fast = launch_ms[1] > launch_ms[2]
+                kname = "sc_match_e_kernel<split-f16>, structure channel"
+                fpp, kms = FLOP_PER_PAIR_F16X2 // 2, launch_ms[0]
+                launches = [{"kernel": kname, "ms": launch_ms[0], "flop_per_pair": fpp, "frac": pairs * fpp / (launch_ms[0] * 1e-3) / 1e12 / peak},
+                            {"kernel": "sc_match_e_kernel<single product on the hi halves + integer rounding>, intensity channel (binary)", "ms": launch_ms[1],
+                             "flop_per_pair": FLOP_PER_PAIR // 2, "frac": (pairs * (FLOP_PER_PAIR // 2) / (launch_ms[1] * 1e-3) / 1e12 / peak) if fast else None},
+                            {"kernel": "sc_match_e_kernel<split-f16>, intensity channel", "ms": launch_ms[2], "flop_per_pair": FLOP_PER_PAIR_F16X2 // 2,
+                             "frac": None if fast else pairs * (FLOP_PER_PAIR_F16X2 // 2) / (launch_ms[2] * 1e-3) / 1e12 / peak}]
+            ach = pairs * fpp / (kms * 1e-3) / 1e12
+            traffic = None   # HBM bytes per launch from the committed PMC passes (FETCH_SIZE x2 on gfx950 + WRITE_SIZE)
+            traffic_file = None
+            for cand in (("r06_traffic.json", "r05_traffic.json", "r04b_traffic.json") if binary else ("r04_traffic.json", "r03_traffic.json")):   # the newest committed PMC passes of this command
+                try:
+                    tr = json.load(open(os.path.join(ROOT, "profiles", cand)))
+                    if tr["workload"] == {"db": n, "queries": m, "n_gpus": world}:
+                        traffic = next(v["hbm_bytes_per_launch"] for kk, v in tr.items() if kk.startswith(kname.split("<")[0]) and (arith != "f16") == ("<false" not in kk)
+                                       and (not binary or v.get("launch") == "structure channel"))
+                        traffic_file = cand
+                        break
+                except Exception:
+                    pass
+            out.update({
+                "roofline": {"kernel": kname, "bound": "mfma", "achieved": ach, "peak": peak,
+                             "unit": "TFLOP/s", "frac": ach / peak, "traffic": traffic,
+                             "traffic_source": (f"profiles/{traffic_file}: rocprofv3 --pmc FETCH_SIZE (x2 on gfx950) + WRITE_SIZE passes of this command, per launch "
+                                                "(a committed measurement of one box, not a live counter)" if traffic is not None else None),
+                             "flop_per_pair": fpp, "pairs_per_launch": pairs, "ms_per_launch": kms,
+                             "matcher_ms_per_step": kms_all, "launches": launches,
+                             "binary_channel_state": st_bin,
+                             # a loop of nothing but f16 MFMAs on split-f16-like operands sustains 0.66 - 0.68 of `peak` on this chip (it clocks against its
+                             # power limit; zeros reach 0.98): tools/ubench/mfma_power.hip, profiles/r06_mfma_power_box{A,B}.txt (committed, not live)
+                             "sustained_mfma_ceiling_frac_of_peak": 0.67 if f16 else None,
+                             "frac_of_sustained_mfma_ceiling": (ach / peak / 0.67) if f16 else None,
+                             # the same launch priced as the fp32 formulation it replaces (what an fp32-MFMA kernel would need)
+                             "fp32_formulation_tflops": pairs * FLOP_PER_PAIR / (kms_all * 1e-3) / 1e12,
+                             "fp32_formulation_frac_of_157.3": pairs * FLOP_PER_PAIR / (kms_all * 1e-3) / 1e12 / MFMA_F32_PEAK_TFLOPS,
+                             "dense_equivalent_tflops": pairs * 576000 / (kms_all * 1e-3) / 1e12},
+                "parity": {"planted_top1_correct": planted_ok, "queries": m, "queries_flagged_for_exact_rows": flagged},
+                "collective": coll,
+                # one instrumented step per rank (outside the timed region): where a step's time goes on every GPU - compute scales with
+                # shard_fraction (compare matcher_ns_per_pair with the N = 1 line: the kernel's efficiency at the shard's size), the all-gathers do not
+                "per_rank": per_rank,
+            })
+        out["setup_s"] = gen_s
+        if args.full and world == 1 and not args.no_cpu_baseline:
             sys.path.insert(0, os.path.join(ROOT, "tests"))
             import oracle_lib                                           # the checker: CPU port of the reference
             cores = os.cpu_count() or 1
@@ -880,7 +898,7 @@ def main():
                                   "oracle_top1_equal_with_exact_statistics": exact_idx_ok,
                                   "score_note": "planted matches sit at z ~ -160; the returned score is exact in the pair's distances (fp64 re-evaluation), "
                                                 "its row statistics carry the fp32 pass's ~2e-7 relative error (DESIGN.md)"})
-        if world == 1 and not args.no_extra:
+        if args.full and world == 1 and not args.no_extra:
             mt.close()
             del db, mt
             torch.cuda.empty_cache()

@@ -1,10 +1,12 @@
-"""bench.py --dump-outputs and the step arguments, without a GPU: the files the option writes and the arguments it refuses."""
+"""bench.py --dump-outputs and the step arguments: the files the option writes and the arguments it refuses (without a GPU), and what a
+plain run leaves to --full (GPU)."""
 import importlib.util
 import os
 import subprocess
 import sys
 
 import numpy as np
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -48,3 +50,25 @@ def test_steps_below_one_are_refused():
     for argv in (["--steps", "0"], ["--warmup", "-1"]):
         r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *argv], capture_output=True, text=True, timeout=120)
         assert r.returncode == 2 and "--steps must be >= 1" in r.stderr, r.stderr[-500:]
+
+
+@pytest.mark.gpu
+def test_plain_run_prints_the_headline_and_dumps_what_a_full_run_dumps(tmp_path):
+    """A plain run stops after the timed steps: its line carries the headline fields and none of what --full measures, and its
+    dump and headline fields are those of a --full run of the same arguments."""
+    import json
+    common = ["--steps", "1", "--warmup", "0", "--db", "6001", "--queries", "130"]
+    lines = {}
+    for name, extra in (("plain", []), ("full", ["--full", "--no-cpu-baseline", "--no-extra"])):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *common, *extra, "--dump-outputs", str(tmp_path / name)],
+                           capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines[name] = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    plain, full = lines["plain"], lines["full"]
+    assert plain["value"] > 0 and plain["ms_per_step"] > 0 and plain["unit"] == "queries/s" and plain["higher_is_better"] is True
+    for key in ("metric", "unit", "higher_is_better", "dtype", "n_gpus", "steps", "warmup", "config"):
+        assert plain[key] == full[key], key
+    assert not {"roofline", "parity", "collective", "per_rank", "cpu_baseline", "extra"} & set(plain)
+    assert {"roofline", "parity", "collective", "per_rank"} <= set(full) and full["parity"]["planted_top1_correct"] == 130
+    for f in ("idx.npy", "score.npy"):
+        assert np.array_equal(np.load(tmp_path / "plain" / f), np.load(tmp_path / "full" / f))

@@ -177,7 +177,7 @@ def test_bench_two_ranks_on_one_gpu(tmp_path, arith):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     # the driver's plain command: no launcher around it, bench.py starts its own ranks (bench.py::self_launch)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1",
-           "--warmup", "0", "--db", "6001", "--queries", "130", "--backend", "gloo", "--no-cpu-baseline", "--no-extra", "--sc-arith", arith,
+           "--warmup", "0", "--db", "6001", "--queries", "130", "--backend", "gloo", "--full", "--no-cpu-baseline", "--no-extra", "--sc-arith", arith,
            "--dump-outputs", str(tmp_path / "two")]
     if arith == "f16":   # and the driver's launcher form (python -m torch.distributed.run ... bench.py --gpus 2) for the other arithmetic
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
@@ -210,7 +210,7 @@ def test_bench_two_ranks_on_one_gpu(tmp_path, arith):
             assert {"flagged count", "exact rows", "all_gather D (exact moments)", "exact select", "all_gather E (exact lists)",
                     "exact merge"} <= set(r_["phases_ms"])
     one = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "0", "--db", "6001",
-                          "--queries", "130", "--no-cpu-baseline", "--no-extra", "--sc-arith", arith, "--dump-outputs", str(tmp_path / "one")],
+                          "--queries", "130", "--full", "--no-cpu-baseline", "--no-extra", "--sc-arith", arith, "--dump-outputs", str(tmp_path / "one")],
                          capture_output=True, text=True, timeout=600)
     assert one.returncode == 0, one.stderr[-2000:]
     d1 = json.loads([l for l in one.stdout.splitlines() if l.startswith("{")][-1])

@@ -3,7 +3,7 @@
 v=$1; n=${2:-3}
 for i in $(seq $n); do
   for lib in "" tools/expbuild/libpr_amd_$v.so; do
-    PR_AMD_LIB=$lib python bench.py --steps 5 --warmup 2 --no-extra --no-cpu-baseline --sc-arith f16 2>/dev/null | python -c "
+    PR_AMD_LIB=$lib python bench.py --steps 5 --warmup 2 --full --no-extra --no-cpu-baseline --sc-arith f16 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -5,7 +5,7 @@ n=$1; shift
 for i in $(seq $n); do
   for v in "" "$@"; do
     lib=${v:+tools/expbuild/libpr_amd_$v.so}
-    PR_AMD_LIB=$lib python bench.py --steps 5 --warmup 2 --no-extra --no-cpu-baseline 2>/dev/null | python -c "
+    PR_AMD_LIB=$lib python bench.py --steps 5 --warmup 2 --full --no-extra --no-cpu-baseline 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

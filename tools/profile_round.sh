@@ -10,15 +10,15 @@ out=$root/gpurun_out; mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
 f=$out/$tag.txt
 {
-  echo "# $tag: python bench.py --steps 3 --warmup 1 (kernel trace: + --no-cpu-baseline; PMC passes: --steps 1 --warmup 0 --no-cpu-baseline --no-extra)"
+  echo "# $tag: python bench.py --steps 3 --warmup 1 --full (kernel trace: + --no-cpu-baseline; PMC passes: --steps 1 --warmup 0 --full --no-cpu-baseline --no-extra)"
   echo "# MI355X, rocprofv3 --kernel-trace --stats, then one --pmc group per run"
   echo
   echo "## bench.py JSON line (un-profiled run, with the CPU baseline)"
-  python $root/bench.py --steps 5 --warmup 2 2> $out/${tag}_bench.err | tail -n 1
+  python $root/bench.py --steps 5 --warmup 2 --full 2> $out/${tag}_bench.err | tail -n 1
   echo
 } > $f
 rm -rf $out/${tag}_trace
-rocprofv3 --kernel-trace --stats -d $out/${tag}_trace -o sc -- python $root/bench.py --steps 3 --warmup 1 --no-cpu-baseline > $out/${tag}_trace.log 2>&1
+rocprofv3 --kernel-trace --stats -d $out/${tag}_trace -o sc -- python $root/bench.py --steps 3 --warmup 1 --full --no-cpu-baseline > $out/${tag}_trace.log 2>&1
 python $root/profiles/summarize.py $(find $out/${tag}_trace -name "*_results.db") | grep -v "at::native\|elementwise_kernel" >> $f
 i=0
 for grp in "SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_MFMA GRBM_GUI_ACTIVE" "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_ANY" \
@@ -27,14 +27,14 @@ for grp in "SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_MFMA GRBM_GUI_ACTIVE
   i=$((i+1))
   d=$out/${tag}_p$i
   rm -rf $d
-  rocprofv3 --pmc $grp -d $d -o sc -- python $root/bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-extra ${PMC_BENCH_ARGS:-} > $d.log 2>&1
+  rocprofv3 --pmc $grp -d $d -o sc -- python $root/bench.py --steps 1 --warmup 0 --full --no-cpu-baseline --no-extra ${PMC_BENCH_ARGS:-} > $d.log 2>&1
   echo >> $f
   python $root/profiles/summarize.py $(find $d -name "*_results.db") | grep -E "^==|^--|sc_match|sc_pack|fuse_select|row_moments|rerank_kernel" >> $f
 done
 python - $out $tag <<'PY'
 import glob, json, re, sqlite3, sys
 out, tag = sys.argv[1], sys.argv[2]
-res = {"source": f"gpurun_out/{tag}.txt: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes of `python bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-extra`; "
+res = {"source": f"{tag}.txt: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes of `python bench.py --steps 1 --warmup 0 --full --no-cpu-baseline --no-extra`; "
                  "KiB per launch; FETCH_SIZE x2 (gfx950 wide-read correction, MI355X_MICROARCH.md)",
        "workload": {"db": 100000, "queries": 4096, "n_gpus": 1}}
 for db in glob.glob(f"{out}/{tag}_p*/**/*_results.db", recursive=True):
