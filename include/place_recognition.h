@@ -21,6 +21,7 @@ typedef struct pr_ctx pr_ctx;
 typedef struct pr_sigset pr_sigset;
 typedef struct pr_clouds pr_clouds;
 typedef struct pr_bow_vocab pr_bow_vocab;
+typedef struct pr_bow_db pr_bow_db;
 
 enum { PR_OK = 0, PR_EINVAL = -1, PR_ENOMEM = -2, PR_EHIP = -3, PR_EIO = -4, PR_ENAN = -5 };
 enum { PR_TYPE_SC = 0, PR_TYPE_M2DP = 1, PR_TYPE_DELIGHT = 2, PR_TYPE_GIST = 3, PR_TYPE_BOW = 4 };   /* run_test.m:26-36 `type` */
@@ -52,7 +53,7 @@ enum { PR_SC_ARITH_F16X2 = 0, PR_SC_ARITH_F32 = 1, PR_SC_ARITH_F16 = 2 };
  * PR_NAN_EXCLUDE (default) does exactly that and reports PR_WARN_NAN_ROWS; PR_NAN_FAIL turns it into the error PR_ENAN at pr_sync. */
 enum { PR_NAN_EXCLUDE = 0, PR_NAN_FAIL = 1 };
 enum { PR_WARN_NAN_ROWS = 1, PR_WARN_M2DP_SVD = 2, PR_WARN_F16_FALLBACK = 4, PR_WARN_ORDER_RESOLVED = 8,
-       PR_WARN_ORDER_UNRESOLVED = 16, PR_WARN_BOW_TRUNCATED = 32 };   /* bits of pr_take_warnings; ORDER_RESOLVED: a query was answered from its exact fp64 row (order or containment
+       PR_WARN_ORDER_UNRESOLVED = 16, PR_WARN_BOW_TRUNCATED = 32, PR_WARN_BOW_ROWS = 64 };   /* bits of pr_take_warnings; ORDER_RESOLVED: a query was answered from its exact fp64 row (order or containment
                                             check, below); the last one: a caller of the sharded per-pass form stopped (last_pass != 0) with flagged queries left -
                                             those keep the answer of the re-evaluated candidate list.  The library's own calls, stream-ordered or not, run every pass */
 
@@ -205,6 +206,38 @@ int pr_gist_distance(pr_ctx* ctx, const double* h1, int32_t m, const double* h2,
 int pr_bow_distance(pr_ctx* ctx, const double* h1, int32_t m, const double* h2, int32_t n, int32_t cols, float* dist);
 int pr_match_topk_cols(pr_ctx* ctx, int type, const double* h1, int32_t m, const double* h2, int32_t n, int32_t cols,
                        int32_t mask_width, int32_t k, int32_t* idx, float* score);
+
+/* BoW matching through an inverted file (word-major lists of (row, weight) postings), exact in fp64: distances and top-k are those of
+ * processBoW.m:22-37 + run_test.m:47-57 evaluated in double, bit for bit (ties -> lower index, masked entries +Inf, NaN never selected,
+ * -1 / NaN fill), for CONFORMING rows: before the reference's end of a row (its first column p < cols - 1 with !(id > -1); the last column
+ * is never read) every id is an integer in [0, n_words) and the ids ascend strictly - what test_bow.cpp:147-162 and pr_bow_generate* write.
+ * Weights may be any double.  Rows: [2 n][cols] f64, ids | weights per image (pr_bow_distance's layout).
+ *   pr_bow_db_create   capacities are fixed here: max_sigs rows, max_postings words over all rows; n_words the vocabulary size.  The
+ *                      device scratch of one match chunk (<= 512 MB of fp64 accumulators) and a tail segment are allocated once.
+ *                      Environment: PR_BOW_TAIL_ROWS (tail capacity, default 1024), PR_BOW_CHUNK (queries per chunk), PR_BOW_THREADS
+ *                      (64 | 256, threads per query).
+ *   pr_bow_db_set      replaces the contents with rows (where: PR_HOST | PR_DEVICE) and builds the index (validate, count, scan, scatter).
+ *   pr_bow_db_append   adds rows count .. count + n_new - 1 to a tail segment whose lists are rebuilt from the tail rows only; a full tail
+ *                      is first folded into the main lists (the one step whose cost grows with n).  Any sequence of appends gives the
+ *                      results of one set of the same rows.
+ *                      Both synchronise, reject a non-conforming row with PR_EINVAL naming the first one, exceed a capacity with PR_ENOMEM.
+ *   pr_bow_match_topk_dev  q DEVICE [2 m][cols] against all rows; idx DEVICE [m][k] global rows (db_row0 + local), score DEVICE f64 [m][k],
+ *                      ascending by (score, index) with -1 / NaN last (pr_merge_topk_dev merges shards unchanged); the mask compares
+ *                      q_row0 + i with db_row0 + j.  k <= 128.  Stream-ordered, allocation-free, graph-capturable.  A non-conforming
+ *                      query row gets -1 / NaN in all k slots and raises PR_WARN_BOW_ROWS (pr_take_warnings).
+ *   pr_bow_match_topk_f64  the host form of run_test.m:32-57 for 'bow' in fp64 (h1 [2 m][cols], h2 [2 n][cols] host);
+ *   pr_bow_distance_f64    the exact fp64 matrix dist [m][n] (host) through the same index.  Both return PR_EINVAL for a non-conforming
+ *                      row of either side. */
+int pr_bow_db_create(pr_ctx* ctx, int32_t max_sigs, int32_t cols, int32_t n_words, int64_t max_postings, pr_bow_db** out);
+void pr_bow_db_destroy(pr_ctx* ctx, pr_bow_db* db);
+int pr_bow_db_set(pr_ctx* ctx, pr_bow_db* db, const double* rows, int where, int32_t n);
+int pr_bow_db_append(pr_ctx* ctx, pr_bow_db* db, const double* rows, int where, int32_t n_new);
+int32_t pr_bow_db_count(const pr_bow_db* db);
+int pr_bow_match_topk_dev(pr_ctx* ctx, const pr_bow_db* db, const double* q, int32_t m, int32_t q_row0, int32_t db_row0,
+                          int32_t mask_width, int32_t k, int32_t* idx, double* score);
+int pr_bow_match_topk_f64(pr_ctx* ctx, const double* h1, int32_t m, const double* h2, int32_t n, int32_t cols,
+                          int32_t mask_width, int32_t k, int32_t* idx, double* score);
+int pr_bow_distance_f64(pr_ctx* ctx, const double* h1, int32_t m, const double* h2, int32_t n, int32_t cols, double* dist);
 
 /* BASELINE.json config 5, "fused SC + M2DP scoring" - NO reference counterpart (run_test.m handles one type per run);
  * build-defined as in SURVEY.md §6: score = [p z(sc_struct) + z(sc_int)] + [p z(m2dp_count) + z(m2dp_int)] with the row

@@ -14,6 +14,7 @@ SC_ARITH_F16X2, SC_ARITH_F32, SC_ARITH_F16 = 0, 1, 2
 NAN_EXCLUDE, NAN_FAIL = 0, 1
 WARN_NAN_ROWS, WARN_M2DP_SVD, WARN_F16_FALLBACK, WARN_ORDER_RESOLVED, WARN_ORDER_UNRESOLVED = 1, 2, 4, 8, 16
 WARN_BOW_TRUNCATED = 32
+WARN_BOW_ROWS = 64     # a non-conforming BoW query row answered -1 / NaN (pr_bow_match_topk_dev)
 ROLE_QUERY, ROLE_DB = 0, 1
 F64, F32 = 0, 1
 U8 = 2              # 8-bit images (pr_gist_generate*)
@@ -103,6 +104,14 @@ SYMBOLS = {
     "pr_fuse_select2_f64_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _dbl, _i32, _vp, _vp, _vp]),
     "pr_fuse_select_f64_dev": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _dbl, _i32, _vp, _vp, _vp]),
     "pr_match_topk_cols": (C.c_int, [_vp, C.c_int, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "pr_bow_db_create": (C.c_int, [_vp, _i32, _i32, _i32, C.c_int64, C.POINTER(_vp)]),
+    "pr_bow_db_destroy": (None, [_vp, _vp]),
+    "pr_bow_db_set": (C.c_int, [_vp, _vp, _vp, C.c_int, _i32]),
+    "pr_bow_db_append": (C.c_int, [_vp, _vp, _vp, C.c_int, _i32]),
+    "pr_bow_db_count": (_i32, [_vp]),
+    "pr_bow_match_topk_dev": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "pr_bow_match_topk_f64": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "pr_bow_distance_f64": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _i32, _vp]),
     "pr_delight_generate_dev": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _vp]),
     "pr_sc_distance": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _vp, _vp]),
     "pr_m2dp_distance": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _vp, _vp]),

@@ -262,6 +262,17 @@ void launch_bow_aggregate(hipStream_t st, const int64_t* offs, int N, int64_t n_
                           int* n_words, int* flags);   // node null: a vocabulary without words, every row empty
 void launch_bow_fill_words(hipStream_t st, int* feat_words, int64_t n, int v);
 void bow_release(void* state);                  // bow.cpp: frees a context's device vocabularies and scratch (pr_destroy, streams idle)
+// bow_match.hip — the inverted-file BoW matcher (see the file header); all pointers are device pointers
+void launch_bow_rows_check(hipStream_t st, const double* rows, int n, int cols, int n_words, int row_name0, int* counts,
+                           unsigned long long* total, int* bad);      // counts may be null (validation only)
+void launch_bow_scatter(hipStream_t st, const double* rows, int n, int cols, int j0, unsigned long long* cursor, int* prow, double* pw);
+int bow_scan_tiles(int nw);                     // tile sums the scan needs
+void launch_bow_scan(hipStream_t st, const int* counts, int nw, unsigned long long* tsum, unsigned long long* off, unsigned long long* cursor);
+void launch_bow_fold(hipStream_t st, int nw, const unsigned long long* moff, const int* mrow, const double* mw, const unsigned long long* toff,
+                     const int* trow, const double* tw, unsigned long long* noff, int* nrow, double* nwt);
+void launch_bow_score(hipStream_t st, int threads, const double* q, int m, int cols, int n_words, int q_row0, const unsigned long long* moff,
+                      const int* mrow, const double* mw, const unsigned long long* toff, const int* trow, const double* tw, int n, int db_row0,
+                      int mask_width, int k, double* acc, int32_t* idx, double* score, int* flag);   // k = 0: acc rows [m][n] keep d
 // pr_api.cpp: what gist.cpp and bow.cpp need of a context
 hipStream_t ctx_stream(pr_ctx* ctx);
 int ctx_device(pr_ctx* ctx);
@@ -269,6 +280,7 @@ void ctx_set_error(pr_ctx* ctx, const char* msg);
 void*& ctx_gist(pr_ctx* ctx);
 void*& ctx_bow(pr_ctx* ctx);
 int* ctx_bow_flag(pr_ctx* ctx);                 // [1] device word: a BoW row was truncated (PR_WARN_BOW_TRUNCATED at pr_take_warnings)
+int* ctx_bow_rows_flag(pr_ctx* ctx);            // [1] device word: a non-conforming BoW query row (PR_WARN_BOW_ROWS at pr_take_warnings)
 
 // prestage.hip — utils/pts_preprocess.h:135-232 on the GPU (see the file header); all pointers are device pointers
 int64_t prestage_cells(double range, int polar);          // dense cell-table length per pose

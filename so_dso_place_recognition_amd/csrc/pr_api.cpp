@@ -37,7 +37,7 @@ struct pr_ctx {
   hipEvent_t ev_m2[4] = {nullptr, nullptr, nullptr, nullptr};   // M2DP generation: two batches in flight (binning | singular pairs), launch_m2dp_bin_svd
   std::string err;
   int* d_svd_rows = nullptr;     // [1 + M2DP_SVD_ROWS_CAP] rows of the last pr_m2dp_generate* call whose leading singular pair did not converge
-  int* d_flags = nullptr;        // [4] deferred bits: [0] zero-norm row at pack time, [1] M2DP singular pair not converged, [2] a query was answered with fp64 row statistics, [3] more flagged queries than one stream-ordered pass resolves; [5] a BoW row was truncated
+  int* d_flags = nullptr;        // [4] deferred bits: [0] zero-norm row at pack time, [1] M2DP singular pair not converged, [2] a query was answered with fp64 row statistics, [3] more flagged queries than one stream-ordered pass resolves; [5] a BoW row was truncated; [6] a BoW query row was not conforming
   bool sc_online_h = false;      // PR_SC_ONLINE=h: calls of up to 8 queries through sc_match_h.hip's one-group form (the default until round 5)
   double* d_twiddle = nullptr;   // cos[60], sin[60] of 2*pi*t/60
   float* d_cst = nullptr;        // SC stage-2 constants [31][2][64]
@@ -171,13 +171,17 @@ size_t sigset_floats(int type, int role, int32_t max_sigs, int* groups, int sc_m
 }
 
 int check_flags(pr_ctx* ctx) {
-  int h[6];                      // h[4] is not a deferred bit (ScBin::viol) and stays as it is
+  int h[7];                      // h[4] is not a deferred bit (ScBin::viol) and stays as it is
   PR_HIP(ctx, hipMemcpyAsync(h, ctx->d_flags, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
   PR_HIP(ctx, hipStreamSynchronize(ctx->stream));
   if (h[0] || h[1] || h[2] || h[3]) PR_HIP(ctx, hipMemsetAsync(ctx->d_flags, 0, 4 * sizeof(int), ctx->stream));
   if (h[5]) {
     PR_HIP(ctx, hipMemsetAsync(ctx->d_flags + 5, 0, sizeof(int), ctx->stream));
     ctx->warnings |= PR_WARN_BOW_TRUNCATED;
+  }
+  if (h[6]) {
+    PR_HIP(ctx, hipMemsetAsync(ctx->d_flags + 6, 0, sizeof(int), ctx->stream));
+    ctx->warnings |= PR_WARN_BOW_ROWS;
   }
   if (h[1]) ctx->warnings |= PR_WARN_M2DP_SVD;
   if (h[2]) ctx->warnings |= PR_WARN_ORDER_RESOLVED;
@@ -2038,4 +2042,5 @@ void ctx_set_error(pr_ctx* ctx, const char* msg) { if (ctx) ctx->err = msg; else
 void*& ctx_gist(pr_ctx* ctx) { return ctx->gist; }
 void*& ctx_bow(pr_ctx* ctx) { return ctx->bow; }
 int* ctx_bow_flag(pr_ctx* ctx) { return ctx->d_flags + 5; }
+int* ctx_bow_rows_flag(pr_ctx* ctx) { return ctx->d_flags + 6; }
 }  // namespace pr

@@ -32,6 +32,7 @@ With one rank steps 2, 4, 6 and 7's gathers are skipped (pr_rerank_dev does 5 + 
 from __future__ import annotations
 
 import ctypes as C
+import weakref
 
 import numpy as np
 import torch
@@ -573,7 +574,11 @@ class CapturedMatch:
     def __init__(self, graph, stream, queries, idx, score):
         self.graph, self.stream, self.queries, self.idx, self.score = graph, stream, queries, idx, score
 
+    check = None          # optional callable run before a replay (BowMatcher.capture: raises once the graph is stale)
+
     def run(self, new_queries: torch.Tensor | None = None, sync: bool = True):
+        if self.check is not None:
+            self.check()
         if new_queries is not None:
             self.stream.wait_stream(torch.cuda.current_stream(new_queries.device))   # whoever produced new_queries did it there
             new_queries.record_stream(self.stream)
@@ -617,6 +622,127 @@ class FusedMatcher(_Base):
     def match(self, sc_queries: torch.Tensor, m2dp_queries: torch.Tensor, mask_width: int = 0, p_weight: float = 2.0, k: int = 1,
               db_row0: int = 0, q_row0: int = 0, group=None, f16_fallback: bool = True, exact_order: bool = True):
         return self._match((sc_queries, m2dp_queries), mask_width, p_weight, k, db_row0, q_row0, group, False, f16_fallback, exact_order, None)
+
+
+class BowMatcher(_Base):
+    """BoW (processBoW.m + run_test.m:47-57) against a device-resident inverted file (pr_bow_db): scores are the reference's fp64 values
+    bit for bit and the order is its double-precision order, for conforming rows (include/place_recognition.h).  The DB grows in place
+    (append_database: a tail segment folded into the main lists when full) and shards like Matcher's plain path: every rank holds rows
+    [db_row0, db_row0 + n) and all queries, returns its own top-k by GLOBAL row, the lists are merged by pr_merge_topk_dev.
+    Rows: float64 device tensors [2 n, cols] (ids | weights per image, as bow_generate_torch writes them; taken without a copy).
+    max_postings: words over all DB rows the index can hold (default max_db * (cols - 1), every row full)."""
+    plain = True
+
+    def __init__(self, max_queries: int, max_db: int, cols: int, n_words: int, ctx: Context | None = None, device: int | None = None,
+                 max_postings: int | None = None):
+        self._init_ctx(ctx, device)
+        self._spec = (max_queries, max_db, cols, n_words)
+        self.max_queries, self.max_db, self.cols, self.n_words = max_queries, max_db, cols, n_words
+        self.rows_per_sig, self.sig_len = 2, cols
+        self.db = C.c_void_p()
+        mp = max_db * max(cols - 1, 0) if max_postings is None else int(max_postings)
+        self.ctx.check(self.lib.pr_bow_db_create(self.ctx.h, int(max_db), int(cols), int(n_words), int(mp), C.byref(self.db)))
+        self.n = 0
+        self._q_sig = None
+        self.generation = 0            # counts set / append calls: a captured match is valid for the generation it was captured at
+
+    @property
+    def descs(self):
+        return (self,)
+
+    def close(self):
+        super().close()
+        if self.db:
+            self.lib.pr_bow_db_destroy(self.ctx.h, self.db)
+            self.db = None
+
+    def _rows(self, rows: torch.Tensor) -> int:
+        if not (rows.is_cuda and rows.dtype == torch.float64 and rows.is_contiguous() and rows.dim() == 2 and rows.shape[1] == self.cols
+                and rows.shape[0] % 2 == 0):
+            raise ValueError(f"BoW rows must be a contiguous float64 CUDA tensor [2 n, {self.cols}]")
+        return rows.shape[0] // 2
+
+    def pack_database(self, rows: torch.Tensor):
+        """Replaces the DB with `rows` and builds the index (pr_bow_db_set: synchronises; PRError naming the first non-conforming row)."""
+        n = self._rows(rows)
+        self._enter()
+        self.generation += 1
+        self.ctx.check(self.lib.pr_bow_db_set(self.ctx.h, self.db, _dptr(rows), _lib.DEVICE, n))
+        self.n = int(self.lib.pr_bow_db_count(self.db))
+
+    def reserve_database(self, rows: torch.Tensor | None = None):
+        """A DB that grows: the index has its capacity from construction, so this only starts it (empty, or with `rows`)."""
+        if rows is None:
+            rows = torch.empty((0, self.cols), dtype=torch.float64, device=self.dev)
+        self.pack_database(rows)
+
+    def append_database(self, rows: torch.Tensor):
+        """Rows [n, n + n_new) (pr_bow_db_append: the tail's lists, or a fold of a full tail; synchronises)."""
+        k = self._rows(rows)
+        self._enter()
+        self.generation += 1
+        self.ctx.check(self.lib.pr_bow_db_append(self.ctx.h, self.db, _dptr(rows), _lib.DEVICE, k))
+        self.n = int(self.lib.pr_bow_db_count(self.db))
+
+    def local_phase1(self, queries: torch.Tensor):
+        """The plain path has no row statistics: zero moments [m, 2, 3]."""
+        m = self._rows(queries)
+        assert m <= self.max_queries
+        self._q_sig, self._m = queries, m
+        return torch.zeros((m, 2, 3), dtype=torch.float64, device=self.dev)
+
+    def local_select(self, mom_all, G, mask_width, p_weight, k, db_row0, q_row0):
+        """This shard's top-k (idx int32 [m, k] global rows, score float64 [m, k]) - pr_bow_match_topk_dev."""
+        m = self._m
+        idx = torch.empty((m, k), dtype=torch.int32, device=self.dev)
+        score = torch.empty((m, k), dtype=torch.float64, device=self.dev)
+        self._enter()
+        self.ctx.check(self.lib.pr_bow_match_topk_dev(self.ctx.h, self.db, _dptr(self._q_sig), m, int(q_row0), int(db_row0), int(mask_width),
+                                                      int(k), _dptr(idx), _dptr(score)))
+        self._leave()
+        return idx, score
+
+    def match(self, queries: torch.Tensor, mask_width: int = 0, k: int = 1, db_row0: int = 0, q_row0: int = 0, group=None,
+              force_exchange: bool = False, mark=None):
+        """(idx int32 [m,k] GLOBAL DB rows, score float64 [m,k]) device tensors; no host synchronisation.  A non-conforming query row gets
+        -1 / NaN and raises _lib.WARN_BOW_ROWS (take_warnings)."""
+        G = _world(group)
+        return sharded_topk(lambda: self.local_phase1(queries),
+                            lambda mom_all, G_: self.local_select(mom_all, G_, mask_width, 0.0, k, db_row0, q_row0),
+                            k, group if (G > 1 or force_exchange) else None, G, merge=self.merge, force_exchange=force_exchange, mark=mark)
+
+    @classmethod
+    def on_new_stream(cls, max_queries: int, max_db: int, cols: int, n_words: int, device: int | None = None, **kw):
+        """A matcher whose library context lives on a stream of its own (`.stream`), as capture() needs."""
+        device = torch.cuda.current_device() if device is None else device
+        st = torch.cuda.Stream(device)
+        with torch.cuda.stream(st):
+            mt = cls(max_queries, max_db, cols, n_words, ctx=_stream_context(device), **kw)
+        mt.stream = st
+        return mt
+
+    def capture(self, queries: torch.Tensor, mask_width: int = 0, k: int = 1, db_row0: int = 0, q_row0: int = 0):
+        """One single-rank match() of the STATIC tensor `queries` as a hipGraph (CapturedMatch; the matcher must come from on_new_stream).
+        The graph holds the DB's row count and index buffers as they were at capture; pack_database / append_database change them (an
+        append rebuilds the tail lists with rows the graph does not know, a fold swaps the main buffers), so after either the graph must be
+        captured again: its run() raises RuntimeError instead of replaying it."""
+        st = self.stream
+        with torch.cuda.stream(st):
+            assert self.ctx.stream == int(st.cuda_stream)
+            self.match(queries, mask_width, k, db_row0, q_row0)
+            st.synchronize()
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, stream=st):
+                idx, score = self.match(queries, mask_width, k, db_row0, q_row0)
+        cap = CapturedMatch(g, st, queries, idx, score)
+        gen, mt = self.generation, weakref.ref(self)
+
+        def valid():
+            m_ = mt()
+            if m_ is None or m_.db is None or m_.generation != gen:
+                raise RuntimeError("BowMatcher.capture: the database changed (or was closed) since this graph was captured; capture again")
+        cap.check = valid
+        return cap
 
 
 def _world(group) -> int:

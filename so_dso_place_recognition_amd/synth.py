@@ -179,6 +179,48 @@ def bow_signatures(seed: int, n: int, cols: int = 120, vocab: int = 400, fill=(2
     return out
 
 
+def bow_signatures_torch(seed: int, n: int, cols: int = 120, vocab: int = 400, fill=(20, 90), zipf: float | None = None, device="cuda",
+                         chunk: int = 8192):
+    """bow_signatures' layout drawn on the device (torch generator, not the numpy stream): [2 n][cols] float64, per image a row of
+    distinct word ids in ascending order and a row of L1-normalised weights, both padded with -1.  A row's word count is uniform in
+    `fill` (at most cols; words past column cols - 2 are never read, as in the reference).  zipf = s: word ranks drawn with probability
+    ~ rank^-s, ranks mapped to ids by a random permutation (near-stop words whose lists hold a large share of the rows); None: uniform.
+    Duplicate draws are dropped, so with a steep zipf a row may get fewer words than drawn."""
+    import torch
+    g = torch.Generator(device=device)
+    g.manual_seed(int(seed))
+    hi = max(0, min(int(fill[1]), cols, vocab))
+    lo = min(int(fill[0]), hi)
+    S = max(2 * hi + 8, 1)
+    if zipf is not None:
+        cdf = torch.cumsum(torch.arange(1, vocab + 1, dtype=torch.float64, device=device) ** (-float(zipf)), 0)
+        cdf /= cdf[-1].clone()
+        perm = torch.randperm(vocab, generator=g, device=device)
+    out = torch.full((2 * n, cols), -1.0, dtype=torch.float64, device=device)
+    for s0 in range(0, n, chunk):
+        r = min(n, s0 + chunk) - s0
+        if zipf is not None:
+            u = torch.rand((r, S), generator=g, device=device, dtype=torch.float64)
+            w = perm[torch.searchsorted(cdf, u).clamp_(max=vocab - 1)]
+        else:
+            w = torch.randint(0, vocab, (r, S), generator=g, device=device)
+        w, _ = torch.sort(w, dim=1)
+        dup = torch.zeros_like(w, dtype=torch.bool)
+        dup[:, 1:] = w[:, 1:] == w[:, :-1]
+        key = torch.where(dup, torch.full_like(w, 2, dtype=torch.float64), torch.rand((r, S), generator=g, device=device, dtype=torch.float64))
+        ks, ki = torch.sort(key, dim=1)                      # the distinct words in random order
+        k = torch.randint(lo, hi + 1, (r,), generator=g, device=device)
+        valid = (torch.arange(hi, device=device)[None, :] < k[:, None]) & (ks[:, :hi] < 2)
+        sel, _ = torch.sort(torch.where(valid, torch.gather(w, 1, ki[:, :hi]), torch.full_like(w[:, :hi], vocab)), dim=1)
+        keep = sel < vocab
+        wt = torch.where(keep, torch.rand((r, hi), generator=g, device=device, dtype=torch.float64) + 0.05, torch.zeros((), dtype=torch.float64,
+                                                                                                                      device=device))
+        wt = wt / wt.sum(1, keepdim=True).clamp_min(1e-300)
+        out[2 * s0:2 * (s0 + r):2, :hi] = torch.where(keep, sel.to(torch.float64), torch.full_like(wt, -1.0))
+        out[2 * s0 + 1:2 * (s0 + r):2, :hi] = torch.where(keep, wt, torch.full_like(wt, -1.0))
+    return out
+
+
 def gist_signatures(seed: int, n: int, cols: int = 96):
     rng = np.random.default_rng(seed)
     return np.abs(rng.normal(0.1, 0.05, size=(n, cols)))
