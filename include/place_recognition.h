@@ -239,6 +239,43 @@ int pr_bow_match_topk_f64(pr_ctx* ctx, const double* h1, int32_t m, const double
                           int32_t mask_width, int32_t k, int32_t* idx, double* score);
 int pr_bow_distance_f64(pr_ctx* ctx, const double* h1, int32_t m, const double* h2, int32_t n, int32_t cols, double* dist);
 
+/* GIST matching against a device-resident database, exact in fp64: for rows a, b of cols doubles d = ((0 + t_0) + t_1) + ... with
+ * t_c = RN(RN(a_c - b_c)^2), ascending columns, no contraction (processGIST.m:7 read left to right), then run_test.m:47-57 generalised
+ * to top-k as for pr_bow_match_topk_dev: masked entries +Inf, ascending by (score, index), ties -> lower index, NaN distances (a NaN in
+ * either row) never selected, -1 / NaN fill.  Indices and score bits are those of that arithmetic for every input.  A coarse pass on the
+ * f16 matrix cores lists k + 8 candidates per query and DB slab, their distances are re-evaluated in fp64, and a query whose list is not
+ * provably complete under a worst-case error bound is answered from its exact row.
+ *   pr_gist_db_create   capacity max_sigs rows of cols doubles (any cols >= 1); all device memory, scratch included, is allocated here
+ *                       (pr_gist_db_bytes reports it).  Environment: PR_GIST_EXACT=1 answers every query from its exact row;
+ *                       PR_GIST_CENTRE=0 packs the rows without subtracting their mean (same results, a wider bound: for A/B runs).
+ *   pr_gist_db_set      replaces the contents with rows [n][cols] (where: PR_HOST | PR_DEVICE).
+ *   pr_gist_db_append   adds rows count .. count + n_new - 1; any sequence of appends gives the results of one set of the same rows.
+ *                       Both synchronise; beyond max_sigs they return PR_ENOMEM.
+ *   pr_gist_db_set_exact  on != 0: every query takes the exact-row path (the independent implementation tests compare against).
+ *   pr_gist_match_topk_dev  q DEVICE [m][cols]; idx DEVICE [m][k] global rows (db_row0 + local), score DEVICE f64 [m][k]
+ *                       (pr_merge_topk_dev merges shards unchanged); the mask compares q_row0 + i with db_row0 + j.  k <= 128.
+ *                       Stream-ordered, allocation-free, graph-capturable.
+ *                       The call writes the database's scratch: one match at a time per database (two contexts must not match the
+ *                       same database concurrently).
+ *   pr_gist_flagged_count  of the m queries of this context's last pr_gist_match_topk_dev (m must be that call's m, else PR_EINVAL; the
+ *                       database must still exist), how many were answered from their exact row (synchronises).
+ *   pr_gist_match_topk_f64  the host form of run_test.m:32-57 for 'gist' in fp64 (h1 [m][cols], h2 [n][cols] host).
+ *   pr_gist_distance_f64    the exact fp64 matrix dist [m][n] (host). */
+typedef struct pr_gist_db pr_gist_db;
+int pr_gist_db_create(pr_ctx* ctx, int32_t max_sigs, int32_t cols, pr_gist_db** out);
+void pr_gist_db_destroy(pr_ctx* ctx, pr_gist_db* db);
+int pr_gist_db_set(pr_ctx* ctx, pr_gist_db* db, const double* rows, int where, int32_t n);
+int pr_gist_db_append(pr_ctx* ctx, pr_gist_db* db, const double* rows, int where, int32_t n_new);
+int32_t pr_gist_db_count(const pr_gist_db* db);
+int64_t pr_gist_db_bytes(const pr_gist_db* db);
+void pr_gist_db_set_exact(pr_gist_db* db, int on);
+int pr_gist_match_topk_dev(pr_ctx* ctx, const pr_gist_db* db, const double* q, int32_t m, int32_t q_row0, int32_t db_row0,
+                           int32_t mask_width, int32_t k, int32_t* idx, double* score);
+int pr_gist_flagged_count(pr_ctx* ctx, int32_t m, int32_t* count);
+int pr_gist_match_topk_f64(pr_ctx* ctx, const double* h1, int32_t m, const double* h2, int32_t n, int32_t cols,
+                           int32_t mask_width, int32_t k, int32_t* idx, double* score);
+int pr_gist_distance_f64(pr_ctx* ctx, const double* h1, int32_t m, const double* h2, int32_t n, int32_t cols, double* dist);
+
 /* BASELINE.json config 5, "fused SC + M2DP scoring" - NO reference counterpart (run_test.m handles one type per run);
  * build-defined as in SURVEY.md §6: score = [p z(sc_struct) + z(sc_int)] + [p z(m2dp_count) + z(m2dp_int)] with the row
  * z-scores of run_test.m:40, then mask and row minimum (run_test.m:47-57).  sc: [m][2400], m2dp: [4 m][384] of the same places.

@@ -678,6 +678,34 @@ def bow_match_topk(hist1, hist2, mask_width=0, k=1, ctx: Context | None = None):
     return idx, sc
 
 
+def _gist_pair(hist1, hist2):
+    h1 = np.ascontiguousarray(hist1, np.float64); h2 = np.ascontiguousarray(hist2, np.float64)
+    if h1.ndim != 2 or h2.ndim != 2 or h1.shape[1] != h2.shape[1] or h1.shape[1] < 1:
+        raise ValueError("GIST files hold one row of the same width per image")
+    return h1, h2, h1.shape[0], h2.shape[0]
+
+
+def gist_distance_f64(hist1, hist2, ctx: Context | None = None):
+    """processGIST(hist1, hist2) in fp64 as the reference evaluates it (processGIST.m:7: differences, squares, sum in ascending column
+    order, no contraction; pr_gist_distance_f64): float64 [m, n], bit for bit."""
+    ctx = ctx or default_context()
+    h1, h2, m, n = _gist_pair(hist1, hist2)
+    d = np.empty((m, n), np.float64)
+    ctx.check(ctx.lib.pr_gist_distance_f64(ctx.h, _ptr(h1), m, _ptr(h2), n, h1.shape[1], _ptr(d)))
+    return d
+
+
+def gist_match_topk(hist1, hist2, mask_width=0, k=1, ctx: Context | None = None):
+    """run_test.m:32-57 for 'gist' in fp64 (pr_gist_match_topk_f64): (idx int32 [m,k], score float64 [m,k]), the reference's
+    double-precision ranking (ties -> lower index, -1 / NaN when fewer than k candidates).  k <= 128.
+    match_topk('gist', ...) keeps the fp32 all-pairs path."""
+    ctx = ctx or default_context()
+    h1, h2, m, n = _gist_pair(hist1, hist2)
+    idx = np.empty((m, k), np.int32); sc = np.empty((m, k), np.float64)
+    ctx.check(ctx.lib.pr_gist_match_topk_f64(ctx.h, _ptr(h1), m, _ptr(h2), n, h1.shape[1], int(mask_width), int(k), _ptr(idx), _ptr(sc)))
+    return idx, sc
+
+
 def match_topk(type_, hist1, hist2, mask_width=0, p_weight=2.0, k=1, ctx: Context | None = None):
     """run_test.m:26-57 generalised to top-k: returns (idx int32 [m,k] 0-based, score float64 [m,k] as MATLAB holds it;
     float32 for gist / bow, whose distances are a single fp32 matrix)."""

@@ -273,6 +273,23 @@ void launch_bow_fold(hipStream_t st, int nw, const unsigned long long* moff, con
 void launch_bow_score(hipStream_t st, int threads, const double* q, int m, int cols, int n_words, int q_row0, const unsigned long long* moff,
                       const int* mrow, const double* mw, const unsigned long long* toff, const int* trow, const double* tw, int n, int db_row0,
                       int mask_width, int k, double* acc, int32_t* idx, double* score, int* flag);   // k = 0: acc rows [m][n] keep d
+// gist_match.hip — the two-stage exact GIST matcher (see the file header); all pointers are device pointers.  KS = K-steps of 16 columns
+// (a multiple of 4), S = DB slabs, C = list length per (query, slab), S * C <= 2048.
+void launch_gist_mean(hipStream_t st, const double* rows, int nr, int cols, double* mu);
+void launch_gist_pack(hipStream_t st, const double* rows, int n, int cols, int KS, const double* mu, int row0, void* img, float* nd, float* rs,
+                      unsigned* stat /* null (queries) | [0] max nd, [1] max rs as float bits */);
+size_t gist_coarse_lds_bytes(int KS, int C);
+void launch_gist_coarse(hipStream_t st, const void* qpk, const float* qn, int m, const void* dpk, const float* dn, int n, int KS, int S, int C,
+                        int q_row0, int db_row0, int mask_width, int* cand /* [m][S][C] local rows, -1 = empty */, float* wout /* [m][S] */);
+void launch_gist_rerank(hipStream_t st, const double* q, const double* raw, int cols, int KP, int m, int S, int C, const int* cand,
+                        const float* wout, const float* qn, const float* qr, const unsigned* dstat, int db_row0, int k, int32_t* idx,
+                        double* score, int* flags /* [m] 1: not provably complete */);
+void launch_gist_compact(hipStream_t st, const int* flags, int m, int* list, int* cnt /* [0] = count, [1] += count */);
+void launch_gist_fill(hipStream_t st, int* p, int n, int v);
+void launch_gist_xdist(hipStream_t st, const double* q, const double* raw, int cols, int n, const int* list, const int* cnt, int offset,
+                       int direct_count, int cap, double* out, size_t ld, int q_row0, int db_row0, int mask_width);
+void launch_gist_xselect(hipStream_t st, const double* rows, size_t ld, int n, const int* list, const int* cnt, int offset, int cap, int db_row0,
+                         int k, int32_t* idx, double* score);
 // pr_api.cpp: what gist.cpp and bow.cpp need of a context
 hipStream_t ctx_stream(pr_ctx* ctx);
 int ctx_device(pr_ctx* ctx);

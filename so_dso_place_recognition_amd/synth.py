@@ -226,6 +226,26 @@ def gist_signatures(seed: int, n: int, cols: int = 96):
     return np.abs(rng.normal(0.1, 0.05, size=(n, cols)))
 
 
+def gist_signatures_torch(seed: int, n: int, cols: int = 512, device="cuda", clusters: int = 0, cluster_size: int = 40, eps: float = 1e-6,
+                          chunk: int = 16384):
+    """gist_signatures' distribution (|N(0.1, 0.05)| entries) drawn on the device from a torch generator of its own (not the numpy
+    stream): float64 [n, cols].  clusters > 0 plants that many runs of `cluster_size` consecutive near-copies `base + eps * noise`
+    (noise standard normal; eps = 0: exact duplicates) at evenly spaced rows - a vehicle standing still."""
+    import torch
+    g = torch.Generator(device=device)
+    g.manual_seed(int(seed))
+    out = torch.empty((n, cols), dtype=torch.float64, device=device)
+    for s0 in range(0, n, chunk):
+        r = min(n, s0 + chunk) - s0
+        out[s0:s0 + r] = (torch.randn((r, cols), generator=g, device=device, dtype=torch.float64) * 0.05 + 0.1).abs_()
+    cs = min(int(cluster_size), n)
+    for c in range(int(clusters)):
+        r0 = min(n - cs, (n // (clusters + 1)) * (c + 1))
+        base = out[r0].clone()
+        out[r0:r0 + cs] = base[None, :] + float(eps) * torch.randn((cs, cols), generator=g, device=device, dtype=torch.float64)
+    return out
+
+
 # ----------------------------------------------------------------------------- the same samplers on a torch device
 # Bit-identical to the numpy versions above (uint64 arithmetic carried in int64 two's complement: add / multiply wrap,
 # logical shifts by masking), so that full-size inputs (10^5 - 10^6 signatures, 5000 x 50 000 points) are drawn in HBM in
