@@ -276,6 +276,45 @@ int pr_gist_match_topk_f64(pr_ctx* ctx, const double* h1, int32_t m, const doubl
                            int32_t mask_width, int32_t k, int32_t* idx, double* score);
 int pr_gist_distance_f64(pr_ctx* ctx, const double* h1, int32_t m, const double* h2, int32_t n, int32_t cols, double* dist);
 
+/* DELIGHT matching against a device-resident database, exact in fp64 (processDELIGHT.m:7-37): for signatures a, b of 16 x 256 doubles and
+ * each of the four octant permutations (row r of a against row r ^ X of b, X = 0, 5, 6, 3): ts = tc = 0; for c = 0..255, for r = 0..15:
+ * sum = a + b, if (sum > 0) { ts += ((2 (a - b)) (a - b)) / sum; tc += 1 }; ts = ts / tc; d = the smallest ts (NaN never wins, +Inf when
+ * no bin is occupied), no contraction.  Then run_test.m:47-57 generalised to top-k as for pr_gist_match_topk_dev: masked entries +Inf,
+ * ascending by (score, index), ties -> lower index, NaN never selected, -1 / NaN fill.  Indices and score bits are those of that
+ * arithmetic for every input.  A coarse fp32 pass (the arithmetic of pr_match_topk's DELIGHT kernel, no m x n matrix) lists k + 8
+ * candidates per query and DB slab, their distances are re-evaluated in fp64, and a query whose list is not provably complete under a
+ * worst-case error bound is answered from its exact row.  A signature with an element that is not an integer in
+ * [0, 2^24] is outside the coarse pass: as a query it takes the exact-row path, as a DB row it sends every query there.
+ *   pr_delight_db_create   capacity max_sigs signatures; all device memory, scratch included, is allocated here (pr_delight_db_bytes
+ *                       reports it: 49 668 bytes per signature + scratch).  Environment: PR_DELIGHT_EXACT=1 answers every query from
+ *                       its exact row.
+ *   pr_delight_db_set      replaces the contents with rows [16 n][256] (where: PR_HOST | PR_DEVICE).
+ *   pr_delight_db_append   adds signatures count .. count + n_new - 1; any sequence of appends equals one set of the same rows.
+ *                       Both synchronise; beyond max_sigs they return PR_ENOMEM.
+ *   pr_delight_db_set_exact  on != 0: every query takes the exact-row path (the independent implementation tests compare against).
+ *   pr_delight_match_topk_dev  q DEVICE [16 m][256]; idx DEVICE [m][k] global rows (db_row0 + local), score DEVICE f64 [m][k]
+ *                       (pr_merge_topk_dev merges shards unchanged); the mask compares q_row0 + i with db_row0 + j.  k <= 128.
+ *                       Stream-ordered, allocation-free, graph-capturable.  The call writes the database's scratch: one match at a
+ *                       time per database.
+ *   pr_delight_flagged_count  of the m queries of this context's last pr_delight_match_topk_dev (m must be that call's m, else
+ *                       PR_EINVAL; the database must still exist), how many were answered from their exact row (synchronises).
+ *   pr_delight_match_topk_f64  the host form of run_test.m:32-57 for 'delight' in fp64 (h1 [16 m][256], h2 [16 n][256] host).
+ *   pr_delight_distance_f64    the exact fp64 matrix dist [m][n] (host). */
+typedef struct pr_delight_db pr_delight_db;
+int pr_delight_db_create(pr_ctx* ctx, int32_t max_sigs, pr_delight_db** out);
+void pr_delight_db_destroy(pr_ctx* ctx, pr_delight_db* db);
+int pr_delight_db_set(pr_ctx* ctx, pr_delight_db* db, const double* rows, int where, int32_t n);
+int pr_delight_db_append(pr_ctx* ctx, pr_delight_db* db, const double* rows, int where, int32_t n_new);
+int32_t pr_delight_db_count(const pr_delight_db* db);
+int64_t pr_delight_db_bytes(const pr_delight_db* db);
+void pr_delight_db_set_exact(pr_delight_db* db, int on);
+int pr_delight_match_topk_dev(pr_ctx* ctx, const pr_delight_db* db, const double* q, int32_t m, int32_t q_row0, int32_t db_row0,
+                              int32_t mask_width, int32_t k, int32_t* idx, double* score);
+int pr_delight_flagged_count(pr_ctx* ctx, int32_t m, int32_t* count);
+int pr_delight_match_topk_f64(pr_ctx* ctx, const double* h1, int32_t m, const double* h2, int32_t n, int32_t mask_width, int32_t k,
+                              int32_t* idx, double* score);
+int pr_delight_distance_f64(pr_ctx* ctx, const double* h1, int32_t m, const double* h2, int32_t n, double* dist);
+
 /* BASELINE.json config 5, "fused SC + M2DP scoring" - NO reference counterpart (run_test.m handles one type per run);
  * build-defined as in SURVEY.md §6: score = [p z(sc_struct) + z(sc_int)] + [p z(m2dp_count) + z(m2dp_int)] with the row
  * z-scores of run_test.m:40, then mask and row minimum (run_test.m:47-57).  sc: [m][2400], m2dp: [4 m][384] of the same places.

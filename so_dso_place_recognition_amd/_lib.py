@@ -123,6 +123,17 @@ SYMBOLS = {
     "pr_gist_flagged_count": (C.c_int, [_vp, _i32, C.POINTER(_i32)]),
     "pr_gist_match_topk_f64": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     "pr_gist_distance_f64": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _i32, _vp]),
+    "pr_delight_db_create": (C.c_int, [_vp, _i32, C.POINTER(_vp)]),
+    "pr_delight_db_destroy": (None, [_vp, _vp]),
+    "pr_delight_db_set": (C.c_int, [_vp, _vp, _vp, C.c_int, _i32]),
+    "pr_delight_db_append": (C.c_int, [_vp, _vp, _vp, C.c_int, _i32]),
+    "pr_delight_db_count": (_i32, [_vp]),
+    "pr_delight_db_bytes": (C.c_int64, [_vp]),
+    "pr_delight_db_set_exact": (None, [_vp, C.c_int]),
+    "pr_delight_match_topk_dev": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "pr_delight_flagged_count": (C.c_int, [_vp, _i32, C.POINTER(_i32)]),
+    "pr_delight_match_topk_f64": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp]),
+    "pr_delight_distance_f64": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _vp]),
     "pr_delight_generate_dev": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _vp]),
     "pr_sc_distance": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _vp, _vp]),
     "pr_m2dp_distance": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _vp, _vp]),

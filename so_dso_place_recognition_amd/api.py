@@ -706,6 +706,35 @@ def gist_match_topk(hist1, hist2, mask_width=0, k=1, ctx: Context | None = None)
     return idx, sc
 
 
+def _delight_pair(hist1, hist2):
+    h1 = np.ascontiguousarray(hist1, np.float64); h2 = np.ascontiguousarray(hist2, np.float64)
+    if h1.ndim != 2 or h2.ndim != 2 or h1.shape[1] != 256 or h2.shape[1] != 256 or h1.shape[0] % 16 or h2.shape[0] % 16:
+        raise ValueError("DELIGHT files hold 16 rows of 256 bins per cloud")
+    return h1, h2, h1.shape[0] // 16, h2.shape[0] // 16
+
+
+def delight_distance_f64(hist1, hist2, ctx: Context | None = None):
+    """processDELIGHT(hist1, hist2) in fp64 as the reference evaluates it (processDELIGHT.m:7-37: per permutation the terms of the
+    occupied bins added in column-major order, divided by their count, the smallest of the four; no contraction;
+    pr_delight_distance_f64): float64 [m, n], bit for bit."""
+    ctx = ctx or default_context()
+    h1, h2, m, n = _delight_pair(hist1, hist2)
+    d = np.empty((m, n), np.float64)
+    ctx.check(ctx.lib.pr_delight_distance_f64(ctx.h, _ptr(h1), m, _ptr(h2), n, _ptr(d)))
+    return d
+
+
+def delight_match_topk(hist1, hist2, mask_width=0, k=1, ctx: Context | None = None):
+    """run_test.m:32-57 for 'delight' in fp64 (pr_delight_match_topk_f64): (idx int32 [m,k], score float64 [m,k]), the reference's
+    double-precision ranking (ties -> lower index, -1 / NaN when fewer than k candidates).  k <= 128.
+    match_topk('delight', ...) keeps the fp32 all-pairs path."""
+    ctx = ctx or default_context()
+    h1, h2, m, n = _delight_pair(hist1, hist2)
+    idx = np.empty((m, k), np.int32); sc = np.empty((m, k), np.float64)
+    ctx.check(ctx.lib.pr_delight_match_topk_f64(ctx.h, _ptr(h1), m, _ptr(h2), n, int(mask_width), int(k), _ptr(idx), _ptr(sc)))
+    return idx, sc
+
+
 def match_topk(type_, hist1, hist2, mask_width=0, p_weight=2.0, k=1, ctx: Context | None = None):
     """run_test.m:26-57 generalised to top-k: returns (idx int32 [m,k] 0-based, score float64 [m,k] as MATLAB holds it;
     float32 for gist / bow, whose distances are a single fp32 matrix)."""

@@ -290,6 +290,18 @@ void launch_gist_xdist(hipStream_t st, const double* q, const double* raw, int c
                        int direct_count, int cap, double* out, size_t ld, int q_row0, int db_row0, int mask_width);
 void launch_gist_xselect(hipStream_t st, const double* rows, size_t ld, int n, const int* list, const int* cnt, int offset, int cap, int db_row0,
                          int k, int32_t* idx, double* score);
+// delight_match.hip — the two-stage exact DELIGHT matcher (see the file header); all pointers are device pointers.  S = DB slabs,
+// C = list length per (query, slab) <= 136, S * C <= 2048.  Selection and compaction of the exact rows: launch_gist_xselect / _compact.
+void launch_delight_dpack(hipStream_t st, const double* rows, int n, int row0, float* img, unsigned* mask, int* okflag,
+                          unsigned* stat /* null (queries) | [0] += rows that are not coarse-exact */);
+void launch_delight_coarse(hipStream_t st, const float* q, int m, const float* db, const unsigned* dbmask, int n, int S, int C, int q_row0,
+                           int db_row0, int mask_width, int* cand /* [m][S][C] local rows, -1 = empty */, float* ckey /* [m][S][C] */,
+                           float* wout /* [m][S] */);
+void launch_delight_rerank(hipStream_t st, const double* q, const double* raw, int m, int S, int C, const int* cand, const float* ckey,
+                           const float* wout, const int* qok, const unsigned* dstat, int db_row0, int k, int32_t* idx, double* score,
+                           int* flags /* [m] 1: not provably complete */);
+void launch_delight_xdist(hipStream_t st, const double* q, const double* raw, int n, const int* list, const int* cnt, int offset,
+                          int direct_count, int cap, double* out, size_t ld, int q_row0, int db_row0, int mask_width);
 // pr_api.cpp: what gist.cpp and bow.cpp need of a context
 hipStream_t ctx_stream(pr_ctx* ctx);
 int ctx_device(pr_ctx* ctx);

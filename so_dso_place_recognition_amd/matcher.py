@@ -880,6 +880,142 @@ class GistMatcher(_Base):
         return cap
 
 
+class DelightMatcher(_Base):
+    """DELIGHT (processDELIGHT.m + run_test.m:47-57) against a device-resident database (pr_delight_db): indices and fp64 score bits are
+    the reference's double-precision answer for every input.  A coarse fp32 pass lists candidates without an m x n matrix, their
+    distances are re-evaluated in fp64, and a query whose list is not provably complete is answered from its exact row.
+    The DB grows in place and shards like GistMatcher: every rank holds signatures [db_row0, db_row0 + n) and all queries, the lists are
+    merged by pr_merge_topk_dev.  Rows: float64 device tensors [16 n, 256], as delight_generate_torch writes them (taken without a copy).
+    exact=True (or PR_DELIGHT_EXACT=1): every query takes the exact-row path."""
+    plain = True
+
+    def __init__(self, max_queries: int, max_db: int, ctx: Context | None = None, device: int | None = None, exact: bool = False):
+        if min(int(max_queries), int(max_db)) < 1:
+            raise ValueError("DelightMatcher: max_queries and max_db must be >= 1")
+        self._init_ctx(ctx, device)
+        self._spec = (max_queries, max_db)
+        self.max_queries, self.max_db, self.cols = max_queries, max_db, 256
+        self.rows_per_sig, self.sig_len = 16, 256
+        self.db = C.c_void_p()
+        self.ctx.check(self.lib.pr_delight_db_create(self.ctx.h, int(max_db), C.byref(self.db)))
+        if exact:
+            self.lib.pr_delight_db_set_exact(self.db, 1)
+        self.n = 0
+        self._q_sig = None
+        self.generation = 0            # counts set / append calls: a captured match is valid for the generation it was captured at
+
+    @property
+    def descs(self):
+        return (self,)
+
+    @property
+    def device_bytes(self) -> int:
+        """Device memory the database holds, scratch included (all of it allocated at construction)."""
+        return int(self.lib.pr_delight_db_bytes(self.db))
+
+    def set_exact(self, on: bool):
+        self.lib.pr_delight_db_set_exact(self.db, 1 if on else 0)
+
+    def close(self):
+        super().close()
+        if self.db:
+            self.lib.pr_delight_db_destroy(self.ctx.h, self.db)
+            self.db = None
+
+    def _rows(self, rows: torch.Tensor) -> int:
+        if not (rows.is_cuda and rows.dtype == torch.float64 and rows.is_contiguous() and rows.dim() == 2 and rows.shape[1] == 256
+                and rows.shape[0] % 16 == 0):
+            raise ValueError("DELIGHT rows must be a contiguous float64 CUDA tensor [16 n, 256]")
+        return rows.shape[0] // 16
+
+    def pack_database(self, rows: torch.Tensor):
+        """Replaces the DB with `rows` (pr_delight_db_set: synchronises)."""
+        n = self._rows(rows)
+        self._enter()
+        self.generation += 1
+        self.ctx.check(self.lib.pr_delight_db_set(self.ctx.h, self.db, _dptr(rows), _lib.DEVICE, n))
+        self.n = int(self.lib.pr_delight_db_count(self.db))
+
+    def reserve_database(self, rows: torch.Tensor | None = None):
+        """A DB that grows: the capacity is there from construction, so this only starts it (empty, or with `rows`)."""
+        if rows is None:
+            rows = torch.empty((0, 256), dtype=torch.float64, device=self.dev)
+        self.pack_database(rows)
+
+    def append_database(self, rows: torch.Tensor):
+        """Rows [n, n + n_new) (pr_delight_db_append; synchronises)."""
+        k = self._rows(rows)
+        self._enter()
+        self.generation += 1
+        self.ctx.check(self.lib.pr_delight_db_append(self.ctx.h, self.db, _dptr(rows), _lib.DEVICE, k))
+        self.n = int(self.lib.pr_delight_db_count(self.db))
+
+    def flagged_count(self) -> int:
+        """Queries of the last match() that were answered from their exact row (synchronises)."""
+        c = C.c_int32(0)
+        self._enter()
+        self.ctx.check(self.lib.pr_delight_flagged_count(self.ctx.h, int(self._m), C.byref(c)))
+        return int(c.value)
+
+    def local_phase1(self, queries: torch.Tensor):
+        """The plain path has no row statistics: zero moments [m, 2, 3]."""
+        m = self._rows(queries)
+        assert m <= self.max_queries
+        self._q_sig, self._m = queries, m
+        return torch.zeros((m, 2, 3), dtype=torch.float64, device=self.dev)
+
+    def local_select(self, mom_all, G, mask_width, p_weight, k, db_row0, q_row0):
+        """This shard's top-k (idx int32 [m, k] global rows, score float64 [m, k]) - pr_delight_match_topk_dev."""
+        m = self._m
+        idx = torch.empty((m, k), dtype=torch.int32, device=self.dev)
+        score = torch.empty((m, k), dtype=torch.float64, device=self.dev)
+        self._enter()
+        self.ctx.check(self.lib.pr_delight_match_topk_dev(self.ctx.h, self.db, _dptr(self._q_sig), m, int(q_row0), int(db_row0), int(mask_width),
+                                                       int(k), _dptr(idx), _dptr(score)))
+        self._leave()
+        return idx, score
+
+    def match(self, queries: torch.Tensor, mask_width: int = 0, k: int = 1, db_row0: int = 0, q_row0: int = 0, group=None,
+              force_exchange: bool = False, mark=None):
+        """(idx int32 [m,k] GLOBAL DB rows, score float64 [m,k]) device tensors; no host synchronisation."""
+        G = _world(group)
+        return sharded_topk(lambda: self.local_phase1(queries),
+                            lambda mom_all, G_: self.local_select(mom_all, G_, mask_width, 0.0, k, db_row0, q_row0),
+                            k, group if (G > 1 or force_exchange) else None, G, merge=self.merge, force_exchange=force_exchange, mark=mark)
+
+    @classmethod
+    def on_new_stream(cls, max_queries: int, max_db: int, device: int | None = None, **kw):
+        """A matcher whose library context lives on a stream of its own (`.stream`), as capture() needs."""
+        device = torch.cuda.current_device() if device is None else device
+        st = torch.cuda.Stream(device)
+        with torch.cuda.stream(st):
+            mt = cls(max_queries, max_db, ctx=_stream_context(device), **kw)
+        mt.stream = st
+        return mt
+
+    def capture(self, queries: torch.Tensor, mask_width: int = 0, k: int = 1, db_row0: int = 0, q_row0: int = 0):
+        """One single-rank match() of the STATIC tensor `queries` as a hipGraph (CapturedMatch; the matcher must come from on_new_stream).
+        The graph holds the DB's row count as it was at capture, so after pack_database / append_database it must be captured again:
+        its run() raises RuntimeError instead of replaying it."""
+        st = self.stream
+        with torch.cuda.stream(st):
+            assert self.ctx.stream == int(st.cuda_stream)
+            self.match(queries, mask_width, k, db_row0, q_row0)
+            st.synchronize()
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, stream=st):
+                idx, score = self.match(queries, mask_width, k, db_row0, q_row0)
+        cap = CapturedMatch(g, st, queries, idx, score)
+        gen, mt = self.generation, weakref.ref(self)
+
+        def valid():
+            m_ = mt()
+            if m_ is None or m_.db is None or m_.generation != gen:
+                raise RuntimeError("DelightMatcher.capture: the database changed (or was closed) since this graph was captured; capture again")
+        cap.check = valid
+        return cap
+
+
 def _world(group) -> int:
     import torch.distributed as dist
     return dist.get_world_size(group) if (group is not None or (dist.is_available() and dist.is_initialized())) else 1

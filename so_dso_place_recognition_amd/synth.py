@@ -246,6 +246,47 @@ def gist_signatures_torch(seed: int, n: int, cols: int = 512, device="cuda", clu
     return out
 
 
+DELIGHT_CLUSTER_LEVEL = 2200          # a cluster member's own bin holds about this many counts (delight_signatures_torch)
+
+
+def delight_cluster_bins(cluster_size: int):
+    """(flat bins [cs] of the 16 x 256 histogram, counts [cs]) of a planted DELIGHT cluster: member t owns bin 37 t + 11, where every
+    member holds 2200 + 3 pi(t) - pi a permutation of 0 .. cs - 1 that is not the identity - and member t one more."""
+    cs = int(cluster_size)
+    a = next(x for x in range(max(2, (cs * 5) // 8), 2 * cs + 3) if np.gcd(x, cs) == 1)
+    t = np.arange(cs)
+    return (37 * t + 11) % 4096, DELIGHT_CLUSTER_LEVEL + 3 * ((a * t + 1) % cs)
+
+
+def delight_signatures_torch(seed: int, n: int, device="cuda", clusters: int = 0, cluster_size: int = 40, chunk: int = 4096):
+    """delight_database's distribution (per histogram a level 4 .. 32, half of the bins empty, integer counts) drawn on the device from
+    a torch generator of its own (not the numpy stream): float64 [16 n, 256].  clusters > 0 plants that many runs of `cluster_size`
+    consecutive near-copies at evenly spaced entries - a vehicle standing still: all members are one base entry whose bins
+    delight_cluster_bins() hold ~2200 counts, and member t holds one count more in its own bin.  Against a query that differs from the
+    base in some other bin by a large amount, the members' distances differ by ~1e-10 relative: below fp32, far above fp64."""
+    import torch
+    g = torch.Generator(device=device)
+    g.manual_seed(int(seed))
+    out = torch.empty((n, 16, 256), dtype=torch.float64, device=device)
+    for s0 in range(0, n, chunk):
+        r = min(n, s0 + chunk) - s0
+        u = torch.rand((r, 16, 256), generator=g, device=device, dtype=torch.float64)
+        scale = 4.0 + 28.0 * torch.rand((r, 16, 1), generator=g, device=device, dtype=torch.float64)
+        out[s0:s0 + r] = torch.floor(u * scale * (u < 0.5))
+    cs = min(int(cluster_size), n)
+    if clusters > 0 and cs > 0:
+        bins, level = delight_cluster_bins(cs)
+        bins_t = torch.as_tensor(bins, device=device)
+        flat = out.view(n, 4096)
+        for c in range(int(clusters)):
+            r0 = min(n - cs, (n // (clusters + 1)) * (c + 1))
+            base = flat[r0].clone()
+            base[bins_t] = torch.as_tensor(level, dtype=torch.float64, device=device)
+            flat[r0:r0 + cs] = base[None, :]
+            flat[r0 + torch.arange(cs, device=device), bins_t] += 1.0
+    return out.view(16 * n, 256)
+
+
 # ----------------------------------------------------------------------------- the same samplers on a torch device
 # Bit-identical to the numpy versions above (uint64 arithmetic carried in int64 two's complement: add / multiply wrap,
 # logical shifts by masking), so that full-size inputs (10^5 - 10^6 signatures, 5000 x 50 000 points) are drawn in HBM in
