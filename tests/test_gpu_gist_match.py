@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import oracle_lib
+from resident_fuzz_cases import bits_equal, oracle_select
 from so_dso_place_recognition_amd import api, synth
 from so_dso_place_recognition_amd.matcher import GistMatcher, merge_topk
 
@@ -14,21 +15,8 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 
-def bits_equal(a, b):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    na, nb = np.isnan(a), np.isnan(b)
-    return a.shape == b.shape and np.array_equal(na, nb) and np.array_equal(a[~na].view(np.int64), b[~nb].view(np.int64))
-
-
 def oracle_topk(h1, h2, mask_width, k, q_row0=0, db_row0=0):
-    d = oracle_lib.gist_distance(h1, h2)
-    m, n = d.shape
-    gi = q_row0 + np.arange(m)[:, None]
-    gj = db_row0 + np.arange(n)[None, :]
-    d = np.where(np.abs(gi - gj) < mask_width, np.inf, d)
-    rc, idx, sc = oracle_lib.select_topk(d, 0, k)
-    assert rc == 0
-    return np.where(idx >= 0, idx + db_row0, -1).astype(np.int32), sc
+    return oracle_select(oracle_lib.gist_distance(h1, h2), mask_width, k, q_row0, db_row0)
 
 
 def dev(a):

@@ -2,7 +2,10 @@
 device-resident Matcher / FusedMatcher), the three SC arithmetics, k up to 60, wide masks, zero-norm rows, duplicated rows (exact ties),
 ragged shapes; and the three generators on ragged batches with empty / one-point / collinear clouds.
 usage: python tools/fuzz_all.py [seed] [cases] [what: match,group,matcher,fused,gen[,big]]   (big: rows of 16k - 130k entries, 1 - 40 queries)
-Prints one line per case; exits 1 if any case differed (indices must be equal, scores inside tests/helpers.score_tol)."""
+Prints one line per case; exits 1 if any case differed (indices must be equal, scores inside tests/helpers.score_tol).
+what = bow_match, gist_match, delight_match (not in the default set): the device-resident matchers on the cases of
+tests/resident_fuzz_cases.py for this seed (with big: 1 - 4 queries against 16k - 100k rows) - bulk, exact rows, grown, sharded and
+host-buffer forms, every one equal to the oracle in indices and score bits."""
 import sys
 import time
 import traceback
@@ -86,6 +89,59 @@ def spoil(q, db, div, planted=None):
 sigma_ties = []
 
 
+def resident_leg(kind, it):
+    """one case of tests/resident_fuzz_cases.py through the forms of tests/test_gpu_fuzz_resident.py (the graph replay apart)"""
+    import torch
+    import resident_fuzz_cases as F
+    from so_dso_place_recognition_amd import matcher as M
+    c = F.draw(kind, seed, it, big=BIG)
+    d = F.oracle_distance(kind, c.q, c.db)
+    want, want0 = F.oracle_select(d, c.mask_width, c.k, c.q_row0, c.db_row0), F.oracle_select(d, c.mask_width, c.k)
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float64)).cuda()
+
+    def make(n, exact=False):
+        if kind == "bow":
+            return M.BowMatcher(c.m, n, c.cols, c.vocab)
+        return M.GistMatcher(c.m, n, c.cols, exact=exact) if kind == "gist" else M.DelightMatcher(c.m, n, exact=exact)
+
+    def same(got, w):
+        torch.cuda.synchronize()
+        gi, gs = (x.cpu().numpy() if hasattr(x, "cpu") else x for x in got)
+        return np.array_equal(gi, w[0]) and F.bits_equal(gs, w[1])
+
+    q, res, fl = dev(c.q), {}, 0
+    for form in ("bulk", "exact"):
+        if form == "exact" and kind == "bow":
+            continue
+        mt = make(c.n, form == "exact")
+        mt.pack_database(dev(c.db))
+        res[form] = same(mt.match(q, c.mask_width, c.k, c.db_row0, c.q_row0), want)
+        if form == "bulk" and kind != "bow":
+            fl = mt.flagged_count()
+        mt.close()
+    mt = make(c.n)
+    at = c.chunks[0]
+    mt.reserve_database(dev(c.rows(c.db, 0, at)) if at else None)
+    for step in c.chunks[1:]:
+        mt.append_database(dev(c.rows(c.db, at, at + step)))
+        at += step
+    res["grown"] = same(mt.match(q, c.mask_width, c.k, c.db_row0, c.q_row0), want)
+    mt.close()
+    parts = []
+    for lo, hi in zip(c.cuts[:-1], c.cuts[1:]):
+        mt = make(hi - lo)
+        mt.pack_database(dev(c.rows(c.db, lo, hi)))
+        parts.append(mt.match(q, c.mask_width, c.k, c.db_row0 + lo, c.q_row0))
+        torch.cuda.synchronize()
+        mt.close()
+    res["shards"] = same(M.merge_topk(torch.stack([p[0] for p in parts]), torch.stack([p[1] for p in parts]), c.k), want)
+    res["host"] = same(getattr(api, kind + "_match_topk")(c.q, c.db, c.mask_width, c.k), want0)
+    for form, ok in res.items():
+        if not ok:
+            bad.append((it, kind + "_match", form, repr(c)))
+    return f"{c!r} flagged={fl} " + " ".join(f"{form}:{'ok' if ok else 'BAD'}" for form, ok in res.items())
+
+
 def check(tag, idx, sc, oidx, osc, tol, resolved=True):
     """resolved=False (a path without fp64 row statistics - none since round 4): neighbours whose scores agree to 1e-5 may come out in the
     other order - the limit of fp32 row statistics; such cases are counted apart, not as findings ("order not guaranteed": must stay empty)."""
@@ -126,7 +182,17 @@ import os
 ONLY = int(os.environ["FUZZ_ONLY"]) if "FUZZ_ONLY" in os.environ else None     # re-run ONE case of a (seed, what) sweep: the others only draw their random numbers
 DUMP = os.environ.get("FUZZ_DUMP")                                            # ... and leave its inputs + oracle answer in this .npz
 t_start = time.time()
-for it in range(cases):
+RESIDENT = [x for x in ("bow", "gist", "delight") if x + "_match" in what]
+for x in RESIDENT:
+    what.discard(x + "_match")
+for it in range(cases if RESIDENT else 0):
+    for kind in RESIDENT:
+        try:
+            print(f"{it}:", resident_leg(kind, it), f"[{time.time() - t_start:.0f}s]", flush=True)
+        except Exception as e:      # an error return is a finding too
+            bad.append((it, kind + "_match", "exception", repr(e)))
+            traceback.print_exc()
+for it in range(cases if what else 0):
     m, n, k, mask = shapes()
     line = [f"{it}: m={m} n={n} k={k} mask={mask}"]
     if ONLY is not None and it != ONLY:
