@@ -639,6 +639,40 @@ int pr_write_points(const char* path, const int32_t* ids, const double* xyz, con
 int pr_precision_recall(const double* diff_v, const int32_t* diff_idx, int32_t m, const double* gt1, const double* gt2, int32_t n,
                         int32_t cols, double loop_diff, int32_t mask_width, double* auc, double* top_recall, int32_t* lp_detected,
                         int32_t* n_detected);
+/* The same evaluation on the device (eval.hip), bit for bit the reference's arithmetic: squared distances
+ * ((0 + t_0^2) + t_1^2) + ... with every product and sum rounded, the FIRST minimum per query (strict `min_diff > diff` from +Inf / -1: a NaN
+ * or +Inf distance never wins), a stable ascending rank of diff_v with NaN after +Inf, IEEE divisions, and the trapz sum added in index order.
+ * cols <= 768.  m = 0 and n = 0 are valid.  PR_EINVAL (text: pr_last_error) for negative sizes, cols < 1 or a NULL required pointer.
+ *   pr_ground_truth_pairs_dev  run_test.m:3-22.  d_gt1 [m][cols], d_gt2 [n][cols] DEVICE.  Outputs (DEVICE, any may be NULL): d_min_j [m]
+ *                       the nearest unmasked row (-1: none), d_min_d [m] its squared distance (+Inf: none), d_lp_gt [m][2] the pairs
+ *                       (i, min_j) with min_d < loop_diff^2 in ascending i (the first *d_n_gt are written), d_n_gt [1].
+ *   pr_precision_recall_dev  run_test.m:3-22 + :58-85.  d_diff_v (f64) / d_diff_idx (i32): element i at [i * ld], so that column 0 of a
+ *                       matcher's [m][k] result is read in place with ld = k.  A rank is a true positive when its index b (-1 read as 0)
+ *                       is < n and the squared distance of gt1[a], gt2[b] is < loop_diff^2.  d_scalars: DEVICE record
+ *                       {f64 auc, f64 top_recall, i32 n_gt, i32 n_detected} (24 bytes).  Optional DEVICE outputs: d_lp_gt [m][2],
+ *                       d_lp_detected [m][2] (the first n_detected pairs (query, match) are written), d_precision [m], d_recall [m].
+ *   pr_trapz_dev        *d_auc = sum over i < m - 1 of ((recall[i+1] - recall[i]) * (precision[i] + precision[i+1])) / 2, added in that
+ *                       order from 0.0 (run_test.m:84 as the oracle evaluates it).
+ *                       All three are stream-ordered on the context's stream without host read-back; their scratch is grow-only in the
+ *                       context: a call whose shapes an earlier call covered allocates nothing and can be captured in a hipGraph.
+ *   pr_ground_truth_pairs / pr_precision_recall_gpu  the host-buffer forms: upload, the calls above, read back, synchronise.  lp_gt and
+ *                       lp_detected are [m][2] (optional, like n_gt, n_detected, precision [m], recall [m], min_j, min_d).
+ *   pr_eval_tile_rows   gt2 rows a workgroup stages at a time.  pr_set_eval_path: tests and experiments - split 0: by shape, 1: every
+ *                       workgroup scans all of gt2, 2: per-range partials and a combining launch; queries_per_lane 0: by shape, 1 or 4.
+ *                       The results do not depend on either. */
+int pr_ground_truth_pairs_dev(pr_ctx* ctx, const double* d_gt1, int32_t m, const double* d_gt2, int32_t n, int32_t cols, double loop_diff,
+                              int32_t mask_width, int32_t* d_min_j, double* d_min_d, int32_t* d_lp_gt, int32_t* d_n_gt);
+int pr_precision_recall_dev(pr_ctx* ctx, const double* d_diff_v, const int32_t* d_diff_idx, int32_t ld, int32_t m, const double* d_gt1,
+                            const double* d_gt2, int32_t n, int32_t cols, double loop_diff, int32_t mask_width, void* d_scalars,
+                            int32_t* d_lp_gt, int32_t* d_lp_detected, double* d_precision, double* d_recall);
+int pr_trapz_dev(pr_ctx* ctx, const double* d_recall, const double* d_precision, int32_t m, double* d_auc);
+int pr_ground_truth_pairs(pr_ctx* ctx, const double* gt1, int32_t m, const double* gt2, int32_t n, int32_t cols, double loop_diff,
+                          int32_t mask_width, int32_t* min_j, double* min_d, int32_t* lp_gt, int32_t* n_gt);
+int pr_precision_recall_gpu(pr_ctx* ctx, const double* diff_v, const int32_t* diff_idx, int32_t m, const double* gt1, const double* gt2,
+                            int32_t n, int32_t cols, double loop_diff, int32_t mask_width, double* auc, double* top_recall, int32_t* lp_gt,
+                            int32_t* n_gt, int32_t* lp_detected, int32_t* n_detected, double* precision, double* recall);
+int32_t pr_eval_tile_rows(void);
+int pr_set_eval_path(pr_ctx* ctx, int split, int queries_per_lane);
 const char* pr_host_last_error(void);
 
 #ifdef __cplusplus

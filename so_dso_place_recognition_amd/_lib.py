@@ -179,6 +179,14 @@ SYMBOLS = {
     "pr_write_points": (C.c_int, [C.c_char_p, _vp, _vp, _vp, C.c_int64]),
     "pr_precision_recall": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _i32, _i32, _dbl, _i32, C.POINTER(_dbl), C.POINTER(_dbl), _vp,
                                       C.POINTER(_i32)]),
+    "pr_ground_truth_pairs_dev": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _i32, _dbl, _i32, _vp, _vp, _vp, _vp]),
+    "pr_precision_recall_dev": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _i32, _dbl, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "pr_trapz_dev": (C.c_int, [_vp, _vp, _vp, _i32, _vp]),
+    "pr_ground_truth_pairs": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _i32, _dbl, _i32, _vp, _vp, _vp, _vp]),
+    "pr_precision_recall_gpu": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _dbl, _i32, C.POINTER(_dbl), C.POINTER(_dbl), _vp,
+                                          C.POINTER(_i32), _vp, C.POINTER(_i32), _vp, _vp]),
+    "pr_eval_tile_rows": (_i32, []),
+    "pr_set_eval_path": (C.c_int, [_vp, C.c_int, C.c_int]),
     "pr_host_last_error": (C.c_char_p, []),
 }
 

@@ -858,11 +858,12 @@ def sc_relative_pose(frames_q, frames_db, variant) -> np.ndarray:
     return T
 
 
-def run_test(type_, hist1, hist2, gt1=None, gt2=None, loop_diff=None, mask_width=0, ctx: Context | None = None):
+def run_test(type_, hist1, hist2, gt1=None, gt2=None, loop_diff=None, mask_width=0, ctx: Context | None = None, device_eval: bool = False):
     """run_test.m:1.  Without ground truth: returns (diff_v, diff_idx) of run_test.m:57 (0-based indices).
     With gt1/gt2/loop_diff: returns (AUC, top_recall, lp_detected) through eval.precision_recall; the sweep ranks the QUERIES by their
     best score (run_test.m:58), so every query is then answered from its exact fp64 row unless the caller brings a context of its own
-    (pr_set_exact_statistics: scores are the reference's doubles to rounding, two queries whose scores agree to 1e-5 keep their places)."""
+    (pr_set_exact_statistics: scores are the reference's doubles to rounding, two queries whose scores agree to 1e-5 keep their places).
+    device_eval: the evaluation runs on the device (eval.precision_recall_gpu) instead of the host loops; the same values."""
     if gt1 is not None and ctx is None and type_ in ("sc", "m2dp", TYPE_SC, TYPE_M2DP):
         with _exact_statistics(default_context()) as c:            # the default context (its device, its arithmetic), exact statistics for this call
             idx, sc = match_topk(type_, hist1, hist2, mask_width, 2.0, 1, c)
@@ -871,6 +872,8 @@ def run_test(type_, hist1, hist2, gt1=None, gt2=None, loop_diff=None, mask_width
     if gt1 is None:
         return sc[:, 0], idx[:, 0]
     from . import eval as _eval
+    if device_eval:
+        return _eval.precision_recall_gpu(sc[:, 0], idx[:, 0], np.asarray(gt1), np.asarray(gt2), loop_diff, mask_width, ctx)[:3]
     return _eval.precision_recall(sc[:, 0], idx[:, 0], np.asarray(gt1), np.asarray(gt2), loop_diff, mask_width)[:3]
 
 

@@ -4,6 +4,7 @@
 //   [--devices 0,1,...]               hist2 row-sharded over these GPUs (pr_group: RCCL all-gathers between the kernels; sc | m2dp)
 //   [--gt1 F --gt2 F --loop_diff L]   positions of the signatures (text matrices, one row per signature): the evaluation half of
 //                                     run_test (run_test.m:3-22, :58-85) - prints `AUC = ...` and `top_recall = ...`
+//   [--eval_device 1]                 that evaluation on the GPU (pr_precision_recall_gpu) instead of the host loops; the same printed lines
 //   [--exact_statistics 0|1]          every query answered from its exact fp64 row (scores = the reference's doubles to rounding).  Default: 1
 //                                     with --gt1 / --gt2 - the sweep ranks the QUERIES by score (run_test.m:58), and two queries whose scores
 //                                     agree to 1e-5 must not change places -, else 0
@@ -131,6 +132,13 @@ int main(int argc, char** argv) {
     for (int32_t i = 0; i < m; i++) { v[i] = score[(size_t)i * k]; bi[i] = idx[(size_t)i * k]; }
     double auc = 0, tr = 0;
     int32_t nd = 0;
+    if (prm.num("eval_device", 0) != 0) {
+      if (!ctx && pr_create(dev_ids.empty() ? (int)prm.num("device", 0) : dev_ids[0], &ctx) != PR_OK) { fprintf(stderr, "%s\n", pr_last_error(nullptr)); return 3; }
+      if (pr_precision_recall_gpu(ctx, v.data(), bi.data(), m, g1, g2, n, (int32_t)gc1, prm.num("loop_diff", 10.0), (int32_t)prm.num("mask_width", 0),
+                                  &auc, &tr, nullptr, nullptr, nullptr, &nd, nullptr, nullptr) != PR_OK) {
+        fprintf(stderr, "%s\n", pr_last_error(ctx)); pr_destroy(ctx); return 4;
+      }
+    } else
     if (pr_precision_recall(v.data(), bi.data(), m, g1, g2, n, (int32_t)gc1, prm.num("loop_diff", 10.0), (int32_t)prm.num("mask_width", 0), &auc, &tr,
                             nullptr, &nd) != PR_OK) { fprintf(stderr, "%s\n", pr_host_last_error()); pr_destroy(ctx); return 4; }
     printf("AUC = %.9g\ntop_recall = %.9g\nlp_detected = %d\n", auc, tr, nd);

@@ -302,12 +302,32 @@ void launch_delight_rerank(hipStream_t st, const double* q, const double* raw, i
                            int* flags /* [m] 1: not provably complete */);
 void launch_delight_xdist(hipStream_t st, const double* q, const double* raw, int n, const int* list, const int* cnt, int offset,
                           int direct_count, int cap, double* out, size_t ld, int q_row0, int db_row0, int mask_width);
+// eval.hip — the evaluation half of run_test.m on the device (see the file header); all pointers are device pointers
+constexpr int EVAL_TILE = 256;                  // gt2 rows a workgroup stages in LDS at a time (cols <= 3)
+constexpr int EVAL_MAX_COLS = 3 * EVAL_TILE;    // widest position row: the generic kernel's tile holds at least one
+constexpr int EVAL_SCAN = 1024;                 // items per workgroup of the two-level integer scans
+struct EvalScalars { double auc, top_recall; int32_t n_gt, n_detected; };   // pr_precision_recall_dev's d_scalars
+// run_test.m:3-16: per query the first minimum over gt2 rows [s chunk, (s + 1) chunk) for s < nsplit, written at [s][m] of out_d / out_j;
+// chunk is a multiple of EVAL_TILE; rq = 1 | 4 queries per lane (4: cols <= 3 only)
+void launch_eval_gt(hipStream_t st, const double* gt1, int m, const double* gt2, int n, int cols, int mask_width, int chunk, int nsplit, int rq,
+                    double* out_d, int* out_j);
+void launch_eval_gt_combine(hipStream_t st, const double* part_d, const int* part_j, int m, int nsplit, double* min_d, int* min_j);
+// run_test.m:17-20: the pairs with min_d < thr in ascending i (two-level scan: loc [m], bsum [2 blocks + 2] scratch); lp may be null
+void launch_eval_gt_pairs(hipStream_t st, const double* min_d, const int* min_j, int m, double thr, int* loc, int* bsum, int32_t* lp, int32_t* n_gt);
+// run_test.m:58-85.  cnt / rank / bidx / cls / loc [m], bsum [2 blocks + 2], prec / rec / term [m] scratch (prec, rec may be the caller's)
+void launch_eval_sweep(hipStream_t st, const double* diff_v, const int32_t* diff_idx, int ld, int m, const double* gt1, const double* gt2, int n,
+                       int cols, double thr, int* cnt, int* rank, int* bidx, int* cls, int* loc, int* bsum, double* prec, double* rec,
+                       double* term, EvalScalars* scal, int32_t* lp_detected);
+// sum over i < m - 1 of ((r[i+1] - r[i]) * (p[i] + p[i+1])) / 2, added in that order from 0 by one lane; term [m] scratch
+void launch_eval_trapz(hipStream_t st, const double* rec, const double* prec, int m, double* term, double* out);
+void eval_release(void* state);                 // eval_dev.cpp: frees a context's evaluation scratch (pr_destroy, streams idle)
 // pr_api.cpp: what gist.cpp and bow.cpp need of a context
 hipStream_t ctx_stream(pr_ctx* ctx);
 int ctx_device(pr_ctx* ctx);
 void ctx_set_error(pr_ctx* ctx, const char* msg);
 void*& ctx_gist(pr_ctx* ctx);
 void*& ctx_bow(pr_ctx* ctx);
+void*& ctx_eval(pr_ctx* ctx);
 int* ctx_bow_flag(pr_ctx* ctx);                 // [1] device word: a BoW row was truncated (PR_WARN_BOW_TRUNCATED at pr_take_warnings)
 int* ctx_bow_rows_flag(pr_ctx* ctx);            // [1] device word: a non-conforming BoW query row (PR_WARN_BOW_ROWS at pr_take_warnings)
 

@@ -71,6 +71,7 @@ struct pr_ctx {
   int timing_valid = 0;          // 0: nothing recorded; 1: ev_t[0], ev_t[3] only (one launch); 3: all four (channel 0 | channel 1 split | channel 1 single)
   void* gist = nullptr;          // GIST filter tables per parameter set and grow-only scratch (gist.cpp)
   void* bow = nullptr;           // BoW device vocabularies and grow-only scratch (bow.cpp)
+  void* eval = nullptr;          // grow-only scratch and path selection of the device evaluation (eval_dev.cpp)
 };
 
 struct pr_sigset {
@@ -380,6 +381,7 @@ void pr_destroy(pr_ctx* ctx) {
   if (ctx->d_planes) (void)hipFree(ctx->d_planes);
   pr::gist_release(ctx->gist);
   pr::bow_release(ctx->bow);
+  pr::eval_release(ctx->eval);
   delete ctx;
 }
 
@@ -2041,6 +2043,7 @@ int ctx_device(pr_ctx* ctx) { return ctx->device; }
 void ctx_set_error(pr_ctx* ctx, const char* msg) { if (ctx) ctx->err = msg; else g_err = msg; }
 void*& ctx_gist(pr_ctx* ctx) { return ctx->gist; }
 void*& ctx_bow(pr_ctx* ctx) { return ctx->bow; }
+void*& ctx_eval(pr_ctx* ctx) { return ctx->eval; }
 int* ctx_bow_flag(pr_ctx* ctx) { return ctx->d_flags + 5; }
 int* ctx_bow_rows_flag(pr_ctx* ctx) { return ctx->d_flags + 6; }
 }  // namespace pr

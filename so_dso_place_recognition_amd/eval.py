@@ -1,5 +1,6 @@
 """Evaluation harness of match_signatures/run_test.m: ground-truth loop pairs (:3-22) and the
-precision/recall sweep, top recall at 100 % precision and AUC (:58-85).  Host numpy; O(m n) and O(m log m)."""
+precision/recall sweep, top recall at 100 % precision and AUC (:58-85).  Host numpy, O(m n) and O(m log m); the `_torch` / `_gpu`
+functions run the same arithmetic on the device (csrc/eval.hip)."""
 from __future__ import annotations
 
 import numpy as np
@@ -62,6 +63,113 @@ def precision_recall(diff_v, diff_idx, gt1, gt2, loop_diff: float, mask_width: i
             auc += (recall[i + 1] - recall[i]) * (precision[i] + precision[i + 1]) / 2.0
     lp_detected = np.stack([rank[:top_count], diff_idx[rank[:top_count]]], 1)
     return auc, float(top_recall), lp_detected, precision, recall
+
+
+# ------------------------------------------------------------------ the same on the device (csrc/eval.hip)
+def gt2_tile_rows() -> int:
+    """gt2 rows a workgroup of the ground-truth kernel stages at a time (pr_eval_tile_rows)."""
+    from . import _lib
+    return int(_lib.load().pr_eval_tile_rows())
+
+
+def _positions(gt1, gt2):
+    import torch
+    if not (gt1.is_cuda and gt2.is_cuda) or gt1.dim() != 2 or gt2.dim() != 2 or gt1.shape[1] != gt2.shape[1]:
+        raise ValueError("expected CUDA position tensors [m, cols] and [n, cols]")
+    return gt1.to(torch.float64).contiguous(), gt2.to(torch.float64).contiguous()
+
+
+class _on_stream:
+    """ctx given: its stream is the caller's to order.  ctx None: the per-device default context, joined to torch's current stream by
+    stream waits on both sides (no host wait), the tensors marked as used there for torch's caching allocator."""
+
+    def __init__(self, ctx, device, tensors):
+        self.ctx, self.lib_stream, self.cur, self.tensors = ctx, None, None, tensors
+        if ctx is None:
+            import torch
+            from . import api
+            self.ctx, self.lib_stream = api._torch_default_context(device.index or 0)
+            self.cur = torch.cuda.current_stream(device)
+
+    def __enter__(self):
+        if self.lib_stream is not None:
+            self.lib_stream.wait_stream(self.cur)
+        return self.ctx
+
+    def __exit__(self, *exc):
+        if self.lib_stream is not None:
+            self.cur.wait_stream(self.lib_stream)
+            for t in self.tensors:
+                t.record_stream(self.lib_stream)
+
+
+def _p(t):
+    import ctypes as C
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def ground_truth_pairs_torch(gt1, gt2, loop_diff: float, mask_width: int, ctx=None):
+    """run_test.m:3-22 on the device (pr_ground_truth_pairs_dev): gt1 [m, cols], gt2 [n, cols] CUDA tensors ->
+    (lp_gt int32 [m, 2], n_gt int32 [1], min_j int32 [m], min_d float64 [m]), all on the device; the first n_gt rows of lp_gt are the
+    pairs (i, j) in ascending i.  Nothing synchronises: `lp_gt[:int(n_gt)]` is the caller's read."""
+    import torch
+    g1, g2 = _positions(gt1, gt2)
+    m, n, cols = g1.shape[0], g2.shape[0], g1.shape[1]
+    dev = g1.device
+    lp = torch.empty((m, 2), dtype=torch.int32, device=dev)
+    n_gt = torch.empty(1, dtype=torch.int32, device=dev)
+    min_j = torch.empty(m, dtype=torch.int32, device=dev)
+    min_d = torch.empty(m, dtype=torch.float64, device=dev)
+    with _on_stream(ctx, dev, (g1, g2, lp, n_gt, min_j, min_d)) as c:
+        c.check(c.lib.pr_ground_truth_pairs_dev(c.h, _p(g1), m, _p(g2), n, cols, float(loop_diff), int(mask_width), _p(min_j), _p(min_d),
+                                                _p(lp), _p(n_gt)))
+    return lp, n_gt, min_j, min_d
+
+
+def precision_recall_torch(score, idx, gt1, gt2, loop_diff: float, mask_width: int, ctx=None, out=None):
+    """run_test.m:3-22 + :58-85 on the device (pr_precision_recall_dev).  score (float64) / idx (int32): CUDA tensors [m] or the [m, k]
+    pair a matcher returned (column 0 is read in place).  Returns a dict of device tensors: auc, top_recall (float64 [1] views of one
+    record), n_gt, n_detected (int32 [1]), lp_gt, lp_detected (int32 [m, 2]; the first n_gt / n_detected rows are written), precision,
+    recall (float64 [m]).  Nothing synchronises until the caller reads them.  out: a dict this call returned for the same m - its tensors
+    are written again (fixed addresses: what a captured graph needs)."""
+    import torch
+    g1, g2 = _positions(gt1, gt2)
+    m, n, cols = g1.shape[0], g2.shape[0], g1.shape[1]
+    if not (score.is_cuda and idx.is_cuda) or score.dtype != torch.float64 or idx.dtype != torch.int32 or score.shape != idx.shape \
+            or score.dim() not in (1, 2) or score.shape[0] != m or not (score.is_contiguous() and idx.is_contiguous()):
+        raise ValueError("precision_recall_torch: score (float64) / idx (int32) must be contiguous CUDA tensors [m] or [m, k]")
+    ld = 1 if score.dim() == 1 else int(score.shape[1])
+    dev = g1.device
+    if out is None:
+        rec = torch.empty(3, dtype=torch.float64, device=dev)     # {f64 auc, f64 top_recall, i32 n_gt, i32 n_detected}
+        cnt = rec[2:].view(torch.int32)
+        out = dict(_record=rec, auc=rec[0:1], top_recall=rec[1:2], n_gt=cnt[0:1], n_detected=cnt[1:2],
+                   lp_gt=torch.empty((m, 2), dtype=torch.int32, device=dev), lp_detected=torch.empty((m, 2), dtype=torch.int32, device=dev),
+                   precision=torch.empty(m, dtype=torch.float64, device=dev), recall=torch.empty(m, dtype=torch.float64, device=dev))
+    elif out["precision"].shape[0] != m:
+        raise ValueError("precision_recall_torch: out belongs to another m")
+    with _on_stream(ctx, dev, (score, idx, g1, g2, out["_record"], out["lp_gt"], out["lp_detected"], out["precision"], out["recall"])) as c:
+        c.check(c.lib.pr_precision_recall_dev(c.h, _p(score), _p(idx), ld, m, _p(g1), _p(g2), n, cols, float(loop_diff), int(mask_width),
+                                              _p(out["_record"]), _p(out["lp_gt"]), _p(out["lp_detected"]), _p(out["precision"]),
+                                              _p(out["recall"])))
+    return out
+
+
+def precision_recall_gpu(diff_v, diff_idx, gt1, gt2, loop_diff: float, mask_width: int, ctx=None):
+    """precision_recall() through the device evaluation, host arrays in and out (pr_precision_recall_gpu): the same tuple
+    (AUC, top_recall, lp_detected, precision, recall)."""
+    import ctypes as C
+    from . import api
+    ctx = ctx or api.default_context()
+    gt1 = np.ascontiguousarray(gt1, np.float64); gt2 = np.ascontiguousarray(gt2, np.float64)
+    v = np.ascontiguousarray(diff_v, np.float64); bi = np.ascontiguousarray(diff_idx, np.int32)
+    m, n, cols = gt1.shape[0], gt2.shape[0], gt1.shape[1]
+    auc, tr, nd = C.c_double(), C.c_double(), C.c_int32()
+    lp = np.zeros((max(m, 1), 2), np.int32); prec = np.zeros(max(m, 1)); rec = np.zeros(max(m, 1))
+    ctx.check(ctx.lib.pr_precision_recall_gpu(ctx.h, api._ptr(v), api._ptr(bi), m, api._ptr(gt1), api._ptr(gt2), n, cols, float(loop_diff),
+                                              int(mask_width), C.byref(auc), C.byref(tr), None, None, api._ptr(lp), C.byref(nd),
+                                              api._ptr(prec), api._ptr(rec)))
+    return auc.value, tr.value, lp[:nd.value].astype(np.int64), prec[:m], rec[:m]
 
 
 # ------------------------------------------------------------------ the drivers: test_kitti.m, test_robotcar.m

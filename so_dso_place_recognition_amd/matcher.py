@@ -407,6 +407,16 @@ class _Base:
         ch = slice(0 if raw6[0] is not None else 2, 4 if raw6[3] is not None else 2)     # the channels of the matcher's descriptor types
         return var[..., ch], dist[..., ch]
 
+    def evaluate(self, idx: torch.Tensor, score: torch.Tensor, gt1: torch.Tensor, gt2: torch.Tensor, loop_diff: float, mask_width: int = 0,
+                 out=None):
+        """run_test.m:3-22 + :58-85 of a match()'s (idx, score) (their [m, k] tensors as returned: column 0 is read in place) on this
+        matcher's context and stream, without read-back: eval.precision_recall_torch's dict of device tensors."""
+        from . import eval as _eval
+        self._enter()
+        res = _eval.precision_recall_torch(score, idx, gt1, gt2, loop_diff, mask_width, ctx=self.ctx, out=out)
+        self._leave()
+        return res
+
     def flagged_count(self) -> int:
         """Queries the last match(..., exact_order=False) of ONE rank left flagged by the order / containment checks (the ones the default
         match() answers from their exact rows).  Synchronises (pr_order_flagged_count); 0 once a resolving call has taken the flags."""
