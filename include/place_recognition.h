@@ -673,6 +673,52 @@ int pr_precision_recall_gpu(pr_ctx* ctx, const double* diff_v, const int32_t* di
                             int32_t* n_gt, int32_t* lp_detected, int32_t* n_detected, double* precision, double* recall);
 int32_t pr_eval_tile_rows(void);
 int pr_set_eval_path(pr_ctx* ctx, int split, int queries_per_lane);
+
+/* ---- ICP refinement and verification of matched cloud pairs (icp.hip; no reference counterpart) --------------------
+ * Point-to-point ICP in fp64 of a source cloud (the query keyframe) onto a target cloud (the DB entry) from a seed T0 = [R | t], e.g.
+ * pr_sc_relative_pose's.  Clouds are CSR sets as pr_sc_generate_dev takes them (xyz [offs[N]][3] f64, offs [N + 1] i64), one set for the
+ * queries and one for the DB (they may be the same); pair i is (pair_src[i], pair_dst[i]), -1 = none; a source cloud may appear in several
+ * pairs.  Per iteration: p' = ((R00 x + R01 y) + R02 z) + t0 (every product and sum rounded), the nearest target point by
+ * d2 = ((dx dx) + dy dy) + dz dz with the FIRST minimum (strict `best > d2` from (+Inf, -1): a NaN or +Inf distance never wins), inliers
+ * d2 < max_corr^2, Kabsch on the inliers, R <- dR R, t <- dR t + dt.  It stops when |rmse - rmse_prev| < tol_rmse and |fitness -
+ * fitness_prev| < tol_fitness (PR_ICP_CONVERGED), with fewer than min_inliers inliers (PR_ICP_TOO_FEW) or collinear ones (second singular
+ * value of H <= 1e-12 x the first: PR_ICP_DEGENERATE) - T is then the last one a valid update produced, T0 if none -, or after max_iter
+ * updates (PR_ICP_MAX_ITER).  One more correspondence pass under the final T gives the reported fitness = n_inl / |source|, rmse =
+ * sqrt(sum of the inliers' d2 / n_inl) (0 without inliers) and n_inl.  A pair of -1: PR_ICP_NO_PAIR, T0, zeros.
+ *   pr_icp_nn_dev     one correspondence pass for c pairs under d_T [c][3][4].  DEVICE outputs: d_out_offs [c + 1] the prefix of the
+ *                     pairs' source sizes (0 for a pair of -1), d_nn_idx (-1: none) and d_nn_d2 (+Inf: none) [out_offs[c]].
+ *   pr_icp_pairs_dev  the refinement.  DEVICE outputs d_T_out [c][3][4] (may be d_T0) and d_stats [c].
+ *                     Both are stream-ordered on the context's stream without host read-back, a fixed number of launches whatever the data
+ *                     (a finished pair's launches return at once); the scratch is grow-only in the context: a call whose shapes an earlier
+ *                     call covered allocates nothing and can be captured in a hipGraph.  max_src_pts / max_dst_pts: the most points a
+ *                     source / target cloud of a pair has - the launch geometry and the scratch are sized by them, and a cloud is read
+ *                     up to that many points.  c <= 65535, clouds of up to 2^26 points.
+ *   pr_icp_nn / pr_icp_pairs  the host-buffer forms: upload, the calls above (bounds taken from the offsets), read back, synchronise.
+ *   pr_icp_tile_rows  target rows a workgroup stages at a time.  pr_set_icp_path: tests and experiments - split 0: by shape, 1: every
+ *                     workgroup scans the whole target, 2: the target split across workgroups and a combining launch.  Indices and d2
+ *                     bits do not depend on it.
+ * PR_EINVAL (text: pr_last_error) before any device is touched for negative sizes, a NULL required pointer, max_iter < 0, max_corr <= 0
+ * or not finite, min_inliers < 3, no context.  c = 0 and empty clouds are valid. */
+#define PR_ICP_CONVERGED 0
+#define PR_ICP_MAX_ITER 1
+#define PR_ICP_TOO_FEW 2
+#define PR_ICP_DEGENERATE 3
+#define PR_ICP_NO_PAIR 4
+typedef struct pr_icp_stats { double fitness, rmse; int32_t n_inl, iters, status, pad; } pr_icp_stats;
+int pr_icp_nn_dev(pr_ctx* ctx, const double* d_xyz_q, const int64_t* d_offs_q, int32_t Nq, const double* d_xyz_db, const int64_t* d_offs_db,
+                  int32_t Ndb, const int32_t* d_pair_src, const int32_t* d_pair_dst, int32_t c, const double* d_T, int32_t max_src_pts,
+                  int32_t max_dst_pts, int64_t* d_out_offs, int32_t* d_nn_idx, double* d_nn_d2);
+int pr_icp_pairs_dev(pr_ctx* ctx, const double* d_xyz_q, const int64_t* d_offs_q, int32_t Nq, const double* d_xyz_db, const int64_t* d_offs_db,
+                     int32_t Ndb, const int32_t* d_pair_src, const int32_t* d_pair_dst, int32_t c, const double* d_T0, int32_t max_src_pts,
+                     int32_t max_dst_pts, int32_t max_iter, double max_corr, double tol_rmse, double tol_fitness, int32_t min_inliers,
+                     double* d_T_out, pr_icp_stats* d_stats);
+int pr_icp_nn(pr_ctx* ctx, const double* xyz_q, const int64_t* offs_q, int32_t Nq, const double* xyz_db, const int64_t* offs_db, int32_t Ndb,
+              const int32_t* pair_src, const int32_t* pair_dst, int32_t c, const double* T, int64_t* out_offs, int32_t* nn_idx, double* nn_d2);
+int pr_icp_pairs(pr_ctx* ctx, const double* xyz_q, const int64_t* offs_q, int32_t Nq, const double* xyz_db, const int64_t* offs_db, int32_t Ndb,
+                 const int32_t* pair_src, const int32_t* pair_dst, int32_t c, const double* T0, int32_t max_iter, double max_corr,
+                 double tol_rmse, double tol_fitness, int32_t min_inliers, double* T_out, pr_icp_stats* stats);
+int32_t pr_icp_tile_rows(void);
+int pr_set_icp_path(pr_ctx* ctx, int split);
 const char* pr_host_last_error(void);
 
 #ifdef __cplusplus

@@ -19,6 +19,7 @@ ROLE_QUERY, ROLE_DB = 0, 1
 F64, F32 = 0, 1
 U8 = 2              # 8-bit images (pr_gist_generate*)
 HOST, DEVICE = 0, 1
+ICP_CONVERGED, ICP_MAX_ITER, ICP_TOO_FEW, ICP_DEGENERATE, ICP_NO_PAIR = 0, 1, 2, 3, 4     # pr_icp_stats.status
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PR_AMD_LIB") or os.path.join(_HERE, "libpr_amd.so")   # PR_AMD_LIB: experiment builds only
@@ -187,6 +188,12 @@ SYMBOLS = {
                                           C.POINTER(_i32), _vp, C.POINTER(_i32), _vp, _vp]),
     "pr_eval_tile_rows": (_i32, []),
     "pr_set_eval_path": (C.c_int, [_vp, C.c_int, C.c_int]),
+    "pr_icp_nn_dev": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp]),
+    "pr_icp_pairs_dev": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _dbl, _dbl, _dbl, _i32, _vp, _vp]),
+    "pr_icp_nn": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "pr_icp_pairs": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _i32, _dbl, _dbl, _dbl, _i32, _vp, _vp]),
+    "pr_icp_tile_rows": (_i32, []),
+    "pr_set_icp_path": (C.c_int, [_vp, C.c_int]),
     "pr_host_last_error": (C.c_char_p, []),
 }
 

@@ -858,6 +858,116 @@ def sc_relative_pose(frames_q, frames_db, variant) -> np.ndarray:
     return T
 
 
+# ------------------------------------------------------------------------------- ICP refinement and verification (icp.hip)
+ICP_STATS = np.dtype([("fitness", "<f8"), ("rmse", "<f8"), ("n_inl", "<i4"), ("iters", "<i4"), ("status", "<i4"), ("pad", "<i4")])   # pr_icp_stats
+
+
+def icp_tile_rows() -> int:
+    """Target rows a workgroup of the correspondence kernel stages at a time (pr_icp_tile_rows)."""
+    return int(_lib.load().pr_icp_tile_rows())
+
+
+def _icp_sets(xyz_q, offs_q, xyz_db, offs_db, pair_src, pair_dst, T):
+    xq = np.ascontiguousarray(xyz_q, np.float64).reshape(-1, 3); oq = np.ascontiguousarray(offs_q, np.int64).reshape(-1)
+    xd = np.ascontiguousarray(xyz_db, np.float64).reshape(-1, 3); od = np.ascontiguousarray(offs_db, np.int64).reshape(-1)
+    ps = np.ascontiguousarray(pair_src, np.int32).reshape(-1); pd = np.ascontiguousarray(pair_dst, np.int32).reshape(-1)
+    if len(oq) < 1 or len(od) < 1 or oq[-1] != len(xq) or od[-1] != len(xd):
+        raise ValueError("clouds are CSR sets: xyz [offs[-1], 3] and offs [N + 1]")
+    if len(ps) != len(pd):
+        raise ValueError("pair_src and pair_dst must have the same length")
+    c = len(ps)
+    T = np.ascontiguousarray(T, np.float64)
+    if T.size != 12 * c:
+        raise ValueError("T must be [c, 3, 4]")
+    return xq, oq, xd, od, ps, pd, c, T.reshape(c, 3, 4)
+
+
+def icp_nn(xyz_q, offs_q, xyz_db, offs_db, pair_src, pair_dst, T, ctx: Context | None = None):
+    """One correspondence pass (pr_icp_nn) for the pairs (pair_src[i] of the query clouds, pair_dst[i] of the DB clouds; -1 = none) under
+    T [c, 3, 4]: returns (out_offs int64 [c + 1], nn_idx int32, nn_d2 float64): pair i's source points are rows out_offs[i] .. out_offs[i + 1];
+    -1 / +Inf where a point has no finite candidate."""
+    ctx = ctx or default_context()
+    xq, oq, xd, od, ps, pd, c, T = _icp_sets(xyz_q, offs_q, xyz_db, offs_db, pair_src, pair_dst, T)
+    total = int(sum(oq[s + 1] - oq[s] for s, d in zip(ps, pd) if 0 <= s < len(oq) - 1 and d >= 0))
+    out_offs = np.zeros(c + 1, np.int64); idx = np.empty(total, np.int32); d2 = np.empty(total, np.float64)
+    ctx.check(ctx.lib.pr_icp_nn(ctx.h, _ptr(xq), _ptr(oq), len(oq) - 1, _ptr(xd), _ptr(od), len(od) - 1, _ptr(ps), _ptr(pd), c, _ptr(T),
+                                _ptr(out_offs), _ptr(idx), _ptr(d2)))
+    return out_offs, idx, d2
+
+
+def icp_refine(xyz_q, offs_q, xyz_db, offs_db, pair_src, pair_dst, T0, max_iter: int = 30, max_corr: float = 1.0, tol_rmse: float = 1e-6,
+               tol_fitness: float = 1e-6, min_inliers: int = 3, ctx: Context | None = None):
+    """Point-to-point ICP of every pair from its seed T0 [c, 3, 4] (pr_icp_pairs; the arithmetic is in the header): returns
+    (T float64 [c, 3, 4], stats [c] of dtype ICP_STATS: fitness, rmse, n_inl, iters, status = _lib.ICP_*)."""
+    ctx = ctx or default_context()
+    xq, oq, xd, od, ps, pd, c, T0 = _icp_sets(xyz_q, offs_q, xyz_db, offs_db, pair_src, pair_dst, T0)
+    T = np.empty((c, 3, 4)); stats = np.zeros(c, ICP_STATS)
+    ctx.check(ctx.lib.pr_icp_pairs(ctx.h, _ptr(xq), _ptr(oq), len(oq) - 1, _ptr(xd), _ptr(od), len(od) - 1, _ptr(ps), _ptr(pd), c, _ptr(T0),
+                                   int(max_iter), float(max_corr), float(tol_rmse), float(tol_fitness), int(min_inliers), _ptr(T), _ptr(stats)))
+    return T, stats
+
+
+def icp_refine_torch(xyz_q, offs_q, xyz_db, offs_db, pair_src, pair_dst, T0, max_src_pts: int, max_dst_pts: int, max_iter: int = 30,
+                     max_corr: float = 1.0, tol_rmse: float = 1e-6, tol_fitness: float = 1e-6, min_inliers: int = 3, ctx: Context | None = None,
+                     out=None):
+    """Device form (pr_icp_pairs_dev): CUDA tensors xyz float64 [*, 3], offs int64 [N + 1], pairs int32 [c], T0 float64 [c, 3, 4];
+    max_src_pts / max_dst_pts: the most points a source / target cloud of a pair has (host numbers: nothing is read back).  Returns
+    (T float64 [c, 3, 4], stats uint8 [c, 32] - view it on the host with ICP_STATS), device tensors; nothing synchronises.  out: the pair
+    (T, stats) an earlier call returned for the same c - written again (fixed addresses: what a captured graph needs).
+    ctx given: its stream is the caller's to order; ctx None: the per-device default context, joined to torch's current stream."""
+    import torch
+    from .eval import _on_stream, _p
+    ts = (xyz_q, offs_q, xyz_db, offs_db, pair_src, pair_dst, T0)
+    want = (torch.float64, torch.int64, torch.float64, torch.int64, torch.int32, torch.int32, torch.float64)
+    if any((not t.is_cuda) or t.dtype != w or not t.is_contiguous() for t, w in zip(ts, want)):
+        raise ValueError("icp_refine_torch: expected contiguous CUDA tensors xyz f64, offs i64, pairs i32, T0 f64")
+    c = pair_src.numel()
+    if pair_dst.numel() != c or T0.numel() != 12 * c:
+        raise ValueError("icp_refine_torch: pair_src, pair_dst [c] and T0 [c, 3, 4] disagree")
+    dev = xyz_q.device
+    if out is None:
+        out = (torch.empty((c, 3, 4), dtype=torch.float64, device=dev), torch.zeros((c, ICP_STATS.itemsize), dtype=torch.uint8, device=dev))
+    elif out[0].shape != (c, 3, 4) or out[1].shape != (c, ICP_STATS.itemsize):
+        raise ValueError("icp_refine_torch: out belongs to another c")
+    with _on_stream(ctx, dev, ts + tuple(out)) as cx:
+        cx.check(cx.lib.pr_icp_pairs_dev(cx.h, _p(xyz_q), _p(offs_q), offs_q.numel() - 1, _p(xyz_db), _p(offs_db), offs_db.numel() - 1,
+                                         _p(pair_src), _p(pair_dst), c, _p(T0), int(max_src_pts), int(max_dst_pts), int(max_iter),
+                                         float(max_corr), float(tol_rmse), float(tol_fitness), int(min_inliers), _p(out[0]), _p(out[1])))
+    return out
+
+
+def icp_accept(stats, min_fitness: float, max_rmse: float) -> np.ndarray:
+    """accepted = (status is converged or max_iter) and fitness >= min_fitness and rmse <= max_rmse, per pair."""
+    ok = (stats["status"] == _lib.ICP_CONVERGED) | (stats["status"] == _lib.ICP_MAX_ITER)
+    return ok & (stats["fitness"] >= min_fitness) & (stats["rmse"] <= max_rmse)
+
+
+def verify_matches(clouds_q, clouds_db, idx, variant, frames_q, frames_db, max_corr: float = 1.0, min_fitness: float = 0.5,
+                   max_rmse: float = 0.5, max_iter: int = 30, tol_rmse: float = 1e-6, tol_fitness: float = 1e-6, min_inliers: int = 3,
+                   ctx: Context | None = None):
+    """Use a match: sc_relative_pose -> icp_refine for every (query q, candidate idx[q, j]).  clouds_q / clouds_db: (xyz, offs) CSR sets;
+    idx [m, k] DB rows as match_topk returns them (-1 = none); variant [m, k] the SC structure-channel variants (match_align(...)[0][..., 0]);
+    frames_q [m, 16] / frames_db [n, 16] as cloud_frames returns them.  Returns (T [m, k, 3, 4], stats [m, k] of ICP_STATS, accepted bool
+    [m, k]); a pair without a candidate or a variant has status ICP_NO_PAIR, T = identity and is not accepted.  SC only: only SC has a
+    relative pose."""
+    ix = np.ascontiguousarray(idx, np.int32)
+    v = np.ascontiguousarray(variant, np.int32)
+    if ix.ndim != 2 or v.shape != ix.shape:
+        raise ValueError("idx and variant must be [m, k]")
+    m, k = ix.shape
+    fq = np.ascontiguousarray(frames_q, np.float64).reshape(-1, 16); fd = np.ascontiguousarray(frames_db, np.float64).reshape(-1, 16)
+    has = ((ix >= 0) & (v >= 0)).reshape(-1)
+    src = np.repeat(np.arange(m, dtype=np.int32), k)
+    dst = np.where(has, ix.reshape(-1), -1).astype(np.int32)
+    src = np.where(has, src, -1).astype(np.int32)
+    T0 = np.tile(np.hstack([np.eye(3), np.zeros((3, 1))]), (m * k, 1, 1))
+    if has.any():
+        T0[has] = sc_relative_pose(fq[src[has]], fd[dst[has]], v.reshape(-1)[has])
+    T, stats = icp_refine(clouds_q[0], clouds_q[1], clouds_db[0], clouds_db[1], src, dst, T0, max_iter, max_corr, tol_rmse, tol_fitness,
+                          min_inliers, ctx)
+    return T.reshape(m, k, 3, 4), stats.reshape(m, k), icp_accept(stats, min_fitness, max_rmse).reshape(m, k)
+
+
 def run_test(type_, hist1, hist2, gt1=None, gt2=None, loop_diff=None, mask_width=0, ctx: Context | None = None, device_eval: bool = False):
     """run_test.m:1.  Without ground truth: returns (diff_v, diff_idx) of run_test.m:57 (0-based indices).
     With gt1/gt2/loop_diff: returns (AUC, top_recall, lp_detected) through eval.precision_recall; the sweep ranks the QUERIES by their

@@ -321,6 +321,32 @@ void launch_eval_sweep(hipStream_t st, const double* diff_v, const int32_t* diff
 // sum over i < m - 1 of ((r[i+1] - r[i]) * (p[i] + p[i+1])) / 2, added in that order from 0 by one lane; term [m] scratch
 void launch_eval_trapz(hipStream_t st, const double* rec, const double* prec, int m, double* term, double* out);
 void eval_release(void* state);                 // eval_dev.cpp: frees a context's evaluation scratch (pr_destroy, streams idle)
+// icp.hip — point-to-point ICP of matched cloud pairs (see the file header); all pointers are device pointers
+constexpr int ICP_TILE = 256;                   // target rows a workgroup stages in LDS at a time
+constexpr int ICP_PARTIAL = 17;                 // fp64 sums per chunk: n, sum d2, sum p' [3], sum q [3], sum p' q^T [3][3]
+enum { ICP_RUNNING = -1, ICP_CONVERGED = 0, ICP_MAX_ITER = 1, ICP_TOO_FEW = 2, ICP_DEGENERATE = 3, ICP_NO_PAIR = 4 };   // PR_ICP_* of the header
+struct IcpStats { double fitness, rmse; int32_t n_inl, iters, status, pad; };   // pr_icp_pairs_dev's stats record
+struct IcpParams { double tol_rmse, tol_fitness; int min_inliers; };
+// two CSR cloud sets and c pairs (pair_src[i] of the query set onto pair_dst[i] of the DB set; -1 or out of range: none); clouds are read
+// up to max_src / max_dst points
+struct IcpClouds {
+  const double* xyz_q; const int64_t* offs_q; int Nq;
+  const double* xyz_d; const int64_t* offs_d; int Nd;
+  const int32_t* pair_src; const int32_t* pair_dst; int c;
+  int max_src, max_dst;
+};
+// rq = 1 | 4 source points per lane; nsplit target ranges of whole tiles (> 1: slots [nsplit][c][ld] + the combining launch);
+// ld = row stride of the per-pair arrays; chunk_pts = source points per partial (256 rq, 256 with a split), nchunks = partials per pair
+struct IcpGeometry { int rq, nsplit, ld, chunk_pts, nchunks; };
+void launch_icp_offsets(hipStream_t st, const IcpClouds& A, long long* out_offs /* [c + 1] */);
+void launch_icp_init(hipStream_t st, const IcpClouds& A, const double* T0, double* T, IcpStats* stats, int* done, double* prev /* [c][2] */);
+// one correspondence pass under T [c][3][4]: nn_d / nn_j rows at base[pair] (or pair * ld); done (or null): pairs to skip;
+// part (or null) [c][nchunks][ICP_PARTIAL]: the inliers' (d2 < mc2) sums per chunk
+void launch_icp_nn(hipStream_t st, const IcpClouds& A, const IcpGeometry& g, const double* T, const int* done, double* slot_d, int* slot_j,
+                   const long long* base, double* nn_d, int* nn_j, double mc2, double* part);
+void launch_icp_finish(hipStream_t st, const IcpClouds& A, const IcpGeometry& g, const double* part, const IcpParams& P, int final_pass, double* T,
+                       IcpStats* stats, int* done, double* prev);
+void icp_release(void* state);                  // icp.cpp: frees a context's ICP scratch (pr_destroy, streams idle)
 // pr_api.cpp: what gist.cpp and bow.cpp need of a context
 hipStream_t ctx_stream(pr_ctx* ctx);
 int ctx_device(pr_ctx* ctx);
@@ -328,6 +354,7 @@ void ctx_set_error(pr_ctx* ctx, const char* msg);
 void*& ctx_gist(pr_ctx* ctx);
 void*& ctx_bow(pr_ctx* ctx);
 void*& ctx_eval(pr_ctx* ctx);
+void*& ctx_icp(pr_ctx* ctx);
 int* ctx_bow_flag(pr_ctx* ctx);                 // [1] device word: a BoW row was truncated (PR_WARN_BOW_TRUNCATED at pr_take_warnings)
 int* ctx_bow_rows_flag(pr_ctx* ctx);            // [1] device word: a non-conforming BoW query row (PR_WARN_BOW_ROWS at pr_take_warnings)
 

@@ -72,6 +72,7 @@ struct pr_ctx {
   void* gist = nullptr;          // GIST filter tables per parameter set and grow-only scratch (gist.cpp)
   void* bow = nullptr;           // BoW device vocabularies and grow-only scratch (bow.cpp)
   void* eval = nullptr;          // grow-only scratch and path selection of the device evaluation (eval_dev.cpp)
+  void* icp = nullptr;           // grow-only scratch and path selection of the ICP refinement (icp.cpp)
 };
 
 struct pr_sigset {
@@ -382,6 +383,7 @@ void pr_destroy(pr_ctx* ctx) {
   pr::gist_release(ctx->gist);
   pr::bow_release(ctx->bow);
   pr::eval_release(ctx->eval);
+  pr::icp_release(ctx->icp);
   delete ctx;
 }
 
@@ -2044,6 +2046,7 @@ void ctx_set_error(pr_ctx* ctx, const char* msg) { if (ctx) ctx->err = msg; else
 void*& ctx_gist(pr_ctx* ctx) { return ctx->gist; }
 void*& ctx_bow(pr_ctx* ctx) { return ctx->bow; }
 void*& ctx_eval(pr_ctx* ctx) { return ctx->eval; }
+void*& ctx_icp(pr_ctx* ctx) { return ctx->icp; }
 int* ctx_bow_flag(pr_ctx* ctx) { return ctx->d_flags + 5; }
 int* ctx_bow_rows_flag(pr_ctx* ctx) { return ctx->d_flags + 6; }
 }  // namespace pr

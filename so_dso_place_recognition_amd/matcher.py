@@ -417,6 +417,39 @@ class _Base:
         self._leave()
         return res
 
+    def verify(self, idx: torch.Tensor, clouds_q, clouds_db, frames_q, frames_db, max_src_pts: int, max_dst_pts: int, max_corr: float = 1.0,
+               min_fitness: float = 0.5, max_rmse: float = 0.5, max_iter: int = 30, tol_rmse: float = 1e-6, tol_fitness: float = 1e-6,
+               min_inliers: int = 3, db_row0: int = 0):
+        """Use a match (api.verify_matches on this matcher's context and stream): align(idx) -> pr_sc_relative_pose -> pr_icp_pairs_dev for
+        every (query q of the last match(), DB row idx[q, j]).  clouds_q / clouds_db: (xyz float64 [*, 3], offs int64 [N + 1]) device
+        tensors, cloud q of clouds_q = query q, cloud r of clouds_db = DB row db_row0 + r; frames_q [m, 16] / frames_db [n, 16] their PCA
+        frames (device tensors or arrays); max_src_pts / max_dst_pts: the largest query / DB cloud.  Returns device tensors (T float64
+        [m, k, 3, 4], stats uint8 [m, k, 32] - api.ICP_STATS on the host -, accepted bool [m, k]).  The seed is host code
+        (pr_sc_relative_pose): the variants are read back once; the refinement itself is stream-ordered.  SC only: only SC has a pose."""
+        from . import api
+        assert getattr(self, "type", None) == _lib.TYPE_SC, "verify() needs an SC matcher: only SC has a relative pose"
+        var, _ = self.align(idx, db_row0)
+        m, k = idx.shape
+        v = var[..., 0].reshape(-1).cpu().numpy()
+        ix = idx.reshape(-1).cpu().numpy().astype(np.int64) - int(db_row0)
+        has = (v >= 0) & (ix >= 0)
+        fq = frames_q.cpu().numpy() if torch.is_tensor(frames_q) else np.asarray(frames_q)
+        fd = frames_db.cpu().numpy() if torch.is_tensor(frames_db) else np.asarray(frames_db)
+        src = np.where(has, np.repeat(np.arange(m), k), -1).astype(np.int32)
+        dst = np.where(has, ix, -1).astype(np.int32)
+        T0 = np.tile(np.hstack([np.eye(3), np.zeros((3, 1))]), (m * k, 1, 1))
+        if has.any():
+            T0[has] = api.sc_relative_pose(fq[src[has]], fd[dst[has]], v[has])
+        dT0, dsrc, ddst = (torch.from_numpy(a).to(self.dev) for a in (T0, src, dst))
+        self._enter()
+        T, stats = api.icp_refine_torch(clouds_q[0], clouds_q[1], clouds_db[0], clouds_db[1], dsrc, ddst, dT0, max_src_pts, max_dst_pts, max_iter,
+                                        max_corr, tol_rmse, tol_fitness, min_inliers, ctx=self.ctx)
+        self._leave()
+        f64 = stats.view(torch.float64)                    # [c, 4]: fitness, rmse, (n_inl, iters), (status, pad)
+        status = stats.view(torch.int32)[:, 6]
+        accepted = ((status == _lib.ICP_CONVERGED) | (status == _lib.ICP_MAX_ITER)) & (f64[:, 0] >= min_fitness) & (f64[:, 1] <= max_rmse)
+        return T.view(m, k, 3, 4), stats.view(m, k, -1), accepted.view(m, k)
+
     def flagged_count(self) -> int:
         """Queries the last match(..., exact_order=False) of ONE rank left flagged by the order / containment checks (the ones the default
         match() answers from their exact rows).  Synchronises (pr_order_flagged_count); 0 once a resolving call has taken the flags."""
