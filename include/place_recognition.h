@@ -719,6 +719,54 @@ int pr_icp_pairs(pr_ctx* ctx, const double* xyz_q, const int64_t* offs_q, int32_
                  double tol_rmse, double tol_fitness, int32_t min_inliers, double* T_out, pr_icp_stats* stats);
 int32_t pr_icp_tile_rows(void);
 int pr_set_icp_path(pr_ctx* ctx, int split);
+
+/* ---- pose seeds for every matcher type and the stream-ordered verify chain (pose.hip; no reference counterpart) ------
+ * The seed of a matched pair from the two clouds' PCA frames ([16] doubles as pr_cloud_frames_dev writes them: mean, E = [v0 v1 v2] by
+ * ascending eigenvalue, 0, point count) and the pair's best-aligning variant (pr_align_pairs_dev / pr_delight_align_pairs_dev):
+ * R = E_db S E_q^T, t = mu_db - R mu_q, T = [R | t] maps points of the QUERY's camera frame into the DB entry's.
+ *   PR_POSE_SC       v = 2 s + r < 120: S = diag(sigma, B), exactly pr_sc_relative_pose (the same operations in the same order)
+ *   PR_POSE_M2DP     v = 4 a + b < 16: S0 = D_b D_a, D_u = diag(dx, dy, dx dy) the variant row u of test_m2dp.cpp:46-57,
+ *                    (dx, dy) = (-1,-1), (-1,+1), (+1,-1), (+1,+1) for u = 0 .. 3
+ *   PR_POSE_DELIGHT  v = k < 4: S0 = I, diag(-1,1,-1), diag(1,-1,-1), diag(-1,-1,1): the octant XOR 0, 5, 6, 3 of Mut's row k
+ *                    (processDELIGHT.m:2-5; octant = 4 (z > 0) + 2 (y > 0) + (x > 0), DELIGHT.cpp:21)
+ *   M2DP and DELIGHT: S = diag(sigma, 1, 1) S0 with sigma = sign(det E_db) sign(det E_q): R is proper whatever the eigen-solver's handedness.
+ * pr_relative_pose      the host form (no context): frames_q / frames_db [c][16], variant [c] -> T [c][3][4].  PR_EINVAL (text:
+ *                       pr_last_error(NULL)) for an unknown type, a variant outside the type's range or a frame of fewer than 3 points.
+ * pr_relative_pose_dev  one lane per slot of [m][k][H]: hypothesis h of pair p = q k + j reads d_idx[p] (GLOBAL DB row, frame
+ *                       d_idx[p] - db_row0 of d_frames_db [n_local][16]), d_variant[p * variant_stride + h] and frame q of d_frames_q
+ *                       [m][16]; DEVICE outputs d_T0 [m k H][3][4], d_pair_src (= q) and d_pair_dst (= the local DB row) [m k H] as
+ *                       pr_icp_pairs_dev takes them.  A slot gets (-1, -1) and [I | 0] - PR_ICP_NO_PAIR downstream - for idx < 0 or
+ *                       outside [db_row0, db_row0 + n_local), a variant that is negative or outside the type's range, a frame of fewer than
+ *                       3 points or with a non-finite entry, and a hypothesis 1 whose variant equals hypothesis 0's.  variant_stride: ints
+ *                       between two pairs' variants (1 for DELIGHT's [m][k]; 4 for the [m][k][4] of pr_align_pairs_dev, whose slots 0, 1
+ *                       are SC's two channels and 2, 3 M2DP's: pass d_variant + 2 for those).  H = 1 | 2 (1 for DELIGHT), m k H <= 65535.
+ * pr_verify_select_dev  one lane per pair: of the pair's H refined hypotheses (d_T_h [c][H][3][4], d_stats_h [c][H]) the one whose status
+ *                       is converged or max_iter with the larger fitness, then the smaller rmse, then the smaller h (IEEE comparisons; a
+ *                       NaN never wins over a number); hypothesis 0 when none qualifies.  DEVICE outputs d_T [c][3][4], d_stats [c],
+ *                       d_hyp [c] and d_accepted [c] = qualified && fitness >= min_fitness && rmse <= max_rmse.  Public because a caller
+ *                       who refines hypotheses of its own (other seeds, more than two, several pr_icp_pairs_dev calls) needs the same
+ *                       rule on the device, and because the rule can only be tested on chosen statistics through it; H >= 1.
+ * pr_verify_pairs_dev   the chain: seed -> pr_icp_pairs_dev over the m k H slots (query cloud q of the query set onto DB cloud
+ *                       idx - db_row0 of the DB set) -> select, on the context's stream: a fixed number of launches, no read-back, the
+ *                       scratch grow-only in the context - a call whose shapes an earlier call covered allocates nothing and can be
+ *                       captured in a hipGraph (the first call of a context uploads the SC angle table and cannot).
+ * PR_EINVAL before any device is touched as for the ICP calls, and for an unknown type, H outside 1 | 2, variant_stride < H,
+ * m k H > 65535, a NaN threshold. */
+#define PR_POSE_SC 0
+#define PR_POSE_M2DP 1
+#define PR_POSE_DELIGHT 2
+int pr_relative_pose(int type, const double* frames_q, const double* frames_db, const int32_t* variant, int32_t c, double* T);
+int pr_relative_pose_dev(pr_ctx* ctx, int type, const double* d_frames_q, int32_t m, const double* d_frames_db, int32_t n_local, int32_t db_row0,
+                         int32_t k, const int32_t* d_idx, const int32_t* d_variant, int32_t variant_stride, int32_t H, double* d_T0,
+                         int32_t* d_pair_src, int32_t* d_pair_dst);
+int pr_verify_select_dev(pr_ctx* ctx, const double* d_T_h, const pr_icp_stats* d_stats_h, int32_t c, int32_t H, double min_fitness, double max_rmse,
+                         double* d_T, pr_icp_stats* d_stats, uint8_t* d_accepted, int32_t* d_hyp);
+int pr_verify_pairs_dev(pr_ctx* ctx, int type, const double* d_xyz_q, const int64_t* d_offs_q, int32_t Nq, const double* d_xyz_db,
+                        const int64_t* d_offs_db, int32_t Ndb, const double* d_frames_q, const double* d_frames_db, int32_t m, int32_t n_local,
+                        int32_t db_row0, int32_t k, const int32_t* d_idx, const int32_t* d_variant, int32_t variant_stride, int32_t H,
+                        int32_t max_src_pts, int32_t max_dst_pts, int32_t max_iter, double max_corr, double tol_rmse, double tol_fitness,
+                        int32_t min_inliers, double min_fitness, double max_rmse, double* d_T, pr_icp_stats* d_stats, uint8_t* d_accepted,
+                        int32_t* d_hyp);
 const char* pr_host_last_error(void);
 
 #ifdef __cplusplus

@@ -20,6 +20,7 @@ F64, F32 = 0, 1
 U8 = 2              # 8-bit images (pr_gist_generate*)
 HOST, DEVICE = 0, 1
 ICP_CONVERGED, ICP_MAX_ITER, ICP_TOO_FEW, ICP_DEGENERATE, ICP_NO_PAIR = 0, 1, 2, 3, 4     # pr_icp_stats.status
+POSE_SC, POSE_M2DP, POSE_DELIGHT = 0, 1, 2          # pr_relative_pose*'s type
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PR_AMD_LIB") or os.path.join(_HERE, "libpr_amd.so")   # PR_AMD_LIB: experiment builds only
@@ -194,6 +195,11 @@ SYMBOLS = {
     "pr_icp_pairs": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _i32, _dbl, _dbl, _dbl, _i32, _vp, _vp]),
     "pr_icp_tile_rows": (_i32, []),
     "pr_set_icp_path": (C.c_int, [_vp, C.c_int]),
+    "pr_relative_pose": (C.c_int, [C.c_int, _vp, _vp, _vp, _i32, _vp]),
+    "pr_relative_pose_dev": (C.c_int, [_vp, C.c_int, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp]),
+    "pr_verify_select_dev": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _dbl, _dbl, _vp, _vp, _vp, _vp]),
+    "pr_verify_pairs_dev": (C.c_int, [_vp, C.c_int, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _i32,
+                                      _i32, _dbl, _dbl, _dbl, _i32, _dbl, _dbl, _vp, _vp, _vp, _vp]),
     "pr_host_last_error": (C.c_char_p, []),
 }
 

@@ -968,6 +968,116 @@ def verify_matches(clouds_q, clouds_db, idx, variant, frames_q, frames_db, max_c
     return T.reshape(m, k, 3, 4), stats.reshape(m, k), icp_accept(stats, min_fitness, max_rmse).reshape(m, k)
 
 
+# ------------------------------------------------------------------------------- pose seeds of every type and the device verify chain (pose.hip)
+_POSE_TYPES = {"sc": _lib.POSE_SC, "m2dp": _lib.POSE_M2DP, "delight": _lib.POSE_DELIGHT, _lib.POSE_SC: _lib.POSE_SC, _lib.POSE_M2DP: _lib.POSE_M2DP,
+               _lib.POSE_DELIGHT: _lib.POSE_DELIGHT}
+
+
+def _pose_type(type_) -> int:
+    if type_ not in _POSE_TYPES:
+        raise ValueError("pose type must be 'sc', 'm2dp' or 'delight'")
+    return _POSE_TYPES[type_]
+
+
+def relative_pose(type_, frames_q, frames_db, variant) -> np.ndarray:
+    """sc_relative_pose for every type with variants (pr_relative_pose, host only): type_ 'sc' | 'm2dp' | 'delight', the frames [c, 16] of
+    the clouds the descriptors were generated from and the pair's variant [c] (one channel of match_align / Matcher.align) ->
+    [R | t] float64 [c, 3, 4] mapping query-camera-frame points into the DB entry's camera frame.  For 'sc': sc_relative_pose's bits."""
+    t = _pose_type(type_)
+    fq = np.ascontiguousarray(frames_q, np.float64).reshape(-1, 16)
+    fd = np.ascontiguousarray(frames_db, np.float64).reshape(-1, 16)
+    v = np.ascontiguousarray(variant, np.int32).reshape(-1)
+    if fq.shape[0] != v.shape[0] or fd.shape[0] != v.shape[0]:
+        raise ValueError("frames_q, frames_db and variant must describe the same pairs")
+    T = np.empty((v.shape[0], 3, 4), np.float64)
+    lib = _lib.load()
+    rc = lib.pr_relative_pose(t, _ptr(fq), _ptr(fd), _ptr(v), v.shape[0], _ptr(T))
+    if rc != 0:
+        raise PRError(rc, lib.pr_last_error(None).decode())
+    return T
+
+
+def _variant_view(variant, m, k, H):
+    """(pointer tensor, stride in ints) of a variant tensor [m, k] or [m, k, >= H] whose channels may be a slice of a wider tensor."""
+    import torch
+    if variant.dtype != torch.int32 or not variant.is_cuda:
+        raise ValueError("variant must be an int32 CUDA tensor")
+    if variant.dim() == 2:
+        variant = variant.unsqueeze(-1)
+    if variant.dim() != 3 or tuple(variant.shape[:2]) != (m, k) or variant.shape[2] < H:
+        raise ValueError("variant must be [m, k] or [m, k, >= hypotheses]")
+    if m * k == 0:
+        return variant, max(H, 1)
+    stride = variant.stride(1) if k > 1 or m == 1 else variant.stride(0)
+    ok = (variant.shape[2] == 1 or variant.stride(2) == 1) and (k == 1 or variant.stride(1) == stride) and (m == 1 or variant.stride(0) == k * stride)
+    if not ok or stride < H:
+        variant = variant.contiguous()
+        stride = variant.shape[2]
+    return variant, int(stride)
+
+
+def relative_pose_torch(type_, frames_q, frames_db, idx, variant, hypotheses: int = 1, db_row0: int = 0, ctx: Context | None = None):
+    """Device form (pr_relative_pose_dev): CUDA tensors frames_q [m, 16] / frames_db [n_local, 16] float64, idx int32 [m, k] GLOBAL DB rows,
+    variant int32 [m, k] or [m, k, >= hypotheses] (a channel slice of Matcher.align's tensor is read in place).  Returns device tensors
+    (T0 float64 [m, k, H, 3, 4], pair_src int32 [m, k, H], pair_dst int32 [m, k, H]) for icp_refine_torch; slots without a pose are -1 /
+    [I | 0].  Nothing synchronises."""
+    import torch
+    from .eval import _on_stream, _p
+    t = _pose_type(type_)
+    H = int(hypotheses)
+    if any((not x.is_cuda) or x.dtype != w or not x.is_contiguous() for x, w in ((frames_q, torch.float64), (frames_db, torch.float64), (idx, torch.int32))):
+        raise ValueError("relative_pose_torch: expected contiguous CUDA tensors frames f64 [*, 16], idx i32 [m, k]")
+    m, k = idx.shape
+    if frames_q.shape != (m, 16) or frames_db.dim() != 2 or frames_db.shape[1] != 16:
+        raise ValueError("relative_pose_torch: frames_q must be [m, 16] and frames_db [n_local, 16]")
+    var, stride = _variant_view(variant, m, k, H)
+    dev = idx.device
+    T0 = torch.empty((m, k, H, 3, 4), dtype=torch.float64, device=dev)
+    src = torch.empty((m, k, H), dtype=torch.int32, device=dev)
+    dst = torch.empty((m, k, H), dtype=torch.int32, device=dev)
+    with _on_stream(ctx, dev, (frames_q, frames_db, idx, var, T0, src, dst)) as cx:
+        cx.check(cx.lib.pr_relative_pose_dev(cx.h, t, _p(frames_q), m, _p(frames_db), frames_db.shape[0], int(db_row0), k, _p(idx), _p(var), stride, H,
+                                             _p(T0), _p(src), _p(dst)))
+    return T0, src, dst
+
+
+def verify_pairs_torch(type_, clouds_q, clouds_db, frames_q, frames_db, idx, variant, max_src_pts: int, max_dst_pts: int, hypotheses: int = 1,
+                       db_row0: int = 0, max_corr: float = 1.0, min_fitness: float = 0.5, max_rmse: float = 0.5, max_iter: int = 30,
+                       tol_rmse: float = 1e-6, tol_fitness: float = 1e-6, min_inliers: int = 3, ctx: Context | None = None, out=None):
+    """The device form of verify (pr_verify_pairs_dev): seed -> ICP over the [m, k, hypotheses] slots -> the better hypothesis, all on the
+    context's stream without read-back.  clouds_q / clouds_db: (xyz float64 [*, 3], offs int64 [N + 1]) CUDA tensors, cloud q = query q,
+    cloud r = DB row db_row0 + r; frames, idx, variant as relative_pose_torch takes them.  Returns device tensors (T float64 [m, k, 3, 4],
+    stats uint8 [m, k, 32] - ICP_STATS on the host -, accepted bool [m, k], hyp int32 [m, k]); out: the tuple an earlier call returned for
+    the same [m, k] - written again (fixed addresses: what a captured graph needs)."""
+    import torch
+    from .eval import _on_stream, _p
+    t = _pose_type(type_)
+    H = int(hypotheses)
+    xq, oq = clouds_q
+    xd, od = clouds_db
+    ts = (xq, oq, xd, od, frames_q, frames_db, idx)
+    want = (torch.float64, torch.int64, torch.float64, torch.int64, torch.float64, torch.float64, torch.int32)
+    if any((not x.is_cuda) or x.dtype != w or not x.is_contiguous() for x, w in zip(ts, want)):
+        raise ValueError("verify_pairs_torch: expected contiguous CUDA tensors xyz f64, offs i64, frames f64, idx i32")
+    m, k = idx.shape
+    if frames_q.shape != (m, 16) or frames_db.dim() != 2 or frames_db.shape[1] != 16:
+        raise ValueError("verify_pairs_torch: frames_q must be [m, 16] and frames_db [n_local, 16]")
+    var, stride = _variant_view(variant, m, k, H)
+    dev = idx.device
+    if out is None:
+        # (every element is written by the call; torch.empty enqueues nothing on torch's stream that the context's stream could overtake)
+        out = (torch.empty((m, k, 3, 4), dtype=torch.float64, device=dev), torch.empty((m, k, ICP_STATS.itemsize), dtype=torch.uint8, device=dev),
+               torch.empty((m, k), dtype=torch.bool, device=dev), torch.empty((m, k), dtype=torch.int32, device=dev))
+    elif out[0].shape != (m, k, 3, 4) or out[1].shape != (m, k, ICP_STATS.itemsize) or out[2].shape != (m, k) or out[3].shape != (m, k):
+        raise ValueError("verify_pairs_torch: out belongs to another [m, k]")
+    with _on_stream(ctx, dev, ts + (var,) + tuple(out)) as cx:
+        cx.check(cx.lib.pr_verify_pairs_dev(cx.h, t, _p(xq), _p(oq), oq.numel() - 1, _p(xd), _p(od), od.numel() - 1, _p(frames_q), _p(frames_db), m,
+                                            frames_db.shape[0], int(db_row0), k, _p(idx), _p(var), stride, H, int(max_src_pts), int(max_dst_pts),
+                                            int(max_iter), float(max_corr), float(tol_rmse), float(tol_fitness), int(min_inliers),
+                                            float(min_fitness), float(max_rmse), _p(out[0]), _p(out[1]), _p(out[2]), _p(out[3])))
+    return out
+
+
 def run_test(type_, hist1, hist2, gt1=None, gt2=None, loop_diff=None, mask_width=0, ctx: Context | None = None, device_eval: bool = False):
     """run_test.m:1.  Without ground truth: returns (diff_v, diff_idx) of run_test.m:57 (0-based indices).
     With gt1/gt2/loop_diff: returns (AUC, top_recall, lp_detected) through eval.precision_recall; the sweep ranks the QUERIES by their

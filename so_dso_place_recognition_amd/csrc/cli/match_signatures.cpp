@@ -17,12 +17,16 @@
 //                                     the indices are rows of hist1): one line per query, K groups "v_ch0 v_ch1", -1 where there is none.  SC: structure,
 //                                     intensity, v = 2 shift + mirror (processSC.m:24-27); M2DP: count, intensity, v = 4 a + b (processM2DP.m:18);
 //                                     DELIGHT: the octant permutation (processDELIGHT.m:2-5) and -1.  sc | m2dp | delight
-//   [--icp_out F --poses1 F --pts1 F [--poses2 F --pts2 F]]   refine and verify every returned pair (--type sc): the clouds of hist1 (and of
-//                                     hist2 for a cross match; with --online or without --poses2 they are hist1's) come from the pose / point
-//                                     files through pr_pts_preprocess_gpu (--lidarRange 45), the seed from pr_match_align + pr_sc_relative_pose,
+//   [--icp_out F --poses1 F --pts1 F [--poses2 F --pts2 F]]   refine and verify every returned pair (--type sc|delight): the clouds of hist1 (and
+//                                     of hist2 for a cross match; with --online or without --poses2 they are hist1's) come from the pose / point
+//                                     files through pr_pts_preprocess_gpu (--lidarRange 45; the down-sampling of the type's generator: voxel for
+//                                     sc, polar for delight), the seed from pr_match_align + pr_sc_relative_pose / pr_relative_pose,
 //                                     the refinement from pr_icp_pairs (--icp_max_corr 1 --icp_max_iter 30 --icp_tol_rmse 1e-6 --icp_tol_fitness
 //                                     1e-6 --icp_min_inliers 3).  One line per (query, candidate): "query match status iters fitness rmse" and
 //                                     the 12 numbers of [R | t] row by row (status: PR_ICP_*; match -1 / status 4 where there is no pair)
+//   [--icp_hyp 2]                     (--type sc) also refine the intensity channel's variant where it differs from the structure channel's and
+//                                     keep the better result (larger fitness, then smaller rmse, among status converged / max_iter; DESIGN.md
+//                                     4.12); the line then ends with the kept hypothesis "hyp" (0 | 1)
 // Output: one line per query: K pairs "index score" (0-based indices unless --one_based 1), and the reference's
 // console lines `type` / `tm` (ms per query, run_test.m:42-44).  Scores are doubles, as MATLAB holds them.
 #include <chrono>
@@ -33,6 +37,7 @@
 
 #include "../../../include/place_recognition.h"
 #include "cli_common.hpp"
+#include "../pose_seed.hpp"
 
 int main(int argc, char** argv) {
   Params prm(argc, argv);
@@ -51,7 +56,10 @@ int main(int argc, char** argv) {
   const bool want_icp = prm.get("icp_out", icpf);
   if (want_icp) {
     std::string a, b;
-    if (t != PR_TYPE_SC || !prm.get("poses1", a) || !prm.get("pts1", b)) { fprintf(stderr, "--icp_out needs --type sc and --poses1 / --pts1 (only SC has a relative pose)\n"); return 1; }
+    // (m2dp has a seed too - pr_relative_pose(PR_POSE_M2DP) - but the executable keeps refusing it for now)
+    if ((t != PR_TYPE_SC && t != PR_TYPE_DELIGHT) || !prm.get("poses1", a) || !prm.get("pts1", b)) { fprintf(stderr, "--icp_out needs --type sc|delight and --poses1 / --pts1\n"); return 1; }
+    const int hyp = (int)prm.num("icp_hyp", 1);
+    if (hyp != 1 && !(hyp == 2 && t == PR_TYPE_SC)) { fprintf(stderr, "--icp_out: --icp_hyp is 1, or 2 with --type sc (DELIGHT has one variant per pair)\n"); return 1; }
   }
   const int div = t == PR_TYPE_SC ? 1 : t == PR_TYPE_M2DP ? 4 : t == PR_TYPE_DELIGHT ? 16 : t == PR_TYPE_BOW ? 2 : 1;
   int64_t width = t == PR_TYPE_SC ? PR_SC_SIG_LEN : (t == PR_TYPE_M2DP ? PR_M2DP_SIG_LEN : PR_DELIGHT_SIG_LEN);
@@ -173,15 +181,17 @@ int main(int argc, char** argv) {
     }
     fclose(fa);
   }
-  if (want_icp) {   // seed (pr_match_align + pr_sc_relative_pose) and ICP refinement of every returned pair, on one device
+  if (want_icp) {   // seed (pr_match_align + pr_sc_relative_pose / pr_relative_pose) and ICP refinement of every returned pair, on one device
     if (!ctx && pr_create(dev_ids.empty() ? (int)prm.num("device", 0) : dev_ids[0], &ctx) != PR_OK) { fprintf(stderr, "%s\n", pr_last_error(nullptr)); return 3; }
     std::string p1, s1, p2, s2;
     prm.get("poses1", p1); prm.get("pts1", s1);
     const bool two = !online && prm.get("poses2", p2) && prm.get("pts2", s2);
     pr_clouds *cl1 = nullptr, *cl2 = nullptr;
     const double range = prm.num("lidarRange", 45.0);
-    if (pr_pts_preprocess_gpu(ctx, p1.c_str(), s1.c_str(), nullptr, range, 0, 0, &cl1) != PR_OK ||
-        (two && pr_pts_preprocess_gpu(ctx, p2.c_str(), s2.c_str(), nullptr, range, 0, 0, &cl2) != PR_OK)) {
+    const int polar = t == PR_TYPE_DELIGHT ? 1 : 0;                      // the down-sampling of the type's generator (generate_main.hpp)
+    const int H = (int)prm.num("icp_hyp", 1);
+    if (pr_pts_preprocess_gpu(ctx, p1.c_str(), s1.c_str(), nullptr, range, polar, 0, &cl1) != PR_OK ||
+        (two && pr_pts_preprocess_gpu(ctx, p2.c_str(), s2.c_str(), nullptr, range, polar, 0, &cl2) != PR_OK)) {
       fprintf(stderr, "pre-stage failed: %s\n", pr_last_error(ctx)); pr_destroy(ctx); return 4;
     }
     if (!two) cl2 = cl1;
@@ -207,18 +217,22 @@ int main(int argc, char** argv) {
     };
     std::vector<double> f1, f2;
     if (!frames_of(cl1, m, f1) || !frames_of(cl2, nd, f2)) { fprintf(stderr, "frames failed: %s\n", pr_last_error(ctx)); pr_destroy(ctx); return 4; }
-    const size_t c = (size_t)m * k;
-    std::vector<int32_t> src(c, -1), dst(c, -1);
-    std::vector<double> T0(c * 12, 0.0), T(c * 12, 0.0);
-    for (size_t e = 0; e < c; e++) {
-      T0[e * 12] = T0[e * 12 + 5] = T0[e * 12 + 10] = 1.0;
-      const int32_t q = (int32_t)(e / k), b = idx[e], v = var[e * 2];
-      if (b < 0 || b >= nd || v < 0) continue;
-      if (pr_sc_relative_pose(f1.data() + (size_t)q * 16, f2.data() + (size_t)b * 16, &v, 1, T0.data() + e * 12) != PR_OK) continue;   // (a cloud of fewer than 3 points)
-      src[e] = q; dst[e] = b;
-    }
-    std::vector<pr_icp_stats> stats(c);
-    if (pr_icp_pairs(ctx, pr_clouds_xyz(cl1), pr_clouds_offs(cl1), m, pr_clouds_xyz(cl2), pr_clouds_offs(cl2), nd, src.data(), dst.data(), (int32_t)c,
+    const size_t c = (size_t)m * k, slots = c * H;                       // slot e * H + h: hypothesis h of pair e
+    std::vector<int32_t> src(slots, -1), dst(slots, -1);
+    std::vector<double> T0(slots * 12, 0.0), T(slots * 12, 0.0);
+    for (size_t e = 0; e < c; e++)
+      for (int h = 0; h < H; h++) {
+        const size_t o = e * H + h;
+        T0[o * 12] = T0[o * 12 + 5] = T0[o * 12 + 10] = 1.0;
+        const int32_t q = (int32_t)(e / k), b = idx[e], v = var[e * 2 + h];
+        if (b < 0 || b >= nd || v < 0 || (h > 0 && v == var[e * 2])) continue;
+        const double *fq = f1.data() + (size_t)q * 16, *fb = f2.data() + (size_t)b * 16;
+        const int rc_seed = t == PR_TYPE_SC ? pr_sc_relative_pose(fq, fb, &v, 1, T0.data() + o * 12) : pr_relative_pose(PR_POSE_DELIGHT, fq, fb, &v, 1, T0.data() + o * 12);
+        if (rc_seed != PR_OK) continue;   // (a cloud of fewer than 3 points)
+        src[o] = q; dst[o] = b;
+      }
+    std::vector<pr_icp_stats> stats(slots);
+    if (pr_icp_pairs(ctx, pr_clouds_xyz(cl1), pr_clouds_offs(cl1), m, pr_clouds_xyz(cl2), pr_clouds_offs(cl2), nd, src.data(), dst.data(), (int32_t)slots,
                      T0.data(), (int32_t)prm.num("icp_max_iter", 30), prm.num("icp_max_corr", 1.0), prm.num("icp_tol_rmse", 1e-6),
                      prm.num("icp_tol_fitness", 1e-6), (int32_t)prm.num("icp_min_inliers", 3), T.data(), stats.data()) != PR_OK) {
       fprintf(stderr, "refinement failed: %s\n", pr_last_error(ctx)); pr_destroy(ctx); return 4;
@@ -226,8 +240,11 @@ int main(int argc, char** argv) {
     FILE* fi = fopen(icpf.c_str(), "w");
     if (!fi) { fprintf(stderr, "cannot write %s\n", icpf.c_str()); pr_destroy(ctx); return 5; }
     for (size_t e = 0; e < c; e++) {
-      fprintf(fi, "%d %d %d %d %.17g %.17g", (int)(e / k), dst[e], stats[e].status, stats[e].iters, stats[e].fitness, stats[e].rmse);
-      for (int a = 0; a < 12; a++) fprintf(fi, " %.17g", T[e * 12 + a]);
+      const int kept = pr::pose_select(stats.data() + e * H, H, PR_ICP_CONVERGED, PR_ICP_MAX_ITER);    // the rule of verify_select_kernel
+      const size_t o = e * H + (kept < 0 ? 0 : kept);
+      fprintf(fi, "%d %d %d %d %.17g %.17g", (int)(e / k), dst[o], stats[o].status, stats[o].iters, stats[o].fitness, stats[o].rmse);
+      for (int a = 0; a < 12; a++) fprintf(fi, " %.17g", T[o * 12 + a]);
+      if (H == 2) fprintf(fi, " %d", kept < 0 ? 0 : kept);
       fputc('\n', fi);
     }
     fclose(fi);

@@ -85,14 +85,14 @@ pr::IcpGeometry geometry(const IcpState* S, int c, int max_src, int max_dst) {
 }
 
 int check_sets(pr_ctx* ctx, const char* fn, const void* xyz_q, const void* offs_q, int32_t Nq, const void* xyz_d, const void* offs_d, int32_t Nd,
-               const void* pair_src, const void* pair_dst, int32_t c, int64_t max_src, int64_t max_dst) {
+               const void* pair_src, const void* pair_dst, int32_t c, int64_t max_src, int64_t max_dst, bool need_pairs = true) {
   if (Nq < 0 || Nd < 0 || c < 0 || max_src < 0 || max_dst < 0)
     return fail(ctx, PR_EINVAL, "%s: negative size (Nq=%d, Nd=%d, c=%d, max_src_pts=%lld, max_dst_pts=%lld)", fn, Nq, Nd, c, (long long)max_src,
                 (long long)max_dst);
   if (c > 65535 || max_src > (1 << 26) || max_dst > (1 << 26))
     return fail(ctx, PR_EINVAL, "%s: more than 65535 pairs or 2^26 points per cloud (c=%d, max_src_pts=%lld, max_dst_pts=%lld)", fn, c,
                 (long long)max_src, (long long)max_dst);
-  if (!offs_q || !offs_d || (c > 0 && (!pair_src || !pair_dst)) || (c > 0 && max_src > 0 && !xyz_q) || (c > 0 && max_dst > 0 && !xyz_d))
+  if (!offs_q || !offs_d || (c > 0 && need_pairs && (!pair_src || !pair_dst)) || (c > 0 && max_src > 0 && !xyz_q) || (c > 0 && max_dst > 0 && !xyz_d))
     return fail(ctx, PR_EINVAL, "%s: a required pointer is NULL", fn);
   return PR_OK;
 }
@@ -155,6 +155,13 @@ int host_shapes(pr_ctx* ctx, const char* fn, const int64_t* offs_q, int32_t Nq, 
 }  // namespace
 
 namespace pr {
+int icp_check_pairs_args(pr_ctx* ctx, const char* fn, const void* xyz_q, const void* offs_q, int32_t Nq, const void* xyz_d, const void* offs_d,
+                         int32_t Nd, int32_t c, int64_t max_src, int64_t max_dst, int32_t max_iter, double max_corr, double tol_rmse,
+                         double tol_fitness, int32_t min_inliers) {
+  if (int rc = check_sets(ctx, fn, xyz_q, offs_q, Nq, xyz_d, offs_d, Nd, nullptr, nullptr, c, max_src, max_dst, /*need_pairs=*/false)) return rc;
+  return check_params(ctx, fn, max_iter, max_corr, tol_rmse, tol_fitness, min_inliers);
+}
+
 void icp_release(void* p) {
   if (!p) return;
   IcpState* S = static_cast<IcpState*>(p);

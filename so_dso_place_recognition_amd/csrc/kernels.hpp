@@ -347,6 +347,18 @@ void launch_icp_nn(hipStream_t st, const IcpClouds& A, const IcpGeometry& g, con
 void launch_icp_finish(hipStream_t st, const IcpClouds& A, const IcpGeometry& g, const double* part, const IcpParams& P, int final_pass, double* T,
                        IcpStats* stats, int* done, double* prev);
 void icp_release(void* state);                  // icp.cpp: frees a context's ICP scratch (pr_destroy, streams idle)
+// icp.cpp: pr_icp_pairs_dev's argument checks (cloud sets, bounds, parameters) for a caller that brings pair lists of its own: PR_OK or
+// PR_EINVAL with the context's error text set, nothing touched
+int icp_check_pairs_args(pr_ctx* ctx, const char* fn, const void* xyz_q, const void* offs_q, int32_t Nq, const void* xyz_d, const void* offs_d,
+                         int32_t Nd, int32_t c, int64_t max_src, int64_t max_dst, int32_t max_iter, double max_corr, double tol_rmse,
+                         double tol_fitness, int32_t min_inliers);
+// pose.hip — the pose seed of matched pairs and the choice among a pair's refined hypotheses (see the file header)
+// slots [m][k][H]: hypothesis h of pair p reads variant[p * stride + h]; angles: cos | sin of k 2 pi / 60, k = 0 .. 60 (pose_seed.hpp)
+void launch_pose_seed(hipStream_t st, int type, const double* frames_q, int m, const double* frames_db, int n_local, int db_row0, int k,
+                      const int* idx, const int* variant, int stride, int H, const double* angles, double* T0, int* pair_src, int* pair_dst);
+void launch_verify_select(hipStream_t st, const double* T_h /* [c][H][3][4] */, const IcpStats* stats_h /* [c][H] */, int c, int H,
+                          double min_fitness, double max_rmse, double* T, IcpStats* stats, unsigned char* accepted, int* hyp);
+void pose_release(void* state);                 // pose.cpp: frees a context's angle tables and verify scratch (pr_destroy, streams idle)
 // pr_api.cpp: what gist.cpp and bow.cpp need of a context
 hipStream_t ctx_stream(pr_ctx* ctx);
 int ctx_device(pr_ctx* ctx);
@@ -355,6 +367,7 @@ void*& ctx_gist(pr_ctx* ctx);
 void*& ctx_bow(pr_ctx* ctx);
 void*& ctx_eval(pr_ctx* ctx);
 void*& ctx_icp(pr_ctx* ctx);
+void*& ctx_pose(pr_ctx* ctx);
 int* ctx_bow_flag(pr_ctx* ctx);                 // [1] device word: a BoW row was truncated (PR_WARN_BOW_TRUNCATED at pr_take_warnings)
 int* ctx_bow_rows_flag(pr_ctx* ctx);            // [1] device word: a non-conforming BoW query row (PR_WARN_BOW_ROWS at pr_take_warnings)
 

@@ -73,6 +73,7 @@ struct pr_ctx {
   void* bow = nullptr;           // BoW device vocabularies and grow-only scratch (bow.cpp)
   void* eval = nullptr;          // grow-only scratch and path selection of the device evaluation (eval_dev.cpp)
   void* icp = nullptr;           // grow-only scratch and path selection of the ICP refinement (icp.cpp)
+  void* pose = nullptr;          // angle tables and grow-only scratch of the pose seed / verify chain (pose.cpp)
 };
 
 struct pr_sigset {
@@ -384,6 +385,7 @@ void pr_destroy(pr_ctx* ctx) {
   pr::bow_release(ctx->bow);
   pr::eval_release(ctx->eval);
   pr::icp_release(ctx->icp);
+  pr::pose_release(ctx->pose);
   delete ctx;
 }
 
@@ -2047,6 +2049,7 @@ void*& ctx_gist(pr_ctx* ctx) { return ctx->gist; }
 void*& ctx_bow(pr_ctx* ctx) { return ctx->bow; }
 void*& ctx_eval(pr_ctx* ctx) { return ctx->eval; }
 void*& ctx_icp(pr_ctx* ctx) { return ctx->icp; }
+void*& ctx_pose(pr_ctx* ctx) { return ctx->pose; }
 int* ctx_bow_flag(pr_ctx* ctx) { return ctx->d_flags + 5; }
 int* ctx_bow_rows_flag(pr_ctx* ctx) { return ctx->d_flags + 6; }
 }  // namespace pr

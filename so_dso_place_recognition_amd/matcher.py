@@ -450,6 +450,37 @@ class _Base:
         accepted = ((status == _lib.ICP_CONVERGED) | (status == _lib.ICP_MAX_ITER)) & (f64[:, 0] >= min_fitness) & (f64[:, 1] <= max_rmse)
         return T.view(m, k, 3, 4), stats.view(m, k, -1), accepted.view(m, k)
 
+    def verify_dev(self, idx: torch.Tensor, clouds_q, clouds_db, frames_q: torch.Tensor, frames_db: torch.Tensor, max_src_pts: int,
+                   max_dst_pts: int, hypotheses: int = 1, seed: str | None = None, max_corr: float = 1.0, min_fitness: float = 0.5,
+                   max_rmse: float = 0.5, max_iter: int = 30, tol_rmse: float = 1e-6, tol_fitness: float = 1e-6, min_inliers: int = 3,
+                   db_row0: int = 0, out=None):
+        """verify() without leaving the stream, for every type with variants: align(idx) -> pr_verify_pairs_dev (seed, ICP, choice of the
+        hypothesis) with the device tensors as they are - no read-back, no host arithmetic, capturable once an eager call has covered the
+        shapes.  clouds_q / clouds_db, max_src_pts / max_dst_pts, the ICP parameters and the thresholds as verify() takes them; frames_q
+        [m, 16] / frames_db [n, 16] float64 device tensors: the PCA frames of the clouds this matcher's descriptors were generated from.
+        hypotheses = 2 also refines the second channel's variant where it differs from the first's (SC: intensity, M2DP: intensity) and
+        keeps the better result; DELIGHT has one variant per pair.  A FusedMatcher chooses the seeding descriptor with seed = "sc" | "m2dp".
+        Returns device tensors (T float64 [m, k, 3, 4], stats uint8 [m, k, 32], accepted bool [m, k], hyp int32 [m, k]: the kept
+        hypothesis); out: an earlier call's tuple, written again."""
+        from . import api
+        names = {_lib.TYPE_SC: "sc", _lib.TYPE_M2DP: "m2dp", _lib.TYPE_DELIGHT: "delight"}
+        have = [names[d.type] for d in self.descs if d.type in names]
+        if seed is None and len(have) == 1:
+            seed = have[0]
+        if seed not in have:
+            raise ValueError(f"verify_dev: seed must name one of this matcher's descriptor types {have} (a FusedMatcher needs it), not {seed!r}")
+        if hypotheses not in (1, 2) or (hypotheses == 2 and seed == "delight"):
+            raise ValueError("verify_dev: hypotheses is 1 or 2, and 1 for DELIGHT (one variant per pair)")
+        var, _ = self.align(idx, db_row0)
+        if var.shape[-1] == 4 and seed == "m2dp":
+            var = var[..., 2:]
+        idx = idx.to(torch.int32).contiguous()
+        self._enter()
+        res = api.verify_pairs_torch(seed, clouds_q, clouds_db, frames_q, frames_db, idx, var, max_src_pts, max_dst_pts, hypotheses, db_row0,
+                                     max_corr, min_fitness, max_rmse, max_iter, tol_rmse, tol_fitness, min_inliers, ctx=self.ctx, out=out)
+        self._leave()
+        return res
+
     def flagged_count(self) -> int:
         """Queries the last match(..., exact_order=False) of ONE rank left flagged by the order / containment checks (the ones the default
         match() answers from their exact rows).  Synchronises (pr_order_flagged_count); 0 once a resolving call has taken the flags."""
