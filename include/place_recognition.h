@@ -619,6 +619,53 @@ const double* pr_clouds_dev_frames(const pr_clouds* c);  /* [N][16] */
 int pr_generate_clouds(pr_ctx* ctx, int type, const pr_clouds* c, double max_rho, double* out);
 void pr_clouds_free(pr_clouds* c);
 
+/* ---- the pre-stage one keyframe at a time: a resident point window (window.hip) --------------------------
+ * pr_pts_preprocess* need the two finished text files of a drive.  A pr_window holds the reference's "nearby" point set
+ * (utils/pts_preprocess.h:135-216) in HBM instead: one push per keyframe, in this order: reset test (|translation column of
+ * w2c| < 1.0 clears the set, the overflow flag and the warm-up counter), the keyframe's new world points are appended, the
+ * first 30 pushes after a reset emit and prune nothing; every later push keeps the points with |p| < lidarRange in the
+ * camera frame (strict; the others leave the set for good, the survivors keep their order), down-samples to the best point per
+ * cell (polar = 0: voxel grid, smallest camera-y; polar = 1: 1 deg x 1 deg, smallest norm; ties: the earlier point) and emits
+ * the cloud in the iteration order of the reference's std::unordered_map.  Points, order, PCA frame and float intensity
+ * average are bit for bit those of pr_pts_preprocess_gpu over the same drive.
+ *
+ *   pr_window_create    point_capacity: most points the set holds at once (alive + one keyframe's new ones, < 2^30);
+ *                       max_new_points: most new points of one push (<= point_capacity); max_out_points: most points of an
+ *                       emitted cloud.  All device memory a push needs is allocated here.  The window is bound to ctx and its
+ *                       stream and must be destroyed before ctx.
+ *   pr_window_push_dev  stream-ordered, no host decision, no read-back, nothing allocated; the launch geometry depends on the
+ *                       create capacities only, so a captured push serves every keyframe.  EVERY argument is device memory:
+ *                       pose12 [12] the row-major 3x4 w2c, xyz_new [max_new][3] world points, inten_new [max_new], n_new_dev
+ *                       [1] int32 (clamped to 0 .. max_new; max_new <= max_new_points).  Outputs: out_xyz [max_out_points][3],
+ *                       out_inten [max_out_points], out_offs [2] int64 = {0, n_out} and out_frame [16] - what
+ *                       pr_sc_generate_frames_dev / pr_m2dp_generate_frames_dev / pr_delight_generate_frames_dev take with
+ *                       N = 1 and frames_have_ave = 1; a push that emits nothing writes {0, 0} and a zero frame.
+ *                       info [4] int32 = {emitted 0/1, n_out, points alive after the push, flags}.
+ *   OVERFLOW cannot be an error without a read-back, so it is a FLAG: when the alive set plus the new points exceeds
+ *   point_capacity (or n_new exceeds max_new) the excess NEW points are dropped, when the emitted cloud exceeds max_out_points
+ *   the excess OUTPUT points are dropped, and PR_WINDOW_OVERFLOW is set in info[3] of that push and of every later one until
+ *   the next reset (a reset pose or pr_window_reset).  From the first flagged push on the clouds are no longer the
+ *   reference's.  PR_WINDOW_ORDER_GLOBAL in info[3] (this push only) says that the order step kept its scratch in HBM
+ *   rather than in LDS (more than about 2 x 10^4 cells occupied).
+ *   pr_window_push      the host form: host pose, points and count in, host cloud (out_xyz / out_inten hold max_out_points),
+ *                       n_out, frame and info out; uploads, runs the same device path, synchronises.  n_new > max_new_points
+ *                       is PR_EINVAL here.
+ *   pr_window_reset     clears the set, the flag and the warm-up counter (stream-ordered).
+ *   pr_window_count     synchronising read of the alive count (diagnostics).
+ * PR_EINVAL (text: pr_last_error(ctx)) for a NULL handle or pointer, a non-positive capacity, max_new_points > point_capacity,
+ * max_new outside 1 .. max_new_points, polar other than 0 / 1, a lidarRange that is not finite and positive. */
+typedef struct pr_window pr_window;
+enum { PR_WINDOW_OVERFLOW = 1, PR_WINDOW_ORDER_GLOBAL = 2 };
+int pr_window_create(pr_ctx* ctx, double lidarRange, int polar, int32_t point_capacity, int32_t max_new_points, int32_t max_out_points,
+                     pr_window** out);
+void pr_window_destroy(pr_window* w);
+int pr_window_reset(pr_window* w);
+int pr_window_count(pr_window* w, int32_t* n_alive);
+int pr_window_push_dev(pr_window* w, const double* pose12, const double* xyz_new, const float* inten_new, const int32_t* n_new_dev,
+                       int32_t max_new, double* out_xyz, float* out_inten, int64_t* out_offs, double* out_frame, int32_t* info);
+int pr_window_push(pr_window* w, const double* pose12, const double* xyz_new, const float* inten_new, int32_t n_new, double* out_xyz,
+                   float* out_inten, int32_t* n_out, double* out_frame, int32_t* info);
+
 /* Signature matrix text I/O: writer = `ofstream << Eigen::MatrixXd` (test_sc.cpp:63-66, test_m2dp.cpp:83-86);
  * reader = whitespace-tolerant load (test_kitti.m:26); *out is released with pr_free. */
 int pr_write_signatures(const char* path, const double* sig, int64_t rows, int64_t cols);

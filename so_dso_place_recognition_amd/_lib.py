@@ -21,6 +21,7 @@ U8 = 2              # 8-bit images (pr_gist_generate*)
 HOST, DEVICE = 0, 1
 ICP_CONVERGED, ICP_MAX_ITER, ICP_TOO_FEW, ICP_DEGENERATE, ICP_NO_PAIR = 0, 1, 2, 3, 4     # pr_icp_stats.status
 POSE_SC, POSE_M2DP, POSE_DELIGHT = 0, 1, 2          # pr_relative_pose*'s type
+WINDOW_OVERFLOW, WINDOW_ORDER_GLOBAL = 1, 2         # info[3] of a pr_window push
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PR_AMD_LIB") or os.path.join(_HERE, "libpr_amd.so")   # PR_AMD_LIB: experiment builds only
@@ -164,6 +165,12 @@ SYMBOLS = {
     "pr_pts_preprocess": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, _dbl, C.c_int, C.c_int, C.POINTER(_vp)]),
     "pr_pts_preprocess_gpu": (C.c_int, [_vp, C.c_char_p, C.c_char_p, C.c_char_p, _dbl, C.c_int, C.c_int, C.POINTER(_vp)]),
     "pr_hash_order": (C.c_int, [_vp, _i32, _vp]),
+    "pr_window_create": (C.c_int, [_vp, _dbl, C.c_int, _i32, _i32, _i32, C.POINTER(_vp)]),
+    "pr_window_destroy": (None, [_vp]),
+    "pr_window_reset": (C.c_int, [_vp]),
+    "pr_window_count": (C.c_int, [_vp, C.POINTER(_i32)]),
+    "pr_window_push_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "pr_window_push": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _vp, _vp, C.POINTER(_i32), _vp, _vp]),
     "pr_clouds_avg_ms": (C.c_double, [_vp]),
     "pr_clouds_avg_pts": (C.c_double, [_vp]),
     "pr_clouds_count": (C.c_int64, [_vp]),

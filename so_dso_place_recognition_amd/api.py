@@ -1098,10 +1098,159 @@ def run_test(type_, hist1, hist2, gt1=None, gt2=None, loop_diff=None, mask_width
 
 
 # ------------------------------------------------------------------------------- host-side rows a1 / a2
+class CloudWindow:
+    """pr_window: the pre-stage one keyframe at a time.  The reference's "nearby" point set stays in HBM; push() appends a keyframe's new
+    world points, prunes against its pose and returns its down-sampled cloud (None during the 30 warm-up frames after a reset) - bit for
+    bit the cloud the batch pre-stage emits for that pose.  point_capacity: most points alive at once (plus one keyframe's new ones),
+    max_new: most new points of a push, max_out: most points of an emitted cloud.  Exceeding a capacity drops the excess and sets
+    WINDOW_OVERFLOW in info[3] until the next reset (there is no error: nothing is read back in the device form)."""
+
+    def __init__(self, ctx: Context | None = None, lidar_range: float = 45.0, polar: bool = False, point_capacity: int = 1 << 20,
+                 max_new: int = 1 << 16, max_out: int = 1 << 17):
+        self.ctx = ctx or default_context()
+        self.lib = self.ctx.lib
+        self.polar, self.lidar_range = bool(polar), float(lidar_range)
+        self.point_capacity, self.max_new, self.max_out = int(point_capacity), int(max_new), int(max_out)
+        h = C.c_void_p()
+        self.ctx.check(self.lib.pr_window_create(self.ctx.h, self.lidar_range, int(polar) if isinstance(polar, (bool, np.bool_)) else polar,
+                                                 self.point_capacity, self.max_new, self.max_out, C.byref(h)))
+        self.h = h
+        self._oxyz = np.empty((self.max_out, 3), np.float64)
+        self._oint = np.empty(self.max_out, np.float32)
+
+    def push(self, pose, xyz, inten):
+        """Host form (pr_window_push; synchronises): pose = 3x4 world-to-camera (12 numbers, row-major), xyz [n, 3] world points, inten [n].
+        Returns (xyz [n_out, 3] f64 | None, inten [n_out] f32 | None, frame [16] f64, info [4] i32 = emitted, n_out, alive, flags)."""
+        w = np.ascontiguousarray(pose, np.float64).reshape(12)
+        x = np.ascontiguousarray(xyz, np.float64).reshape(-1, 3)
+        it = np.ascontiguousarray(inten, np.float32).reshape(-1)
+        if len(it) != len(x):
+            raise ValueError("CloudWindow.push: xyz [n, 3] and inten [n] disagree")
+        frame = np.empty(16, np.float64); info = np.empty(4, np.int32); n_out = C.c_int32()
+        self.ctx.check(self.lib.pr_window_push(self.h, _ptr(w), _ptr(x) if len(x) else None, _ptr(it) if len(x) else None, len(x),
+                                               _ptr(self._oxyz), _ptr(self._oint), C.byref(n_out), _ptr(frame), _ptr(info)))
+        if not info[0]:
+            return None, None, frame, info
+        return self._oxyz[:n_out.value].copy(), self._oint[:n_out.value].copy(), frame, info
+
+    def empty_out(self, device=None):
+        """The output tensors of push_torch (fixed addresses for a captured graph): dict xyz [max_out, 3] f64, inten [max_out] f32,
+        offs [2] i64, frame [16] f64, info [4] i32."""
+        import torch
+        dev = device if device is not None else torch.device("cuda", self.ctx.device)
+        return dict(xyz=torch.zeros((self.max_out, 3), dtype=torch.float64, device=dev), inten=torch.zeros(self.max_out, dtype=torch.float32, device=dev),
+                    offs=torch.zeros(2, dtype=torch.int64, device=dev), frame=torch.zeros(16, dtype=torch.float64, device=dev),
+                    info=torch.zeros(4, dtype=torch.int32, device=dev))
+
+    def push_torch(self, pose, xyz, inten, n_new, out=None):
+        """Device form (pr_window_push_dev): contiguous CUDA tensors pose f64 [12] (or [3, 4]), xyz f64 [max_new', 3], inten f32 [max_new'],
+        n_new i32 [1] - the count is read on the device.  Enqueued on the window's context's stream (the caller orders it against the
+        producers of the inputs, e.g. a Context made on torch's current stream); nothing synchronises, nothing is allocated when out= (a
+        dict of empty_out()) is given, so the call can be captured and the graph replayed for every keyframe.  Returns out."""
+        import torch
+        ts = (pose, xyz, inten, n_new)
+        want = (torch.float64, torch.float64, torch.float32, torch.int32)
+        if any((not t.is_cuda) or t.dtype != w or not t.is_contiguous() for t, w in zip(ts, want)):
+            raise ValueError("push_torch: expected contiguous CUDA tensors pose f64, xyz f64, inten f32, n_new i32")
+        if pose.numel() != 12 or xyz.dim() != 2 or xyz.shape[1] != 3 or inten.numel() != xyz.shape[0] or n_new.numel() != 1:
+            raise ValueError("push_torch: pose [12], xyz [n, 3], inten [n], n_new [1]")
+        if out is None:
+            out = self.empty_out(pose.device)
+        elif out["xyz"].shape != (self.max_out, 3) or out["inten"].numel() != self.max_out:
+            raise ValueError("push_torch: out belongs to another window")
+        p = lambda t: C.c_void_p(t.data_ptr())
+        self.ctx.check(self.lib.pr_window_push_dev(self.h, p(pose), p(xyz), p(inten), p(n_new), int(xyz.shape[0]), p(out["xyz"]), p(out["inten"]),
+                                                   p(out["offs"]), p(out["frame"]), p(out["info"])))
+        return out
+
+    def reset(self):
+        self.ctx.check(self.lib.pr_window_reset(self.h))
+
+    def count(self) -> int:
+        n = C.c_int32()
+        self.ctx.check(self.lib.pr_window_count(self.h, C.byref(n)))
+        return int(n.value)
+
+    def close(self):
+        if getattr(self, "h", None) and getattr(self.ctx, "h", None):
+            self.lib.pr_window_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def split_points_by_pose(pose_ids, point_ids) -> np.ndarray:
+    """The reference's cursor rule (utils/pts_preprocess.h:196-200) as per-pose pushes: at pose p the cursor takes points while
+    id <= pose id, so an out-of-order id makes it wait.  Returns cuts int64 [len(pose_ids) + 1]: pose p is pushed the points
+    [cuts[p], cuts[p + 1]) of the file; points behind cuts[-1] are never delivered."""
+    pid = np.asarray(pose_ids, np.int64).reshape(-1)
+    qid = np.asarray(point_ids, np.int64).reshape(-1)
+    # the cursor stops at the first point with id > pose id: position c advances past point j while max(id[.. j]) <= pose id
+    run = np.maximum.accumulate(qid) if len(qid) else qid
+    cuts = np.zeros(len(pid) + 1, np.int64)
+    c = 0
+    for p, i in enumerate(pid):
+        c = max(c, int(np.searchsorted(run, i, side="right")))
+        cuts[p + 1] = c
+    return cuts
+
+
+def read_poses_points(poses_file: str, pts_file: str):
+    """The two PosesPts text files as arrays, parsed like the reference's reader for well-formed files:
+    (pose_ids i32 [M], w2c f64 [M, 12], point_ids i32 [T], xyz f64 [T, 3], inten f32 [T]).  A missing file is an empty one."""
+    def rows(path, ncol):
+        try:
+            txt = open(path).read().split()
+        except OSError:
+            txt = []
+        n = len(txt) // ncol
+        return np.array(txt[:n * ncol], dtype=object).reshape(n, ncol)
+    pr_, qr = rows(poses_file, 13), rows(pts_file, 5)
+    pid = pr_[:, 0].astype(np.int64).astype(np.int32) if len(pr_) else np.zeros(0, np.int32)
+    w = np.array([[float(v) for v in r[1:]] for r in pr_], np.float64).reshape(len(pr_), 12)
+    qid = qr[:, 0].astype(np.int64).astype(np.int32) if len(qr) else np.zeros(0, np.int32)
+    xyz = np.array([[float(v) for v in r[1:4]] for r in qr], np.float64).reshape(len(qr), 3)
+    it = np.array([np.float32(r[4]) for r in qr], np.float32).reshape(len(qr))
+    return pid, w, qid, xyz, it
+
+
+def _pts_preprocess_stream(poses_file, pts_file, incoming_id_file, lidarRange, polar_filter, ctx, capacities=None, return_frames=False):
+    """A pair of files replayed through a CloudWindow, keyframe by keyframe."""
+    pid, w, qid, xyz, it = read_poses_points(poses_file, pts_file)
+    cuts = split_points_by_pose(pid, qid)
+    per = np.diff(cuts)
+    cap = capacities or (max(int(cuts[-1]), 1), max(int(per.max()) if len(per) else 1, 1), max(int(cuts[-1]), 1))
+    win = CloudWindow(ctx, lidarRange, polar_filter, *cap)
+    X, I, offs, ids, frames = [], [], [0], [], []
+    try:
+        for p in range(len(pid)):
+            a, b = int(cuts[p]), int(cuts[p + 1])
+            ox, oi, fr, info = win.push(w[p], xyz[a:b], it[a:b])
+            if info[0]:
+                X.append(ox); I.append(oi); offs.append(offs[-1] + len(oi)); ids.append(pid[p]); frames.append(fr)
+    finally:
+        win.close()
+    if incoming_id_file:
+        with open(incoming_id_file, "w") as f:
+            f.write("".join("%d\n" % i for i in ids))
+    res = (np.concatenate(X) if X else np.zeros((0, 3)), np.concatenate(I) if I else np.zeros((0,), np.float32),
+           np.array(offs, np.int64), np.array(ids, np.int32))
+    return res + (np.array(frames, np.float64).reshape(len(ids), 16),) if return_frames else res
+
+
 def pts_preprocess(poses_file: str, pts_file: str, incoming_id_file: str | None, lidarRange: float = 45.0,
-                   polar_filter: bool = False, verbose: bool = False, gpu: bool = False, ctx: Context | None = None):
+                   polar_filter: bool = False, verbose: bool = False, gpu=False, ctx: Context | None = None):
     """pts_preprocess(...) of utils/pts_preprocess.h:169-232 -> (xyz [T,3] f64, inten [T] f32, offs [N+1] i64, ids [N] i32).
-    gpu=True runs the sliding-window / best-point-per-cell work on the device (same clouds, same point order)."""
+    gpu=True runs the sliding-window / best-point-per-cell work on the device (same clouds, same point order); gpu="stream" replays the
+    files keyframe by keyframe through a CloudWindow (the online form: the same clouds again)."""
+    if isinstance(gpu, str):
+        if gpu != "stream":
+            raise ValueError('pts_preprocess: gpu is False, True or "stream"')
+        return _pts_preprocess_stream(poses_file, pts_file, incoming_id_file, lidarRange, polar_filter, ctx or default_context())
     lib = _lib.load()
     h = C.c_void_p()
     args = (poses_file.encode(), pts_file.encode(), incoming_id_file.encode() if incoming_id_file else None,

@@ -11,6 +11,8 @@
 // tests/test_prestage.py pins the whole thing against std::unordered_map (through the oracle).
 #pragma once
 #include <cstdint>
+#include <unordered_map>
+#include <vector>
 
 #if defined(__HIPCC__)
 #define PR_HD __host__ __device__
@@ -65,6 +67,18 @@ PR_HD inline void hash_order(const int* keys, int K, const int* sched_cnt, const
   }
   int t = 0;
   for (int p = head; p != HO_BB; p = next[p]) order[t++] = p;
+}
+
+// The bucket count libstdc++ picks when the element count crosses each threshold, read off the real container (it
+// depends on counts only, never on keys): the table is rehashed to nb[i] buckets when a key is inserted while cnt[i]
+// elements exist.  Host code.
+inline void probe_bucket_schedule(int kmax, std::vector<int>& cnt, std::vector<int>& nb) {
+  std::unordered_map<int, int> m;
+  size_t last = m.bucket_count();
+  for (int k = 0; k < kmax; k++) {
+    m[k] = k;
+    if (m.bucket_count() != last) { cnt.push_back(k); nb.push_back((int)m.bucket_count()); last = m.bucket_count(); }
+  }
 }
 
 }  // namespace pr

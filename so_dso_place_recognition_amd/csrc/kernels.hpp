@@ -388,4 +388,34 @@ void launch_gather(hipStream_t st, int E, int64_t total, const int64_t* off, con
                    const int* win, const double* xyz, const float* inten, const double* W, double range, double* oxyz, float* oint,
                    double* frames /* non-NULL: one workgroup per cloud, which also leaves the cloud's PCA frame [E][16] (frames.hpp) */);
 
+// The pre-stage's cell grid (prestage_common.hpp: make_grid / cell_of)
+struct Grid { double range, step[3]; int dim[3]; int polar, azi_bins; double inv; };
+
+// window.hip — the pre-stage one keyframe at a time.  WinView: what the kernels of a push need of a pr_window (window.cpp);
+// every pointer is device memory allocated at create.
+constexpr int WIN_STATE_WORDS = 16;
+constexpr int WIN_OVERFLOW = 1;              // = PR_WINDOW_OVERFLOW
+constexpr int WIN_ORDER_GLOBAL = 2;          // = PR_WINDOW_ORDER_GLOBAL
+constexpr int WIN_ORDER_LDS_INTS = 40960;    // the order kernel's LDS scratch (160 KB): next[K] + bkt[bucket count] live there when they fit
+struct WinView {
+  Grid grid;
+  int cap, max_new, max_out, nsched;
+  int64_t C;                                 // cells of the dense table
+  int* st;                                   // [WIN_STATE_WORDS] state words
+  double* xyz[2];                            // [cap][3] world points of the set, ping-pong
+  float* inten[2];                           // [cap]
+  int *bcnt, *boff, *kcnt, *koff;            // [ceil(cap / 256)] per-workgroup counts and their exclusive scans (survivors | keys)
+  int* cell;                                 // [cap] per member
+  unsigned long long* val;                   // [cap]
+  unsigned long long* tval;                  // [C] per cell: minimum ordering value, first member, winner
+  unsigned *tfirst, *tbest;
+  int *keys, *win, *next, *order;            // [cap]
+  int* bkt;                                  // [largest bucket count of the schedule]
+  const int *sched_cnt, *sched_nb;           // [nsched] libstdc++'s growth schedule (probe_bucket_schedule)
+};
+void window_fill_grid(WinView& v, double range, int polar);
+void launch_window_reset(hipStream_t st, const WinView& v);
+void launch_window_push(hipStream_t st, const WinView& v, const double* pose, const double* xyz_new, const float* inten_new,
+                        const int* n_new_dev, int max_new, double* out_xyz, float* out_inten, int64_t* out_offs, double* out_frame, int* info);
+
 }  // namespace pr

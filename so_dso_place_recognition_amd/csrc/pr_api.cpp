@@ -433,22 +433,10 @@ int pr_sync(pr_ctx* ctx) {
 
 
 // ------------------------------------------------------------------------------------------- GPU pre-stage (row f1)
-// The bucket count libstdc++ picks when the element count crosses each threshold, read off the real container (it
-// depends on counts only, never on keys): the table is rehashed to nb[i] buckets when a key is inserted while cnt[i]
-// elements exist.
-static void probe_bucket_schedule(int kmax, std::vector<int>& cnt, std::vector<int>& nb) {
-  std::unordered_map<int, int> m;
-  size_t last = m.bucket_count();
-  for (int k = 0; k < kmax; k++) {
-    m[k] = k;
-    if (m.bucket_count() != last) { cnt.push_back(k); nb.push_back((int)m.bucket_count()); last = m.bucket_count(); }
-  }
-}
-
 int pr_hash_order(const int32_t* keys, int32_t K, int32_t* order) {   // host build of hash_order.hpp (tests; not a hot path)
   if (K < 0 || (K > 0 && (!keys || !order))) return PR_EINVAL;
   std::vector<int> cnt, nb;
-  probe_bucket_schedule(K, cnt, nb);
+  pr::probe_bucket_schedule(K, cnt, nb);
   std::vector<int> next((size_t)K + 1), bkt(nb.empty() ? 1 : (size_t)nb.back());
   pr::hash_order(keys, K, cnt.data(), nb.data(), (int)cnt.size(), next.data(), bkt.data(), order);
   return PR_OK;
@@ -570,7 +558,7 @@ int pr_pts_preprocess_gpu(pr_ctx* ctx, const char* poses_file, const char* pts_f
     int kmax = 0;
     for (int e = 0; e < E; e++) kmax = std::max(kmax, nk[e]);
     std::vector<int> scnt, snb;
-    probe_bucket_schedule(kmax, scnt, snb);
+    pr::probe_bucket_schedule(kmax, scnt, snb);
     if (scnt.empty()) { scnt.push_back(0); snb.push_back(1); }
     std::vector<int64_t> boff((size_t)E + 1, 0), ooff((size_t)E + 1, 0);
     for (int e = 0; e < E; e++) {

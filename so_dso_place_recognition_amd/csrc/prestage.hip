@@ -23,19 +23,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "frames.hpp"
 #include "hash_order.hpp"
 #include "kernels.hpp"
+#include "prestage_common.hpp"
 
 namespace pr {
 namespace {
-
-__device__ __forceinline__ bool to_camera(const double* __restrict__ w, const double* __restrict__ g, double range, double* l) {
-#pragma unroll
-  for (int r = 0; r < 3; r++) l[r] = ((w[4 * r] * g[0] + w[4 * r + 1] * g[1]) + w[4 * r + 2] * g[2]) + w[4 * r + 3] * 1.0;   // :141-142
-  const double nrm = sqrt((l[0] * l[0] + l[1] * l[1]) + l[2] * l[2]);
-  return nrm < range;                                                                                                   // :144
-}
 
 __global__ __launch_bounds__(256) void death_kernel(const double* __restrict__ xyz, const int* __restrict__ birth, int64_t T,
                                                     const double* __restrict__ W, const unsigned char* __restrict__ emit,
@@ -51,22 +44,6 @@ __global__ __launch_bounds__(256) void death_kernel(const double* __restrict__ x
     if (!to_camera(W + 12 * (size_t)p, g, range, l)) { d = p; break; }
   }
   death[j] = d;
-}
-
-// block-wide exclusive scan of 0/1 flags (256 threads = 4 waves); returns this thread's rank and the block total
-__device__ __forceinline__ int block_rank(bool flag, int* total) {
-  __shared__ int wsum[4];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const unsigned long long m = __ballot(flag);
-  const int r = __popcll(m & ((1ull << lane) - 1ull));
-  if (lane == 0) wsum[w] = __popcll(m);
-  __syncthreads();
-  int base = 0, tot = 0;
-#pragma unroll
-  for (int i = 0; i < 4; i++) { if (i < w) base += wsum[i]; tot += wsum[i]; }
-  __syncthreads();
-  *total = tot;
-  return base + r;
 }
 
 // members of emitting pose e: alive points of [first_alive[e], cursor[e]) in ascending index.  list == nullptr: count only.
@@ -87,30 +64,6 @@ __global__ __launch_bounds__(256) void members_kernel(const int* __restrict__ de
     n += tot;
   }
   if (!list && threadIdx.x == 0) cnt[e] = n;
-}
-
-__device__ __forceinline__ unsigned long long orderable(double v) {   // monotone map double -> u64 (-0.0 == +0.0)
-  v = v + 0.0;
-  const unsigned long long b = (unsigned long long)__double_as_longlong(v);
-  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-
-struct Grid { double range, step[3]; int dim[3]; int polar, azi_bins; double inv; };
-
-__device__ __forceinline__ void cell_of(const Grid& g, const double* l, int* cell, unsigned long long* val) {
-  if (g.polar) {                                                            // :100-119
-    const double xz = sqrt(l[0] * l[0] + l[2] * l[2]);
-    const int azi = (int)floor((atan2(l[2], l[0]) + M_PI) * g.inv);
-    const int ele = (int)floor((atan2(l[1], xz) + M_PI / 2) * g.inv);
-    *cell = azi + ele * g.azi_bins;
-    *val = orderable(sqrt((l[0] * l[0] + l[1] * l[1]) + l[2] * l[2]));
-  } else {                                                                  // :55-80
-    const int xi = (int)floor((l[0] + g.range) * g.step[0]);
-    const int yi = (int)floor((l[1] + g.range) * g.step[1]);
-    const int zi = (int)floor((l[2] + g.range) * g.step[2]);
-    *cell = xi + yi * g.dim[0] + zi * g.dim[0] * g.dim[1];
-    *val = orderable(l[1]);
-  }
 }
 
 __device__ __forceinline__ int pose_ordinal(const int64_t* __restrict__ off, int e0, int e1, int64_t s) {   // off[e] <= s < off[e+1]
@@ -210,57 +163,17 @@ __global__ __launch_bounds__(256) void gather_kernel(int E, const int64_t* __res
   oint[o] = inten[j];
 }
 
-// The same emission with one workgroup per cloud, which also adds up the cloud's raw moments on the way and leaves its PCA frame
-// (pts_align.h:7-46): thread t emits points t, t + 256, ... - the order in which cloud_frames_kernel (sc_gen.hip) reads them - and both
-// use reduce_moments_to_frame, so frames[e] has the bits a moments pass over the emitted cloud would produce; the float intensity average
-// is added too, and the generators then run their binning pass only (pr_*_generate_frames_dev).
+// The same emission with one workgroup per cloud, which also adds up the cloud's raw moments on the way and leaves its PCA frame and float
+// intensity average (gather_frames_cloud, prestage_common.hpp): the generators then run their binning pass only (pr_*_generate_frames_dev).
 __global__ __launch_bounds__(FRAME_THREADS) void gather_frames_kernel(const int64_t* __restrict__ off, const int64_t* __restrict__ ooff,
                                                                       const int* __restrict__ pose_of, const int* __restrict__ order,
                                                                       const int* __restrict__ win, const double* __restrict__ xyz,
                                                                       const float* __restrict__ inten, const double* __restrict__ W,
                                                                       double range, double* __restrict__ oxyz, float* __restrict__ oint,
                                                                       double* __restrict__ frames) {
-  __shared__ double red[FRAME_THREADS / 64][9];
-  __shared__ __attribute__((aligned(16))) float stage[2][2048 + 32];
-  const int e = blockIdx.x, tid = threadIdx.x;
+  const int e = blockIdx.x;
   const int64_t o0 = ooff[e], P = ooff[e + 1] - o0, m0 = off[e];
-  const double* w = W + 12 * (size_t)pose_of[e];
-  double s[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-  for (int64_t i = tid; i < P; i += FRAME_THREADS) {
-    const int j = win[m0 + order[m0 + i]];
-    const double gp[3] = {xyz[3 * (size_t)j], xyz[3 * (size_t)j + 1], xyz[3 * (size_t)j + 2]};
-    double l[3];
-    (void)to_camera(w, gp, range, l);
-    const int64_t o = o0 + i;
-    oxyz[3 * o] = l[0]; oxyz[3 * o + 1] = l[1]; oxyz[3 * o + 2] = l[2];
-    oint[o] = inten[j];
-    const double x = l[0], y = l[1], z = l[2];
-    s[0] += x; s[1] += y; s[2] += z;
-    s[3] += x * x; s[4] += x * y; s[5] += x * z; s[6] += y * y; s[7] += y * z; s[8] += z * z;
-  }
-  reduce_moments_to_frame(s, (double)P, red, frames + (size_t)e * 16);
-  // ... and the reference's float average of the emitted intensities (in emission order), so that the generators have nothing left to do
-  // but their binning pass: frames[e][14], [15] = 1
-  __threadfence_block();
-  __syncthreads();                                 // this workgroup's oint stores are visible to it
-  const float a = block_sequential_average(oint + o0, P, stage);
-  if (tid == 0) { frames[(size_t)e * 16 + 14] = (double)a; frames[(size_t)e * 16 + 15] = 1.0; }
-}
-
-Grid make_grid(double range, int polar) {
-  Grid g;
-  g.range = range;
-  g.polar = polar;
-  const double res[3] = {30, 60, 30};
-  for (int a = 0; a < 3; a++) {                                 // :55-60
-    const double r = range / res[a];
-    g.step[a] = 1.0 / r;
-    g.dim[a] = (int)(floor(2 * range * g.step[a]) + 1);
-  }
-  const double pres = 1.0 / 180.0 * M_PI;                       // :100-103
-  g.inv = 1.0 / pres;
-  g.azi_bins = (int)(floor(2 * M_PI * g.inv) + 1);
-  return g;
+  gather_frames_cloud(P, order + m0, win + m0, xyz, inten, W + 12 * (size_t)pose_of[e], range, oxyz + 3 * o0, oint + o0, frames + (size_t)e * 16);
 }
 
 }  // namespace
