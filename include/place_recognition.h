@@ -767,6 +767,36 @@ int pr_icp_pairs(pr_ctx* ctx, const double* xyz_q, const int64_t* offs_q, int32_
 int32_t pr_icp_tile_rows(void);
 int pr_set_icp_path(pr_ctx* ctx, int split);
 
+/* ---- the exact uniform-grid correspondence search of the ICP stage (icp_grid.hip; no reference counterpart) ----------
+ * Only correspondences with d2 < max_corr^2 enter an update or a statistic.  PR_ICP_SEARCH_GRID finds exactly those - the same indices,
+ * the same d2 bits - from a uniform grid over the finite target points instead of the scan of every target point: built once per call and
+ * per pair slot (cell edge h = max(max_corr (1 + 2^-10), largest extent / G), on the device), probed in the 27 cells around every
+ * transformed source point.  With it pr_icp_pairs_dev (and everything built on it: pr_icp_pairs, pr_verify_pairs_dev) returns the bytes
+ * PR_ICP_SEARCH_BRUTE returns under pr_set_icp_path(ctx, 2); against the other brute-force geometries status, iters, n_inl and fitness
+ * are equal and rmse, R, t differ by the order of the sums only ("What is bit-reproducible").  The launch contract is the
+ * brute-force one: stream-ordered, no read-back, a fixed number of launches for given (c, max_src_pts, max_dst_pts, max_iter), scratch
+ * grow-only in the context (per pair slot: cells x 4 B + max_dst_pts x 4 B + a box; cells = the power of two >= 2 max_dst_pts, halved
+ * until c slots hold at most 256 MiB of cell words; PR_ENOMEM if the allocation fails).  A coarser grid is slower, never wrong.
+ *   pr_set_icp_search / pr_get_icp_search  the context's mode: PR_ICP_SEARCH_BRUTE (the default; nothing of the calls above changes) or
+ *                     PR_ICP_SEARCH_GRID.  PR_ICP_SEARCH=brute|grid in the environment gives the initial value (read at pr_create).
+ *                     PR_EINVAL for another mode (text: pr_last_error) or a NULL context.  pr_icp_nn_dev is brute force in either mode.
+ *   pr_icp_nn_radius_dev  one correspondence pass as pr_icp_nn_dev's, for every source point the brute-force result (j, d2) where
+ *                     d2 < max_corr^2 and (-1, +Inf) elsewhere - in BRUTE mode the scan followed by a mask, in GRID mode the grid: the two
+ *                     agree bit for bit on every input (first minimum = the smaller j among equal d2; a NaN or +Inf distance never wins;
+ *                     a non-finite target point is not in the grid, a source point whose p' is non-finite or more than one cell outside
+ *                     the targets' box has no correspondent).  PR_EINVAL as pr_icp_nn_dev, and for max_corr <= 0 or not finite.
+ *   pr_icp_nn_radius  the host-buffer form. */
+#define PR_ICP_SEARCH_BRUTE 0
+#define PR_ICP_SEARCH_GRID 1
+int pr_set_icp_search(pr_ctx* ctx, int mode);
+int pr_get_icp_search(pr_ctx* ctx);
+int pr_icp_nn_radius_dev(pr_ctx* ctx, const double* d_xyz_q, const int64_t* d_offs_q, int32_t Nq, const double* d_xyz_db, const int64_t* d_offs_db,
+                         int32_t Ndb, const int32_t* d_pair_src, const int32_t* d_pair_dst, int32_t c, const double* d_T, int32_t max_src_pts,
+                         int32_t max_dst_pts, double max_corr, int64_t* d_out_offs, int32_t* d_nn_idx, double* d_nn_d2);
+int pr_icp_nn_radius(pr_ctx* ctx, const double* xyz_q, const int64_t* offs_q, int32_t Nq, const double* xyz_db, const int64_t* offs_db, int32_t Ndb,
+                     const int32_t* pair_src, const int32_t* pair_dst, int32_t c, const double* T, double max_corr, int64_t* out_offs,
+                     int32_t* nn_idx, double* nn_d2);
+
 /* ---- pose seeds for every matcher type and the stream-ordered verify chain (pose.hip; no reference counterpart) ------
  * The seed of a matched pair from the two clouds' PCA frames ([16] doubles as pr_cloud_frames_dev writes them: mean, E = [v0 v1 v2] by
  * ascending eigenvalue, 0, point count) and the pair's best-aligning variant (pr_align_pairs_dev / pr_delight_align_pairs_dev):

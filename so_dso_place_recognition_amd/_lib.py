@@ -20,6 +20,7 @@ F64, F32 = 0, 1
 U8 = 2              # 8-bit images (pr_gist_generate*)
 HOST, DEVICE = 0, 1
 ICP_CONVERGED, ICP_MAX_ITER, ICP_TOO_FEW, ICP_DEGENERATE, ICP_NO_PAIR = 0, 1, 2, 3, 4     # pr_icp_stats.status
+ICP_SEARCH_BRUTE, ICP_SEARCH_GRID = 0, 1            # pr_set_icp_search's mode
 POSE_SC, POSE_M2DP, POSE_DELIGHT = 0, 1, 2          # pr_relative_pose*'s type
 WINDOW_OVERFLOW, WINDOW_ORDER_GLOBAL = 1, 2         # info[3] of a pr_window push
 
@@ -202,6 +203,10 @@ SYMBOLS = {
     "pr_icp_pairs": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _i32, _dbl, _dbl, _dbl, _i32, _vp, _vp]),
     "pr_icp_tile_rows": (_i32, []),
     "pr_set_icp_path": (C.c_int, [_vp, C.c_int]),
+    "pr_set_icp_search": (C.c_int, [_vp, C.c_int]),
+    "pr_get_icp_search": (C.c_int, [_vp]),
+    "pr_icp_nn_radius_dev": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _i32, _i32, _dbl, _vp, _vp, _vp]),
+    "pr_icp_nn_radius": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _dbl, _vp, _vp, _vp]),
     "pr_relative_pose": (C.c_int, [C.c_int, _vp, _vp, _vp, _i32, _vp]),
     "pr_relative_pose_dev": (C.c_int, [_vp, C.c_int, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp]),
     "pr_verify_select_dev": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _dbl, _dbl, _vp, _vp, _vp, _vp]),

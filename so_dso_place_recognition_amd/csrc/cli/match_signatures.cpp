@@ -27,6 +27,8 @@
 //   [--icp_hyp 2]                     (--type sc) also refine the intensity channel's variant where it differs from the structure channel's and
 //                                     keep the better result (larger fitness, then smaller rmse, among status converged / max_iter; DESIGN.md
 //                                     4.12); the line then ends with the kept hypothesis "hyp" (0 | 1)
+//   [--icp_search brute|grid]         the correspondence search of the refinement (pr_set_icp_search; default: the context's mode, i.e. brute
+//                                     force unless PR_ICP_SEARCH says otherwise).  grid: the exact uniform-grid search
 // Output: one line per query: K pairs "index score" (0-based indices unless --one_based 1), and the reference's
 // console lines `type` / `tm` (ms per query, run_test.m:42-44).  Scores are doubles, as MATLAB holds them.
 #include <chrono>
@@ -61,6 +63,9 @@ int main(int argc, char** argv) {
     const int hyp = (int)prm.num("icp_hyp", 1);
     if (hyp != 1 && !(hyp == 2 && t == PR_TYPE_SC)) { fprintf(stderr, "--icp_out: --icp_hyp is 1, or 2 with --type sc (DELIGHT has one variant per pair)\n"); return 1; }
   }
+  std::string icp_search;
+  const bool has_icp_search = prm.get("icp_search", icp_search);
+  if (has_icp_search && icp_search != "brute" && icp_search != "grid") { fprintf(stderr, "--icp_search is brute or grid, not %s\n", icp_search.c_str()); return 1; }
   const int div = t == PR_TYPE_SC ? 1 : t == PR_TYPE_M2DP ? 4 : t == PR_TYPE_DELIGHT ? 16 : t == PR_TYPE_BOW ? 2 : 1;
   int64_t width = t == PR_TYPE_SC ? PR_SC_SIG_LEN : (t == PR_TYPE_M2DP ? PR_M2DP_SIG_LEN : PR_DELIGHT_SIG_LEN);
   double *h1 = nullptr, *h2 = nullptr;
@@ -232,6 +237,9 @@ int main(int argc, char** argv) {
         src[o] = q; dst[o] = b;
       }
     std::vector<pr_icp_stats> stats(slots);
+    if (has_icp_search && pr_set_icp_search(ctx, icp_search == "grid" ? PR_ICP_SEARCH_GRID : PR_ICP_SEARCH_BRUTE) != PR_OK) {
+      fprintf(stderr, "%s\n", pr_last_error(ctx)); pr_destroy(ctx); return 4;
+    }
     if (pr_icp_pairs(ctx, pr_clouds_xyz(cl1), pr_clouds_offs(cl1), m, pr_clouds_xyz(cl2), pr_clouds_offs(cl2), nd, src.data(), dst.data(), (int32_t)slots,
                      T0.data(), (int32_t)prm.num("icp_max_iter", 30), prm.num("icp_max_corr", 1.0), prm.num("icp_tol_rmse", 1e-6),
                      prm.num("icp_tol_fitness", 1e-6), (int32_t)prm.num("icp_min_inliers", 3), T.data(), stats.data()) != PR_OK) {

@@ -14,54 +14,13 @@
 // (Jacobi on H^T H, frames.hpp; left vectors as H v / |H v|, the third pair by cross products, which is Kabsch's det correction),
 // applies the stop rules and updates T, the statistics and the pair's `done` word.  A finished pair's later launches return at once.
 #include "frames.hpp"
+#include "icp_common.hpp"
 #include "kernels.hpp"
 
 namespace pr {
 namespace {
 
-constexpr int IC_THREADS = 256;
-
-struct PairShape { long long q0, d0; int ns, nd; };
-
-// the pair's clouds: first rows and sizes (clamped to the call's bounds); false: no pair
-__device__ __forceinline__ bool pair_shape(const IcpClouds& A, int pair, PairShape& s) {
-  const int src = A.pair_src[pair], dst = A.pair_dst[pair];
-  if (src < 0 || dst < 0 || src >= A.Nq || dst >= A.Nd) return false;
-  s.q0 = A.offs_q[src];
-  s.d0 = A.offs_d[dst];
-  const long long ns = A.offs_q[src + 1] - s.q0, nd = A.offs_d[dst + 1] - s.d0;
-  s.ns = (int)(ns < 0 ? 0 : (ns > A.max_src ? A.max_src : ns));
-  s.nd = (int)(nd < 0 ? 0 : (nd > A.max_dst ? A.max_dst : nd));
-  return true;
-}
-
-__device__ __forceinline__ void transform(const double* __restrict__ T, double x, double y, double z, double (&p)[3]) {
-#pragma unroll
-  for (int a = 0; a < 3; a++) p[a] = ((T[4 * a] * x + T[4 * a + 1] * y) + T[4 * a + 2] * z) + T[4 * a + 3];
-}
-
-// one inlier's terms, added to the lane's 17 sums
-__device__ __forceinline__ void add_inlier(double (&a)[ICP_PARTIAL], const double (&p)[3], const double* __restrict__ q, double d2) {
-  const double qx = q[0], qy = q[1], qz = q[2];
-  a[0] += 1.0; a[1] += d2;
-  a[2] += p[0]; a[3] += p[1]; a[4] += p[2];
-  a[5] += qx; a[6] += qy; a[7] += qz;
-#pragma unroll
-  for (int r = 0; r < 3; r++) { a[8 + 3 * r] += p[r] * qx; a[9 + 3 * r] += p[r] * qy; a[10 + 3 * r] += p[r] * qz; }
-}
-
-// the fixed tree of a chunk: 64-lane shuffle tree per wave, then the four waves in order
-__device__ __forceinline__ void reduce_partial(const double (&a)[ICP_PARTIAL], double (*red)[ICP_PARTIAL], double* __restrict__ out) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < ICP_PARTIAL; k++) {
-    double v = a[k];
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d);
-    if (lane == 0) red[w][k] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < ICP_PARTIAL) out[threadIdx.x] = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
-}
+using namespace icp_dev;
 
 // grid (source chunks of 256 R points, pairs, target splits).  nsplit = 1: nn_d / nn_j are the results (row base of a pair: base[pair]
 // or pair * ld) and part (or null) receives the chunk's sums; nsplit > 1: nn_d / nn_j are the slots [split][pair][ld]
@@ -135,12 +94,9 @@ __global__ __launch_bounds__(IC_THREADS) void icp_combine_kernel(IcpClouds A, co
   if (!pair_shape(A, pair, S)) return;
   const int i0 = blockIdx.x * IC_THREADS, i = i0 + threadIdx.x;
   if (i0 >= S.ns) return;
-  double a[ICP_PARTIAL];
-#pragma unroll
-  for (int k = 0; k < ICP_PARTIAL; k++) a[k] = 0.0;
+  double bd = INFINITY;
+  int bj = -1;
   if (i < S.ns) {
-    double bd = INFINITY;
-    int bj = -1;
     for (int s = 0; s < nsplit; s++) {
       const size_t e = ((size_t)s * A.c + pair) * (size_t)ld + i;
       const double d = slot_d[e];
@@ -150,14 +106,8 @@ __global__ __launch_bounds__(IC_THREADS) void icp_combine_kernel(IcpClouds A, co
     const size_t row = base ? (size_t)base[pair] : (size_t)pair * ld;
     nn_d[row + i] = bd;
     nn_j[row + i] = bj;
-    if (part && bd < mc2) {
-      const double* s = A.xyz_q + 3 * (size_t)(S.q0 + i);
-      double p[3];
-      transform(T + 12 * (size_t)pair, s[0], s[1], s[2], p);
-      add_inlier(a, p, A.xyz_d + 3 * (size_t)(S.d0 + bj), bd);
-    }
   }
-  if (part) reduce_partial(a, red, part + ((size_t)pair * nchunks + blockIdx.x) * ICP_PARTIAL);
+  if (part) chunk_sums(A, S, T, pair, i, i < S.ns, bd, bj, mc2, red, part + ((size_t)pair * nchunks + blockIdx.x) * ICP_PARTIAL);
 }
 
 // out_offs[0 .. c]: prefix of the pairs' (clamped) source sizes, 0 for a pair of -1.  One workgroup.

@@ -346,6 +346,20 @@ void launch_icp_nn(hipStream_t st, const IcpClouds& A, const IcpGeometry& g, con
                    const long long* base, double* nn_d, int* nn_j, double mc2, double* part);
 void launch_icp_finish(hipStream_t st, const IcpClouds& A, const IcpGeometry& g, const double* part, const IcpParams& P, int final_pass, double* T,
                        IcpStats* stats, int* done, double* prev);
+// icp_grid.hip — the exact uniform-grid correspondence search.  Per pair slot: the box of the finite target points, the
+// cell edge h and the cells per axis; `ends` [c][cells] ints (counts, then exclusive starts, after the scatter the cells' ends) and
+// `sorted` [c][max_dst] ints (the finite target points' indices, cell by cell)
+struct IcpGridBox { double x0[3], h; int n[3], flags; };      // flags 1: h is not finite - one cell holds every finite point
+struct IcpGrid { IcpGridBox* box; int* ends; int* sorted; int cells, G; };   // cells per pair slot (>= (G + 1)^3), G: the host's cells per axis
+constexpr double ICP_GRID_SLACK = 1.0 + 0x1p-10;               // h >= max_corr * ICP_GRID_SLACK
+// box -> clear -> count -> scan -> scatter: five launches on st, no read-back
+void launch_icp_grid_build(hipStream_t st, const IcpClouds& A, const IcpGrid& gr, double max_corr);
+// one pass: 27 cells per source point, results (j, d2) where d2 < mc2, (-1, +Inf) elsewhere, at base[pair] (or pair * ld); part (or
+// null) [c][nchunks][ICP_PARTIAL]: the sums of chunks of 256 points (icp_common.hpp's chunk_sums, as the brute-force combining launch)
+void launch_icp_grid_probe(hipStream_t st, const IcpClouds& A, const IcpGrid& gr, const double* T, const int* done, int ld, const long long* base,
+                           double* nn_d, int* nn_j, double mc2, double* part, int nchunks);
+// the brute-force pass's rows masked to d2 < mc2: (-1, +Inf) elsewhere
+void launch_icp_radius_mask(hipStream_t st, const IcpClouds& A, const long long* base, double* nn_d, int* nn_j, double mc2);
 void icp_release(void* state);                  // icp.cpp: frees a context's ICP scratch (pr_destroy, streams idle)
 // icp.cpp: pr_icp_pairs_dev's argument checks (cloud sets, bounds, parameters) for a caller that brings pair lists of its own: PR_OK or
 // PR_EINVAL with the context's error text set, nothing touched

@@ -339,6 +339,7 @@ static int create_common(int device_id, hipStream_t external, bool use_external,
   if (const char* s = getenv("PR_SC_NSPLIT")) ctx->sc_nsplit = atoi(s);
   if (const char* s = getenv("PR_FORCE_ORDER_FLAGS")) ctx->force_order = atoi(s) != 0;
   if (const char* s = getenv("PR_SC_MATCH")) ctx->sc_mode = (strcmp(s, "f32") == 0) ? PR_SC_ARITH_F32 : (strcmp(s, "f16") == 0) ? PR_SC_ARITH_F16 : PR_SC_ARITH_F16X2;
+  if (const char* s = getenv("PR_ICP_SEARCH")) (void)pr_set_icp_search(ctx, strcmp(s, "grid") == 0 ? PR_ICP_SEARCH_GRID : PR_ICP_SEARCH_BRUTE);
   if (const char* s = getenv("PR_SC_KERNEL")) ctx->sc_kernel = (strcmp(s, "h") == 0) ? 0 : 2;
   if (const char* s = getenv("PR_SC_BINARY")) ctx->sc_binary = atoi(s) != 0;
   if (const char* s = getenv("PR_SC_BINARY_PAIR_SCALE")) ctx->sc_pair_scale = (float)atof(s);

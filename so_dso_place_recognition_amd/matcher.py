@@ -419,13 +419,14 @@ class _Base:
 
     def verify(self, idx: torch.Tensor, clouds_q, clouds_db, frames_q, frames_db, max_src_pts: int, max_dst_pts: int, max_corr: float = 1.0,
                min_fitness: float = 0.5, max_rmse: float = 0.5, max_iter: int = 30, tol_rmse: float = 1e-6, tol_fitness: float = 1e-6,
-               min_inliers: int = 3, db_row0: int = 0):
+               min_inliers: int = 3, db_row0: int = 0, search: str | None = None):
         """Use a match (api.verify_matches on this matcher's context and stream): align(idx) -> pr_sc_relative_pose -> pr_icp_pairs_dev for
         every (query q of the last match(), DB row idx[q, j]).  clouds_q / clouds_db: (xyz float64 [*, 3], offs int64 [N + 1]) device
         tensors, cloud q of clouds_q = query q, cloud r of clouds_db = DB row db_row0 + r; frames_q [m, 16] / frames_db [n, 16] their PCA
         frames (device tensors or arrays); max_src_pts / max_dst_pts: the largest query / DB cloud.  Returns device tensors (T float64
         [m, k, 3, 4], stats uint8 [m, k, 32] - api.ICP_STATS on the host -, accepted bool [m, k]).  The seed is host code
-        (pr_sc_relative_pose): the variants are read back once; the refinement itself is stream-ordered.  SC only: only SC has a pose."""
+        (pr_sc_relative_pose): the variants are read back once; the refinement itself is stream-ordered.  SC only: only SC has a pose.
+        search: None | "brute" | "grid", the ICP correspondence search of this call (api.icp_search)."""
         from . import api
         assert getattr(self, "type", None) == _lib.TYPE_SC, "verify() needs an SC matcher: only SC has a relative pose"
         var, _ = self.align(idx, db_row0)
@@ -443,7 +444,7 @@ class _Base:
         dT0, dsrc, ddst = (torch.from_numpy(a).to(self.dev) for a in (T0, src, dst))
         self._enter()
         T, stats = api.icp_refine_torch(clouds_q[0], clouds_q[1], clouds_db[0], clouds_db[1], dsrc, ddst, dT0, max_src_pts, max_dst_pts, max_iter,
-                                        max_corr, tol_rmse, tol_fitness, min_inliers, ctx=self.ctx)
+                                        max_corr, tol_rmse, tol_fitness, min_inliers, ctx=self.ctx, search=search)
         self._leave()
         f64 = stats.view(torch.float64)                    # [c, 4]: fitness, rmse, (n_inl, iters), (status, pad)
         status = stats.view(torch.int32)[:, 6]
@@ -453,7 +454,7 @@ class _Base:
     def verify_dev(self, idx: torch.Tensor, clouds_q, clouds_db, frames_q: torch.Tensor, frames_db: torch.Tensor, max_src_pts: int,
                    max_dst_pts: int, hypotheses: int = 1, seed: str | None = None, max_corr: float = 1.0, min_fitness: float = 0.5,
                    max_rmse: float = 0.5, max_iter: int = 30, tol_rmse: float = 1e-6, tol_fitness: float = 1e-6, min_inliers: int = 3,
-                   db_row0: int = 0, out=None):
+                   db_row0: int = 0, out=None, search: str | None = None):
         """verify() without leaving the stream, for every type with variants: align(idx) -> pr_verify_pairs_dev (seed, ICP, choice of the
         hypothesis) with the device tensors as they are - no read-back, no host arithmetic, capturable once an eager call has covered the
         shapes.  clouds_q / clouds_db, max_src_pts / max_dst_pts, the ICP parameters and the thresholds as verify() takes them; frames_q
@@ -461,7 +462,8 @@ class _Base:
         hypotheses = 2 also refines the second channel's variant where it differs from the first's (SC: intensity, M2DP: intensity) and
         keeps the better result; DELIGHT has one variant per pair.  A FusedMatcher chooses the seeding descriptor with seed = "sc" | "m2dp".
         Returns device tensors (T float64 [m, k, 3, 4], stats uint8 [m, k, 32], accepted bool [m, k], hyp int32 [m, k]: the kept
-        hypothesis); out: an earlier call's tuple, written again."""
+        hypothesis); out: an earlier call's tuple, written again.  search: None | "brute" | "grid", the ICP correspondence search of this
+        call (api.icp_search); the context's mode is what it was afterwards."""
         from . import api
         names = {_lib.TYPE_SC: "sc", _lib.TYPE_M2DP: "m2dp", _lib.TYPE_DELIGHT: "delight"}
         have = [names[d.type] for d in self.descs if d.type in names]
@@ -477,7 +479,8 @@ class _Base:
         idx = idx.to(torch.int32).contiguous()
         self._enter()
         res = api.verify_pairs_torch(seed, clouds_q, clouds_db, frames_q, frames_db, idx, var, max_src_pts, max_dst_pts, hypotheses, db_row0,
-                                     max_corr, min_fitness, max_rmse, max_iter, tol_rmse, tol_fitness, min_inliers, ctx=self.ctx, out=out)
+                                     max_corr, min_fitness, max_rmse, max_iter, tol_rmse, tol_fitness, min_inliers, ctx=self.ctx, out=out,
+                                     search=search)
         self._leave()
         return res
 

@@ -6,8 +6,13 @@ Per shape one JSON line: ms per pr_icp_pairs_dev call (HIP events on the context
 warm-ups), one correspondence pass alone (pr_icp_nn_dev), point pairs per second of the call (31 passes) and the fraction of the non-FMA
 fp64 vector rate: 9 fp64 lane-operations per pair (3 subtractions, 3 products, 2 sums, 1 compare; the three 32-bit selects issue on the
 same port but are not counted) against 1024 SIMDs x 16 lanes x 2.4 GHz = 39.3 T/s, the figure DESIGN.md 4.10 uses.
+--search brute|grid|both chooses the correspondence search (pr_set_icp_search), both in one process so that the clocks are
+comparable.  Every line carries `search`; a grid line times one pass through pr_icp_nn_radius_dev (grid build + one probe), gives the
+build's share of the call from a call with max_iter = 0 less one probe pass (`grid_build_ms`, `grid_build_frac`), checks that T and the
+statistics equal the brute-force split path's bytes when both ran (`equals_brute_split`), and leaves out frac_of_fp64_vector_rate and the
+pair rates: they count pairs the grid never forms.
 
-    python tools/bench_icp.py [--iters 5] [--only 4096] [--out profiles/icp/bench.jsonl]"""
+    python tools/bench_icp.py [--iters 5] [--only 4096] [--search both] [--out profiles/icp/bench.jsonl]"""
 import argparse
 import ctypes as C
 import json
@@ -28,10 +33,11 @@ def main():
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--only", type=int, default=0, help="only the shape with this many points per cloud")
     ap.add_argument("--max-iter", type=int, default=30)
+    ap.add_argument("--search", choices=("brute", "grid", "both"), default="brute")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     import torch
-    from so_dso_place_recognition_amd import api
+    from so_dso_place_recognition_amd import _lib, api
     from so_dso_place_recognition_amd.matcher import _stream_context
     ctx = _stream_context(0)
     lib = ctx.lib
@@ -53,13 +59,11 @@ def main():
         T = torch.empty_like(T0); stats = torch.zeros((c, 32), dtype=torch.uint8, device="cuda")
         oo = torch.empty(c + 1, dtype=torch.int64, device="cuda"); nj = torch.empty(c * P, dtype=torch.int32, device="cuda")
         nd = torch.empty(c * P, dtype=torch.float64, device="cuda")
-        calls = {
-            "icp": lambda: lib.pr_icp_pairs_dev(ctx.h, p(xq), p(offs), c, p(xd), p(offs), c, p(pair), p(pair), c, p(T0), P, P, a.max_iter, 1.0, 0.0, 0.0,
-                                                3, p(T), p(stats)),
-            "nn": lambda: lib.pr_icp_nn_dev(ctx.h, p(xq), p(offs), c, p(xd), p(offs), c, p(pair), p(pair), c, p(T0), P, P, p(oo), p(nj), p(nd)),
-        }
-        ms = {}
-        for name, fn in calls.items():
+        def pairs_call(max_iter, T_out):
+            return lambda: lib.pr_icp_pairs_dev(ctx.h, p(xq), p(offs), c, p(xd), p(offs), c, p(pair), p(pair), c, p(T0), P, P, max_iter, 1.0, 0.0, 0.0,
+                                                3, p(T_out), p(stats))
+
+        def timed(fn):
             ts = []
             for it in range(a.iters + 2):
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -69,19 +73,45 @@ def main():
                 e1.synchronize()
                 if it >= 2:
                     ts.append(e0.elapsed_time(e1))
-            ms[name] = (float(np.median(ts)), float(min(ts)), float(max(ts)))
-        st = np.frombuffer(stats.cpu().numpy().tobytes(), api.ICP_STATS)
-        passes = a.max_iter + 1
-        pairs = float(c) * P * P * passes
-        rate = pairs / (ms["icp"][0] * 1e-3)
-        line = dict(bench="icp", pairs=c, points=P, max_iter=a.max_iter, passes=passes, iters=a.iters, icp_ms=round(ms["icp"][0], 4),
-                    icp_ms_min=round(ms["icp"][1], 4), icp_ms_max=round(ms["icp"][2], 4), nn_pass_ms=round(ms["nn"][0], 4),
-                    point_pairs_per_s=round(rate, 1), nn_pass_point_pairs_per_s=round(float(c) * P * P / (ms["nn"][0] * 1e-3), 1),
-                    frac_of_fp64_vector_rate=round(rate * OPS_PER_PAIR / PEAK, 4), ops_per_pair=OPS_PER_PAIR,
-                    status=sorted(set(st["status"].tolist())), iters_done=sorted(set(st["iters"].tolist())),
-                    fitness_min=float(st["fitness"].min()), rmse_max=float(st["rmse"].max()))
-        print(json.dumps(line), flush=True)
-        lines.append(line)
+            return float(np.median(ts)), float(min(ts)), float(max(ts))
+
+        split_bytes = None
+        for search in (("brute", "grid") if a.search == "both" else (a.search,)):
+            grid = search == "grid"
+            ctx.check(lib.pr_set_icp_search(ctx.h, _lib.ICP_SEARCH_GRID if grid else _lib.ICP_SEARCH_BRUTE))
+            calls = {"icp": pairs_call(a.max_iter, T)}
+            if grid:
+                calls["nn"] = lambda: lib.pr_icp_nn_radius_dev(ctx.h, p(xq), p(offs), c, p(xd), p(offs), c, p(pair), p(pair), c, p(T0), P, P, 1.0, p(oo),
+                                                               p(nj), p(nd))
+                calls["icp0"] = pairs_call(0, torch.empty_like(T0))              # init + build + one probe + one finish
+            else:
+                calls["nn"] = lambda: lib.pr_icp_nn_dev(ctx.h, p(xq), p(offs), c, p(xd), p(offs), c, p(pair), p(pair), c, p(T0), P, P, p(oo), p(nj), p(nd))
+            ms = {name: timed(calls[name]) for name in ("nn", "icp0", "icp") if name in calls}      # "icp" last: T and stats are the full call's
+            st = np.frombuffer(stats.cpu().numpy().tobytes(), api.ICP_STATS)
+            passes = a.max_iter + 1
+            line = dict(bench="icp", search=search, pairs=c, points=P, max_iter=a.max_iter, passes=passes, iters=a.iters, icp_ms=round(ms["icp"][0], 4),
+                        icp_ms_min=round(ms["icp"][1], 4), icp_ms_max=round(ms["icp"][2], 4), nn_pass_ms=round(ms["nn"][0], 4))
+            if grid:
+                per_pass = (ms["icp"][0] - ms["icp0"][0]) / max(a.max_iter, 1)  # one probe + one finish
+                build = max(ms["icp0"][0] - per_pass, 0.0)
+                line.update(grid_build_ms=round(build, 4), grid_build_frac=round(build / ms["icp"][0], 4), grid_pass_ms=round(per_pass, 4))
+                if split_bytes is not None:
+                    line.update(equals_brute_split=bool(split_bytes == (T.cpu().numpy().tobytes(), stats.cpu().numpy().tobytes())))
+            else:
+                pairs = float(c) * P * P * passes
+                rate = pairs / (ms["icp"][0] * 1e-3)
+                line.update(point_pairs_per_s=round(rate, 1), nn_pass_point_pairs_per_s=round(float(c) * P * P / (ms["nn"][0] * 1e-3), 1),
+                            frac_of_fp64_vector_rate=round(rate * OPS_PER_PAIR / PEAK, 4), ops_per_pair=OPS_PER_PAIR)
+                if a.search == "both":                                           # the bytes the grid has to return: the split path's
+                    ctx.check(lib.pr_set_icp_path(ctx.h, 2))
+                    ctx.check(pairs_call(a.max_iter, T)())
+                    ctx.check(lib.pr_set_icp_path(ctx.h, 0))
+                    split_bytes = (T.cpu().numpy().tobytes(), stats.cpu().numpy().tobytes())
+            line.update(status=sorted(set(st["status"].tolist())), iters_done=sorted(set(st["iters"].tolist())),
+                        fitness_min=float(st["fitness"].min()), rmse_max=float(st["rmse"].max()))
+            print(json.dumps(line), flush=True)
+            lines.append(line)
+        ctx.check(lib.pr_set_icp_search(ctx.h, _lib.ICP_SEARCH_BRUTE))
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
