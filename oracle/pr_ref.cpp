@@ -413,12 +413,9 @@ void fuse_topk(const double* dp, const double* di, int m, int n, int mask_width,
   }
 }
 
-// DELIGHT/DELIGHT.cpp:8-24 on one cloud (alignment inside, :12-13): 16 x 256 intensity histograms
-void delight_signature(const double* xyz, const float* inten, int64_t P, double* out /*16*256*/) {
+// DELIGHT/DELIGHT.cpp:17-24 on already-aligned points (alignment is :12-13): 16 x 256 intensity histograms
+void delight_signature_aligned(const double* al, const float* inten, int64_t P, double* out /*16*256*/) {
   std::fill(out, out + 16 * 256, 0.0);
-  if (P <= 0) return;
-  std::vector<double> al(3 * (size_t)P);
-  align_pca(xyz, P, al.data(), nullptr);
   for (int64_t i = 0; i < P; i++) {
     const double* p = &al[3 * i];
     float x = p[0], y = p[1], z = p[2];                                           // :17-19 (double -> float)
@@ -429,6 +426,14 @@ void delight_signature(const double* xyz, const float* inten, int64_t P, double*
     if (bin < 0 || bin >= 256) continue;   // out of range is undefined behaviour in the reference; dropped here
     out[hist * 256 + bin]++;
   }
+}
+
+// DELIGHT/DELIGHT.cpp:8-24 on one cloud (alignment inside, :12-13)
+void delight_signature(const double* xyz, const float* inten, int64_t P, double* out /*16*256*/) {
+  if (P <= 0) { std::fill(out, out + 16 * 256, 0.0); return; }
+  std::vector<double> al(3 * (size_t)P);
+  align_pca(xyz, P, al.data(), nullptr);
+  delight_signature_aligned(al.data(), inten, P, out);
 }
 
 // processDELIGHT.m:1-38: chi-square over non-empty bins, min over the 4 octant permutations
@@ -527,6 +532,16 @@ int pr_ref_sc_generate(const double* xyz, const float* inten, const int64_t* off
     sc_signature_aligned(al.data(), inten + offs[c], P, max_rho, out + (size_t)c * 2400);
   }
   return PR_REF_OK;
+}
+
+// SC.cpp:12-76 on one ALREADY-ALIGNED cloud (tests with hand-made frames): out2400 = [structure(1200) | intensity(1200)]
+void pr_ref_sc_signature_aligned(const double* aligned, const float* inten, int64_t P, double max_rho, double* out2400) {
+  sc_signature_aligned(aligned, inten, P, max_rho, out2400);
+}
+
+// DELIGHT.cpp:17-24 on one ALREADY-ALIGNED cloud (tests with hand-made frames): out4096 = 16 x 256 counts
+void pr_ref_delight_signature_aligned(const double* aligned, const float* inten, int64_t P, double* out4096) {
+  delight_signature_aligned(aligned, inten, P < 0 ? 0 : P, out4096);
 }
 
 // Exposes the intermediate matrices of one (dx,dy) variant of one ALREADY-ALIGNED cloud (tests).

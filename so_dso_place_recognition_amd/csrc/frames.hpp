@@ -1,5 +1,10 @@
-// frames.hpp — PCA frame of a cloud (utils/pts_align.h:7-46) from its raw moments, shared by sc_gen.hip (cloud_frames) and prestage.hip
-// (the gather pass that emits the frames with the points).  Device code; include in files compiled with -ffp-contract=off.
+// frames.hpp — PCA frame of a cloud (utils/pts_align.h:7-46) from its moments about a PIVOT, shared by sc_gen.hip (cloud_frames) and
+// prestage.hip (the gather pass that emits the frames with the points).  Device code; include in files compiled with -ffp-contract=off.
+//
+// The pivot is the cloud's FIRST point in input (emission) order.  Every moments pass subtracts it from each point before the products
+// (sum d, sum d d^T with d = p - pivot), so the sums have the size of the cloud's extent and not of its distance from the origin: the
+// frame of a cloud translated by kilometres (world-frame or UTM coordinates) keeps the accuracy of a centred one (raw moments lose
+// |t|^2 / extent^2 ulps in cov = sum pp^T - n mean mean^T: 3e-4 rad at a UTM northing).  The reference centres first (pts_align.h:21-30).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -39,12 +44,12 @@ __device__ inline void jacobi_eig3(double a[3][3], double v[3][3]) {
   }
 }
 
-// raw moments (sum p, sum p p^T) of a cloud of n points -> frame {mean[3], v0[3], v1[3], v2[3], 0, n, ave, has_ave} (the last two are not
-// written here: the reference's sequential FLOAT average of the intensities, SC.cpp:60-64 / M2DP.cpp:77-81, widened, and 1.0 when it is there): scatter matrix
-// cov = sum pp^T - n mean mean^T (un-normalised as pts_align.h:30), 3x3 Jacobi, eigenvalues ascending (Eigen::SelfAdjointEigenSolver
+// pivoted moments (sum d, sum d d^T, d = p - pivot) of a cloud of n points -> frame {mean[3], v0[3], v1[3], v2[3], 0, n, ave, has_ave} (the last two are not
+// written here: the reference's sequential FLOAT average of the intensities, SC.cpp:60-64 / M2DP.cpp:77-81, widened, and 1.0 when it is there):
+// mean = pivot + m' with m' = sum d / n, scatter matrix cov = sum dd^T - n m' m'^T (un-normalised as pts_align.h:30), 3x3 Jacobi, eigenvalues ascending (Eigen::SelfAdjointEigenSolver
 // order, :32-34), canonical signs (N3)
-__device__ __attribute__((noinline)) inline void finish_frame(const double s[9], double n, double* f) {
-  const double mx = s[0] / n, my = s[1] / n, mz = s[2] / n;
+__device__ __attribute__((noinline)) inline void finish_frame(const double s[9], double n, const double pivot[3], double* f) {
+  const double mx = s[0] / n, my = s[1] / n, mz = s[2] / n;          // m': the mean relative to the pivot
   double a[3][3], v[3][3];
   a[0][0] = s[3] - n * mx * mx; a[0][1] = s[4] - n * mx * my; a[0][2] = s[5] - n * mx * mz;
   a[1][1] = s[6] - n * my * my; a[1][2] = s[7] - n * my * mz; a[2][2] = s[8] - n * mz * mz;
@@ -65,15 +70,17 @@ __device__ __attribute__((noinline)) inline void finish_frame(const double s[9],
   const double cx = e[0][1] * e[1][2] - e[0][2] * e[1][1], cy = e[0][2] * e[1][0] - e[0][0] * e[1][2],
                cz = e[0][0] * e[1][1] - e[0][1] * e[1][0];
   if (cx * e[2][0] + cy * e[2][1] + cz * e[2][2] < 0) for (int k = 0; k < 3; k++) e[2][k] = -e[2][k];   // det = +1
-  f[0] = mx; f[1] = my; f[2] = mz;
+  f[0] = pivot[0] + mx; f[1] = pivot[1] + my; f[2] = pivot[2] + mz;
   for (int j = 0; j < 3; j++)
     for (int k = 0; k < 3; k++) f[3 + 3 * j + k] = e[j][k];
   f[12] = 0; f[13] = n;      // slots 14, 15: the cloud's float intensity average and its presence flag - written by whoever computes it
 }
 
 // the fixed reduction tree of a moments pass: 64-lane shuffle tree per wave, then the waves in order; thread 0 writes the frame.
-// Every moments pass that feeds thread t the same points in the same order (cloud_frames_kernel, gather_frames_kernel) gives the same bits.
-__device__ __forceinline__ void reduce_moments_to_frame(const double (&s)[9], double n, double (*red)[9] /* LDS [FRAME_THREADS / 64][9] */, double* frame) {
+// Every moments pass that feeds thread t the same points in the same order about the same pivot (cloud_frames_kernel, gather_frames_kernel)
+// gives the same bits.
+__device__ __forceinline__ void reduce_moments_to_frame(const double (&s)[9], double n, const double (&pivot)[3],
+                                                        double (*red)[9] /* LDS [FRAME_THREADS / 64][9] */, double* frame) {
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
 #pragma unroll
   for (int k = 0; k < 9; k++) {
@@ -89,7 +96,7 @@ __device__ __forceinline__ void reduce_moments_to_frame(const double (&s)[9], do
       for (int i = 0; i < FRAME_THREADS / 64; i++) v += red[i][k];
       t[k] = v;
     }
-    finish_frame(t, n, frame);
+    finish_frame(t, n, pivot, frame);
   }
 }
 

@@ -163,7 +163,7 @@ __global__ __launch_bounds__(256) void gather_kernel(int E, const int64_t* __res
   oint[o] = inten[j];
 }
 
-// The same emission with one workgroup per cloud, which also adds up the cloud's raw moments on the way and leaves its PCA frame and float
+// The same emission with one workgroup per cloud, which also adds up the cloud's moments about its first point (frames.hpp) on the way and leaves its PCA frame and float
 // intensity average (gather_frames_cloud, prestage_common.hpp): the generators then run their binning pass only (pr_*_generate_frames_dev).
 __global__ __launch_bounds__(FRAME_THREADS) void gather_frames_kernel(const int64_t* __restrict__ off, const int64_t* __restrict__ ooff,
                                                                       const int* __restrict__ pose_of, const int* __restrict__ order,

@@ -87,6 +87,12 @@ __device__ __forceinline__ void gather_frames_cloud(int64_t P, const int* __rest
   __shared__ __attribute__((aligned(16))) float stage[2][2048 + 32];
   const int tid = threadIdx.x;
   double s[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  double pv[3] = {0, 0, 0};                         // the pivot of the moments (frames.hpp): the first emitted point, as every thread computes it
+  if (P > 0) {
+    const int j = win[order[0]];
+    const double gp[3] = {xyz[3 * (size_t)j], xyz[3 * (size_t)j + 1], xyz[3 * (size_t)j + 2]};
+    (void)to_camera(w, gp, range, pv);
+  }
   for (int64_t i = tid; i < P; i += FRAME_THREADS) {
     const int j = win[order[i]];
     const double gp[3] = {xyz[3 * (size_t)j], xyz[3 * (size_t)j + 1], xyz[3 * (size_t)j + 2]};
@@ -94,11 +100,11 @@ __device__ __forceinline__ void gather_frames_cloud(int64_t P, const int* __rest
     (void)to_camera(w, gp, range, l);
     oxyz[3 * i] = l[0]; oxyz[3 * i + 1] = l[1]; oxyz[3 * i + 2] = l[2];
     oint[i] = inten[j];
-    const double x = l[0], y = l[1], z = l[2];
+    const double x = l[0] - pv[0], y = l[1] - pv[1], z = l[2] - pv[2];
     s[0] += x; s[1] += y; s[2] += z;
     s[3] += x * x; s[4] += x * y; s[5] += x * z; s[6] += y * y; s[7] += y * z; s[8] += z * z;
   }
-  reduce_moments_to_frame(s, (double)P, red, frame);
+  reduce_moments_to_frame(s, (double)P, pv, red, frame);
   // ... and the reference's float average of the emitted intensities (in emission order), so that the generators have nothing left to do
   // but their binning pass
   __threadfence_block();

@@ -7,8 +7,8 @@
 //                  cloud (8 independent chains per wave, per-lane 16-byte loads, two batches of 8 loads in flight per lane).
 //                  Runs on a high-priority side stream beside the moments AND the binning pass (11 cycles per dependent add: 0.27 ms per
 //                  50 000 points - longer than either pass).  -> ave[c] (float) and / or frames[c][14..15] (frames.hpp).
-//   cloud_frames : one streaming pass over the cloud: fp64 raw moments (sum p, sum p p^T), fixed reduction tree;
-//                  mean, scatter matrix cov = sum pp^T - P mean mean^T (un-normalised as :30), 3x3 symmetric Jacobi
+//   cloud_frames : one streaming pass over the cloud: fp64 moments about the cloud's first point (sum d, sum d d^T, d = p - p[0]:
+//                  frames.hpp), fixed reduction tree; mean = p[0] + m', scatter matrix cov = sum dd^T - P m' m'^T (un-normalised as :30), 3x3 symmetric Jacobi
 //                  eigen-solver, eigenvalues ascending, canonical signs (N3)
 //                  -> frames[c] = {mean[3], v0[3], v1[3], v2[3], 0, P, [float average, flag]} (16 doubles, frames.hpp).  Callers that
 //                  bring the frames (the GPU pre-stage emits them, averages included) skip this pass and the chain.
@@ -135,7 +135,9 @@ __global__ __launch_bounds__(FT) void cloud_frames_kernel(const double* __restri
   const int64_t P = offs[c + 1] - o0;
   double s[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
   const double* p = xyz + 3 * o0;
-  auto add = [&](double x, double y, double z) {
+  const double pv[3] = {P > 0 ? p[0] : 0.0, P > 0 ? p[1] : 0.0, P > 0 ? p[2] : 0.0};   // the pivot (frames.hpp): the cloud's first point
+  auto add = [&](double px, double py, double pz) {
+    const double x = px - pv[0], y = py - pv[1], z = pz - pv[2];
     s[0] += x; s[1] += y; s[2] += z;
     s[3] += x * x; s[4] += x * y; s[5] += x * z; s[6] += y * y; s[7] += y * z; s[8] += z * z;
   };
@@ -150,7 +152,7 @@ __global__ __launch_bounds__(FT) void cloud_frames_kernel(const double* __restri
     for (int u = 0; u < 4; u++) add(v[u][0], v[u][1], v[u][2]);
   }
   for (; i < P; i += FT) add(p[3 * i], p[3 * i + 1], p[3 * i + 2]);
-  reduce_moments_to_frame(s, (double)P, red, frames + (size_t)c * 16);
+  reduce_moments_to_frame(s, (double)P, pv, red, frames + (size_t)c * 16);
 }
 
 __device__ __forceinline__ unsigned long long dkey(double x) {   // order-preserving map double -> u64
@@ -258,11 +260,12 @@ __global__ __launch_bounds__(FT) void cloud_frames_split_kernel(const double* __
   const int64_t o0 = offs[c];
   const int64_t P = offs[c + 1] - o0;
   const int64_t i0 = P * sl / W, i1 = P * (sl + 1) / W;
+  const double* p = xyz + 3 * o0;
+  const double pv[3] = {P > 0 ? p[0] : 0.0, P > 0 ? p[1] : 0.0, P > 0 ? p[2] : 0.0};   // the pivot (frames.hpp): the CLOUD's first point, in every slice
   {
     double s[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    const double* p = xyz + 3 * o0;
     for (int64_t i = i0 + tid; i < i1; i += FT) {
-      const double x = p[3 * i], y = p[3 * i + 1], z = p[3 * i + 2];
+      const double x = p[3 * i] - pv[0], y = p[3 * i + 1] - pv[1], z = p[3 * i + 2] - pv[2];
       s[0] += x; s[1] += y; s[2] += z;
       s[3] += x * x; s[4] += x * y; s[5] += x * z; s[6] += y * y; s[7] += y * z; s[8] += z * z;
     }
@@ -284,7 +287,7 @@ __global__ __launch_bounds__(FT) void cloud_frames_split_kernel(const double* __
     double s[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     for (int u = 0; u < W; u++)                                   // slice order: the sum does not depend on the arrival order
       for (int k = 0; k < 9; k++) s[k] += partial[((size_t)cl * W + u) * 9 + k];
-    finish_frame(s, (double)P, frames + (size_t)c * 16);
+    finish_frame(s, (double)P, pv, frames + (size_t)c * 16);
   }
 }
 
@@ -444,11 +447,13 @@ void sc_gen_cluster_kernel(const double* __restrict__ xyz, const float* __restri
       pv[u] = ok ? itn[i] : 0.f;
     }
     for (int b = tid; b < 1200; b += 512) { cnt[b] = 0u; lo[b] = ~0ull; hi[b] = 0ull; sum[b] = 0.0; }
-    {   // moments of the slice (pts_align.h:9-21); points past the slice are zeros
+    const double pvt[3] = {P > 0 ? p[0] : 0.0, P > 0 ? p[1] : 0.0, P > 0 ? p[2] : 0.0};   // the pivot (frames.hpp): the cloud's first point
+    {   // moments of the slice about the pivot (pts_align.h:9-21); slots past the slice add zeros
       double s[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
       for (int u = 0; u < CK; u++) {
-        const double x = px[u], y = py[u], z = pz[u];
+        const bool ok = i0 + tid + 512 * u < i1;
+        const double x = ok ? px[u] - pvt[0] : 0.0, y = ok ? py[u] - pvt[1] : 0.0, z = ok ? pz[u] - pvt[2] : 0.0;
         s[0] += x; s[1] += y; s[2] += z;
         s[3] += x * x; s[4] += x * y; s[5] += x * z; s[6] += y * y; s[7] += y * z; s[8] += z * z;
       }
@@ -473,7 +478,7 @@ void sc_gen_cluster_kernel(const double* __restrict__ xyz, const float* __restri
         for (int u = 0; u < CW; u++)                                  // slice order: the sum does not depend on the arrival order
           for (int k = 0; k < 9; k++) s[k] += mom[u * 9 + k];
         double f[16];
-        finish_frame(s, (double)P, f);
+        finish_frame(s, (double)P, pvt, f);
         for (int k = 0; k < 16; k++) { frs[k] = f[k]; fr[k] = f[k]; frames[(size_t)c * 16 + k] = f[k]; }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __hip_atomic_store(&my->seq[par], it + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

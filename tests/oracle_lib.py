@@ -44,6 +44,8 @@ def lib():
     L.pr_ref_sc_distance.argtypes = [_dp, C.c_int32, _dp, C.c_int32, _dp, _dp]
     L.pr_ref_m2dp_distance.argtypes = [_dp, C.c_int32, _dp, C.c_int32, _dp, _dp]
     L.pr_ref_delight_generate.argtypes = [_dp, _fp, _lp, C.c_int32, _dp]
+    L.pr_ref_sc_signature_aligned.argtypes = [_dp, _fp, C.c_int64, C.c_double, _dp]
+    L.pr_ref_delight_signature_aligned.argtypes = [_dp, _fp, C.c_int64, _dp]
     L.pr_ref_delight_distance.argtypes = [_dp, C.c_int32, _dp, C.c_int32, _dp]
     L.pr_ref_match_topk_fused.argtypes = [_dp, _dp, C.c_int32, _dp, _dp, C.c_int32, C.c_int32, C.c_double, C.c_int32, _ip, _dp]
     L.pr_ref_gist_distance.argtypes = [_dp, C.c_int32, _dp, C.c_int32, C.c_int32, _dp]
@@ -118,6 +120,39 @@ def top_singular_pair(A):
     out = np.empty(192)
     lib().pr_ref_top_singular_pair(np.ascontiguousarray(A, np.float64), out)
     return out
+
+
+def sc_signature_aligned(aligned, inten, max_rho=45.0):
+    """SC.cpp:12-76 on the ALREADY-ALIGNED points of one cloud -> [structure(1200) | intensity(1200)]."""
+    aligned = np.ascontiguousarray(aligned, np.float64).reshape(-1, 3)
+    out = np.empty(2400)
+    lib().pr_ref_sc_signature_aligned(aligned, np.ascontiguousarray(inten, np.float32), aligned.shape[0], max_rho, out)
+    return out
+
+
+def delight_signature_aligned(aligned, inten):
+    """DELIGHT.cpp:17-24 on the ALREADY-ALIGNED points of one cloud -> [16, 256] counts."""
+    aligned = np.ascontiguousarray(aligned, np.float64).reshape(-1, 3)
+    out = np.empty((16, 256))
+    lib().pr_ref_delight_signature_aligned(aligned, np.ascontiguousarray(inten, np.float32), aligned.shape[0], out)
+    return out
+
+
+M2DP_VARIANTS = ((-1, -1), (-1, 1), (1, -1), (1, 1))      # (dx, dy) in the order of test_m2dp.cpp:47-48
+
+
+def m2dp_signature_aligned(aligned, inten, max_rho=45.0, with_matrices=False):
+    """The four variant rows of pr_ref_m2dp_generate for one ALREADY-ALIGNED cloud: [4, 384], row = [cnt U1|V1 | int U1|V1].
+    with_matrices: also the eight matrices [4, 2, 64, 128] (count, intensity) the rows come from."""
+    aligned = np.ascontiguousarray(aligned, np.float64).reshape(-1, 3)
+    rows = np.empty((4, 384))
+    mats = np.empty((4, 2, 64, 128))
+    for v, (dx, dy) in enumerate(M2DP_VARIANTS):
+        cm, im = m2dp_matrices(aligned, inten, max_rho, dx, dy)
+        rows[v, :192] = top_singular_pair(cm)
+        rows[v, 192:] = top_singular_pair(im)
+        mats[v, 0], mats[v, 1] = cm, im
+    return (rows, mats) if with_matrices else rows
 
 
 def plane_table():
