@@ -844,6 +844,62 @@ int pr_verify_pairs_dev(pr_ctx* ctx, int type, const double* d_xyz_q, const int6
                         int32_t max_src_pts, int32_t max_dst_pts, int32_t max_iter, double max_corr, double tol_rmse, double tol_fitness,
                         int32_t min_inliers, double min_fitness, double max_rmse, double* d_T, pr_icp_stats* d_stats, uint8_t* d_accepted,
                         int32_t* d_hyp);
+
+/* ---- the resident keyframe map: a CSR set of keyframe clouds that grows on the stream (map.hip) ----------------------
+ * pr_verify_pairs_dev needs the clouds and PCA frames of every earlier keyframe as one CSR set.  A pr_map keeps that set while a drive
+ * runs, over CALLER-OWNED device buffers in the layouts the rest of this header takes (pr_map_buffers): xyz [point_capacity][3] f64,
+ * inten [point_capacity] f32, offs [keyframe_capacity + 1] i64, frames [keyframe_capacity][16] f64 (as pr_cloud_frames_dev / a window push
+ * writes them, intensity-average slots included), poses [keyframe_capacity][12] f64 (w2c), ids [keyframe_capacity] i32 and
+ * state [4] i32 = {keyframes, flags, 0, 0}.  The addresses never change, so a graph captured around an append or a verify is replayed
+ * for every keyframe, and every stream-ordered call of this header reads the map in place (xyz + offs as a CSR set of keyframe_capacity
+ * clouds, frames as its [n][16] frames).
+ *
+ *   pr_map_create      binds the buffers (they must outlive the map), allocates the plan scratch (sized by max_append: the most clouds of
+ *                      one append) and zeroes offs, frames and state.  max_cloud_points: most points of a stored cloud (<= point_capacity).
+ *                      The map is bound to ctx and its stream and must be destroyed before ctx.  pr_map_destroy frees the handle and its
+ *                      scratch, never the buffers.
+ *   pr_map_append_dev  stream-ordered, no host decision, no read-back, nothing allocated: three launches (plan, copy, commit) whose
+ *                      geometry depends on N, max_points and the create capacities only, so one captured append serves every keyframe.
+ *                      EVERY argument is device memory: cloud i is the points [d_offs[i], d_offs[i + 1]) of d_xyz / d_inten (d_offs[0]
+ *                      need not be 0; a negative size counts as 0), d_frames [N][16], d_poses [N][12] or NULL (zeros are stored), d_ids
+ *                      [N] or NULL (-1), d_emitted [>= 1] or NULL, d_info [4].  max_points: the most points the N clouds hold together -
+ *                      one copy lane per point; values above max_cloud_points x N are clamped.  After a window push:
+ *                      pr_map_append_dev(map, out_xyz, out_inten, out_offs, out_frame, pose, id, info_of_the_push, 1, max_out_points, info).
+ *     The rule, decided on the device.  d_emitted != NULL and d_emitted[0] == 0: nothing happens, info = {0, -1, keyframes, flags}.
+ *     Otherwise the N clouds are taken in order.  A cloud that finds no free row (keyframes == keyframe_capacity) is not appended and
+ *     PR_MAP_OVERFLOW is set.  A cloud with a free row ALWAYS consumes it - the map stays row for row in step with a signature database
+ *     that grows beside it - and its pose and id are stored; its points and frame are stored too unless it has more than
+ *     max_cloud_points points, its points do not fit into what is left of point_capacity, or they lie beyond the call's max_points:
+ *     then the row holds an EMPTY cloud and a ZERO frame (never a truncated cloud under the full cloud's frame) and
+ *     PR_MAP_OVERFLOW | PR_MAP_DROPPED is set.  info = {clouds appended, first row or -1, keyframes after, flags}: PR_MAP_OVERFLOW stays
+ *     set (in state[1] and in every later info) until pr_map_reset, PR_MAP_DROPPED is reported by the call that dropped.
+ *     Between calls: offs[0] = 0 and offs ascends over rows 0 .. keyframes; every row >= keyframes has an all-zero frame, so
+ *     pr_relative_pose_dev turns a candidate there into PR_ICP_NO_PAIR, and its offs read as an empty or negative size, which the ICP
+ *     kernels clamp to 0.  Nothing is written outside the seven buffers' stated extents or to a row >= keyframe_capacity.
+ *   pr_map_append      the host form: host arrays of the same meaning (info [4] host), uploads, runs the device path, synchronises.
+ *   pr_map_reset       zeroes offs, frames and state (stream-ordered).
+ *   pr_map_count       synchronising read of keyframes, stored points and the flags (diagnostics).
+ *   pr_map_verify_dev  pr_verify_pairs_dev with the map as the DB set: Ndb = n_local = keyframe_capacity, db_row0 = 0, max_dst_pts =
+ *                      max_cloud_points, d_idx = rows of the map; the same launches, scratch and capturability, no arithmetic of its own.
+ * PR_EINVAL (text: pr_last_error) before any device is touched for a NULL handle, buffer or required pointer, a non-positive capacity,
+ * max_cloud_points > point_capacity, max_cloud_points x max_append >= 2^38, N outside 0 .. max_append, a negative max_points.  N = 0 is
+ * valid. */
+typedef struct pr_map pr_map;
+typedef struct pr_map_buffers { double* xyz; float* inten; int64_t* offs; double* frames; double* poses; int32_t* ids; int32_t* state; } pr_map_buffers;
+enum { PR_MAP_OVERFLOW = 1, PR_MAP_DROPPED = 2 };
+int pr_map_create(pr_ctx* ctx, const pr_map_buffers* buffers, int32_t keyframe_capacity, int64_t point_capacity, int32_t max_cloud_points,
+                  int32_t max_append, pr_map** out);
+void pr_map_destroy(pr_map* m);
+int pr_map_reset(pr_map* m);
+int pr_map_count(pr_map* m, int32_t* keyframes, int64_t* points, int32_t* flags);
+int pr_map_append_dev(pr_map* m, const double* d_xyz, const float* d_inten, const int64_t* d_offs, const double* d_frames, const double* d_poses,
+                      const int32_t* d_ids, const int32_t* d_emitted, int32_t N, int64_t max_points, int32_t* d_info);
+int pr_map_append(pr_map* m, const double* xyz, const float* inten, const int64_t* offs, const double* frames, const double* poses,
+                  const int32_t* ids, const int32_t* emitted, int32_t N, int32_t* info);
+int pr_map_verify_dev(pr_map* m, int type, const double* d_xyz_q, const int64_t* d_offs_q, int32_t Nq, const double* d_frames_q, int32_t mq,
+                      int32_t k, const int32_t* d_idx, const int32_t* d_variant, int32_t variant_stride, int32_t H, int32_t max_src_pts,
+                      int32_t max_iter, double max_corr, double tol_rmse, double tol_fitness, int32_t min_inliers, double min_fitness,
+                      double max_rmse, double* d_T, pr_icp_stats* d_stats, uint8_t* d_accepted, int32_t* d_hyp);
 const char* pr_host_last_error(void);
 
 #ifdef __cplusplus

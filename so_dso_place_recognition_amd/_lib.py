@@ -23,6 +23,7 @@ ICP_CONVERGED, ICP_MAX_ITER, ICP_TOO_FEW, ICP_DEGENERATE, ICP_NO_PAIR = 0, 1, 2,
 ICP_SEARCH_BRUTE, ICP_SEARCH_GRID = 0, 1            # pr_set_icp_search's mode
 POSE_SC, POSE_M2DP, POSE_DELIGHT = 0, 1, 2          # pr_relative_pose*'s type
 WINDOW_OVERFLOW, WINDOW_ORDER_GLOBAL = 1, 2         # info[3] of a pr_window push
+MAP_OVERFLOW, MAP_DROPPED = 1, 2                    # info[3] of a pr_map append
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PR_AMD_LIB") or os.path.join(_HERE, "libpr_amd.so")   # PR_AMD_LIB: experiment builds only
@@ -212,8 +213,23 @@ SYMBOLS = {
     "pr_verify_select_dev": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _dbl, _dbl, _vp, _vp, _vp, _vp]),
     "pr_verify_pairs_dev": (C.c_int, [_vp, C.c_int, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _i32,
                                       _i32, _dbl, _dbl, _dbl, _i32, _dbl, _dbl, _vp, _vp, _vp, _vp]),
+    "pr_map_create": (C.c_int, [_vp, _vp, _i32, C.c_int64, _i32, _i32, C.POINTER(_vp)]),
+    "pr_map_destroy": (None, [_vp]),
+    "pr_map_reset": (C.c_int, [_vp]),
+    "pr_map_count": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(C.c_int64), C.POINTER(_i32)]),
+    "pr_map_append_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, C.c_int64, _vp]),
+    "pr_map_append": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
+    "pr_map_verify_dev": (C.c_int, [_vp, C.c_int, _vp, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _dbl, _dbl, _dbl, _i32, _dbl,
+                                    _dbl, _vp, _vp, _vp, _vp]),
     "pr_host_last_error": (C.c_char_p, []),
 }
+
+
+
+class MapBuffers(C.Structure):
+    """pr_map_buffers: the seven caller-owned device buffers of a pr_map."""
+    _fields_ = [(n, _vp) for n in ("xyz", "inten", "offs", "frames", "poses", "ids", "state")]
+
 
 _lib = None
 HIP_RUNTIME = "system"      # which libamdhip64 this process ended up on (_one_hip_runtime)

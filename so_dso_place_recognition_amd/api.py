@@ -1083,6 +1083,18 @@ def relative_pose_torch(type_, frames_q, frames_db, idx, variant, hypotheses: in
     return T0, src, dst
 
 
+def _verify_out(out, m, k, dev, who):
+    """The result tensors (T, stats, accepted, hyp) of a verify call over [m, k] pairs: new ones, or the checked tuple of an earlier call."""
+    import torch
+    if out is None:
+        # (every element is written by the call; torch.empty enqueues nothing on torch's stream that the context's stream could overtake)
+        return (torch.empty((m, k, 3, 4), dtype=torch.float64, device=dev), torch.empty((m, k, ICP_STATS.itemsize), dtype=torch.uint8, device=dev),
+                torch.empty((m, k), dtype=torch.bool, device=dev), torch.empty((m, k), dtype=torch.int32, device=dev))
+    if out[0].shape != (m, k, 3, 4) or out[1].shape != (m, k, ICP_STATS.itemsize) or out[2].shape != (m, k) or out[3].shape != (m, k):
+        raise ValueError(f"{who}: out belongs to another [m, k]")
+    return out
+
+
 def verify_pairs_torch(type_, clouds_q, clouds_db, frames_q, frames_db, idx, variant, max_src_pts: int, max_dst_pts: int, hypotheses: int = 1,
                        db_row0: int = 0, max_corr: float = 1.0, min_fitness: float = 0.5, max_rmse: float = 0.5, max_iter: int = 30,
                        tol_rmse: float = 1e-6, tol_fitness: float = 1e-6, min_inliers: int = 3, ctx: Context | None = None, out=None,
@@ -1108,12 +1120,7 @@ def verify_pairs_torch(type_, clouds_q, clouds_db, frames_q, frames_db, idx, var
         raise ValueError("verify_pairs_torch: frames_q must be [m, 16] and frames_db [n_local, 16]")
     var, stride = _variant_view(variant, m, k, H)
     dev = idx.device
-    if out is None:
-        # (every element is written by the call; torch.empty enqueues nothing on torch's stream that the context's stream could overtake)
-        out = (torch.empty((m, k, 3, 4), dtype=torch.float64, device=dev), torch.empty((m, k, ICP_STATS.itemsize), dtype=torch.uint8, device=dev),
-               torch.empty((m, k), dtype=torch.bool, device=dev), torch.empty((m, k), dtype=torch.int32, device=dev))
-    elif out[0].shape != (m, k, 3, 4) or out[1].shape != (m, k, ICP_STATS.itemsize) or out[2].shape != (m, k) or out[3].shape != (m, k):
-        raise ValueError("verify_pairs_torch: out belongs to another [m, k]")
+    out = _verify_out(out, m, k, dev, "verify_pairs_torch")
     with _on_stream(ctx, dev, ts + (var,) + tuple(out)) as cx, icp_search(cx, search):
         cx.check(cx.lib.pr_verify_pairs_dev(cx.h, t, _p(xq), _p(oq), oq.numel() - 1, _p(xd), _p(od), od.numel() - 1, _p(frames_q), _p(frames_db), m,
                                             frames_db.shape[0], int(db_row0), k, _p(idx), _p(var), stride, H, int(max_src_pts), int(max_dst_pts),
@@ -1218,6 +1225,148 @@ class CloudWindow:
     def close(self):
         if getattr(self, "h", None) and getattr(self.ctx, "h", None):
             self.lib.pr_window_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class KeyframeMap:
+    """pr_map: the clouds, PCA frames, poses and ids of the keyframes seen so far as one CSR set in HBM that grows on the stream - what
+    verify_dev needs as its DB side, at fixed addresses.  The seven buffers are zeroed torch tensors on the context's
+    device (or the caller's: buffers = dict of the seven names): .xyz [point_capacity, 3] f64, .inten [point_capacity] f32, .offs
+    [keyframe_capacity + 1] i64, .frames [keyframe_capacity, 16] f64, .poses [keyframe_capacity, 12] f64, .ids [keyframe_capacity] i32,
+    .state [4] i32 = keyframes, flags, 0, 0; .clouds = (xyz, offs).  A cloud that finds a free row always takes it (the map stays in step
+    with a signature database growing beside it); one that does not fit (more than max_cloud_points points, no room left in xyz, beyond
+    the call's max_points) leaves an empty cloud and a zero frame there and sets MAP_OVERFLOW | MAP_DROPPED in info[3]; without a free
+    row nothing is appended and MAP_OVERFLOW is set.  MAP_OVERFLOW stays until reset().  There is no error: nothing is read back."""
+
+    NAMES = ("xyz", "inten", "offs", "frames", "poses", "ids", "state")
+
+    def __init__(self, ctx: Context | None, keyframe_capacity: int, point_capacity: int, max_cloud_points: int, max_append: int = 1,
+                 buffers: dict | None = None):
+        import torch
+        self.ctx = ctx or default_context()
+        self.lib = self.ctx.lib
+        self.keyframe_capacity, self.point_capacity = int(keyframe_capacity), int(point_capacity)
+        self.max_cloud_points, self.max_append = int(max_cloud_points), int(max_append)
+        self.h = None
+        kc, pc = max(self.keyframe_capacity, 0), max(self.point_capacity, 0)
+        dev = torch.device("cuda", self.ctx.device)
+        shapes = dict(xyz=((pc, 3), torch.float64), inten=((pc,), torch.float32), offs=((kc + 1,), torch.int64), frames=((kc, 16), torch.float64),
+                      poses=((kc, 12), torch.float64), ids=((kc,), torch.int32), state=((4,), torch.int32))
+        if buffers is None:
+            buffers = {n: torch.zeros(s, dtype=dt, device=dev) for n, (s, dt) in shapes.items()}
+        for n, (s, dt) in shapes.items():
+            t = buffers[n]
+            if (not t.is_cuda) or t.dtype != dt or not t.is_contiguous() or tuple(t.shape) != tuple(s):
+                raise ValueError(f"KeyframeMap: buffer {n} must be a contiguous CUDA tensor {dt} {list(s)}")
+            setattr(self, n, t)
+        torch.cuda.synchronize(dev)                       # torch's fills (its stream) before the library's stream writes the buffers
+        rec = _lib.MapBuffers(*(C.c_void_p(getattr(self, n).data_ptr()) for n in self.NAMES))
+        h = C.c_void_p()
+        self.ctx.check(self.lib.pr_map_create(self.ctx.h, C.byref(rec), self.keyframe_capacity, self.point_capacity, self.max_cloud_points,
+                                              self.max_append, C.byref(h)))
+        self.h = h
+
+    @property
+    def clouds(self):
+        return self.xyz, self.offs
+
+    def append_torch(self, xyz, inten, offs, frames, poses=None, ids=None, emitted=None, max_points=None, info=None):
+        """Device form (pr_map_append_dev): contiguous CUDA tensors xyz f64 [n, 3], inten f32 [n], offs i64 [N + 1] (cloud i = points
+        offs[i] .. offs[i + 1]; offs[0] need not be 0), frames f64 [N, 16] ([16] for N = 1), poses f64 [N, 12] | None (zeros), ids i32 [N] |
+        None (-1), emitted i32 [>= 1] | None - emitted[0] == 0 switches the call off on the device (info of the window push in front).
+        max_points: the most points the N clouds hold together (default n).  Enqueued on the map's context's stream; nothing synchronises,
+        nothing is allocated when info= (i32 [4]) is given, so a captured append serves every keyframe.  Returns info (device) =
+        clouds appended, first row | -1, keyframes after, flags."""
+        import torch
+        N = offs.numel() - 1
+        ts = [(xyz, torch.float64), (inten, torch.float32), (offs, torch.int64), (frames, torch.float64)]
+        ts += [(t, w) for t, w in ((poses, torch.float64), (ids, torch.int32), (emitted, torch.int32), (info, torch.int32)) if t is not None]
+        if any((not t.is_cuda) or t.dtype != w or not t.is_contiguous() for t, w in ts):
+            raise ValueError("append_torch: expected contiguous CUDA tensors xyz f64, inten f32, offs i64, frames f64, poses f64, ids i32, "
+                             "emitted i32, info i32")
+        if N < 0 or xyz.dim() != 2 or xyz.shape[1] != 3 or inten.numel() != xyz.shape[0] or frames.numel() != 16 * N \
+                or (poses is not None and poses.numel() != 12 * N) or (ids is not None and ids.numel() != N) \
+                or (emitted is not None and emitted.numel() < 1) or (info is not None and info.numel() != 4):
+            raise ValueError("append_torch: xyz [n, 3], inten [n], offs [N + 1], frames [N, 16], poses [N, 12], ids [N], emitted [>= 1], info [4]")
+        if info is None:
+            info = torch.empty(4, dtype=torch.int32, device=xyz.device)
+        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        self.ctx.check(self.lib.pr_map_append_dev(self.h, p(xyz), p(inten), p(offs), p(frames), p(poses), p(ids), p(emitted), N,
+                                                  int(xyz.shape[0] if max_points is None else max_points), p(info)))
+        return info
+
+    def append_push(self, out, pose=None, id=None, info=None):
+        """The keyframe a CloudWindow.push_torch left in `out` (its cloud, frame and - as emitted - its info: a warm-up push appends
+        nothing), with pose f64 [12] and id i32 [1] device tensors (or None)."""
+        return self.append_torch(out["xyz"], out["inten"], out["offs"], out["frame"], poses=pose, ids=id, emitted=out["info"],
+                                 max_points=int(out["xyz"].shape[0]), info=info)
+
+    def append(self, xyz, inten, offs, frames, poses=None, ids=None, emitted=None):
+        """Host form (pr_map_append; synchronises): numpy arrays of the same meaning.  Returns info int32 [4]."""
+        o = np.ascontiguousarray(offs, np.int64).reshape(-1)
+        N = len(o) - 1
+        x = np.ascontiguousarray(xyz, np.float64).reshape(-1, 3)
+        it = np.ascontiguousarray(inten, np.float32).reshape(-1)
+        fr = np.ascontiguousarray(frames, np.float64).reshape(-1)
+        po = None if poses is None else np.ascontiguousarray(poses, np.float64).reshape(-1)
+        ii = None if ids is None else np.ascontiguousarray(ids, np.int32).reshape(-1)
+        em = None if emitted is None else np.ascontiguousarray(emitted, np.int32).reshape(-1)
+        if N < 0 or len(it) != len(x) or len(fr) != 16 * N or (po is not None and len(po) != 12 * N) or (ii is not None and len(ii) != N) \
+                or (em is not None and len(em) < 1) or (N > 0 and (o.min() < 0 or o.max() > len(x))):
+            raise ValueError("KeyframeMap.append: xyz [n, 3], inten [n], offs [N + 1] within n, frames [N, 16], poses [N, 12], ids [N], emitted [>= 1]")
+        info = np.empty(4, np.int32)
+        self.ctx.check(self.lib.pr_map_append(self.h, _ptr(x), _ptr(it), _ptr(o), _ptr(fr), _ptr(po), _ptr(ii), _ptr(em), N, _ptr(info)))
+        return info
+
+    def verify_dev(self, matcher, idx, clouds_q, frames_q, max_src_pts: int, hypotheses: int = 1, seed: str | None = None, max_corr: float = 1.0,
+                   min_fitness: float = 0.5, max_rmse: float = 0.5, max_iter: int = 30, tol_rmse: float = 1e-6, tol_fitness: float = 1e-6,
+                   min_inliers: int = 3, out=None, search: str | None = None):
+        """matcher.verify_dev with this map as the DB side (pr_map_verify_dev): matcher.align(idx), then seed -> ICP -> choice against the
+        map's rows idx - stream-ordered, capturable, the keywords and the result of matcher.verify_dev.  A row the map does not hold yet
+        (or holds as a dropped cloud) comes back ICP_NO_PAIR / not accepted.  The matcher must run on the map's context."""
+        import torch
+        from .eval import _p
+        if matcher.ctx is not self.ctx:
+            raise ValueError("KeyframeMap.verify_dev: the matcher and the map must share one context (one stream)")
+        seed, var, idx = matcher._verify_variants(idx, hypotheses, seed, 0)
+        H = int(hypotheses)
+        xq, oq = clouds_q
+        ts = (xq, oq, frames_q, idx)
+        if any((not x.is_cuda) or x.dtype != w or not x.is_contiguous() for x, w in zip(ts, (torch.float64, torch.int64, torch.float64, torch.int32))):
+            raise ValueError("KeyframeMap.verify_dev: expected contiguous CUDA tensors xyz f64, offs i64, frames f64, idx i32")
+        m, k = idx.shape
+        if frames_q.shape != (m, 16):
+            raise ValueError("KeyframeMap.verify_dev: frames_q must be [m, 16]")
+        var, stride = _variant_view(var, m, k, H)
+        dev = idx.device
+        out = _verify_out(out, m, k, dev, "KeyframeMap.verify_dev")
+        matcher._enter()
+        with icp_search(self.ctx, search):
+            self.ctx.check(self.lib.pr_map_verify_dev(self.h, _pose_type(seed), _p(xq), _p(oq), oq.numel() - 1, _p(frames_q), m, k, _p(idx), _p(var),
+                                                      stride, H, int(max_src_pts), int(max_iter), float(max_corr), float(tol_rmse),
+                                                      float(tol_fitness), int(min_inliers), float(min_fitness), float(max_rmse), _p(out[0]),
+                                                      _p(out[1]), _p(out[2]), _p(out[3])))
+        matcher._leave()
+        return out
+
+    def reset(self):
+        self.ctx.check(self.lib.pr_map_reset(self.h))
+
+    def count(self):
+        """(keyframes, stored points, flags); synchronises (pr_map_count)."""
+        k, f, n = C.c_int32(), C.c_int32(), C.c_int64()
+        self.ctx.check(self.lib.pr_map_count(self.h, C.byref(k), C.byref(n), C.byref(f)))
+        return int(k.value), int(n.value), int(f.value)
+
+    def close(self):
+        if getattr(self, "h", None) and getattr(self.ctx, "h", None):
+            self.lib.pr_map_destroy(self.h)
         self.h = None
 
     def __del__(self):

@@ -432,4 +432,22 @@ void launch_window_reset(hipStream_t st, const WinView& v);
 void launch_window_push(hipStream_t st, const WinView& v, const double* pose, const double* xyz_new, const float* inten_new,
                         const int* n_new_dev, int max_new, double* out_xyz, float* out_inten, int64_t* out_offs, double* out_frame, int* info);
 
+// map.hip — the resident keyframe map.  MapView: the caller's seven buffers, the create capacities and the plan scratch of
+// a pr_map (map.cpp).  plan [MAP_PLAN_HEAD + 3 max_append + 1] int64: the head words below, then cum [max_append + 1] (the clouds' first
+// points counted from the call's first point), dst [max_append] (first point in the map's xyz; -1: no points stored) and end [max_append]
+// (the map's offs behind the cloud's row).
+constexpr int MAP_OVERFLOW = 1;              // = PR_MAP_OVERFLOW
+constexpr int MAP_DROPPED = 2;               // = PR_MAP_DROPPED
+constexpr int MAP_PLAN_HEAD = 6;             // plan[0] rows appended, [1] first row | -1, [2] points the copy covers, [3] flags of this call,
+                                             // [4] keyframes before the call, [5] 0: the call was switched off by d_emitted
+struct MapView {
+  double* xyz; float* inten; int64_t* offs; double* frames; double* poses; int* ids; int* state;
+  int kcap, max_cloud, max_append;
+  int64_t pcap;
+  int64_t* plan;
+};
+inline size_t map_plan_words(int max_append) { return (size_t)MAP_PLAN_HEAD + 3 * (size_t)max_append + 1; }
+void launch_map_append(hipStream_t st, const MapView& v, const double* xyz, const float* inten, const int64_t* offs, const double* frames,
+                       const double* poses, const int* ids, const int* emitted, int N, int64_t max_points, int* info);
+
 }  // namespace pr

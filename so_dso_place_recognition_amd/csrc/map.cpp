@@ -1,0 +1,218 @@
+// map.cpp — host side of the resident keyframe map (map.hip): the opaque pr_map over the caller's seven buffers with its
+// plan scratch, the argument checks, the stream-ordered entry points, the host form of an append and pr_map_verify_dev = pr_verify_pairs_dev
+// over the map's arrays.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdarg>
+#include <cstdio>
+#include <cstring>
+#include <new>
+
+#include "../../include/place_recognition.h"
+#include "kernels.hpp"
+
+static_assert(pr::MAP_OVERFLOW == PR_MAP_OVERFLOW && pr::MAP_DROPPED == PR_MAP_DROPPED, "flag bits");
+
+struct pr_map {
+  pr_ctx* ctx = nullptr;
+  pr::MapView v;
+};
+
+namespace {
+
+int fail(pr_ctx* ctx, int code, const char* fmt, ...) __attribute__((format(printf, 3, 4)));
+int fail(pr_ctx* ctx, int code, const char* fmt, ...) {
+  char b[512];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(b, sizeof b, fmt, ap);
+  va_end(ap);
+  pr::ctx_set_error(ctx, b);
+  return code;
+}
+
+#define MP_HIP(ctx, call)                                                                                         \
+  do {                                                                                                            \
+    hipError_t _e = (call);                                                                                       \
+    if (_e != hipSuccess)                                                                                         \
+      return fail(ctx, _e == hipErrorOutOfMemory ? PR_ENOMEM : PR_EHIP, "%s failed: %s", #call, hipGetErrorString(_e)); \
+  } while (0)
+
+// offs, frames and state to zero on the stream: what create and reset leave (the invariants of DESIGN.md 4.15)
+int clear(pr_map* m) {
+  const pr::MapView& v = m->v;
+  hipStream_t st = pr::ctx_stream(m->ctx);
+  MP_HIP(m->ctx, hipMemsetAsync(v.offs, 0, ((size_t)v.kcap + 1) * sizeof(int64_t), st));
+  MP_HIP(m->ctx, hipMemsetAsync(v.frames, 0, (size_t)v.kcap * 16 * sizeof(double), st));
+  MP_HIP(m->ctx, hipMemsetAsync(v.state, 0, 4 * sizeof(int32_t), st));
+  return PR_OK;
+}
+
+// device memory of the host form (pr_map_append), released when it leaves
+struct Staging {
+  void* p = nullptr;
+  ~Staging() { if (p) (void)hipFree(p); }
+};
+
+size_t up16(size_t n) { return (n + 15) & ~(size_t)15; }
+
+}  // namespace
+
+extern "C" {
+
+int pr_map_create(pr_ctx* ctx, const pr_map_buffers* buffers, int32_t keyframe_capacity, int64_t point_capacity, int32_t max_cloud_points,
+                  int32_t max_append, pr_map** out) {
+  // the value checks come first and need no device: with ctx == NULL their text goes to pr_last_error(NULL)
+  if (!out) return fail(ctx, PR_EINVAL, "pr_map_create: out is NULL");
+  *out = nullptr;
+  if (!buffers) return fail(ctx, PR_EINVAL, "pr_map_create: buffers is NULL");
+  if (!buffers->xyz || !buffers->inten || !buffers->offs || !buffers->frames || !buffers->poses || !buffers->ids || !buffers->state)
+    return fail(ctx, PR_EINVAL, "pr_map_create: a buffer is NULL (xyz, inten, offs, frames, poses, ids, state)");
+  if (keyframe_capacity <= 0 || point_capacity <= 0 || max_cloud_points <= 0 || max_append <= 0)
+    return fail(ctx, PR_EINVAL, "pr_map_create: capacities must be positive (keyframe_capacity=%d, point_capacity=%lld, max_cloud_points=%d, "
+                "max_append=%d)", keyframe_capacity, (long long)point_capacity, max_cloud_points, max_append);
+  if (max_cloud_points > point_capacity)
+    return fail(ctx, PR_EINVAL, "pr_map_create: max_cloud_points=%d exceeds point_capacity=%lld", max_cloud_points, (long long)point_capacity);
+  if ((int64_t)max_cloud_points * max_append >= ((int64_t)1 << 38))
+    return fail(ctx, PR_EINVAL, "pr_map_create: max_cloud_points x max_append = %lld must be below 2^38 (one lane per point of an append)",
+                (long long)max_cloud_points * max_append);
+  if (!ctx) return fail(nullptr, PR_EINVAL, "pr_map_create: ctx is NULL");
+  MP_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
+  pr_map* m = new (std::nothrow) pr_map;
+  if (!m) return fail(ctx, PR_ENOMEM, "out of host memory");
+  m->ctx = ctx;
+  pr::MapView& v = m->v;
+  memset(&v, 0, sizeof v);
+  v.xyz = buffers->xyz; v.inten = buffers->inten; v.offs = buffers->offs; v.frames = buffers->frames; v.poses = buffers->poses;
+  v.ids = buffers->ids; v.state = buffers->state;
+  v.kcap = keyframe_capacity; v.pcap = point_capacity; v.max_cloud = max_cloud_points; v.max_append = max_append;
+  void* plan = nullptr;
+  hipError_t e = hipMalloc(&plan, pr::map_plan_words(max_append) * sizeof(int64_t));
+  if (e != hipSuccess) {
+    delete m;
+    return fail(ctx, e == hipErrorOutOfMemory ? PR_ENOMEM : PR_EHIP, "pr_map_create: plan scratch: %s", hipGetErrorString(e));
+  }
+  v.plan = static_cast<int64_t*>(plan);
+  int rc = clear(m);
+  if (rc == PR_OK && hipStreamSynchronize(pr::ctx_stream(ctx)) != hipSuccess) rc = fail(ctx, PR_EHIP, "pr_map_create: synchronise failed");
+  if (rc != PR_OK) { (void)hipFree(plan); delete m; return rc; }
+  *out = m;
+  return PR_OK;
+}
+
+void pr_map_destroy(pr_map* m) {
+  if (!m) return;
+  (void)hipSetDevice(pr::ctx_device(m->ctx));
+  (void)hipStreamSynchronize(pr::ctx_stream(m->ctx));
+  (void)hipFree(m->v.plan);             // the seven buffers are the caller's
+  delete m;
+}
+
+int pr_map_reset(pr_map* m) {
+  if (!m) return fail(nullptr, PR_EINVAL, "pr_map_reset: map is NULL");
+  MP_HIP(m->ctx, hipSetDevice(pr::ctx_device(m->ctx)));
+  return clear(m);
+}
+
+int pr_map_count(pr_map* m, int32_t* keyframes, int64_t* points, int32_t* flags) {
+  if (!m) return fail(nullptr, PR_EINVAL, "pr_map_count: map is NULL");
+  if (!keyframes || !points || !flags) return fail(m->ctx, PR_EINVAL, "pr_map_count: a required pointer is NULL");
+  MP_HIP(m->ctx, hipSetDevice(pr::ctx_device(m->ctx)));
+  hipStream_t st = pr::ctx_stream(m->ctx);
+  int32_t s[4];
+  MP_HIP(m->ctx, hipMemcpyAsync(s, m->v.state, sizeof s, hipMemcpyDeviceToHost, st));
+  MP_HIP(m->ctx, hipStreamSynchronize(st));
+  const int32_t k = std::min(std::max(s[0], 0), m->v.kcap);
+  MP_HIP(m->ctx, hipMemcpyAsync(points, m->v.offs + k, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  MP_HIP(m->ctx, hipStreamSynchronize(st));
+  *keyframes = s[0];
+  *flags = s[1];
+  return PR_OK;
+}
+
+int pr_map_append_dev(pr_map* m, const double* d_xyz, const float* d_inten, const int64_t* d_offs, const double* d_frames, const double* d_poses,
+                      const int32_t* d_ids, const int32_t* d_emitted, int32_t N, int64_t max_points, int32_t* d_info) {
+  // (the checks that need no handle come first: with m == NULL their text goes to pr_last_error(NULL))
+  if (N < 0) return fail(m ? m->ctx : nullptr, PR_EINVAL, "pr_map_append_dev: N=%d is negative", N);
+  if (max_points < 0) return fail(m ? m->ctx : nullptr, PR_EINVAL, "pr_map_append_dev: max_points=%lld is negative", (long long)max_points);
+  if (!m) return fail(nullptr, PR_EINVAL, "pr_map_append_dev: map is NULL");
+  if (N > m->v.max_append) return fail(m->ctx, PR_EINVAL, "pr_map_append_dev: N=%d outside 0 .. max_append=%d", N, m->v.max_append);
+  if (!d_info || (N > 0 && (!d_offs || !d_frames)) || (N > 0 && max_points > 0 && (!d_xyz || !d_inten)))
+    return fail(m->ctx, PR_EINVAL, "pr_map_append_dev: a required pointer is NULL");
+  max_points = std::min<int64_t>(max_points, (int64_t)m->v.max_cloud * N);
+  MP_HIP(m->ctx, hipSetDevice(pr::ctx_device(m->ctx)));
+  pr::launch_map_append(pr::ctx_stream(m->ctx), m->v, d_xyz, d_inten, d_offs, d_frames, d_poses, d_ids, d_emitted, N, max_points, d_info);
+  MP_HIP(m->ctx, hipGetLastError());
+  return PR_OK;
+}
+
+int pr_map_append(pr_map* m, const double* xyz, const float* inten, const int64_t* offs, const double* frames, const double* poses,
+                  const int32_t* ids, const int32_t* emitted, int32_t N, int32_t* info) {
+  if (N < 0) return fail(m ? m->ctx : nullptr, PR_EINVAL, "pr_map_append: N=%d is negative", N);
+  if (!m) return fail(nullptr, PR_EINVAL, "pr_map_append: map is NULL");
+  pr_ctx* ctx = m->ctx;
+  if (N > m->v.max_append) return fail(ctx, PR_EINVAL, "pr_map_append: N=%d outside 0 .. max_append=%d", N, m->v.max_append);
+  if (!info || (N > 0 && (!offs || !frames))) return fail(ctx, PR_EINVAL, "pr_map_append: a required pointer is NULL");
+  int64_t lo = 0, hi = 0;                          // the points any of the N clouds names
+  for (int32_t i = 0; i <= N && N > 0; i++) {
+    if (offs[i] < 0) return fail(ctx, PR_EINVAL, "pr_map_append: offs[%d]=%lld is negative", i, (long long)offs[i]);
+    lo = i ? std::min(lo, offs[i]) : offs[i];
+    hi = i ? std::max(hi, offs[i]) : offs[i];
+  }
+  const int64_t npts = hi - lo;
+  if (npts > 0 && (!xyz || !inten)) return fail(ctx, PR_EINVAL, "pr_map_append: a required pointer is NULL");
+  MP_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
+  hipStream_t st = pr::ctx_stream(ctx);
+  const size_t n = (size_t)N, np = (size_t)npts;
+  const size_t o_xyz = 0, o_int = o_xyz + up16(np * 24), o_offs = o_int + up16(np * 4), o_fr = o_offs + up16((n + 1) * 8),
+               o_pose = o_fr + up16(n * 128), o_ids = o_pose + up16(n * 96), o_emit = o_ids + up16(n * 4), o_info = o_emit + 16,
+               total = o_info + 16;
+  Staging s;
+  MP_HIP(ctx, hipMalloc(&s.p, total));
+  char* b = static_cast<char*>(s.p);
+  if (np) {
+    MP_HIP(ctx, hipMemcpyAsync(b + o_xyz, xyz + 3 * lo, np * 24, hipMemcpyHostToDevice, st));
+    MP_HIP(ctx, hipMemcpyAsync(b + o_int, inten + lo, np * 4, hipMemcpyHostToDevice, st));
+  }
+  int64_t* rel = nullptr;                          // the offsets counted from the first uploaded point
+  if (N > 0) {
+    rel = new (std::nothrow) int64_t[n + 1];
+    if (!rel) return fail(ctx, PR_ENOMEM, "out of host memory");
+    for (size_t i = 0; i <= n; i++) rel[i] = offs[i] - lo;
+  }
+  hipError_t e = hipSuccess;
+  if (N > 0) {
+    e = hipMemcpyAsync(b + o_offs, rel, (n + 1) * 8, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(b + o_fr, frames, n * 128, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && poses) e = hipMemcpyAsync(b + o_pose, poses, n * 96, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && ids) e = hipMemcpyAsync(b + o_ids, ids, n * 4, hipMemcpyHostToDevice, st);
+  }
+  if (e == hipSuccess && emitted) e = hipMemcpyAsync(b + o_emit, emitted, 4, hipMemcpyHostToDevice, st);
+  int rc = PR_OK;
+  if (e == hipSuccess)
+    rc = pr_map_append_dev(m, reinterpret_cast<double*>(b + o_xyz), reinterpret_cast<float*>(b + o_int), reinterpret_cast<int64_t*>(b + o_offs),
+                           reinterpret_cast<double*>(b + o_fr), poses ? reinterpret_cast<double*>(b + o_pose) : nullptr,
+                           ids ? reinterpret_cast<int32_t*>(b + o_ids) : nullptr, emitted ? reinterpret_cast<int32_t*>(b + o_emit) : nullptr, N,
+                           npts, reinterpret_cast<int32_t*>(b + o_info));
+  if (e == hipSuccess && rc == PR_OK) e = hipMemcpyAsync(info, b + o_info, 16, hipMemcpyDeviceToHost, st);
+  const hipError_t e2 = hipStreamSynchronize(st);   // rel and the staging are in flight until here
+  delete[] rel;
+  if (rc != PR_OK) return rc;
+  MP_HIP(ctx, e);
+  MP_HIP(ctx, e2);
+  return PR_OK;
+}
+
+int pr_map_verify_dev(pr_map* m, int type, const double* d_xyz_q, const int64_t* d_offs_q, int32_t Nq, const double* d_frames_q, int32_t mq,
+                      int32_t k, const int32_t* d_idx, const int32_t* d_variant, int32_t variant_stride, int32_t H, int32_t max_src_pts,
+                      int32_t max_iter, double max_corr, double tol_rmse, double tol_fitness, int32_t min_inliers, double min_fitness,
+                      double max_rmse, double* d_T, pr_icp_stats* d_stats, uint8_t* d_accepted, int32_t* d_hyp) {
+  if (!m) return fail(nullptr, PR_EINVAL, "pr_map_verify_dev: map is NULL");
+  const pr::MapView& v = m->v;
+  return pr_verify_pairs_dev(m->ctx, type, d_xyz_q, d_offs_q, Nq, v.xyz, v.offs, v.kcap, d_frames_q, v.frames, mq, v.kcap, 0, k, d_idx, d_variant,
+                             variant_stride, H, max_src_pts, v.max_cloud, max_iter, max_corr, tol_rmse, tol_fitness, min_inliers, min_fitness,
+                             max_rmse, d_T, d_stats, d_accepted, d_hyp);
+}
+
+}  // extern "C"

@@ -463,8 +463,27 @@ class _Base:
         keeps the better result; DELIGHT has one variant per pair.  A FusedMatcher chooses the seeding descriptor with seed = "sc" | "m2dp".
         Returns device tensors (T float64 [m, k, 3, 4], stats uint8 [m, k, 32], accepted bool [m, k], hyp int32 [m, k]: the kept
         hypothesis); out: an earlier call's tuple, written again.  search: None | "brute" | "grid", the ICP correspondence search of this
-        call (api.icp_search); the context's mode is what it was afterwards."""
+        call (api.icp_search); the context's mode is what it was afterwards.
+        clouds_db may be an api.KeyframeMap (with frames_db = None and max_dst_pts = None): the call is then KeyframeMap.verify_dev - the
+        map's clouds and frames at their fixed addresses, idx = rows of the map."""
         from . import api
+        if isinstance(clouds_db, api.KeyframeMap):
+            if frames_db is not None or max_dst_pts is not None or db_row0 != 0:
+                raise ValueError("verify_dev: a KeyframeMap brings its frames and bounds: frames_db=None, max_dst_pts=None, db_row0=0")
+            return clouds_db.verify_dev(self, idx, clouds_q, frames_q, max_src_pts, hypotheses=hypotheses, seed=seed, max_corr=max_corr,
+                                        min_fitness=min_fitness, max_rmse=max_rmse, max_iter=max_iter, tol_rmse=tol_rmse, tol_fitness=tol_fitness,
+                                        min_inliers=min_inliers, out=out, search=search)
+        seed, var, idx = self._verify_variants(idx, hypotheses, seed, db_row0)
+        self._enter()
+        res = api.verify_pairs_torch(seed, clouds_q, clouds_db, frames_q, frames_db, idx, var, max_src_pts, max_dst_pts, hypotheses, db_row0,
+                                     max_corr, min_fitness, max_rmse, max_iter, tol_rmse, tol_fitness, min_inliers, ctx=self.ctx, out=out,
+                                     search=search)
+        self._leave()
+        return res
+
+    def _verify_variants(self, idx: torch.Tensor, hypotheses: int, seed: str | None, db_row0: int):
+        """What verify_dev hands to the verify chain: (the seeding descriptor's name, align(idx)'s variants of that descriptor, idx as
+        contiguous int32)."""
         names = {_lib.TYPE_SC: "sc", _lib.TYPE_M2DP: "m2dp", _lib.TYPE_DELIGHT: "delight"}
         have = [names[d.type] for d in self.descs if d.type in names]
         if seed is None and len(have) == 1:
@@ -476,13 +495,7 @@ class _Base:
         var, _ = self.align(idx, db_row0)
         if var.shape[-1] == 4 and seed == "m2dp":
             var = var[..., 2:]
-        idx = idx.to(torch.int32).contiguous()
-        self._enter()
-        res = api.verify_pairs_torch(seed, clouds_q, clouds_db, frames_q, frames_db, idx, var, max_src_pts, max_dst_pts, hypotheses, db_row0,
-                                     max_corr, min_fitness, max_rmse, max_iter, tol_rmse, tol_fitness, min_inliers, ctx=self.ctx, out=out,
-                                     search=search)
-        self._leave()
-        return res
+        return seed, var, idx.to(torch.int32).contiguous()
 
     def flagged_count(self) -> int:
         """Queries the last match(..., exact_order=False) of ONE rank left flagged by the order / containment checks (the ones the default
