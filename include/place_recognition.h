@@ -566,7 +566,9 @@ int pr_delight_generate_dev(pr_ctx* ctx, const double* xyz, const float* inten, 
  * pr_cloud_frames_dev writes them (asynchronously, on the context's streams; with inten != NULL the averages too), and
  * pr_pts_preprocess_gpu leaves them - averages included - beside the clouds it emits (pr_clouds_dev_frames).
  * frames_have_ave != 0: slots 14 of the frames hold the averages and the call is the binning pass alone; 0: the call computes them
- * (a chain of dependent float adds per cloud, beside the binning pass).  Same results, bit for bit, as the calls above. */
+ * (a chain of dependent float adds per cloud, beside the binning pass).  Same results, bit for bit, as the calls above.
+ * pr_sc_generate_frames_dev with frames_have_ave != 0 is one launch without any allocation and may be captured in a hipGraph (it
+ * synchronises the context's stream before it returns, except while that stream is capturing). */
 int pr_cloud_frames_dev(pr_ctx* ctx, const double* xyz, const float* inten /* may be NULL */, const int64_t* offs, int32_t N, double* frames);
 int pr_sc_generate_frames_dev(pr_ctx* ctx, const double* xyz, const float* inten, const int64_t* offs, int32_t N, double max_rho,
                               const double* frames, int frames_have_ave, double* out);
@@ -900,6 +902,51 @@ int pr_map_verify_dev(pr_map* m, int type, const double* d_xyz_q, const int64_t*
                       int32_t k, const int32_t* d_idx, const int32_t* d_variant, int32_t variant_stride, int32_t H, int32_t max_src_pts,
                       int32_t max_iter, double max_corr, double tol_rmse, double tol_fitness, int32_t min_inliers, double min_fitness,
                       double max_rmse, double* d_T, pr_icp_stats* d_stats, uint8_t* d_accepted, int32_t* d_hyp);
+
+/* ---- the online signature database: raw SC or M2DP rows with a device-side count, matched exactly in fp64 (online.hip) --
+ * A pr_sigset takes its row count from the host, so a captured match is frozen at the count it was captured with.  A pr_online is the
+ * sibling of pr_map for signatures: the RAW rows of the keyframes seen so far over CALLER-OWNED device buffers (pr_online_buffers):
+ * sig [capacity * rows_per_sig][sig_len] f64 (1 x 2400 for PR_TYPE_SC, 4 x 384 for PR_TYPE_M2DP, the layouts pr_align_pairs_dev takes)
+ * and state [4] i32 = {count, flags, 0, 0}.  The addresses never change and every launch's geometry depends on capacity and max_k
+ * only, so ONE captured match + append serves every keyframe of a drive, whatever the count, and pr_align_pairs_dev reads the rows in
+ * place (n_local = capacity, db_row0 = 0: every idx a match returns is below the count).  It is for drives (thousands of rows: the
+ * direct pair formulation walks all 120 variants of every entry), not for a 100k database, and it is exact by construction: no order flags, no
+ * containment check.
+ *
+ *   pr_online_create      binds the buffers (they must outlive the handle), allocates ALL scratch (the distance rows [2][capacity], the
+ *                         per-workgroup partial sums, the statistics, the staging of the host form) and zeroes state.  No later call
+ *                         allocates.  The handle is bound to ctx and its stream and must be destroyed before ctx; pr_online_destroy
+ *                         frees the handle and its scratch, never the buffers.  1 <= max_k <= 128.
+ *   pr_online_match_dev   stream-ordered, no host decision, no read-back: three launches (rows, stats, select).  d_sig: the query's
+ *                         signature, DEVICE [rows_per_sig][sig_len] f64; d_emitted DEVICE [>= 1] or NULL; d_idx [k] i32, d_score [k]
+ *                         f64; d_rows DEVICE [2][capacity] f64 or NULL.
+ *     The rule, decided on the device.  d_emitted != NULL and d_emitted[0] == 0: d_idx[0 .. k) = -1, d_score = NaN, nothing else
+ *     happens.  Otherwise, with n = state[0]: the two channel distances of the query to every row j < n in the reference's own pair
+ *     formulation in fp64 (processSC.m:15-33 / processM2DP.m:12-22: the device functions the re-evaluation and pr_align_pairs_dev use,
+ *     so a duplicated row gives identical bits); the row statistics of normalize(.,2) (NaN left out, N - 1; the mean from ordered partial
+ *     sums, the deviation by a second pass about it: scores within 1e-9 of the fp64 restatement); fused_j = p_weight z_p + z_i;
+ *     +Inf where |n - j| < mask_width - the query is row n, the row it will get; the k smallest by (score, index), NaN never selected,
+ *     missing slots -1 / NaN.  With n < 2 there are no statistics and every slot is -1 / NaN, masked or not.  d_rows, when given,
+ *     receives the distances: the first n of each half.  1 <= k <= max_k.
+ *   pr_online_append_dev  stream-ordered, one launch.  d_emitted off: info = {0, -1, count, flags}.  Otherwise the signature goes to row
+ *                         count and count + 1 is committed; at count == capacity nothing is stored and PR_ONLINE_OVERFLOW is set (in
+ *                         state[1] and every later info) until pr_online_reset.  d_info DEVICE [4] = {appended, row or -1, count after,
+ *                         flags}.  Nothing is written outside the two buffers' stated extents.
+ *   pr_online_append      the host form: sig host [rows_per_sig][sig_len], info host [4]; uploads, runs the device path, synchronises.
+ *   pr_online_reset       zeroes state (stream-ordered).    pr_online_count   synchronising read of count and flags (diagnostics).
+ * PR_EINVAL (text: pr_last_error) before any device is touched for a NULL handle, buffer or required pointer, a type other than
+ * PR_TYPE_SC | PR_TYPE_M2DP, capacity outside 1 .. PR_MAX_SIGS, max_k or k out of range, a non-finite p_weight, mask_width < 0. */
+typedef struct pr_online pr_online;
+typedef struct pr_online_buffers { double* sig; int32_t* state; } pr_online_buffers;
+#define PR_ONLINE_OVERFLOW 1
+int pr_online_create(pr_ctx* ctx, int type, const pr_online_buffers* buffers, int32_t capacity, int32_t max_k, pr_online** out);
+void pr_online_destroy(pr_online* o);
+int pr_online_reset(pr_online* o);
+int pr_online_count(pr_online* o, int32_t* count, int32_t* flags);
+int pr_online_match_dev(pr_online* o, const double* d_sig, const int32_t* d_emitted, int32_t mask_width, double p_weight, int32_t k,
+                        int32_t* d_idx, double* d_score, double* d_rows);
+int pr_online_append_dev(pr_online* o, const double* d_sig, const int32_t* d_emitted, int32_t* d_info);
+int pr_online_append(pr_online* o, const double* sig, int32_t* info);
 const char* pr_host_last_error(void);
 
 #ifdef __cplusplus

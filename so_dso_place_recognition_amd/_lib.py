@@ -24,6 +24,8 @@ ICP_SEARCH_BRUTE, ICP_SEARCH_GRID = 0, 1            # pr_set_icp_search's mode
 POSE_SC, POSE_M2DP, POSE_DELIGHT = 0, 1, 2          # pr_relative_pose*'s type
 WINDOW_OVERFLOW, WINDOW_ORDER_GLOBAL = 1, 2         # info[3] of a pr_window push
 MAP_OVERFLOW, MAP_DROPPED = 1, 2                    # info[3] of a pr_map append
+ONLINE_OVERFLOW = 1                                 # info[3] of a pr_online append
+ONLINE_NB = 512                                     # most workgroups of a pr_online match's rows kernel (online.hpp)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PR_AMD_LIB") or os.path.join(_HERE, "libpr_amd.so")   # PR_AMD_LIB: experiment builds only
@@ -221,6 +223,13 @@ SYMBOLS = {
     "pr_map_append": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
     "pr_map_verify_dev": (C.c_int, [_vp, C.c_int, _vp, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _dbl, _dbl, _dbl, _i32, _dbl,
                                     _dbl, _vp, _vp, _vp, _vp]),
+    "pr_online_create": (C.c_int, [_vp, C.c_int, _vp, _i32, _i32, C.POINTER(_vp)]),
+    "pr_online_destroy": (None, [_vp]),
+    "pr_online_reset": (C.c_int, [_vp]),
+    "pr_online_count": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32)]),
+    "pr_online_match_dev": (C.c_int, [_vp, _vp, _vp, _i32, _dbl, _i32, _vp, _vp, _vp]),
+    "pr_online_append_dev": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "pr_online_append": (C.c_int, [_vp, _vp, _vp]),
     "pr_host_last_error": (C.c_char_p, []),
 }
 
@@ -229,6 +238,11 @@ SYMBOLS = {
 class MapBuffers(C.Structure):
     """pr_map_buffers: the seven caller-owned device buffers of a pr_map."""
     _fields_ = [(n, _vp) for n in ("xyz", "inten", "offs", "frames", "poses", "ids", "state")]
+
+
+class OnlineBuffers(C.Structure):
+    """pr_online_buffers: the two caller-owned device buffers of a pr_online."""
+    _fields_ = [(n, _vp) for n in ("sig", "state")]
 
 
 _lib = None

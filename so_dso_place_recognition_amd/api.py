@@ -1355,6 +1355,33 @@ class KeyframeMap:
         matcher._leave()
         return out
 
+    def verify_variants(self, type_, idx, variant, clouds_q, frames_q, max_src_pts: int, hypotheses: int = 1, max_corr: float = 1.0,
+                        min_fitness: float = 0.5, max_rmse: float = 0.5, max_iter: int = 30, tol_rmse: float = 1e-6, tol_fitness: float = 1e-6,
+                        min_inliers: int = 3, out=None, search: str | None = None):
+        """verify_dev without a matcher (pr_map_verify_dev): the pairs' variants are the caller's - OnlineDatabase.align's, or any int32
+        tensor [m, k] / [m, k, >= hypotheses] as relative_pose_torch takes them - and type_ = 'sc' | 'm2dp' | 'delight' names the seed.
+        The other arguments, the result and the capturability are verify_dev's.  Enqueued on the map's context's stream."""
+        import torch
+        from .eval import _p
+        H = int(hypotheses)
+        if H not in (1, 2) or (H == 2 and type_ == "delight"):
+            raise ValueError("KeyframeMap.verify_variants: hypotheses is 1 or 2, and 1 for DELIGHT (one variant per pair)")
+        xq, oq = clouds_q
+        ts = (xq, oq, frames_q, idx)
+        if any((not x.is_cuda) or x.dtype != w or not x.is_contiguous() for x, w in zip(ts, (torch.float64, torch.int64, torch.float64, torch.int32))):
+            raise ValueError("KeyframeMap.verify_variants: expected contiguous CUDA tensors xyz f64, offs i64, frames f64, idx i32")
+        m, k = idx.shape
+        if frames_q.shape != (m, 16):
+            raise ValueError("KeyframeMap.verify_variants: frames_q must be [m, 16]")
+        var, stride = _variant_view(variant, m, k, H)
+        out = _verify_out(out, m, k, idx.device, "KeyframeMap.verify_variants")
+        with icp_search(self.ctx, search):
+            self.ctx.check(self.lib.pr_map_verify_dev(self.h, _pose_type(type_), _p(xq), _p(oq), oq.numel() - 1, _p(frames_q), m, k, _p(idx), _p(var),
+                                                      stride, H, int(max_src_pts), int(max_iter), float(max_corr), float(tol_rmse),
+                                                      float(tol_fitness), int(min_inliers), float(min_fitness), float(max_rmse), _p(out[0]),
+                                                      _p(out[1]), _p(out[2]), _p(out[3])))
+        return out
+
     def reset(self):
         self.ctx.check(self.lib.pr_map_reset(self.h))
 
@@ -1367,6 +1394,149 @@ class KeyframeMap:
     def close(self):
         if getattr(self, "h", None) and getattr(self.ctx, "h", None):
             self.lib.pr_map_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class OnlineDatabase:
+    """pr_online: the raw SC or M2DP rows of the keyframes seen so far with a DEVICE-side count, matched exactly in fp64 and grown on the
+    stream - the sibling of KeyframeMap for signatures.  type_ 'sc' | 'm2dp'; the two buffers are zeroed torch tensors
+    on the context's device (or the caller's: buffers = dict(sig=, state=)): .sig [capacity * rows_per_sig, sig_len] f64 (1 x 2400 /
+    4 x 384) and .state [4] i32 = count, flags, 0, 0.  Every call's launch geometry depends on capacity and max_k only and the count is
+    read on the device, so ONE captured step_torch serves every keyframe of a drive.  At count == capacity an append stores nothing and
+    sets ONLINE_OVERFLOW in info[3] until reset().  There is no error: nothing is read back.  All *_torch calls are enqueued on the
+    context's stream (the caller orders it against the producers of the inputs, e.g. a Context made on torch's current stream)."""
+
+    NAMES = ("sig", "state")
+
+    def __init__(self, ctx: Context | None, type_: str, capacity: int, max_k: int = 8, buffers: dict | None = None):
+        import torch
+        if type_ not in ("sc", "m2dp"):
+            raise ValueError("OnlineDatabase: type_ is 'sc' or 'm2dp'")
+        self.ctx = ctx or default_context()
+        self.lib = self.ctx.lib
+        self.type_name, self.type = type_, {"sc": _lib.TYPE_SC, "m2dp": _lib.TYPE_M2DP}[type_]
+        self.rows_per_sig, self.sig_len = (1, 2400) if type_ == "sc" else (4, 384)
+        self.capacity, self.max_k = int(capacity), int(max_k)
+        self.h = None
+        cap = max(self.capacity, 0)
+        dev = torch.device("cuda", self.ctx.device)
+        shapes = dict(sig=((cap * self.rows_per_sig, self.sig_len), torch.float64), state=((4,), torch.int32))
+        if buffers is None:
+            buffers = {n: torch.zeros(s, dtype=dt, device=dev) for n, (s, dt) in shapes.items()}
+        for n, (s, dt) in shapes.items():
+            t = buffers[n]
+            if (not t.is_cuda) or t.dtype != dt or not t.is_contiguous() or tuple(t.shape) != tuple(s):
+                raise ValueError(f"OnlineDatabase: buffer {n} must be a contiguous CUDA tensor {dt} {list(s)}")
+            setattr(self, n, t)
+        torch.cuda.synchronize(dev)                       # torch's fills (its stream) before the library's stream writes the buffers
+        rec = _lib.OnlineBuffers(*(C.c_void_p(getattr(self, n).data_ptr()) for n in self.NAMES))
+        h = C.c_void_p()
+        self.ctx.check(self.lib.pr_online_create(self.ctx.h, self.type, C.byref(rec), self.capacity, self.max_k, C.byref(h)))
+        self.h = h
+
+    def _sig(self, sig, who):
+        import torch
+        if (not sig.is_cuda) or sig.dtype != torch.float64 or not sig.is_contiguous() or sig.numel() != self.rows_per_sig * self.sig_len:
+            raise ValueError(f"{who}: sig must be a contiguous CUDA tensor f64 [{self.rows_per_sig}, {self.sig_len}]")
+
+    @staticmethod
+    def _opt(t, dtype, numel, who, what):
+        if t is not None and ((not t.is_cuda) or t.dtype != dtype or not t.is_contiguous() or t.numel() < numel):
+            raise ValueError(f"{who}: {what}")
+
+    def match_torch(self, sig, mask_width: int = 0, p_weight: float = 2.0, k: int = 1, emitted=None, out=None, rows=None):
+        """Device form (pr_online_match_dev): the query's signature sig f64 [rows_per_sig, sig_len] against the rows the database holds
+        NOW (the count is read on the device); the query counts as row `count` for the mask.  emitted i32 [>= 1] | None: emitted[0] == 0
+        switches the call off on the device (idx = -1, score = NaN).  Returns (idx int32 [1, k], score float64 [1, k]) - the shape
+        verify takes; out: an earlier call's pair, written again.  rows f64 [2, capacity] | None receives the channel distances (the first
+        `count` of each half).  Nothing synchronises, nothing is allocated when out= is given."""
+        import torch
+        who = "OnlineDatabase.match_torch"
+        self._sig(sig, who)
+        k = int(k)
+        self._opt(emitted, torch.int32, 1, who, "emitted must be a CUDA tensor i32 [>= 1]")
+        if rows is not None and ((not rows.is_cuda) or rows.dtype != torch.float64 or not rows.is_contiguous() or tuple(rows.shape) != (2, self.capacity)):
+            raise ValueError(f"{who}: rows must be a contiguous CUDA tensor f64 [2, capacity]")
+        if out is None:
+            out = (torch.empty((1, max(k, 0)), dtype=torch.int32, device=sig.device), torch.empty((1, max(k, 0)), dtype=torch.float64, device=sig.device))
+        elif tuple(out[0].shape) != (1, k) or tuple(out[1].shape) != (1, k) or out[0].dtype != torch.int32 or out[1].dtype != torch.float64 \
+                or not (out[0].is_cuda and out[1].is_cuda and out[0].is_contiguous() and out[1].is_contiguous()):
+            raise ValueError(f"{who}: out must be (idx i32 [1, k], score f64 [1, k]) CUDA tensors")
+        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        self.ctx.check(self.lib.pr_online_match_dev(self.h, p(sig), p(emitted), int(mask_width), float(p_weight), k, p(out[0]), p(out[1]), p(rows)))
+        return out
+
+    def append_torch(self, sig, emitted=None, info=None):
+        """Device form (pr_online_append_dev): sig becomes row `count` (emitted as in match_torch).  Returns info (device i32 [4]) =
+        appended, row | -1, count after, flags."""
+        import torch
+        who = "OnlineDatabase.append_torch"
+        self._sig(sig, who)
+        self._opt(emitted, torch.int32, 1, who, "emitted must be a CUDA tensor i32 [>= 1]")
+        if info is None:
+            info = torch.empty(4, dtype=torch.int32, device=sig.device)
+        elif (not info.is_cuda) or info.dtype != torch.int32 or not info.is_contiguous() or info.numel() != 4:
+            raise ValueError(f"{who}: info must be a CUDA tensor i32 [4]")
+        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        self.ctx.check(self.lib.pr_online_append_dev(self.h, p(sig), p(emitted), p(info)))
+        return info
+
+    def step_torch(self, sig, mask_width: int = 0, p_weight: float = 2.0, k: int = 1, emitted=None, out=None, rows=None, info=None):
+        """One keyframe: match_torch against the rows seen so far, then append_torch of the same signature.  Returns (idx, score, info)."""
+        idx, score = self.match_torch(sig, mask_width, p_weight, k, emitted=emitted, out=out, rows=rows)
+        return idx, score, self.append_torch(sig, emitted=emitted, info=info)
+
+    def align(self, idx, sig, out=None):
+        """The best-aligning variant of the pairs (query sig, row idx[0, j]) from the raw rows in place (pr_align_pairs_dev with n_local =
+        capacity): (variant int32 [1, k, 2], dist float64 [1, k, 2]) per channel, as Matcher.align returns them - the variants are what
+        KeyframeMap.verify_variants takes.  idx int32 [1, k] as match_torch returns it (-1: no pair).  out: an earlier call's pair."""
+        import torch
+        who = "OnlineDatabase.align"
+        self._sig(sig, who)
+        if (not idx.is_cuda) or idx.dtype != torch.int32 or not idx.is_contiguous() or idx.dim() != 2 or idx.shape[0] != 1:
+            raise ValueError(f"{who}: idx must be a contiguous CUDA tensor i32 [1, k]")
+        k = idx.shape[1]
+        ch = slice(0, 2) if self.type == _lib.TYPE_SC else slice(2, 4)
+        if out is None:
+            var = torch.empty((1, k, 4), dtype=torch.int32, device=idx.device)
+            dist = torch.empty((1, k, 4), dtype=torch.float64, device=idx.device)
+        else:
+            var, dist = out[0]._base, out[1]._base
+            if var is None or dist is None or tuple(var.shape) != (1, k, 4) or tuple(dist.shape) != (1, k, 4):
+                raise ValueError(f"{who}: out must be the pair an earlier align() of the same k returned")
+        p = lambda t: C.c_void_p(t.data_ptr())
+        sc = (p(sig), p(self.sig), _lib.F64) if self.type == _lib.TYPE_SC else (None, None, 0)
+        m2 = (p(sig), p(self.sig), _lib.F64) if self.type == _lib.TYPE_M2DP else (None, None, 0)
+        self.ctx.check(self.lib.pr_align_pairs_dev(self.ctx.h, *sc, *m2, 1, self.capacity, 0, k, p(idx), p(var), p(dist)))
+        return var[..., ch], dist[..., ch]
+
+    def append(self, sig):
+        """Host form (pr_online_append; synchronises): sig a numpy array of rows_per_sig x sig_len numbers.  Returns info int32 [4]."""
+        s = np.ascontiguousarray(sig, np.float64).reshape(-1)
+        if len(s) != self.rows_per_sig * self.sig_len:
+            raise ValueError(f"OnlineDatabase.append: sig must hold {self.rows_per_sig} x {self.sig_len} numbers")
+        info = np.empty(4, np.int32)
+        self.ctx.check(self.lib.pr_online_append(self.h, _ptr(s), _ptr(info)))
+        return info
+
+    def reset(self):
+        self.ctx.check(self.lib.pr_online_reset(self.h))
+
+    def count(self):
+        """(count, flags); synchronises (pr_online_count)."""
+        n, f = C.c_int32(), C.c_int32()
+        self.ctx.check(self.lib.pr_online_count(self.h, C.byref(n), C.byref(f)))
+        return int(n.value), int(f.value)
+
+    def close(self):
+        if getattr(self, "h", None) and getattr(self.ctx, "h", None):
+            self.lib.pr_online_destroy(self.h)
         self.h = None
 
     def __del__(self):

@@ -1734,6 +1734,10 @@ int pr_sc_generate_frames_dev(pr_ctx* ctx, const double* xyz, const float* inten
   if (frames_have_ave) {        // everything but the binning pass came with the frames
     pr::launch_sc_bin(ctx->stream, xyz, inten, offs, N, max_rho, frames, nullptr, out, 1);
     PR_HIP(ctx, hipGetLastError());
+    // One launch and nothing allocated: the form an online step captures in a graph.  A synchronise is not permitted
+    // while the stream is capturing - the graph's own order stands in for it; outside a capture the call synchronises as it always did.
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(ctx->stream, &cap) == hipSuccess && cap == hipStreamCaptureStatusActive) return PR_OK;
     PR_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return PR_OK;
   }
