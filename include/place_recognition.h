@@ -947,6 +947,75 @@ int pr_online_match_dev(pr_online* o, const double* d_sig, const int32_t* d_emit
                         int32_t* d_idx, double* d_score, double* d_rows);
 int pr_online_append_dev(pr_online* o, const double* d_sig, const int32_t* d_emitted, int32_t* d_info);
 int pr_online_append(pr_online* o, const double* sig, int32_t* info);
+
+/* ---- the loop-closure log and the pose-graph relaxation of the map's poses (posegraph.hip) ------------------------------
+ * A verify leaves (T, stats, accepted, hyp) in buffers the next keyframe overwrites.  A pr_posegraph keeps the accepted pairs of a drive
+ * over CALLER-OWNED device buffers (pr_posegraph_buffers): edge_ij [edge_capacity][2] i32 (DB row i, query row j), edge_Z
+ * [edge_capacity][12] f64 (the measured Z_ij), edge_w [edge_capacity][2] f64 (w_rot, w_trans) and state [4] i32 = {edges, flags, 0, 0},
+ * and relaxes the map's poses over the odometry chain plus those edges.  A pose P_i = [R_i | t_i] is a row of pr_map_buffers.poses
+ * (world to camera), verify's T maps query-camera points into the DB entry's camera frame, so an edge measures Z_ij ~ P_i P_j^-1.
+ * Products and inverses are of rigid transforms: A B = [R_A R_B | R_A t_B + t_A], A^-1 = [R^T | -R^T t].
+ *
+ *   pr_posegraph_create    binds the buffers (they must outlive the handle), allocates ALL scratch the relaxation will ever need (sized
+ *                          by the two capacities) and the staging of the host form, zeroes state.  No later call allocates.  The handle
+ *                          is bound to ctx and its stream and must be destroyed before ctx; pr_posegraph_destroy frees the handle and
+ *                          its scratch, never the buffers.  node_capacity, edge_capacity in 1 .. 2^20, max_outer in 1 .. 64, max_inner
+ *                          in 1 .. 65536.
+ *   pr_posegraph_add_dev   stream-ordered, one launch of one workgroup, 1 <= k <= 128.  EVERY array is device memory: d_idx [k] i32,
+ *                          d_T [k][12] f64, d_accepted [k] u8 (a verify's idx, T, accepted), d_query_row [>= 1] i32 - the row the query
+ *                          keyframe received: word 1 of the map append's info ("first row or -1") - and d_info [4] i32.
+ *     The rule, decided on the device.  For p = 0 .. k - 1 in ascending order slot p is logged if and only if accepted[p] != 0,
+ *     idx[p] >= 0, query_row >= 0, idx[p] != query_row and all 12 entries of T[p] are finite (a negative query_row switches the call
+ *     off).  A logged slot stores (idx[p], query_row), T[p] and (w_rot, w_trans) at row `edges`, then edges + 1 is committed; at
+ *     edges == edge_capacity nothing is stored and PR_POSEGRAPH_OVERFLOW is set (in state[1] and in every later info) until
+ *     pr_posegraph_reset.  info = {edges logged by this call, first row or -1, edges after, flags}.  A scribbled state[0] is clamped
+ *     into 0 .. edge_capacity before any address is formed from it.  Nothing is written outside the four buffers' stated extents.
+ *   pr_posegraph_add       the host form: host arrays of the same meaning, query_row by value, info [4] host; uploads, runs the device
+ *                          path, synchronises.
+ *   pr_posegraph_reset     zeroes state (stream-ordered).    pr_posegraph_count   synchronising read of edges and flags (diagnostics).
+ *   pr_posegraph_relax_dev stream-ordered, 3 outer + 3 launches whose grids depend on the create sizes only: d_n[0] (pass the map's
+ *                          state: word 0 is the keyframe count; clamped to 0 .. node_capacity) and the edge count (state) are read on
+ *                          the device, so one captured call serves every count.  d_poses_in, d_poses_out [node_capacity][12] (they may
+ *                          be equal: pass the map's poses for both to correct the map in place), d_report [outer + 2] f64.
+ *     The rule (restated in fp64 in tests/posegraph_np.py).  n = d_n[0].  Edges: the odometry edges (i, i + 1), 0 <= i < n - 1, with
+ *     Z = P_i (P_i+1)^-1 of the INPUT poses and the weights (w_odo_rot, w_odo_trans); behind them the logged edges in log order.  A
+ *     logged edge is skipped if i or j lies outside 0 .. n - 1, if i == j, or if its Z or weights are not finite; any edge is skipped
+ *     if one of its two input poses has a non-finite entry.  Residual of an edge: E = Z^-1 P_i P_j^-1, r = [log_SO3(R_E); t_E], cost
+ *     w_rot |r_rot|^2 + w_trans |r_trans|^2.  log_SO3: v = vee(R_E - R_E^T) / 2, theta = atan2(|v|, (tr R_E - 1) / 2), r_rot = k v with
+ *     k = theta / |v|, and below theta = 1e-4 the series k = 1 + theta^2 / 6 (the ONE small-angle branch: it also switches the inverse
+ *     left Jacobian's coefficient 1 / theta^2 - (1 + cos) / (2 theta sin) to 1 / 12 + theta^2 / 720, and exp's sin / theta and
+ *     (1 - cos) / theta^2 to 1 - theta^2 / 6 and 1 / 2 - theta^2 / 24).  Residual rotations above 2 rad are outside the contract.
+ *     Update of a node by delta = [w; v]: R <- exp(w) R, t <- exp(w) t + v; a delta of six exact zeros leaves the row's bytes alone.
+ *     Node 0 is fixed (the gauge): its delta is 0, its gradient 0, its preconditioner block the identity.  One outer step: every
+ *     edge is linearised at the current poses with the analytic Jacobians A = dr / d delta_i, B = dr / d delta_j at delta = 0;
+ *     g = -sum J^T W r; D_i = lambda I + sum J^T W J (6 x 6), inverted by Gauss-Jordan without pivoting - a pivot that is not positive
+ *     makes the inverse the zero block (a node without a weighted edge at lambda = 0 does not move); exactly `inner` iterations of
+ *     preconditioned conjugate gradients on (lambda I + J^T W J) x = g from x = 0, the matrix applied edge by edge; alpha = rz / pq if
+ *     pq > 0 else 0, beta = rz' / rz if rz > 0 else 0; no early exit; then every node is updated.  After `outer` steps the poses of
+ *     rows < n are written; rows >= n of d_poses_out are not.  report[s] = the cost before outer step s, report[outer] = the final
+ *     cost, report[outer + 1] = the number of edges used.
+ *     Nothing to relax: with n < 2, or when no LOGGED edge is used, no step is taken - the odometry edges have zero residual by
+ *     construction - so rows < n are copied bit for bit and every cost is reported as 0.
+ *     Every per-node sum is a gather in a fixed order (odometry edge i - 1, odometry edge i, the logged edges in log order), the dot
+ *     products are summed in a fixed order, there are no floating-point atomics: two runs give the same bytes.
+ * PR_EINVAL (text: pr_last_error) before any device is touched for a NULL handle, buffer, params or required pointer, a capacity or
+ * max_outer / max_inner out of range, k outside 1 .. 128, outer outside 1 .. max_outer, inner outside 1 .. max_inner, a negative or
+ * non-finite weight or lambda. */
+typedef struct pr_posegraph pr_posegraph;
+typedef struct pr_posegraph_buffers { int32_t* edge_ij; double* edge_Z; double* edge_w; int32_t* state; } pr_posegraph_buffers;
+typedef struct pr_posegraph_params { int32_t outer, inner; double lambda, w_odo_rot, w_odo_trans; } pr_posegraph_params;
+#define PR_POSEGRAPH_OVERFLOW 1
+int pr_posegraph_create(pr_ctx* ctx, const pr_posegraph_buffers* buffers, int32_t node_capacity, int32_t edge_capacity, int32_t max_outer,
+                        int32_t max_inner, pr_posegraph** out);
+void pr_posegraph_destroy(pr_posegraph* g);
+int pr_posegraph_reset(pr_posegraph* g);
+int pr_posegraph_count(pr_posegraph* g, int32_t* edges, int32_t* flags);
+int pr_posegraph_add_dev(pr_posegraph* g, const int32_t* d_idx, const double* d_T, const uint8_t* d_accepted, const int32_t* d_query_row, int32_t k,
+                         double w_rot, double w_trans, int32_t* d_info);
+int pr_posegraph_add(pr_posegraph* g, const int32_t* idx, const double* T, const uint8_t* accepted, int32_t query_row, int32_t k, double w_rot,
+                     double w_trans, int32_t* info);
+int pr_posegraph_relax_dev(pr_posegraph* g, const double* d_poses_in, const int32_t* d_n, const pr_posegraph_params* params, double* d_poses_out,
+                           double* d_report);
 const char* pr_host_last_error(void);
 
 #ifdef __cplusplus

@@ -26,6 +26,8 @@ WINDOW_OVERFLOW, WINDOW_ORDER_GLOBAL = 1, 2         # info[3] of a pr_window pus
 MAP_OVERFLOW, MAP_DROPPED = 1, 2                    # info[3] of a pr_map append
 ONLINE_OVERFLOW = 1                                 # info[3] of a pr_online append
 ONLINE_NB = 512                                     # most workgroups of a pr_online match's rows kernel (online.hpp)
+POSEGRAPH_OVERFLOW = 1                              # info[3] of a pr_posegraph add
+POSEGRAPH_MAX_K = 128                               # most slots of one pr_posegraph add
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PR_AMD_LIB") or os.path.join(_HERE, "libpr_amd.so")   # PR_AMD_LIB: experiment builds only
@@ -230,6 +232,13 @@ SYMBOLS = {
     "pr_online_match_dev": (C.c_int, [_vp, _vp, _vp, _i32, _dbl, _i32, _vp, _vp, _vp]),
     "pr_online_append_dev": (C.c_int, [_vp, _vp, _vp, _vp]),
     "pr_online_append": (C.c_int, [_vp, _vp, _vp]),
+    "pr_posegraph_create": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, C.POINTER(_vp)]),
+    "pr_posegraph_destroy": (None, [_vp]),
+    "pr_posegraph_reset": (C.c_int, [_vp]),
+    "pr_posegraph_count": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32)]),
+    "pr_posegraph_add_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _dbl, _dbl, _vp]),
+    "pr_posegraph_add": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _dbl, _dbl, _vp]),
+    "pr_posegraph_relax_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "pr_host_last_error": (C.c_char_p, []),
 }
 
@@ -243,6 +252,16 @@ class MapBuffers(C.Structure):
 class OnlineBuffers(C.Structure):
     """pr_online_buffers: the two caller-owned device buffers of a pr_online."""
     _fields_ = [(n, _vp) for n in ("sig", "state")]
+
+
+class PoseGraphBuffers(C.Structure):
+    """pr_posegraph_buffers: the four caller-owned device buffers of a pr_posegraph."""
+    _fields_ = [(n, _vp) for n in ("edge_ij", "edge_Z", "edge_w", "state")]
+
+
+class PoseGraphParams(C.Structure):
+    """pr_posegraph_params: the budgets and weights of one pr_posegraph_relax_dev (filled by position: `lambda` is no Python name)."""
+    _fields_ = [("outer", _i32), ("inner", _i32), ("lambda", _dbl), ("w_odo_rot", _dbl), ("w_odo_trans", _dbl)]
 
 
 _lib = None

@@ -1546,6 +1546,136 @@ class OnlineDatabase:
             pass
 
 
+class PoseGraph:
+    """pr_posegraph: the accepted closures of a drive over caller-owned buffers with a DEVICE-side count, and a pose-graph relaxation of
+    the map's poses over the odometry chain plus those closures.  The four buffers are zeroed torch tensors on the
+    context's device (or the caller's: buffers = dict of the four names): .edge_ij [edge_capacity, 2] i32 (DB row i, query row j),
+    .edge_Z [edge_capacity, 12] f64, .edge_w [edge_capacity, 2] f64 (w_rot, w_trans) and .state [4] i32 = edges, flags, 0, 0.  Every
+    launch's geometry depends on the create sizes (and outer) only and both counts are read on the device, so ONE captured add_torch
+    serves every keyframe and ONE captured relax_torch every count.  At edges == edge_capacity an add stores nothing and sets
+    POSEGRAPH_OVERFLOW in info[3] until reset().  All *_torch calls are enqueued on the context's stream; nothing is read back."""
+
+    NAMES = ("edge_ij", "edge_Z", "edge_w", "state")
+
+    def __init__(self, ctx: Context | None, node_capacity: int, edge_capacity: int, max_outer: int = 10, max_inner: int = 256,
+                 buffers: dict | None = None):
+        import torch
+        self.ctx = ctx or default_context()
+        self.lib = self.ctx.lib
+        self.node_capacity, self.edge_capacity = int(node_capacity), int(edge_capacity)
+        self.max_outer, self.max_inner = int(max_outer), int(max_inner)
+        self.h = None
+        ec = max(self.edge_capacity, 0)
+        dev = torch.device("cuda", self.ctx.device)
+        shapes = dict(edge_ij=((ec, 2), torch.int32), edge_Z=((ec, 12), torch.float64), edge_w=((ec, 2), torch.float64), state=((4,), torch.int32))
+        if buffers is None:
+            buffers = {n: torch.zeros(s, dtype=dt, device=dev) for n, (s, dt) in shapes.items()}
+        for n, (s, dt) in shapes.items():
+            t = buffers[n]
+            if (not t.is_cuda) or t.dtype != dt or not t.is_contiguous() or tuple(t.shape) != tuple(s):
+                raise ValueError(f"PoseGraph: buffer {n} must be a contiguous CUDA tensor {dt} {list(s)}")
+            setattr(self, n, t)
+        torch.cuda.synchronize(dev)                       # torch's fills (its stream) before the library's stream writes the buffers
+        rec = _lib.PoseGraphBuffers(*(C.c_void_p(getattr(self, n).data_ptr()) for n in self.NAMES))
+        h = C.c_void_p()
+        self.ctx.check(self.lib.pr_posegraph_create(self.ctx.h, C.byref(rec), self.node_capacity, self.edge_capacity, self.max_outer,
+                                                    self.max_inner, C.byref(h)))
+        self.h = h
+
+    @staticmethod
+    def _dev(t, dtype, numel, who, what, exact=True):
+        if (not t.is_cuda) or t.dtype != dtype or not t.is_contiguous() or (t.numel() != numel if exact else t.numel() < numel):
+            raise ValueError(f"{who}: {what}")
+
+    def add_torch(self, idx, T, accepted, query_row, w_rot: float = 1.0, w_trans: float = 1.0, info=None):
+        """Device form (pr_posegraph_add_dev): a verify's idx i32 [1, k] (or [k]), T f64 [1, k, 3, 4] and accepted bool | u8 [1, k], and query_row
+        i32 [>= 1] - the row the query keyframe received: map_info[1:2] of the map append in front (a negative value switches the call
+        off on the device).  Every accepted pair with a valid row and a finite T is logged as the edge (idx, query_row) with the weights
+        (w_rot, w_trans).  Returns info (device i32 [4]) = edges logged, first row | -1, edges after, flags.  Nothing synchronises,
+        nothing is allocated when info= is given."""
+        import torch
+        who = "PoseGraph.add_torch"
+        k = idx.numel()
+        self._dev(idx, torch.int32, k, who, "idx must be a contiguous CUDA tensor i32 [k]")
+        self._dev(T, torch.float64, 12 * k, who, "T must be a contiguous CUDA tensor f64 [k, 3, 4]")
+        self._dev(accepted, torch.bool if accepted.dtype == torch.bool else torch.uint8, k, who,
+                  "accepted must be a contiguous CUDA tensor bool or u8 [k]")
+        self._dev(query_row, torch.int32, 1, who, "query_row must be a CUDA tensor i32 [>= 1]", exact=False)
+        if info is None:
+            info = torch.empty(4, dtype=torch.int32, device=idx.device)
+        else:
+            self._dev(info, torch.int32, 4, who, "info must be a CUDA tensor i32 [4]")
+        p = lambda t: C.c_void_p(t.data_ptr())
+        self.ctx.check(self.lib.pr_posegraph_add_dev(self.h, p(idx), p(T), p(accepted), p(query_row), k, float(w_rot), float(w_trans), p(info)))
+        return info
+
+    def add(self, idx, T, accepted, query_row: int, w_rot: float = 1.0, w_trans: float = 1.0):
+        """Host form (pr_posegraph_add; synchronises): numpy arrays of the same meaning, query_row an int.  Returns info int32 [4]."""
+        i = np.ascontiguousarray(idx, np.int32).reshape(-1)
+        k = len(i)
+        t = np.ascontiguousarray(T, np.float64).reshape(-1)
+        a = np.ascontiguousarray(accepted, np.uint8).reshape(-1)
+        if len(t) != 12 * k or len(a) != k:
+            raise ValueError("PoseGraph.add: idx [k], T [k, 3, 4], accepted [k]")
+        info = np.empty(4, np.int32)
+        self.ctx.check(self.lib.pr_posegraph_add(self.h, _ptr(i), _ptr(t), _ptr(a), int(query_row), k, float(w_rot), float(w_trans), _ptr(info)))
+        return info
+
+    def relax_torch(self, poses, n, outer: int = 5, inner: int = 64, lam: float = 1e-9, w_odo_rot: float = 1.0, w_odo_trans: float = 1.0,
+                    out=None, report=None):
+        """Device form (pr_posegraph_relax_dev): poses f64 [node_capacity, 12] (world to camera), n i32 [>= 1] whose word 0 is the node
+        count - a KeyframeMap's .poses and .state.  `outer` damped Gauss-Newton steps of exactly `inner` preconditioned conjugate gradient
+        iterations each over the odometry chain of the input poses (weights w_odo_rot, w_odo_trans) plus the logged edges.  out: f64
+        [node_capacity, 12], may be poses itself (rows >= n are not written); report f64 [outer + 2] = the cost before each step, the
+        final cost, the edges used.  Returns (out, report).  Nothing synchronises, nothing is allocated when out= and report= are given."""
+        import torch
+        who = "PoseGraph.relax_torch"
+        outer = int(outer)
+        self._dev(poses, torch.float64, 12 * self.node_capacity, who, "poses must be a contiguous CUDA tensor f64 [node_capacity, 12]")
+        self._dev(n, torch.int32, 1, who, "n must be a CUDA tensor i32 [>= 1]", exact=False)
+        if out is None:
+            out = torch.zeros((self.node_capacity, 12), dtype=torch.float64, device=poses.device)
+        else:
+            self._dev(out, torch.float64, 12 * self.node_capacity, who, "out must be a contiguous CUDA tensor f64 [node_capacity, 12]")
+        if report is None:
+            report = torch.zeros(max(outer, 0) + 2, dtype=torch.float64, device=poses.device)
+        else:
+            self._dev(report, torch.float64, outer + 2, who, "report must be a CUDA tensor f64 [outer + 2]")
+        prm = _lib.PoseGraphParams(outer, int(inner), float(lam), float(w_odo_rot), float(w_odo_trans))
+        p = lambda t: C.c_void_p(t.data_ptr())
+        self.ctx.check(self.lib.pr_posegraph_relax_dev(self.h, p(poses), p(n), C.byref(prm), p(out), p(report)))
+        return out, report
+
+    def relax_map(self, km, **kw):
+        """relax_torch(km.poses, km.state, ...) for a KeyframeMap: out=km.poses corrects the map in place.  The map must live on this
+        handle's context (one stream) and have node_capacity keyframes; anything else is refused before the library is called."""
+        if km.ctx is not self.ctx:
+            raise ValueError("PoseGraph.relax_map: the pose graph and the map must share one context (one stream)")
+        if km.keyframe_capacity != self.node_capacity:
+            raise ValueError("PoseGraph.relax_map: node_capacity must equal the map's keyframe_capacity")
+        return self.relax_torch(km.poses, km.state, **kw)
+
+    def reset(self):
+        self.ctx.check(self.lib.pr_posegraph_reset(self.h))
+
+    def count(self):
+        """(edges, flags); synchronises (pr_posegraph_count)."""
+        n, f = C.c_int32(), C.c_int32()
+        self.ctx.check(self.lib.pr_posegraph_count(self.h, C.byref(n), C.byref(f)))
+        return int(n.value), int(f.value)
+
+    def close(self):
+        if getattr(self, "h", None) and getattr(self.ctx, "h", None):
+            self.lib.pr_posegraph_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def split_points_by_pose(pose_ids, point_ids) -> np.ndarray:
     """The reference's cursor rule (utils/pts_preprocess.h:196-200) as per-pose pushes: at pose p the cursor takes points while
     id <= pose id, so an out-of-order id makes it wait.  Returns cuts int64 [len(pose_ids) + 1]: pose p is pushed the points
