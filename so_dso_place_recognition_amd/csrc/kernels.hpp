@@ -16,8 +16,20 @@ constexpr int SC_DIMG = 2 * SC_NSLOT * SC_DSTEP;  // floats per (channel, 16-ent
 // frequency -> position in the packed images (processing order 0,30,1,2,...,29)
 __host__ __device__ inline int sc_fpos(int f) { return f == 0 ? 0 : (f == 30 ? 1 : f + 1); }
 // split-f16 images (sc_match_h.hip), sizes in BYTES
-constexpr int SCH_QBLK = 1288;                  // (8-query group, frequency): 16 rows x 80 B (Q hi | Q lo), rows 8..15 shifted by 8 B
-constexpr int SCH_QIMG = SC_NF * SCH_QBLK;      // 39 928 per (channel, 8-query group)
+constexpr int SCH_QROW = 80;                    // one query row: Q hi | Q lo, five 16-byte lane pieces
+constexpr int SCH_QBLK = 16 * SCH_QROW;         // (8-query group, frequency): 16 rows, stored in the order of sch_qrow_byte
+constexpr int SCH_QIMG = SC_NF * SCH_QBLK;      // 39 680 per (channel, 8-query group)
+// Every lane piece of the query image is 16-byte aligned, so sc_match_e reads a tile with ONE ds_read_b128 at an immediate offset from a
+// base register per operand pair (the previous image - rows 8..15 shifted by 8 B for ds_read2_b64 - cost a v_add_u32 per read).
+// Row r = (Im << 3) | query sits at place sch_qrow_pos(r) of its block.  ds_read_b128 serves the lanes in four groups of 16 - rows 0-3 and
+// 12-15 of one lane group k with rows 4-11 of the next - and banks by 16-byte slot mod 16; a row at place p starts at slot 5 p.  The places
+// give rows 0-3, 12-15 the slots 0..7 and rows 4-11 the slots 8..15: with the pair offsets below ({0,1,2,0} and {3,4,2,1} slots) that
+// leaves 10 two-way collisions in the 8 group accesses of a frequency's two reads - the least any placement of the rows can reach with
+// these pair offsets (a group is conflict-free only if the slot sets A of rows 0-3, 12-15 and C of rows 4-11 satisfy A = complement of (C+1) =
+// complement of (C+2) in Z16, which no 8-element C does).
+__host__ __device__ constexpr int sch_qrow_pos(int row) { return (int)((0xedbafc9865327410ull >> (4 * row)) & 15); }
+__host__ __device__ constexpr int sch_qrow_byte(int row) { return SCH_QROW * sch_qrow_pos(row); }     // first byte of a row in its block
+static_assert(SCH_QROW % 16 == 0 && SCH_QBLK % 16 == 0 && SCH_QIMG % 16 == 0, "ds_read_b128 needs 16-byte aligned query tiles");
 constexpr int SCH_DTILE = 768;                  // one 16x16x32 column operand: 48 lanes x 16 B
 constexpr int SCH_DFREQ = 4 * SCH_DTILE;        // Re hi, Re lo, Im hi, Im lo
 constexpr int SCH_DIMG = SC_NF * SCH_DFREQ;     // 95 232 per (channel, 16-entry DB group)
@@ -37,9 +49,9 @@ __host__ __device__ constexpr int sch_a2_byte(int k) { return k == 0 ? 48 : k ==
 __host__ __device__ constexpr int sch_b1_byte(int lane) { return lane < 48 ? lane * 16 : SCH_DTILE + (lane - 48) * 16; }   // from the hi tile's first byte
 __host__ __device__ constexpr int sch_b2_byte(int lane) { return lane < 32 ? lane * 16 : lane < 48 ? SCH_DTILE + lane * 16 : SCH_DTILE + (lane - 32) * 16; }
 // single-product f16 images (PR_SC_ARITH_F16, sc_match_e.hip): the hi halves only
-constexpr int SCF_QBLK = 640;                   // (8-query group, frequency): 16 rows x 40 B, NO shift of rows 8..15: the rows are read with ds_read2_b64
-                                                // (banks = dword mod 32, 16 consecutive lanes per access) and 10 r mod 32 is distinct for r = 0..15 - the 8-byte shift
-                                                // the 80-byte rows of the split image need made rows 8, 9, 10 collide with rows 5, 6, 7 here (round 6: SQ_LDS_BANK_CONFLICT)
+constexpr int SCF_QBLK = 640;                   // (8-query group, frequency): 16 rows x 40 B in row order, NO shift of rows 8..15: the rows are read with ds_read2_b64
+                                                // (banks = dword mod 32, 16 consecutive lanes per access) and 10 r mod 32 is distinct for r = 0..15 - an 8-byte shift
+                                                // of rows 8..15 made rows 8, 9, 10 collide with rows 5, 6, 7 here (round 6: SQ_LDS_BANK_CONFLICT)
 constexpr int SCF_QIMG = SC_NF * SCF_QBLK;      // 20 088 per (channel, 8-query group); a workgroup holds 8 groups = 64 queries
 constexpr int SCF_DFREQ = 2 * SCH_DTILE;        // Re, Im
 constexpr int SCF_DIMG = SC_NF * SCF_DFREQ;     // 47 616 per (channel, 16-entry DB group) = 2976 B per entry and channel

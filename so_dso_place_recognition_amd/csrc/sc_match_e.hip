@@ -29,7 +29,8 @@
 // live in the AccVGPR half without ever passing through a VALU instruction: vector-memory and LDS loads write AccVGPRs directly and MFMAs
 // take A / B operands from there.  So the DB operand ring (E_BACC), the query operand ring (E_AACC) and the stage-2 constants are loaded
 // straight into AccVGPRs (hipcc does this by itself once every reader of the loaded value is an asm operand with an "a" constraint) - 136
-// ArchVGPRs free, which (a) lets the rings run deeper (5 / 3 walk positions instead of 4 / 2), (b) keeps the first half's hi operand
+// ArchVGPRs free, which (a) lets the rings run deeper (6 / 3 walk positions instead of 4 / 2; 5 / 3 until the stage-2 constants became
+// resident; 6 against 5: -1.0 % per launch, 7 no better - tools/experiments/README.md), (b) keeps the first half's hi operand
 // tuples and the lo tuples of register 0 in ArchVGPRs - 48 v_accvgpr_write per unit instead of 128 - and (c) leaves hipcc no reason to
 // shuffle values through AccVGPRs on its own (it had parked 16 registers and restored them right in front of asm MFMAs).  Measured
 // (alternating runs, three boxes): 40.3 -> 39.1, 41.2 -> 39.6, 41.5 -> 39.9 ms per 4096 x 100k launch (-3.9 %); -DE_NO_ACC_OPERANDS builds the
@@ -42,7 +43,7 @@
 #define E_AACC
 #define E_SPLIT3
 #ifndef E_BD
-#define E_BD 5
+#define E_BD 6
 #endif
 #ifndef E_AD
 #define E_AD 3
@@ -52,7 +53,7 @@
 #endif
 #endif
 #ifndef E_BD
-#define E_BD 4          // depth of the DB operand ring, split-f16 form
+#define E_BD 4          // depth of the DB operand ring, split-f16 form (-DE_NO_ACC_OPERANDS; 6 with the operands in AccVGPRs, above)
 #endif
 #ifndef E_BD1
 #define E_BD1 8         // the same, single-product form (a position is only two MFMAs long); round 6: 6 -> 8, binary launch 9.06 -> 8.90 ms (-1.8 %, alternating
@@ -78,10 +79,13 @@ enum { B_REH = 0, B_REL = 1, B_IMH = 2, B_IML = 3 };
 // walk order of the frequencies: position P -> f.  Pairs (f, f + 8) inside each half of 16; P = 31 is the ghost frequency 31
 __host__ __device__ constexpr int seqf(int P) { return 16 * (P >> 4) + ((P & 15) >> 1) + 8 * (P & 1); }
 
-typedef const u32x4_a8 __attribute__((address_space(3))) * lds_tile_p;
-template <int T>
+// split-f16 image: every lane piece is 16-byte aligned (kernels.hpp) - ds_read_b128 at an immediate offset; compact image: 40-byte rows, ds_read2_b64
+typedef const u32x4 __attribute__((address_space(3))) * lds_tile_p;
+typedef const u32x4_a8 __attribute__((address_space(3))) * lds_tile_a8_p;
+template <int T, bool LO>
 __device__ __forceinline__ void load_a(AOps& a, unsigned addr) {   // addr = this lane's 16 B of the frequency's rows: operand pair 1 (h) | pair 2 (l), kernels.hpp
-  const u32x4 v = *reinterpret_cast<lds_tile_p>(addr);
+  u32x4 v;
+  if constexpr (LO) v = *reinterpret_cast<lds_tile_p>(addr); else v = *reinterpret_cast<lds_tile_a8_p>(addr);
   if (T == A_H) a.h = v; else a.l = v;
 }
 template <bool LO, int F, int T, bool SV = false>
@@ -323,7 +327,7 @@ __device__ __forceinline__ void valu_slot(f32x4 (&T)[2][8], Half<LO> (&hbs)[2]) 
 // SV (single-product form only): the kernel reads the hi halves of SPLIT-f16 images (the query groups are gathered into the compact LDS
 // image, the DB loads address the hi tiles) and rounds the result to the integer count of a binary channel (ep_store_round)
 template <bool LO, int NW, int NQG, bool SV = false>
-__global__ __launch_bounds__(64 * NW, NW / 4) void sc_match_e_kernel(const char* __restrict__ qpk,   // [2][QG32][4][31][1288 B]
+__global__ __launch_bounds__(64 * NW, NW / 4) void sc_match_e_kernel(const char* __restrict__ qpk,   // [2][QG32][4][31][1280 B]
                                                             const char* __restrict__ dpk,   // [2][DG][31][4][768 B] + zero groups
                                                             const u32x4* __restrict__ cst,  // [2][2][2][64] x 16 B
                                                             float* __restrict__ dist_p, float* __restrict__ dist_i,
@@ -357,7 +361,7 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void sc_match_e_kernel(const char*
   constexpr int QROW = LO ? 80 : 40;
   static_assert(NW == 4 || !LO, "two waves per SIMD: single-product form only (a split-f16 unit needs all 512 registers)");
   if constexpr (SV) {  // the hi halves of this workgroup's query groups of the split image -> the compact LDS image, 8 bytes at a time:
-    // compact block (group, f) = 80 words: 16 rows of 5 words; split block = 1288 B, row = 80 B (hi | lo), rows 8..15 shifted by 8 B
+    // compact block (group, f) = 80 words: 16 rows of 5 words; split block = 1280 B, row = 80 B (hi | lo) at sch_qrow_byte(row)
     constexpr int WPG = SC_NF * 80;
     unsigned long long* dst = reinterpret_cast<unsigned long long*>(lds);
     for (int i = tid; i < NQG * WPG + 8; i += 64 * NW) {
@@ -366,7 +370,7 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void sc_match_e_kernel(const char*
       const int rr = j / 5, c = j - rr * 5;
       unsigned long long v = 0ull;
       if (i < NQG * WPG && gq < QG8)
-        v = *reinterpret_cast<const unsigned long long*>(qpk + ((size_t)ch * QG8 + gq) * SCH_QIMG + (size_t)f * SCH_QBLK + rr * 80 + (rr >= 8 ? 8 : 0) + c * 8);
+        v = *reinterpret_cast<const unsigned long long*>(qpk + ((size_t)ch * QG8 + gq) * SCH_QIMG + (size_t)f * SCH_QBLK + sch_qrow_byte(rr) + c * 8);
       dst[i] = v;
     }
     // ... and behind the image {sqrt(ones) 2^-25, 1/sqrt(ones)} of the workgroup's 8 NQG queries (ep_store_round)
@@ -393,7 +397,8 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void sc_match_e_kernel(const char*
   constexpr int BD = LO ? E_BD : E_BD1;            // depth of the DB operand ring: the tiles of BD - 1 walk positions are in flight
   constexpr int AD = LO ? E_AD : 3;                // the same for the query tiles
   // split-f16 form: the two operand pairs of a frequency (kernels.hpp) - this lane's 16 bytes of its query row, and of the DB tiles below
-  const unsigned natr = lds0 + wq * QIMG + row * QROW + ((LO && row >= 8) ? 8 : 0);
+  static_assert(!LO || (QIMG % 16 == 0 && QBLK % 16 == 0 && QROW % 16 == 0), "split-f16 query tiles are read with ds_read_b128");
+  const unsigned natr = lds0 + wq * QIMG + (LO ? sch_qrow_byte(row) : row * QROW);
   const unsigned nat0 = natr + (LO ? sch_a1_byte(kg) : kg * 16);
   [[maybe_unused]] const unsigned nat1 = natr + sch_a2_byte(kg);
   const int voff = LO ? sch_b1_byte(lane) : ((lane < 48) ? lane * 16 : (int)0x80000000);     // single product, lanes 48-63: out of range -> zeros (K = 24..31)
@@ -422,6 +427,11 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void sc_match_e_kernel(const char*
     for (int r = 0; r < 4; r++) qinf[r] = qi[wq * 8 + r + ((lane & 16) ? 4 : 0)];
   }
 
+  // stage-2 constants.  Split-f16 form: loaded ONCE, into AccVGPRs (32 of the ~110 the wave leaves idle), where the stage-2 MFMAs read them
+  // for the whole sweep.  Single-product form (two waves per SIMD, 252 of 256 registers in use): requested again in every unit - a copy in
+  // the LDS behind the query image instead of the four global loads measured no gain beyond the spread of repeated runs (tools/experiments/README.md)
+  Consts c0, c1;
+  if constexpr (LO) { load_consts<0, LO>(c0, rc, lane * 16); load_consts<1, LO>(c1, rc, lane * 16); }
   AOps At[AD];
   BOps Bt[BD];
   __amdgpu_buffer_rsrc_t rs =
@@ -436,7 +446,7 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void sc_match_e_kernel(const char*
       load_b<LO, seqf(_p), _tt, SV>(Bt[_p % BD], RSRC, (LO && (_tt == B_REL || _tt == B_IML)) ? voff2 : voff);        \
     } else if constexpr ((K) < NREQ) {                                                                             \
       constexpr int _k = (K) - (BD - 1) * TPB, _p = _k / TPA, _t = _k % TPA;                                       \
-      load_a<_t>(At[_p % AD], (_t == A_L ? nat1 : nat0) + seqf(_p) * QBLK);                                        \
+      load_a<_t, LO>(At[_p % AD], (_t == A_L ? nat1 : nat0) + seqf(_p) * QBLK);                                    \
     } }
   FIRST_REQ(0, rs) FIRST_REQ(1, rs) FIRST_REQ(2, rs) FIRST_REQ(3, rs) FIRST_REQ(4, rs) FIRST_REQ(5, rs) FIRST_REQ(6, rs) FIRST_REQ(7, rs)
   FIRST_REQ(8, rs) FIRST_REQ(9, rs) FIRST_REQ(10, rs) FIRST_REQ(11, rs) FIRST_REQ(12, rs) FIRST_REQ(13, rs) FIRST_REQ(14, rs) FIRST_REQ(15, rs)
@@ -448,12 +458,13 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void sc_match_e_kernel(const char*
     const __amdgpu_buffer_rsrc_t rsn =
         __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(dbase + (size_t)gn * DIMG), 0, DIMG, 0x00020000);
     Half<LO> hbs[2];
-    Consts c0, c1;
     f32x4 T[2][8];
+    if constexpr (LO)      // (pins the resident constants in their AccVGPR tuples across the back edge, as park_half does)
+      asm volatile("" : "+a"(c0.ch), "+a"(c0.cl), "+a"(c0.sh), "+a"(c0.sl), "+a"(c1.ch), "+a"(c1.cl), "+a"(c1.sh), "+a"(c1.sl));
 
 // request tile T of walk position Q of this unit (Q >= 31: nothing)
 #define LDB(Q, TT) { if constexpr ((Q) < 32 && seqf((Q) < 32 ? (Q) : 0) < SC_NF && (LO || (TT == B_REH || TT == B_IMH))) load_b<LO, seqf((Q) < 32 ? (Q) : 0), TT, SV>(Bt[(Q) % BD], rs, (LO && (TT == B_REL || TT == B_IML)) ? voff2 : voff); }
-#define LDA(Q, TT) { if constexpr ((Q) < 32 && seqf((Q) < 32 ? (Q) : 0) < SC_NF && (LO || TT == A_H)) load_a<TT>(At[(Q) % AD], (TT == A_L ? nat1 : nat0) + seqf((Q) < 32 ? (Q) : 0) * QBLK); }
+#define LDA(Q, TT) { if constexpr ((Q) < 32 && seqf((Q) < 32 ? (Q) : 0) < SC_NF && (LO || TT == A_H)) load_a<TT, LO>(At[(Q) % AD], (TT == A_L ? nat1 : nat0) + seqf((Q) < 32 ? (Q) : 0) * QBLK); }
 #define VS(P, G) valu_slot<LO, ((P) >> 2), (((P) & 3) * 6 + (G))>(T, hbs)
 // one walk position: its 6 (LO) or 2 MFMAs, the requests for positions P + AD - 1 (query tiles) and P + BD - 1 (DB tiles), the quad's VALU
 // work of its six slots
@@ -536,11 +547,11 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void sc_match_e_kernel(const char*
     // (quad 4 has just finished the splits of quad 3: the first half's operands are complete)
     if constexpr (NW == 4) { SB(); park_half<LO>(hbs[0]); SB(); }      // one wave per SIMD: 512 registers, half of them AccVGPRs
     FREQ(20) FREQ(21) FREQ(22) FREQ(23) FREQ(24) FREQ(25) FREQ(26) FREQ(27)
-    // the last quad also requests the stage-2 constants (the operand rings are draining)
+    // single-product form: the last quad also requests the stage-2 constants (the operand rings are draining)
     FREQ(28) FREQ(29)
-    load_consts<0, LO>(c0, rc, lane * 16);
+    if constexpr (!LO) load_consts<0, LO>(c0, rc, lane * 16);
     FREQ(30)
-    load_consts<1, LO>(c1, rc, lane * 16);
+    if constexpr (!LO) load_consts<1, LO>(c1, rc, lane * 16);
     FREQ(31)
     SB(); DRAIN(); SB();
 #define VD(G) valu_slot<LO, 8, G>(T, hbs);

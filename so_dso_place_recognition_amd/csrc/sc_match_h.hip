@@ -184,7 +184,7 @@ __device__ __forceinline__ void ep_store(float mx, __amdgpu_buffer_rsrc_t rd, in
 // - wave w takes DB groups g0 + w, g0 + w + 4, ... - instead of four query groups sharing every DB group, so a call
 // takes a quarter of the time (three of four waves would otherwise multiply padding).
 template <bool ONEQ>
-__global__ __launch_bounds__(256, 1) void sc_match_h_kernel(const char* __restrict__ qpk,   // [2][QG32][4][31][1288 B]
+__global__ __launch_bounds__(256, 1) void sc_match_h_kernel(const char* __restrict__ qpk,   // [2][QG32][4][31][1280 B]
                                                             const char* __restrict__ dpk,   // [2][DG][31][4][768 B] + one zero group
                                                             const u32x4* __restrict__ cst,  // [2][2][2][64] x 16 B
                                                             float* __restrict__ dist_p, float* __restrict__ dist_i,
@@ -221,8 +221,8 @@ __global__ __launch_bounds__(256, 1) void sc_match_h_kernel(const char* __restri
   const unsigned lds0 = (unsigned)(unsigned long long)(__attribute__((address_space(3))) char*)lds;
   constexpr int GS = ONEQ ? 4 : 1;                                  // DB groups between two units of a wave
   const int wq = ONEQ ? 0 : w;                                      // this wave's query group inside the workgroup's image
-  const unsigned nat0 = lds0 + wq * SCH_QIMG + row * 80 + (row >= 8 ? 8 : 0) + sch_a1_byte(kg);
-  const unsigned rot0 = lds0 + wq * SCH_QIMG + (row ^ 8) * 80 + (row >= 8 ? 0 : 8) + sch_a1_byte(kg);
+  const unsigned nat0 = lds0 + wq * SCH_QIMG + sch_qrow_byte(row) + sch_a1_byte(kg);
+  const unsigned rot0 = lds0 + wq * SCH_QIMG + sch_qrow_byte(row ^ 8) + sch_a1_byte(kg);
   const unsigned dl = sch_a2_byte(kg) - sch_a1_byte(kg);
   const int voff = sch_b1_byte(lane), voff2 = sch_b2_byte(lane);
   const float sg = (lane < 32) ? 1.0f : -1.0f;

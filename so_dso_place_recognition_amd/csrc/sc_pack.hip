@@ -83,7 +83,7 @@ __global__ __launch_bounds__(256) void sc_pack_kernel(const T* __restrict__ sig,
 // Split-f16 images for sc_match_h.hip: every spectrum value x (queries scaled by 2^8, DB by 2^7) is stored as
 // hi = f16(x), lo = f16(x - hi).
 //   query image  [ch][group of 8][f = 0..30]{ 16 rows x 80 B: Qhi ring 0..19 | Qlo ring 16..19, 0..15 }, row = (Im<<3) | e,
-//                rows 8..15 shifted by 8 B (LDS bank spread), 1288 B per frequency
+//                stored at sch_qrow_byte(row) (kernels.hpp: 16-byte aligned lane pieces, LDS bank spread), 1280 B per frequency
 //   DB image     [ch][group of 16][f = 0..30][Re hi | Re lo | Im hi | Im lo]{ 768 B: lane = (ring>>3)<<4 | j, 16 B per
 //                lane = rings 8g..8g+7; rings 20..23 stay zero in the hi tiles and hold D hi 16..19 again in the lo tiles }
 //   (kernels.hpp: how the matchers' two operand pairs per frequency read these)
@@ -144,7 +144,7 @@ __global__ __launch_bounds__(320) void sc_pack_h_kernel(const T* __restrict__ si
       size_t bh, bl;   // byte offsets of hi and lo
       if (role == 0) {
         const int g = row >> 3, rr = (im << 3) | (row & 7);
-        const size_t base = ((size_t)ch * groups + g) * SCH_QIMG + (size_t)ff * SCH_QBLK + rr * 80 + (rr >= 8 ? 8 : 0);
+        const size_t base = ((size_t)ch * groups + g) * SCH_QIMG + (size_t)ff * SCH_QBLK + sch_qrow_byte(rr);
         bh = base + ring * 2;
         bl = base + sch_qlo_byte(ring);
       } else {
@@ -178,7 +178,7 @@ __global__ __launch_bounds__(320) void sc_pack_h_kernel(const T* __restrict__ si
 //               into SGPRs and cost no vector or LDS bandwidth: 16 v_fma_f64 per 8-byte load, nothing else in the loop
 //   norm      = every lane sums the squares of its column, the 20 partial sums of a signature are added in ring order
 //   output    = hi / lo halves scattered into an LDS copy of the workgroup's 8 frequency slices of the group image
-//               (a slice is contiguous: 3072 B per DB group, 1288 B per query group), then copied out linearly.
+//               (a slice is contiguous: 3072 B per DB group, 1280 B per query group), then copied out linearly.
 // Binary-channel statistics (kernels.hpp: ScBin; LO images only, channel 1, binfo != null): the frequency-block-0 workgroup of a row block
 // decides whether each row is binary (all non-zero entries equal and positive) and leaves binfo and, in the block's slot behind bstat, the
 // non-binary flag and the largest ones; every workgroup adds up the w-weighted squares of the rounding residuals val - hi of its own
@@ -318,7 +318,7 @@ __global__ __launch_bounds__(320) void sc_pack_h_col_kernel(const T* __restrict_
     int bh, bl;   // byte offsets of hi and lo in the LDS copy
     if (ROLE == 0) {
       const int rr = (im << 3) | (lrow & 7);
-      bh = ((lrow >> 3) * 8 + slice) * SL + rr * QROW + ((LO && rr >= 8) ? 8 : 0) + ring * 2;
+      bh = ((lrow >> 3) * 8 + slice) * SL + (LO ? sch_qrow_byte(rr) : rr * QROW) + ring * 2;
       bl = bh - ring * 2 + sch_qlo_byte(ring);
     } else {
       bh = slice * SL + im * (LO ? 2 : 1) * SCH_DTILE + (((ring >> 3) << 4) | lrow) * 16 + (ring & 7) * 2;
@@ -458,7 +458,7 @@ __global__ __launch_bounds__(320) void sc_pack_h_few_kernel(const T* __restrict_
     size_t bh;
     if (ROLE == 0) {
       const int g = row >> 3, rr = (im << 3) | (row & 7);
-      bh = ((size_t)ch * groups + g) * IMGB + (size_t)ff * SL + rr * QROW + ((LO && rr >= 8) ? 8 : 0) + ring * 2;
+      bh = ((size_t)ch * groups + g) * IMGB + (size_t)ff * SL + (LO ? sch_qrow_byte(rr) : rr * QROW) + ring * 2;
       *reinterpret_cast<_Float16*>(out + bh) = hi;
       if (LO) *reinterpret_cast<_Float16*>(out + bh - ring * 2 + sch_qlo_byte(ring)) = lo;
     } else {
