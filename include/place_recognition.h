@@ -118,10 +118,18 @@ int pr_sc_generate(pr_ctx* ctx, const double* xyz, const float* inten, const int
  * M2DP::getSignature (M2DP/M2DP.h:12-30, M2DP/M2DP.cpp:38-109) each.  out[4N][384]. */
 int pr_m2dp_generate(pr_ctx* ctx, const double* xyz, const float* inten, const int64_t* offs, int32_t N,
                      double max_rho, double* out);
-/* The rows (cloud * 4 + variant, ascending) of the LAST pr_m2dp_generate / pr_m2dp_generate_dev call of this context whose leading
- * singular pair is not unique (sigma_2 / sigma_1 > ~0.99: M2DP/M2DP.cpp:94-103's JacobiSVD returns whichever of the two near-equal
- * directions its sweeps end on, and so does this library - those rows may differ from the reference's; PR_WARN_M2DP_SVD is the
- * call-wide bit).  At most cap rows are written, *count is the number of such rows (the library records the first 1024 pairs of a call). */
+/* The rows (cloud * 4 + variant, ascending, each once) of the LAST pr_m2dp_generate* call of this context whose leading singular pair is
+ * not unique: M2DP/M2DP.cpp:94-103's JacobiSVD returns whichever of the near-equal directions its sweeps end on, and so does this library -
+ * those rows may differ from the reference's; PR_WARN_M2DP_SVD is the call-wide bit, which stays until pr_take_warnings.
+ * The rule, per count / intensity matrix of a row (sigma_1 >= sigma_2 its two largest singular values): the row is named when the power
+ * iteration on A A^T has not converged in 400 steps, or when trace(G^256) > 1.001, G the Gram matrix normalised to unit Frobenius norm
+ * after each of 8 squarings (1 for a unique pair, sqrt(j) for a j-fold tie).  A row is ALWAYS named for sigma_1 / sigma_2 <= 1.01, exact
+ * ties (sigma_1 == sigma_2: common, the count matrix holds integers) included, and NEVER for sigma_1 / sigma_2 >= 1.03, a rank-1 or a zero
+ * matrix; in between either.  An unnamed row is the reference's to 1e-9.  A named row is still a valid signature row: per channel u is a
+ * unit vector, to 1e-9 inside the span of the left singular vectors whose sigma_i >= sigma_1 / 1.03, sum(u) >= 0, and v = A^T u / ||A^T u||;
+ * a channel of a named row whose own matrix has a unique pair is the reference's to 1e-9.
+ * At most cap rows are written (cap = 0: rows may be NULL), *count is the number of such rows; the library records the first 1024
+ * (row, channel) pairs of a call, so *count <= 1024 and, beyond that many pairs, further rows are covered by the call-wide bit only. */
 int pr_m2dp_svd_rows(pr_ctx* ctx, int32_t* rows, int32_t cap, int32_t* count);
 
 /* Replaces DELIGHT::getSignature looped as in DELIGHT/test_delight.cpp:41-56 (DELIGHT/DELIGHT.h:11-18, DELIGHT.cpp:8-24;

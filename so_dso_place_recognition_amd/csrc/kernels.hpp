@@ -235,11 +235,12 @@ void launch_sc_bin(hipStream_t st, const double* xyz, const float* inten, const 
                    int ave_in_frames = 0 /* with ave = NULL: the averages are frames[c][14] */);
 void launch_m2dp_bin_svd(hipStream_t st, const double* xyz, const float* inten, const int64_t* offs, int N,
                          double max_rho, const double* frames, const float* ave, const double* planes, double* mats,
-                         double* out, int* flags /* [1] |= 1: a leading singular pair did not converge */,
+                         double* out, int* flags /* [1] |= 1: a leading singular pair is not unique */,
                          int* svd_rows /* [0] += 1 and [1 + slot] = signature row (cloud * 4 + variant) for each such pair */,
                          hipStream_t st2 = nullptr, hipEvent_t* ev_bin = nullptr, hipEvent_t* ev_svd = nullptr /* [2] each: more than one
                          batch of clouds -> the singular pairs of a batch run on st2 beside the binning of the next (see m2dp_gen.hip) */);
 constexpr int M2DP_SVD_ROWS_CAP = 1024;
+constexpr double M2DP_SVD_TIE_TRACE = 1.001;   // trace(G^256) above this: the leading pair is (nearly) tied (m2dp_svd_kernel; sigma_1 / sigma_2 < ~1.0136)
 size_t m2dp_generate_scratch_bytes(int N);
 
 // plain_match.hip — processGIST.m:1-10, processBoW.m:1-38 (h1, h2: device, row-major doubles; BoW rows alternate ids | weights)

@@ -15,6 +15,7 @@
 //               V.col(0), M2DP.cpp:94-103) in fp64: G = A A^T (64x64) in LDS, 8 normalised squarings (G^256),
 //               u = dominant column, then polished with u <- A(A^T u)/||.|| on the original matrix until the
 //               update is below 4e-15; v = A^T u / sigma.  Sign: sum(u) >= 0 (N6).  Zero matrix -> (e0, e0).
+//               A pair that is not unique - no convergence in 400 steps, or trace(G^256) > 1.001 - is named (pr_m2dp_svd_rows).
 // Bound: VALU (~50 fp32 instructions per projection, 256 P projections per cloud) + LDS atomics, not HBM and not MFMA.
 #include <type_traits>
 
@@ -310,6 +311,12 @@ __global__ __launch_bounds__(256) void m2dp_svd_kernel(const double* __restrict_
     double s = 0.0;
     for (int k = 0; k < 64; k++) s += G[tid * 65 + k];
     u[tid] = s;
+    // trace(G): G has unit Frobenius norm and the eigenvalues t_i / sqrt(sum t^2), t_i = (sigma_i / sigma_1)^512, so the trace is
+    // (1 + sum_{i>1} t_i) / sqrt(1 + sum_{i>1} t_i^2): 1 for a unique leading pair, sqrt(j) for a j-fold tie (the test below)
+    double tr = G[tid * 65 + tid];
+#pragma unroll
+    for (int s2 = 32; s2 > 0; s2 >>= 1) tr += __shfl_xor(tr, s2, 64);
+    if (tid == 0) bc[2] = tr;          // (read after the polish: many barriers on)
   }
   __syncthreads();
   {
@@ -365,15 +372,24 @@ __global__ __launch_bounds__(256) void m2dp_svd_kernel(const double* __restrict_
     const double dmax = bc[1];
     if (dmax < 4e-15 && it >= 1) { converged = true; break; }
   }
-  // sigma_2 / sigma_1 > ~0.99: the leading pair is ill-defined in the reference too (JacobiSVD returns whichever of the two
-  // near-equal directions its sweeps end on); the vector reached so far is written and the call reports it
-  // (pr_take_warnings bit PR_WARN_M2DP_SVD; the row joins the list pr_m2dp_svd_rows returns: [0] = count, then up to M2DP_SVD_ROWS_CAP rows)
-  if (!converged && tid == 0) {
+  // A leading pair that is not unique is ill-defined in the reference too (JacobiSVD returns whichever of the near-equal directions its
+  // sweeps end on); the vector reached so far is written and the call reports it (pr_take_warnings bit PR_WARN_M2DP_SVD; the
+  // row joins the list pr_m2dp_svd_rows returns: [0] = count, then up to M2DP_SVD_ROWS_CAP rows).  Two tests, either names the row:
+  //   * the polish did not converge in 400 steps: sigma_1 / sigma_2 from 1.00001 to ~1.02;
+  //   * trace(G^256) > M2DP_SVD_TIE_TRACE.  An exact or nearly exact tie DOES converge, at once: the start vector G^256 * ones is the
+  //     symmetric mix of the tied vectors, a fixed point of the polish step, so convergence cannot tell it from a unique pair.  With
+  //     t = (sigma_2 / sigma_1)^512 the trace is >= (1 + t) / sqrt(1 + t^2): >= 1.0061 for sigma_1 / sigma_2 <= 1.01 (t >= 6.1e-3), and
+  //     <= 1 + 63 * 2.7e-7 = 1.000017 when every other singular value is at sigma_1 / 1.03 or below, where the polish also converges
+  //     (within ~260 steps).  So a row is always named for sigma_1 / sigma_2 <= 1.01 and never for >= 1.03.
+  // Both are block-uniform (bc[] is read by every thread), and neither touches the iteration: an unnamed row has the bits it always had.
+  const bool named = !converged || bc[2] > M2DP_SVD_TIE_TRACE;
+  if (named && tid == 0) {
     atomicOr(flags + 1, 1);
     const int slot = atomicAdd(svd_rows, 1);
     if (slot < M2DP_SVD_ROWS_CAP) svd_rows[1 + slot] = (c0 + cl) * 4 + var;
   }
-  // v = A^T u / sigma, sign so that sum(u) >= 0
+  // v = A^T u / sigma, sign so that sum(u) >= 0.  sigma = sqrt(|| A A^T u ||) is || A^T u || only when u is a singular vector; a named
+  // row's u is a unit vector of the tied span, where the two differ by up to 1e-4 relative, so its v is normalised by its own norm.
   __syncthreads();
   {
     double s = 0.0;
@@ -381,7 +397,13 @@ __global__ __launch_bounds__(256) void m2dp_svd_kernel(const double* __restrict_
     red[tid] = s;
   }
   __syncthreads();
-  if (tid < 128) v[tid] = (red[tid] + red[tid + 128]) / sigma;
+  const double vv = (tid < 128) ? red[tid] + red[tid + 128] : 0.0;
+  double vnorm = sigma;
+  if (named) {
+    __syncthreads();                   // every read of red[] above is done: block_sum256 reuses red[0..3]
+    vnorm = sqrt(block_sum256(vv * vv, red, tid));
+  }
+  if (tid < 128) v[tid] = vv / vnorm;
   __syncthreads();
   const double su = block_sum256(tid < 64 ? u[tid] : 0.0, red, tid);
   const double sg = (su < 0.0) ? -1.0 : 1.0;

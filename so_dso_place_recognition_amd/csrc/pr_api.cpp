@@ -36,8 +36,8 @@ struct pr_ctx {
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   hipEvent_t ev_m2[4] = {nullptr, nullptr, nullptr, nullptr};   // M2DP generation: two batches in flight (binning | singular pairs), launch_m2dp_bin_svd
   std::string err;
-  int* d_svd_rows = nullptr;     // [1 + M2DP_SVD_ROWS_CAP] rows of the last pr_m2dp_generate* call whose leading singular pair did not converge
-  int* d_flags = nullptr;        // [4] deferred bits: [0] zero-norm row at pack time, [1] M2DP singular pair not converged, [2] a query was answered with fp64 row statistics, [3] more flagged queries than one stream-ordered pass resolves; [5] a BoW row was truncated; [6] a BoW query row was not conforming
+  int* d_svd_rows = nullptr;     // [1 + M2DP_SVD_ROWS_CAP] rows of the last pr_m2dp_generate* call whose leading singular pair is not unique
+  int* d_flags = nullptr;        // [4] deferred bits: [0] zero-norm row at pack time, [1] an M2DP leading singular pair is not unique, [2] a query was answered with fp64 row statistics, [3] more flagged queries than one stream-ordered pass resolves; [5] a BoW row was truncated; [6] a BoW query row was not conforming
   bool sc_online_h = false;      // PR_SC_ONLINE=h: calls of up to 8 queries through sc_match_h.hip's one-group form (the default until round 5)
   double* d_twiddle = nullptr;   // cos[60], sin[60] of 2*pi*t/60
   float* d_cst = nullptr;        // SC stage-2 constants [31][2][64]

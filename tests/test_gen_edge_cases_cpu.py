@@ -5,9 +5,11 @@
                  cannot pass;
   guards       : in longdouble, no base point within 1e-6 bins of an SC / M2DP edge or 1e-6 m of a DELIGHT octant plane / the 10 m sphere,
                  no near-edge probe closer than 1e-11 bins to its edge (the device atan2 may differ from glibc's in the last ulp: < 1e-13 bins);
-  conditioning : the two leading singular values of all eight matrices of every M2DP case are a factor >= 1.05 apart.  m2dp_svd_kernel has
-                 no threshold of its own: it names a row when 8 squarings of the Gram matrix and 400 polish steps have not brought the
-                 change of u below 4e-15, i.e. when (s2/s1)^(2*256 + 2*400) > 4e-15, s1/s2 < 1.026; 1.05 is inside the converging side."""
+  conditioning : the two leading singular values of all eight matrices of every M2DP case are a factor >= 1.05 apart.  m2dp_svd_kernel names
+                 a row on a (nearly) exact tie (trace of the squared Gram matrix, s1/s2 < 1.0136) and when 8 squarings of the Gram
+                 matrix and 400 polish steps have not brought the change of u below 4e-15, i.e. when (s2/s1)^(2*256 + 2*400) > 4e-15,
+                 s1/s2 < 1.026; 1.05 is inside the converging side.
+                 (Everything below 1.05 - ties, near ties, the slow band - is m2dp_svd_cases.py / test_gpu_m2dp_svd.py's subject.)"""
 import numpy as np
 import pytest
 
