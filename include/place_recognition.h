@@ -575,8 +575,9 @@ int pr_delight_generate_dev(pr_ctx* ctx, const double* xyz, const float* inten, 
  * pr_pts_preprocess_gpu leaves them - averages included - beside the clouds it emits (pr_clouds_dev_frames).
  * frames_have_ave != 0: slots 14 of the frames hold the averages and the call is the binning pass alone; 0: the call computes them
  * (a chain of dependent float adds per cloud, beside the binning pass).  Same results, bit for bit, as the calls above.
- * pr_sc_generate_frames_dev with frames_have_ave != 0 is one launch without any allocation and may be captured in a hipGraph (it
- * synchronises the context's stream before it returns, except while that stream is capturing). */
+ * pr_sc_generate_frames_dev with frames_have_ave != 0, and pr_delight_generate_frames_dev, are one launch without any allocation and
+ * may be captured in a hipGraph (they synchronise the context's stream before they return, except while that stream is capturing).
+ * pr_m2dp_generate_frames_dev allocates scratch and forks onto side streams: it cannot be captured. */
 int pr_cloud_frames_dev(pr_ctx* ctx, const double* xyz, const float* inten /* may be NULL */, const int64_t* offs, int32_t N, double* frames);
 int pr_sc_generate_frames_dev(pr_ctx* ctx, const double* xyz, const float* inten, const int64_t* offs, int32_t N, double max_rho,
                               const double* frames, int frames_have_ave, double* out);
@@ -955,6 +956,47 @@ int pr_online_match_dev(pr_online* o, const double* d_sig, const int32_t* d_emit
                         int32_t* d_idx, double* d_score, double* d_rows);
 int pr_online_append_dev(pr_online* o, const double* d_sig, const int32_t* d_emitted, int32_t* d_info);
 int pr_online_append(pr_online* o, const double* sig, int32_t* info);
+
+/* ---- online signature SETS: fused SC + M2DP, and DELIGHT, with ONE device-side count (onlineset.hip) ----------------------
+ * A pr_online holds one SC or one M2DP database.  BASELINE config 5 (pr_match_topk_fused_f64: the four row z-scores of the SC and the
+ * M2DP distances in one selection) needs both, and two handles would mean two counts that can disagree after an overflow; DELIGHT has no
+ * z-scores at all.  A pr_onlineset is the same device-counted database for these two kinds over CALLER-OWNED buffers (pr_onlineset_buffers):
+ *   PR_ONLINESET_FUSED    sc [capacity][2400] f64 and m2dp [capacity * 4][384] f64; delight must be NULL;   d_rows [4][capacity] in the order
+ *                         SC structure, SC intensity, M2DP count, M2DP intensity (the order of pr_align_pairs_dev's [m][k][4])
+ *   PR_ONLINESET_DELIGHT  delight [capacity * 16][256] f64; sc and m2dp must be NULL;                        d_rows [1][capacity]
+ * and state [4] i32 = {count, flags, 0, 0}: ONE count for all parts.  As for pr_online: create allocates all scratch in one block and no
+ * later call allocates; every launch's geometry depends on capacity only; d_emitted[0] == 0 switches a call off on the device; a
+ * scribbled state[0] is clamped into 0 .. capacity before an address is derived from it; nothing is written outside the stated extents.
+ * A call names the parts of its set's kind and passes NULL for the others (d_sc + d_m2dp, or d_delight).
+ *
+ *   pr_onlineset_match_dev   stream-ordered, no host decision, no read-back.  With n = state[0]:
+ *     FUSED (three launches: rows, stats, select): the four distances of every row j < n by the pair functions pr_online uses (identical
+ *     bits); per channel the row statistics of normalize(.,2) exactly as pr_online (NaN left out, N - 1); f = 0; f += p_weight z0;
+ *     f += z1; f += p_weight z2; f += z3; THEN +Inf where n - j < mask_width (the query is row n; a masked NaN becomes a selectable
+ *     +Inf); the k smallest by (score, index), NaN never selected, missing slots -1 / NaN.  n < 2: every slot -1 / NaN.
+ *     DELIGHT (two launches: rows, select): d_j = processDELIGHT.m in fp64 in the reference's summation order (the function the DELIGHT
+ *     matcher's exact rows use); no statistics and no fusion (run_test.m:26-41): the score is the distance, +Inf under the mask, the k
+ *     smallest by (score, index), NaN never selected, +Inf selectable.  n = 0: -1 / NaN; n = 1 already returns row 0.
+ *   pr_onlineset_append_dev  stream-ordered, ONE launch: every part of the keyframe goes to row count, then one thread commits count + 1
+ *                            and d_info [4] = {appended, row or -1, count after, flags}.  At count == capacity NO part is stored and
+ *                            PR_ONLINE_OVERFLOW is set (sticky until pr_onlineset_reset).  d_emitted off: info = {0, -1, count, flags}.
+ *   pr_onlineset_append      the host form: host arrays of one keyframe's parts, info host [4]; uploads, runs the device path, synchronises.
+ *   pr_onlineset_reset       zeroes state (stream-ordered).    pr_onlineset_count   synchronising read of count and flags (diagnostics).
+ * PR_EINVAL (text: pr_last_error) before any device is touched for a NULL handle, buffer or required pointer, a part that does not
+ * belong to the kind, a kind other than the two, capacity outside 1 .. PR_MAX_SIGS, max_k or k outside 1 .. 128 (k <= max_k), a
+ * non-finite p_weight, mask_width < 0. */
+enum { PR_ONLINESET_FUSED = 0, PR_ONLINESET_DELIGHT = 1 };
+typedef struct pr_onlineset pr_onlineset;
+typedef struct pr_onlineset_buffers { double* sc; double* m2dp; double* delight; int32_t* state; } pr_onlineset_buffers;
+int pr_onlineset_create(pr_ctx* ctx, int kind, const pr_onlineset_buffers* buffers, int32_t capacity, int32_t max_k, pr_onlineset** out);
+void pr_onlineset_destroy(pr_onlineset* o);
+int pr_onlineset_reset(pr_onlineset* o);
+int pr_onlineset_count(pr_onlineset* o, int32_t* count, int32_t* flags);
+int pr_onlineset_match_dev(pr_onlineset* o, const double* d_sc, const double* d_m2dp, const double* d_delight, const int32_t* d_emitted,
+                           int32_t mask_width, double p_weight, int32_t k, int32_t* d_idx, double* d_score, double* d_rows);
+int pr_onlineset_append_dev(pr_onlineset* o, const double* d_sc, const double* d_m2dp, const double* d_delight, const int32_t* d_emitted,
+                            int32_t* d_info);
+int pr_onlineset_append(pr_onlineset* o, const double* sc, const double* m2dp, const double* delight, int32_t* info);
 
 /* ---- the loop-closure log and the pose-graph relaxation of the map's poses (posegraph.hip) ------------------------------
  * A verify leaves (T, stats, accepted, hyp) in buffers the next keyframe overwrites.  A pr_posegraph keeps the accepted pairs of a drive

@@ -26,6 +26,8 @@ WINDOW_OVERFLOW, WINDOW_ORDER_GLOBAL = 1, 2         # info[3] of a pr_window pus
 MAP_OVERFLOW, MAP_DROPPED = 1, 2                    # info[3] of a pr_map append
 ONLINE_OVERFLOW = 1                                 # info[3] of a pr_online append
 ONLINE_NB = 512                                     # most workgroups of a pr_online match's rows kernel (online.hpp)
+ONLINESET_FUSED, ONLINESET_DELIGHT = 0, 1             # pr_onlineset_create's kind
+ONLINESET_NB_FUSED, ONLINESET_NB_DELIGHT = 512, 64  # most workgroups of a pr_onlineset match's rows kernel (onlineset.hpp): 1 / 16 entries each per stride
 POSEGRAPH_OVERFLOW = 1                              # info[3] of a pr_posegraph add
 POSEGRAPH_MAX_K = 128                               # most slots of one pr_posegraph add
 
@@ -232,6 +234,13 @@ SYMBOLS = {
     "pr_online_match_dev": (C.c_int, [_vp, _vp, _vp, _i32, _dbl, _i32, _vp, _vp, _vp]),
     "pr_online_append_dev": (C.c_int, [_vp, _vp, _vp, _vp]),
     "pr_online_append": (C.c_int, [_vp, _vp, _vp]),
+    "pr_onlineset_create": (C.c_int, [_vp, C.c_int, _vp, _i32, _i32, C.POINTER(_vp)]),
+    "pr_onlineset_destroy": (None, [_vp]),
+    "pr_onlineset_reset": (C.c_int, [_vp]),
+    "pr_onlineset_count": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32)]),
+    "pr_onlineset_match_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _dbl, _i32, _vp, _vp, _vp]),
+    "pr_onlineset_append_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "pr_onlineset_append": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "pr_posegraph_create": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, C.POINTER(_vp)]),
     "pr_posegraph_destroy": (None, [_vp]),
     "pr_posegraph_reset": (C.c_int, [_vp]),
@@ -252,6 +261,11 @@ class MapBuffers(C.Structure):
 class OnlineBuffers(C.Structure):
     """pr_online_buffers: the two caller-owned device buffers of a pr_online."""
     _fields_ = [(n, _vp) for n in ("sig", "state")]
+
+
+class OnlineSetBuffers(C.Structure):
+    """pr_onlineset_buffers: the caller-owned device buffers of a pr_onlineset (the parts its kind does not have are NULL)."""
+    _fields_ = [(n, _vp) for n in ("sc", "m2dp", "delight", "state")]
 
 
 class PoseGraphBuffers(C.Structure):

@@ -1546,6 +1546,175 @@ class OnlineDatabase:
             pass
 
 
+class OnlineSet:
+    """pr_onlineset: the online signature database for the two configurations one OnlineDatabase cannot hold - kind
+    'fused' (BASELINE config 5: the SC and the M2DP rows of every keyframe, the four row z-scores in one selection) or 'delight' - with
+    ONE device-side count for all parts.  The buffers are zeroed torch tensors on the context's device (or the caller's: buffers = dict
+    of NAMES[kind]): .sc [capacity, 2400] and .m2dp [capacity * 4, 384] f64, or .delight [capacity * 16, 256] f64, and .state [4] i32 =
+    count, flags, 0, 0.  `sigs` below is the keyframe's (sc [1, 2400], m2dp [4, 384]) pair for 'fused' and the DELIGHT tensor [16, 256]
+    for 'delight'.  Everything else is OnlineDatabase's: launch geometry from capacity alone, the count read on the device, so ONE captured
+    step_torch serves every keyframe of a drive; at count == capacity an append stores NO part and sets ONLINE_OVERFLOW in info[3] until
+    reset(); nothing is read back.  All *_torch calls are enqueued on the context's stream."""
+
+    NAMES = {"fused": ("sc", "m2dp", "state"), "delight": ("delight", "state")}
+    PARTS = {"fused": (("sc", 1, 2400), ("m2dp", 4, 384)), "delight": (("delight", 16, 256),)}
+    CHANNELS = {"fused": 4, "delight": 1}
+
+    def __init__(self, ctx: Context | None, kind: str, capacity: int, max_k: int = 8, buffers: dict | None = None):
+        import torch
+        if kind not in ("fused", "delight"):
+            raise ValueError("OnlineSet: kind is 'fused' or 'delight'")
+        self.ctx = ctx or default_context()
+        self.lib = self.ctx.lib
+        self.kind_name, self.kind = kind, {"fused": _lib.ONLINESET_FUSED, "delight": _lib.ONLINESET_DELIGHT}[kind]
+        self.parts, self.channels = self.PARTS[kind], self.CHANNELS[kind]
+        self.capacity, self.max_k = int(capacity), int(max_k)
+        self.h = None
+        self._align_tmp = {}
+        cap = max(self.capacity, 0)
+        dev = torch.device("cuda", self.ctx.device)
+        shapes = {n: ((cap * r, L), torch.float64) for n, r, L in self.parts}
+        shapes["state"] = ((4,), torch.int32)
+        if buffers is None:
+            buffers = {n: torch.zeros(s, dtype=dt, device=dev) for n, (s, dt) in shapes.items()}
+        for n, (s, dt) in shapes.items():
+            t = buffers[n]
+            if (not t.is_cuda) or t.dtype != dt or not t.is_contiguous() or tuple(t.shape) != tuple(s):
+                raise ValueError(f"OnlineSet: buffer {n} must be a contiguous CUDA tensor {dt} {list(s)}")
+            setattr(self, n, t)
+        torch.cuda.synchronize(dev)                       # torch's fills (its stream) before the library's stream writes the buffers
+        rec = _lib.OnlineSetBuffers(*(C.c_void_p(getattr(self, n).data_ptr()) if n in shapes else None for n, _ in _lib.OnlineSetBuffers._fields_))
+        h = C.c_void_p()
+        self.ctx.check(self.lib.pr_onlineset_create(self.ctx.h, self.kind, C.byref(rec), self.capacity, self.max_k, C.byref(h)))
+        self.h = h
+
+    def _sigs(self, sigs, who):
+        """the three part pointers (sc, m2dp, delight) of a call, None for the parts this kind does not have"""
+        import torch
+        ts = tuple(sigs) if isinstance(sigs, (tuple, list)) else (sigs,)
+        if len(ts) != len(self.parts):
+            raise ValueError(f"{who}: sigs must hold {len(self.parts)} tensor(s): " + ", ".join(n for n, _, _ in self.parts))
+        for t, (n, r, L) in zip(ts, self.parts):
+            if (not t.is_cuda) or t.dtype != torch.float64 or not t.is_contiguous() or t.numel() != r * L:
+                raise ValueError(f"{who}: {n} must be a contiguous CUDA tensor f64 [{r}, {L}]")
+        ptr = {n: C.c_void_p(t.data_ptr()) for t, (n, _, _) in zip(ts, self.parts)}
+        return ts, (ptr.get("sc"), ptr.get("m2dp"), ptr.get("delight"))
+
+    def match_torch(self, sigs, mask_width: int = 0, p_weight: float = 2.0, k: int = 1, emitted=None, out=None, rows=None):
+        """Device form (pr_onlineset_match_dev): the query's parts against the rows the set holds NOW (the count is read on the device);
+        the query counts as row `count` for the mask.  emitted i32 [>= 1] | None: emitted[0] == 0 switches the call off on the device
+        (idx = -1, score = NaN).  Returns (idx int32 [1, k], score float64 [1, k]); out: an earlier call's pair, written again.  rows f64
+        [4, capacity] ('fused': SC structure, SC intensity, M2DP count, M2DP intensity) or [1, capacity] ('delight') | None receives the
+        distances (the first `count` of each row).  p_weight is not used by 'delight'.  Nothing synchronises, nothing is allocated when
+        out= is given."""
+        import torch
+        who = "OnlineSet.match_torch"
+        ts, parts = self._sigs(sigs, who)
+        k = int(k)
+        OnlineDatabase._opt(emitted, torch.int32, 1, who, "emitted must be a CUDA tensor i32 [>= 1]")
+        if rows is not None and ((not rows.is_cuda) or rows.dtype != torch.float64 or not rows.is_contiguous()
+                                 or tuple(rows.shape) != (self.channels, self.capacity)):
+            raise ValueError(f"{who}: rows must be a contiguous CUDA tensor f64 [{self.channels}, capacity]")
+        dev = ts[0].device
+        if out is None:
+            out = (torch.empty((1, max(k, 0)), dtype=torch.int32, device=dev), torch.empty((1, max(k, 0)), dtype=torch.float64, device=dev))
+        elif tuple(out[0].shape) != (1, k) or tuple(out[1].shape) != (1, k) or out[0].dtype != torch.int32 or out[1].dtype != torch.float64 \
+                or not (out[0].is_cuda and out[1].is_cuda and out[0].is_contiguous() and out[1].is_contiguous()):
+            raise ValueError(f"{who}: out must be (idx i32 [1, k], score f64 [1, k]) CUDA tensors")
+        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        self.ctx.check(self.lib.pr_onlineset_match_dev(self.h, *parts, p(emitted), int(mask_width), float(p_weight), k, p(out[0]), p(out[1]), p(rows)))
+        return out
+
+    def append_torch(self, sigs, emitted=None, info=None):
+        """Device form (pr_onlineset_append_dev, one launch): every part becomes row `count`, then the one count is committed (emitted as
+        in match_torch).  Returns info (device i32 [4]) = appended, row | -1, count after, flags."""
+        import torch
+        who = "OnlineSet.append_torch"
+        ts, parts = self._sigs(sigs, who)
+        OnlineDatabase._opt(emitted, torch.int32, 1, who, "emitted must be a CUDA tensor i32 [>= 1]")
+        if info is None:
+            info = torch.empty(4, dtype=torch.int32, device=ts[0].device)
+        elif (not info.is_cuda) or info.dtype != torch.int32 or not info.is_contiguous() or info.numel() != 4:
+            raise ValueError(f"{who}: info must be a CUDA tensor i32 [4]")
+        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        self.ctx.check(self.lib.pr_onlineset_append_dev(self.h, *parts, p(emitted), p(info)))
+        return info
+
+    def step_torch(self, sigs, mask_width: int = 0, p_weight: float = 2.0, k: int = 1, emitted=None, out=None, rows=None, info=None):
+        """One keyframe: match_torch against the rows seen so far, then append_torch of the same parts.  Returns (idx, score, info)."""
+        idx, score = self.match_torch(sigs, mask_width, p_weight, k, emitted=emitted, out=out, rows=rows)
+        return idx, score, self.append_torch(sigs, emitted=emitted, info=info)
+
+    def align(self, idx, sigs, out=None):
+        """The best-aligning variant of the pairs (query, row idx[0, j]) from the raw rows in place.  'fused': (variant int32 [1, k, 4],
+        dist float64 [1, k, 4]) through ONE pr_align_pairs_dev, channels as rows= (var[..., :2] and var[..., 2:] are what
+        KeyframeMap.verify_variants('sc' | 'm2dp', ...) takes).  'delight': [1, k, 2] through pr_delight_align_pairs_dev in Matcher.align's
+        convention ([..., 0] the octant permutation, [..., 1] = -1 / NaN).  idx int32 [1, k] as match_torch returns it (-1: no pair).
+        out: an earlier call's pair, written again (nothing is allocated then)."""
+        import torch
+        who = "OnlineSet.align"
+        ts, _ = self._sigs(sigs, who)
+        if (not idx.is_cuda) or idx.dtype != torch.int32 or not idx.is_contiguous() or idx.dim() != 2 or idx.shape[0] != 1:
+            raise ValueError(f"{who}: idx must be a contiguous CUDA tensor i32 [1, k]")
+        k = idx.shape[1]
+        C_ = 4 if self.kind == _lib.ONLINESET_FUSED else 2
+        if out is None:
+            var = torch.empty((1, k, C_), dtype=torch.int32, device=idx.device)
+            dist = torch.empty((1, k, C_), dtype=torch.float64, device=idx.device)
+        else:
+            var, dist = out
+            if tuple(var.shape) != (1, k, C_) or tuple(dist.shape) != (1, k, C_) or var.dtype != torch.int32 or dist.dtype != torch.float64 \
+                    or not (var.is_cuda and dist.is_cuda and var.is_contiguous() and dist.is_contiguous()):
+                raise ValueError(f"{who}: out must be the pair an earlier align() of the same k returned")
+        p = lambda t: C.c_void_p(t.data_ptr())
+        if self.kind == _lib.ONLINESET_FUSED:
+            self.ctx.check(self.lib.pr_align_pairs_dev(self.ctx.h, p(ts[0]), p(self.sc), _lib.F64, p(ts[1]), p(self.m2dp), _lib.F64, 1, self.capacity, 0, k,
+                                                       p(idx), p(var), p(dist)))
+            return var, dist
+        tmp = self._align_tmp.get(k)                      # the library writes [1][k] contiguous: staged, then copied into slot 0
+        if tmp is None:
+            tmp = self._align_tmp[k] = (torch.empty((1, k), dtype=torch.int32, device=idx.device), torch.empty((1, k), dtype=torch.float64, device=idx.device))
+        self.ctx.check(self.lib.pr_delight_align_pairs_dev(self.ctx.h, p(ts[0]), p(self.delight), _lib.F64, 1, self.capacity, 0, k, p(idx), p(tmp[0]), p(tmp[1])))
+        var[..., 0].copy_(tmp[0]); var[..., 1].fill_(-1)
+        dist[..., 0].copy_(tmp[1]); dist[..., 1].fill_(float("nan"))
+        return var, dist
+
+    def append(self, sigs):
+        """Host form (pr_onlineset_append; synchronises): sigs numpy array(s) of the parts' sizes.  Returns info int32 [4]."""
+        hs = tuple(sigs) if isinstance(sigs, (tuple, list)) else (sigs,)
+        if len(hs) != len(self.parts):
+            raise ValueError(f"OnlineSet.append: sigs must hold {len(self.parts)} array(s)")
+        arr = {}
+        for a, (n, r, L) in zip(hs, self.parts):
+            arr[n] = np.ascontiguousarray(a, np.float64).reshape(-1)
+            if len(arr[n]) != r * L:
+                raise ValueError(f"OnlineSet.append: {n} must hold {r} x {L} numbers")
+        info = np.empty(4, np.int32)
+        ptr = lambda n: _ptr(arr[n]) if n in arr else None
+        self.ctx.check(self.lib.pr_onlineset_append(self.h, ptr("sc"), ptr("m2dp"), ptr("delight"), _ptr(info)))
+        return info
+
+    def reset(self):
+        self.ctx.check(self.lib.pr_onlineset_reset(self.h))
+
+    def count(self):
+        """(count, flags); synchronises (pr_onlineset_count)."""
+        n, f = C.c_int32(), C.c_int32()
+        self.ctx.check(self.lib.pr_onlineset_count(self.h, C.byref(n), C.byref(f)))
+        return int(n.value), int(f.value)
+
+    def close(self):
+        if getattr(self, "h", None) and getattr(self.ctx, "h", None):
+            self.lib.pr_onlineset_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class PoseGraph:
     """pr_posegraph: the accepted closures of a drive over caller-owned buffers with a DEVICE-side count, and a pose-graph relaxation of
     the map's poses over the odometry chain plus those closures.  The four buffers are zeroed torch tensors on the

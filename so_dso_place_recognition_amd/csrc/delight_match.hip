@@ -14,10 +14,10 @@
 //                    distance; sorted by (score, index) -> the k best; containment: every row outside the lists has
 //                    d >= L = (min_s w - ABS) / (1 + REL), so the answer is final iff the k-th score < L
 //   delight_xdist    exact rows of the flagged queries; selection and compaction are gist_match.hip's (launch_gist_xselect / _compact)
-// Exact distances (rerank and exact rows alike): a batch of 16 pairs per workgroup; 256 threads compute the terms of 4 columns x 16 rows x
-// 4 permutations of every pair in parallel, then 64 threads - one per (pair, permutation) - add them in the normative order.
+// Exact distances (rerank and exact rows alike): exact_batch of delight_exact.hpp, a batch of 16 pairs per workgroup.
 #include <climits>
 
+#include "delight_exact.hpp"
 #include "kernels.hpp"
 
 namespace pr {
@@ -25,7 +25,6 @@ namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef double f64x2 __attribute__((ext_vector_type(2)));
 
 // |key - d| <= DM_REL d + DM_ABS for a pair of coarse-exact rows (tests/test_delight_match_cpu.py restates it)
 constexpr double DM_REL = 4200.0 * 0x1p-24;
@@ -205,57 +204,6 @@ __global__ __launch_bounds__(256, 2) void delight_coarse_kernel(const float* __r
     for (int e = lane; e < C; e += 64) { cand[o + e] = li[w][e]; ckey[o + e] = lk[w][e]; }
     if (lane == 0) wout[(size_t)i * S + s] = T;
   }
-}
-
-// ------------------------------------------------------------------------------------------------ exact distances, 16 pairs at a time
-constexpr int XB = 16;            // pairs per batch
-struct XShared {
-  double term[64][65];            // [4 columns x 16 rows in the normative order][pair * 4 + permutation], padded
-  double fin[XB][4];
-};
-
-// d[p] = the normative distance of (A[p], B[p]) for p < np (1 <= np <= 16); all 256 threads call it.  A skipped term is stored as -1:
-// a term that is added is >= +0, +Inf or NaN, never negative.
-__device__ __forceinline__ void exact_batch(XShared& sh, int tid, int np, const double* const* A, const double* const* B, double* d) {
-  const int p = tid >> 4, r = tid & 15, pl = p < np ? p : 0;
-  const double* pa = A[pl] + r * 256;
-  const double* pb = B[pl] + r * 256;
-  double ts = 0.0;
-  int tc = 0;
-  for (int c0 = 0; c0 < 256; c0 += 4) {
-    const f64x2 a0 = *reinterpret_cast<const f64x2*>(pa + c0), a1 = *reinterpret_cast<const f64x2*>(pa + c0 + 2);
-    const f64x2 b0 = *reinterpret_cast<const f64x2*>(pb + c0), b1 = *reinterpret_cast<const f64x2*>(pb + c0 + 2);
-    const double av[4] = {a0[0], a0[1], a1[0], a1[1]}, bv[4] = {b0[0], b0[1], b1[0], b1[1]};
-#pragma unroll
-    for (int cc = 0; cc < 4; cc++) {
-      const double a = av[cc];
-      const double b[4] = {bv[cc], __shfl_xor(bv[cc], 5), __shfl_xor(bv[cc], 6), __shfl_xor(bv[cc], 3)};   // row r ^ X of the same pair
-#pragma unroll
-      for (int k = 0; k < 4; k++) {
-        const double sum = a + b[k], df = a - b[k];
-        const double t = ((2.0 * df) * df) / sum;
-        sh.term[cc * 16 + r][p * 4 + k] = sum > 0.0 ? t : -1.0;
-      }
-    }
-    __syncthreads();
-    if (tid < 64) {
-      for (int e = 0; e < 64; e++) {
-        const double t = sh.term[e][tid];
-        if (t != -1.0) { ts += t; tc++; }
-      }
-    }
-    __syncthreads();
-  }
-  if (tid < 64) sh.fin[tid >> 2][tid & 3] = ts / (double)tc;
-  __syncthreads();
-  if (tid < np) {
-    double best = __builtin_inf();
-#pragma unroll
-    for (int k = 0; k < 4; k++)
-      if (best > sh.fin[tid][k]) best = sh.fin[tid][k];
-    d[tid] = best;
-  }
-  __syncthreads();
 }
 
 // ascending bitonic sort of (sk, si)[0, N) by (score, index); N a power of two, 256 threads

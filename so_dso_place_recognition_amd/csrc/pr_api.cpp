@@ -1904,13 +1904,21 @@ static int delight_generate_impl(pr_ctx* ctx, const double* xyz, const float* in
   if (int rc = check_gen_args(ctx, xyz, inten, offs, N, 1.0, out)) return rc;
   if (N == 0) return PR_OK;
   if (int rc = set_device(ctx)) return rc;
+  if (frames_in) {
+    pr::launch_delight_gen(ctx->stream, xyz, inten, offs, N, frames_in, out);
+    PR_HIP(ctx, hipGetLastError());
+    // One launch and nothing allocated, as pr_sc_generate_frames_dev: the form an online step captures in a graph.  No
+    // synchronise while - and only while - the stream is capturing; outside a capture the call synchronises as it always did.
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(ctx->stream, &cap) == hipSuccess && cap == hipStreamCaptureStatusActive) return PR_OK;
+    PR_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return PR_OK;
+  }
   DevScope scope_(ctx);
   DevBuf frames;
-  if (!frames_in) {
-    PR_HIP(ctx, frames.alloc((size_t)N * 16 * 8));
-    pr::launch_cloud_frames(ctx->stream, xyz, offs, N, frames.as<double>());
-  }
-  pr::launch_delight_gen(ctx->stream, xyz, inten, offs, N, frames_in ? frames_in : frames.as<double>(), out);
+  PR_HIP(ctx, frames.alloc((size_t)N * 16 * 8));
+  pr::launch_cloud_frames(ctx->stream, xyz, offs, N, frames.as<double>());
+  pr::launch_delight_gen(ctx->stream, xyz, inten, offs, N, frames.as<double>(), out);
   PR_HIP(ctx, hipGetLastError());
   PR_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return PR_OK;
