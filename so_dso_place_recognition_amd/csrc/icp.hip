@@ -9,11 +9,11 @@
 // rule under any partition, so indices and d2 bits do not depend on the launch geometry.
 //
 // Update: the launch that knows a chunk's final correspondences (the scan itself without a split, the combine with one) reduces the
-// chunk's inliers (d2 < max_corr^2) to 17 fp64 sums - n, sum d2, sum p', sum q, sum p' q^T - by a fixed shuffle tree and writes them to
-// scratch: no floating-point atomics.  icp_finish_kernel (one wave per pair) adds the chunks in order, forms H, solves the 3 x 3 problem
-// (Jacobi on H^T H, frames.hpp; left vectors as H v / |H v|, the third pair by cross products, which is Kabsch's det correction),
-// applies the stop rules and updates T, the statistics and the pair's `done` word.  A finished pair's later launches return at once.
-#include "frames.hpp"
+// chunk's inliers (d2 < max_corr^2) to 17 fp64 sums - n, sum d2, sum p', sum q, sum p' q^T, with p' and q taken about the chunk's pivot
+// (icp_common.hpp) - by a fixed shuffle tree and writes them to scratch: no floating-point atomics.  icp_finish_kernel (one wave per
+// pair) adds the chunks in order about one pivot, forms H, solves the 3 x 3 problem (one-sided Jacobi on H itself: the singular
+// triples at H's own conditioning; the third pair by cross products, which is Kabsch's det correction), applies the stop rules and
+// updates T, the statistics and the pair's `done` word.  A finished pair's later launches return at once.
 #include "icp_common.hpp"
 #include "kernels.hpp"
 
@@ -67,18 +67,27 @@ __global__ __launch_bounds__(IC_THREADS) void icp_nn_kernel(IcpClouds A, const d
     }
   }
   const size_t row = nsplit > 1 ? ((size_t)blockIdx.z * A.c + pair) * (size_t)ld : (base ? (size_t)base[pair] : (size_t)pair * ld);
-  double a[ICP_PARTIAL];
+  unsigned first = 0xFFFFFFFFu;                    // the lane's first inlier: its index in the chunk and (fj) its target row
+  int fj = -1;
 #pragma unroll
-  for (int k = 0; k < ICP_PARTIAL; k++) a[k] = 0.0;
-#pragma unroll
-  for (int r = 0; r < R; r++) {
+  for (int r = R - 1; r >= 0; r--) {
     const int i = i0 + r * IC_THREADS + threadIdx.x;
     if (i >= S.ns) continue;
     nn_d[row + i] = bd[r];
     nn_j[row + i] = bj[r];
-    if (part && bd[r] < mc2) add_inlier(a, p[r], xd + 3 * (size_t)bj[r], bd[r]);
+    if (bd[r] < mc2) { first = r * IC_THREADS + threadIdx.x; fj = bj[r]; }
   }
-  if (part) reduce_partial(a, red, part + ((size_t)pair * nchunks + blockIdx.x) * ICP_PARTIAL);
+  if (!part) return;
+  double a[ICP_SUMS], c[3];
+#pragma unroll
+  for (int k = 0; k < ICP_SUMS; k++) a[k] = 0.0;
+  chunk_pivot(first, fj, xd, red, c);
+#pragma unroll
+  for (int r = 0; r < R; r++) {
+    const int i = i0 + r * IC_THREADS + threadIdx.x;
+    if (i < S.ns && bd[r] < mc2) add_inlier(a, p[r], xd + 3 * (size_t)bj[r], bd[r], c);
+  }
+  reduce_partial(a, c, red, part + ((size_t)pair * nchunks + blockIdx.x) * ICP_PARTIAL);
 }
 
 // grid (chunks of 256 points, pairs): the nsplit slots of a point -> its result (smaller d2, then smaller j; (+Inf, -1) = no candidate),
@@ -155,30 +164,72 @@ __device__ __forceinline__ void cross3(const double (&a)[3], const double (&b)[3
   c[0] = a[1] * b[2] - a[2] * b[1]; c[1] = a[2] * b[0] - a[0] * b[2]; c[2] = a[0] * b[1] - a[1] * b[0];
 }
 
+// exchange singular pairs j and k (column j / k of W = G V and of V, squared norm m) when k's is the larger
+__device__ __forceinline__ void lead_first(double (&W)[3][3], double (&V)[3][3], double (&m)[3], int j, int k) {
+  if (!(m[k] > m[j])) return;
+  for (int a = 0; a < 3; a++) {
+    const double w = W[a][j], v = V[a][j];
+    W[a][j] = W[a][k]; V[a][j] = V[a][k];
+    W[a][k] = w; V[a][k] = v;
+  }
+  const double t = m[j];
+  m[j] = m[k]; m[k] = t;
+}
+
 // Kabsch: the rotation dR that maximises trace(dR H), H = sum (p - mu_p)(q - mu_q)^T.  With H = U S V^T: dR = V diag(1, 1, det(V U^T)) U^T.
-// V from the Jacobi eigenvectors of H^T H (two leading ones), u_k = H v_k / |H v_k|, and u_3 = u_1 x u_2, v_3 = v_1 x v_2: both triples
-// right-handed, which is the det correction.  s1 >= s2: the two leading singular values.  noinline: one copy, off the callers' registers.
+// The singular triples come from ONE-SIDED Jacobi on G = H / max |H|: plane rotations of V's columns until the columns of W = G V are
+// orthogonal; then W = U S.  H^T H is never formed (its eigenvectors carry eps (s1 / s2)^2, H's own singular vectors eps s1 / s2).  Every
+// sweep takes its angles from a W formed afresh as G V, and so is the W the results are read from: w_k is one 3-term product sum off G,
+// in error by a few eps s1 whatever the number of rotations.  A pair of columns whose inner product is below rounding is left alone
+// (an exactly symmetric H or a multiple of a rotation ends at once); a sweep whose largest tangent is below 2^-50 is the last, and 12
+// sweeps bound the equal-singular-value cases, where rounding alone picks the angles and any of them is right.
+// u_k = w_k / |w_k| for the two leading pairs, and u_3 = u_1 x u_2, v_3 = v_1 x v_2: both triples right-handed, which is the det
+// correction.  s1 >= s2: the two leading singular values (|w_k| max |H|).  noinline: one copy, off the callers' registers.
 __device__ __attribute__((noinline)) void kabsch(const double (&H)[3][3], double (&dR)[3][3], double& s1, double& s2) {
   double hmax = 0.0;
   for (int a = 0; a < 3; a++)
     for (int b = 0; b < 3; b++) hmax = fmax(hmax, fabs(H[a][b]));
   s1 = s2 = 0.0;
   if (!(hmax > 0.0) || !(hmax < INFINITY)) return;
-  double G[3][3], A[3][3], V[3][3];
+  double G[3][3], V[3][3], W[3][3];
   for (int a = 0; a < 3; a++)
-    for (int b = 0; b < 3; b++) G[a][b] = H[a][b] / hmax;
-  for (int a = 0; a < 3; a++)
-    for (int b = a; b < 3; b++) A[a][b] = A[b][a] = (G[0][a] * G[0][b] + G[1][a] * G[1][b]) + G[2][a] * G[2][b];
-  jacobi_eig3(A, V);
-  int o[3] = {0, 1, 2};
-  for (int i = 0; i < 2; i++)
-    for (int j = 0; j < 2 - i; j++)
-      if (A[o[j + 1]][o[j + 1]] > A[o[j]][o[j]]) { const int t = o[j]; o[j] = o[j + 1]; o[j + 1] = t; }
+    for (int b = 0; b < 3; b++) { G[a][b] = H[a][b] / hmax; V[a][b] = a == b ? 1.0 : 0.0; }
+  bool rotate = true;
+  for (int sweep = 0;; sweep++) {
+#pragma unroll
+    for (int a = 0; a < 3; a++)
+#pragma unroll
+      for (int k = 0; k < 3; k++) W[a][k] = (G[a][0] * V[0][k] + G[a][1] * V[1][k]) + G[a][2] * V[2][k];
+    if (!rotate || sweep == 12) break;
+    double big = 0.0;
+#pragma unroll
+    for (int p = 0; p < 2; p++)
+#pragma unroll
+      for (int q = p + 1; q < 3; q++) {
+        const double al = (W[0][p] * W[0][p] + W[1][p] * W[1][p]) + W[2][p] * W[2][p];
+        const double be = (W[0][q] * W[0][q] + W[1][q] * W[1][q]) + W[2][q] * W[2][q];
+        const double ga = (W[0][p] * W[0][q] + W[1][p] * W[1][q]) + W[2][p] * W[2][q];
+        if (!(ga * ga > 1e-31 * (al * be))) continue;            // |cos| of the two columns <= 3.2e-16: orthogonal to rounding (or a zero column)
+        const double zeta = (be - al) / (2.0 * ga);
+        const double t = (zeta >= 0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(zeta * zeta + 1.0));
+        const double cs = 1.0 / sqrt(t * t + 1.0), sn = t * cs;
+#pragma unroll
+        for (int a = 0; a < 3; a++) {
+          const double x = W[a][p], y = W[a][q], vx = V[a][p], vy = V[a][q];
+          W[a][p] = cs * x - sn * y; W[a][q] = sn * x + cs * y;
+          V[a][p] = cs * vx - sn * vy; V[a][q] = sn * vx + cs * vy;
+        }
+        big = fmax(big, fabs(t));
+      }
+    rotate = big > 0x1p-50;                                      // if not: one more product G V and no more rotations
+  }
+  double m[3];
+#pragma unroll
+  for (int k = 0; k < 3; k++) m[k] = (W[0][k] * W[0][k] + W[1][k] * W[1][k]) + W[2][k] * W[2][k];
+  lead_first(W, V, m, 0, 1); lead_first(W, V, m, 1, 2); lead_first(W, V, m, 0, 1);
   double v[3][3], u[3][3];
   for (int k = 0; k < 2; k++)
-    for (int a = 0; a < 3; a++) v[k][a] = V[a][o[k]];
-  for (int k = 0; k < 2; k++)
-    for (int a = 0; a < 3; a++) u[k][a] = (G[a][0] * v[k][0] + G[a][1] * v[k][1]) + G[a][2] * v[k][2];
+    for (int a = 0; a < 3; a++) { v[k][a] = V[a][k]; u[k][a] = W[a][k]; }
   const double n1 = norm3(u[0]), n2 = norm3(u[1]);
   s1 = n1 * hmax; s2 = n2 * hmax;
   if (!(n2 > 1e-12 * n1)) return;
@@ -199,17 +250,47 @@ __device__ __attribute__((noinline)) void kabsch(const double (&H)[3][3], double
 __global__ __launch_bounds__(64) void icp_finish_kernel(IcpClouds A, const double* __restrict__ part, int nchunks, int chunk_pts, IcpParams P,
                                                          int final_pass, double* __restrict__ T, IcpStats* __restrict__ stats,
                                                          int* __restrict__ done, double* __restrict__ prev) {
-  __shared__ double sum[ICP_PARTIAL];
+  __shared__ double sum[ICP_SUMS];
+  __shared__ double piv[3];
   const int pair = blockIdx.x;
   PairShape S;
   if (!pair_shape(A, pair, S)) return;
   if (!final_pass && done[pair]) return;
   const int used = min(nchunks, (S.ns + chunk_pts - 1) / chunk_pts);
-  if (threadIdx.x < ICP_PARTIAL) {
-    double v = 0.0;
-    for (int k = 0; k < used; k++) v += part[((size_t)pair * nchunks + k) * ICP_PARTIAL + threadIdx.x];
-    sum[threadIdx.x] = v;
+  const double* __restrict__ pp = part + (size_t)pair * nchunks * ICP_PARTIAL;
+  if (threadIdx.x < 3) {                          // the common pivot: that of the first chunk with an inlier
+    int k0 = 0;
+    while (k0 < used && !(pp[(size_t)k0 * ICP_PARTIAL] > 0.0)) k0++;
+    piv[threadIdx.x] = k0 < used ? pp[(size_t)k0 * ICP_PARTIAL + ICP_SUMS + threadIdx.x] : 0.0;
   }
+  __syncthreads();
+  __shared__ double third[3][ICP_SUMS];
+  if (threadIdx.x < 3 * ICP_SUMS) {
+    // lane (g, t) adds sum t of the g-th third of the chunks in chunk order, each moved from its own pivot c_k to the common one by
+    // d = c_k - piv:  sum (x - piv) = sum (x - c_k) + n_k d;  sum (p - piv)(q - piv)^T = sum (p - c_k)(q - c_k)^T + S_p d^T + d S_q^T + n_k d d^T
+    const int g = threadIdx.x / ICP_SUMS, t = threadIdx.x % ICP_SUMS, per = (used + 2) / 3;
+    const int a = t >= 8 ? (t - 8) / 3 : (t >= 5 ? t - 5 : (t >= 2 ? t - 2 : 0)), b = t >= 8 ? (t - 8) % 3 : 0;
+    const int kend = min(used, (g + 1) * per);
+    double v = 0.0;
+#pragma unroll 8
+    for (int k = g * per; k < kend; k++) {         // no branch on the chunk: a chunk without inliers holds zeros (pivot included) and adds +-0
+      const double* __restrict__ ck = pp + (size_t)k * ICP_PARTIAL;
+      const double nk = ck[0];
+      double x = ck[t];
+      if (t >= 2) {
+        const double da = ck[ICP_SUMS + a] - piv[a];
+        if (t < 8) x += nk * da;
+        else {
+          const double db = ck[ICP_SUMS + b] - piv[b];
+          x += (ck[2 + a] * db + da * ck[5 + b]) + nk * (da * db);
+        }
+      }
+      v += x;
+    }
+    third[g][t] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < ICP_SUMS) sum[threadIdx.x] = (third[0][threadIdx.x] + third[1][threadIdx.x]) + third[2][threadIdx.x];
   __syncthreads();
   if (threadIdx.x != 0) return;
   const double n = sum[0];
@@ -227,12 +308,12 @@ __global__ __launch_bounds__(64) void icp_finish_kernel(IcpClouds A, const doubl
   kabsch(H, dR, s1, s2);
   if (!(s2 > 1e-12 * s1)) { st.status = ICP_DEGENERATE; done[pair] = 1; return; }
   double* Tp = T + 12 * (size_t)pair;
-  double Tn[12];
+  double Tn[12], e[3];
+  const double c[3] = {piv[0], piv[1], piv[2]};
+  for (int b = 0; b < 3; b++) e[b] = (Tp[4 * b + 3] - c[b]) - sum[2 + b] / n;      // t - mu_p: the sums are about the pivot c
   for (int a = 0; a < 3; a++) {
     for (int b = 0; b < 3; b++) Tn[4 * a + b] = (dR[a][0] * Tp[b] + dR[a][1] * Tp[4 + b]) + dR[a][2] * Tp[8 + b];
-    const double rt = (dR[a][0] * Tp[3] + dR[a][1] * Tp[7]) + dR[a][2] * Tp[11];
-    const double rm = (dR[a][0] * sum[2] + dR[a][1] * sum[3]) + dR[a][2] * sum[4];
-    Tn[4 * a + 3] = rt + (sum[5 + a] / n - rm / n);
+    Tn[4 * a + 3] = ((dR[a][0] * e[0] + dR[a][1] * e[1]) + dR[a][2] * e[2]) + (c[a] + sum[5 + a] / n);      // dR (t - mu_p) + mu_q
   }
   for (int k = 0; k < 12; k++) Tp[k] = Tn[k];
   const int it = st.iters;

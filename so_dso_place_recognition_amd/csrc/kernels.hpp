@@ -336,7 +336,8 @@ void launch_eval_trapz(hipStream_t st, const double* rec, const double* prec, in
 void eval_release(void* state);                 // eval_dev.cpp: frees a context's evaluation scratch (pr_destroy, streams idle)
 // icp.hip — point-to-point ICP of matched cloud pairs (see the file header); all pointers are device pointers
 constexpr int ICP_TILE = 256;                   // target rows a workgroup stages in LDS at a time
-constexpr int ICP_PARTIAL = 17;                 // fp64 sums per chunk: n, sum d2, sum p' [3], sum q [3], sum p' q^T [3][3]
+constexpr int ICP_SUMS = 17;                    // fp64 sums per chunk: n, sum d2, sum p' [3], sum q [3], sum p' q^T [3][3] (p', q about the chunk's pivot)
+constexpr int ICP_PARTIAL = ICP_SUMS + 3;       // a chunk's record: its sums and its pivot [3]
 enum { ICP_RUNNING = -1, ICP_CONVERGED = 0, ICP_MAX_ITER = 1, ICP_TOO_FEW = 2, ICP_DEGENERATE = 3, ICP_NO_PAIR = 4 };   // PR_ICP_* of the header
 struct IcpStats { double fitness, rmse; int32_t n_inl, iters, status, pad; };   // pr_icp_pairs_dev's stats record
 struct IcpParams { double tol_rmse, tol_fitness; int min_inliers; };
