@@ -957,7 +957,7 @@ int pr_online_match_dev(pr_online* o, const double* d_sig, const int32_t* d_emit
 int pr_online_append_dev(pr_online* o, const double* d_sig, const int32_t* d_emitted, int32_t* d_info);
 int pr_online_append(pr_online* o, const double* sig, int32_t* info);
 
-/* ---- online signature SETS: fused SC + M2DP, and DELIGHT, with ONE device-side count (onlineset.hip) ----------------------
+/* ---- online signature SETS: fused SC + M2DP, and DELIGHT, with ONE device-side count (online.hip) -------------------------
  * A pr_online holds one SC or one M2DP database.  BASELINE config 5 (pr_match_topk_fused_f64: the four row z-scores of the SC and the
  * M2DP distances in one selection) needs both, and two handles would mean two counts that can disagree after an overflow; DELIGHT has no
  * z-scores at all.  A pr_onlineset is the same device-counted database for these two kinds over CALLER-OWNED buffers (pr_onlineset_buffers):

@@ -1403,7 +1403,126 @@ class KeyframeMap:
             pass
 
 
-class OnlineDatabase:
+class _OnlineEngine:
+    """What OnlineDatabase and OnlineSet share - the two front ends of ONE engine (online.hip): the buffers, made or validated from
+    .parts = ((name, rows per entry, row length), ...); the checks of emitted= / out= / rows= / info=; match, append, step, reset, count
+    and close.  A subclass names itself (_WHO), its C family (_C), its buffers record (_REC) and the order in which the family's calls
+    take the part pointers (_ORDER; None for a part this object does not have), and sets .parts and .channels before _create."""
+
+    def _create(self, ctx, code, capacity, max_k, buffers):
+        import torch
+        self.ctx = ctx or default_context()
+        self.lib = self.ctx.lib
+        self.capacity, self.max_k, self.h = int(capacity), int(max_k), None
+        cap, dev = max(self.capacity, 0), torch.device("cuda", self.ctx.device)
+        shapes = {**{n: ((cap * r, L), torch.float64) for n, r, L in self.parts}, "state": ((4,), torch.int32)}
+        if buffers is None:
+            buffers = {n: torch.zeros(s, dtype=dt, device=dev) for n, (s, dt) in shapes.items()}
+        for n, (s, dt) in shapes.items():
+            t = buffers[n]
+            if (not t.is_cuda) or t.dtype != dt or not t.is_contiguous() or tuple(t.shape) != tuple(s):
+                raise ValueError(f"{self._WHO}: buffer {n} must be a contiguous CUDA tensor {dt} {list(s)}")
+            setattr(self, n, t)
+        torch.cuda.synchronize(dev)                       # torch's fills (its stream) before the library's stream writes the buffers
+        rec = self._REC(*(self._p(getattr(self, n)) if n in shapes else None for n, _ in self._REC._fields_))
+        h = C.c_void_p()
+        self.ctx.check(self._fn("create")(self.ctx.h, code, C.byref(rec), self.capacity, self.max_k, C.byref(h)))
+        self.h = h
+
+    _p = staticmethod(lambda t: None if t is None else C.c_void_p(t.data_ptr()))
+
+    def _fn(self, name):
+        return getattr(self.lib, f"{self._C}_{name}")
+
+    def _sigs(self, sigs, who, emitted=None):
+        """the call's part tensors, checked (as is emitted=), and their pointers in the C family's order"""
+        import torch
+        ts = tuple(sigs) if isinstance(sigs, (tuple, list)) else (sigs,)
+        if len(ts) != len(self.parts):
+            raise ValueError(f"{who}: sigs must hold {len(self.parts)} tensor(s): " + ", ".join(n for n, _, _ in self.parts))
+        for t, (n, r, L) in zip(ts, self.parts):
+            if (not t.is_cuda) or t.dtype != torch.float64 or not t.is_contiguous() or t.numel() != r * L:
+                raise ValueError(f"{who}: {n} must be a contiguous CUDA tensor f64 [{r}, {L}]")
+        if emitted is not None and ((not emitted.is_cuda) or emitted.dtype != torch.int32 or not emitted.is_contiguous() or emitted.numel() < 1):
+            raise ValueError(f"{who}: emitted must be a CUDA tensor i32 [>= 1]")
+        ptr = {n: self._p(t) for t, (n, _, _) in zip(ts, self.parts)}
+        return ts, tuple(ptr.get(n) for n in self._ORDER)
+
+    def match_torch(self, sigs, mask_width: int = 0, p_weight: float = 2.0, k: int = 1, emitted=None, out=None, rows=None):
+        """Device form (<family>_match_dev): the query's part(s) against the rows held NOW (the count is read on the device); the query
+        counts as row `count` for the mask.  emitted i32 [>= 1] | None: emitted[0] == 0 switches the call off on the device (idx = -1,
+        score = NaN).  Returns (idx int32 [1, k], score float64 [1, k]) - the shape verify takes; out: an earlier call's pair, written
+        again.  rows f64 [channels, capacity] | None receives the distances (the first `count` of each row): 'sc' structure, intensity;
+        'm2dp' count, intensity; 'fused' those four; 'delight' its one (no p_weight).  Nothing synchronises or, given out=, allocates."""
+        import torch
+        who = f"{self._WHO}.match_torch"
+        ts, parts = self._sigs(sigs, who, emitted)
+        k = int(k)
+        dev, shape = ts[0].device, (self.channels, self.capacity)
+        if rows is not None and ((not rows.is_cuda) or rows.dtype != torch.float64 or not rows.is_contiguous() or tuple(rows.shape) != shape):
+            raise ValueError(f"{who}: rows must be a contiguous CUDA tensor f64 [{self.channels}, capacity]")
+        if out is None:
+            out = (torch.empty((1, max(k, 0)), dtype=torch.int32, device=dev), torch.empty((1, max(k, 0)), dtype=torch.float64, device=dev))
+        elif tuple(out[0].shape) != (1, k) or tuple(out[1].shape) != (1, k) or out[0].dtype != torch.int32 or out[1].dtype != torch.float64 \
+                or not (out[0].is_cuda and out[1].is_cuda and out[0].is_contiguous() and out[1].is_contiguous()):
+            raise ValueError(f"{who}: out must be (idx i32 [1, k], score f64 [1, k]) CUDA tensors")
+        p = self._p
+        self.ctx.check(self._fn("match_dev")(self.h, *parts, p(emitted), int(mask_width), float(p_weight), k, p(out[0]), p(out[1]), p(rows)))
+        return out
+
+    def append_torch(self, sigs, emitted=None, info=None):
+        """Device form (<family>_append_dev, one launch): every part becomes row `count`, then the one count is committed (emitted as in
+        match_torch).  Returns info (device i32 [4]) = appended, row | -1, count after, flags."""
+        import torch
+        who = f"{self._WHO}.append_torch"
+        ts, parts = self._sigs(sigs, who, emitted)
+        if info is None:
+            info = torch.empty(4, dtype=torch.int32, device=ts[0].device)
+        elif (not info.is_cuda) or info.dtype != torch.int32 or not info.is_contiguous() or info.numel() != 4:
+            raise ValueError(f"{who}: info must be a CUDA tensor i32 [4]")
+        self.ctx.check(self._fn("append_dev")(self.h, *parts, self._p(emitted), self._p(info)))
+        return info
+
+    def step_torch(self, sigs, mask_width: int = 0, p_weight: float = 2.0, k: int = 1, emitted=None, out=None, rows=None, info=None):
+        """One keyframe: match_torch against the rows seen so far, then append_torch of the same part(s).  Returns (idx, score, info)."""
+        idx, score = self.match_torch(sigs, mask_width, p_weight, k, emitted=emitted, out=out, rows=rows)
+        return idx, score, self.append_torch(sigs, emitted=emitted, info=info)
+
+    def append(self, sigs):
+        """Host form (<family>_append; synchronises): sigs numpy array(s) of the parts' sizes.  Returns info int32 [4]."""
+        hs = tuple(sigs) if isinstance(sigs, (tuple, list)) else (sigs,)
+        if len(hs) != len(self.parts):
+            raise ValueError(f"{self._WHO}.append: sigs must hold {len(self.parts)} array(s)")
+        arr = {n: np.ascontiguousarray(a, np.float64).reshape(-1) for a, (n, _, _) in zip(hs, self.parts)}
+        for n, r, L in self.parts:
+            if len(arr[n]) != r * L:
+                raise ValueError(f"{self._WHO}.append: {n} must hold {r} x {L} numbers")
+        info = np.empty(4, np.int32)
+        self.ctx.check(self._fn("append")(self.h, *(_ptr(arr[n]) if n in arr else None for n in self._ORDER), _ptr(info)))
+        return info
+
+    def reset(self):
+        self.ctx.check(self._fn("reset")(self.h))
+
+    def count(self):
+        """(count, flags); synchronises (<family>_count)."""
+        n, f = C.c_int32(), C.c_int32()
+        self.ctx.check(self._fn("count")(self.h, C.byref(n), C.byref(f)))
+        return int(n.value), int(f.value)
+
+    def close(self):
+        if getattr(self, "h", None) and getattr(self.ctx, "h", None):
+            self._fn("destroy")(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class OnlineDatabase(_OnlineEngine):
     """pr_online: the raw SC or M2DP rows of the keyframes seen so far with a DEVICE-side count, matched exactly in fp64 and grown on the
     stream - the sibling of KeyframeMap for signatures.  type_ 'sc' | 'm2dp'; the two buffers are zeroed torch tensors
     on the context's device (or the caller's: buffers = dict(sig=, state=)): .sig [capacity * rows_per_sig, sig_len] f64 (1 x 2400 /
@@ -1413,84 +1532,28 @@ class OnlineDatabase:
     context's stream (the caller orders it against the producers of the inputs, e.g. a Context made on torch's current stream)."""
 
     NAMES = ("sig", "state")
+    _WHO, _C, _REC, _ORDER = "OnlineDatabase", "pr_online", _lib.OnlineBuffers, ("sig",)
 
     def __init__(self, ctx: Context | None, type_: str, capacity: int, max_k: int = 8, buffers: dict | None = None):
-        import torch
         if type_ not in ("sc", "m2dp"):
             raise ValueError("OnlineDatabase: type_ is 'sc' or 'm2dp'")
-        self.ctx = ctx or default_context()
-        self.lib = self.ctx.lib
         self.type_name, self.type = type_, {"sc": _lib.TYPE_SC, "m2dp": _lib.TYPE_M2DP}[type_]
         self.rows_per_sig, self.sig_len = (1, 2400) if type_ == "sc" else (4, 384)
-        self.capacity, self.max_k = int(capacity), int(max_k)
-        self.h = None
-        cap = max(self.capacity, 0)
-        dev = torch.device("cuda", self.ctx.device)
-        shapes = dict(sig=((cap * self.rows_per_sig, self.sig_len), torch.float64), state=((4,), torch.int32))
-        if buffers is None:
-            buffers = {n: torch.zeros(s, dtype=dt, device=dev) for n, (s, dt) in shapes.items()}
-        for n, (s, dt) in shapes.items():
-            t = buffers[n]
-            if (not t.is_cuda) or t.dtype != dt or not t.is_contiguous() or tuple(t.shape) != tuple(s):
-                raise ValueError(f"OnlineDatabase: buffer {n} must be a contiguous CUDA tensor {dt} {list(s)}")
-            setattr(self, n, t)
-        torch.cuda.synchronize(dev)                       # torch's fills (its stream) before the library's stream writes the buffers
-        rec = _lib.OnlineBuffers(*(C.c_void_p(getattr(self, n).data_ptr()) for n in self.NAMES))
-        h = C.c_void_p()
-        self.ctx.check(self.lib.pr_online_create(self.ctx.h, self.type, C.byref(rec), self.capacity, self.max_k, C.byref(h)))
-        self.h = h
+        self.parts, self.channels = (("sig", self.rows_per_sig, self.sig_len),), 2
+        self._create(ctx, self.type, capacity, max_k, buffers)
 
-    def _sig(self, sig, who):
-        import torch
-        if (not sig.is_cuda) or sig.dtype != torch.float64 or not sig.is_contiguous() or sig.numel() != self.rows_per_sig * self.sig_len:
-            raise ValueError(f"{who}: sig must be a contiguous CUDA tensor f64 [{self.rows_per_sig}, {self.sig_len}]")
-
-    @staticmethod
-    def _opt(t, dtype, numel, who, what):
-        if t is not None and ((not t.is_cuda) or t.dtype != dtype or not t.is_contiguous() or t.numel() < numel):
-            raise ValueError(f"{who}: {what}")
-
+    # The engine's calls (documented there) of the one part: sig f64 [rows_per_sig, sig_len], rows f64 [2, capacity].
     def match_torch(self, sig, mask_width: int = 0, p_weight: float = 2.0, k: int = 1, emitted=None, out=None, rows=None):
-        """Device form (pr_online_match_dev): the query's signature sig f64 [rows_per_sig, sig_len] against the rows the database holds
-        NOW (the count is read on the device); the query counts as row `count` for the mask.  emitted i32 [>= 1] | None: emitted[0] == 0
-        switches the call off on the device (idx = -1, score = NaN).  Returns (idx int32 [1, k], score float64 [1, k]) - the shape
-        verify takes; out: an earlier call's pair, written again.  rows f64 [2, capacity] | None receives the channel distances (the first
-        `count` of each half).  Nothing synchronises, nothing is allocated when out= is given."""
-        import torch
-        who = "OnlineDatabase.match_torch"
-        self._sig(sig, who)
-        k = int(k)
-        self._opt(emitted, torch.int32, 1, who, "emitted must be a CUDA tensor i32 [>= 1]")
-        if rows is not None and ((not rows.is_cuda) or rows.dtype != torch.float64 or not rows.is_contiguous() or tuple(rows.shape) != (2, self.capacity)):
-            raise ValueError(f"{who}: rows must be a contiguous CUDA tensor f64 [2, capacity]")
-        if out is None:
-            out = (torch.empty((1, max(k, 0)), dtype=torch.int32, device=sig.device), torch.empty((1, max(k, 0)), dtype=torch.float64, device=sig.device))
-        elif tuple(out[0].shape) != (1, k) or tuple(out[1].shape) != (1, k) or out[0].dtype != torch.int32 or out[1].dtype != torch.float64 \
-                or not (out[0].is_cuda and out[1].is_cuda and out[0].is_contiguous() and out[1].is_contiguous()):
-            raise ValueError(f"{who}: out must be (idx i32 [1, k], score f64 [1, k]) CUDA tensors")
-        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        self.ctx.check(self.lib.pr_online_match_dev(self.h, p(sig), p(emitted), int(mask_width), float(p_weight), k, p(out[0]), p(out[1]), p(rows)))
-        return out
+        return super().match_torch(sig, mask_width, p_weight, k, emitted=emitted, out=out, rows=rows)
 
     def append_torch(self, sig, emitted=None, info=None):
-        """Device form (pr_online_append_dev): sig becomes row `count` (emitted as in match_torch).  Returns info (device i32 [4]) =
-        appended, row | -1, count after, flags."""
-        import torch
-        who = "OnlineDatabase.append_torch"
-        self._sig(sig, who)
-        self._opt(emitted, torch.int32, 1, who, "emitted must be a CUDA tensor i32 [>= 1]")
-        if info is None:
-            info = torch.empty(4, dtype=torch.int32, device=sig.device)
-        elif (not info.is_cuda) or info.dtype != torch.int32 or not info.is_contiguous() or info.numel() != 4:
-            raise ValueError(f"{who}: info must be a CUDA tensor i32 [4]")
-        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        self.ctx.check(self.lib.pr_online_append_dev(self.h, p(sig), p(emitted), p(info)))
-        return info
+        return super().append_torch(sig, emitted=emitted, info=info)
 
     def step_torch(self, sig, mask_width: int = 0, p_weight: float = 2.0, k: int = 1, emitted=None, out=None, rows=None, info=None):
-        """One keyframe: match_torch against the rows seen so far, then append_torch of the same signature.  Returns (idx, score, info)."""
-        idx, score = self.match_torch(sig, mask_width, p_weight, k, emitted=emitted, out=out, rows=rows)
-        return idx, score, self.append_torch(sig, emitted=emitted, info=info)
+        return super().step_torch(sig, mask_width, p_weight, k, emitted=emitted, out=out, rows=rows, info=info)
+
+    def append(self, sig):
+        return super().append((sig,))                     # (a list of numbers is one part, not a list of parts)
 
     def align(self, idx, sig, out=None):
         """The best-aligning variant of the pairs (query sig, row idx[0, j]) from the raw rows in place (pr_align_pairs_dev with n_local =
@@ -1498,7 +1561,7 @@ class OnlineDatabase:
         KeyframeMap.verify_variants takes.  idx int32 [1, k] as match_torch returns it (-1: no pair).  out: an earlier call's pair."""
         import torch
         who = "OnlineDatabase.align"
-        self._sig(sig, who)
+        self._sigs(sig, who)
         if (not idx.is_cuda) or idx.dtype != torch.int32 or not idx.is_contiguous() or idx.dim() != 2 or idx.shape[0] != 1:
             raise ValueError(f"{who}: idx must be a contiguous CUDA tensor i32 [1, k]")
         k = idx.shape[1]
@@ -1516,134 +1579,27 @@ class OnlineDatabase:
         self.ctx.check(self.lib.pr_align_pairs_dev(self.ctx.h, *sc, *m2, 1, self.capacity, 0, k, p(idx), p(var), p(dist)))
         return var[..., ch], dist[..., ch]
 
-    def append(self, sig):
-        """Host form (pr_online_append; synchronises): sig a numpy array of rows_per_sig x sig_len numbers.  Returns info int32 [4]."""
-        s = np.ascontiguousarray(sig, np.float64).reshape(-1)
-        if len(s) != self.rows_per_sig * self.sig_len:
-            raise ValueError(f"OnlineDatabase.append: sig must hold {self.rows_per_sig} x {self.sig_len} numbers")
-        info = np.empty(4, np.int32)
-        self.ctx.check(self.lib.pr_online_append(self.h, _ptr(s), _ptr(info)))
-        return info
 
-    def reset(self):
-        self.ctx.check(self.lib.pr_online_reset(self.h))
-
-    def count(self):
-        """(count, flags); synchronises (pr_online_count)."""
-        n, f = C.c_int32(), C.c_int32()
-        self.ctx.check(self.lib.pr_online_count(self.h, C.byref(n), C.byref(f)))
-        return int(n.value), int(f.value)
-
-    def close(self):
-        if getattr(self, "h", None) and getattr(self.ctx, "h", None):
-            self.lib.pr_online_destroy(self.h)
-        self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class OnlineSet:
+class OnlineSet(_OnlineEngine):
     """pr_onlineset: the online signature database for the two configurations one OnlineDatabase cannot hold - kind
     'fused' (BASELINE config 5: the SC and the M2DP rows of every keyframe, the four row z-scores in one selection) or 'delight' - with
     ONE device-side count for all parts.  The buffers are zeroed torch tensors on the context's device (or the caller's: buffers = dict
     of NAMES[kind]): .sc [capacity, 2400] and .m2dp [capacity * 4, 384] f64, or .delight [capacity * 16, 256] f64, and .state [4] i32 =
-    count, flags, 0, 0.  `sigs` below is the keyframe's (sc [1, 2400], m2dp [4, 384]) pair for 'fused' and the DELIGHT tensor [16, 256]
-    for 'delight'.  Everything else is OnlineDatabase's: launch geometry from capacity alone, the count read on the device, so ONE captured
-    step_torch serves every keyframe of a drive; at count == capacity an append stores NO part and sets ONLINE_OVERFLOW in info[3] until
-    reset(); nothing is read back.  All *_torch calls are enqueued on the context's stream."""
+    count, flags, 0, 0.  `sigs` is the keyframe's (sc [1, 2400], m2dp [4, 384]) pair for 'fused' and the DELIGHT tensor [16, 256] for
+    'delight'.  Everything else is OnlineDatabase's, the calls included (one engine); at count == capacity an append stores NO part."""
 
     NAMES = {"fused": ("sc", "m2dp", "state"), "delight": ("delight", "state")}
     PARTS = {"fused": (("sc", 1, 2400), ("m2dp", 4, 384)), "delight": (("delight", 16, 256),)}
     CHANNELS = {"fused": 4, "delight": 1}
+    _WHO, _C, _REC, _ORDER = "OnlineSet", "pr_onlineset", _lib.OnlineSetBuffers, ("sc", "m2dp", "delight")
 
     def __init__(self, ctx: Context | None, kind: str, capacity: int, max_k: int = 8, buffers: dict | None = None):
-        import torch
         if kind not in ("fused", "delight"):
             raise ValueError("OnlineSet: kind is 'fused' or 'delight'")
-        self.ctx = ctx or default_context()
-        self.lib = self.ctx.lib
         self.kind_name, self.kind = kind, {"fused": _lib.ONLINESET_FUSED, "delight": _lib.ONLINESET_DELIGHT}[kind]
         self.parts, self.channels = self.PARTS[kind], self.CHANNELS[kind]
-        self.capacity, self.max_k = int(capacity), int(max_k)
-        self.h = None
         self._align_tmp = {}
-        cap = max(self.capacity, 0)
-        dev = torch.device("cuda", self.ctx.device)
-        shapes = {n: ((cap * r, L), torch.float64) for n, r, L in self.parts}
-        shapes["state"] = ((4,), torch.int32)
-        if buffers is None:
-            buffers = {n: torch.zeros(s, dtype=dt, device=dev) for n, (s, dt) in shapes.items()}
-        for n, (s, dt) in shapes.items():
-            t = buffers[n]
-            if (not t.is_cuda) or t.dtype != dt or not t.is_contiguous() or tuple(t.shape) != tuple(s):
-                raise ValueError(f"OnlineSet: buffer {n} must be a contiguous CUDA tensor {dt} {list(s)}")
-            setattr(self, n, t)
-        torch.cuda.synchronize(dev)                       # torch's fills (its stream) before the library's stream writes the buffers
-        rec = _lib.OnlineSetBuffers(*(C.c_void_p(getattr(self, n).data_ptr()) if n in shapes else None for n, _ in _lib.OnlineSetBuffers._fields_))
-        h = C.c_void_p()
-        self.ctx.check(self.lib.pr_onlineset_create(self.ctx.h, self.kind, C.byref(rec), self.capacity, self.max_k, C.byref(h)))
-        self.h = h
-
-    def _sigs(self, sigs, who):
-        """the three part pointers (sc, m2dp, delight) of a call, None for the parts this kind does not have"""
-        import torch
-        ts = tuple(sigs) if isinstance(sigs, (tuple, list)) else (sigs,)
-        if len(ts) != len(self.parts):
-            raise ValueError(f"{who}: sigs must hold {len(self.parts)} tensor(s): " + ", ".join(n for n, _, _ in self.parts))
-        for t, (n, r, L) in zip(ts, self.parts):
-            if (not t.is_cuda) or t.dtype != torch.float64 or not t.is_contiguous() or t.numel() != r * L:
-                raise ValueError(f"{who}: {n} must be a contiguous CUDA tensor f64 [{r}, {L}]")
-        ptr = {n: C.c_void_p(t.data_ptr()) for t, (n, _, _) in zip(ts, self.parts)}
-        return ts, (ptr.get("sc"), ptr.get("m2dp"), ptr.get("delight"))
-
-    def match_torch(self, sigs, mask_width: int = 0, p_weight: float = 2.0, k: int = 1, emitted=None, out=None, rows=None):
-        """Device form (pr_onlineset_match_dev): the query's parts against the rows the set holds NOW (the count is read on the device);
-        the query counts as row `count` for the mask.  emitted i32 [>= 1] | None: emitted[0] == 0 switches the call off on the device
-        (idx = -1, score = NaN).  Returns (idx int32 [1, k], score float64 [1, k]); out: an earlier call's pair, written again.  rows f64
-        [4, capacity] ('fused': SC structure, SC intensity, M2DP count, M2DP intensity) or [1, capacity] ('delight') | None receives the
-        distances (the first `count` of each row).  p_weight is not used by 'delight'.  Nothing synchronises, nothing is allocated when
-        out= is given."""
-        import torch
-        who = "OnlineSet.match_torch"
-        ts, parts = self._sigs(sigs, who)
-        k = int(k)
-        OnlineDatabase._opt(emitted, torch.int32, 1, who, "emitted must be a CUDA tensor i32 [>= 1]")
-        if rows is not None and ((not rows.is_cuda) or rows.dtype != torch.float64 or not rows.is_contiguous()
-                                 or tuple(rows.shape) != (self.channels, self.capacity)):
-            raise ValueError(f"{who}: rows must be a contiguous CUDA tensor f64 [{self.channels}, capacity]")
-        dev = ts[0].device
-        if out is None:
-            out = (torch.empty((1, max(k, 0)), dtype=torch.int32, device=dev), torch.empty((1, max(k, 0)), dtype=torch.float64, device=dev))
-        elif tuple(out[0].shape) != (1, k) or tuple(out[1].shape) != (1, k) or out[0].dtype != torch.int32 or out[1].dtype != torch.float64 \
-                or not (out[0].is_cuda and out[1].is_cuda and out[0].is_contiguous() and out[1].is_contiguous()):
-            raise ValueError(f"{who}: out must be (idx i32 [1, k], score f64 [1, k]) CUDA tensors")
-        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        self.ctx.check(self.lib.pr_onlineset_match_dev(self.h, *parts, p(emitted), int(mask_width), float(p_weight), k, p(out[0]), p(out[1]), p(rows)))
-        return out
-
-    def append_torch(self, sigs, emitted=None, info=None):
-        """Device form (pr_onlineset_append_dev, one launch): every part becomes row `count`, then the one count is committed (emitted as
-        in match_torch).  Returns info (device i32 [4]) = appended, row | -1, count after, flags."""
-        import torch
-        who = "OnlineSet.append_torch"
-        ts, parts = self._sigs(sigs, who)
-        OnlineDatabase._opt(emitted, torch.int32, 1, who, "emitted must be a CUDA tensor i32 [>= 1]")
-        if info is None:
-            info = torch.empty(4, dtype=torch.int32, device=ts[0].device)
-        elif (not info.is_cuda) or info.dtype != torch.int32 or not info.is_contiguous() or info.numel() != 4:
-            raise ValueError(f"{who}: info must be a CUDA tensor i32 [4]")
-        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        self.ctx.check(self.lib.pr_onlineset_append_dev(self.h, *parts, p(emitted), p(info)))
-        return info
-
-    def step_torch(self, sigs, mask_width: int = 0, p_weight: float = 2.0, k: int = 1, emitted=None, out=None, rows=None, info=None):
-        """One keyframe: match_torch against the rows seen so far, then append_torch of the same parts.  Returns (idx, score, info)."""
-        idx, score = self.match_torch(sigs, mask_width, p_weight, k, emitted=emitted, out=out, rows=rows)
-        return idx, score, self.append_torch(sigs, emitted=emitted, info=info)
+        self._create(ctx, self.kind, capacity, max_k, buffers)
 
     def align(self, idx, sigs, out=None):
         """The best-aligning variant of the pairs (query, row idx[0, j]) from the raw rows in place.  'fused': (variant int32 [1, k, 4],
@@ -1678,41 +1634,6 @@ class OnlineSet:
         var[..., 0].copy_(tmp[0]); var[..., 1].fill_(-1)
         dist[..., 0].copy_(tmp[1]); dist[..., 1].fill_(float("nan"))
         return var, dist
-
-    def append(self, sigs):
-        """Host form (pr_onlineset_append; synchronises): sigs numpy array(s) of the parts' sizes.  Returns info int32 [4]."""
-        hs = tuple(sigs) if isinstance(sigs, (tuple, list)) else (sigs,)
-        if len(hs) != len(self.parts):
-            raise ValueError(f"OnlineSet.append: sigs must hold {len(self.parts)} array(s)")
-        arr = {}
-        for a, (n, r, L) in zip(hs, self.parts):
-            arr[n] = np.ascontiguousarray(a, np.float64).reshape(-1)
-            if len(arr[n]) != r * L:
-                raise ValueError(f"OnlineSet.append: {n} must hold {r} x {L} numbers")
-        info = np.empty(4, np.int32)
-        ptr = lambda n: _ptr(arr[n]) if n in arr else None
-        self.ctx.check(self.lib.pr_onlineset_append(self.h, ptr("sc"), ptr("m2dp"), ptr("delight"), _ptr(info)))
-        return info
-
-    def reset(self):
-        self.ctx.check(self.lib.pr_onlineset_reset(self.h))
-
-    def count(self):
-        """(count, flags); synchronises (pr_onlineset_count)."""
-        n, f = C.c_int32(), C.c_int32()
-        self.ctx.check(self.lib.pr_onlineset_count(self.h, C.byref(n), C.byref(f)))
-        return int(n.value), int(f.value)
-
-    def close(self):
-        if getattr(self, "h", None) and getattr(self.ctx, "h", None):
-            self.lib.pr_onlineset_destroy(self.h)
-        self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class PoseGraph:

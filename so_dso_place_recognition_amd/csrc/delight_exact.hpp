@@ -1,5 +1,5 @@
 // delight_exact.hpp - the exact DELIGHT pair distance in fp64, 16 pairs at a time (processDELIGHT.m:7-37 in the reference's summation
-// order), shared by delight_match.hip (rerank and exact rows) and onlineset.hip (the rows of an online DELIGHT set): one text, so a
+// order), shared by delight_match.hip (rerank and exact rows) and online.hip (the rows of an online DELIGHT set): one text, so a
 // duplicated row gives both the same bits.  256 threads compute the terms of 4 columns x 16 rows x 4 permutations of every pair in
 // parallel, then 64 threads - one per (pair, permutation) - add them in the normative order.
 #pragma once

@@ -1,5 +1,5 @@
-// online.cpp — host side of the online signature database (online.hip): the opaque pr_online over the caller's two buffers
-// with its scratch, the argument checks, the stream-ordered entry points and the host form of an append.
+// online.cpp — host side of the online engine (online.hip): ONE core - the view over the caller's buffers, its scratch, match, append and
+// the host form of an append - behind two C families, pr_online (SC, M2DP) and pr_onlineset (FUSED, DELIGHT), whose entry points do their own argument checks.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -13,15 +13,18 @@
 #include "online.hpp"
 
 static_assert(pr::ONLINE_OVERFLOW == PR_ONLINE_OVERFLOW, "flag bit");
-static_assert(PR_TYPE_SC == 0 && PR_TYPE_M2DP == 1, "online.hip tells the types apart by these values");
+static_assert(PR_TYPE_SC == pr::ONLINE_SC && PR_TYPE_M2DP == pr::ONLINE_M2DP, "pr_online_create passes its type on as the kind");
+static_assert(PR_ONLINESET_FUSED == 0 && PR_ONLINESET_DELIGHT == 1 && pr::ONLINE_DELIGHT == pr::ONLINE_FUSED + 1, "pr_onlineset_create adds ONLINE_FUSED");
 
-struct pr_online {
+struct OnlineCore {
   pr_ctx* ctx = nullptr;
   pr::OnlineView v;
   void* scratch = nullptr;            // one allocation: rows, partial, stats and the staging of the host form
-  double* stage_sig = nullptr;        // [sig_doubles]
+  double* stage_sig = nullptr;        // [len[0] + len[1]]: the parts, one behind the other
   int32_t* stage_info = nullptr;      // [4]
 };
+struct pr_online : OnlineCore {};
+struct pr_onlineset : OnlineCore {};
 
 namespace {
 
@@ -45,36 +48,30 @@ int fail(pr_ctx* ctx, int code, const char* fmt, ...) {
 
 size_t up16(size_t n) { return (n + 15) & ~(size_t)15; }
 
-}  // namespace
-
-extern "C" {
-
-int pr_online_create(pr_ctx* ctx, int type, const pr_online_buffers* buffers, int32_t capacity, int32_t max_k, pr_online** out) {
-  // the value checks come first and need no device: with ctx == NULL their text goes to pr_last_error(NULL)
-  if (!out) return fail(ctx, PR_EINVAL, "pr_online_create: out is NULL");
-  *out = nullptr;
-  if (!buffers) return fail(ctx, PR_EINVAL, "pr_online_create: buffers is NULL");
-  if (!buffers->sig || !buffers->state) return fail(ctx, PR_EINVAL, "pr_online_create: a buffer is NULL (sig, state)");
-  if (type != PR_TYPE_SC && type != PR_TYPE_M2DP) return fail(ctx, PR_EINVAL, "pr_online_create: type=%d is neither PR_TYPE_SC nor PR_TYPE_M2DP", type);
-  if (capacity < 1 || capacity > PR_MAX_SIGS)
-    return fail(ctx, PR_EINVAL, "pr_online_create: capacity=%d outside 1 .. PR_MAX_SIGS=%d", capacity, PR_MAX_SIGS);
-  if (max_k < 1 || max_k > pr::ONLINE_MAX_K) return fail(ctx, PR_EINVAL, "pr_online_create: max_k=%d outside 1 .. %d", max_k, pr::ONLINE_MAX_K);
-  if (!ctx) return fail(nullptr, PR_EINVAL, "pr_online_create: ctx is NULL");
+// Below, fn is the entry point's name and noun what it calls its handle ("database" / "set").  create: what is left once the entry point has
+// checked its own arguments - the checks both families share, the handle, the view over (p0, p1, state) and the scratch, from (kind, capacity) alone.
+template <class T>
+int create(pr_ctx* ctx, const char* fn, int kind, double* p0, double* p1, int32_t* state, int32_t capacity, int32_t max_k, T** out) {
+  if (capacity < 1 || capacity > PR_MAX_SIGS) return fail(ctx, PR_EINVAL, "%s: capacity=%d outside 1 .. PR_MAX_SIGS=%d", fn, capacity, PR_MAX_SIGS);
+  if (max_k < 1 || max_k > pr::ONLINE_MAX_K) return fail(ctx, PR_EINVAL, "%s: max_k=%d outside 1 .. %d", fn, max_k, pr::ONLINE_MAX_K);
+  if (!ctx) return fail(nullptr, PR_EINVAL, "%s: ctx is NULL", fn);
   ON_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
-  pr_online* o = new (std::nothrow) pr_online;
+  T* o = new (std::nothrow) T;
   if (!o) return fail(ctx, PR_ENOMEM, "out of host memory");
   o->ctx = ctx;
   pr::OnlineView& v = o->v;
   memset(&v, 0, sizeof v);
-  v.sig = buffers->sig; v.state = buffers->state;
-  v.type = type; v.capacity = capacity; v.max_k = max_k; v.NB = pr::online_blocks(capacity);
-  v.sig_doubles = type == PR_TYPE_SC ? 2400 : 4 * 384;
-  const size_t o_rows = 0, o_part = o_rows + up16((size_t)2 * capacity * 8), o_stats = o_part + up16((size_t)v.NB * 4 * 8), o_sig = o_stats + 32,
-               o_info = o_sig + up16((size_t)v.sig_doubles * 8), total = o_info + 16;
+  v.part[0] = p0; v.part[1] = p1; v.state = state;
+  v.len[0] = kind == pr::ONLINE_M2DP ? pr::ONLINE_M2DP_LEN : (kind == pr::ONLINE_DELIGHT ? pr::ONLINE_DELIGHT_LEN : pr::ONLINE_SC_LEN);
+  v.len[1] = kind == pr::ONLINE_FUSED ? pr::ONLINE_M2DP_LEN : 0;
+  v.kind = kind; v.capacity = capacity; v.max_k = max_k; v.NB = pr::online_blocks(kind, capacity);
+  const size_t C = (size_t)pr::online_channels(kind);
+  const size_t o_rows = 0, o_part = o_rows + up16(C * capacity * 8), o_stats = o_part + up16((size_t)v.NB * 2 * C * 8), o_sig = o_stats + 2 * C * 8,
+               o_info = o_sig + up16((size_t)(v.len[0] + v.len[1]) * 8), total = o_info + 16;
   hipError_t e = hipMalloc(&o->scratch, total);
   if (e != hipSuccess) {
     delete o;
-    return fail(ctx, e == hipErrorOutOfMemory ? PR_ENOMEM : PR_EHIP, "pr_online_create: scratch: %s", hipGetErrorString(e));
+    return fail(ctx, e == hipErrorOutOfMemory ? PR_ENOMEM : PR_EHIP, "%s: scratch: %s", fn, hipGetErrorString(e));
   }
   char* b = static_cast<char*>(o->scratch);
   v.rows = reinterpret_cast<double*>(b + o_rows); v.partial = reinterpret_cast<double*>(b + o_part); v.stats = reinterpret_cast<double*>(b + o_stats);
@@ -86,80 +83,181 @@ int pr_online_create(pr_ctx* ctx, int type, const pr_online_buffers* buffers, in
   if (e != hipSuccess) {
     (void)hipFree(o->scratch);
     delete o;
-    return fail(ctx, PR_EHIP, "pr_online_create: clearing the state failed: %s", hipGetErrorString(e));
+    return fail(ctx, PR_EHIP, "%s: clearing the state failed: %s", fn, hipGetErrorString(e));
   }
   *out = o;
   return PR_OK;
 }
 
-void pr_online_destroy(pr_online* o) {
+template <class T>
+void destroy(T* o) {
   if (!o) return;
   (void)hipSetDevice(pr::ctx_device(o->ctx));
   (void)hipStreamSynchronize(pr::ctx_stream(o->ctx));
-  (void)hipFree(o->scratch);            // the two buffers are the caller's
+  (void)hipFree(o->scratch);            // the buffers are the caller's
   delete o;
 }
 
-int pr_online_reset(pr_online* o) {
-  if (!o) return fail(nullptr, PR_EINVAL, "pr_online_reset: database is NULL");
+int no_handle(const char* fn, const char* noun) { return fail(nullptr, PR_EINVAL, "%s: %s is NULL", fn, noun); }
+
+int reset(OnlineCore* o, const char* fn, const char* noun) {
+  if (!o) return no_handle(fn, noun);
   ON_HIP(o->ctx, hipSetDevice(pr::ctx_device(o->ctx)));
   ON_HIP(o->ctx, hipMemsetAsync(o->v.state, 0, 4 * sizeof(int32_t), pr::ctx_stream(o->ctx)));
   return PR_OK;
 }
 
-int pr_online_count(pr_online* o, int32_t* count, int32_t* flags) {
-  if (!o) return fail(nullptr, PR_EINVAL, "pr_online_count: database is NULL");
-  if (!count || !flags) return fail(o->ctx, PR_EINVAL, "pr_online_count: a required pointer is NULL");
+int read_count(OnlineCore* o, const char* fn, const char* noun, int32_t* count, int32_t* flags) {
+  if (!o) return no_handle(fn, noun);
+  if (!count || !flags) return fail(o->ctx, PR_EINVAL, "%s: a required pointer is NULL", fn);
   ON_HIP(o->ctx, hipSetDevice(pr::ctx_device(o->ctx)));
   hipStream_t st = pr::ctx_stream(o->ctx);
   int32_t s[4];
   ON_HIP(o->ctx, hipMemcpyAsync(s, o->v.state, sizeof s, hipMemcpyDeviceToHost, st));
   ON_HIP(o->ctx, hipStreamSynchronize(st));
-  *count = s[0];
-  *flags = s[1];
+  *count = s[0]; *flags = s[1];
   return PR_OK;
 }
 
-int pr_online_match_dev(pr_online* o, const double* d_sig, const int32_t* d_emitted, int32_t mask_width, double p_weight, int32_t k,
-                        int32_t* d_idx, double* d_score, double* d_rows) {
-  // (the checks that need no handle come first: with o == NULL their text goes to pr_last_error(NULL))
+// The checks of a match that come before its pointers.  Those that need no handle come first: with o == NULL their text goes to pr_last_error(NULL).
+int check_match(const OnlineCore* o, const char* fn, const char* noun, int32_t mask_width, double p_weight, int32_t k) {
   pr_ctx* ctx = o ? o->ctx : nullptr;
-  if (mask_width < 0) return fail(ctx, PR_EINVAL, "pr_online_match_dev: mask_width=%d is negative", mask_width);
-  if (!std::isfinite(p_weight)) return fail(ctx, PR_EINVAL, "pr_online_match_dev: p_weight is not finite");
-  if (k < 1 || k > pr::ONLINE_MAX_K) return fail(ctx, PR_EINVAL, "pr_online_match_dev: k=%d outside 1 .. %d", k, pr::ONLINE_MAX_K);
-  if (!o) return fail(nullptr, PR_EINVAL, "pr_online_match_dev: database is NULL");
-  if (k > o->v.max_k) return fail(ctx, PR_EINVAL, "pr_online_match_dev: k=%d outside 1 .. max_k=%d", k, o->v.max_k);
-  if (!d_sig || !d_idx || !d_score) return fail(ctx, PR_EINVAL, "pr_online_match_dev: a required pointer is NULL (d_sig, d_idx, d_score)");
-  ON_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
-  pr::launch_online_match(pr::ctx_stream(ctx), o->v, d_sig, d_emitted, mask_width, p_weight, k, d_idx, d_score, d_rows ? d_rows : o->v.rows);
-  ON_HIP(ctx, hipGetLastError());
-  return PR_OK;
+  if (mask_width < 0) return fail(ctx, PR_EINVAL, "%s: mask_width=%d is negative", fn, mask_width);
+  if (!std::isfinite(p_weight)) return fail(ctx, PR_EINVAL, "%s: p_weight is not finite", fn);
+  if (k < 1 || k > pr::ONLINE_MAX_K) return fail(ctx, PR_EINVAL, "%s: k=%d outside 1 .. %d", fn, k, pr::ONLINE_MAX_K);
+  if (!o) return no_handle(fn, noun);
+  if (k > o->v.max_k) return fail(ctx, PR_EINVAL, "%s: k=%d outside 1 .. max_k=%d", fn, k, o->v.max_k);
+  return 0;
 }
 
-int pr_online_append_dev(pr_online* o, const double* d_sig, const int32_t* d_emitted, int32_t* d_info) {
-  if (!o) return fail(nullptr, PR_EINVAL, "pr_online_append_dev: database is NULL");
-  if (!d_sig || !d_info) return fail(o->ctx, PR_EINVAL, "pr_online_append_dev: a required pointer is NULL (d_sig, d_info)");
+int match(OnlineCore* o, const pr::OnlineParts& q, const int32_t* d_emitted, int32_t mask_width, double p_weight, int32_t k, int32_t* d_idx,
+          double* d_score, double* d_rows) {
   ON_HIP(o->ctx, hipSetDevice(pr::ctx_device(o->ctx)));
-  pr::launch_online_append(pr::ctx_stream(o->ctx), o->v, d_sig, d_emitted, d_info);
+  pr::launch_online_match(pr::ctx_stream(o->ctx), o->v, q, d_emitted, mask_width, p_weight, k, d_idx, d_score, d_rows ? d_rows : o->v.rows);
   ON_HIP(o->ctx, hipGetLastError());
   return PR_OK;
 }
 
-int pr_online_append(pr_online* o, const double* sig, int32_t* info) {
-  if (!o) return fail(nullptr, PR_EINVAL, "pr_online_append: database is NULL");
-  pr_ctx* ctx = o->ctx;
-  if (!sig || !info) return fail(ctx, PR_EINVAL, "pr_online_append: a required pointer is NULL (sig, info)");
-  ON_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
-  hipStream_t st = pr::ctx_stream(ctx);
-  hipError_t e = hipMemcpyAsync(o->stage_sig, sig, (size_t)o->v.sig_doubles * sizeof(double), hipMemcpyHostToDevice, st);
-  int rc = PR_OK;
-  if (e == hipSuccess) rc = pr_online_append_dev(o, o->stage_sig, nullptr, o->stage_info);
-  if (e == hipSuccess && rc == PR_OK) e = hipMemcpyAsync(info, o->stage_info, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, st);
-  const hipError_t e2 = hipStreamSynchronize(st);    // sig is in flight until here
-  if (rc != PR_OK) return rc;
-  ON_HIP(ctx, e);
-  ON_HIP(ctx, e2);
+int append_dev(OnlineCore* o, const pr::OnlineParts& src, const int32_t* d_emitted, int32_t* d_info) {
+  ON_HIP(o->ctx, hipSetDevice(pr::ctx_device(o->ctx)));
+  pr::launch_online_append(pr::ctx_stream(o->ctx), o->v, src, d_emitted, d_info);
+  ON_HIP(o->ctx, hipGetLastError());
   return PR_OK;
+}
+
+// The host form: the parts through stage_sig, the device path, info back; synchronises.
+int append_host(OnlineCore* o, const pr::OnlineParts& src, int32_t* info) {
+  ON_HIP(o->ctx, hipSetDevice(pr::ctx_device(o->ctx)));
+  hipStream_t st = pr::ctx_stream(o->ctx);
+  double* const stage[2] = {o->stage_sig, o->v.len[1] ? o->stage_sig + o->v.len[0] : nullptr};
+  hipError_t e = hipSuccess;
+  for (int p = 0; p < 2 && o->v.len[p] && e == hipSuccess; p++)
+    e = hipMemcpyAsync(stage[p], src.p[p], (size_t)o->v.len[p] * sizeof(double), hipMemcpyHostToDevice, st);
+  int rc = PR_OK;
+  if (e == hipSuccess) rc = append_dev(o, {{stage[0], stage[1]}}, nullptr, o->stage_info);
+  if (e == hipSuccess && rc == PR_OK) e = hipMemcpyAsync(info, o->stage_info, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, st);
+  const hipError_t e2 = hipStreamSynchronize(st);    // the host arrays are in flight until here
+  if (rc != PR_OK) return rc;
+  ON_HIP(o->ctx, e);
+  ON_HIP(o->ctx, e2);
+  return PR_OK;
+}
+
+// The parts a pr_onlineset call of this kind takes: FUSED needs sc and m2dp and no delight, DELIGHT the reverse.  0, or PR_EINVAL with the text set.
+int check_parts(pr_ctx* ctx, const char* fn, int kind, const void* sc, const void* m2dp, const void* delight, const char* prefix) {
+  if (kind == pr::ONLINE_FUSED) {
+    if (delight) return fail(ctx, PR_EINVAL, "%s: %sdelight must be NULL for a PR_ONLINESET_FUSED set", fn, prefix);
+    if (!sc || !m2dp) return fail(ctx, PR_EINVAL, "%s: a required pointer is NULL (%ssc, %sm2dp)", fn, prefix, prefix);
+  } else {
+    if (sc || m2dp) return fail(ctx, PR_EINVAL, "%s: %ssc and %sm2dp must be NULL for a PR_ONLINESET_DELIGHT set", fn, prefix, prefix);
+    if (!delight) return fail(ctx, PR_EINVAL, "%s: a required pointer is NULL (%sdelight)", fn, prefix);
+  }
+  return 0;
+}
+// (after check_parts) the set's parts in the view's order
+pr::OnlineParts set_parts(const double* sc, const double* m2dp, const double* delight) { return {{sc ? sc : delight, m2dp}}; }
+
+}  // namespace
+
+extern "C" {
+
+// In both creates the value checks come first and need no device: with ctx == NULL their text goes to pr_last_error(NULL).
+int pr_online_create(pr_ctx* ctx, int type, const pr_online_buffers* buffers, int32_t capacity, int32_t max_k, pr_online** out) {
+  if (!out) return fail(ctx, PR_EINVAL, "pr_online_create: out is NULL");
+  *out = nullptr;
+  if (!buffers) return fail(ctx, PR_EINVAL, "pr_online_create: buffers is NULL");
+  if (!buffers->sig || !buffers->state) return fail(ctx, PR_EINVAL, "pr_online_create: a buffer is NULL (sig, state)");
+  if (type != PR_TYPE_SC && type != PR_TYPE_M2DP) return fail(ctx, PR_EINVAL, "pr_online_create: type=%d is neither PR_TYPE_SC nor PR_TYPE_M2DP", type);
+  return create(ctx, "pr_online_create", type, buffers->sig, nullptr, buffers->state, capacity, max_k, out);
+}
+
+int pr_onlineset_create(pr_ctx* ctx, int kind, const pr_onlineset_buffers* buffers, int32_t capacity, int32_t max_k, pr_onlineset** out) {
+  if (!out) return fail(ctx, PR_EINVAL, "pr_onlineset_create: out is NULL");
+  *out = nullptr;
+  if (!buffers) return fail(ctx, PR_EINVAL, "pr_onlineset_create: buffers is NULL");
+  if (kind != PR_ONLINESET_FUSED && kind != PR_ONLINESET_DELIGHT)
+    return fail(ctx, PR_EINVAL, "pr_onlineset_create: kind=%d is neither PR_ONLINESET_FUSED nor PR_ONLINESET_DELIGHT", kind);
+  if (!buffers->state) return fail(ctx, PR_EINVAL, "pr_onlineset_create: a buffer is NULL (state)");
+  if (kind == PR_ONLINESET_FUSED) {
+    if (buffers->delight) return fail(ctx, PR_EINVAL, "pr_onlineset_create: buffer delight must be NULL for a PR_ONLINESET_FUSED set");
+    if (!buffers->sc || !buffers->m2dp) return fail(ctx, PR_EINVAL, "pr_onlineset_create: a buffer is NULL (sc, m2dp)");
+  } else {
+    if (buffers->sc || buffers->m2dp) return fail(ctx, PR_EINVAL, "pr_onlineset_create: buffers sc and m2dp must be NULL for a PR_ONLINESET_DELIGHT set");
+    if (!buffers->delight) return fail(ctx, PR_EINVAL, "pr_onlineset_create: a buffer is NULL (delight)");
+  }
+  return create(ctx, "pr_onlineset_create", pr::ONLINE_FUSED + kind, kind == PR_ONLINESET_FUSED ? buffers->sc : buffers->delight, buffers->m2dp,
+                buffers->state, capacity, max_k, out);
+}
+
+void pr_online_destroy(pr_online* o) { destroy(o); }
+void pr_onlineset_destroy(pr_onlineset* o) { destroy(o); }
+
+int pr_online_reset(pr_online* o) { return reset(o, "pr_online_reset", "database"); }
+int pr_onlineset_reset(pr_onlineset* o) { return reset(o, "pr_onlineset_reset", "set"); }
+
+int pr_online_count(pr_online* o, int32_t* count, int32_t* flags) { return read_count(o, "pr_online_count", "database", count, flags); }
+int pr_onlineset_count(pr_onlineset* o, int32_t* count, int32_t* flags) { return read_count(o, "pr_onlineset_count", "set", count, flags); }
+
+int pr_online_match_dev(pr_online* o, const double* d_sig, const int32_t* d_emitted, int32_t mask_width, double p_weight, int32_t k,
+                        int32_t* d_idx, double* d_score, double* d_rows) {
+  if (int rc = check_match(o, "pr_online_match_dev", "database", mask_width, p_weight, k)) return rc;
+  if (!d_sig || !d_idx || !d_score) return fail(o->ctx, PR_EINVAL, "pr_online_match_dev: a required pointer is NULL (d_sig, d_idx, d_score)");
+  return match(o, {{d_sig, nullptr}}, d_emitted, mask_width, p_weight, k, d_idx, d_score, d_rows);
+}
+
+int pr_onlineset_match_dev(pr_onlineset* o, const double* d_sc, const double* d_m2dp, const double* d_delight, const int32_t* d_emitted,
+                           int32_t mask_width, double p_weight, int32_t k, int32_t* d_idx, double* d_score, double* d_rows) {
+  if (int rc = check_match(o, "pr_onlineset_match_dev", "set", mask_width, p_weight, k)) return rc;
+  if (int rc = check_parts(o->ctx, "pr_onlineset_match_dev", o->v.kind, d_sc, d_m2dp, d_delight, "d_")) return rc;
+  if (!d_idx || !d_score) return fail(o->ctx, PR_EINVAL, "pr_onlineset_match_dev: a required pointer is NULL (d_idx, d_score)");
+  return match(o, set_parts(d_sc, d_m2dp, d_delight), d_emitted, mask_width, p_weight, k, d_idx, d_score, d_rows);
+}
+
+int pr_online_append_dev(pr_online* o, const double* d_sig, const int32_t* d_emitted, int32_t* d_info) {
+  if (!o) return no_handle("pr_online_append_dev", "database");
+  if (!d_sig || !d_info) return fail(o->ctx, PR_EINVAL, "pr_online_append_dev: a required pointer is NULL (d_sig, d_info)");
+  return append_dev(o, {{d_sig, nullptr}}, d_emitted, d_info);
+}
+
+int pr_onlineset_append_dev(pr_onlineset* o, const double* d_sc, const double* d_m2dp, const double* d_delight, const int32_t* d_emitted,
+                            int32_t* d_info) {
+  if (!o) return no_handle("pr_onlineset_append_dev", "set");
+  if (int rc = check_parts(o->ctx, "pr_onlineset_append_dev", o->v.kind, d_sc, d_m2dp, d_delight, "d_")) return rc;
+  if (!d_info) return fail(o->ctx, PR_EINVAL, "pr_onlineset_append_dev: a required pointer is NULL (d_info)");
+  return append_dev(o, set_parts(d_sc, d_m2dp, d_delight), d_emitted, d_info);
+}
+
+int pr_online_append(pr_online* o, const double* sig, int32_t* info) {
+  if (!o) return no_handle("pr_online_append", "database");
+  if (!sig || !info) return fail(o->ctx, PR_EINVAL, "pr_online_append: a required pointer is NULL (sig, info)");
+  return append_host(o, {{sig, nullptr}}, info);
+}
+
+int pr_onlineset_append(pr_onlineset* o, const double* sc, const double* m2dp, const double* delight, int32_t* info) {
+  if (!o) return no_handle("pr_onlineset_append", "set");
+  if (int rc = check_parts(o->ctx, "pr_onlineset_append", o->v.kind, sc, m2dp, delight, "")) return rc;
+  if (!info) return fail(o->ctx, PR_EINVAL, "pr_onlineset_append: a required pointer is NULL (info)");
+  return append_host(o, set_parts(sc, m2dp, delight), info);
 }
 
 }  // extern "C"

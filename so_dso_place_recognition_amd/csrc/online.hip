@@ -1,66 +1,109 @@
-// online.hip — the online signature database (no reference counterpart): the raw SC or M2DP rows of the keyframes seen so
-// far in a caller-owned buffer with a DEVICE-side count, matched exactly in fp64 and grown on the stream.  The sibling of map.hip for
-// signatures: every grid depends on the create sizes only, everything that varies (how many rows the database holds, whether the push
-// in front emitted at all) is read from device memory, so one captured match + append serves every keyframe.
-//   rows    NB workgroups: workgroup b takes entries b, b + NB, ... < count and both channels of each - the reference's own pair
-//           formulation (rerank_common.hpp: sc_pair_exact / m2dp_pair_exact, processSC.m:15-33 / processM2DP.m:12-22) - and ALWAYS
-//           writes its partial (entries that are not NaN, sum of d - 0.5) per channel, zeros included
-//   stats   one workgroup: the partials in workgroup order -> mean; a second pass over the row about that mean -> sd (N - 1, NaN left
-//           out: normalize(.,2)).  Deterministic: fixed lanes, fixed order.
-//   select  one workgroup: fused = p_weight z_p + z_i in xrow_select_kernel's operation order, +Inf under the mask (the query is row
-//           `count`), and the k smallest by (score, index) in k sweeps; NaN is never selected
-//   append  one workgroup: the row to `count`, then - behind its own barrier - state and info
-// No kernel waits for another workgroup: no atomics, no tickets.  Plain C++, vector stores only.
+// online.hip — the online engine (no reference counterpart): the raw signature rows of the keyframes seen so far in
+// caller-owned buffers with ONE DEVICE-side count, matched exactly in fp64 and grown on the stream.  Four kinds: SC and M2DP (pr_online),
+// FUSED = SC + M2DP in one selection (BASELINE config 5) and DELIGHT (pr_onlineset).  The sibling of map.hip for signatures: every grid
+// depends on the create sizes only; the count and whether the push in front emitted at all are read from device memory, so one captured
+// match + append serves every keyframe.  With C channels (SC 2, M2DP 2, FUSED 4, DELIGHT 1):
+//   rows    NB workgroups.  Z-scored kinds: workgroup b takes entries b, b + NB, ... < count and every channel of each - the reference's
+//           pair formulation (rerank_common.hpp: sc_pair_exact / m2dp_pair_exact; FUSED makes SC's calls and M2DP's, so the same bits) -
+//           and ALWAYS writes its partial (entries that are not NaN, sum of d - 0.5) per channel.  DELIGHT: batches of 16 entries
+//           through exact_batch (delight_exact.hpp: the text the DelightMatcher's exact rows use)
+//   stats   C > 1, one workgroup: the partials in workgroup order -> mean; a second pass about that mean -> sd (N - 1, NaN left out)
+//   select  one workgroup: f = 0; f += p_weight z_0; f += z_1; ... (the oracle's order), THEN +Inf under the mask (the query is row
+//           `count`; a masked NaN becomes a selectable +Inf), and the k smallest by (score, index) in k sweeps; NaN is never selected.
+//           DELIGHT: the distance is the score, no statistics (run_test.m:26-41), so one row is enough
+//   append  one workgroup: every part to row `count`, then - behind its own barrier - ONE thread commits state and info
+// No kernel waits for another workgroup: no atomics, no tickets.  Fixed-order reductions.  Plain C++, vector stores only.
 #include "online.hpp"
+#include "delight_exact.hpp"
 #include "rerank_common.hpp"
 
 namespace pr {
 namespace {
 
-__device__ __forceinline__ bool online_off(const int* emitted) { return emitted && emitted[0] == 0; }
+static_assert(ONLINE_NB == ONLINESET_NB_FUSED, "online_blocks() uses one number for the three z-scored kinds");
+__device__ __forceinline__ bool emitted_off(const int* emitted) { return emitted && emitted[0] == 0; }
 // a scribbled state word must not turn into a row outside the buffers
 __device__ __forceinline__ int online_count(const OnlineView& v) {
   const int n = v.state[0];
   return n < 0 ? 0 : (n > v.capacity ? v.capacity : n);
 }
+__device__ __forceinline__ bool sel_less(double av, int aj, double bv, int bj) { return av < bv || (av == bv && aj < bj); }
 
-template <bool SC>
-__global__ __launch_bounds__(256) void online_rows_kernel(OnlineView v, const double* __restrict__ sig, const int* __restrict__ emitted,
-                                                          double* __restrict__ rows) {
-  __shared__ double buf[SC ? 60 * 21 + 1200 : 1];
-  __shared__ double red[256];
-  if (online_off(emitted)) return;
+// The LDS of the z-scored rows kernels, at namespace scope: all three instantiations hand the pair functions the SAME two addresses, so
+// the compiler knows them inside sc_pair_exact / m2dp_pair_exact.  With arrays of its own in every instantiation the SC and FUSED kernels
+// need 28 and 12 more VGPRs (a wave per SIMD less each).  The M2DP kernel does not touch rows_buf: its LDS is rows_red alone, 2 048 B.
+__shared__ double rows_buf[60 * 21 + 1200];
+__shared__ double rows_red[256];
+
+// q0, q1: the query's parts in the view's order (q1 only for FUSED)
+template <bool SC, bool M2DP>
+__global__ __launch_bounds__(256) void online_rows_kernel(OnlineView v, const double* __restrict__ q0, const double* __restrict__ q1,
+                                                          const int* __restrict__ emitted, double* __restrict__ rows) {
+  constexpr int C = 2 * (SC + M2DP), M = SC ? 2 : 0;             // M: the first M2DP channel
+  if (emitted_off(emitted)) return;
   const int tid = threadIdx.x, b = blockIdx.x;
   const int n = online_count(v);
-  double c0 = 0.0, s0 = 0.0, c1 = 0.0, s1 = 0.0;
-  for (int j = b; j < n; j += v.NB) {                            // j < capacity: the rows of sig and both halves of rows exist
-    const double dp = SC ? sc_pair_exact(sig, 0, 0, v.sig, 0, (size_t)j * 2400, buf, red, tid)
-                         : m2dp_pair_exact(sig, 0, 0, v.sig, 0, (size_t)j * 1536, 0, red, tid);
-    const double di = SC ? sc_pair_exact(sig, 0, 1200, v.sig, 0, (size_t)j * 2400 + 1200, buf, red, tid)
-                         : m2dp_pair_exact(sig, 0, 0, v.sig, 0, (size_t)j * 1536, 1, red, tid);
-    if (tid == 0) { rows[j] = dp; rows[(size_t)v.capacity + j] = di; }      // (every thread holds the block-wide value)
-    if (dp == dp) { c0 += 1.0; s0 += dp - 0.5; }
-    if (di == di) { c1 += 1.0; s1 += di - 0.5; }
+  const double* qm = SC ? q1 : q0;
+  const double* dm = v.part[SC ? 1 : 0];
+  double cnt[C] = {}, sum[C] = {};
+  for (int j = b; j < n; j += v.NB) {                            // j < capacity: row j of every part and of every channel of rows exists
+    double d[C];
+    if constexpr (SC) {
+      d[0] = sc_pair_exact(q0, 0, 0, v.part[0], 0, (size_t)j * 2400, rows_buf, rows_red, tid);
+      d[1] = sc_pair_exact(q0, 0, 1200, v.part[0], 0, (size_t)j * 2400 + 1200, rows_buf, rows_red, tid);
+    }
+    if constexpr (M2DP) {
+      d[M] = m2dp_pair_exact(qm, 0, 0, dm, 0, (size_t)j * 1536, 0, rows_red, tid);
+      d[M + 1] = m2dp_pair_exact(qm, 0, 0, dm, 0, (size_t)j * 1536, 1, rows_red, tid);
+    }
+    if (tid == 0) {                                              // (every thread holds the block-wide value)
+#pragma unroll
+      for (int c = 0; c < C; c++) rows[(size_t)c * v.capacity + j] = d[c];
+    }
+#pragma unroll
+    for (int c = 0; c < C; c++)
+      if (d[c] == d[c]) { cnt[c] += 1.0; sum[c] += d[c] - 0.5; }
   }
   if (tid == 0) {
-    double* p = v.partial + (size_t)b * 4;                       // b < NB = the grid
-    p[0] = c0; p[1] = s0; p[2] = c1; p[3] = s1;
+    double* p = v.partial + (size_t)b * (2 * C);                 // b < NB = the grid
+#pragma unroll
+    for (int c = 0; c < C; c++) { p[2 * c] = cnt[c]; p[2 * c + 1] = sum[c]; }
   }
 }
 
-__global__ __launch_bounds__(256) void online_stats_kernel(OnlineView v, const int* __restrict__ emitted, const double* __restrict__ rows) {
-  __shared__ double tot[4];
-  __shared__ double red[4];
-  if (blockIdx.x != 0 || online_off(emitted)) return;
+__global__ __launch_bounds__(256) void online_delight_rows_kernel(OnlineView v, const double* __restrict__ sig, const int* __restrict__ emitted,
+                                                                  double* __restrict__ rows) {
+  __shared__ XShared sh;
+  __shared__ const double* pa[XB];
+  __shared__ const double* pb[XB];
+  __shared__ double dd[XB];
+  if (emitted_off(emitted)) return;
   const int tid = threadIdx.x;
   const int n = online_count(v);
-  if (tid < 4) {
+  for (int rb = blockIdx.x * XB; rb < n; rb += v.NB * XB) {      // uniform over the workgroup
+    const int np = n - rb < XB ? n - rb : XB;                    // rb + np <= n <= capacity
+    if (tid < XB) { pa[tid] = sig; pb[tid] = v.part[0] + (size_t)(rb + (tid < np ? tid : 0)) * 4096; }
+    __syncthreads();
+    exact_batch(sh, tid, np, pa, pb, dd);
+    if (tid < np) rows[rb + tid] = dd[tid];
+    __syncthreads();
+  }
+}
+
+template <int C>
+__global__ __launch_bounds__(256) void online_stats_kernel(OnlineView v, const int* __restrict__ emitted, const double* __restrict__ rows) {
+  __shared__ double tot[2 * C];
+  __shared__ double red[4];
+  if (blockIdx.x != 0 || emitted_off(emitted)) return;
+  const int tid = threadIdx.x;
+  const int n = online_count(v);
+  if (tid < 2 * C) {
     double s = 0.0;
-    for (int b = 0; b < v.NB; b++) s += v.partial[(size_t)b * 4 + tid];      // workgroup order: deterministic
+    for (int b = 0; b < v.NB; b++) s += v.partial[(size_t)b * (2 * C) + tid];      // workgroup order: deterministic
     tot[tid] = s;
   }
   __syncthreads();
-  for (int ch = 0; ch < 2; ch++) {
+  for (int ch = 0; ch < C; ch++) {
     const double N = tot[2 * ch], mean = 0.5 + tot[2 * ch + 1] / N;          // no entry: 0 / 0 = NaN
     const double* r = rows + (size_t)ch * v.capacity;
     double a = 0.0, c = 0.0;
@@ -68,16 +111,15 @@ __global__ __launch_bounds__(256) void online_stats_kernel(OnlineView v, const i
       const double d = r[j];
       if (d == d) { const double x = d - mean; a += x * x; c += x; }
     }
-    const double A = block_sum256(a, red, tid), C = block_sum256(c, red, tid);
+    const double A = block_sum256(a, red, tid), S = block_sum256(c, red, tid);
     if (tid == 0) {
       v.stats[2 * ch] = mean;
-      v.stats[2 * ch + 1] = sqrt((A - C * C / N) / (N - 1.0));               // one entry: 0 / 0 = NaN
+      v.stats[2 * ch + 1] = sqrt((A - S * S / N) / (N - 1.0));               // one entry: 0 / 0 = NaN
     }
   }
 }
 
-__device__ __forceinline__ bool sel_less(double av, int aj, double bv, int bj) { return av < bv || (av == bv && aj < bj); }
-
+template <int C>
 __global__ __launch_bounds__(256) void online_select_kernel(OnlineView v, const int* __restrict__ emitted, const double* __restrict__ rows,
                                                             int mask_width, double p_weight, int k, int* __restrict__ idx,
                                                             double* __restrict__ score) {
@@ -85,25 +127,27 @@ __global__ __launch_bounds__(256) void online_select_kernel(OnlineView v, const 
   __shared__ int ired[4];
   if (blockIdx.x != 0) return;
   const int tid = threadIdx.x;
-  if (online_off(emitted)) {
+  if (emitted_off(emitted)) {
     if (tid < k) { idx[tid] = -1; score[tid] = __builtin_nan(""); }          // k <= 128
     return;
   }
   const int n = online_count(v);
-  const int nn = n < 2 ? 0 : n;                                  // under two entries there are no row statistics: nothing is reported, masked or not
-  const double m0 = v.stats[0], sd0 = v.stats[1], m1 = v.stats[2], sd1 = v.stats[3];
-  const double* r0 = rows;
-  const double* r1 = rows + (size_t)v.capacity;
+  const int nn = C > 1 && n < 2 ? 0 : n;                         // z-scored, under two entries: no row statistics, nothing is reported, masked or not
+  double mean[C], sd[C];
+#pragma unroll
+  for (int c = 0; c < C; c++) { mean[c] = C > 1 ? v.stats[2 * c] : 0.0; sd[c] = C > 1 ? v.stats[2 * c + 1] : 1.0; }
+  const size_t cap = (size_t)v.capacity;
+  constexpr int U = C == 2 ? 4 : 2;                              // the unroll factor of the sweep
   double pv = -__builtin_inf();
   int pj = -1;
   for (int t = 0; t < k; t++) {
     double bv = __builtin_nan("");
     int bj = 0x7fffffff;
-#pragma unroll 4
+#pragma unroll U
     for (int j = tid; j < nn; j += 256) {
-      double f = 0.0;                                            // run_test.m:40 in xrow_select_kernel's operation order, then the mask (:47-53)
-      f += p_weight * ((r0[j] - m0) / sd0);
-      f += 1.0 * ((r1[j] - m1) / sd1);
+      double f = C == 1 ? rows[j] : 0.0;                         // C > 1: run_test.m:40 in the oracle's order of additions, then the mask (:47-53)
+#pragma unroll
+      for (int c = 0; C > 1 && c < C; c++) f += (c & 1 ? 1.0 : p_weight) * ((rows[c * cap + j] - mean[c]) / sd[c]);
       if (n - j < mask_width) f = __builtin_inf();               // the query is row n
       if (f != f || !sel_less(pv, pj, f, j)) continue;           // NaN, or selected already
       if (bj == 0x7fffffff || sel_less(f, j, bv, bj)) { bv = f; bj = j; }
@@ -119,19 +163,21 @@ __global__ __launch_bounds__(256) void online_select_kernel(OnlineView v, const 
   }
 }
 
-__global__ __launch_bounds__(256) void online_append_kernel(OnlineView v, const double* __restrict__ sig, const int* __restrict__ emitted,
-                                                            int* __restrict__ info) {
+__global__ __launch_bounds__(256) void online_append_kernel(OnlineView v, OnlineParts src, const int* __restrict__ emitted, int* __restrict__ info) {
   if (blockIdx.x != 0) return;
   const int tid = threadIdx.x;
   const int n = online_count(v);
   int flags = v.state[1] & ONLINE_OVERFLOW;
-  const bool off = online_off(emitted), store = !off && n < v.capacity;
-  if (store) {
-    double* dst = v.sig + (size_t)n * v.sig_doubles;             // row n < capacity
-    for (int i = tid; i < v.sig_doubles; i += 256) dst[i] = sig[i];
+  const bool off = emitted_off(emitted), store = !off && n < v.capacity;
+  if (store) {                                                   // row n < capacity of every part (len[1] = 0: there is no second)
+#pragma unroll
+    for (int p = 0; p < 2; p++) {
+      double* dst = v.part[p] + (size_t)n * v.len[p];
+      for (int i = tid; i < v.len[p]; i += 256) dst[i] = src.p[p][i];
+    }
   }
   __syncthreads();                                               // every thread has read state
-  if (tid == 0) {
+  if (tid == 0) {                                                // the ONE commit
     if (!off) {
       if (!store) flags |= ONLINE_OVERFLOW;
       v.state[0] = n + (store ? 1 : 0);
@@ -143,16 +189,25 @@ __global__ __launch_bounds__(256) void online_append_kernel(OnlineView v, const 
 
 }  // namespace
 
-void launch_online_match(hipStream_t st, const OnlineView& v, const double* sig, const int* emitted, int mask_width, double p_weight, int k,
+void launch_online_match(hipStream_t st, const OnlineView& v, const OnlineParts& q, const int* emitted, int mask_width, double p_weight, int k,
                          int* idx, double* score, double* rows) {
-  if (v.type == 0) hipLaunchKernelGGL(online_rows_kernel<true>, dim3(v.NB), dim3(256), 0, st, v, sig, emitted, rows);
-  else hipLaunchKernelGGL(online_rows_kernel<false>, dim3(v.NB), dim3(256), 0, st, v, sig, emitted, rows);
-  hipLaunchKernelGGL(online_stats_kernel, dim3(1), dim3(256), 0, st, v, emitted, (const double*)rows);
-  hipLaunchKernelGGL(online_select_kernel, dim3(1), dim3(256), 0, st, v, emitted, (const double*)rows, mask_width, p_weight, k, idx, score);
+  const dim3 grid(v.NB), one(1), block(256);
+  const double* r = rows;
+  switch (v.kind) {
+    case ONLINE_SC: hipLaunchKernelGGL((online_rows_kernel<true, false>), grid, block, 0, st, v, q.p[0], q.p[1], emitted, rows); break;
+    case ONLINE_M2DP: hipLaunchKernelGGL((online_rows_kernel<false, true>), grid, block, 0, st, v, q.p[0], q.p[1], emitted, rows); break;
+    case ONLINE_FUSED: hipLaunchKernelGGL((online_rows_kernel<true, true>), grid, block, 0, st, v, q.p[0], q.p[1], emitted, rows); break;
+    default: hipLaunchKernelGGL(online_delight_rows_kernel, grid, block, 0, st, v, q.p[0], emitted, rows); break;
+  }
+  if (v.kind == ONLINE_FUSED) hipLaunchKernelGGL(online_stats_kernel<4>, one, block, 0, st, v, emitted, r);
+  else if (v.kind != ONLINE_DELIGHT) hipLaunchKernelGGL(online_stats_kernel<2>, one, block, 0, st, v, emitted, r);
+  if (v.kind == ONLINE_FUSED) hipLaunchKernelGGL(online_select_kernel<4>, one, block, 0, st, v, emitted, r, mask_width, p_weight, k, idx, score);
+  else if (v.kind == ONLINE_DELIGHT) hipLaunchKernelGGL(online_select_kernel<1>, one, block, 0, st, v, emitted, r, mask_width, p_weight, k, idx, score);
+  else hipLaunchKernelGGL(online_select_kernel<2>, one, block, 0, st, v, emitted, r, mask_width, p_weight, k, idx, score);
 }
 
-void launch_online_append(hipStream_t st, const OnlineView& v, const double* sig, const int* emitted, int* info) {
-  hipLaunchKernelGGL(online_append_kernel, dim3(1), dim3(256), 0, st, v, sig, emitted, info);
+void launch_online_append(hipStream_t st, const OnlineView& v, const OnlineParts& src, const int* emitted, int* info) {
+  hipLaunchKernelGGL(online_append_kernel, dim3(1), dim3(256), 0, st, v, src, emitted, info);
 }
 
 }  // namespace pr

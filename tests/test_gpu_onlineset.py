@@ -1,4 +1,4 @@
-"""The online signature sets on the device (pr_onlineset, onlineset.hip): a FUSED (SC + M2DP) and a DELIGHT match against
+"""The online signature sets on the device (pr_onlineset, online.hip): a FUSED (SC + M2DP) and a DELIGHT match against
 the rows held so far equal the NumPy model over the oracle (onlineset_model.py) at the kernels' edges and through the reference's corner
 rules; the fused rows are the bits two pr_online databases give; the fused result agrees with FusedMatcher; the append rule - ONE count,
 every part on the same row or no part at all - equals the model with guard words behind every buffer; ONE captured step serves a growing
