@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/place_recognition.h"
+#include "host_common.hpp"
 #include "kernels.hpp"
 
 namespace pr {
@@ -50,23 +51,7 @@ int herr(int code, const char* fmt, ...) {
   return code;
 }
 
-int fail(pr_ctx* ctx, int code, const char* fmt, ...) __attribute__((format(printf, 3, 4)));
-int fail(pr_ctx* ctx, int code, const char* fmt, ...) {
-  char b[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(b, sizeof b, fmt, ap);
-  va_end(ap);
-  pr::ctx_set_error(ctx, b);
-  return code;
-}
-
-#define BOW_HIP(ctx, call)                                                                                        \
-  do {                                                                                                            \
-    hipError_t _e = (call);                                                                                       \
-    if (_e != hipSuccess)                                                                                         \
-      return fail(ctx, _e == hipErrorOutOfMemory ? PR_ENOMEM : PR_EHIP, "%s failed: %s", #call, hipGetErrorString(_e)); \
-  } while (0)
+using pr::fail;
 
 int check_header(int32_t k, int32_t L, int32_t scoring, int32_t weighting) {   // :1360-1364
   if (k < 0 || k > 20 || L < 1 || L > 10 || scoring < 0 || scoring > 5 || weighting < 0 || weighting > 3)
@@ -455,21 +440,21 @@ int generate_dev(pr_ctx* ctx, const pr_bow_vocab* vocab, const uint8_t* desc, in
   if (n_desc > 0 && !desc) return fail(ctx, PR_EINVAL, "pr_bow_generate_dev: desc is NULL");
   if (reinterpret_cast<uintptr_t>(desc) % 16) return fail(ctx, PR_EINVAL, "pr_bow_generate_dev: desc must be 16-byte aligned");
   if (N == 0 && n_desc == 0) return PR_OK;
-  BOW_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
+  PR_CHECK_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
   BowState* st = state(ctx);
   hipStream_t s = pr::ctx_stream(ctx);
   if (vocab->n_words == 0) {                     // transform returns an empty vector at once (:1135-1138)
     if (feat_words) pr::launch_bow_fill_words(s, feat_words, n_desc, -1);
     pr::launch_bow_aggregate(s, offs, N, n_desc, nullptr, nullptr, nullptr, vocab->weighting, vocab->scoring, cols, nullptr, nullptr,
                              nullptr, out, n_words, flag);
-    BOW_HIP(ctx, hipGetLastError());
+    PR_CHECK_HIP(ctx, hipGetLastError());
     return PR_OK;
   }
   const DevVocab* dv = nullptr;
   if (int rc = device_vocab(ctx, st, vocab, &dv)) return rc;
   if (n_desc > st->cap) {                        // grow-only: a later call of at most this size allocates nothing
     if (st->node) {
-      BOW_HIP(ctx, hipStreamSynchronize(s));
+      PR_CHECK_HIP(ctx, hipStreamSynchronize(s));
       free_scratch(st);
     }
     hipError_t e = hipMalloc(&st->node, (size_t)n_desc * sizeof(int));
@@ -485,7 +470,7 @@ int generate_dev(pr_ctx* ctx, const pr_bow_vocab* vocab, const uint8_t* desc, in
   pr::launch_bow_descend(s, desc, n_desc, dv->desc, dv->child, dv->word, st->lanes, st->node, feat_words);
   pr::launch_bow_aggregate(s, offs, N, n_desc, st->node, dv->word, dv->weight, vocab->weighting, vocab->scoring, cols, st->wgt, st->vals,
                            st->gkeys, out, n_words, flag);
-  BOW_HIP(ctx, hipGetLastError());
+  PR_CHECK_HIP(ctx, hipGetLastError());
   return PR_OK;
 }
 
@@ -509,7 +494,7 @@ int pr_bow_generate(pr_ctx* ctx, const pr_bow_vocab* vocab, const uint8_t* desc,
   const int64_t F = offs[N];
   if (F >= (1LL << 31)) return fail(ctx, PR_EINVAL, "pr_bow_generate: %lld descriptors in one call (at most 2^31 - 1)", (long long)F);
   if (F > 0 && !desc) return fail(ctx, PR_EINVAL, "pr_bow_generate: desc is NULL");
-  BOW_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
+  PR_CHECK_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
   hipStream_t s = pr::ctx_stream(ctx);
   const size_t out_bytes = (size_t)2 * N * cols * sizeof(double);
   uint8_t* ddesc = nullptr;

@@ -5,14 +5,11 @@
 #include <algorithm>
 #include <climits>
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <utility>
 
-#include "../../include/place_recognition.h"
-#include "kernels.hpp"
+#include "resident_match.hpp"
 
 typedef unsigned long long u64;
 
@@ -37,23 +34,7 @@ struct pr_bow_db {
 
 namespace {
 
-int fail(pr_ctx* ctx, int code, const char* fmt, ...) __attribute__((format(printf, 3, 4)));
-int fail(pr_ctx* ctx, int code, const char* fmt, ...) {
-  char b[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(b, sizeof b, fmt, ap);
-  va_end(ap);
-  pr::ctx_set_error(ctx, b);
-  return code;
-}
-
-#define BM_HIP(ctx, call)                                                                                         \
-  do {                                                                                                            \
-    hipError_t _e = (call);                                                                                       \
-    if (_e != hipSuccess)                                                                                         \
-      return fail(ctx, _e == hipErrorOutOfMemory ? PR_ENOMEM : PR_EHIP, "%s failed: %s", #call, hipGetErrorString(_e)); \
-  } while (0)
+using pr::fail;
 
 constexpr size_t SCRATCH_BYTES = (size_t)512 << 20;   // accumulators of one chunk
 constexpr int MAX_WORDS = 1 << 26;                   // vocabulary size limit (64-bit offsets: 512 MB per offset array)
@@ -97,15 +78,15 @@ struct DevTmp {
 int check_rows(pr_ctx* ctx, pr_bow_db* db, const double* drows, int n, int row_name0, bool counts, int64_t* posts, int* bad) {
   hipStream_t st = pr::ctx_stream(ctx);
   const int none = INT_MAX;
-  if (counts) BM_HIP(ctx, hipMemsetAsync(db->counts, 0, (size_t)db->n_words * sizeof(int), st));
-  BM_HIP(ctx, hipMemsetAsync(db->stat, 0, sizeof(u64), st));
-  BM_HIP(ctx, hipMemcpyAsync(db->stat + 1, &none, sizeof(int), hipMemcpyHostToDevice, st));
+  if (counts) PR_CHECK_HIP(ctx, hipMemsetAsync(db->counts, 0, (size_t)db->n_words * sizeof(int), st));
+  PR_CHECK_HIP(ctx, hipMemsetAsync(db->stat, 0, sizeof(u64), st));
+  PR_CHECK_HIP(ctx, hipMemcpyAsync(db->stat + 1, &none, sizeof(int), hipMemcpyHostToDevice, st));
   pr::launch_bow_rows_check(st, drows, n, db->cols, db->n_words, row_name0, counts ? db->counts : nullptr, db->stat,
                             reinterpret_cast<int*>(db->stat + 1));
-  BM_HIP(ctx, hipGetLastError());
+  PR_CHECK_HIP(ctx, hipGetLastError());
   u64 h[2];
-  BM_HIP(ctx, hipMemcpyAsync(h, db->stat, sizeof h, hipMemcpyDeviceToHost, st));
-  BM_HIP(ctx, hipStreamSynchronize(st));
+  PR_CHECK_HIP(ctx, hipMemcpyAsync(h, db->stat, sizeof h, hipMemcpyDeviceToHost, st));
+  PR_CHECK_HIP(ctx, hipStreamSynchronize(st));
   *posts = (int64_t)h[0];
   int b;
   memcpy(&b, &h[1], sizeof b);
@@ -118,7 +99,7 @@ int scatter_rows(pr_ctx* ctx, pr_bow_db* db, const double* drows, int n, int j0,
   hipStream_t st = pr::ctx_stream(ctx);
   pr::launch_bow_scan(st, db->counts, db->n_words, db->tsum, off, db->cursor);
   pr::launch_bow_scatter(st, drows, n, db->cols, j0, db->cursor, prow, pw);
-  BM_HIP(ctx, hipGetLastError());
+  PR_CHECK_HIP(ctx, hipGetLastError());
   return PR_OK;
 }
 
@@ -142,7 +123,7 @@ int fold(pr_ctx* ctx, pr_bow_db* db) {
   hipStream_t st = pr::ctx_stream(ctx);
   if (db->tail_rows == 0) return PR_OK;
   pr::launch_bow_fold(st, db->n_words, db->moff, db->mrow, db->mw, db->toff, db->trow, db->tw, db->moff2, db->mrow2, db->mw2);
-  BM_HIP(ctx, hipGetLastError());
+  PR_CHECK_HIP(ctx, hipGetLastError());
   std::swap(db->moff, db->moff2);
   std::swap(db->mrow, db->mrow2);
   std::swap(db->mw, db->mw2);
@@ -150,7 +131,7 @@ int fold(pr_ctx* ctx, pr_bow_db* db) {
   db->main_post += db->tail_post;
   db->tail_rows = 0;
   db->tail_post = 0;
-  BM_HIP(ctx, hipMemsetAsync(db->toff, 0, ((size_t)db->n_words + 1) * sizeof(u64), st));
+  PR_CHECK_HIP(ctx, hipMemsetAsync(db->toff, 0, ((size_t)db->n_words + 1) * sizeof(u64), st));
   return PR_OK;
 }
 
@@ -164,7 +145,7 @@ int launch_match(pr_ctx* ctx, const pr_bow_db* db, const double* q, int32_t m, i
                          db->toff, db->trow, db->tw, n, db_row0, mask_width, k, db->acc, idx + (size_t)c0 * k, score + (size_t)c0 * k,
                          pr::ctx_bow_rows_flag(ctx));
   }
-  BM_HIP(ctx, hipGetLastError());
+  PR_CHECK_HIP(ctx, hipGetLastError());
   return PR_OK;
 }
 
@@ -208,7 +189,7 @@ int create_db(pr_ctx* ctx, int32_t max_sigs, int32_t cols, int32_t n_words, int6
     return fail(ctx, PR_EINVAL, "pr_bow_db_create: bad arguments (max_sigs=%d, cols=%d, n_words=%d, max_postings=%lld; 1 <= n_words <= %d)",
                 max_sigs, cols, n_words, (long long)max_postings, MAX_WORDS);
   *out = nullptr;
-  BM_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
+  PR_CHECK_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
   pr_bow_db* db = new pr_bow_db;
   db->device = pr::ctx_device(ctx);
   db->max_sigs = max_sigs; db->cols = cols; db->n_words = n_words; db->max_postings = max_postings;
@@ -231,7 +212,7 @@ int create_db(pr_ctx* ctx, int32_t max_sigs, int32_t cols, int32_t n_words, int6
   if (e == hipSuccess) e = hipMemset(db->toff, 0, nw1 * sizeof(u64));
   if (e != hipSuccess) {
     release(db);
-    return fail(ctx, e == hipErrorOutOfMemory ? PR_ENOMEM : PR_EHIP, "pr_bow_db_create: device allocation failed (%s)", hipGetErrorString(e));
+    return fail(ctx, pr::hip_code(e), "pr_bow_db_create: device allocation failed (%s)", hipGetErrorString(e));
   }
   *out = db;
   return PR_OK;
@@ -270,14 +251,14 @@ int set_rows(pr_ctx* ctx, const char* fn, pr_bow_db* db, const double* rows, int
   if (!db || n < 0 || (n > 0 && !rows) || (where != PR_HOST && where != PR_DEVICE))
     return fail(ctx, PR_EINVAL, "%s: bad arguments (n=%d, where=%d)", fn, n, where);
   if (n > db->max_sigs) return fail(ctx, PR_ENOMEM, "%s: %d rows exceed the capacity of %d", fn, n, db->max_sigs);
-  BM_HIP(ctx, hipSetDevice(db->device));
+  PR_CHECK_HIP(ctx, hipSetDevice(db->device));
   hipStream_t st = pr::ctx_stream(ctx);
   DevTmp tmp;
   const double* d = rows;
   if (where == PR_HOST && n > 0) {
     const size_t bytes = (size_t)2 * n * db->cols * sizeof(double);
-    BM_HIP(ctx, hipMalloc(&tmp.p, bytes));
-    BM_HIP(ctx, hipMemcpyAsync(tmp.p, rows, bytes, hipMemcpyHostToDevice, st));
+    PR_CHECK_HIP(ctx, hipMalloc(&tmp.p, bytes));
+    PR_CHECK_HIP(ctx, hipMemcpyAsync(tmp.p, rows, bytes, hipMemcpyHostToDevice, st));
     d = static_cast<const double*>(tmp.p);
   }
   int64_t posts = 0;
@@ -287,10 +268,10 @@ int set_rows(pr_ctx* ctx, const char* fn, pr_bow_db* db, const double* rows, int
   if (posts > db->max_postings)
     return fail(ctx, PR_ENOMEM, "%s: %lld postings exceed the capacity of %lld", fn, (long long)posts, (long long)db->max_postings);
   if (int rc = scatter_rows(ctx, db, d, n, 0, db->moff, db->mrow, db->mw)) return rc;
-  BM_HIP(ctx, hipMemsetAsync(db->toff, 0, ((size_t)db->n_words + 1) * sizeof(u64), st));
+  PR_CHECK_HIP(ctx, hipMemsetAsync(db->toff, 0, ((size_t)db->n_words + 1) * sizeof(u64), st));
   db->main_rows = n; db->main_post = posts;
   db->tail_rows = 0; db->tail_post = 0;
-  BM_HIP(ctx, hipStreamSynchronize(st));
+  PR_CHECK_HIP(ctx, hipStreamSynchronize(st));
   return PR_OK;
 }
 
@@ -307,14 +288,14 @@ int pr_bow_db_append(pr_ctx* ctx, pr_bow_db* db, const double* rows, int where, 
   const int32_t count = db->main_rows + db->tail_rows;
   if (n_new > db->max_sigs - count)
     return fail(ctx, PR_ENOMEM, "pr_bow_db_append: %d + %d rows exceed the capacity of %d", count, n_new, db->max_sigs);
-  BM_HIP(ctx, hipSetDevice(db->device));
+  PR_CHECK_HIP(ctx, hipSetDevice(db->device));
   hipStream_t st = pr::ctx_stream(ctx);
   const size_t row2 = (size_t)2 * db->cols;
   DevTmp tmp;
   const double* d = rows;
   if (where == PR_HOST) {
-    BM_HIP(ctx, hipMalloc(&tmp.p, row2 * n_new * sizeof(double)));
-    BM_HIP(ctx, hipMemcpyAsync(tmp.p, rows, row2 * n_new * sizeof(double), hipMemcpyHostToDevice, st));
+    PR_CHECK_HIP(ctx, hipMalloc(&tmp.p, row2 * n_new * sizeof(double)));
+    PR_CHECK_HIP(ctx, hipMemcpyAsync(tmp.p, rows, row2 * n_new * sizeof(double), hipMemcpyHostToDevice, st));
     d = static_cast<const double*>(tmp.p);
   }
   int64_t posts = 0;
@@ -328,12 +309,12 @@ int pr_bow_db_append(pr_ctx* ctx, pr_bow_db* db, const double* rows, int where, 
     if (db->tail_rows == db->tail_cap)
       if (int rc = fold(ctx, db)) return rc;
     const int32_t piece = std::min(n_new - r0, db->tail_cap - db->tail_rows);
-    BM_HIP(ctx, hipMemcpyAsync(db->traw + row2 * db->tail_rows, d + row2 * r0, row2 * piece * sizeof(double), hipMemcpyDeviceToDevice, st));
+    PR_CHECK_HIP(ctx, hipMemcpyAsync(db->traw + row2 * db->tail_rows, d + row2 * r0, row2 * piece * sizeof(double), hipMemcpyDeviceToDevice, st));
     db->tail_rows += piece;
     r0 += piece;
     if (int rc = rebuild_tail(ctx, db)) return rc;
   }
-  BM_HIP(ctx, hipStreamSynchronize(st));
+  PR_CHECK_HIP(ctx, hipStreamSynchronize(st));
   return PR_OK;
 }
 
@@ -343,7 +324,7 @@ int pr_bow_match_topk_dev(pr_ctx* ctx, const pr_bow_db* db, const double* q, int
   if (!db || m < 0 || k < 1 || k > 128 || (m > 0 && (!q || !idx || !score)))
     return fail(ctx, PR_EINVAL, "pr_bow_match_topk_dev: bad arguments (m=%d, k=%d; 1 <= k <= 128)", m, k);
   if (m == 0) return PR_OK;
-  BM_HIP(ctx, hipSetDevice(db->device));
+  PR_CHECK_HIP(ctx, hipSetDevice(db->device));
   return launch_match(ctx, db, q, m, q_row0, db_row0, mask_width, k, idx, score);
 }
 
@@ -353,29 +334,11 @@ int pr_bow_match_topk_f64(pr_ctx* ctx, const double* h1, int32_t m, const double
   if (m < 0 || n < 0 || cols < 1 || k < 1 || k > 128 || (m > 0 && (!h1 || !idx || !score)) || (n > 0 && !h2) || m > PR_MAX_SIGS || n > PR_MAX_SIGS)
     return fail(ctx, PR_EINVAL, "pr_bow_match_topk_f64: bad arguments (m=%d, n=%d, cols=%d, k=%d; 1 <= k <= 128)", m, n, cols, k);
   if (m == 0) return PR_OK;
-  BM_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
+  PR_CHECK_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
   pr_bow_db* db = nullptr;
   if (int rc = host_db(ctx, "pr_bow_match_topk_f64", h1, m, h2, n, cols, m, &db)) return rc;
-  hipStream_t st = pr::ctx_stream(ctx);
-  void *dq = nullptr, *di = nullptr, *ds = nullptr;
-  int rc = PR_OK;
-  const size_t qb = (size_t)2 * m * cols * sizeof(double);
-  hipError_t e = hipMalloc(&dq, qb);
-  if (e == hipSuccess) e = hipMalloc(&di, (size_t)m * k * sizeof(int32_t));
-  if (e == hipSuccess) e = hipMalloc(&ds, (size_t)m * k * sizeof(double));
-  if (e == hipSuccess) e = hipMemcpyAsync(dq, h1, qb, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) {
-    rc = launch_match(ctx, db, static_cast<double*>(dq), m, 0, 0, mask_width, k, static_cast<int32_t*>(di), static_cast<double*>(ds));
-    if (rc == PR_OK) {
-      e = hipMemcpyAsync(idx, di, (size_t)m * k * sizeof(int32_t), hipMemcpyDeviceToHost, st);
-      if (e == hipSuccess) e = hipMemcpyAsync(score, ds, (size_t)m * k * sizeof(double), hipMemcpyDeviceToHost, st);
-      if (e == hipSuccess) e = hipStreamSynchronize(st);
-    }
-  }
-  if (e != hipSuccess && rc == PR_OK)
-    rc = fail(ctx, e == hipErrorOutOfMemory ? PR_ENOMEM : PR_EHIP, "pr_bow_match_topk_f64: %s", hipGetErrorString(e));
-  (void)hipStreamSynchronize(st);
-  for (void* p : {dq, di, ds}) if (p) (void)hipFree(p);
+  const int rc = pr::resident::host_topk(ctx, "pr_bow_match_topk_f64", h1, (size_t)2 * m * cols * sizeof(double), m, k, idx, score,
+                                        [&](const double* dq, int32_t* di, double* ds) { return launch_match(ctx, db, dq, m, 0, 0, mask_width, k, di, ds); });
   pr_bow_db_destroy(ctx, db);
   return rc;
 }
@@ -385,7 +348,7 @@ int pr_bow_distance_f64(pr_ctx* ctx, const double* h1, int32_t m, const double* 
   if (m < 0 || n < 0 || cols < 1 || (m > 0 && !h1) || (n > 0 && !h2) || (m > 0 && n > 0 && !dist) || m > PR_MAX_SIGS || n > PR_MAX_SIGS)
     return fail(ctx, PR_EINVAL, "pr_bow_distance_f64: bad arguments (m=%d, n=%d, cols=%d)", m, n, cols);
   if (m == 0) return PR_OK;
-  BM_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
+  PR_CHECK_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
   pr_bow_db* db = nullptr;
   if (int rc = host_db(ctx, "pr_bow_distance_f64", h1, m, h2, n, cols, 1 /* its matrix is the scratch */, &db)) return rc;
   if (n == 0) { pr_bow_db_destroy(ctx, db); return PR_OK; }
@@ -404,7 +367,7 @@ int pr_bow_distance_f64(pr_ctx* ctx, const double* h1, int32_t m, const double* 
     if (e == hipSuccess) e = hipMemcpyAsync(dist, dd, (size_t)m * n * sizeof(double), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
   }
-  if (e != hipSuccess) rc = fail(ctx, e == hipErrorOutOfMemory ? PR_ENOMEM : PR_EHIP, "pr_bow_distance_f64: %s", hipGetErrorString(e));
+  if (e != hipSuccess) rc = fail(ctx, pr::hip_code(e), "pr_bow_distance_f64: %s", hipGetErrorString(e));
   (void)hipStreamSynchronize(st);
   for (void* p : {dq, dd}) if (p) (void)hipFree(p);
   pr_bow_db_destroy(ctx, db);

@@ -3,12 +3,12 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
 
 #include "../../include/place_recognition.h"
+#include "host_common.hpp"
 #include "kernels.hpp"
 
 namespace {
@@ -21,23 +21,7 @@ struct EvalState {
   Buf part_d, part_j, min_d, min_j, loc, bsum, cnt, rank, bidx, cls, prec, rec, term;
 };
 
-int fail(pr_ctx* ctx, int code, const char* fmt, ...) __attribute__((format(printf, 3, 4)));
-int fail(pr_ctx* ctx, int code, const char* fmt, ...) {
-  char b[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(b, sizeof b, fmt, ap);
-  va_end(ap);
-  pr::ctx_set_error(ctx, b);
-  return code;
-}
-
-#define EV_HIP(ctx, call)                                                                                         \
-  do {                                                                                                            \
-    hipError_t _e = (call);                                                                                       \
-    if (_e != hipSuccess)                                                                                         \
-      return fail(ctx, _e == hipErrorOutOfMemory ? PR_ENOMEM : PR_EHIP, "%s failed: %s", #call, hipGetErrorString(_e)); \
-  } while (0)
+using pr::fail;
 
 EvalState* state(pr_ctx* ctx) {
   void*& slot = pr::ctx_eval(ctx);
@@ -50,11 +34,11 @@ int grow(pr_ctx* ctx, Buf& b, size_t bytes) {
   bytes = std::max<size_t>(bytes, 64);
   if (b.cap >= bytes) return PR_OK;
   if (b.p) {
-    EV_HIP(ctx, hipStreamSynchronize(pr::ctx_stream(ctx)));
+    PR_CHECK_HIP(ctx, hipStreamSynchronize(pr::ctx_stream(ctx)));
     (void)hipFree(b.p);
     b.p = nullptr; b.cap = 0;
   }
-  EV_HIP(ctx, hipMalloc(&b.p, bytes));
+  PR_CHECK_HIP(ctx, hipMalloc(&b.p, bytes));
   b.cap = bytes;
   return PR_OK;
 }
@@ -102,7 +86,7 @@ int gt_run(pr_ctx* ctx, EvalState* S, const double* gt1, int m, const double* gt
     if (int rc = grow(ctx, S->bsum, (2 * nb + 2) * 4)) return rc;
     pr::launch_eval_gt_pairs(st, min_d, min_j, m, thr, ptr<int>(S->loc), ptr<int>(S->bsum), lp_gt, n_gt);
   }
-  EV_HIP(ctx, hipGetLastError());
+  PR_CHECK_HIP(ctx, hipGetLastError());
   return PR_OK;
 }
 
@@ -166,7 +150,7 @@ int pr_ground_truth_pairs_dev(pr_ctx* ctx, const double* d_gt1, int32_t m, const
   if (int rc = check_shapes(ctx, "pr_ground_truth_pairs_dev", m, n, cols)) return rc;
   if ((m > 0 && !d_gt1) || (m > 0 && n > 0 && !d_gt2)) return fail(ctx, PR_EINVAL, "pr_ground_truth_pairs_dev: gt1 / gt2 is NULL");
   if (!ctx) return fail(ctx, PR_EINVAL, "pr_ground_truth_pairs_dev: ctx is NULL");
-  EV_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
+  PR_CHECK_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
   return gt_run(ctx, state(ctx), d_gt1, m, d_gt2, n, cols, loop_diff * loop_diff, clamp_mask(mask_width), d_min_j, d_min_d, d_lp_gt, d_n_gt);
 }
 
@@ -178,7 +162,7 @@ int pr_precision_recall_dev(pr_ctx* ctx, const double* d_diff_v, const int32_t* 
   if (!d_scalars || (m > 0 && (!d_diff_v || !d_diff_idx || !d_gt1)) || (m > 0 && n > 0 && !d_gt2))
     return fail(ctx, PR_EINVAL, "pr_precision_recall_dev: a required pointer is NULL");
   if (!ctx) return fail(ctx, PR_EINVAL, "pr_precision_recall_dev: ctx is NULL");
-  EV_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
+  PR_CHECK_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
   EvalState* S = state(ctx);
   pr::EvalScalars* scal = static_cast<pr::EvalScalars*>(d_scalars);
   const double thr = loop_diff * loop_diff;
@@ -192,7 +176,7 @@ int pr_precision_recall_dev(pr_ctx* ctx, const double* d_diff_v, const int32_t* 
   pr::launch_eval_sweep(pr::ctx_stream(ctx), d_diff_v, d_diff_idx, ld, m, d_gt1, d_gt2, n, cols, thr, ptr<int>(S->cnt), ptr<int>(S->rank),
                         ptr<int>(S->bidx), ptr<int>(S->cls), ptr<int>(S->loc), ptr<int>(S->bsum), d_precision, d_recall, ptr<double>(S->term),
                         scal, d_lp_detected);
-  EV_HIP(ctx, hipGetLastError());
+  PR_CHECK_HIP(ctx, hipGetLastError());
   return PR_OK;
 }
 
@@ -200,11 +184,11 @@ int pr_trapz_dev(pr_ctx* ctx, const double* d_recall, const double* d_precision,
   if (m < 0 || m > PR_MAX_SIGS) return fail(ctx, PR_EINVAL, "pr_trapz_dev: m=%d outside 0..%d", m, PR_MAX_SIGS);
   if (!d_auc || (m > 0 && (!d_recall || !d_precision))) return fail(ctx, PR_EINVAL, "pr_trapz_dev: a required pointer is NULL");
   if (!ctx) return fail(ctx, PR_EINVAL, "pr_trapz_dev: ctx is NULL");
-  EV_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
+  PR_CHECK_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
   EvalState* S = state(ctx);
   if (int rc = grow(ctx, S->term, (size_t)m * 8)) return rc;
   pr::launch_eval_trapz(pr::ctx_stream(ctx), d_recall, d_precision, m, ptr<double>(S->term), d_auc);
-  EV_HIP(ctx, hipGetLastError());
+  PR_CHECK_HIP(ctx, hipGetLastError());
   return PR_OK;
 }
 
@@ -213,7 +197,7 @@ int pr_ground_truth_pairs(pr_ctx* ctx, const double* gt1, int32_t m, const doubl
   if (int rc = check_shapes(ctx, "pr_ground_truth_pairs", m, n, cols)) return rc;
   if ((m > 0 && !gt1) || (n > 0 && !gt2)) return fail(ctx, PR_EINVAL, "pr_ground_truth_pairs: gt1 / gt2 is NULL");
   if (!ctx) return fail(ctx, PR_EINVAL, "pr_ground_truth_pairs: ctx is NULL");
-  EV_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
+  PR_CHECK_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
   hipStream_t st = pr::ctx_stream(ctx);
   Staging s;
   const size_t mc = (size_t)m * cols * 8, nc = (size_t)n * cols * 8;
@@ -244,7 +228,7 @@ int pr_precision_recall_gpu(pr_ctx* ctx, const double* diff_v, const int32_t* di
   if ((m > 0 && (!diff_v || !diff_idx || !gt1)) || (n > 0 && !gt2) || !auc || !top_recall)
     return fail(ctx, PR_EINVAL, "pr_precision_recall_gpu: a required pointer is NULL");
   if (!ctx) return fail(ctx, PR_EINVAL, "pr_precision_recall_gpu: ctx is NULL");
-  EV_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
+  PR_CHECK_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
   hipStream_t st = pr::ctx_stream(ctx);
   Staging s;
   double* dv = static_cast<double*>(s.up(diff_v, (size_t)m * 8, st));

@@ -4,7 +4,6 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <string>
 #include <utility>
@@ -12,6 +11,7 @@
 
 #include "../../include/place_recognition.h"
 #include "gist_tables.hpp"
+#include "host_common.hpp"
 #include "kernels.hpp"
 
 namespace {
@@ -28,23 +28,7 @@ struct GistState {
   size_t scratch_floats = 0;
 };
 
-int fail(pr_ctx* ctx, int code, const char* fmt, ...) __attribute__((format(printf, 3, 4)));
-int fail(pr_ctx* ctx, int code, const char* fmt, ...) {
-  char b[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(b, sizeof b, fmt, ap);
-  va_end(ap);
-  pr::ctx_set_error(ctx, b);
-  return code;
-}
-
-#define GIST_HIP(ctx, call)                                                                                       \
-  do {                                                                                                            \
-    hipError_t _e = (call);                                                                                       \
-    if (_e != hipSuccess)                                                                                         \
-      return fail(ctx, _e == hipErrorOutOfMemory ? PR_ENOMEM : PR_EHIP, "%s failed: %s", #call, hipGetErrorString(_e)); \
-  } while (0)
+using pr::fail;
 
 int check_params(pr_ctx* ctx, const char* fn, int nblocks, int n_scale, const int32_t* orients) {
   if (nblocks < 1 || nblocks > 16) return fail(ctx, PR_EINVAL, "%s: nblocks must be 1..16 (got %d)", fn, nblocks);
@@ -153,7 +137,7 @@ int pr_gist_generate_dev(pr_ctx* ctx, const void* img, int dtype, int32_t N, int
                          int32_t n_scale, const int32_t* orients, float* out) {
   if (int rc = check_args(ctx, "pr_gist_generate_dev", img, dtype, N, height, width, nblocks, n_scale, orients, out)) return rc;
   if (N == 0) return PR_OK;
-  GIST_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
+  PR_CHECK_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
   GistState* st = state(ctx);
   float* gabor = nullptr;
   if (int rc = tables(ctx, st, n_scale, orients, &gabor)) return rc;
@@ -164,12 +148,12 @@ int pr_gist_generate_dev(pr_ctx* ctx, const void* img, int dtype, int32_t N, int
   hipStream_t s = pr::ctx_stream(ctx);
   if (need > st->scratch_floats) {               // grow-only: a later call of at most this size allocates nothing
     if (st->scratch) {
-      GIST_HIP(ctx, hipStreamSynchronize(s));
-      GIST_HIP(ctx, hipFree(st->scratch));
+      PR_CHECK_HIP(ctx, hipStreamSynchronize(s));
+      PR_CHECK_HIP(ctx, hipFree(st->scratch));
       st->scratch = nullptr;
       st->scratch_floats = 0;
     }
-    GIST_HIP(ctx, hipMalloc(&st->scratch, need * sizeof(float)));
+    PR_CHECK_HIP(ctx, hipMalloc(&st->scratch, need * sizeof(float)));
     st->scratch_floats = need;
   }
   const size_t px = (size_t)GS * GS * (dtype == PR_U8 ? 1 : 4);
@@ -179,7 +163,7 @@ int pr_gist_generate_dev(pr_ctx* ctx, const void* img, int dtype, int32_t N, int
     pr::launch_gist(s, static_cast<const char*>(img) + c0 * px, dtype == PR_U8, n, nblocks, nf, st->circ, gabor, st->tw, st->scratch,
                     out + c0 * D);
   }
-  GIST_HIP(ctx, hipGetLastError());
+  PR_CHECK_HIP(ctx, hipGetLastError());
   return PR_OK;
 }
 
@@ -187,7 +171,7 @@ int pr_gist_generate(pr_ctx* ctx, const void* img, int dtype, int32_t N, int32_t
                      const int32_t* orients, float* out) {
   if (int rc = check_args(ctx, "pr_gist_generate", img, dtype, N, height, width, nblocks, n_scale, orients, out)) return rc;
   if (N == 0) return PR_OK;
-  GIST_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
+  PR_CHECK_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
   hipStream_t s = pr::ctx_stream(ctx);
   const size_t in_bytes = (size_t)N * GS * GS * (dtype == PR_U8 ? 1 : 4);
   const size_t D = (size_t)pr_gist_signature_size(nblocks, n_scale, orients);

@@ -5,13 +5,13 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
 
 #include "../../include/place_recognition.h"
+#include "host_common.hpp"
 #include "kernels.hpp"
 
 static_assert(sizeof(pr::IcpStats) == sizeof(pr_icp_stats), "stats record");
@@ -32,23 +32,7 @@ struct IcpState {
 
 constexpr size_t GRID_CELL_BUDGET = (size_t)256 << 20;   // bytes of cell words a call may hold
 
-int fail(pr_ctx* ctx, int code, const char* fmt, ...) __attribute__((format(printf, 3, 4)));
-int fail(pr_ctx* ctx, int code, const char* fmt, ...) {
-  char b[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(b, sizeof b, fmt, ap);
-  va_end(ap);
-  pr::ctx_set_error(ctx, b);
-  return code;
-}
-
-#define IC_HIP(ctx, call)                                                                                         \
-  do {                                                                                                            \
-    hipError_t _e = (call);                                                                                       \
-    if (_e != hipSuccess)                                                                                         \
-      return fail(ctx, _e == hipErrorOutOfMemory ? PR_ENOMEM : PR_EHIP, "%s failed: %s", #call, hipGetErrorString(_e)); \
-  } while (0)
+using pr::fail;
 
 IcpState* state(pr_ctx* ctx) {
   void*& slot = pr::ctx_icp(ctx);
@@ -61,11 +45,11 @@ int grow(pr_ctx* ctx, Buf& b, size_t bytes) {
   bytes = std::max<size_t>(bytes, 64);
   if (b.cap >= bytes) return PR_OK;
   if (b.p) {
-    IC_HIP(ctx, hipStreamSynchronize(pr::ctx_stream(ctx)));
+    PR_CHECK_HIP(ctx, hipStreamSynchronize(pr::ctx_stream(ctx)));
     (void)hipFree(b.p);
     b.p = nullptr; b.cap = 0;
   }
-  IC_HIP(ctx, hipMalloc(&b.p, bytes));
+  PR_CHECK_HIP(ctx, hipMalloc(&b.p, bytes));
   b.cap = bytes;
   return PR_OK;
 }
@@ -243,10 +227,10 @@ int pr_icp_nn_radius_dev(pr_ctx* ctx, const double* d_xyz_q, const int64_t* d_of
       return rc;
     const pr::IcpClouds A = clouds(d_xyz_q, d_offs_q, Nq, d_xyz_db, d_offs_db, Ndb, d_pair_src, d_pair_dst, c, max_src_pts, max_dst_pts);
     pr::launch_icp_radius_mask(pr::ctx_stream(ctx), A, reinterpret_cast<const long long*>(d_out_offs), d_nn_d2, d_nn_idx, mc2);
-    IC_HIP(ctx, hipGetLastError());
+    PR_CHECK_HIP(ctx, hipGetLastError());
     return PR_OK;
   }
-  IC_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
+  PR_CHECK_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
   hipStream_t st = pr::ctx_stream(ctx);
   const pr::IcpClouds A = clouds(d_xyz_q, d_offs_q, Nq, d_xyz_db, d_offs_db, Ndb, d_pair_src, d_pair_dst, c, max_src_pts, max_dst_pts);
   pr::launch_icp_offsets(st, A, reinterpret_cast<long long*>(d_out_offs));
@@ -256,7 +240,7 @@ int pr_icp_nn_radius_dev(pr_ctx* ctx, const double* d_xyz_q, const int64_t* d_of
     pr::launch_icp_grid_probe(st, A, gr, d_T, nullptr, std::max(max_src_pts, 1), reinterpret_cast<const long long*>(d_out_offs), d_nn_d2, d_nn_idx,
                               mc2, nullptr, 1);
   }
-  IC_HIP(ctx, hipGetLastError());
+  PR_CHECK_HIP(ctx, hipGetLastError());
   return PR_OK;
 }
 
@@ -268,7 +252,7 @@ int pr_icp_nn_dev(pr_ctx* ctx, const double* d_xyz_q, const int64_t* d_offs_q, i
   if (!d_out_offs || (c > 0 && !d_T) || (c > 0 && max_src_pts > 0 && (!d_nn_idx || !d_nn_d2)))
     return fail(ctx, PR_EINVAL, "%s: a required pointer is NULL", fn);
   if (!ctx) return fail(ctx, PR_EINVAL, "%s: ctx is NULL", fn);
-  IC_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
+  PR_CHECK_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
   IcpState* S = state(ctx);
   hipStream_t st = pr::ctx_stream(ctx);
   const pr::IcpClouds A = clouds(d_xyz_q, d_offs_q, Nq, d_xyz_db, d_offs_db, Ndb, d_pair_src, d_pair_dst, c, max_src_pts, max_dst_pts);
@@ -280,7 +264,7 @@ int pr_icp_nn_dev(pr_ctx* ctx, const double* d_xyz_q, const int64_t* d_offs_q, i
   pr::launch_icp_offsets(st, A, reinterpret_cast<long long*>(d_out_offs));
   pr::launch_icp_nn(st, A, g, d_T, nullptr, ptr<double>(S->slot_d), ptr<int>(S->slot_j), reinterpret_cast<const long long*>(d_out_offs), d_nn_d2,
                     d_nn_idx, 0.0, nullptr);
-  IC_HIP(ctx, hipGetLastError());
+  PR_CHECK_HIP(ctx, hipGetLastError());
   return PR_OK;
 }
 
@@ -294,7 +278,7 @@ int pr_icp_pairs_dev(pr_ctx* ctx, const double* d_xyz_q, const int64_t* d_offs_q
   if (c > 0 && (!d_T0 || !d_T_out || !d_stats)) return fail(ctx, PR_EINVAL, "%s: a required pointer is NULL", fn);
   if (!ctx) return fail(ctx, PR_EINVAL, "%s: ctx is NULL", fn);
   if (c == 0) return PR_OK;
-  IC_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
+  PR_CHECK_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
   IcpState* S = state(ctx);
   hipStream_t st = pr::ctx_stream(ctx);
   const pr::IcpClouds A = clouds(d_xyz_q, d_offs_q, Nq, d_xyz_db, d_offs_db, Ndb, d_pair_src, d_pair_dst, c, max_src_pts, max_dst_pts);
@@ -332,7 +316,7 @@ int pr_icp_pairs_dev(pr_ctx* ctx, const double* d_xyz_q, const int64_t* d_offs_q
                         ptr<int>(S->nn_j), mc2, ptr<double>(S->part));
     pr::launch_icp_finish(st, A, g, ptr<double>(S->part), P, last ? 1 : 0, d_T_out, stats, done, ptr<double>(S->prev));
   }
-  IC_HIP(ctx, hipGetLastError());
+  PR_CHECK_HIP(ctx, hipGetLastError());
   return PR_OK;
 }
 
@@ -351,7 +335,7 @@ static int nn_host(pr_ctx* ctx, const char* fn, bool radius, const double* xyz_q
   const int64_t total = prefix[(size_t)c];
   if (total > 0 && (!nn_idx || !nn_d2)) return fail(ctx, PR_EINVAL, "%s: a required pointer is NULL", fn);
   if (!ctx) return fail(ctx, PR_EINVAL, "%s: ctx is NULL", fn);
-  IC_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
+  PR_CHECK_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
   hipStream_t st = pr::ctx_stream(ctx);
   Staging s;
   double* dxq = static_cast<double*>(s.up(xyz_q, (size_t)offs_q[Nq] * 24, st));
@@ -403,7 +387,7 @@ int pr_icp_pairs(pr_ctx* ctx, const double* xyz_q, const int64_t* offs_q, int32_
   if (int rc = check_sets(ctx, fn, xyz_q, offs_q, Nq, xyz_db, offs_db, Ndb, pair_src, pair_dst, c, ms, md)) return rc;
   if (!ctx) return fail(ctx, PR_EINVAL, "%s: ctx is NULL", fn);
   if (c == 0) return PR_OK;
-  IC_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
+  PR_CHECK_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
   hipStream_t st = pr::ctx_stream(ctx);
   Staging s;
   double* dxq = static_cast<double*>(s.up(xyz_q, (size_t)offs_q[Nq] * 24, st));

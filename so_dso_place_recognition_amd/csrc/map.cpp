@@ -4,12 +4,12 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <new>
 
 #include "../../include/place_recognition.h"
+#include "host_common.hpp"
 #include "kernels.hpp"
 
 static_assert(pr::MAP_OVERFLOW == PR_MAP_OVERFLOW && pr::MAP_DROPPED == PR_MAP_DROPPED, "flag bits");
@@ -21,31 +21,15 @@ struct pr_map {
 
 namespace {
 
-int fail(pr_ctx* ctx, int code, const char* fmt, ...) __attribute__((format(printf, 3, 4)));
-int fail(pr_ctx* ctx, int code, const char* fmt, ...) {
-  char b[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(b, sizeof b, fmt, ap);
-  va_end(ap);
-  pr::ctx_set_error(ctx, b);
-  return code;
-}
-
-#define MP_HIP(ctx, call)                                                                                         \
-  do {                                                                                                            \
-    hipError_t _e = (call);                                                                                       \
-    if (_e != hipSuccess)                                                                                         \
-      return fail(ctx, _e == hipErrorOutOfMemory ? PR_ENOMEM : PR_EHIP, "%s failed: %s", #call, hipGetErrorString(_e)); \
-  } while (0)
+using pr::fail;
 
 // offs, frames and state to zero on the stream: what create and reset leave (the invariants of DESIGN.md 4.15)
 int clear(pr_map* m) {
   const pr::MapView& v = m->v;
   hipStream_t st = pr::ctx_stream(m->ctx);
-  MP_HIP(m->ctx, hipMemsetAsync(v.offs, 0, ((size_t)v.kcap + 1) * sizeof(int64_t), st));
-  MP_HIP(m->ctx, hipMemsetAsync(v.frames, 0, (size_t)v.kcap * 16 * sizeof(double), st));
-  MP_HIP(m->ctx, hipMemsetAsync(v.state, 0, 4 * sizeof(int32_t), st));
+  PR_CHECK_HIP(m->ctx, hipMemsetAsync(v.offs, 0, ((size_t)v.kcap + 1) * sizeof(int64_t), st));
+  PR_CHECK_HIP(m->ctx, hipMemsetAsync(v.frames, 0, (size_t)v.kcap * 16 * sizeof(double), st));
+  PR_CHECK_HIP(m->ctx, hipMemsetAsync(v.state, 0, 4 * sizeof(int32_t), st));
   return PR_OK;
 }
 
@@ -78,7 +62,7 @@ int pr_map_create(pr_ctx* ctx, const pr_map_buffers* buffers, int32_t keyframe_c
     return fail(ctx, PR_EINVAL, "pr_map_create: max_cloud_points x max_append = %lld must be below 2^38 (one lane per point of an append)",
                 (long long)max_cloud_points * max_append);
   if (!ctx) return fail(nullptr, PR_EINVAL, "pr_map_create: ctx is NULL");
-  MP_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
+  PR_CHECK_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
   pr_map* m = new (std::nothrow) pr_map;
   if (!m) return fail(ctx, PR_ENOMEM, "out of host memory");
   m->ctx = ctx;
@@ -111,21 +95,21 @@ void pr_map_destroy(pr_map* m) {
 
 int pr_map_reset(pr_map* m) {
   if (!m) return fail(nullptr, PR_EINVAL, "pr_map_reset: map is NULL");
-  MP_HIP(m->ctx, hipSetDevice(pr::ctx_device(m->ctx)));
+  PR_CHECK_HIP(m->ctx, hipSetDevice(pr::ctx_device(m->ctx)));
   return clear(m);
 }
 
 int pr_map_count(pr_map* m, int32_t* keyframes, int64_t* points, int32_t* flags) {
   if (!m) return fail(nullptr, PR_EINVAL, "pr_map_count: map is NULL");
   if (!keyframes || !points || !flags) return fail(m->ctx, PR_EINVAL, "pr_map_count: a required pointer is NULL");
-  MP_HIP(m->ctx, hipSetDevice(pr::ctx_device(m->ctx)));
+  PR_CHECK_HIP(m->ctx, hipSetDevice(pr::ctx_device(m->ctx)));
   hipStream_t st = pr::ctx_stream(m->ctx);
   int32_t s[4];
-  MP_HIP(m->ctx, hipMemcpyAsync(s, m->v.state, sizeof s, hipMemcpyDeviceToHost, st));
-  MP_HIP(m->ctx, hipStreamSynchronize(st));
+  PR_CHECK_HIP(m->ctx, hipMemcpyAsync(s, m->v.state, sizeof s, hipMemcpyDeviceToHost, st));
+  PR_CHECK_HIP(m->ctx, hipStreamSynchronize(st));
   const int32_t k = std::min(std::max(s[0], 0), m->v.kcap);
-  MP_HIP(m->ctx, hipMemcpyAsync(points, m->v.offs + k, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-  MP_HIP(m->ctx, hipStreamSynchronize(st));
+  PR_CHECK_HIP(m->ctx, hipMemcpyAsync(points, m->v.offs + k, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  PR_CHECK_HIP(m->ctx, hipStreamSynchronize(st));
   *keyframes = s[0];
   *flags = s[1];
   return PR_OK;
@@ -141,9 +125,9 @@ int pr_map_append_dev(pr_map* m, const double* d_xyz, const float* d_inten, cons
   if (!d_info || (N > 0 && (!d_offs || !d_frames)) || (N > 0 && max_points > 0 && (!d_xyz || !d_inten)))
     return fail(m->ctx, PR_EINVAL, "pr_map_append_dev: a required pointer is NULL");
   max_points = std::min<int64_t>(max_points, (int64_t)m->v.max_cloud * N);
-  MP_HIP(m->ctx, hipSetDevice(pr::ctx_device(m->ctx)));
+  PR_CHECK_HIP(m->ctx, hipSetDevice(pr::ctx_device(m->ctx)));
   pr::launch_map_append(pr::ctx_stream(m->ctx), m->v, d_xyz, d_inten, d_offs, d_frames, d_poses, d_ids, d_emitted, N, max_points, d_info);
-  MP_HIP(m->ctx, hipGetLastError());
+  PR_CHECK_HIP(m->ctx, hipGetLastError());
   return PR_OK;
 }
 
@@ -162,18 +146,18 @@ int pr_map_append(pr_map* m, const double* xyz, const float* inten, const int64_
   }
   const int64_t npts = hi - lo;
   if (npts > 0 && (!xyz || !inten)) return fail(ctx, PR_EINVAL, "pr_map_append: a required pointer is NULL");
-  MP_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
+  PR_CHECK_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
   hipStream_t st = pr::ctx_stream(ctx);
   const size_t n = (size_t)N, np = (size_t)npts;
   const size_t o_xyz = 0, o_int = o_xyz + up16(np * 24), o_offs = o_int + up16(np * 4), o_fr = o_offs + up16((n + 1) * 8),
                o_pose = o_fr + up16(n * 128), o_ids = o_pose + up16(n * 96), o_emit = o_ids + up16(n * 4), o_info = o_emit + 16,
                total = o_info + 16;
   Staging s;
-  MP_HIP(ctx, hipMalloc(&s.p, total));
+  PR_CHECK_HIP(ctx, hipMalloc(&s.p, total));
   char* b = static_cast<char*>(s.p);
   if (np) {
-    MP_HIP(ctx, hipMemcpyAsync(b + o_xyz, xyz + 3 * lo, np * 24, hipMemcpyHostToDevice, st));
-    MP_HIP(ctx, hipMemcpyAsync(b + o_int, inten + lo, np * 4, hipMemcpyHostToDevice, st));
+    PR_CHECK_HIP(ctx, hipMemcpyAsync(b + o_xyz, xyz + 3 * lo, np * 24, hipMemcpyHostToDevice, st));
+    PR_CHECK_HIP(ctx, hipMemcpyAsync(b + o_int, inten + lo, np * 4, hipMemcpyHostToDevice, st));
   }
   int64_t* rel = nullptr;                          // the offsets counted from the first uploaded point
   if (N > 0) {
@@ -199,8 +183,8 @@ int pr_map_append(pr_map* m, const double* xyz, const float* inten, const int64_
   const hipError_t e2 = hipStreamSynchronize(st);   // rel and the staging are in flight until here
   delete[] rel;
   if (rc != PR_OK) return rc;
-  MP_HIP(ctx, e);
-  MP_HIP(ctx, e2);
+  PR_CHECK_HIP(ctx, e);
+  PR_CHECK_HIP(ctx, e2);
   return PR_OK;
 }
 

@@ -3,12 +3,12 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <new>
 
 #include "../../include/place_recognition.h"
+#include "host_common.hpp"
 #include "kernels.hpp"
 #include "online.hpp"
 
@@ -28,23 +28,7 @@ struct pr_onlineset : OnlineCore {};
 
 namespace {
 
-int fail(pr_ctx* ctx, int code, const char* fmt, ...) __attribute__((format(printf, 3, 4)));
-int fail(pr_ctx* ctx, int code, const char* fmt, ...) {
-  char b[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(b, sizeof b, fmt, ap);
-  va_end(ap);
-  pr::ctx_set_error(ctx, b);
-  return code;
-}
-
-#define ON_HIP(ctx, call)                                                                                         \
-  do {                                                                                                            \
-    hipError_t _e = (call);                                                                                       \
-    if (_e != hipSuccess)                                                                                         \
-      return fail(ctx, _e == hipErrorOutOfMemory ? PR_ENOMEM : PR_EHIP, "%s failed: %s", #call, hipGetErrorString(_e)); \
-  } while (0)
+using pr::fail;
 
 size_t up16(size_t n) { return (n + 15) & ~(size_t)15; }
 
@@ -55,7 +39,7 @@ int create(pr_ctx* ctx, const char* fn, int kind, double* p0, double* p1, int32_
   if (capacity < 1 || capacity > PR_MAX_SIGS) return fail(ctx, PR_EINVAL, "%s: capacity=%d outside 1 .. PR_MAX_SIGS=%d", fn, capacity, PR_MAX_SIGS);
   if (max_k < 1 || max_k > pr::ONLINE_MAX_K) return fail(ctx, PR_EINVAL, "%s: max_k=%d outside 1 .. %d", fn, max_k, pr::ONLINE_MAX_K);
   if (!ctx) return fail(nullptr, PR_EINVAL, "%s: ctx is NULL", fn);
-  ON_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
+  PR_CHECK_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
   T* o = new (std::nothrow) T;
   if (!o) return fail(ctx, PR_ENOMEM, "out of host memory");
   o->ctx = ctx;
@@ -102,19 +86,19 @@ int no_handle(const char* fn, const char* noun) { return fail(nullptr, PR_EINVAL
 
 int reset(OnlineCore* o, const char* fn, const char* noun) {
   if (!o) return no_handle(fn, noun);
-  ON_HIP(o->ctx, hipSetDevice(pr::ctx_device(o->ctx)));
-  ON_HIP(o->ctx, hipMemsetAsync(o->v.state, 0, 4 * sizeof(int32_t), pr::ctx_stream(o->ctx)));
+  PR_CHECK_HIP(o->ctx, hipSetDevice(pr::ctx_device(o->ctx)));
+  PR_CHECK_HIP(o->ctx, hipMemsetAsync(o->v.state, 0, 4 * sizeof(int32_t), pr::ctx_stream(o->ctx)));
   return PR_OK;
 }
 
 int read_count(OnlineCore* o, const char* fn, const char* noun, int32_t* count, int32_t* flags) {
   if (!o) return no_handle(fn, noun);
   if (!count || !flags) return fail(o->ctx, PR_EINVAL, "%s: a required pointer is NULL", fn);
-  ON_HIP(o->ctx, hipSetDevice(pr::ctx_device(o->ctx)));
+  PR_CHECK_HIP(o->ctx, hipSetDevice(pr::ctx_device(o->ctx)));
   hipStream_t st = pr::ctx_stream(o->ctx);
   int32_t s[4];
-  ON_HIP(o->ctx, hipMemcpyAsync(s, o->v.state, sizeof s, hipMemcpyDeviceToHost, st));
-  ON_HIP(o->ctx, hipStreamSynchronize(st));
+  PR_CHECK_HIP(o->ctx, hipMemcpyAsync(s, o->v.state, sizeof s, hipMemcpyDeviceToHost, st));
+  PR_CHECK_HIP(o->ctx, hipStreamSynchronize(st));
   *count = s[0]; *flags = s[1];
   return PR_OK;
 }
@@ -132,22 +116,22 @@ int check_match(const OnlineCore* o, const char* fn, const char* noun, int32_t m
 
 int match(OnlineCore* o, const pr::OnlineParts& q, const int32_t* d_emitted, int32_t mask_width, double p_weight, int32_t k, int32_t* d_idx,
           double* d_score, double* d_rows) {
-  ON_HIP(o->ctx, hipSetDevice(pr::ctx_device(o->ctx)));
+  PR_CHECK_HIP(o->ctx, hipSetDevice(pr::ctx_device(o->ctx)));
   pr::launch_online_match(pr::ctx_stream(o->ctx), o->v, q, d_emitted, mask_width, p_weight, k, d_idx, d_score, d_rows ? d_rows : o->v.rows);
-  ON_HIP(o->ctx, hipGetLastError());
+  PR_CHECK_HIP(o->ctx, hipGetLastError());
   return PR_OK;
 }
 
 int append_dev(OnlineCore* o, const pr::OnlineParts& src, const int32_t* d_emitted, int32_t* d_info) {
-  ON_HIP(o->ctx, hipSetDevice(pr::ctx_device(o->ctx)));
+  PR_CHECK_HIP(o->ctx, hipSetDevice(pr::ctx_device(o->ctx)));
   pr::launch_online_append(pr::ctx_stream(o->ctx), o->v, src, d_emitted, d_info);
-  ON_HIP(o->ctx, hipGetLastError());
+  PR_CHECK_HIP(o->ctx, hipGetLastError());
   return PR_OK;
 }
 
 // The host form: the parts through stage_sig, the device path, info back; synchronises.
 int append_host(OnlineCore* o, const pr::OnlineParts& src, int32_t* info) {
-  ON_HIP(o->ctx, hipSetDevice(pr::ctx_device(o->ctx)));
+  PR_CHECK_HIP(o->ctx, hipSetDevice(pr::ctx_device(o->ctx)));
   hipStream_t st = pr::ctx_stream(o->ctx);
   double* const stage[2] = {o->stage_sig, o->v.len[1] ? o->stage_sig + o->v.len[0] : nullptr};
   hipError_t e = hipSuccess;
@@ -158,8 +142,8 @@ int append_host(OnlineCore* o, const pr::OnlineParts& src, int32_t* info) {
   if (e == hipSuccess && rc == PR_OK) e = hipMemcpyAsync(info, o->stage_info, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, st);
   const hipError_t e2 = hipStreamSynchronize(st);    // the host arrays are in flight until here
   if (rc != PR_OK) return rc;
-  ON_HIP(o->ctx, e);
-  ON_HIP(o->ctx, e2);
+  PR_CHECK_HIP(o->ctx, e);
+  PR_CHECK_HIP(o->ctx, e2);
   return PR_OK;
 }
 

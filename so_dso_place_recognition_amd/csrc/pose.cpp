@@ -4,10 +4,10 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 
 #include "../../include/place_recognition.h"
+#include "host_common.hpp"
 #include "kernels.hpp"
 #include "pose_seed.hpp"
 
@@ -22,23 +22,7 @@ struct PoseState {
   Buf T0, src, dst, Th, sth;     // the [m k H] slots of pr_verify_pairs_dev
 };
 
-int fail(pr_ctx* ctx, int code, const char* fmt, ...) __attribute__((format(printf, 3, 4)));
-int fail(pr_ctx* ctx, int code, const char* fmt, ...) {
-  char b[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(b, sizeof b, fmt, ap);
-  va_end(ap);
-  pr::ctx_set_error(ctx, b);
-  return code;
-}
-
-#define PO_HIP(ctx, call)                                                                                         \
-  do {                                                                                                            \
-    hipError_t _e = (call);                                                                                       \
-    if (_e != hipSuccess)                                                                                         \
-      return fail(ctx, _e == hipErrorOutOfMemory ? PR_ENOMEM : PR_EHIP, "%s failed: %s", #call, hipGetErrorString(_e)); \
-  } while (0)
+using pr::fail;
 
 // the angles of pr_sc_relative_pose: (double)k * D through the same cos / sin calls
 void sc_angles(double* t) {
@@ -71,11 +55,11 @@ int grow(pr_ctx* ctx, Buf& b, size_t bytes) {
   bytes = std::max<size_t>(bytes, 64);
   if (b.cap >= bytes) return PR_OK;
   if (b.p) {
-    PO_HIP(ctx, hipStreamSynchronize(pr::ctx_stream(ctx)));
+    PR_CHECK_HIP(ctx, hipStreamSynchronize(pr::ctx_stream(ctx)));
     (void)hipFree(b.p);
     b.p = nullptr; b.cap = 0;
   }
-  PO_HIP(ctx, hipMalloc(&b.p, bytes));
+  PR_CHECK_HIP(ctx, hipMalloc(&b.p, bytes));
   b.cap = bytes;
   return PR_OK;
 }
@@ -137,12 +121,12 @@ int pr_relative_pose_dev(pr_ctx* ctx, int type, const double* d_frames_q, int32_
   if ((long long)m * k > 0 && (!d_T0 || !d_pair_src || !d_pair_dst)) return fail(ctx, PR_EINVAL, "%s: a required pointer is NULL", fn);
   if (!ctx) return fail(ctx, PR_EINVAL, "%s: ctx is NULL", fn);
   if ((long long)m * k == 0) return PR_OK;
-  PO_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
+  PR_CHECK_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
   PoseState* S;
   if (int rc = state(ctx, &S)) return rc;
   pr::launch_pose_seed(pr::ctx_stream(ctx), type, d_frames_q, m, d_frames_db, n_local, db_row0, k, d_idx, d_variant, variant_stride, H, S->angles,
                        d_T0, d_pair_src, d_pair_dst);
-  PO_HIP(ctx, hipGetLastError());
+  PR_CHECK_HIP(ctx, hipGetLastError());
   return PR_OK;
 }
 
@@ -154,10 +138,10 @@ int pr_verify_select_dev(pr_ctx* ctx, const double* d_T_h, const pr_icp_stats* d
   if (c > 0 && (!d_T_h || !d_stats_h || !d_T || !d_stats || !d_accepted || !d_hyp)) return fail(ctx, PR_EINVAL, "%s: a required pointer is NULL", fn);
   if (!ctx) return fail(ctx, PR_EINVAL, "%s: ctx is NULL", fn);
   if (c == 0) return PR_OK;
-  PO_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
+  PR_CHECK_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
   pr::launch_verify_select(pr::ctx_stream(ctx), d_T_h, reinterpret_cast<const pr::IcpStats*>(d_stats_h), c, H, min_fitness, max_rmse, d_T,
                            reinterpret_cast<pr::IcpStats*>(d_stats), d_accepted, d_hyp);
-  PO_HIP(ctx, hipGetLastError());
+  PR_CHECK_HIP(ctx, hipGetLastError());
   return PR_OK;
 }
 
@@ -178,7 +162,7 @@ int pr_verify_pairs_dev(pr_ctx* ctx, int type, const double* d_xyz_q, const int6
   if (!ctx) return fail(ctx, PR_EINVAL, "%s: ctx is NULL", fn);
   PoseState* S = nullptr;
   if (c > 0) {
-    PO_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
+    PR_CHECK_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
     if (int rc = state(ctx, &S)) return rc;
     if (int rc = grow(ctx, S->T0, (size_t)slots * 96)) return rc;
     if (int rc = grow(ctx, S->src, (size_t)slots * 4)) return rc;

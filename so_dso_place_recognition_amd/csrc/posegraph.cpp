@@ -3,12 +3,12 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <new>
 
 #include "../../include/place_recognition.h"
+#include "host_common.hpp"
 #include "kernels.hpp"
 #include "posegraph.hpp"
 
@@ -28,23 +28,7 @@ struct pr_posegraph {
 
 namespace {
 
-int fail(pr_ctx* ctx, int code, const char* fmt, ...) __attribute__((format(printf, 3, 4)));
-int fail(pr_ctx* ctx, int code, const char* fmt, ...) {
-  char b[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(b, sizeof b, fmt, ap);
-  va_end(ap);
-  pr::ctx_set_error(ctx, b);
-  return code;
-}
-
-#define PG_HIP(ctx, call)                                                                                         \
-  do {                                                                                                            \
-    hipError_t _e = (call);                                                                                       \
-    if (_e != hipSuccess)                                                                                         \
-      return fail(ctx, _e == hipErrorOutOfMemory ? PR_ENOMEM : PR_EHIP, "%s failed: %s", #call, hipGetErrorString(_e)); \
-  } while (0)
+using pr::fail;
 
 constexpr int32_t MAX_NODES = 1 << 20, MAX_EDGES = 1 << 20, MAX_OUTER = 64, MAX_INNER = 1 << 16;
 
@@ -69,7 +53,7 @@ int pr_posegraph_create(pr_ctx* ctx, const pr_posegraph_buffers* buffers, int32_
   if (max_outer < 1 || max_outer > MAX_OUTER) return fail(ctx, PR_EINVAL, "pr_posegraph_create: max_outer=%d outside 1 .. %d", max_outer, MAX_OUTER);
   if (max_inner < 1 || max_inner > MAX_INNER) return fail(ctx, PR_EINVAL, "pr_posegraph_create: max_inner=%d outside 1 .. %d", max_inner, MAX_INNER);
   if (!ctx) return fail(nullptr, PR_EINVAL, "pr_posegraph_create: ctx is NULL");
-  PG_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
+  PR_CHECK_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
   pr_posegraph* g = new (std::nothrow) pr_posegraph;
   if (!g) return fail(ctx, PR_ENOMEM, "out of host memory");
   g->ctx = ctx;
@@ -123,19 +107,19 @@ void pr_posegraph_destroy(pr_posegraph* g) {
 
 int pr_posegraph_reset(pr_posegraph* g) {
   if (!g) return fail(nullptr, PR_EINVAL, "pr_posegraph_reset: graph is NULL");
-  PG_HIP(g->ctx, hipSetDevice(pr::ctx_device(g->ctx)));
-  PG_HIP(g->ctx, hipMemsetAsync(g->v.state, 0, 4 * sizeof(int32_t), pr::ctx_stream(g->ctx)));
+  PR_CHECK_HIP(g->ctx, hipSetDevice(pr::ctx_device(g->ctx)));
+  PR_CHECK_HIP(g->ctx, hipMemsetAsync(g->v.state, 0, 4 * sizeof(int32_t), pr::ctx_stream(g->ctx)));
   return PR_OK;
 }
 
 int pr_posegraph_count(pr_posegraph* g, int32_t* edges, int32_t* flags) {
   if (!g) return fail(nullptr, PR_EINVAL, "pr_posegraph_count: graph is NULL");
   if (!edges || !flags) return fail(g->ctx, PR_EINVAL, "pr_posegraph_count: a required pointer is NULL");
-  PG_HIP(g->ctx, hipSetDevice(pr::ctx_device(g->ctx)));
+  PR_CHECK_HIP(g->ctx, hipSetDevice(pr::ctx_device(g->ctx)));
   hipStream_t st = pr::ctx_stream(g->ctx);
   int32_t s[4];
-  PG_HIP(g->ctx, hipMemcpyAsync(s, g->v.state, sizeof s, hipMemcpyDeviceToHost, st));
-  PG_HIP(g->ctx, hipStreamSynchronize(st));
+  PR_CHECK_HIP(g->ctx, hipMemcpyAsync(s, g->v.state, sizeof s, hipMemcpyDeviceToHost, st));
+  PR_CHECK_HIP(g->ctx, hipStreamSynchronize(st));
   *edges = s[0];
   *flags = s[1];
   return PR_OK;
@@ -151,9 +135,9 @@ int pr_posegraph_add_dev(pr_posegraph* g, const int32_t* d_idx, const double* d_
   if (!g) return fail(nullptr, PR_EINVAL, "pr_posegraph_add_dev: graph is NULL");
   if (!d_idx || !d_T || !d_accepted || !d_query_row || !d_info)
     return fail(ctx, PR_EINVAL, "pr_posegraph_add_dev: a required pointer is NULL (d_idx, d_T, d_accepted, d_query_row, d_info)");
-  PG_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
+  PR_CHECK_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
   pr::launch_posegraph_add(pr::ctx_stream(ctx), g->v, d_idx, d_T, d_accepted, d_query_row, k, w_rot, w_trans, d_info);
-  PG_HIP(ctx, hipGetLastError());
+  PR_CHECK_HIP(ctx, hipGetLastError());
   return PR_OK;
 }
 
@@ -163,7 +147,7 @@ int pr_posegraph_add(pr_posegraph* g, const int32_t* idx, const double* T, const
   if (k < 1 || k > pr::POSEGRAPH_MAX_K) return fail(ctx, PR_EINVAL, "pr_posegraph_add: k=%d outside 1 .. %d", k, pr::POSEGRAPH_MAX_K);
   if (!g) return fail(nullptr, PR_EINVAL, "pr_posegraph_add: graph is NULL");
   if (!idx || !T || !accepted || !info) return fail(ctx, PR_EINVAL, "pr_posegraph_add: a required pointer is NULL (idx, T, accepted, info)");
-  PG_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
+  PR_CHECK_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
   hipStream_t st = pr::ctx_stream(ctx);
   const int32_t row[4] = {query_row, 0, 0, 0};
   hipError_t e = hipMemcpyAsync(g->stage_idx, idx, (size_t)k * 4, hipMemcpyHostToDevice, st);
@@ -175,8 +159,8 @@ int pr_posegraph_add(pr_posegraph* g, const int32_t* idx, const double* T, const
   if (e == hipSuccess && rc == PR_OK) e = hipMemcpyAsync(info, g->stage_info, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, st);
   const hipError_t e2 = hipStreamSynchronize(st);     // the host arrays are in flight until here
   if (rc != PR_OK) return rc;
-  PG_HIP(ctx, e);
-  PG_HIP(ctx, e2);
+  PR_CHECK_HIP(ctx, e);
+  PR_CHECK_HIP(ctx, e2);
   return PR_OK;
 }
 
@@ -194,10 +178,10 @@ int pr_posegraph_relax_dev(pr_posegraph* g, const double* d_poses_in, const int3
   if (params->inner > g->v.max_inner) return fail(ctx, PR_EINVAL, "pr_posegraph_relax_dev: inner=%d outside 1 .. max_inner=%d", params->inner, g->v.max_inner);
   if (!d_poses_in || !d_n || !d_poses_out || !d_report)
     return fail(ctx, PR_EINVAL, "pr_posegraph_relax_dev: a required pointer is NULL (d_poses_in, d_n, d_poses_out, d_report)");
-  PG_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
+  PR_CHECK_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
   const pr::PoseGraphParams prm = {params->outer, params->inner, params->lambda, params->w_odo_rot, params->w_odo_trans};
   pr::launch_posegraph_relax(pr::ctx_stream(ctx), g->v, d_poses_in, d_n, prm, d_poses_out, d_report);
-  PG_HIP(ctx, hipGetLastError());
+  PR_CHECK_HIP(ctx, hipGetLastError());
   return PR_OK;
 }
 

@@ -4,7 +4,6 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <new>
@@ -12,6 +11,7 @@
 
 #include "../../include/place_recognition.h"
 #include "hash_order.hpp"
+#include "host_common.hpp"
 #include "kernels.hpp"
 
 static_assert(pr::WIN_OVERFLOW == PR_WINDOW_OVERFLOW && pr::WIN_ORDER_GLOBAL == PR_WINDOW_ORDER_GLOBAL, "flag bits");
@@ -30,28 +30,12 @@ struct pr_window {
 
 namespace {
 
-int fail(pr_ctx* ctx, int code, const char* fmt, ...) __attribute__((format(printf, 3, 4)));
-int fail(pr_ctx* ctx, int code, const char* fmt, ...) {
-  char b[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(b, sizeof b, fmt, ap);
-  va_end(ap);
-  pr::ctx_set_error(ctx, b);
-  return code;
-}
-
-#define WN_HIP(ctx, call)                                                                                         \
-  do {                                                                                                            \
-    hipError_t _e = (call);                                                                                       \
-    if (_e != hipSuccess)                                                                                         \
-      return fail(ctx, _e == hipErrorOutOfMemory ? PR_ENOMEM : PR_EHIP, "%s failed: %s", #call, hipGetErrorString(_e)); \
-  } while (0)
+using pr::fail;
 
 template <class T>
 int dev_alloc(pr_window* w, T*& p, size_t n) {
   void* q = nullptr;
-  WN_HIP(w->ctx, hipMalloc(&q, (n ? n : 1) * sizeof(T)));
+  PR_CHECK_HIP(w->ctx, hipMalloc(&q, (n ? n : 1) * sizeof(T)));
   w->owned.push_back(q);
   p = static_cast<T*>(q);
   return PR_OK;
@@ -94,13 +78,13 @@ int build(pr_window* w, double range, int polar, int32_t cap, int32_t max_new, i
 #undef WN_ALLOC
   v.sched_cnt = d_scnt; v.sched_nb = d_snb;
   hipStream_t st = pr::ctx_stream(w->ctx);
-  WN_HIP(w->ctx, hipMemcpyAsync(d_scnt, scnt.data(), scnt.size() * sizeof(int), hipMemcpyHostToDevice, st));
-  WN_HIP(w->ctx, hipMemcpyAsync(d_snb, snb.data(), snb.size() * sizeof(int), hipMemcpyHostToDevice, st));
-  WN_HIP(w->ctx, hipMemsetAsync(v.st, 0, pr::WIN_STATE_WORDS * sizeof(int), st));
-  WN_HIP(w->ctx, hipMemsetAsync(v.tval, 0xFF, (size_t)v.C * 8, st));      // "empty"; every push leaves the table so (win_clear_kernel)
-  WN_HIP(w->ctx, hipMemsetAsync(v.tfirst, 0xFF, (size_t)v.C * 4, st));
-  WN_HIP(w->ctx, hipMemsetAsync(v.tbest, 0xFF, (size_t)v.C * 4, st));
-  WN_HIP(w->ctx, hipStreamSynchronize(st));                               // scnt / snb are this function's locals
+  PR_CHECK_HIP(w->ctx, hipMemcpyAsync(d_scnt, scnt.data(), scnt.size() * sizeof(int), hipMemcpyHostToDevice, st));
+  PR_CHECK_HIP(w->ctx, hipMemcpyAsync(d_snb, snb.data(), snb.size() * sizeof(int), hipMemcpyHostToDevice, st));
+  PR_CHECK_HIP(w->ctx, hipMemsetAsync(v.st, 0, pr::WIN_STATE_WORDS * sizeof(int), st));
+  PR_CHECK_HIP(w->ctx, hipMemsetAsync(v.tval, 0xFF, (size_t)v.C * 8, st));      // "empty"; every push leaves the table so (win_clear_kernel)
+  PR_CHECK_HIP(w->ctx, hipMemsetAsync(v.tfirst, 0xFF, (size_t)v.C * 4, st));
+  PR_CHECK_HIP(w->ctx, hipMemsetAsync(v.tbest, 0xFF, (size_t)v.C * 4, st));
+  PR_CHECK_HIP(w->ctx, hipStreamSynchronize(st));                               // scnt / snb are this function's locals
   return PR_OK;
 }
 
@@ -123,7 +107,7 @@ int pr_window_create(pr_ctx* ctx, double lidarRange, int polar, int32_t point_ca
   if (max_new_points > point_capacity)
     return fail(ctx, PR_EINVAL, "pr_window_create: max_new_points=%d exceeds point_capacity=%d", max_new_points, point_capacity);
   if (!ctx) return fail(nullptr, PR_EINVAL, "pr_window_create: ctx is NULL");
-  WN_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
+  PR_CHECK_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
   pr_window* w = new (std::nothrow) pr_window;
   if (!w) return fail(ctx, PR_ENOMEM, "out of host memory");
   w->ctx = ctx;
@@ -136,19 +120,19 @@ void pr_window_destroy(pr_window* w) { release(w); }
 
 int pr_window_reset(pr_window* w) {
   if (!w) return fail(nullptr, PR_EINVAL, "pr_window_reset: window is NULL");
-  WN_HIP(w->ctx, hipSetDevice(pr::ctx_device(w->ctx)));
+  PR_CHECK_HIP(w->ctx, hipSetDevice(pr::ctx_device(w->ctx)));
   pr::launch_window_reset(pr::ctx_stream(w->ctx), w->v);
-  WN_HIP(w->ctx, hipGetLastError());
+  PR_CHECK_HIP(w->ctx, hipGetLastError());
   return PR_OK;
 }
 
 int pr_window_count(pr_window* w, int32_t* n_alive) {
   if (!w) return fail(nullptr, PR_EINVAL, "pr_window_count: window is NULL");
   if (!n_alive) return fail(w->ctx, PR_EINVAL, "pr_window_count: n_alive is NULL");
-  WN_HIP(w->ctx, hipSetDevice(pr::ctx_device(w->ctx)));
+  PR_CHECK_HIP(w->ctx, hipSetDevice(pr::ctx_device(w->ctx)));
   hipStream_t st = pr::ctx_stream(w->ctx);
-  WN_HIP(w->ctx, hipMemcpyAsync(n_alive, w->v.st, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  WN_HIP(w->ctx, hipStreamSynchronize(st));
+  PR_CHECK_HIP(w->ctx, hipMemcpyAsync(n_alive, w->v.st, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  PR_CHECK_HIP(w->ctx, hipStreamSynchronize(st));
   return PR_OK;
 }
 
@@ -159,10 +143,10 @@ int pr_window_push_dev(pr_window* w, const double* pose12, const double* xyz_new
     return fail(w->ctx, PR_EINVAL, "pr_window_push_dev: a required pointer is NULL");
   if (max_new <= 0 || max_new > w->v.max_new)
     return fail(w->ctx, PR_EINVAL, "pr_window_push_dev: max_new=%d outside 1 .. max_new_points=%d", max_new, w->v.max_new);
-  WN_HIP(w->ctx, hipSetDevice(pr::ctx_device(w->ctx)));
+  PR_CHECK_HIP(w->ctx, hipSetDevice(pr::ctx_device(w->ctx)));
   pr::launch_window_push(pr::ctx_stream(w->ctx), w->v, pose12, xyz_new, inten_new, n_new_dev, max_new, out_xyz, out_inten, out_offs, out_frame,
                          info);
-  WN_HIP(w->ctx, hipGetLastError());
+  PR_CHECK_HIP(w->ctx, hipGetLastError());
   return PR_OK;
 }
 
@@ -174,24 +158,24 @@ int pr_window_push(pr_window* w, const double* pose12, const double* xyz_new, co
     return fail(ctx, PR_EINVAL, "pr_window_push: a required pointer is NULL");
   if (n_new < 0 || n_new > w->v.max_new)
     return fail(ctx, PR_EINVAL, "pr_window_push: n_new=%d outside 0 .. max_new_points=%d", n_new, w->v.max_new);
-  WN_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
+  PR_CHECK_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
   hipStream_t st = pr::ctx_stream(ctx);
-  WN_HIP(ctx, hipMemcpyAsync(w->h_pose, pose12, 12 * sizeof(double), hipMemcpyHostToDevice, st));
+  PR_CHECK_HIP(ctx, hipMemcpyAsync(w->h_pose, pose12, 12 * sizeof(double), hipMemcpyHostToDevice, st));
   if (n_new > 0) {
-    WN_HIP(ctx, hipMemcpyAsync(w->h_xyz, xyz_new, (size_t)n_new * 24, hipMemcpyHostToDevice, st));
-    WN_HIP(ctx, hipMemcpyAsync(w->h_int, inten_new, (size_t)n_new * 4, hipMemcpyHostToDevice, st));
+    PR_CHECK_HIP(ctx, hipMemcpyAsync(w->h_xyz, xyz_new, (size_t)n_new * 24, hipMemcpyHostToDevice, st));
+    PR_CHECK_HIP(ctx, hipMemcpyAsync(w->h_int, inten_new, (size_t)n_new * 4, hipMemcpyHostToDevice, st));
   }
-  WN_HIP(ctx, hipMemcpyAsync(w->h_n, &n_new, sizeof(int), hipMemcpyHostToDevice, st));
+  PR_CHECK_HIP(ctx, hipMemcpyAsync(w->h_n, &n_new, sizeof(int), hipMemcpyHostToDevice, st));
   if (int rc = pr_window_push_dev(w, w->h_pose, w->h_xyz, w->h_int, w->h_n, w->v.max_new, w->h_oxyz, w->h_oint, w->h_offs, w->h_frame, w->h_info))
     return rc;
-  WN_HIP(ctx, hipMemcpyAsync(info, w->h_info, 4 * sizeof(int), hipMemcpyDeviceToHost, st));
-  WN_HIP(ctx, hipMemcpyAsync(out_frame, w->h_frame, 16 * sizeof(double), hipMemcpyDeviceToHost, st));
-  WN_HIP(ctx, hipStreamSynchronize(st));
+  PR_CHECK_HIP(ctx, hipMemcpyAsync(info, w->h_info, 4 * sizeof(int), hipMemcpyDeviceToHost, st));
+  PR_CHECK_HIP(ctx, hipMemcpyAsync(out_frame, w->h_frame, 16 * sizeof(double), hipMemcpyDeviceToHost, st));
+  PR_CHECK_HIP(ctx, hipStreamSynchronize(st));
   *n_out = info[1];
   if (*n_out > 0) {
-    WN_HIP(ctx, hipMemcpyAsync(out_xyz, w->h_oxyz, (size_t)*n_out * 24, hipMemcpyDeviceToHost, st));
-    WN_HIP(ctx, hipMemcpyAsync(out_inten, w->h_oint, (size_t)*n_out * 4, hipMemcpyDeviceToHost, st));
-    WN_HIP(ctx, hipStreamSynchronize(st));
+    PR_CHECK_HIP(ctx, hipMemcpyAsync(out_xyz, w->h_oxyz, (size_t)*n_out * 24, hipMemcpyDeviceToHost, st));
+    PR_CHECK_HIP(ctx, hipMemcpyAsync(out_inten, w->h_oint, (size_t)*n_out * 4, hipMemcpyDeviceToHost, st));
+    PR_CHECK_HIP(ctx, hipStreamSynchronize(st));
   }
   return PR_OK;
 }

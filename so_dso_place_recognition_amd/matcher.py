@@ -632,12 +632,7 @@ class Matcher(_Base):
     def on_new_stream(cls, type_: str, max_queries: int, max_db: int, device: int | None = None):
         """A matcher whose library context lives on a stream of its own (`.stream`): what hipGraph capture needs (the null
         stream cannot be captured).  Use it under `with torch.cuda.stream(mt.stream):`."""
-        device = torch.cuda.current_device() if device is None else device
-        st = torch.cuda.Stream(device)
-        with torch.cuda.stream(st):
-            mt = cls(type_, max_queries, max_db, ctx=_stream_context(device))
-        mt.stream = st
-        return mt
+        return _on_new_stream(cls, device, type_, max_queries, max_db)
 
     def capture(self, queries: torch.Tensor, mask_width: int = 0, p_weight: float = 2.0, k: int = 1):
         """Captures one single-rank match() of the STATIC tensor `queries` against the resident, packed DB into a hipGraph
@@ -714,24 +709,29 @@ class FusedMatcher(_Base):
         return self._match((sc_queries, m2dp_queries), mask_width, p_weight, k, db_row0, q_row0, group, False, f16_fallback, exact_order, None)
 
 
-class BowMatcher(_Base):
-    """BoW (processBoW.m + run_test.m:47-57) against a device-resident inverted file (pr_bow_db): scores are the reference's fp64 values
-    bit for bit and the order is its double-precision order, for conforming rows (include/place_recognition.h).  The DB grows in place
-    (append_database: a tail segment folded into the main lists when full) and shards like Matcher's plain path: every rank holds rows
-    [db_row0, db_row0 + n) and all queries, returns its own top-k by GLOBAL row, the lists are merged by pr_merge_topk_dev.
-    Rows: float64 device tensors [2 n, cols] (ids | weights per image, as bow_generate_torch writes them; taken without a copy).
-    max_postings: words over all DB rows the index can hold (default max_db * (cols - 1), every row full)."""
-    plain = True
+def _on_new_stream(cls, device, *args, **kw):
+    """cls(*args, **kw) with a library context on a stream of its own (`.stream`): what hipGraph capture needs (the null stream cannot
+    be captured)."""
+    device = torch.cuda.current_device() if device is None else device
+    st = torch.cuda.Stream(device)
+    with torch.cuda.stream(st):
+        mt = cls(*args, ctx=_stream_context(device), **kw)
+    mt.stream = st
+    return mt
 
-    def __init__(self, max_queries: int, max_db: int, cols: int, n_words: int, ctx: Context | None = None, device: int | None = None,
-                 max_postings: int | None = None):
-        self._init_ctx(ctx, device)
-        self._spec = (max_queries, max_db, cols, n_words)
-        self.max_queries, self.max_db, self.cols, self.n_words = max_queries, max_db, cols, n_words
-        self.rows_per_sig, self.sig_len = 2, cols
-        self.db = C.c_void_p()
-        mp = max_db * max(cols - 1, 0) if max_postings is None else int(max_postings)
-        self.ctx.check(self.lib.pr_bow_db_create(self.ctx.h, int(max_db), int(cols), int(n_words), int(mp), C.byref(self.db)))
+
+class _ResidentMatcher(_Base):
+    """What the matchers over a device-resident exact database (pr_<_kind>_db: BoW, GIST, DELIGHT) share: the DB grows in place and shards
+    like Matcher's plain path - every rank holds rows [db_row0, db_row0 + n) and all queries, returns its own top-k by GLOBAL row, the
+    lists are merged by pr_merge_topk_dev.  A subclass gives _kind (the C prefix), _name (its name in messages), _rows() (the shape rule
+    of its row tensors -> signatures) and an __init__ that creates self.db and ends with _start()."""
+    plain = True
+    _kind = _name = None
+
+    def _fn(self, name: str):
+        return getattr(self.lib, f"pr_{self._kind}_{name}")
+
+    def _start(self):
         self.n = 0
         self._q_sig = None
         self.generation = 0            # counts set / append calls: a captured match is valid for the generation it was captured at
@@ -743,36 +743,30 @@ class BowMatcher(_Base):
     def close(self):
         super().close()
         if self.db:
-            self.lib.pr_bow_db_destroy(self.ctx.h, self.db)
+            self._fn("db_destroy")(self.ctx.h, self.db)
             self.db = None
 
-    def _rows(self, rows: torch.Tensor) -> int:
-        if not (rows.is_cuda and rows.dtype == torch.float64 and rows.is_contiguous() and rows.dim() == 2 and rows.shape[1] == self.cols
-                and rows.shape[0] % 2 == 0):
-            raise ValueError(f"BoW rows must be a contiguous float64 CUDA tensor [2 n, {self.cols}]")
-        return rows.shape[0] // 2
-
-    def pack_database(self, rows: torch.Tensor):
-        """Replaces the DB with `rows` and builds the index (pr_bow_db_set: synchronises; PRError naming the first non-conforming row)."""
+    def _load(self, fn: str, rows: torch.Tensor):
         n = self._rows(rows)
         self._enter()
         self.generation += 1
-        self.ctx.check(self.lib.pr_bow_db_set(self.ctx.h, self.db, _dptr(rows), _lib.DEVICE, n))
-        self.n = int(self.lib.pr_bow_db_count(self.db))
+        self.ctx.check(self._fn(fn)(self.ctx.h, self.db, _dptr(rows), _lib.DEVICE, n))
+        self.n = int(self._fn("db_count")(self.db))
+
+    def pack_database(self, rows: torch.Tensor):
+        """Replaces the DB with `rows` (pr_<kind>_db_set: synchronises; BoW builds its index and raises PRError naming the first
+        non-conforming row)."""
+        self._load("db_set", rows)
 
     def reserve_database(self, rows: torch.Tensor | None = None):
-        """A DB that grows: the index has its capacity from construction, so this only starts it (empty, or with `rows`)."""
+        """A DB that grows: the capacity is there from construction, so this only starts it (empty, or with `rows`)."""
         if rows is None:
             rows = torch.empty((0, self.cols), dtype=torch.float64, device=self.dev)
         self.pack_database(rows)
 
     def append_database(self, rows: torch.Tensor):
-        """Rows [n, n + n_new) (pr_bow_db_append: the tail's lists, or a fold of a full tail; synchronises)."""
-        k = self._rows(rows)
-        self._enter()
-        self.generation += 1
-        self.ctx.check(self.lib.pr_bow_db_append(self.ctx.h, self.db, _dptr(rows), _lib.DEVICE, k))
-        self.n = int(self.lib.pr_bow_db_count(self.db))
+        """Rows [n, n + n_new) (pr_<kind>_db_append; synchronises.  BoW: the tail's lists, or a fold of a full tail)."""
+        self._load("db_append", rows)
 
     def local_phase1(self, queries: torch.Tensor):
         """The plain path has no row statistics: zero moments [m, 2, 3]."""
@@ -782,40 +776,30 @@ class BowMatcher(_Base):
         return torch.zeros((m, 2, 3), dtype=torch.float64, device=self.dev)
 
     def local_select(self, mom_all, G, mask_width, p_weight, k, db_row0, q_row0):
-        """This shard's top-k (idx int32 [m, k] global rows, score float64 [m, k]) - pr_bow_match_topk_dev."""
+        """This shard's top-k (idx int32 [m, k] global rows, score float64 [m, k]) - pr_<kind>_match_topk_dev."""
         m = self._m
         idx = torch.empty((m, k), dtype=torch.int32, device=self.dev)
         score = torch.empty((m, k), dtype=torch.float64, device=self.dev)
         self._enter()
-        self.ctx.check(self.lib.pr_bow_match_topk_dev(self.ctx.h, self.db, _dptr(self._q_sig), m, int(q_row0), int(db_row0), int(mask_width),
-                                                      int(k), _dptr(idx), _dptr(score)))
+        self.ctx.check(self._fn("match_topk_dev")(self.ctx.h, self.db, _dptr(self._q_sig), m, int(q_row0), int(db_row0), int(mask_width),
+                                                  int(k), _dptr(idx), _dptr(score)))
         self._leave()
         return idx, score
 
     def match(self, queries: torch.Tensor, mask_width: int = 0, k: int = 1, db_row0: int = 0, q_row0: int = 0, group=None,
               force_exchange: bool = False, mark=None):
-        """(idx int32 [m,k] GLOBAL DB rows, score float64 [m,k]) device tensors; no host synchronisation.  A non-conforming query row gets
-        -1 / NaN and raises _lib.WARN_BOW_ROWS (take_warnings)."""
+        """(idx int32 [m,k] GLOBAL DB rows, score float64 [m,k]) device tensors; no host synchronisation.  BoW: a non-conforming query
+        row gets -1 / NaN and raises _lib.WARN_BOW_ROWS (take_warnings)."""
         G = _world(group)
         return sharded_topk(lambda: self.local_phase1(queries),
                             lambda mom_all, G_: self.local_select(mom_all, G_, mask_width, 0.0, k, db_row0, q_row0),
                             k, group if (G > 1 or force_exchange) else None, G, merge=self.merge, force_exchange=force_exchange, mark=mark)
 
-    @classmethod
-    def on_new_stream(cls, max_queries: int, max_db: int, cols: int, n_words: int, device: int | None = None, **kw):
-        """A matcher whose library context lives on a stream of its own (`.stream`), as capture() needs."""
-        device = torch.cuda.current_device() if device is None else device
-        st = torch.cuda.Stream(device)
-        with torch.cuda.stream(st):
-            mt = cls(max_queries, max_db, cols, n_words, ctx=_stream_context(device), **kw)
-        mt.stream = st
-        return mt
-
     def capture(self, queries: torch.Tensor, mask_width: int = 0, k: int = 1, db_row0: int = 0, q_row0: int = 0):
         """One single-rank match() of the STATIC tensor `queries` as a hipGraph (CapturedMatch; the matcher must come from on_new_stream).
-        The graph holds the DB's row count and index buffers as they were at capture; pack_database / append_database change them (an
-        append rebuilds the tail lists with rows the graph does not know, a fold swaps the main buffers), so after either the graph must be
-        captured again: its run() raises RuntimeError instead of replaying it."""
+        The graph holds the DB's row count (BoW: and index buffers) as they were at capture; pack_database / append_database change them
+        (a BoW append rebuilds the tail lists with rows the graph does not know, a fold swaps the main buffers), so after either the graph
+        must be captured again: its run() raises RuntimeError instead of replaying it."""
         st = self.stream
         with torch.cuda.stream(st):
             assert self.ctx.stream == int(st.cuda_stream)
@@ -825,24 +809,76 @@ class BowMatcher(_Base):
             with torch.cuda.graph(g, stream=st):
                 idx, score = self.match(queries, mask_width, k, db_row0, q_row0)
         cap = CapturedMatch(g, st, queries, idx, score)
-        gen, mt = self.generation, weakref.ref(self)
+        gen, mt, name = self.generation, weakref.ref(self), self._name
 
         def valid():
             m_ = mt()
             if m_ is None or m_.db is None or m_.generation != gen:
-                raise RuntimeError("BowMatcher.capture: the database changed (or was closed) since this graph was captured; capture again")
+                raise RuntimeError(f"{name}.capture: the database changed (or was closed) since this graph was captured; capture again")
         cap.check = valid
         return cap
 
 
-class GistMatcher(_Base):
+class _TwoStageMatcher(_ResidentMatcher):
+    """GIST and DELIGHT: a coarse pass lists candidates, their distances are re-evaluated in fp64, and a query whose list is not provably
+    complete is answered from its exact row (csrc/resident_match.hpp)."""
+
+    @property
+    def device_bytes(self) -> int:
+        """Device memory the database holds, scratch included (all of it allocated at construction)."""
+        return int(self._fn("db_bytes")(self.db))
+
+    def set_exact(self, on: bool):
+        self._fn("db_set_exact")(self.db, 1 if on else 0)
+
+    def flagged_count(self) -> int:
+        """Queries of the last match() that were answered from their exact row (synchronises)."""
+        c = C.c_int32(0)
+        self._enter()
+        self.ctx.check(self._fn("flagged_count")(self.ctx.h, int(self._m), C.byref(c)))
+        return int(c.value)
+
+
+class BowMatcher(_ResidentMatcher):
+    """BoW (processBoW.m + run_test.m:47-57) against a device-resident inverted file (pr_bow_db): scores are the reference's fp64 values
+    bit for bit and the order is its double-precision order, for conforming rows (include/place_recognition.h).  The DB grows in place
+    (append_database: a tail segment folded into the main lists when full) and shards like Matcher's plain path: every rank holds rows
+    [db_row0, db_row0 + n) and all queries, returns its own top-k by GLOBAL row, the lists are merged by pr_merge_topk_dev.
+    Rows: float64 device tensors [2 n, cols] (ids | weights per image, as bow_generate_torch writes them; taken without a copy).
+    max_postings: words over all DB rows the index can hold (default max_db * (cols - 1), every row full)."""
+    _kind, _name = "bow", "BowMatcher"
+
+    def __init__(self, max_queries: int, max_db: int, cols: int, n_words: int, ctx: Context | None = None, device: int | None = None,
+                 max_postings: int | None = None):
+        self._init_ctx(ctx, device)
+        self._spec = (max_queries, max_db, cols, n_words)
+        self.max_queries, self.max_db, self.cols, self.n_words = max_queries, max_db, cols, n_words
+        self.rows_per_sig, self.sig_len = 2, cols
+        self.db = C.c_void_p()
+        mp = max_db * max(cols - 1, 0) if max_postings is None else int(max_postings)
+        self.ctx.check(self.lib.pr_bow_db_create(self.ctx.h, int(max_db), int(cols), int(n_words), int(mp), C.byref(self.db)))
+        self._start()
+
+    def _rows(self, rows: torch.Tensor) -> int:
+        if not (rows.is_cuda and rows.dtype == torch.float64 and rows.is_contiguous() and rows.dim() == 2 and rows.shape[1] == self.cols
+                and rows.shape[0] % 2 == 0):
+            raise ValueError(f"BoW rows must be a contiguous float64 CUDA tensor [2 n, {self.cols}]")
+        return rows.shape[0] // 2
+
+    @classmethod
+    def on_new_stream(cls, max_queries: int, max_db: int, cols: int, n_words: int, device: int | None = None, **kw):
+        """A matcher whose library context lives on a stream of its own (`.stream`), as capture() needs."""
+        return _on_new_stream(cls, device, max_queries, max_db, cols, n_words, **kw)
+
+
+class GistMatcher(_TwoStageMatcher):
     """GIST (processGIST.m + run_test.m:47-57) against a device-resident database (pr_gist_db): indices and fp64 score bits are the
     reference's double-precision answer for every input.  A coarse pass on the f16 matrix cores lists candidates, their distances are
     re-evaluated in fp64, and a query whose list is not provably complete is answered from its exact row.  The DB grows
     in place and shards like BowMatcher: every rank holds rows [db_row0, db_row0 + n) and all queries, the lists are merged by
     pr_merge_topk_dev.  Rows: float64 device tensors [n, cols], as gist_generate_torch writes them (taken without a copy).
     exact=True (or PR_GIST_EXACT=1): every query takes the exact-row path."""
-    plain = True
+    _kind, _name = "gist", "GistMatcher"
 
     def __init__(self, max_queries: int, max_db: int, cols: int, ctx: Context | None = None, device: int | None = None, exact: bool = False):
         if min(int(max_queries), int(max_db), int(cols)) < 1:
@@ -854,130 +890,28 @@ class GistMatcher(_Base):
         self.db = C.c_void_p()
         self.ctx.check(self.lib.pr_gist_db_create(self.ctx.h, int(max_db), int(cols), C.byref(self.db)))
         if exact:
-            self.lib.pr_gist_db_set_exact(self.db, 1)
-        self.n = 0
-        self._q_sig = None
-        self.generation = 0            # counts set / append calls: a captured match is valid for the generation it was captured at
-
-    @property
-    def descs(self):
-        return (self,)
-
-    @property
-    def device_bytes(self) -> int:
-        """Device memory the database holds, scratch included (all of it allocated at construction)."""
-        return int(self.lib.pr_gist_db_bytes(self.db))
-
-    def set_exact(self, on: bool):
-        self.lib.pr_gist_db_set_exact(self.db, 1 if on else 0)
-
-    def close(self):
-        super().close()
-        if self.db:
-            self.lib.pr_gist_db_destroy(self.ctx.h, self.db)
-            self.db = None
+            self.set_exact(True)
+        self._start()
 
     def _rows(self, rows: torch.Tensor) -> int:
         if not (rows.is_cuda and rows.dtype == torch.float64 and rows.is_contiguous() and rows.dim() == 2 and rows.shape[1] == self.cols):
             raise ValueError(f"GIST rows must be a contiguous float64 CUDA tensor [n, {self.cols}]")
         return rows.shape[0]
 
-    def pack_database(self, rows: torch.Tensor):
-        """Replaces the DB with `rows` (pr_gist_db_set: synchronises)."""
-        n = self._rows(rows)
-        self._enter()
-        self.generation += 1
-        self.ctx.check(self.lib.pr_gist_db_set(self.ctx.h, self.db, _dptr(rows), _lib.DEVICE, n))
-        self.n = int(self.lib.pr_gist_db_count(self.db))
-
-    def reserve_database(self, rows: torch.Tensor | None = None):
-        """A DB that grows: the capacity is there from construction, so this only starts it (empty, or with `rows`)."""
-        if rows is None:
-            rows = torch.empty((0, self.cols), dtype=torch.float64, device=self.dev)
-        self.pack_database(rows)
-
-    def append_database(self, rows: torch.Tensor):
-        """Rows [n, n + n_new) (pr_gist_db_append; synchronises)."""
-        k = self._rows(rows)
-        self._enter()
-        self.generation += 1
-        self.ctx.check(self.lib.pr_gist_db_append(self.ctx.h, self.db, _dptr(rows), _lib.DEVICE, k))
-        self.n = int(self.lib.pr_gist_db_count(self.db))
-
-    def flagged_count(self) -> int:
-        """Queries of the last match() that were answered from their exact row (synchronises)."""
-        c = C.c_int32(0)
-        self._enter()
-        self.ctx.check(self.lib.pr_gist_flagged_count(self.ctx.h, int(self._m), C.byref(c)))
-        return int(c.value)
-
-    def local_phase1(self, queries: torch.Tensor):
-        """The plain path has no row statistics: zero moments [m, 2, 3]."""
-        m = self._rows(queries)
-        assert m <= self.max_queries
-        self._q_sig, self._m = queries, m
-        return torch.zeros((m, 2, 3), dtype=torch.float64, device=self.dev)
-
-    def local_select(self, mom_all, G, mask_width, p_weight, k, db_row0, q_row0):
-        """This shard's top-k (idx int32 [m, k] global rows, score float64 [m, k]) - pr_gist_match_topk_dev."""
-        m = self._m
-        idx = torch.empty((m, k), dtype=torch.int32, device=self.dev)
-        score = torch.empty((m, k), dtype=torch.float64, device=self.dev)
-        self._enter()
-        self.ctx.check(self.lib.pr_gist_match_topk_dev(self.ctx.h, self.db, _dptr(self._q_sig), m, int(q_row0), int(db_row0), int(mask_width),
-                                                       int(k), _dptr(idx), _dptr(score)))
-        self._leave()
-        return idx, score
-
-    def match(self, queries: torch.Tensor, mask_width: int = 0, k: int = 1, db_row0: int = 0, q_row0: int = 0, group=None,
-              force_exchange: bool = False, mark=None):
-        """(idx int32 [m,k] GLOBAL DB rows, score float64 [m,k]) device tensors; no host synchronisation."""
-        G = _world(group)
-        return sharded_topk(lambda: self.local_phase1(queries),
-                            lambda mom_all, G_: self.local_select(mom_all, G_, mask_width, 0.0, k, db_row0, q_row0),
-                            k, group if (G > 1 or force_exchange) else None, G, merge=self.merge, force_exchange=force_exchange, mark=mark)
-
     @classmethod
     def on_new_stream(cls, max_queries: int, max_db: int, cols: int, device: int | None = None, **kw):
         """A matcher whose library context lives on a stream of its own (`.stream`), as capture() needs."""
-        device = torch.cuda.current_device() if device is None else device
-        st = torch.cuda.Stream(device)
-        with torch.cuda.stream(st):
-            mt = cls(max_queries, max_db, cols, ctx=_stream_context(device), **kw)
-        mt.stream = st
-        return mt
-
-    def capture(self, queries: torch.Tensor, mask_width: int = 0, k: int = 1, db_row0: int = 0, q_row0: int = 0):
-        """One single-rank match() of the STATIC tensor `queries` as a hipGraph (CapturedMatch; the matcher must come from on_new_stream).
-        The graph holds the DB's row count as it was at capture, so after pack_database / append_database it must be captured again:
-        its run() raises RuntimeError instead of replaying it."""
-        st = self.stream
-        with torch.cuda.stream(st):
-            assert self.ctx.stream == int(st.cuda_stream)
-            self.match(queries, mask_width, k, db_row0, q_row0)
-            st.synchronize()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, stream=st):
-                idx, score = self.match(queries, mask_width, k, db_row0, q_row0)
-        cap = CapturedMatch(g, st, queries, idx, score)
-        gen, mt = self.generation, weakref.ref(self)
-
-        def valid():
-            m_ = mt()
-            if m_ is None or m_.db is None or m_.generation != gen:
-                raise RuntimeError("GistMatcher.capture: the database changed (or was closed) since this graph was captured; capture again")
-        cap.check = valid
-        return cap
+        return _on_new_stream(cls, device, max_queries, max_db, cols, **kw)
 
 
-class DelightMatcher(_Base):
+class DelightMatcher(_TwoStageMatcher):
     """DELIGHT (processDELIGHT.m + run_test.m:47-57) against a device-resident database (pr_delight_db): indices and fp64 score bits are
     the reference's double-precision answer for every input.  A coarse fp32 pass lists candidates without an m x n matrix, their
     distances are re-evaluated in fp64, and a query whose list is not provably complete is answered from its exact row.
     The DB grows in place and shards like GistMatcher: every rank holds signatures [db_row0, db_row0 + n) and all queries, the lists are
     merged by pr_merge_topk_dev.  Rows: float64 device tensors [16 n, 256], as delight_generate_torch writes them (taken without a copy).
     exact=True (or PR_DELIGHT_EXACT=1): every query takes the exact-row path."""
-    plain = True
+    _kind, _name = "delight", "DelightMatcher"
 
     def __init__(self, max_queries: int, max_db: int, ctx: Context | None = None, device: int | None = None, exact: bool = False):
         if min(int(max_queries), int(max_db)) < 1:
@@ -989,28 +923,8 @@ class DelightMatcher(_Base):
         self.db = C.c_void_p()
         self.ctx.check(self.lib.pr_delight_db_create(self.ctx.h, int(max_db), C.byref(self.db)))
         if exact:
-            self.lib.pr_delight_db_set_exact(self.db, 1)
-        self.n = 0
-        self._q_sig = None
-        self.generation = 0            # counts set / append calls: a captured match is valid for the generation it was captured at
-
-    @property
-    def descs(self):
-        return (self,)
-
-    @property
-    def device_bytes(self) -> int:
-        """Device memory the database holds, scratch included (all of it allocated at construction)."""
-        return int(self.lib.pr_delight_db_bytes(self.db))
-
-    def set_exact(self, on: bool):
-        self.lib.pr_delight_db_set_exact(self.db, 1 if on else 0)
-
-    def close(self):
-        super().close()
-        if self.db:
-            self.lib.pr_delight_db_destroy(self.ctx.h, self.db)
-            self.db = None
+            self.set_exact(True)
+        self._start()
 
     def _rows(self, rows: torch.Tensor) -> int:
         if not (rows.is_cuda and rows.dtype == torch.float64 and rows.is_contiguous() and rows.dim() == 2 and rows.shape[1] == 256
@@ -1018,92 +932,11 @@ class DelightMatcher(_Base):
             raise ValueError("DELIGHT rows must be a contiguous float64 CUDA tensor [16 n, 256]")
         return rows.shape[0] // 16
 
-    def pack_database(self, rows: torch.Tensor):
-        """Replaces the DB with `rows` (pr_delight_db_set: synchronises)."""
-        n = self._rows(rows)
-        self._enter()
-        self.generation += 1
-        self.ctx.check(self.lib.pr_delight_db_set(self.ctx.h, self.db, _dptr(rows), _lib.DEVICE, n))
-        self.n = int(self.lib.pr_delight_db_count(self.db))
-
-    def reserve_database(self, rows: torch.Tensor | None = None):
-        """A DB that grows: the capacity is there from construction, so this only starts it (empty, or with `rows`)."""
-        if rows is None:
-            rows = torch.empty((0, 256), dtype=torch.float64, device=self.dev)
-        self.pack_database(rows)
-
-    def append_database(self, rows: torch.Tensor):
-        """Rows [n, n + n_new) (pr_delight_db_append; synchronises)."""
-        k = self._rows(rows)
-        self._enter()
-        self.generation += 1
-        self.ctx.check(self.lib.pr_delight_db_append(self.ctx.h, self.db, _dptr(rows), _lib.DEVICE, k))
-        self.n = int(self.lib.pr_delight_db_count(self.db))
-
-    def flagged_count(self) -> int:
-        """Queries of the last match() that were answered from their exact row (synchronises)."""
-        c = C.c_int32(0)
-        self._enter()
-        self.ctx.check(self.lib.pr_delight_flagged_count(self.ctx.h, int(self._m), C.byref(c)))
-        return int(c.value)
-
-    def local_phase1(self, queries: torch.Tensor):
-        """The plain path has no row statistics: zero moments [m, 2, 3]."""
-        m = self._rows(queries)
-        assert m <= self.max_queries
-        self._q_sig, self._m = queries, m
-        return torch.zeros((m, 2, 3), dtype=torch.float64, device=self.dev)
-
-    def local_select(self, mom_all, G, mask_width, p_weight, k, db_row0, q_row0):
-        """This shard's top-k (idx int32 [m, k] global rows, score float64 [m, k]) - pr_delight_match_topk_dev."""
-        m = self._m
-        idx = torch.empty((m, k), dtype=torch.int32, device=self.dev)
-        score = torch.empty((m, k), dtype=torch.float64, device=self.dev)
-        self._enter()
-        self.ctx.check(self.lib.pr_delight_match_topk_dev(self.ctx.h, self.db, _dptr(self._q_sig), m, int(q_row0), int(db_row0), int(mask_width),
-                                                       int(k), _dptr(idx), _dptr(score)))
-        self._leave()
-        return idx, score
-
-    def match(self, queries: torch.Tensor, mask_width: int = 0, k: int = 1, db_row0: int = 0, q_row0: int = 0, group=None,
-              force_exchange: bool = False, mark=None):
-        """(idx int32 [m,k] GLOBAL DB rows, score float64 [m,k]) device tensors; no host synchronisation."""
-        G = _world(group)
-        return sharded_topk(lambda: self.local_phase1(queries),
-                            lambda mom_all, G_: self.local_select(mom_all, G_, mask_width, 0.0, k, db_row0, q_row0),
-                            k, group if (G > 1 or force_exchange) else None, G, merge=self.merge, force_exchange=force_exchange, mark=mark)
-
     @classmethod
     def on_new_stream(cls, max_queries: int, max_db: int, device: int | None = None, **kw):
         """A matcher whose library context lives on a stream of its own (`.stream`), as capture() needs."""
-        device = torch.cuda.current_device() if device is None else device
-        st = torch.cuda.Stream(device)
-        with torch.cuda.stream(st):
-            mt = cls(max_queries, max_db, ctx=_stream_context(device), **kw)
-        mt.stream = st
-        return mt
+        return _on_new_stream(cls, device, max_queries, max_db, **kw)
 
-    def capture(self, queries: torch.Tensor, mask_width: int = 0, k: int = 1, db_row0: int = 0, q_row0: int = 0):
-        """One single-rank match() of the STATIC tensor `queries` as a hipGraph (CapturedMatch; the matcher must come from on_new_stream).
-        The graph holds the DB's row count as it was at capture, so after pack_database / append_database it must be captured again:
-        its run() raises RuntimeError instead of replaying it."""
-        st = self.stream
-        with torch.cuda.stream(st):
-            assert self.ctx.stream == int(st.cuda_stream)
-            self.match(queries, mask_width, k, db_row0, q_row0)
-            st.synchronize()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, stream=st):
-                idx, score = self.match(queries, mask_width, k, db_row0, q_row0)
-        cap = CapturedMatch(g, st, queries, idx, score)
-        gen, mt = self.generation, weakref.ref(self)
-
-        def valid():
-            m_ = mt()
-            if m_ is None or m_.db is None or m_.generation != gen:
-                raise RuntimeError("DelightMatcher.capture: the database changed (or was closed) since this graph was captured; capture again")
-        cap.check = valid
-        return cap
 
 
 def _world(group) -> int:

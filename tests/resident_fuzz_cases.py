@@ -41,14 +41,14 @@ SEED_SET = {"bow": tuple((4, i) for i in range(48)),
             "delight": tuple((3, i) for i in range(48)) + ((6, 6), (6, 12), (1, 15))}
 
 # ------------------------------------------------------------------------------------------------ the matchers' geometry, restated
-MAX_CAND, MAX_SLABS, QCAP, XCAP = 2048, 256, 4096, 256  # gist_match.cpp / delight_match.cpp: S C <= MAX_CAND, exact rows per pass
+MAX_CAND, MAX_SLABS, QCAP, XCAP = 2048, 256, 4096, 256  # resident_match.hpp: S C <= MAX_CAND, exact rows per pass
 GIST_SLAB_WORK, GIST_MIN_SLABS, GIST_TILE = 1536, 4, 32
 DELIGHT_SLAB_WORK, DELIGHT_QUERIES_PER_WG, DELIGHT_MIN_ENTRIES = 2048, 4, 8
 BOW_TAIL_ROWS = 1024                                  # bow_match.cpp: rows of the tail segment a growing DB folds into its main lists
 
 
 def slab_count(kind, m, n, k):
-    """S of one match chunk (launch_match of gist_match.cpp / delight_match.cpp); m <= QCAP queries are one chunk"""
+    """S of one match chunk (launch_coarse of gist_match.cpp / delight_match.cpp); m <= QCAP queries are one chunk"""
     C, mc = k + 8, min(m, QCAP)
     if kind == "gist":
         qtiles, DT = (mc + GIST_TILE - 1) // GIST_TILE, (n + GIST_TILE - 1) // GIST_TILE

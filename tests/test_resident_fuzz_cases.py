@@ -24,12 +24,16 @@ def const(text, name):
 
 def test_geometry_restates_the_source_text():
     g, d, b = source("gist_match.cpp"), source("delight_match.cpp"), source("bow_match.cpp")
+    core = source("resident_match.hpp")        # what the two kinds share is defined once, there
+    assert const(core, "MAX_CAND") == F.MAX_CAND and const(core, "MAX_SLABS") == F.MAX_SLABS and const(core, "QCAP") == F.QCAP
+    assert f"db->xcap = std::min({F.XCAP}, db->qcap);" in core
+    assert "const int n = db->count, C = k + 8;" in core
     for text in (g, d):
-        assert const(text, "MAX_CAND") == F.MAX_CAND and const(text, "MAX_SLABS") == F.MAX_SLABS
-        assert f"db->xcap = std::min({F.XCAP}, db->qcap);" in text
+        # ... and the kinds use those very names: no definition of their own
+        assert "namespace rm = pr::resident;\nusing pr::fail;\nusing rm::MAX_CAND;\nusing rm::MAX_SLABS;\nusing rm::QCAP;\n" in text
+        assert not re.search(r"constexpr int (MAX_CAND|MAX_SLABS|QCAP)\b", text) and "xcap =" not in text and "C = k" not in text
         assert "S = std::min(S, std::min(MAX_CAND / C, MAX_SLABS));" in text
-        assert "const int n = db->count, C = k + 8;" in text
-    assert f"return create_db(ctx, max_sigs, cols, {F.QCAP}, out);" in g and f"return create_db(ctx, max_sigs, {F.QCAP}, out);" in d
+    assert "return create_db(ctx, max_sigs, cols, QCAP, out);" in g and "return create_db(ctx, max_sigs, QCAP, out);" in d
     assert f"const int qtiles = (mc + {F.GIST_TILE - 1}) / {F.GIST_TILE}, DT = (n + {F.GIST_TILE - 1}) / {F.GIST_TILE};" in g
     assert f"int S = std::max({F.GIST_MIN_SLABS}, ({F.GIST_SLAB_WORK} + qtiles - 1) / qtiles);" in g
     assert "S = std::max(1, std::min(S, DT));" in g
