@@ -1066,6 +1066,63 @@ int pr_posegraph_add(pr_posegraph* g, const int32_t* idx, const double* T, const
                      double w_trans, int32_t* info);
 int pr_posegraph_relax_dev(pr_posegraph* g, const double* d_poses_in, const int32_t* d_n, const pr_posegraph_params* params, double* d_poses_out,
                            double* d_report);
+
+/* ---- the world map: all clouds of a pr_map fused into one world-frame point set (worldmap.hip) ------------------------
+ * A pr_map stores its clouds per camera frame; they do not move when pr_posegraph_relax_dev corrects the poses.  A pr_worldmap fuses
+ * them - under ANY [keyframe_capacity][12] pose array, the map's own or the relaxed ones - into one voxel-deduplicated world-frame set over
+ * CALLER-OWNED device buffers (pr_worldmap_buffers): xyz [out_capacity][3] f64, inten [out_capacity] f32, src [out_capacity] i64 (the
+ * point's index in the map), row [out_capacity] i32 (its keyframe row), count [out_capacity] i32 (the points of its voxel) and state [4]
+ * i32 = {rows written, flags, 0, 0}.
+ *
+ *   pr_worldmap_create    binds the buffers and the map (both must outlive the handle; the handle is destroyed before the map), allocates
+ *                         ALL scratch a fuse will ever need in one block and zeroes state.  No later call allocates.  The scratch is a
+ *                         hash table of T = the smallest power of two >= max(2 point_capacity, 64) slots of 20 bytes, one int32 per
+ *                         point and two per 256 points, and the staging of the host form: 20 T + 4 point_capacity + 8 nblk4 + 96
+ *                         keyframe_capacity + 64 bytes, each part rounded up to 16 (nblk4 = ceil(point_capacity / 256) rounded up to 4);
+ *                         pr_worldmap_scratch_bytes returns the figure (0 for capacities create refuses).  The map's point_capacity
+ *                         may not exceed 2^29.
+ *   pr_worldmap_fuse_dev  stream-ordered: two memset nodes and four launches whose grids depend on the create capacities only.  No host
+ *                         decision, no read-back, nothing allocated, so ONE captured fuse serves every count.  d_poses
+ *                         [keyframe_capacity][12] f64 device, NULL = the map's poses; d_n [>= 1] i32 device, NULL = the map's state;
+ *                         d_info [4] i64 device.  A fuse is a full rebuild: nothing of an earlier call survives.
+ *     The rule (normative; restated in fp64 in tests/worldmap_np.py).  n = d_n[0] clamped into 0 .. keyframe_capacity, as every reader of
+ *     the map's state does; P = offs[n] clamped into 0 .. point_capacity.  Point g, 0 <= g < P, belongs to row r with offs[r] <= g <
+ *     offs[r + 1]; empty and dropped rows own nothing.
+ *     1. World position.  A pose row is world-to-camera [R | t].  d = p - t componentwise, w_a = (R[0][a] d0 + R[1][a] d1) + R[2][a] d2
+ *        in exactly this association, in fp64 without contraction (no fused multiply-add).
+ *     2. Validity.  A point is skipped, and PR_WORLDMAP_SKIPPED set, if any of its pose's 12 entries or any w_a is not finite.
+ *        c_a = floor(w_a / cell) with IEEE division.  A point with any c_a outside [-2^20, 2^20) - compared as a double, before any
+ *        conversion to an integer - is skipped and sets PR_WORLDMAP_RANGE.  key = the three indices biased by 2^20, 21 bits each, packed
+ *        into 63 bits.
+ *     3. Voxels.  All valid points of one key form a voxel; its count is their number; its representative is the smallest g with keep =
+ *        0 (the first observation) and the largest g with keep = 1 (the latest).  A voxel qualifies iff count >= min_count.
+ *     4. Output.  The qualifying voxels in ascending order of their representative's g - a subsequence of the map's points in map order.
+ *        For the j-th: xyz[j] = w of the representative with the bits of step 1, inten[j] its intensity, src[j] = g, row[j] = r, count[j]
+ *        the voxel's count.  Only j < out_capacity are stored; if more qualify PR_WORLDMAP_OVERFLOW is set.  Rows >= min(qualifying,
+ *        out_capacity) are not written.
+ *     5. state = {rows written, flags, 0, 0}, d_info = {rows written, voxels that qualified, valid points, flags}.  The flags are the
+ *        call's; nothing is sticky.  n = 0 or P = 0 gives zero rows and changes no byte of the five output arrays.
+ *     PR_WORLDMAP_TABLE: the table's probe is bounded by T steps, past which the point is dropped with this flag; with T >= 2
+ *     point_capacity that cannot happen and no input makes a lane spin.  Every reduction is an integer atomic or an integer scan and every
+ *     position is computed per point in a fixed association: the output bytes are a function of the inputs alone - equal between runs,
+ *     between eager and replayed calls, and to the restatement.
+ *   pr_worldmap_fuse      the host form: poses [keyframe_capacity][12] and n [1] are HOST arrays (NULL = the map's), runs the device path,
+ *                         synchronises, and copies info [4] and the first `rows written` rows into the host arrays xyz, inten, src, row,
+ *                         count (each of out_capacity rows).
+ *   pr_worldmap_count     synchronising read of rows written and flags (diagnostics).
+ * PR_EINVAL (text: pr_last_error) before any device is touched for a NULL handle, buffer or required pointer, cell not finite or <= 0,
+ * min_count < 1, keep outside {0, 1}, out_capacity < 1, a map of another context or of more than 2^29 points. */
+typedef struct pr_worldmap pr_worldmap;
+typedef struct pr_worldmap_buffers { double* xyz; float* inten; int64_t* src; int32_t* row; int32_t* count; int32_t* state; } pr_worldmap_buffers;
+enum { PR_WORLDMAP_OVERFLOW = 1, PR_WORLDMAP_SKIPPED = 2, PR_WORLDMAP_RANGE = 4, PR_WORLDMAP_TABLE = 8 };
+int pr_worldmap_create(pr_ctx* ctx, pr_map* map, const pr_worldmap_buffers* buffers, int64_t out_capacity, pr_worldmap** out);
+void pr_worldmap_destroy(pr_worldmap* wm);
+int64_t pr_worldmap_scratch_bytes(int32_t keyframe_capacity, int64_t point_capacity);
+int pr_worldmap_count(pr_worldmap* wm, int64_t* rows, int32_t* flags);
+int pr_worldmap_fuse_dev(pr_worldmap* wm, const double* d_poses, const int32_t* d_n, double cell, int32_t min_count, int32_t keep,
+                         int64_t* d_info);
+int pr_worldmap_fuse(pr_worldmap* wm, const double* poses, const int32_t* n, double cell, int32_t min_count, int32_t keep, double* xyz,
+                     float* inten, int64_t* src, int32_t* row, int32_t* count, int64_t* info);
 const char* pr_host_last_error(void);
 
 #ifdef __cplusplus

@@ -30,6 +30,7 @@ ONLINESET_FUSED, ONLINESET_DELIGHT = 0, 1             # pr_onlineset_create's ki
 ONLINESET_NB_FUSED, ONLINESET_NB_DELIGHT = 512, 64  # most workgroups of a pr_onlineset match's rows kernel (onlineset.hpp): 1 / 16 entries each per stride
 POSEGRAPH_OVERFLOW = 1                              # info[3] of a pr_posegraph add
 POSEGRAPH_MAX_K = 128                               # most slots of one pr_posegraph add
+WORLDMAP_OVERFLOW, WORLDMAP_SKIPPED, WORLDMAP_RANGE, WORLDMAP_TABLE = 1, 2, 4, 8   # flags of a pr_worldmap fuse (state[1], info[3])
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PR_AMD_LIB") or os.path.join(_HERE, "libpr_amd.so")   # PR_AMD_LIB: experiment builds only
@@ -248,6 +249,12 @@ SYMBOLS = {
     "pr_posegraph_add_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _dbl, _dbl, _vp]),
     "pr_posegraph_add": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _dbl, _dbl, _vp]),
     "pr_posegraph_relax_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "pr_worldmap_create": (C.c_int, [_vp, _vp, _vp, C.c_int64, C.POINTER(_vp)]),
+    "pr_worldmap_destroy": (None, [_vp]),
+    "pr_worldmap_scratch_bytes": (C.c_int64, [_i32, C.c_int64]),
+    "pr_worldmap_count": (C.c_int, [_vp, C.POINTER(C.c_int64), C.POINTER(_i32)]),
+    "pr_worldmap_fuse_dev": (C.c_int, [_vp, _vp, _vp, _dbl, _i32, _i32, _vp]),
+    "pr_worldmap_fuse": (C.c_int, [_vp, _vp, _vp, _dbl, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pr_host_last_error": (C.c_char_p, []),
 }
 
@@ -271,6 +278,11 @@ class OnlineSetBuffers(C.Structure):
 class PoseGraphBuffers(C.Structure):
     """pr_posegraph_buffers: the four caller-owned device buffers of a pr_posegraph."""
     _fields_ = [(n, _vp) for n in ("edge_ij", "edge_Z", "edge_w", "state")]
+
+
+class WorldMapBuffers(C.Structure):
+    """pr_worldmap_buffers: the six caller-owned device buffers of a pr_worldmap."""
+    _fields_ = [(n, _vp) for n in ("xyz", "inten", "src", "row", "count", "state")]
 
 
 class PoseGraphParams(C.Structure):

@@ -1766,6 +1766,135 @@ class PoseGraph:
             pass
 
 
+class WorldMap:
+    """pr_worldmap: all clouds of a KeyframeMap fused into ONE world-frame point set, one point per occupied voxel, under any pose array -
+    the map's own or the ones PoseGraph.relax_map returns.  The six buffers are zeroed torch tensors on the context's
+    device (or the caller's: buffers = dict of the six names): .xyz [out_capacity, 3] f64, .inten [out_capacity] f32, .src [out_capacity]
+    i64 (the point's index in the map), .row [out_capacity] i32 (its keyframe row), .count [out_capacity] i32 (the points of its voxel)
+    and .state [4] i32 = rows written, flags, 0, 0.  A fuse is a full rebuild by launches whose geometry depends on the create capacities
+    only and both counts are read on the device, so ONE captured fuse_torch serves every count; its bytes are a function of its inputs
+    alone.  All scratch is allocated here; the world map must be closed before its map."""
+
+    NAMES = ("xyz", "inten", "src", "row", "count", "state")
+    KEEP = {"first": 0, "last": 1}
+
+    def __init__(self, ctx: Context | None, km, out_capacity: int, buffers: dict | None = None):
+        import torch
+        self.ctx = ctx or default_context()
+        self.h = None
+        if km.ctx is not self.ctx:
+            raise ValueError("WorldMap: the world map and the map must share one context (one stream)")
+        self.lib = self.ctx.lib
+        self.km = km
+        self.out_capacity = int(out_capacity)
+        oc = max(self.out_capacity, 0)
+        dev = torch.device("cuda", self.ctx.device)
+        shapes = dict(xyz=((oc, 3), torch.float64), inten=((oc,), torch.float32), src=((oc,), torch.int64), row=((oc,), torch.int32),
+                      count=((oc,), torch.int32), state=((4,), torch.int32))
+        if buffers is None:
+            buffers = {n: torch.zeros(s, dtype=dt, device=dev) for n, (s, dt) in shapes.items()}
+        for n, (s, dt) in shapes.items():
+            t = buffers[n]
+            if (not t.is_cuda) or t.dtype != dt or not t.is_contiguous() or tuple(t.shape) != tuple(s):
+                raise ValueError(f"WorldMap: buffer {n} must be a contiguous CUDA tensor {dt} {list(s)}")
+            setattr(self, n, t)
+        torch.cuda.synchronize(dev)                       # torch's fills (its stream) before the library's stream writes the buffers
+        rec = _lib.WorldMapBuffers(*(C.c_void_p(getattr(self, n).data_ptr()) for n in self.NAMES))
+        h = C.c_void_p()
+        self.ctx.check(self.lib.pr_worldmap_create(self.ctx.h, km.h, C.byref(rec), self.out_capacity, C.byref(h)))
+        self.h = h
+
+    def _args(self, who, cell, min_count, keep):
+        """the checks both forms share, made before the library is called; -> (cell, min_count, keep code)"""
+        if keep not in self.KEEP:
+            raise ValueError(f"{who}: keep is 'first' or 'last'")
+        return float(cell), int(min_count), self.KEEP[keep]
+
+    def fuse_torch(self, poses=None, n=None, cell: float = 0.2, min_count: int = 1, keep: str = "first", info=None):
+        """Device form (pr_worldmap_fuse_dev): poses f64 [keyframe_capacity, 12] (world to camera; None = the map's own), n i32 [>= 1] whose
+        word 0 is the keyframe count (None = the map's state), both contiguous CUDA tensors on the map's device.  cell: the voxel's edge;
+        a voxel of fewer than min_count points is left out; keep = 'first' | 'last' picks a voxel's earliest or latest point.  Returns info
+        (device i64 [4]) = rows written, voxels that qualified, valid points, flags (WORLDMAP_*); the rows are .xyz[:rows] ... Enqueued
+        on the context's stream; nothing synchronises, nothing is allocated when info= is given."""
+        import torch
+        who = "WorldMap.fuse_torch"
+        cell, min_count, kcode = self._args(who, cell, min_count, keep)
+        dev = self.state.device
+        if poses is not None and ((not poses.is_cuda) or poses.device != dev or poses.dtype != torch.float64 or not poses.is_contiguous()
+                                  or tuple(poses.shape) != (self.km.keyframe_capacity, 12)):
+            raise ValueError(f"{who}: poses must be a contiguous CUDA tensor f64 [keyframe_capacity, 12] on the map's device")
+        if n is not None and ((not n.is_cuda) or n.device != dev or n.dtype != torch.int32 or not n.is_contiguous() or n.numel() < 1):
+            raise ValueError(f"{who}: n must be a CUDA tensor i32 [>= 1] on the map's device")
+        if info is None:
+            info = torch.empty(4, dtype=torch.int64, device=dev)
+        elif (not info.is_cuda) or info.device != dev or info.dtype != torch.int64 or not info.is_contiguous() or info.numel() != 4:
+            raise ValueError(f"{who}: info must be a CUDA tensor i64 [4] on the map's device")
+        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        self.ctx.check(self.lib.pr_worldmap_fuse_dev(self.h, p(poses), p(n), cell, min_count, kcode, p(info)))
+        return info
+
+    def fuse(self, poses=None, n=None, cell: float = 0.2, min_count: int = 1, keep: str = "first"):
+        """Host form (pr_worldmap_fuse; synchronises): poses a numpy array [keyframe_capacity, 12] or None, n an int or None.  Returns
+        (xyz [rows, 3] f64, inten [rows] f32, src [rows] i64, row [rows] i32, count [rows] i32, info [4] i64) as numpy arrays."""
+        who = "WorldMap.fuse"
+        cell, min_count, kcode = self._args(who, cell, min_count, keep)
+        po = None
+        if poses is not None:
+            po = np.ascontiguousarray(poses, np.float64)
+            if po.shape != (self.km.keyframe_capacity, 12):
+                raise ValueError(f"{who}: poses must be [keyframe_capacity, 12]")
+        nn = None if n is None else np.array([int(n)], np.int32)
+        oc = max(self.out_capacity, 0)
+        xyz, inten = np.zeros((oc, 3), np.float64), np.zeros(oc, np.float32)
+        src, row, count = np.zeros(oc, np.int64), np.zeros(oc, np.int32), np.zeros(oc, np.int32)
+        info = np.zeros(4, np.int64)
+        self.ctx.check(self.lib.pr_worldmap_fuse(self.h, _ptr(po), _ptr(nn), cell, min_count, kcode, _ptr(xyz), _ptr(inten), _ptr(src), _ptr(row),
+                                                 _ptr(count), _ptr(info)))
+        r = int(info[0])
+        return xyz[:r], inten[:r], src[:r], row[:r], count[:r], info
+
+    def rows(self):
+        """The rows the last fuse wrote, as host arrays (xyz, inten, src, row, count); synchronises."""
+        r, _ = self.count_rows()
+        return tuple(getattr(self, n)[:r].cpu().numpy() for n in self.NAMES[:5])
+
+    def write_ply(self, path: str, binary: bool = True) -> int:
+        """The rows of the last fuse as a PLY file (vertex properties x, y, z double, intensity float, count int; binary little endian
+        or ascii).  A debug aid: synchronises and copies to the host.  Returns the number of vertices."""
+        xyz, inten, _, _, count = self.rows()
+        r = len(inten)
+        rec = np.empty(r, np.dtype([("x", "<f8"), ("y", "<f8"), ("z", "<f8"), ("intensity", "<f4"), ("count", "<i4")]))
+        rec["x"], rec["y"], rec["z"], rec["intensity"], rec["count"] = xyz[:, 0], xyz[:, 1], xyz[:, 2], inten, count
+        head = ("ply\nformat %s 1.0\ncomment so_dso_place_recognition_amd world map\nelement vertex %d\nproperty double x\nproperty double y\n"
+                "property double z\nproperty float intensity\nproperty int count\nend_header\n"
+                % ("binary_little_endian" if binary else "ascii", r))
+        with open(path, "wb") as f:
+            f.write(head.encode("ascii"))
+            if binary:
+                f.write(rec.tobytes())
+            else:
+                for v in rec:
+                    f.write(("%r %r %r %r %d\n" % (float(v["x"]), float(v["y"]), float(v["z"]), float(v["intensity"]), int(v["count"]))).encode("ascii"))
+        return r
+
+    def count_rows(self):
+        """(rows written, flags) of the last fuse; synchronises (pr_worldmap_count)."""
+        r, f = C.c_int64(), C.c_int32()
+        self.ctx.check(self.lib.pr_worldmap_count(self.h, C.byref(r), C.byref(f)))
+        return int(r.value), int(f.value)
+
+    def close(self):
+        if getattr(self, "h", None) and getattr(self.ctx, "h", None):
+            self.lib.pr_worldmap_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def split_points_by_pose(pose_ids, point_ids) -> np.ndarray:
     """The reference's cursor rule (utils/pts_preprocess.h:196-200) as per-pose pushes: at pose p the cursor takes points while
     id <= pose id, so an out-of-order id makes it wait.  Returns cuts int64 [len(pose_ids) + 1]: pose p is pushed the points

@@ -464,4 +464,23 @@ inline size_t map_plan_words(int max_append) { return (size_t)MAP_PLAN_HEAD + 3 
 void launch_map_append(hipStream_t st, const MapView& v, const double* xyz, const float* inten, const int64_t* offs, const double* frames,
                        const double* poses, const int* ids, const int* emitted, int N, int64_t max_points, int* info);
 
+// worldmap.hip — the voxel fusion of a map's clouds into one world-frame point set.  WorldMapView: the caller's six
+// output buffers, the map's arrays it reads, the create sizes and the scratch of a pr_worldmap (worldmap.cpp), ONE allocation:
+//   slots [T][2] u64 (key, representative; cleared to all ones) | cnt [T] i32 | ctl [4] i32 (word 0: the call's flags) (cleared to zero) |
+//   slot_of [pcap] i32 (the point's slot, -1: not valid) | blk [2][nblk4] i32 (per 256 points: representatives that qualify, valid points;
+//   after the scan the first half holds the exclusive prefix) | the staging of the host form.
+// T = the smallest power of two >= max(2 pcap, 64), nblk = ceil(pcap / 256), nblk4 = nblk rounded up to 4.
+constexpr int WORLDMAP_OVERFLOW = 1, WORLDMAP_SKIPPED = 2, WORLDMAP_RANGE = 4, WORLDMAP_TABLE = 8;   // = PR_WORLDMAP_*
+constexpr int64_t WORLDMAP_MAX_POINTS = (int64_t)1 << 29;      // slot indices and prefixes are int32
+struct WorldMapView {
+  double* xyz; float* inten; int64_t* src; int* row; int* count; int* state;                // the six output buffers
+  const double* m_xyz; const float* m_inten; const int64_t* m_offs; const double* m_poses; const int* m_state;   // the map
+  int kcap, log2T, nblk;
+  int64_t pcap, ocap;
+  unsigned long long* slots; int* cnt; int* ctl; int* slot_of; int* blk;
+};
+inline int worldmap_log2T(int64_t pcap) { int l = 6; while (((int64_t)1 << l) < 2 * pcap) l++; return l; }
+hipError_t launch_worldmap_fuse(hipStream_t st, const WorldMapView& v, const double* poses, const int* n, double cell, int min_count,
+                                int keep, int64_t* info);
+
 }  // namespace pr
