@@ -1123,6 +1123,83 @@ int pr_worldmap_fuse_dev(pr_worldmap* wm, const double* d_poses, const int32_t* 
                          int64_t* d_info);
 int pr_worldmap_fuse(pr_worldmap* wm, const double* poses, const int32_t* n, double cell, int32_t min_count, int32_t keep, double* xyz,
                      float* inten, int64_t* src, int32_t* row, int32_t* count, int64_t* info);
+
+/* ---- the map localiser: scan-to-map registration against a world map through one shared voxel index (maploc.hip) -----
+ * A pr_worldmap fuse leaves one world-frame point per occupied voxel in caller-owned buffers.  A pr_maploc registers clouds - keyframes of
+ * this drive or of a later one over the same route - against those rows: ONE voxel hash index per fuse, shared by every pair of a call, a
+ * correspondence search through it that is exact within the radius, and the ICP update of pr_icp_pairs_dev on the same code.  Everything
+ * is stream-ordered, reads its counts on the device, allocates nothing after create and can be captured.
+ *
+ *   pr_maploc_create      takes the world map's buffer RECORD (not its handle) and reads only xyz [out_capacity][3] f64, row [out_capacity]
+ *                         i32 and state [4] i32; they must outlive the handle.  `cell` is fixed for the handle's life; the caller fuses
+ *                         with the same cell (a mismatch shows as PR_MAPLOC_DUPLICATE).  Allocates ALL scratch in one block; no later
+ *                         call allocates.  With T = the smallest power of two >= max(2 out_capacity, 64), ld = max(max_src_pts, 1),
+ *                         nchunks = ceil(ld / 256) and pc = pair_capacity the parts are, each rounded up to 16 bytes:
+ *                           16 T (the table: key u64, row u64) | 16 (control: flags, rows indexed) | 16 (offs2 [2] i64) | 4 pc (pair_dst,
+ *                           zeros) | 8 pc ld (nn_d) | 4 pc ld (nn_j) | 160 pc nchunks (chunk partials, 20 doubles each) | 4 pc (done) |
+ *                           16 pc (prev) | staging of the host forms: 24 pc ld (xyz_q) | 8 (pc + 1) (offs_q) | 4 pc (pair_src) | 96 pc (T)
+ *                           | 8 pc (excl) | 8 (pc + 1) (out_offs) | 32 pc (stats) | 32 (info)
+ *                         pr_maploc_scratch_bytes returns the sum (0 for sizes create refuses).
+ *   pr_maploc_index_dev   two memset nodes and two launches.  R = world.state[0] clamped into 0 .. out_capacity.  Row j < R is INDEXED iff
+ *                         its three coordinates are finite (otherwise PR_MAPLOC_SKIPPED), every c_a = floor(x_a / cell) with IEEE division
+ *                         lies in [-2^20, 2^20) - compared as a double before any conversion - (otherwise PR_MAPLOC_RANGE), and it is the
+ *                         smallest j of its key; the key is the three indices biased by 2^20, 21 bits each, packed into 63 bits (c_0
+ *                         highest) exactly as the world map packs it.  A key held by more than one row sets PR_MAPLOC_DUPLICATE: that
+ *                         cannot happen after a fuse at the same cell.  d_info [4] i64 = {rows indexed, R, flags, 0}; the flags are the
+ *                         call's, nothing is sticky; R = 0 gives an empty index.  An index is valid until the world buffers change:
+ *                         re-index after every fuse.  A stale index can return stale rows; it never forms an address outside
+ *                         xyz[0 .. out_capacity).  PR_MAPLOC_TABLE: the table's probe is bounded by T steps, past which the row is dropped
+ *                         with this flag; with T >= 2 out_capacity that cannot happen and no input makes a lane spin.
+ *   pr_maploc_nn_dev      one correspondence pass.  Pair p is off when d_pair_src[p] < 0 or >= Nq: its d_out_offs span is 0 long (in
+ *                         refine: PR_ICP_NO_PAIR, T0 and zeros - pr_icp_pairs_dev's convention).  A source cloud is read up to max_src_pts
+ *                         points.  p' = T s in pr_icp_pairs_dev's association; a non-finite p' has no correspondent; t_a = p'_a / cell by
+ *                         the index's division, and a t_a outside [-2^20 - 1, 2^20 + 1) - tested in floating point - has none either.
+ *                         Candidates: the indexed rows whose voxel differs from floor(t) by at most 1 per axis (27 keys; those outside
+ *                         the 21-bit range are dropped); with d_excl != NULL the rows with excl[p][0] <= world.row[j] <= excl[p][1] are
+ *                         dropped (lo > hi excludes nothing).  d2 = ((dx dx) + dy dy) + dz dz; "smaller d2, then smaller j"; a NaN or
+ *                         +Inf distance never wins; the result is (j, d2) where d2 < fl(max_corr^2) and (-1, +Inf) elsewhere, at
+ *                         d_out_offs[p] + i.  It equals the brute-force first-minimum scan over the indexed, non-excluded rows masked to
+ *                         the radius on every input, because max_corr (1 + 2^-10) <= cell is required.
+ *   pr_maploc_refine_dev  pr_icp_pairs_dev with this search against the one-cloud target {world.xyz, offs2 = {0, R}}: max_iter + 1 rounds
+ *                         of (pass with chunk sums of 256 source points, update); stop rules, statuses and pr_icp_stats unchanged; the
+ *                         bytes of pr_icp_pairs_dev under PR_ICP_SEARCH_GRID on the same target when nothing is excluded and no key is
+ *                         duplicated.  d_T_out may be d_T0.
+ *   pr_maploc_seed_dev    n = d_n[0] clamped into 0 .. keyframe_capacity.  Pair p is ON iff 0 <= d_idx[p] < n, d_accepted == NULL or
+ *                         d_accepted[p] != 0, the pose row's 12 entries are finite and d_T_rel == NULL or its 12 entries are finite.
+ *                         For a world-to-camera P = [R | t]: Rinv[a][b] = R[b][a], tinv_a = -((R[0][a] t0 + R[1][a] t1) + R[2][a] t2).
+ *                         d_T_rel == NULL: T0 = [Rinv | tinv].  Otherwise T0 = inv(P_idx) o T_rel: R0[a][b] = (Rinv[a][0] Rr[0][b] +
+ *                         Rinv[a][1] Rr[1][b]) + Rinv[a][2] Rr[2][b], t0_a = ((Rinv[a][0] tr0 + Rinv[a][1] tr1) + Rinv[a][2] tr2) + tinv_a,
+ *                         fp64 without contraction.  An ON pair writes d_pair_src[p] = d_src ? d_src[p] : p; an OFF pair -1 and T0 =
+ *                         identity.  (pr_verify_pairs_dev's T maps query-camera points into DB row idx's camera frame, so T0 maps them
+ *                         into the world.)
+ *   pr_maploc_index / _nn / _refine   the host forms: upload, run the device form, synchronise, read back.  Their staging is part of the
+ *                         one allocation, so Nq <= pair_capacity and offs_q[Nq] <= pair_capacity x ld are required.
+ *   pr_maploc_count       synchronising read of the last index's rows indexed and flags (diagnostics).
+ * PR_EINVAL (text: pr_last_error) before any device is touched for a NULL handle, record member or required pointer, out_capacity < 1 or
+ * > 2^29, cell not finite or <= 0, pair_capacity outside 1 .. 65535, max_src_pts outside 0 .. 2^26, c < 0 or > pair_capacity,
+ * keyframe_capacity < 1, max_iter < 0, max_corr not positive and finite, min_inliers < 3, a NaN tolerance, and max_corr (1 + 2^-10) >
+ * cell - the contract that makes the 27-voxel search exact. */
+typedef struct pr_maploc pr_maploc;
+enum { PR_MAPLOC_SKIPPED = 1, PR_MAPLOC_RANGE = 2, PR_MAPLOC_DUPLICATE = 4, PR_MAPLOC_TABLE = 8 };
+int pr_maploc_create(pr_ctx* ctx, const pr_worldmap_buffers* world, int64_t out_capacity, double cell, int32_t pair_capacity, int32_t max_src_pts,
+                     pr_maploc** out);
+void pr_maploc_destroy(pr_maploc* ml);
+int64_t pr_maploc_scratch_bytes(int64_t out_capacity, int32_t pair_capacity, int32_t max_src_pts);
+int pr_maploc_count(pr_maploc* ml, int64_t* rows_indexed, int32_t* flags);
+int pr_maploc_index_dev(pr_maploc* ml, int64_t* d_info);
+int pr_maploc_seed_dev(pr_maploc* ml, const double* d_poses, const int32_t* d_n, int32_t keyframe_capacity, const int32_t* d_idx,
+                       const uint8_t* d_accepted, const double* d_T_rel, const int32_t* d_src, int32_t c, double* d_T0, int32_t* d_pair_src);
+int pr_maploc_nn_dev(pr_maploc* ml, const double* d_xyz_q, const int64_t* d_offs_q, int32_t Nq, const int32_t* d_pair_src, int32_t c,
+                     const double* d_T, const int32_t* d_excl, double max_corr, int64_t* d_out_offs, int32_t* d_nn_idx, double* d_nn_d2);
+int pr_maploc_refine_dev(pr_maploc* ml, const double* d_xyz_q, const int64_t* d_offs_q, int32_t Nq, const int32_t* d_pair_src, int32_t c,
+                         const double* d_T0, const int32_t* d_excl, int32_t max_iter, double max_corr, double tol_rmse, double tol_fitness,
+                         int32_t min_inliers, double* d_T_out, pr_icp_stats* d_stats);
+int pr_maploc_index(pr_maploc* ml, int64_t* info);
+int pr_maploc_nn(pr_maploc* ml, const double* xyz_q, const int64_t* offs_q, int32_t Nq, const int32_t* pair_src, int32_t c, const double* T,
+                 const int32_t* excl, double max_corr, int64_t* out_offs, int32_t* nn_idx, double* nn_d2);
+int pr_maploc_refine(pr_maploc* ml, const double* xyz_q, const int64_t* offs_q, int32_t Nq, const int32_t* pair_src, int32_t c, const double* T0,
+                     const int32_t* excl, int32_t max_iter, double max_corr, double tol_rmse, double tol_fitness, int32_t min_inliers,
+                     double* T_out, pr_icp_stats* stats);
 const char* pr_host_last_error(void);
 
 #ifdef __cplusplus

@@ -31,6 +31,7 @@ ONLINESET_NB_FUSED, ONLINESET_NB_DELIGHT = 512, 64  # most workgroups of a pr_on
 POSEGRAPH_OVERFLOW = 1                              # info[3] of a pr_posegraph add
 POSEGRAPH_MAX_K = 128                               # most slots of one pr_posegraph add
 WORLDMAP_OVERFLOW, WORLDMAP_SKIPPED, WORLDMAP_RANGE, WORLDMAP_TABLE = 1, 2, 4, 8   # flags of a pr_worldmap fuse (state[1], info[3])
+MAPLOC_SKIPPED, MAPLOC_RANGE, MAPLOC_DUPLICATE, MAPLOC_TABLE = 1, 2, 4, 8           # flags of a pr_maploc index (info[2])
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PR_AMD_LIB") or os.path.join(_HERE, "libpr_amd.so")   # PR_AMD_LIB: experiment builds only
@@ -255,6 +256,17 @@ SYMBOLS = {
     "pr_worldmap_count": (C.c_int, [_vp, C.POINTER(C.c_int64), C.POINTER(_i32)]),
     "pr_worldmap_fuse_dev": (C.c_int, [_vp, _vp, _vp, _dbl, _i32, _i32, _vp]),
     "pr_worldmap_fuse": (C.c_int, [_vp, _vp, _vp, _dbl, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pr_maploc_create": (C.c_int, [_vp, _vp, C.c_int64, _dbl, _i32, _i32, C.POINTER(_vp)]),
+    "pr_maploc_destroy": (None, [_vp]),
+    "pr_maploc_scratch_bytes": (C.c_int64, [C.c_int64, _i32, _i32]),
+    "pr_maploc_count": (C.c_int, [_vp, C.POINTER(C.c_int64), C.POINTER(_i32)]),
+    "pr_maploc_index_dev": (C.c_int, [_vp, _vp]),
+    "pr_maploc_seed_dev": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp]),
+    "pr_maploc_nn_dev": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _dbl, _vp, _vp, _vp]),
+    "pr_maploc_refine_dev": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _dbl, _dbl, _dbl, _i32, _vp, _vp]),
+    "pr_maploc_index": (C.c_int, [_vp, _vp]),
+    "pr_maploc_nn": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _dbl, _vp, _vp, _vp]),
+    "pr_maploc_refine": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _dbl, _dbl, _dbl, _i32, _vp, _vp]),
     "pr_host_last_error": (C.c_char_p, []),
 }
 

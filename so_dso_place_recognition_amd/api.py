@@ -1895,6 +1895,233 @@ class WorldMap:
             pass
 
 
+class MapLocalizer:
+    """pr_maploc: scan-to-map registration against a WorldMap's rows.  One voxel hash index per fuse, shared by every pair
+    of a call; the correspondence search through it is exact within max_corr (which may not exceed cell / (1 + 2^-10)); the ICP update is
+    pr_icp_pairs_dev's.  `cell` is fixed here and must be the cell the world map is fused with (a mismatch shows as MAPLOC_DUPLICATE in
+    index's info).  Calls are enqueued on the context's stream, read their counts on the device and allocate no device scratch: index_torch
+    behind every fuse_torch, then seed_torch / refine_torch or localize_torch; all of them can be captured.  Close it before its world map."""
+
+    def __init__(self, ctx: Context | None, wm, cell: float, pair_capacity: int, max_src_pts: int):
+        self.ctx = ctx or default_context()
+        self.h = None
+        if wm.ctx is not self.ctx:
+            raise ValueError("MapLocalizer: the localiser and the world map must share one context (one stream)")
+        self.lib = self.ctx.lib
+        self.wm = wm
+        self.cell, self.pair_capacity, self.max_src_pts = float(cell), int(pair_capacity), int(max_src_pts)
+        rec = _lib.WorldMapBuffers(*(C.c_void_p(getattr(wm, n).data_ptr()) for n in wm.NAMES))
+        h = C.c_void_p()
+        self.ctx.check(self.lib.pr_maploc_create(self.ctx.h, C.byref(rec), wm.out_capacity, self.cell, self.pair_capacity, self.max_src_pts,
+                                                 C.byref(h)))
+        self.h = h
+
+    # ---- checks made before the library is called
+    def _t(self, who, name, t, dtype, shape=None, numel_min=None):
+        dev = self.wm.state.device
+        if (not t.is_cuda) or t.device != dev or t.dtype != dtype or not t.is_contiguous():
+            raise ValueError(f"{who}: {name} must be a contiguous CUDA tensor {dtype} on the world map's device")
+        if shape is not None and tuple(t.shape) != tuple(shape):
+            raise ValueError(f"{who}: {name} must be {list(shape)}")
+        if numel_min is not None and t.numel() < numel_min:
+            raise ValueError(f"{who}: {name} must have at least {numel_min} elements")
+        return t
+
+    def _pairs(self, who, xyz_q, offs_q, pair_src, T, excl):
+        import torch
+        self._t(who, "xyz_q", xyz_q, torch.float64)
+        self._t(who, "offs_q", offs_q, torch.int64, numel_min=1)
+        self._t(who, "pair_src", pair_src, torch.int32)
+        if xyz_q.dim() != 2 or xyz_q.shape[1] != 3 or offs_q.dim() != 1 or pair_src.dim() != 1:
+            raise ValueError(f"{who}: xyz_q must be [*, 3], offs_q [Nq + 1] and pair_src [c]")
+        c = pair_src.numel()
+        if c > self.pair_capacity:
+            raise ValueError(f"{who}: c={c} exceeds pair_capacity={self.pair_capacity}")
+        self._t(who, "T", T, torch.float64, (c, 3, 4))
+        if excl is not None:
+            self._t(who, "excl", excl, torch.int32, (c, 2))
+        return c
+
+    @staticmethod
+    def _p(t):
+        return None if t is None else C.c_void_p(t.data_ptr())
+
+    def index_torch(self, info=None):
+        """Device form (pr_maploc_index_dev): rebuilds the index from the world map's rows as they are on the stream; call it behind every
+        fuse_torch.  Returns info (device i64 [4]) = rows indexed, rows read, flags (MAPLOC_*), 0."""
+        import torch
+        who = "MapLocalizer.index_torch"
+        if info is None:
+            info = torch.empty(4, dtype=torch.int64, device=self.wm.state.device)
+        else:
+            self._t(who, "info", info, torch.int64, (4,))
+        self.ctx.check(self.lib.pr_maploc_index_dev(self.h, self._p(info)))
+        return info
+
+    def seed_torch(self, poses, n, idx, accepted=None, T_rel=None, src=None, out=None):
+        """Device form (pr_maploc_seed_dev): poses f64 [keyframe_capacity, 12] (world to camera: KeyframeMap.poses or the relaxed ones), n
+        i32 [>= 1] (KeyframeMap.state), idx i32 [c] map rows (a verify's idx, flattened, as it is), accepted bool / u8 [c] or None, T_rel
+        f64 [c, 3, 4] or None (a verify's T: query camera into row idx's camera), src i32 [c] or None (the pair's query cloud; None: p).
+        Returns (T0 f64 [c, 3, 4] mapping the query cloud into the world, pair_src i32 [c]; -1 and the identity where a pair is off)."""
+        import torch
+        who = "MapLocalizer.seed_torch"
+        self._t(who, "poses", poses, torch.float64)
+        if poses.dim() != 2 or poses.shape[1] != 12 or poses.shape[0] < 1:
+            raise ValueError(f"{who}: poses must be [keyframe_capacity, 12]")
+        self._t(who, "n", n, torch.int32, numel_min=1)
+        idx = idx.reshape(-1) if idx.is_contiguous() else idx
+        self._t(who, "idx", idx, torch.int32)
+        c = idx.numel()
+        if c > self.pair_capacity:
+            raise ValueError(f"{who}: c={c} exceeds pair_capacity={self.pair_capacity}")
+        if accepted is not None:
+            accepted = accepted.reshape(-1) if accepted.is_contiguous() else accepted
+            if accepted.dtype == torch.bool:
+                accepted = accepted.view(torch.uint8)
+            self._t(who, "accepted", accepted, torch.uint8, (c,))
+        if T_rel is not None:
+            T_rel = T_rel.reshape(-1, 3, 4) if T_rel.is_contiguous() else T_rel
+            self._t(who, "T_rel", T_rel, torch.float64, (c, 3, 4))
+        if src is not None:
+            self._t(who, "src", src, torch.int32, (c,))
+        dev = self.wm.state.device
+        if out is None:
+            out = (torch.empty((c, 3, 4), dtype=torch.float64, device=dev), torch.empty(c, dtype=torch.int32, device=dev))
+        else:
+            self._t(who, "out[0]", out[0], torch.float64, (c, 3, 4))
+            self._t(who, "out[1]", out[1], torch.int32, (c,))
+        p = self._p
+        self.ctx.check(self.lib.pr_maploc_seed_dev(self.h, p(poses), p(n), poses.shape[0], p(idx), p(accepted), p(T_rel), p(src), c, p(out[0]),
+                                                   p(out[1])))
+        return out
+
+    def nn_torch(self, xyz_q, offs_q, pair_src, T, excl=None, max_corr: float = 0.9, out=None):
+        """Device form (pr_maploc_nn_dev): one correspondence pass of the clouds (xyz_q f64 [*, 3], offs_q i64 [Nq + 1]) of pair_src i32 [c]
+        under T f64 [c, 3, 4]; excl i32 [c, 2] or None: world rows whose keyframe row lies in [lo, hi] are no candidates.  Returns
+        (out_offs i64 [c + 1], nn_idx i32 [c * max(max_src_pts, 1)], nn_d2 f64 [same]): pair p's points are rows out_offs[p] ..
+        out_offs[p + 1]; -1 / +Inf where no row lies within max_corr."""
+        import torch
+        who = "MapLocalizer.nn_torch"
+        c = self._pairs(who, xyz_q, offs_q, pair_src, T, excl)
+        dev = self.wm.state.device
+        rows = c * max(self.max_src_pts, 1)
+        if out is None:
+            out = (torch.empty(c + 1, dtype=torch.int64, device=dev), torch.empty(rows, dtype=torch.int32, device=dev),
+                   torch.empty(rows, dtype=torch.float64, device=dev))
+        else:
+            self._t(who, "out[0]", out[0], torch.int64, (c + 1,))
+            self._t(who, "out[1]", out[1], torch.int32, (rows,))
+            self._t(who, "out[2]", out[2], torch.float64, (rows,))
+        p = self._p
+        self.ctx.check(self.lib.pr_maploc_nn_dev(self.h, p(xyz_q), p(offs_q), offs_q.numel() - 1, p(pair_src), c, p(T), p(excl), float(max_corr),
+                                                 p(out[0]), p(out[1]), p(out[2])))
+        return out
+
+    def refine_torch(self, xyz_q, offs_q, pair_src, T0, excl=None, max_iter: int = 30, max_corr: float = 0.9, tol_rmse: float = 1e-6,
+                     tol_fitness: float = 1e-6, min_inliers: int = 3, out=None):
+        """Device form (pr_maploc_refine_dev): point-to-point ICP of every pair from its seed T0 f64 [c, 3, 4] against the world rows.
+        Returns (T f64 [c, 3, 4], stats u8 [c, 32] - ICP_STATS on the host); out: the pair an earlier call returned for the same c, written
+        again (fixed addresses: what a captured graph needs); out[0] may be T0."""
+        import torch
+        who = "MapLocalizer.refine_torch"
+        c = self._pairs(who, xyz_q, offs_q, pair_src, T0, excl)
+        dev = self.wm.state.device
+        if out is None:
+            out = (torch.empty((c, 3, 4), dtype=torch.float64, device=dev), torch.zeros((c, ICP_STATS.itemsize), dtype=torch.uint8, device=dev))
+        else:
+            self._t(who, "out[0]", out[0], torch.float64, (c, 3, 4))
+            self._t(who, "out[1]", out[1], torch.uint8, (c, ICP_STATS.itemsize))
+        p = self._p
+        self.ctx.check(self.lib.pr_maploc_refine_dev(self.h, p(xyz_q), p(offs_q), offs_q.numel() - 1, p(pair_src), c, p(T0), p(excl), int(max_iter),
+                                                     float(max_corr), float(tol_rmse), float(tol_fitness), int(min_inliers), p(out[0]),
+                                                     p(out[1])))
+        return out
+
+    def localize_torch(self, xyz_q, offs_q, poses, n, idx, accepted=None, T_rel=None, src=None, excl=None, max_iter: int = 30,
+                       max_corr: float = 0.9, tol_rmse: float = 1e-6, tol_fitness: float = 1e-6, min_inliers: int = 3, min_fitness: float = 0.5,
+                       max_rmse: float = 0.5, out=None):
+        """seed_torch -> refine_torch -> pr_verify_select_dev with one hypothesis, all on the context's stream without read-back.  Returns
+        (T f64 [c, 3, 4] query cloud into the world, stats u8 [c, 32], accepted bool [c] = converged or max_iter, fitness >= min_fitness
+        and rmse <= max_rmse).  out: the dict an earlier call left in .last_localize for the same c (fixed addresses for a capture)."""
+        import torch
+        who = "MapLocalizer.localize_torch"
+        c = idx.numel()
+        dev = self.wm.state.device
+        if out is None:
+            out = dict(seed=None, refine=None, T=torch.empty((c, 3, 4), dtype=torch.float64, device=dev),
+                       stats=torch.zeros((c, ICP_STATS.itemsize), dtype=torch.uint8, device=dev),
+                       accepted=torch.zeros(c, dtype=torch.bool, device=dev), hyp=torch.zeros(c, dtype=torch.int32, device=dev))
+        elif out["T"].shape != (c, 3, 4):
+            raise ValueError(f"{who}: out belongs to another c")
+        out["seed"] = self.seed_torch(poses, n, idx, accepted, T_rel, src, out=out["seed"])
+        T0, pair_src = out["seed"]
+        out["refine"] = self.refine_torch(xyz_q, offs_q, pair_src, T0, excl, max_iter, max_corr, tol_rmse, tol_fitness, min_inliers, out=out["refine"])
+        p = self._p
+        self.ctx.check(self.lib.pr_verify_select_dev(self.ctx.h, p(out["refine"][0]), p(out["refine"][1]), c, 1, float(min_fitness), float(max_rmse),
+                                                     p(out["T"]), p(out["stats"]), p(out["accepted"]), p(out["hyp"])))
+        self.last_localize = out
+        return out["T"], out["stats"], out["accepted"]
+
+    # ---- host forms (synchronise)
+    def index(self):
+        """Host form (pr_maploc_index): info i64 [4] as a numpy array."""
+        info = np.zeros(4, np.int64)
+        self.ctx.check(self.lib.pr_maploc_index(self.h, _ptr(info)))
+        return info
+
+    def _host_pairs(self, who, xyz_q, offs_q, pair_src, T, excl):
+        xq = np.ascontiguousarray(xyz_q, np.float64).reshape(-1, 3); oq = np.ascontiguousarray(offs_q, np.int64).reshape(-1)
+        ps = np.ascontiguousarray(pair_src, np.int32).reshape(-1)
+        if len(oq) < 1 or oq[-1] != len(xq):
+            raise ValueError(f"{who}: the clouds are a CSR set: xyz [offs[-1], 3] and offs [Nq + 1]")
+        c = len(ps)
+        T = np.ascontiguousarray(T, np.float64)
+        if T.size != 12 * c:
+            raise ValueError(f"{who}: T must be [c, 3, 4]")
+        ex = None
+        if excl is not None:
+            ex = np.ascontiguousarray(excl, np.int32)
+            if ex.shape != (c, 2):
+                raise ValueError(f"{who}: excl must be [c, 2]")
+        return xq, oq, ps, c, T.reshape(c, 3, 4), ex
+
+    def nn(self, xyz_q, offs_q, pair_src, T, excl=None, max_corr: float = 0.9):
+        """Host form (pr_maploc_nn) over numpy arrays: (out_offs i64 [c + 1], nn_idx i32 [out_offs[-1]], nn_d2 f64 [same])."""
+        xq, oq, ps, c, T, ex = self._host_pairs("MapLocalizer.nn", xyz_q, offs_q, pair_src, T, excl)
+        Nq = len(oq) - 1
+        total = int(sum(min(int(oq[s + 1] - oq[s]), self.max_src_pts) for s in ps if 0 <= s < Nq))
+        out_offs = np.zeros(c + 1, np.int64); idx = np.empty(total, np.int32); d2 = np.empty(total, np.float64)
+        self.ctx.check(self.lib.pr_maploc_nn(self.h, _ptr(xq), _ptr(oq), Nq, _ptr(ps), c, _ptr(T), _ptr(ex), float(max_corr), _ptr(out_offs),
+                                             _ptr(idx), _ptr(d2)))
+        return out_offs, idx, d2
+
+    def refine(self, xyz_q, offs_q, pair_src, T0, excl=None, max_iter: int = 30, max_corr: float = 0.9, tol_rmse: float = 1e-6,
+               tol_fitness: float = 1e-6, min_inliers: int = 3):
+        """Host form (pr_maploc_refine) over numpy arrays: (T f64 [c, 3, 4], stats [c] of dtype ICP_STATS)."""
+        xq, oq, ps, c, T0, ex = self._host_pairs("MapLocalizer.refine", xyz_q, offs_q, pair_src, T0, excl)
+        T = np.empty((c, 3, 4)); stats = np.zeros(c, ICP_STATS)
+        self.ctx.check(self.lib.pr_maploc_refine(self.h, _ptr(xq), _ptr(oq), len(oq) - 1, _ptr(ps), c, _ptr(T0), _ptr(ex), int(max_iter),
+                                                 float(max_corr), float(tol_rmse), float(tol_fitness), int(min_inliers), _ptr(T), _ptr(stats)))
+        return T, stats
+
+    def count(self):
+        """(rows indexed, flags) of the last index; synchronises (pr_maploc_count)."""
+        r, f = C.c_int64(), C.c_int32()
+        self.ctx.check(self.lib.pr_maploc_count(self.h, C.byref(r), C.byref(f)))
+        return int(r.value), int(f.value)
+
+    def close(self):
+        if getattr(self, "h", None) and getattr(self.ctx, "h", None):
+            self.lib.pr_maploc_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def split_points_by_pose(pose_ids, point_ids) -> np.ndarray:
     """The reference's cursor rule (utils/pts_preprocess.h:196-200) as per-pose pushes: at pose p the cursor takes points while
     id <= pose id, so an out-of-order id makes it wait.  Returns cuts int64 [len(pose_ids) + 1]: pose p is pushed the points

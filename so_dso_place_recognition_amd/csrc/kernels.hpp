@@ -483,4 +483,34 @@ inline int worldmap_log2T(int64_t pcap) { int l = 6; while (((int64_t)1 << l) < 
 hipError_t launch_worldmap_fuse(hipStream_t st, const WorldMapView& v, const double* poses, const int* n, double cell, int min_count,
                                 int keep, int64_t* info);
 
+// maploc.hip — scan-to-map registration against a world map's rows through ONE voxel hash index shared by every pair.
+// MapLocView: the three world buffers it reads, the create sizes and the scratch of a pr_maploc (maploc.cpp), ONE allocation:
+//   table [T][2] u64 (key, smallest row; cleared to all ones) | ctl [4] i32 (the call's flags, rows indexed; cleared to zero) | offs2 [2]
+//   i64 = {0, R} | pair_dst [pair_capacity] i32 zeros | nn_d, nn_j [pair_capacity][ld] | part [pair_capacity][nchunks][ICP_PARTIAL] | done
+//   [pair_capacity] | prev [pair_capacity][2] | the staging of the host forms.
+// T = the smallest power of two >= max(2 out_capacity, 64), ld = max(max_src_pts, 1), nchunks = ceil(ld / 256).
+constexpr int MAPLOC_SKIPPED = 1, MAPLOC_RANGE = 2, MAPLOC_DUPLICATE = 4, MAPLOC_TABLE = 8;          // = PR_MAPLOC_*
+constexpr int64_t MAPLOC_MAX_ROWS = (int64_t)1 << 29;
+constexpr double MAPLOC_SLACK = 1.0 + 0x1p-10;                   // cell >= max_corr * MAPLOC_SLACK
+struct MapLocView {
+  const double* xyz; const int* row; const int* state;          // of the world map (caller-owned)
+  int64_t ocap;
+  double cell;
+  int log2T, pair_cap, max_src, ld, nchunks;
+  unsigned long long* table; int* ctl; int64_t* offs2; int* pair_dst;
+  double* nn_d; int* nn_j; double* part; int* done; double* prev;
+};
+inline int maploc_log2T(int64_t ocap) { int l = 6; while (((int64_t)1 << l) < 2 * ocap) l++; return l; }
+// the target of every pair: the world rows as a one-cloud set
+inline IcpClouds maploc_clouds(const MapLocView& v, const double* xyz_q, const int64_t* offs_q, int Nq, const int32_t* pair_src, int c) {
+  return IcpClouds{xyz_q, offs_q, Nq, v.xyz, v.offs2, 1, pair_src, v.pair_dst, c, v.max_src, (int)v.ocap};
+}
+hipError_t launch_maploc_index(hipStream_t st, const MapLocView& v, int64_t* info);
+// one pass under T [c][3][4]: results at base[pair] (or pair * ld); excl (or null) [c][2]; done (or null): pairs to skip; part (or null)
+// [c][nchunks][ICP_PARTIAL]: the sums of chunks of 256 points (icp_common.hpp's chunk_sums)
+void launch_maploc_probe(hipStream_t st, const MapLocView& v, const IcpClouds& A, const double* T, const int32_t* excl, const int* done,
+                         const long long* base, double* nn_d, int* nn_j, double mc2, double* part);
+void launch_maploc_seed(hipStream_t st, const double* poses, const int* n, int kcap, const int32_t* idx, const unsigned char* accepted,
+                        const double* T_rel, const int32_t* src, int c, double* T0, int32_t* pair_src);
+
 }  // namespace pr
