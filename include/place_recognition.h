@@ -392,6 +392,15 @@ int pr_fuse_select_dev(pr_ctx* ctx, const float* d_p, const float* d_i, int32_t 
 int pr_fuse_select_f64_dev(pr_ctx* ctx, const float* d_p, const float* d_i, int32_t m, int32_t n,
                            const double* mom_all, int32_t G, int32_t q_row0, int32_t db_row0, int32_t mask_width,
                            double p_weight, int32_t k, int32_t* idx, float* score, double* score64);
+/* pr_row_moments_dev + pr_fuse_select_f64_dev of ONE shard (G = 1) in one call: mom [m][2][3], idx, score, score64 [m][k] come out bit
+ * for bit as from the two calls.  Whole-row selections of up to 16 results (the k + 8 of the fp32-grade arithmetics; more rows than
+ * the sliced form takes, rows longer than the one-wave form's) read the distances ONCE: the candidates are collected in the sweep that
+ * accumulates the moments, and a row whose collected set does not provably hold its k best is swept a second time.
+ * PR_SELECT_FUSED=0 in the environment (read once) keeps the two passes.
+ * pr_select_fallback_rows: the rows that took the second sweep since the last call of it (synchronises the stream; clears the count). */
+int pr_moments_select_f64_dev(pr_ctx* ctx, const float* d_p, const float* d_i, int32_t m, int32_t n, double* mom, int32_t q_row0,
+                              int32_t db_row0, int32_t mask_width, double p_weight, int32_t k, int32_t* idx, float* score, double* score64);
+int pr_select_fallback_rows(pr_ctx* ctx, int64_t* rows);
 int pr_fuse_select2_f64_dev(pr_ctx* ctx, const float* d_p, const float* d_i, const float* e_p, const float* e_i, int32_t m, int32_t n,
                             const double* mom_all, const double* mom2_all, int32_t G, int32_t q_row0, int32_t db_row0,
                             int32_t mask_width, double p_weight, int32_t k, int32_t* idx, float* score, double* score64);

@@ -160,6 +160,8 @@ SYMBOLS = {
     "pr_sigset_image": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_size_t), C.POINTER(_i32)]),
     "pr_distances_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "pr_row_moments_dev": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp]),
+    "pr_moments_select_f64_dev": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _dbl, _i32, _vp, _vp, _vp]),
+    "pr_select_fallback_rows": (C.c_int, [_vp, C.POINTER(C.c_int64)]),
     "pr_fuse_select_dev": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _dbl, _i32, _vp, _vp]),
     "pr_sc_generate_dev": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _dbl, _vp]),
     "pr_m2dp_generate_dev": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _dbl, _vp]),

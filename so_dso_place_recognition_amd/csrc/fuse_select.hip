@@ -8,6 +8,7 @@
 //                 fused = p_weight*(d_p-mean_p)/std_p + (d_i-mean_i)/std_i  (run_test.m:40), +Inf where
 //                 |i-j| < mask_width on GLOBAL indices (:47-53), and selects the k smallest (value, index)
 //                 pairs in lexicographic order, i.e. ties go to the lower index like MATLAB min (:57).
+#include <cmath>
 #include <cstdlib>
 
 #include "div_rn.hpp"
@@ -30,46 +31,59 @@ __device__ __forceinline__ double block_sum(double v, double* red, int tid) {
   return r;
 }
 
+// One channel's shifted sums of a row (S1, S2, count about the pivot c), every thread of the workgroup getting all three: row_moments_kernel's
+// body, which moments_select_kernel also runs on rows whose two channels are not co-aligned.
+__device__ __forceinline__ double moments_pivot(float r0) {
+  return (r0 == r0) ? (double)r0 : 0.5;                  // NaN first element: any pivot inside the data range will do
+}
+// NaN entries (distances to / from a zero-norm signature, processSC.m:16,19) are left out of the row statistics,
+// as MATLAB's normalize(.,2) does (mean / std with 'omitnan') [from memory; the reference cannot be run here]
+__device__ __forceinline__ void moments_acc(float v, double c, double& s1, double& s2, double& cnt) {
+  if (v == v) { const double d = (double)v - c; s1 += d; s2 += d * d; cnt += 1.0; }
+}
+__device__ __forceinline__ void moments_store(double* __restrict__ o, double c, double S1, double S2, double N) {
+  o[0] = N;
+  o[1] = N > 0.0 ? c + S1 / N : 0.0;
+  o[2] = N > 0.0 ? S2 - S1 * S1 / N : 0.0;
+}
+__device__ __forceinline__ void moments_channel(const float* __restrict__ row, int n, double* red, int tid, double& c_out, double& S1, double& S2,
+                                                double& N) {
+  // ONE pass over the row: sums of (d - c) and (d - c)^2 in fp64 about the pivot c = first element of the row (distances
+  // are fp32 in [0, 1], so with c inside the data range the M2 = S2 - S1^2/n cancellation costs < 1e-13 relative), fixed
+  // reduction tree -> deterministic.
+  const double c = moments_pivot(row[0]);
+  double s1 = 0.0, s2 = 0.0, cnt = 0.0;
+  auto acc = [&](float v) { moments_acc(v, c, s1, s2, cnt); };
+  // 16-byte loads over the aligned body of the row (4 of them in flight per thread), scalars on the ragged ends
+  int head = (int)((4 - ((reinterpret_cast<size_t>(row) >> 2) & 3)) & 3);
+  if (head > n) head = n;
+  const int nv = (n - head) >> 2;
+  if (tid < head) acc(row[tid]);
+  const f32x4* rv4 = reinterpret_cast<const f32x4*>(row + head);
+  int j = tid;
+  for (; j + 768 < nv; j += 1024) {
+    const f32x4 a = rv4[j], b = rv4[j + 256], c4 = rv4[j + 512], d4 = rv4[j + 768];
+    acc(a[0]); acc(a[1]); acc(a[2]); acc(a[3]);
+    acc(b[0]); acc(b[1]); acc(b[2]); acc(b[3]);
+    acc(c4[0]); acc(c4[1]); acc(c4[2]); acc(c4[3]);
+    acc(d4[0]); acc(d4[1]); acc(d4[2]); acc(d4[3]);
+  }
+  for (; j < nv; j += 256) { const f32x4 a = rv4[j]; acc(a[0]); acc(a[1]); acc(a[2]); acc(a[3]); }
+  for (int t = head + 4 * nv + tid; t < n; t += 256) acc(row[t]);
+  S1 = block_sum(s1, red, tid);
+  S2 = block_sum(s2, red, tid);
+  N = block_sum(cnt, red, tid);
+  c_out = c;
+}
+
 __global__ __launch_bounds__(256) void row_moments_kernel(const float* __restrict__ d_p, const float* __restrict__ d_i,
                                                            int n, double* __restrict__ mom) {
   __shared__ double red[256];
   const int tid = threadIdx.x, q = blockIdx.x;
   for (int ch = 0; ch < 2; ch++) {
-    // ONE pass over the row: sums of (d - c) and (d - c)^2 in fp64 about the pivot c = first element of the row (distances
-    // are fp32 in [0, 1], so with c inside the data range the M2 = S2 - S1^2/n cancellation costs < 1e-13 relative), fixed
-    // reduction tree -> deterministic.
-    const float* row = (ch ? d_i : d_p) + (size_t)q * n;
-    const float r0 = row[0];
-    const double c = (r0 == r0) ? (double)r0 : 0.5;      // NaN first element: any pivot inside the data range will do
-    double s1 = 0.0, s2 = 0.0, cnt = 0.0;
-    // NaN entries (distances to / from a zero-norm signature, processSC.m:16,19) are left out of the row statistics,
-    // as MATLAB's normalize(.,2) does (mean / std with 'omitnan') [from memory; the reference cannot be run here]
-    auto acc = [&](float v) { if (v == v) { const double d = (double)v - c; s1 += d; s2 += d * d; cnt += 1.0; } };
-    // 16-byte loads over the aligned body of the row (4 of them in flight per thread), scalars on the ragged ends
-    int head = (int)((4 - ((reinterpret_cast<size_t>(row) >> 2) & 3)) & 3);
-    if (head > n) head = n;
-    const int nv = (n - head) >> 2;
-    if (tid < head) acc(row[tid]);
-    const f32x4* rv4 = reinterpret_cast<const f32x4*>(row + head);
-    int j = tid;
-    for (; j + 768 < nv; j += 1024) {
-      const f32x4 a = rv4[j], b = rv4[j + 256], c4 = rv4[j + 512], d4 = rv4[j + 768];
-      acc(a[0]); acc(a[1]); acc(a[2]); acc(a[3]);
-      acc(b[0]); acc(b[1]); acc(b[2]); acc(b[3]);
-      acc(c4[0]); acc(c4[1]); acc(c4[2]); acc(c4[3]);
-      acc(d4[0]); acc(d4[1]); acc(d4[2]); acc(d4[3]);
-    }
-    for (; j < nv; j += 256) { const f32x4 a = rv4[j]; acc(a[0]); acc(a[1]); acc(a[2]); acc(a[3]); }
-    for (int t = head + 4 * nv + tid; t < n; t += 256) acc(row[t]);
-    const double S1 = block_sum(s1, red, tid);
-    const double S2 = block_sum(s2, red, tid);
-    const double N = block_sum(cnt, red, tid);
-    if (tid == 0) {
-      double* o = mom + ((size_t)q * 2 + ch) * 3;
-      o[0] = N;
-      o[1] = N > 0.0 ? c + S1 / N : 0.0;
-      o[2] = N > 0.0 ? S2 - S1 * S1 / N : 0.0;
-    }
+    double c, S1, S2, N;
+    moments_channel((ch ? d_i : d_p) + (size_t)q * n, n, red, tid, c, S1, S2, N);
+    if (tid == 0) moments_store(mom + ((size_t)q * 2 + ch) * 3, c, S1, S2, N);
   }
 }
 
@@ -282,6 +296,32 @@ struct SelLds {
   int last;
 };
 
+// The k best of the LDS list lv / lj[0, L) (lj < 0: no entry) by (score, index), one workgroup arg-min round each, emitted in ascending
+// order (-1 where the list runs out); kv / kj: the k-th one (kj < 0: fewer than k entries).  Selected entries are struck from the list.
+template <typename E>
+__device__ __forceinline__ void argmin_rounds(const double* lv, int* lj, int L, int k, double* rv, int* rj, int tid, E&& emit, double& kv, int& kj) {
+  kv = 0.0; kj = -1;
+  for (int t = 0; t < k; t++) {
+    double cv = 0.0;
+    int cj = -1, cs = -1;
+    for (int s = tid; s < L; s += 256)
+      if (lj[s] >= 0 && (cj < 0 || cand_less(lv[s], lj[s], cv, cj))) { cv = lv[s]; cj = lj[s]; cs = s; }
+    rv[tid] = cv; rj[tid] = cj;
+    block_argmin(rv, rj, tid);
+    const double wv = rv[0];
+    const int wj = rj[0];
+    __syncthreads();
+    if (cs >= 0 && cj == wj) lj[cs] = -1;                                          // global indices are unique within a row
+    if (tid == 0) emit(t, wv, wj);
+    kv = wv; kj = wj;
+    if (wj < 0) {
+      if (tid == 0) for (int u = t + 1; u < k; u++) emit(u, 0.0, -1);
+      break;
+    }
+    __syncthreads();
+  }
+}
+
 template <int CAP>
 __device__ __forceinline__ void select_row(const float* __restrict__ d_p, const float* __restrict__ d_i,
                                            const float* __restrict__ e_p, const float* __restrict__ e_i,
@@ -289,7 +329,8 @@ __device__ __forceinline__ void select_row(const float* __restrict__ d_p, const 
                                            int m, int n, const double* __restrict__ mom_all, int G,
                                            int q_row0, int db_row0, int mask_width, double p_weight,
                                            int k, int32_t* __restrict__ idx, float* __restrict__ score, int P,
-                                           double* __restrict__ score64, SelLds<CAP>& W) {
+                                           double* __restrict__ score64, SelLds<CAP>& W, bool have_st = false) {
+  // have_st: W.st[0..3] hold the row's (mean, std) per channel already (moments_select_kernel, which formed them itself)
   double* st = W.st;
   double* rv = W.rv;
   int* rj = W.rj;
@@ -301,7 +342,7 @@ __device__ __forceinline__ void select_row(const float* __restrict__ d_p, const 
   const int tid = threadIdx.x, q = blockIdx.x;
   const bool plain = (d_i == nullptr);   // single distance matrix, no z-score fusion (run_test.m types other than m2dp/sc)
   const bool two = (e_p != nullptr);
-  if (!plain && tid < (two ? 4 : 2)) {  // Chan's parallel combination of the shard moments, fixed (rank) order
+  if (!plain && !have_st && tid < (two ? 4 : 2)) {  // Chan's parallel combination of the shard moments, fixed (rank) order
     double cn = 0.0, mean = 0.0, m2 = 0.0;
     for (int g = 0; g < G; g++) {
       const double* o = (tid < 2 ? mom_all : mom2_all) + (((size_t)g * m + q) * 2 + (tid & 1)) * 3;
@@ -547,24 +588,9 @@ __device__ __forceinline__ void select_row(const float* __restrict__ d_p, const 
     return;
   }
   if (L <= CAP) {
-    for (int t = 0; t < k; t++) {
-      double cv = 0.0;
-      int cj = -1, cs = -1;
-      for (int s = tid; s < L; s += 256)
-        if (lj[s] >= 0 && (cj < 0 || cand_less(lv[s], lj[s], cv, cj))) { cv = lv[s]; cj = lj[s]; cs = s; }
-      rv[tid] = cv; rj[tid] = cj;
-      block_argmin(rv, rj, tid);
-      const double wv = rv[0];
-      const int wj = rj[0];
-      __syncthreads();
-      if (cs >= 0 && cj == wj) lj[cs] = -1;                                          // global indices are unique within a row
-      if (tid == 0) emit(t, wv, wj);
-      if (wj < 0) {
-        if (tid == 0) for (int u = t + 1; u < k; u++) emit(u, 0.0, -1);
-        break;
-      }
-      __syncthreads();
-    }
+    double kv;
+    int kj;
+    argmin_rounds(lv, lj, L, k, rv, rj, tid, emit, kv, kj);
     return;
   }
   // ---- fallback: one pass per selected element
@@ -860,6 +886,243 @@ __global__ FS_BOUNDS void fuse_select_kernel(const float* __restrict__ d_p, cons
   select_row<CAP>(d_p, d_i, e_p, e_i, mom2_all, m, n, mom_all, G, q_row0, db_row0, mask_width, p_weight, k, idx, score, P, score64, L);
 }
 
+// ------------------------------------------------------------------------------------------- moments and selection in ONE sweep of the row
+// row_moments_kernel and fuse_select_kernel read the two distance matrices from HBM back to back: the score needs (mean, std), which
+// only a finished pass over the row gives.  A candidate set can be bounded without them.  The score
+//     F(d_p, d_i) = p * div_rn(d_p - m_p, s_p) + div_rn(d_i - m_i, s_i)
+// is NON-DECREASING in d_p and in d_i when p > 0 and both stds are positive normal numbers: the widening to fp64 and the rounded fp64
+// subtraction of a constant are non-decreasing, so is a correctly rounded division by a positive number (div_rn.hpp gives the IEEE
+// quotient), so is the rounded multiplication by p > 0, and so is the final fp64 addition (fused with the multiplication or not: one or
+// two monotone roundings).  Hence an element above a corner (t_p, t_i) in BOTH channels scores at least F(t_p, t_i), whatever the
+// row's statistics turn out to be, and the elements with d_p <= t_p or d_i <= t_i - an L-shaped region, a few percent of the row with
+// t_p, t_i low sample quantiles - are a superset of the top-k as soon as the k-th best of them scores STRICTLY below F(t_p, t_i) (a tie
+// does not do: an element outside the region with the same score and a lower index would precede it).
+// One 256-thread workgroup per row:
+//   (a) t_p, t_i: per channel the mean over the four waves of the rank-th smallest of a wave's 64 thread minima over the row's first
+//       256 samp columns (masked entries and NaN left out: a self-match's near-copies around the diagonal would pull the corner under
+//       the whole row) - the launcher picks samp and rank so that about 5/8 CAP elements are expected in the region; they steer the
+//       cost only;
+//   (b) one sweep, loads in flight as select_row's sweep_if has them: the shifted sums of both channels in row_moments_kernel's order
+//       per thread (head, j = tid, tid + 256, ..., ragged tail; NaN left out), and the region's elements (d_p, d_i, j) compacted by
+//       ballot into the wave's quarter of the LDS list (no atomics; lv's 8 bytes hold the two floats);
+//   (c) the six sums through block_sum as row_moments_kernel has them -> mom, bit for bit; (mean, std) as select_row combines them;
+//   (d) the list scored, its entries below F(t_p, t_i) (NaN and masked ones struck) moved to the front, their k best by (score, index)
+//       in k arg-min rounds;
+//   (e) accepted when no quarter overflowed and the k-th score is finite and strictly below F(t_p, t_i).
+// Otherwise - and for rows whose std is zero, denormal or not finite, for p <= 0, and for rows whose channels are not co-aligned (the
+// moments' element-to-thread order follows each channel's own alignment) - the same workgroup runs select_row on the row: one more
+// sweep.  `fell` counts those rows.  Rows that fit the list (n <= CAP) go to select_row's whole-row form directly.
+__device__ __forceinline__ void chan_first(double nb, double mb, double m2b, double& mean_o, double& sd_o) {   // select_row's combination, G = 1
+  double cn = 0.0, mean = 0.0, m2 = 0.0;
+  if (!(nb <= 0.0)) {
+    const double tot = cn + nb, delta = mb - mean;
+    mean += delta * (nb / tot);
+    m2 += m2b + delta * delta * (cn * nb / tot);
+    cn = tot;
+  }
+  mean_o = mean;
+  sd_o = sqrt(m2 / (cn - 1.0));
+}
+
+template <int CAP>
+__global__ FS_BOUNDS void moments_select_kernel(const float* __restrict__ d_p, const float* __restrict__ d_i, int m, int n,
+                                                double* __restrict__ mom, int q_row0, int db_row0, int mask_width, double p_weight, int k,
+                                                int32_t* __restrict__ idx, float* __restrict__ score, double* __restrict__ score64,
+                                                int samp, int rank, unsigned long long* __restrict__ fell) {
+  __shared__ SelLds<CAP> W;
+  constexpr int SEG = CAP / 4;                          // a wave's part of the list
+  const int tid = threadIdx.x, q = blockIdx.x, wave = tid >> 6;
+  const float* rp = d_p + (size_t)q * n;
+  const float* ri = d_i + (size_t)q * n;
+  const bool listed = n > CAP && !((reinterpret_cast<size_t>(rp) ^ reinterpret_cast<size_t>(ri)) & 15);
+  const int ig = q_row0 + q;
+  auto masked = [&](int j) {
+    int dij = ig - (db_row0 + j);
+    if (dij < 0) dij = -dij;
+    return dij < mask_width;
+  };
+  double cp, ci, S1p, S2p, Np, S1i, S2i, Ni;
+  float tp = __builtin_inff(), ti = __builtin_inff();
+  if (listed) {
+    // ---- (a)
+    float mnp = __builtin_inff(), mni = __builtin_inff();
+    for (int u = 0; u < samp; u++) {                    // (256 samp <= 4096 < n)
+      const int j = tid + 256 * u;
+      const float vp = rp[j], vi = ri[j];
+      if (!masked(j)) { if (vp < mnp) mnp = vp; if (vi < mni) mni = vi; }
+    }
+    // every wave: the rank-th smallest of its 64 lanes' minima, by counting the minima in front of the lane's own over v_readlane (ties
+    // broken by lane: exactly one lane, if any; fewer than rank minima: +Inf); the corner is the mean of the four waves' values.  (Counting
+    // among all 256 minima through LDS cost a quarter of what the sweep's arithmetic costs.)
+    const int lane = tid & 63;
+    auto ranked = [&](float mine) -> float {
+      int before = 0;
+#pragma unroll
+      for (int u = 0; u < 64; u++) {
+        const float o = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, mine), u));
+        before += (o < mine || (o == mine && u < lane)) ? 1 : 0;
+      }
+      const unsigned long long hit = __builtin_amdgcn_ballot_w64(mine < __builtin_inff() && before == rank - 1);
+      return hit ? __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, mine), __ffsll((long long)hit) - 1)) : __builtin_inff();
+    };
+    const float wtp = ranked(mnp), wti = ranked(mni);
+    float* sm = reinterpret_cast<float*>(W.rv);
+    if (lane == 0) { sm[2 * wave] = wtp; sm[2 * wave + 1] = wti; }
+    __syncthreads();
+    tp = ((sm[0] + sm[2]) + (sm[4] + sm[6])) * 0.25f; ti = ((sm[1] + sm[3]) + (sm[5] + sm[7])) * 0.25f;
+    __syncthreads();                                    // (rv is the reduction buffer of (c))
+    // ---- (b)
+    // moments_acc without its branch: a NaN element enters as the pivot itself, d = 0 - and s1 + 0 = s1 (s1 is never -0: it starts at
+    // +0, and x - x = +0), fma(0, 0, s2) = s2 bit for bit; the count per WAVE, a scalar population count of the comparison's mask (the
+    // tree adds exact integers: N is the row's count however it is spread over the threads).  6 vector instructions per element and
+    // channel instead of 12 (three selected doubles): this sweep is bound by its VALU work, not by HBM
+    const float fp = rp[0] == rp[0] ? rp[0] : 0.5f, fi = ri[0] == ri[0] ? ri[0] : 0.5f;
+    cp = moments_pivot(rp[0]); ci = moments_pivot(ri[0]);                       // (= (double)fp, (double)fi)
+    double s1p = 0.0, s2p = 0.0, s1i = 0.0, s2i = 0.0;
+    int np = 0, ni = 0;                                 // (wave-uniform)
+    auto acc = [](bool valid, float v, float cf, double c, double& s1, double& s2, int& cnt) {
+      const bool ok = valid && v == v;
+      const double d = (double)(ok ? v : cf) - c;
+      s1 += d; s2 += d * d; cnt += __popcll(__builtin_amdgcn_ballot_w64(ok));
+    };
+    int wcnt = 0;                                       // entries of this wave's quarter so far (wave-uniform)
+    float* lpair = reinterpret_cast<float*>(W.lv) + 2 * wave * SEG;      // (d_p, d_i) of entry s in the 8 bytes of lv[s]
+    int* lidx = W.lj + wave * SEG;
+    // all 64 lanes of a wave call step() together (the loops below have workgroup-uniform trip counts): the ballot compacts
+    auto step = [&](bool valid, float vp, float vi, int j) {
+      acc(valid, vp, fp, cp, s1p, s2p, np); acc(valid, vi, fi, ci, s1i, s2i, ni);
+      const bool in = valid && (vp <= tp || vi <= ti);
+      // (the two comparisons' masks or-ed as scalars: a ballot of `in` itself goes through a vector select and a comparison)
+      const unsigned long long mk = __builtin_amdgcn_ballot_w64(valid && vp <= tp) | __builtin_amdgcn_ballot_w64(valid && vi <= ti);
+      if (mk) {
+        if (in) {
+          const int slot = wcnt + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mk >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mk, 0u));
+          if (slot < SEG) { lpair[2 * slot] = vp; lpair[2 * slot + 1] = vi; lidx[slot] = j; }
+        }
+        wcnt += __popcll(mk);
+      }
+    };
+    int head = (int)((4 - ((reinterpret_cast<size_t>(rp) >> 2) & 3)) & 3);     // (n > CAP > head)
+    const int nv = (n - head) >> 2;
+    const f32x4* rp4 = reinterpret_cast<const f32x4*>(rp + head);
+    const f32x4* ri4 = reinterpret_cast<const f32x4*>(ri + head);
+    if (head > 0) { const bool v = tid < head; step(v, v ? rp[tid] : 0.f, v ? ri[tid] : 0.f, tid); }
+    auto four = [&](bool v, const f32x4& a, const f32x4& b, int j) {
+      const int j0 = head + 4 * j;
+#pragma unroll
+      for (int e = 0; e < 4; e++) step(v, a[e], b[e], j0 + e);
+    };
+    int jb = 0;                                         // first vector of the round (workgroup-uniform); this thread's is jb + tid
+    const int rounds = nv >> 10;                        // rounds of 1024 vectors that are full for every thread
+    if (rounds > 0) {
+      // the next round's eight loads are requested before the present round is worked on; two register sets take turns (no copies)
+      struct Round { f32x4 a0, a1, a2, a3, b0, b1, b2, b3; };
+      auto load = [&](Round& R, int j) {
+        R.a0 = rp4[j]; R.a1 = rp4[j + 256]; R.a2 = rp4[j + 512]; R.a3 = rp4[j + 768];
+        R.b0 = ri4[j]; R.b1 = ri4[j + 256]; R.b2 = ri4[j + 512]; R.b3 = ri4[j + 768];
+      };
+      auto work = [&](const Round& R, int j) {
+        four(true, R.a0, R.b0, j); four(true, R.a1, R.b1, j + 256); four(true, R.a2, R.b2, j + 512); four(true, R.a3, R.b3, j + 768);
+      };
+      Round A, B;
+      int j = tid, r = 0;
+      load(A, j);
+      for (;;) {
+        const bool mb = r + 1 < rounds;
+        load(B, mb ? j + 1024 : j);                     // (the last round re-requests its own lines: no branch around the loads)
+        work(A, j);
+        r++; j += 1024;
+        if (!mb) break;
+        const bool ma = r + 1 < rounds;
+        load(A, ma ? j + 1024 : j);
+        work(B, j);
+        r++; j += 1024;
+        if (!ma) break;
+      }
+      jb = rounds << 10;
+    }
+    const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
+    for (; jb < nv; jb += 256) {
+      const int j = jb + tid;
+      const bool v = j < nv;
+      const f32x4 a = v ? rp4[j] : z4, b = v ? ri4[j] : z4;
+      four(v, a, b, j);
+    }
+    for (int t0 = head + 4 * nv; t0 < n; t0 += 256) {
+      const int t = t0 + tid;
+      const bool v = t < n;
+      step(v, v ? rp[t] : 0.f, v ? ri[t] : 0.f, t);
+    }
+    if ((tid & 63) == 0) W.ctl[wave] = wcnt;
+    // ---- (c)
+    const bool first = (tid & 63) == 0;
+    S1p = block_sum(s1p, W.rv, tid); S2p = block_sum(s2p, W.rv, tid); Np = block_sum(first ? (double)np : 0.0, W.rv, tid);
+    S1i = block_sum(s1i, W.rv, tid); S2i = block_sum(s2i, W.rv, tid); Ni = block_sum(first ? (double)ni : 0.0, W.rv, tid);
+  } else {
+    moments_channel(rp, n, W.rv, tid, cp, S1p, S2p, Np);
+    moments_channel(ri, n, W.rv, tid, ci, S1i, S2i, Ni);
+  }
+  if (tid == 0) {
+    moments_store(mom + (size_t)q * 6, cp, S1p, S2p, Np);
+    moments_store(mom + (size_t)q * 6 + 3, ci, S1i, S2i, Ni);
+  }
+  if (tid < 2) {
+    const double c = tid ? ci : cp, S1 = tid ? S1i : S1p, S2 = tid ? S2i : S2p, N = tid ? Ni : Np;
+    double o[3];
+    moments_store(o, c, S1, S2, N);
+    chan_first(o[0], o[1], o[2], W.st[tid * 2], W.st[tid * 2 + 1]);
+  }
+  if (tid == 0) W.lcnt = 0;
+  __syncthreads();
+  auto emit = [&](int t, double v, int jg) {
+    idx[(size_t)q * k + t] = jg;
+    const float f32 = (jg >= 0) ? (float)v : __builtin_nanf("");
+    score[(size_t)q * k + t] = f32;
+    score64[(size_t)q * k + t] = (double)f32;
+  };
+  if (listed) {
+    const double mp = W.st[0], sp = W.st[1], mi = W.st[2], si = W.st[3];
+    const bool fastdiv = sp > 1e-290 && sp < 1e290 && si > 1e-290 && si < 1e290;
+    const int fill = max(max(W.ctl[0], W.ctl[1]), max(W.ctl[2], W.ctl[3]));
+    if (fastdiv && p_weight > 0.0 && fill <= SEG) {
+      const double rsp = 1.0 / sp, rsi = 1.0 / si;
+      // ---- (d): select_row's score (its fastdiv form) of every entry.  Only entries that score strictly below the corner can be among
+      // the k best of an accepted row (its k-th is), NaN and masked ones never: those few - some dozens of the ~2500 - are moved to the
+      // front of the list, 256 slots per step: the barrier between a step's reads and its writes keeps a write (position < entries
+      // seen so far) off every slot not yet read.  The arg-min rounds then scan dozens of entries instead of the whole list.
+      auto F = [&](float vp, float vi) -> double { return p_weight * div_rn((double)vp - mp, sp, rsp) + div_rn((double)vi - mi, si, rsi); };
+      const double Fc = F(tp, ti);                                        // (NaN without a corner: nothing is below it)
+      const float* pairs = reinterpret_cast<const float*>(W.lv);
+      for (int u = 0; u < CAP / 256; u++) {
+        const int w = (u * 256) / SEG, o = u * 256 - w * SEG;             // (workgroup-uniform)
+        if (o >= W.ctl[w]) continue;
+        const int s = u * 256 + tid;
+        double f = 0.0;
+        int jg = -1;
+        if (o + tid < W.ctl[w]) {
+          const int j = W.lj[s];
+          const double fs = F(pairs[2 * s], pairs[2 * s + 1]);
+          if (fs < Fc && !masked(j)) { f = fs; jg = db_row0 + j; }
+        }
+        __syncthreads();
+        if (jg >= 0) {
+          const int slot = atomicAdd(&W.lcnt, 1);
+          W.lv[slot] = f; W.lj[slot] = jg;
+        }
+      }
+      __syncthreads();
+      double kv;
+      int kj;
+      argmin_rounds(W.lv, W.lj, W.lcnt, k, W.rv, W.rj, tid, emit, kv, kj);
+      // ---- (e)
+      if (kj >= 0 && kv < Fc) return;
+      __syncthreads();
+    }
+  }
+  if (n > CAP && tid == 0 && fell) atomicAdd(fell, 1ull);
+  select_row<CAP>(d_p, d_i, nullptr, nullptr, nullptr, m, n, nullptr, 1, q_row0, db_row0, mask_width, p_weight, k, idx, score, 1, score64, W, true);
+}
+
 }  // namespace
 
 // slices per row for m query rows of n columns: 1 = one workgroup per row (enough rows to fill the chip, or short rows)
@@ -890,6 +1153,40 @@ void launch_row_moments(hipStream_t st, const float* d_p, const float* d_i, int 
   hipLaunchKernelGGL(row_moments_kernel, dim3(m), dim3(256), 0, st, d_p, d_i, n, mom);
 }
 
+// whole rows short enough for the one-wave-per-row selection
+static bool wave_form(int m, int n, int k) {
+  static const bool wave_rows = !(getenv("PR_SELECT_WAVE") && atoi(getenv("PR_SELECT_WAVE")) == 0);     // A/B: PR_SELECT_WAVE=0
+  static const int wave_max_n = getenv("PR_SELECT_WAVE_N") ? atoi(getenv("PR_SELECT_WAVE_N")) : 32768;
+  return wave_rows && n <= wave_max_n && k <= 16 && m >= 64;
+}
+
+void launch_moments_select(hipStream_t st, const float* d_p, const float* d_i, int m, int n, double* mom, int q_row0, int db_row0,
+                           int mask_width, double p_weight, int k, int32_t* idx, float* score, double* score64, void* scratch,
+                           unsigned long long* fell) {
+  if (m <= 0) return;
+  static const bool fused = !(getenv("PR_SELECT_FUSED") && atoi(getenv("PR_SELECT_FUSED")) == 0);       // A/B: PR_SELECT_FUSED=0
+  // the fused kernel exactly where launch_fuse_select would run the whole-row fuse_select_kernel with a k + 8 list (its slices and the
+  // moments' are the same P for k <= 16); everything else through the two launchers
+  if (!fused || k > 16 || (scratch ? select_slices(m, n) : 1) > 1 || wave_form(m, n, k)) {
+    launch_row_moments(st, d_p, d_i, m, n, mom, scratch);
+    launch_fuse_select(st, d_p, d_i, m, n, mom, 1, q_row0, db_row0, mask_width, p_weight, k, idx, score, nullptr, nullptr, nullptr, scratch, score64);
+    return;
+  }
+  // the corner (moments_select_kernel (a)): a fraction f = T / (2 n) of each channel, about T = 5/8 FS_CAP elements in the region (half
+  // the list left ~24 elements under the corner for uniform independent channels at n = 100k, too few for k = 16 one row in fourteen;
+  // 5/8 leaves ~37, and the list overflows only when the sample overestimates f by 1.6).  Among ns = 256 samp sampled columns D = f ns
+  // lie below the corner; they fall into about 256 (1 - exp(-D / 256)) different threads, a quarter of them in each wave: the
+  // threshold is that rank among a wave's 64 thread minima.  samp: the largest power of two up to 16 that keeps D <= 80 (rank <= 17 of 64).
+  constexpr double T = FS_CAP * 5.0 / 8.0;
+  int samp = 16;
+  while (samp > 1 && 128.0 * samp * T / n > 80.0) samp >>= 1;
+  const double D = 128.0 * samp * T / n;
+  int rank = (int)std::lround(samp > 1 ? 64.0 * (1.0 - std::exp(-D / 256.0)) : D / 4.0);
+  rank = rank < 1 ? 1 : (rank > 32 ? 32 : rank);
+  hipLaunchKernelGGL(moments_select_kernel<FS_CAP>, dim3(m), dim3(256), 0, st, d_p, d_i, m, n, mom, q_row0, db_row0, mask_width, p_weight, k, idx,
+                     score, score64, samp, rank, fell);
+}
+
 void launch_fuse_select(hipStream_t st, const float* d_p, const float* d_i, int m, int n, const double* mom_all,
                         int G, int q_row0, int db_row0, int mask_width, double p_weight, int k, int32_t* idx,
                         float* score, const float* e_p, const float* e_i, const double* mom2_all, void* scratch, double* score64) {
@@ -909,9 +1206,7 @@ void launch_fuse_select(hipStream_t st, const float* d_p, const float* d_i, int 
     hipLaunchKernelGGL(slice_merge_kernel, dim3(m), dim3(256), (size_t)N * 8, st, sidx, ssc, P, m, k, idx, score, score64);
     return;
   }
-  static const bool wave_rows = !(getenv("PR_SELECT_WAVE") && atoi(getenv("PR_SELECT_WAVE")) == 0);     // A/B: PR_SELECT_WAVE=0
-  static const int wave_max_n = getenv("PR_SELECT_WAVE_N") ? atoi(getenv("PR_SELECT_WAVE_N")) : 32768;
-  if (wave_rows && !e_p && n <= wave_max_n && k <= 16 && m >= 64) {       // short rows: one wave per row (fuse_select_wave_kernel)
+  if (!e_p && wave_form(m, n, k)) {                                       // short rows: one wave per row (fuse_select_wave_kernel)
     hipLaunchKernelGGL(fuse_select_wave_kernel, dim3((m + 3) / 4), dim3(256), 0, st, d_p, d_i, m, n, mom_all, G, q_row0, db_row0, mask_width,
                        p_weight, k, idx, score, score64);
     return;

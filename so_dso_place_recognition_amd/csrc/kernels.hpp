@@ -147,6 +147,11 @@ void launch_fuse_select(hipStream_t st, const float* d_p, const float* d_i, int 
                         int G, int q_row0, int db_row0, int mask_width, double p_weight, int k, int32_t* idx,
                         float* score, const float* e_p = nullptr, const float* e_i = nullptr, const double* mom2_all = nullptr, void* scratch = nullptr,
                         double* score64 = nullptr /* the same scores widened to f64 [m][k] */);
+// launch_row_moments + launch_fuse_select of one shard (G = 1, one channel pair) - in ONE sweep of the rows (moments_select_kernel) where
+// the selection is the whole-row one with up to 16 results; mom, idx, score, score64 come out bit for bit as from the two calls.
+// fell (device, or null): += the rows the fused kernel answered through a second sweep
+void launch_moments_select(hipStream_t st, const float* d_p, const float* d_i, int m, int n, double* mom, int q_row0, int db_row0, int mask_width,
+                           double p_weight, int k, int32_t* idx, float* score, double* score64, void* scratch, unsigned long long* fell);
 
 // rerank.hip — NaN rows / columns of zero-norm signatures (processSC.m:16,19), the fp64 re-evaluation of the fp32
 // selection's survivors (processSC.m:15-33 / processM2DP.m:12-22 + run_test.m:40 per pair) and the k-way shard merge

@@ -31,6 +31,7 @@ struct pr_ctx {
   hipEvent_t ev_b = nullptr;
   char* sc_scratch = nullptr;    // tickets + partial moments / bin grids of the split SC generation, one half per stream
   void* sel_scratch = nullptr;   // slice lists / partial moments of calls with few query rows (fuse_select.hip)
+  unsigned long long* d_sel_fell = nullptr;   // rows moments_select_kernel answered through a second sweep (pr_select_fallback_rows)
   double* rr_scratch = nullptr;  // candidate scores of pr_rerank_dev (grow-only: a steady-state call allocates nothing and can be graph-captured)
   size_t rr_cap = 0;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
@@ -238,6 +239,8 @@ static int create_common(int device_id, hipStream_t external, bool use_external,
     TRY(hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming));
     for (auto& e : ctx->ev_m2) TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     TRY(hipMalloc(&ctx->sel_scratch, pr::select_scratch_bytes()));
+    TRY(hipMalloc((void**)&ctx->d_sel_fell, sizeof(unsigned long long)));
+    TRY(hipMemset(ctx->d_sel_fell, 0, sizeof(unsigned long long)));
     TRY(hipMalloc((void**)&ctx->d_flags, 8 * sizeof(int)));        // [4]: the binary-channel pass's violation flag (kernels.hpp: ScBin), not a deferred bit
     TRY(hipMemset(ctx->d_flags, 0, 8 * sizeof(int)));
     TRY(hipMalloc((void**)&ctx->d_svd_rows, (1 + pr::M2DP_SVD_ROWS_CAP) * sizeof(int)));
@@ -372,6 +375,7 @@ void pr_destroy(pr_ctx* ctx) {
   if (ctx->xqspec) (void)hipFree(ctx->xqspec);
   if (ctx->xpart) (void)hipFree(ctx->xpart);
   if (ctx->sel_scratch) (void)hipFree(ctx->sel_scratch);
+  if (ctx->d_sel_fell) (void)hipFree(ctx->d_sel_fell);
   if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
   if (ctx->ev_join) (void)hipEventDestroy(ctx->ev_join);
   for (auto& e : ctx->ev_m2) if (e) (void)hipEventDestroy(e);
@@ -896,6 +900,26 @@ int pr_fuse_select_f64_dev(pr_ctx* ctx, const float* d_p, const float* d_i, int3
   return fuse_select_impl(ctx, d_p, d_i, m, n, mom_all, G, q_row0, db_row0, mask_width, p_weight, k, idx, score, score64);
 }
 
+int pr_moments_select_f64_dev(pr_ctx* ctx, const float* d_p, const float* d_i, int32_t m, int32_t n, double* mom, int32_t q_row0,
+                              int32_t db_row0, int32_t mask_width, double p_weight, int32_t k, int32_t* idx, float* score, double* score64) {
+  if (!ctx || !d_p || !d_i || !mom || !idx || !score || !score64 || m < 0 || n < 1 || k < 1) return PR_EINVAL;
+  if (int rc = set_device(ctx)) return rc;
+  pr::launch_moments_select(ctx->stream, d_p, d_i, m, n, mom, q_row0, db_row0, mask_width, p_weight, k, idx, score, score64, ctx->sel_scratch,
+                            ctx->d_sel_fell);
+  PR_HIP(ctx, hipGetLastError());
+  return PR_OK;
+}
+int pr_select_fallback_rows(pr_ctx* ctx, int64_t* rows) {
+  if (!ctx || !rows) return PR_EINVAL;
+  if (int rc = set_device(ctx)) return rc;
+  unsigned long long h = 0;
+  PR_HIP(ctx, hipMemcpyAsync(&h, ctx->d_sel_fell, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
+  PR_HIP(ctx, hipMemsetAsync(ctx->d_sel_fell, 0, sizeof h, ctx->stream));
+  PR_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  *rows = (int64_t)h;
+  return PR_OK;
+}
+
 static int fuse_select2_impl(pr_ctx* ctx, const float* d_p, const float* d_i, const float* e_p, const float* e_i, int32_t m, int32_t n,
                              const double* mom_all, const double* mom2_all, int32_t G, int32_t q_row0, int32_t db_row0,
                              int32_t mask_width, double p_weight, int32_t k, int32_t* idx, float* score, double* score64) {
@@ -1294,9 +1318,9 @@ struct Desc {
       case DISTANCES:
         PR_HIP(ctx, dp.alloc((size_t)m * n * 4));
         if (type != PR_TYPE_DELIGHT) PR_HIP(ctx, di.alloc((size_t)m * n * 4));
+        if (type != PR_TYPE_DELIGHT) PR_HIP(ctx, mom.alloc((size_t)m * 6 * 8));
         return pr_distances_dev(ctx, sq.s, sdb.s, dp.as<float>(), di.as<float>());
     }
-    PR_HIP(ctx, mom.alloc((size_t)m * 6 * 8));
     return pr_row_moments_dev(ctx, dp.as<float>(), di.as<float>(), m, n, mom.as<double>());
   }
 };
@@ -1381,18 +1405,21 @@ int plain_topk(pr_ctx* ctx, const float* dist, int32_t m, int32_t n, int32_t mas
 // select -> widen -> rerank -> order-resolve over the query rows [i0, i0 + len) of T's matrices (q_row0: the first one's row number, which
 // only the mask reads), as wide as the context's arithmetic wants; the top-k goes to b.kidx / b.ksc.  Queries whose re-evaluated order hangs
 // on the pass's sigmas get their row statistics in fp64 - in PR_SC_ARITH_F16 the margin check takes the flags instead (f16_fallback).
+// One descriptor type: its moments are still to be formed (the callers stop at DISTANCES) - pr_moments_select_f64_dev writes them in the
+// selection's own sweep; the fused pair comes with both types' moments.
 int topk_core(pr_ctx* ctx, Types& T, int32_t i0, int32_t len, int32_t n, int32_t q_row0, int32_t mask_width, double p_weight, int32_t k,
               TopkBufs& b) {
   const int kin = rerank_width(k, ctx->sc_mode);
   const size_t o = (size_t)i0 * n;
   Desc &sc = T.t[0], &m2 = T.t[1], &one = sc.type >= 0 ? sc : m2;
-  int rc = sc.type >= 0 && m2.type >= 0
+  const bool both = sc.type >= 0 && m2.type >= 0;
+  int rc = both
       ? pr_fuse_select2_dev(ctx, sc.dp.as<float>() + o, sc.di.as<float>() + o, m2.dp.as<float>() + o, m2.di.as<float>() + o, len, n, T.mom(0, i0),
                             T.mom(1, i0), 1, q_row0, 0, mask_width, p_weight, kin, b.idx.as<int32_t>(), b.sc.as<float>())
-      : pr_fuse_select_dev(ctx, one.dp.as<float>() + o, one.di.as<float>() + o, len, n, one.mom.as<double>() + (size_t)i0 * 6, 1, q_row0, 0,
-                           mask_width, p_weight, kin, b.idx.as<int32_t>(), b.sc.as<float>());
+      : pr_moments_select_f64_dev(ctx, one.dp.as<float>() + o, one.di.as<float>() + o, len, n, one.mom.as<double>() + (size_t)i0 * 6, q_row0, 0,
+                                  mask_width, p_weight, kin, b.idx.as<int32_t>(), b.sc.as<float>(), b.sw.as<double>());
   if (rc) return rc;
-  if ((rc = pr_widen_scores_dev(ctx, b.sc.as<float>(), (int64_t)len * kin, b.sw.as<double>()))) return rc;
+  if (both && (rc = pr_widen_scores_dev(ctx, b.sc.as<float>(), (int64_t)len * kin, b.sw.as<double>()))) return rc;
   if ((rc = T.dev(pr_rerank_dev, ctx, i0, len, n, 1, q_row0, 0, mask_width, p_weight, kin, b.idx.as<int32_t>(), b.sw.as<double>(), k,
                   b.kidx.as<int32_t>(), b.ksc.as<double>())))
     return rc;
@@ -1430,7 +1457,11 @@ int f16_fallback(pr_ctx* ctx, Types& T, int32_t m, int32_t n, int32_t mask_width
     for (int32_t r = 0; r < mf; r++) memcpy(rows[i].data() + (size_t)r * sig, T.t[i].hq + (size_t)F[r] * sig, sig * 8);
     Desc& d = R.add(T.t[i].type, rows[i].data(), nullptr);
     d.db = T.t[i].db;
-    for (int s = CREATE; s <= MOMENTS; s++)
+  }
+  const int last = (T.t[0].type >= 0 && T.t[1].type >= 0) ? MOMENTS : DISTANCES;   // (one type: topk_core forms the moments)
+  for (Desc& d : R.t) {
+    if (d.type < 0) continue;
+    for (int s = CREATE; s <= last; s++)
       if (int rc = d.step(ctx, s, mf, n)) return rc;
   }
   // the flagged queries in RUNS: a query's own row number only enters through the mask (run_test.m:47-53), so without a mask the whole list
@@ -1485,7 +1516,7 @@ int topk_host(pr_ctx* ctx, const char* who, int type, const double* a1, const do
   Types T;
   T.add(fused ? PR_TYPE_SC : type, a1, a2);
   if (fused) T.add(PR_TYPE_M2DP, b1, b2);
-  if (int rc = T.prepare(ctx, m, n, plain ? DISTANCES : MOMENTS)) return rc;
+  if (int rc = T.prepare(ctx, m, n, fused ? MOMENTS : DISTANCES)) return rc;   // (one type: topk_core forms the moments)
   if (plain) return plain_topk(ctx, T.t[0].dp.as<float>(), m, n, mask_width, p_weight, k, idx, score);
   TopkBufs top;
   if (int rc = top.alloc(ctx, m, rerank_width(k, ctx->sc_mode), k)) return rc;

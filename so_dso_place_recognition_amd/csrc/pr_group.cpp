@@ -421,18 +421,24 @@ static int match_topk_impl(pr_group* g, const double* h1, int32_t m, int32_t mas
     if (g->timing) G_HIP(g, hipEventRecord(sh.ph[PH_MATCH], sh.stream));
     G_PR(g, sh, pr_distances_dev(sh.ctx, sh.q, sh.db, sh.d_p, sh.d_i));
     if (g->timing) G_HIP(g, hipEventRecord(sh.ph[PH_MOMENTS], sh.stream));
-    G_PR(g, sh, pr_row_moments_dev(sh.ctx, sh.d_p, sh.d_i, m, sh.rows, sh.mom));
+    if (G > 1) G_PR(g, sh, pr_row_moments_dev(sh.ctx, sh.d_p, sh.d_i, m, sh.rows, sh.mom));   // (one shard: step 2 forms them in its own sweep)
   }
   if (int rc = mark(PH_GATHER_A)) return rc;
   std::vector<const void*> src(G);
   std::vector<void*> dst(G);
   // A. moments of every shard on every device
   for (int r = 0; r < G; r++) { src[r] = g->s[r].mom; dst[r] = g->s[r].mom_all; }
-  if (int rc = exchange(g, src, dst, (size_t)m * 6 * 8)) return rc;
+  if (G > 1)
+    if (int rc = exchange(g, src, dst, (size_t)m * 6 * 8)) return rc;
   if (int rc = mark(PH_SELECT)) return rc;
   // 2. per-shard fp32 selection with the whole row's statistics
   for (auto& sh : g->s) {
     G_HIP(g, hipSetDevice(sh.device));
+    if (G == 1) {                                              // moments and selection in one sweep of the distances
+      G_PR(g, sh, pr_moments_select_f64_dev(sh.ctx, sh.d_p, sh.d_i, m, sh.rows, sh.mom_all, 0, sh.row0, mask_width, p_weight, kin, sh.idx_in,
+                                            sh.sc32, sh.sc64));
+      continue;
+    }
     G_PR(g, sh, pr_fuse_select_dev(sh.ctx, sh.d_p, sh.d_i, m, sh.rows, sh.mom_all, G, 0, sh.row0, mask_width, p_weight, kin, sh.idx_in, sh.sc32));
     G_PR(g, sh, pr_widen_scores_dev(sh.ctx, sh.sc32, (int64_t)m * kin, sh.sc64));
   }

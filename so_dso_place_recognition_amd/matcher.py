@@ -200,11 +200,18 @@ class _Base:
         return self._twin
 
     # ---- the protocol (module docstring): phase 1 is the subclass's, everything after it is written here once
-    def local_select(self, mom_all: torch.Tensor, G: int, mask_width, p_weight, k, db_row0, q_row0):
-        """fp32 selection of this shard's k + 8 best with the moments of all shards -> (idx_in i32 [m,kin], score f64 [m,kin])."""
+    def local_select(self, mom_all: torch.Tensor, G: int, mask_width, p_weight, k, db_row0, q_row0, with_moments: bool = False):
+        """fp32 selection of this shard's k + 8 best with the moments of all shards -> (idx_in i32 [m,kin], score f64 [m,kin]).
+        with_moments (one shard, one descriptor type, after local_phase1(moments=False)): mom_all [1, m, 2, 3] is still to be written -
+        pr_moments_select_f64_dev forms the moments in the selection's own sweep of the distances."""
         m, n = self._m, self.n
         stores = self.descs
-        if len(stores) == 1:          # one descriptor type: its moments [G, m, 2, 3] as they are
+        if with_moments:
+            assert G == 1 and len(stores) == 1 and not self.plain and mom_all.is_contiguous()
+            stores[0]._mom = mom_all
+            lib = self.lib
+            select = lambda h, d_p, d_i, m_, n_, mom, G_, *rest: lib.pr_moments_select_f64_dev(h, d_p, d_i, m_, n_, mom, *rest)
+        elif len(stores) == 1:        # one descriptor type: its moments [G, m, 2, 3] as they are
             stores[0]._mom = mom_all.contiguous()
             select = self.lib.pr_fuse_select_f64_dev
         else:                         # SC + M2DP: [G, m, 4, 3] split per type
@@ -359,8 +366,10 @@ class _Base:
         resolve = ((self.exact_moments, self.exact_select, self.exact_merge, lambda: self._exact_passes(exact_order))
                    if (exact_order and not self.plain and not f16) else None)
         post = (lambda cand_sc, idx, score: self._margin(*self._moms(), self._args[0], p_weight, cand_sc, k, score)) if f16 else None
-        idx, score = sharded_topk(lambda: self.local_phase1(*queries),
-                                  lambda mom_all, G_: self.local_select(mom_all, G_, mask_width, p_weight, k, db_row0, q_row0),
+        # one shard of one descriptor type: the moments come out of the selection's sweep (pr_moments_select_f64_dev), phase 1 leaves them out
+        one = G == 1 and not force_exchange and not self.plain and len(self.descs) == 1 and self.descs[0] is self
+        idx, score = sharded_topk((lambda: self.local_phase1(*queries, moments=False)) if one else (lambda: self.local_phase1(*queries)),
+                                  lambda mom_all, G_: self.local_select(mom_all, G_, mask_width, p_weight, k, db_row0, q_row0, with_moments=one),
                                   k, group if (G > 1 or force_exchange) else None, G, merge=self.merge, force_exchange=force_exchange,
                                   rerank=None if self.plain else self.local_rerank, finish=self.finish, post=post, resolve=resolve, mark=mark)
         if f16 and f16_fallback:
@@ -587,8 +596,9 @@ class Matcher(_Base):
         self.n += k
         self.db_sig = self._raw[:self.n * self.rows_per_sig]       # (a new view object: a split-f16 twin of the f16 arithmetic is re-packed when next needed)
 
-    def local_phase1(self, queries: torch.Tensor):
-        """pack(q) + distances + row moments of this shard -> moments [m, 2, 3] f64 (zeros for DELIGHT)."""
+    def local_phase1(self, queries: torch.Tensor, moments: bool = True):
+        """pack(q) + distances + row moments of this shard -> moments [m, 2, 3] f64 (zeros for DELIGHT).
+        moments=False: the returned buffer is left for local_select(with_moments=True) to fill."""
         self._enter()
         m = self._pack(self.q, queries)
         n = self.n
@@ -606,7 +616,8 @@ class Matcher(_Base):
             self._leave()
             mom.zero_()
         else:
-            self.ctx.check(lib.pr_row_moments_dev(h, _dptr(d_p), _dptr(d_i), m, n, _dptr(mom)))
+            if moments:
+                self.ctx.check(lib.pr_row_moments_dev(h, _dptr(d_p), _dptr(d_i), m, n, _dptr(mom)))
             self._leave()
         return mom
 
