@@ -1209,6 +1209,65 @@ int pr_maploc_nn(pr_maploc* ml, const double* xyz_q, const int64_t* offs_q, int3
 int pr_maploc_refine(pr_maploc* ml, const double* xyz_q, const int64_t* offs_q, int32_t Nq, const int32_t* pair_src, int32_t c, const double* T0,
                      const int32_t* excl, int32_t max_iter, double max_corr, double tol_rmse, double tol_fitness, int32_t min_inliers,
                      double* T_out, pr_icp_stats* stats);
+
+/* ---- the closure consistency gate in front of the pose-graph relaxation (gate.hip) -------------------------------------
+ * pr_posegraph_relax_dev has no robust kernel: one wrong closure that passed verify pulls the whole graph.  What exposes such a closure is
+ * that it disagrees with the other closures and with the odometry between them.  A pr_gate checks every ordered pair of logged closures
+ * of a SOURCE log against each other and copies the consistent ones, in log order, into a second log; an ordinary pr_posegraph over that
+ * second log relaxes them.  Everything is stream-ordered, reads both counts on the device, allocates nothing after create; every grid is
+ * a function of the create sizes only, so one capture made on an empty log serves every count.
+ *
+ *   pr_gate_create    takes the buffer RECORDS of two logs (the caller also holds a pr_posegraph over each; both must outlive the gate,
+ *                     which must be destroyed before them).  The gate only reads src; in dst it writes rows [0, kept) of edge_ij, edge_Z
+ *                     and edge_w and the four words of state, and nothing else.  rot_tab and trans2_tab are HOST arrays [max_gap + 1];
+ *                     create uploads them and allocates ALL scratch in one block; no later call allocates or copies from host memory.
+ *                     With EC = edge_capacity and G = max_gap + 1 the parts are, each rounded up to 16 bytes:
+ *                       288 EC (L, M, N: 36 doubles an edge) | 8 EC (the edges' rows) | 4 EC (valid) | 4 EC | 4 EC (keep of the round
+ *                       before and of this one) | 4 EC (support sums) | 4 EC (map) | 8 G (rot_tab) | 8 G (trans2_tab) | 16 (control)
+ *                       | staging of the host form: EC (keep) | 4 EC (support) | 4 EC (map) | 16 (info)
+ *                     pr_gate_scratch_bytes returns the sum (0 for sizes create refuses).
+ *   pr_gate_run_dev   1 + 2 rounds + 2 launches.  d_poses [node_capacity][12] f64 and d_n [>= 1] i32: a pr_map's poses and state.
+ *                     d_keep u8, d_support i32, d_map i32 are [edge_capacity], every entry is written, any of the three may be NULL;
+ *                     d_info [4] i32.  No read-back.
+ *   pr_gate_run       the same with HOST outputs (d_poses and d_n stay device memory); synchronises.
+ *
+ * The rule (restated in tests/gate_np.py; the device equals it bit for bit).  Conventions as for pr_posegraph: a pose is [R | t], 12
+ * doubles row-major, world to camera; A B = [R_A R_B | R_A t_B + t_A]; A^-1 = [R^T | -(R^T t)]; a closure (i, j, Z) measures
+ * Z ~ P_i P_j^-1.  fp64, + and x only, no contraction.  A 3 x 3 product entry is (a0 b0 + a1 b1) + a2 b2; the translation of a product
+ * is ((r0 t0 + r1 t1) + r2 t2) + t_A, of an inverse -((R0r t0 + R1r t1) + R2r t2); R^T is formed first and then multiplied like any
+ * other matrix.
+ *   1. Counts.  E = src.state[0] clamped into 0 .. edge_capacity, n = d_n[0] clamped into 0 .. node_capacity, both before any address
+ *      is formed from them.
+ *   2. Valid edges.  Edge a < E is valid iff 0 <= i, j < n, i != j, its 12 Z entries and 2 weights are finite and the 24 entries of
+ *      P_i, P_j are finite: exactly the relaxation's skip rule.
+ *   3. Per valid edge.  L_a = Z_a^-1 P_ia, M_a = (P_ia^-1 Z_a) P_ja, N_a = P_ja^-1.
+ *   4. Ordered pairs.  For an ordered pair a != b of valid edges: gap = |i_a - i_b| + |j_a - j_b|.  The pair is comparable iff
+ *      gap <= max_gap and j_a != j_b (two candidates of one query keyframe are not independent evidence).  X = (L_a M_b) N_a - that is
+ *      Z_a^-1 (P_ia P_ib^-1) Z_b (P_jb P_ja^-1) re-associated: the identity when both closures agree with each other along the odometry
+ *      between them.  c_rot = 3 - ((X00 + X11) + X22) (= 2 (1 - cos theta)), c_trans = (tx tx + ty ty) + tz tz.  b supports a iff the
+ *      pair is comparable, c_rot <= rot_tab[gap] and c_trans <= trans2_tab[gap].  A NaN supports nothing.  The rule is stated for ordered
+ *      pairs: b supporting a need not imply the converse in floating point; it is evaluated as written.
+ *   5. Rounds.  keep_0 = valid.  For r = 1 .. rounds: s_r[a] = #{b : keep_{r-1}[b], b supports a} and keep_r[a] = keep_{r-1}[a] and
+ *      s_r[a] >= min_support.  The outputs are keep = keep_rounds and support[a] = s_rounds[a] for a valid a (also a removed one), -1 for
+ *      an invalid a (every a >= E is invalid).  PR_GATE_UNSETTLED is set iff keep_rounds != keep_{rounds-1}; when it is clear the kept
+ *      set is the min_support-core of the support relation.
+ *   6. Copy.  Kept edges are copied in log order: map[a] is the rank of a among the kept, or -1; row map[a] of dst gets the bytes of
+ *      row a of src (edge_ij, edge_Z, edge_w); dst.state = {kept, src.state[1] & PR_POSEGRAPH_OVERFLOW, 0, 0}; rows >= kept of dst are
+ *      not written.  info = {valid, kept, E, flags}; PR_GATE_SRC_OVERFLOW mirrors the source log's overflow bit.
+ * PR_EINVAL (text: pr_last_error) before any device is touched for a NULL pointer or a NULL buffer of either record, src and dst sharing
+ * a buffer, node_capacity outside 1 .. 2^20, edge_capacity outside 1 .. 65536, dst_edge_capacity < edge_capacity, max_gap outside
+ * 0 .. 65535, min_support < 0, rounds outside 1 .. 64, and a table entry that is NaN or negative (+Inf is allowed and switches that test
+ * off). */
+typedef struct pr_gate pr_gate;
+typedef struct pr_gate_params { int32_t max_gap, min_support, rounds; } pr_gate_params;
+#define PR_GATE_SRC_OVERFLOW 1
+#define PR_GATE_UNSETTLED 2
+int pr_gate_create(pr_ctx* ctx, const pr_posegraph_buffers* src, const pr_posegraph_buffers* dst, int32_t node_capacity, int32_t edge_capacity,
+                   int32_t dst_edge_capacity, const pr_gate_params* params, const double* rot_tab, const double* trans2_tab, pr_gate** out);
+int pr_gate_run_dev(pr_gate* g, const double* d_poses, const int32_t* d_n, uint8_t* d_keep, int32_t* d_support, int32_t* d_map, int32_t* d_info);
+int pr_gate_run(pr_gate* g, const double* d_poses, const int32_t* d_n, uint8_t* keep, int32_t* support, int32_t* map, int32_t* info);
+size_t pr_gate_scratch_bytes(int32_t node_capacity, int32_t edge_capacity, int32_t max_gap);
+void pr_gate_destroy(pr_gate* g);
 const char* pr_host_last_error(void);
 
 #ifdef __cplusplus

@@ -32,6 +32,7 @@ POSEGRAPH_OVERFLOW = 1                              # info[3] of a pr_posegraph 
 POSEGRAPH_MAX_K = 128                               # most slots of one pr_posegraph add
 WORLDMAP_OVERFLOW, WORLDMAP_SKIPPED, WORLDMAP_RANGE, WORLDMAP_TABLE = 1, 2, 4, 8   # flags of a pr_worldmap fuse (state[1], info[3])
 MAPLOC_SKIPPED, MAPLOC_RANGE, MAPLOC_DUPLICATE, MAPLOC_TABLE = 1, 2, 4, 8           # flags of a pr_maploc index (info[2])
+GATE_SRC_OVERFLOW, GATE_UNSETTLED = 1, 2            # flags of a pr_gate run (info[3])
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PR_AMD_LIB") or os.path.join(_HERE, "libpr_amd.so")   # PR_AMD_LIB: experiment builds only
@@ -269,6 +270,11 @@ SYMBOLS = {
     "pr_maploc_index": (C.c_int, [_vp, _vp]),
     "pr_maploc_nn": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _dbl, _vp, _vp, _vp]),
     "pr_maploc_refine": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _dbl, _dbl, _dbl, _i32, _vp, _vp]),
+    "pr_gate_create": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, C.POINTER(_vp)]),
+    "pr_gate_run_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pr_gate_run": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pr_gate_scratch_bytes": (C.c_size_t, [_i32, _i32, _i32]),
+    "pr_gate_destroy": (None, [_vp]),
     "pr_host_last_error": (C.c_char_p, []),
 }
 
@@ -302,6 +308,11 @@ class WorldMapBuffers(C.Structure):
 class PoseGraphParams(C.Structure):
     """pr_posegraph_params: the budgets and weights of one pr_posegraph_relax_dev (filled by position: `lambda` is no Python name)."""
     _fields_ = [("outer", _i32), ("inner", _i32), ("lambda", _dbl), ("w_odo_rot", _dbl), ("w_odo_trans", _dbl)]
+
+
+class GateParams(C.Structure):
+    """pr_gate_params: what a pr_gate fixes at create."""
+    _fields_ = [("max_gap", _i32), ("min_support", _i32), ("rounds", _i32)]
 
 
 _lib = None

@@ -1766,6 +1766,105 @@ class PoseGraph:
             pass
 
 
+class ClosureGate:
+    """pr_gate: the closure consistency gate in front of the relaxation.  Every ordered pair of closures logged in pg_src
+    is compared along the odometry chain of the poses; a closure is kept when at least min_support kept closures within max_gap
+    keyframes (|i_a - i_b| + |j_a - j_b|, another query keyframe) agree with it, repeated `rounds` times; the kept closures are copied,
+    in log order, into pg_dst's log, which pg_dst.relax_torch / relax_map then relaxes.  The tables are rot_tab[g] = 2 (1 - cos(rad(rot_deg
+    + g rot_deg_per_kf))) and trans2_tab[g] = (trans + g trans_per_kf)^2 for g = 0 .. max_gap, or the arrays given (passed through
+    unchanged; +Inf switches a test off).  Calls are enqueued on the context's stream, read both counts on the device and allocate no
+    device scratch; ONE captured run_torch serves every count.  Close it before either graph."""
+
+    def __init__(self, ctx: Context | None, pg_src, pg_dst, max_gap: int, min_support: int = 2, rounds: int = 8, rot_deg: float = 2.0,
+                 rot_deg_per_kf: float = 0.05, trans: float = 0.5, trans_per_kf: float = 0.02, rot_tab=None, trans2_tab=None):
+        self.ctx = ctx or default_context()
+        self.h = None
+        if pg_src is pg_dst:
+            raise ValueError("ClosureGate: pg_src and pg_dst must be two graphs")
+        if pg_src.ctx is not self.ctx or pg_dst.ctx is not self.ctx:
+            raise ValueError("ClosureGate: the gate and both graphs must share one context (one stream)")
+        if pg_src.node_capacity != pg_dst.node_capacity:
+            raise ValueError("ClosureGate: both graphs must have the same node_capacity")
+        if pg_dst.edge_capacity < pg_src.edge_capacity:
+            raise ValueError("ClosureGate: pg_dst.edge_capacity must be at least pg_src.edge_capacity")
+        self.lib = self.ctx.lib
+        self.src, self.dst = pg_src, pg_dst
+        self.node_capacity, self.edge_capacity = pg_src.node_capacity, pg_src.edge_capacity
+        self.max_gap, self.min_support, self.rounds = int(max_gap), int(min_support), int(rounds)
+        g = np.arange(max(self.max_gap, 0) + 1, dtype=np.float64)
+        if rot_tab is None:
+            rot_tab = 2.0 * (1.0 - np.cos(np.radians(float(rot_deg) + g * float(rot_deg_per_kf))))
+        if trans2_tab is None:
+            trans2_tab = (float(trans) + g * float(trans_per_kf)) ** 2
+        self.rot_tab = np.ascontiguousarray(rot_tab, np.float64).reshape(-1)
+        self.trans2_tab = np.ascontiguousarray(trans2_tab, np.float64).reshape(-1)
+        if len(self.rot_tab) != len(g) or len(self.trans2_tab) != len(g):
+            raise ValueError("ClosureGate: rot_tab and trans2_tab must have max_gap + 1 entries")
+        recs = [_lib.PoseGraphBuffers(*(C.c_void_p(getattr(pg, n).data_ptr()) for n in pg.NAMES)) for pg in (pg_src, pg_dst)]
+        prm = _lib.GateParams(self.max_gap, self.min_support, self.rounds)
+        h = C.c_void_p()
+        self.ctx.check(self.lib.pr_gate_create(self.ctx.h, C.byref(recs[0]), C.byref(recs[1]), self.node_capacity, self.edge_capacity,
+                                               pg_dst.edge_capacity, C.byref(prm), _ptr(self.rot_tab), _ptr(self.trans2_tab), C.byref(h)))
+        self.h = h
+
+    def _t(self, who, name, t, dtype, numel, exact=True):
+        dev = self.src.state.device
+        if (not t.is_cuda) or t.device != dev or t.dtype != dtype or not t.is_contiguous() or (t.numel() != numel if exact else t.numel() < numel):
+            raise ValueError(f"{who}: {name} must be a contiguous CUDA tensor {dtype} of {'' if exact else 'at least '}{numel} elements on the "
+                             "graphs' device")
+        return t
+
+    def run_torch(self, poses, n, keep=None, support=None, map=None, info=None):
+        """Device form (pr_gate_run_dev): poses f64 [node_capacity, 12] (world to camera), n i32 [>= 1] whose word 0 is the node count - a
+        KeyframeMap's .poses and .state.  Returns (keep u8 [edge_capacity], support i32 [edge_capacity] - the kept supporters of the last
+        round, -1 for an edge that is not valid -, map i32 [edge_capacity] - the row in pg_dst or -1 -, info i32 [4] = valid, kept, edges
+        read, flags GATE_*).  Nothing synchronises, nothing is allocated when all four are given."""
+        import torch
+        who = "ClosureGate.run_torch"
+        ec, dev = self.edge_capacity, self.src.state.device
+        self._t(who, "poses", poses, torch.float64, 12 * self.node_capacity)
+        self._t(who, "n", n, torch.int32, 1, exact=False)
+        keep = torch.empty(ec, dtype=torch.uint8, device=dev) if keep is None else self._t(who, "keep", keep, torch.uint8, ec)
+        support = torch.empty(ec, dtype=torch.int32, device=dev) if support is None else self._t(who, "support", support, torch.int32, ec)
+        map = torch.empty(ec, dtype=torch.int32, device=dev) if map is None else self._t(who, "map", map, torch.int32, ec)
+        info = torch.empty(4, dtype=torch.int32, device=dev) if info is None else self._t(who, "info", info, torch.int32, 4)
+        p = lambda t: C.c_void_p(t.data_ptr())
+        self.ctx.check(self.lib.pr_gate_run_dev(self.h, p(poses), p(n), p(keep), p(support), p(map), p(info)))
+        return keep, support, map, info
+
+    def run_map(self, km, **kw):
+        """run_torch(km.poses, km.state, ...) for a KeyframeMap, with PoseGraph.relax_map's refusals."""
+        if km.ctx is not self.ctx:
+            raise ValueError("ClosureGate.run_map: the gate and the map must share one context (one stream)")
+        if km.keyframe_capacity != self.node_capacity:
+            raise ValueError("ClosureGate.run_map: node_capacity must equal the map's keyframe_capacity")
+        return self.run_torch(km.poses, km.state, **kw)
+
+    def run(self, poses, n):
+        """Host form (pr_gate_run; synchronises): poses and n as for run_torch (device tensors); returns NumPy (keep u8, support i32,
+        map i32, info i32 [4])."""
+        import torch
+        who = "ClosureGate.run"
+        self._t(who, "poses", poses, torch.float64, 12 * self.node_capacity)
+        self._t(who, "n", n, torch.int32, 1, exact=False)
+        ec = self.edge_capacity
+        keep, support, map_, info = np.empty(ec, np.uint8), np.empty(ec, np.int32), np.empty(ec, np.int32), np.empty(4, np.int32)
+        self.ctx.check(self.lib.pr_gate_run(self.h, C.c_void_p(poses.data_ptr()), C.c_void_p(n.data_ptr()), _ptr(keep), _ptr(support), _ptr(map_),
+                                            _ptr(info)))
+        return keep, support, map_, info
+
+    def close(self):
+        if getattr(self, "h", None) and getattr(self.ctx, "h", None):
+            self.lib.pr_gate_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class WorldMap:
     """pr_worldmap: all clouds of a KeyframeMap fused into ONE world-frame point set, one point per occupied voxel, under any pose array -
     the map's own or the ones PoseGraph.relax_map returns.  The six buffers are zeroed torch tensors on the context's

@@ -1,0 +1,170 @@
+// gate.cpp — host side of the closure consistency gate (gate.hip): the opaque pr_gate over the buffer records of two
+// loop-closure logs, its ONE scratch allocation with the two tables, the argument checks, the stream-ordered run and its host form.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <new>
+
+#include "../../include/place_recognition.h"
+#include "gate.hpp"
+#include "host_common.hpp"
+#include "kernels.hpp"
+
+static_assert(pr::GATE_SRC_OVERFLOW == PR_GATE_SRC_OVERFLOW && pr::GATE_UNSETTLED == PR_GATE_UNSETTLED, "flag bits");
+static_assert(pr::GATE_LOG_OVERFLOW == PR_POSEGRAPH_OVERFLOW, "the source log's flag bit");
+static_assert(sizeof(pr_gate_params) == 12, "three int32, no padding");
+
+struct pr_gate {
+  pr_ctx* ctx = nullptr;
+  pr::GateView v;
+  void* scratch = nullptr;            // one allocation: everything GateView names and the staging of the host form
+  uint8_t* stage_keep = nullptr;      // [edge_capacity]
+  int32_t* stage_support = nullptr;   // [edge_capacity]
+  int32_t* stage_map = nullptr;       // [edge_capacity]
+  int32_t* stage_info = nullptr;      // [4]
+};
+
+namespace {
+
+using pr::fail;
+
+constexpr int32_t MAX_NODES = 1 << 20, MAX_EDGES = 65536, MAX_GAP = 65535, MAX_ROUNDS = 64;
+
+// where the parts of the one scratch allocation lie (each on a 16-byte boundary); the formula of the header
+struct Layout {
+  size_t lmn, eij, valid, keep0, keep1, sup, map, rot, trans, ctl, s_keep, s_support, s_map, s_info, total;
+};
+
+Layout layout_of(int32_t edge_capacity, int32_t max_gap) {
+  const size_t EC = (size_t)edge_capacity, G = (size_t)max_gap + 1;
+  Layout l;
+  l.total = 0;
+  auto take = [&l](size_t bytes) { const size_t o = l.total; l.total += (bytes + 15) & ~(size_t)15; return o; };
+  l.lmn = take(8 * pr::GATE_LMN * EC); l.eij = take(8 * EC); l.valid = take(4 * EC); l.keep0 = take(4 * EC); l.keep1 = take(4 * EC);
+  l.sup = take(4 * EC); l.map = take(4 * EC); l.rot = take(8 * G); l.trans = take(8 * G); l.ctl = take(16);
+  l.s_keep = take(EC); l.s_support = take(4 * EC); l.s_map = take(4 * EC); l.s_info = take(16);
+  return l;
+}
+
+bool sizes_ok(int32_t node_capacity, int32_t edge_capacity, int32_t max_gap) {
+  return node_capacity >= 1 && node_capacity <= MAX_NODES && edge_capacity >= 1 && edge_capacity <= MAX_EDGES && max_gap >= 0 && max_gap <= MAX_GAP;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t pr_gate_scratch_bytes(int32_t node_capacity, int32_t edge_capacity, int32_t max_gap) {
+  if (!sizes_ok(node_capacity, edge_capacity, max_gap)) return 0;
+  return layout_of(edge_capacity, max_gap).total;
+}
+
+int pr_gate_create(pr_ctx* ctx, const pr_posegraph_buffers* src, const pr_posegraph_buffers* dst, int32_t node_capacity, int32_t edge_capacity,
+                   int32_t dst_edge_capacity, const pr_gate_params* params, const double* rot_tab, const double* trans2_tab, pr_gate** out) {
+  // the value checks come first and need no device: with ctx == NULL their text goes to pr_last_error(NULL)
+  if (!out) return fail(ctx, PR_EINVAL, "pr_gate_create: out is NULL");
+  *out = nullptr;
+  if (!src || !dst) return fail(ctx, PR_EINVAL, "pr_gate_create: a buffer record is NULL (src, dst)");
+  if (!params || !rot_tab || !trans2_tab) return fail(ctx, PR_EINVAL, "pr_gate_create: a required pointer is NULL (params, rot_tab, trans2_tab)");
+  const void* sb[4] = {src->edge_ij, src->edge_Z, src->edge_w, src->state};
+  const void* db[4] = {dst->edge_ij, dst->edge_Z, dst->edge_w, dst->state};
+  for (int a = 0; a < 4; a++)
+    if (!sb[a] || !db[a]) return fail(ctx, PR_EINVAL, "pr_gate_create: a buffer is NULL (edge_ij, edge_Z, edge_w, state of src and dst)");
+  for (int a = 0; a < 4; a++)
+    for (int b = 0; b < 4; b++)
+      if (sb[a] == db[b]) return fail(ctx, PR_EINVAL, "pr_gate_create: src and dst share a buffer");
+  if (node_capacity < 1 || node_capacity > MAX_NODES)
+    return fail(ctx, PR_EINVAL, "pr_gate_create: node_capacity=%d outside 1 .. %d", node_capacity, MAX_NODES);
+  if (edge_capacity < 1 || edge_capacity > MAX_EDGES)
+    return fail(ctx, PR_EINVAL, "pr_gate_create: edge_capacity=%d outside 1 .. %d", edge_capacity, MAX_EDGES);
+  if (dst_edge_capacity < edge_capacity)
+    return fail(ctx, PR_EINVAL, "pr_gate_create: dst_edge_capacity=%d is below edge_capacity=%d", dst_edge_capacity, edge_capacity);
+  if (params->max_gap < 0 || params->max_gap > MAX_GAP) return fail(ctx, PR_EINVAL, "pr_gate_create: max_gap=%d outside 0 .. %d", params->max_gap, MAX_GAP);
+  if (params->min_support < 0) return fail(ctx, PR_EINVAL, "pr_gate_create: min_support=%d is negative", params->min_support);
+  if (params->rounds < 1 || params->rounds > MAX_ROUNDS) return fail(ctx, PR_EINVAL, "pr_gate_create: rounds=%d outside 1 .. %d", params->rounds, MAX_ROUNDS);
+  for (int32_t g = 0; g <= params->max_gap; g++) {               // +Inf is allowed: it switches that test off
+    if (std::isnan(rot_tab[g]) || rot_tab[g] < 0.0) return fail(ctx, PR_EINVAL, "pr_gate_create: rot_tab[%d] is NaN or negative", g);
+    if (std::isnan(trans2_tab[g]) || trans2_tab[g] < 0.0) return fail(ctx, PR_EINVAL, "pr_gate_create: trans2_tab[%d] is NaN or negative", g);
+  }
+  if (!ctx) return fail(nullptr, PR_EINVAL, "pr_gate_create: ctx is NULL");
+  PR_CHECK_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
+  pr_gate* g = new (std::nothrow) pr_gate;
+  if (!g) return fail(ctx, PR_ENOMEM, "out of host memory");
+  g->ctx = ctx;
+  pr::GateView& v = g->v;
+  memset(&v, 0, sizeof v);
+  v.s_ij = src->edge_ij; v.s_Z = src->edge_Z; v.s_w = src->edge_w; v.s_state = src->state;
+  v.d_ij = dst->edge_ij; v.d_Z = dst->edge_Z; v.d_w = dst->edge_w; v.d_state = dst->state;
+  v.node_capacity = node_capacity; v.edge_capacity = edge_capacity;
+  v.max_gap = params->max_gap; v.min_support = params->min_support; v.rounds = params->rounds;
+  const Layout l = layout_of(edge_capacity, params->max_gap);
+  hipError_t e = hipMalloc(&g->scratch, l.total);
+  if (e != hipSuccess) {
+    delete g;
+    return fail(ctx, e == hipErrorOutOfMemory ? PR_ENOMEM : PR_EHIP, "pr_gate_create: scratch of %zu bytes: %s", l.total, hipGetErrorString(e));
+  }
+  char* b = static_cast<char*>(g->scratch);
+  auto ip = [b](size_t o) { return reinterpret_cast<int*>(b + o); };
+  double* rot = reinterpret_cast<double*>(b + l.rot);
+  double* trans = reinterpret_cast<double*>(b + l.trans);
+  v.lmn = reinterpret_cast<double*>(b + l.lmn);
+  v.eij = ip(l.eij); v.valid = ip(l.valid); v.keep[0] = ip(l.keep0); v.keep[1] = ip(l.keep1); v.sup = ip(l.sup); v.map = ip(l.map);
+  v.rot_tab = rot; v.trans2_tab = trans; v.ctl = ip(l.ctl);
+  g->stage_keep = reinterpret_cast<uint8_t*>(b + l.s_keep);
+  g->stage_support = ip(l.s_support); g->stage_map = ip(l.s_map); g->stage_info = ip(l.s_info);
+  hipStream_t st = pr::ctx_stream(ctx);
+  const size_t G = (size_t)params->max_gap + 1;
+  e = hipMemsetAsync(g->scratch, 0, l.total, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(rot, rot_tab, 8 * G, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(trans, trans2_tab, 8 * G, hipMemcpyHostToDevice, st);
+  const hipError_t es = hipStreamSynchronize(st);                // the host tables are in flight until here
+  if (e == hipSuccess) e = es;
+  if (e != hipSuccess) {
+    (void)hipFree(g->scratch);
+    delete g;
+    return fail(ctx, PR_EHIP, "pr_gate_create: clearing the scratch and uploading the tables failed: %s", hipGetErrorString(e));
+  }
+  *out = g;
+  return PR_OK;
+}
+
+void pr_gate_destroy(pr_gate* g) {
+  if (!g) return;
+  (void)hipSetDevice(pr::ctx_device(g->ctx));
+  (void)hipStreamSynchronize(pr::ctx_stream(g->ctx));
+  (void)hipFree(g->scratch);          // the buffers of both logs are the caller's
+  delete g;
+}
+
+int pr_gate_run_dev(pr_gate* g, const double* d_poses, const int32_t* d_n, uint8_t* d_keep, int32_t* d_support, int32_t* d_map, int32_t* d_info) {
+  if (!g) return fail(nullptr, PR_EINVAL, "pr_gate_run_dev: gate is NULL");
+  pr_ctx* ctx = g->ctx;
+  if (!d_poses || !d_n || !d_info) return fail(ctx, PR_EINVAL, "pr_gate_run_dev: a required pointer is NULL (d_poses, d_n, d_info)");
+  PR_CHECK_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
+  pr::launch_gate(pr::ctx_stream(ctx), g->v, d_poses, d_n, d_keep, d_support, d_map, d_info);
+  PR_CHECK_HIP(ctx, hipGetLastError());
+  return PR_OK;
+}
+
+int pr_gate_run(pr_gate* g, const double* d_poses, const int32_t* d_n, uint8_t* keep, int32_t* support, int32_t* map, int32_t* info) {
+  if (!g) return fail(nullptr, PR_EINVAL, "pr_gate_run: gate is NULL");
+  pr_ctx* ctx = g->ctx;
+  if (!d_poses || !d_n || !info) return fail(ctx, PR_EINVAL, "pr_gate_run: a required pointer is NULL (d_poses, d_n, info)");
+  if (int rc = pr_gate_run_dev(g, d_poses, d_n, keep ? g->stage_keep : nullptr, support ? g->stage_support : nullptr,
+                               map ? g->stage_map : nullptr, g->stage_info))
+    return rc;
+  hipStream_t st = pr::ctx_stream(ctx);
+  const size_t EC = (size_t)g->v.edge_capacity;
+  hipError_t e = hipMemcpyAsync(info, g->stage_info, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess && keep) e = hipMemcpyAsync(keep, g->stage_keep, EC, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess && support) e = hipMemcpyAsync(support, g->stage_support, 4 * EC, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess && map) e = hipMemcpyAsync(map, g->stage_map, 4 * EC, hipMemcpyDeviceToHost, st);
+  const hipError_t es = hipStreamSynchronize(st);                // the host arrays are in flight until here
+  if (e == hipSuccess) e = es;
+  if (e != hipSuccess) return fail(ctx, pr::hip_code(e), "pr_gate_run: %s", hipGetErrorString(e));
+  return PR_OK;
+}
+
+}  // extern "C"
