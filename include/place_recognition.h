@@ -1210,6 +1210,79 @@ int pr_maploc_refine(pr_maploc* ml, const double* xyz_q, const int64_t* offs_q, 
                      const int32_t* excl, int32_t max_iter, double max_corr, double tol_rmse, double tol_fitness, int32_t min_inliers,
                      double* T_out, pr_icp_stats* stats);
 
+/* ---- point-to-plane scan-to-map: world-map normals and a plane-metric refinement (mapplane.hip) -------------------------
+ * pr_maploc_refine_dev pulls every source point towards the ONE point its voxel holds, an arbitrary in-plane position: its residual never
+ * reaches zero on a correct pose.  A pr_mapplane over an existing pr_maploc estimates a normal per world row through the localiser's voxel
+ * index and refines with the point-to-plane metric.  It BORROWS the localiser's table, cell, out_capacity, world record, create sizes and
+ * the offsets of the last index, and makes ONE allocation of its own at create; destroy it before the localiser.  Every device call is
+ * stream-ordered on the context's stream, reads nothing back, allocates nothing and can be captured; grids depend on the create sizes and
+ * c only.  fp64 without contraction.
+ *
+ *   pr_mapplane_create    With ld = max(max_src_pts, 1), nchunks = ceil(ld / 256), pc = pair_capacity (the localiser's) the parts of the
+ *                         allocation are, each rounded up to 16 bytes:
+ *                           8 pc ld (nn_d) | 4 pc ld (nn_j) | 240 pc nchunks (chunk partials, 30 doubles each) | 4 pc (done) | 16 pc (prev)
+ *                           | staging of the host forms: 24 pc ld (xyz_q) | 8 (pc + 1) (offs_q) | 4 pc (pair_src) | 96 pc (T) | 8 pc (excl)
+ *                           | 32 pc (stats) | 24 pc ld (normals) | 4 pc ld (ninfo)
+ *                         pr_mapplane_scratch_bytes(pair_capacity, max_src_pts) returns the sum (0 for sizes pr_maploc_create refuses).
+ *   pr_mapplane_normals_dev   one launch, one lane per world row.  d_normals [out_capacity][3] f64 and d_ninfo [out_capacity] i32 are the
+ *                         caller's; every entry is written.  Call it behind pr_maploc_index_dev.  The rule:
+ *                         Row j is PROCESSED iff it is INDEXED in the sense of pr_maploc_index_dev (j < R, finite, in range, the smallest
+ *                         row of its key).  Every other row < out_capacity gets ninfo = 0 and the normal (0, 0, 0).
+ *                         Neighbours: the 27 keys around floor(x_a / cell) in the probe's order - d0 outer, then k = 0 .. 8 with
+ *                         (k / 3 - 1, k % 3 - 1); keys outside the 21-bit range are dropped.  Each key contributes the row the table holds,
+ *                         row j itself included.  A row is kept iff d2 = ((dx dx) + dy dy) + dz dz < fl(radius^2) with d = q - x_j.  The
+ *                         count k includes j itself.
+ *                         Sums, pivoted on the row itself (a UTM-sized offset never enters a product), in visit order from 0.0: the three
+ *                         s_a = sum d_a and the six S_ab = sum d_a d_b; C_ab = S_ab - (s_a s_b) / k (IEEE division).
+ *                         Eigen-decomposition of C by cyclic Jacobi in fp64: 8 sweeps, pivots (0,1), (0,2), (1,2), V = I at the start.  A
+ *                         rotation about (p, q) with third index r is skipped when C_pq is exactly 0; otherwise theta = (C_qq - C_pp) /
+ *                         (2 C_pq), t = sgn(theta) / (|theta| + sqrt(theta theta + 1)) with sgn(0) = +1, c = 1 / sqrt(t t + 1), s = t c;
+ *                         C_pp -= t C_pq, C_qq += t C_pq, C_pq = 0; (C_rp, C_rq) <- (c C_rp - s C_rq, s C_rp + c C_rq); every row a of V:
+ *                         (V_ap, V_aq) <- (c V_ap - s V_aq, s V_ap + c V_aq).  The eigenvalues are the diagonal, sorted l0 <= l1 <= l2
+ *                         by three compare-exchanges (1,0), (2,1), (1,0) on strict "<": the lower index first on ties.
+ *                         The row is VALID iff k >= min_nbrs, every eigenvalue is finite, l1 > 0 and l0 <= max_ratio l1.  A valid row
+ *                         gets ninfo = k and n = the eigenvector (column of V) of l0, every component divided by its norm
+ *                         sqrt((e0 e0 + e1 e1) + e2 e2), the sign chosen so that the component of largest magnitude is positive (the
+ *                         lowest index wins a tie).  An invalid row gets ninfo = -k and the normal (0, 0, 0).
+ *   pr_mapplane_refine_dev    the arguments of pr_maploc_refine_dev plus d_normals and d_ninfo.  max_iter + 1 rounds of (pass, update)
+ *                         with done flags, three launches a round: a fixed launch count.
+ *                         Pass: the correspondence search is pr_maploc_nn_dev's rule - the same launch, the same (j, d2), the exclusion
+ *                         window included.  n_inl, fitness and rmse keep pr_maploc_refine_dev's definitions over ALL correspondents
+ *                         inside the radius, so pr_verify_select_dev's thresholds keep their meaning.  A correspondent enters the UPDATE
+ *                         only if ninfo[j] > 0.  For such a point, with T = [R | t]: p' = T s; u = p' - t (the lever arm about the sensor
+ *                         position: no world-sized coordinate enters a cross product); e = p' - q; r = (n_0 e_0 + n_1 e_1) + n_2 e_2;
+ *                         J = [u x n, n].  Per chunk of 256 source points: the inlier count, sum d2, the plane count, the 21 entries of
+ *                         sum J J^T (upper triangle, row-major) and the 6 of sum J r, by a fixed tree - within a wave (64-lane shuffle
+ *                         tree), then the four waves in order - to [pair][chunk][30] in the handle's own scratch.
+ *                         Update: the chunks are combined in index order.  Fewer than min_inliers plane correspondents: PR_ICP_TOO_FEW.
+ *                         A x = -b is solved by L D L^T without pivoting in the order (w0, w1, w2, v0, v1, v2): d_k = A_kk - sum_m<k
+ *                         (L_km d_m) L_km, L_ik = (A_ik - sum_m<k (L_im d_m) L_km) / d_k, y_i = -b_i - sum_m<i L_im y_m, z_i = y_i / d_i,
+ *                         x_i = z_i - sum_m>i L_mi x_m, every sum subtracted term by term with m ascending.  PR_ICP_DEGENERATE when a d_k
+ *                         is not finite or d_k <= 1e-12 A_kk (the original diagonal entry; scale-free) or an x_i is not finite: a single
+ *                         plane or a corridor without end walls ends here.  R <- Exp(w) R by Rodrigues, Exp(w) = (1 - b th2) I + b w w^T +
+ *                         a [w]x with th2 = |w|^2, a = sin(th) / th, b = (1 - cos(th)) / th2; below th2 = 1e-4 the series
+ *                         a = 1 - th2/6 (1 - th2/20 (1 - th2/42)), b = 1/2 - th2/24 (1 - th2/30 (1 - th2/56)).  t <- t + v.
+ *                         Stop rules, statuses, pr_icp_stats and the convention "T is the last one a valid update produced" are
+ *                         pr_icp_pairs_dev's, as is the final extra pass for the reported statistics.  d_T_out may be d_T0.
+ *   pr_mapplane_normals / _refine   the host forms: upload, run the device form, synchronise, read back.  They stage through the handle's
+ *                         own allocation, so out_capacity <= pair_capacity x ld, Nq <= pair_capacity and offs_q[Nq] <= pair_capacity x ld
+ *                         are required.
+ * PR_EINVAL (text: pr_last_error) before any device is touched: radius not positive and finite; radius (1 + 2^-10) > cell - the containment
+ * argument of DESIGN.md 4.20: everything inside the ball is in the 27 voxels; min_nbrs < 3 or > 27; max_ratio not in (0, 1]; NULL handles
+ * and pointers; for refine everything pr_maploc_refine_dev refuses, and min_inliers < 6. */
+typedef struct pr_mapplane pr_mapplane;
+int pr_mapplane_create(pr_ctx* ctx, pr_maploc* ml, pr_mapplane** out);
+void pr_mapplane_destroy(pr_mapplane* mp);
+int64_t pr_mapplane_scratch_bytes(int32_t pair_capacity, int32_t max_src_pts);
+int pr_mapplane_normals_dev(pr_mapplane* mp, double radius, int32_t min_nbrs, double max_ratio, double* d_normals, int32_t* d_ninfo);
+int pr_mapplane_refine_dev(pr_mapplane* mp, const double* d_xyz_q, const int64_t* d_offs_q, int32_t Nq, const int32_t* d_pair_src, int32_t c,
+                           const double* d_T0, const int32_t* d_excl, int32_t max_iter, double max_corr, double tol_rmse, double tol_fitness,
+                           int32_t min_inliers, const double* d_normals, const int32_t* d_ninfo, double* d_T_out, pr_icp_stats* d_stats);
+int pr_mapplane_normals(pr_mapplane* mp, double radius, int32_t min_nbrs, double max_ratio, double* normals, int32_t* ninfo);
+int pr_mapplane_refine(pr_mapplane* mp, const double* xyz_q, const int64_t* offs_q, int32_t Nq, const int32_t* pair_src, int32_t c,
+                       const double* T0, const int32_t* excl, int32_t max_iter, double max_corr, double tol_rmse, double tol_fitness,
+                       int32_t min_inliers, const double* normals, const int32_t* ninfo, double* T_out, pr_icp_stats* stats);
+
 /* ---- the closure consistency gate in front of the pose-graph relaxation (gate.hip) -------------------------------------
  * pr_posegraph_relax_dev has no robust kernel: one wrong closure that passed verify pulls the whole graph.  What exposes such a closure is
  * that it disagrees with the other closures and with the odometry between them.  A pr_gate checks every ordered pair of logged closures

@@ -270,6 +270,13 @@ SYMBOLS = {
     "pr_maploc_index": (C.c_int, [_vp, _vp]),
     "pr_maploc_nn": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _dbl, _vp, _vp, _vp]),
     "pr_maploc_refine": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _dbl, _dbl, _dbl, _i32, _vp, _vp]),
+    "pr_mapplane_create": (C.c_int, [_vp, _vp, C.POINTER(_vp)]),
+    "pr_mapplane_destroy": (None, [_vp]),
+    "pr_mapplane_scratch_bytes": (C.c_int64, [_i32, _i32]),
+    "pr_mapplane_normals_dev": (C.c_int, [_vp, _dbl, _i32, _dbl, _vp, _vp]),
+    "pr_mapplane_refine_dev": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _dbl, _dbl, _dbl, _i32, _vp, _vp, _vp, _vp]),
+    "pr_mapplane_normals": (C.c_int, [_vp, _dbl, _i32, _dbl, _vp, _vp]),
+    "pr_mapplane_refine": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _dbl, _dbl, _dbl, _i32, _vp, _vp, _vp, _vp]),
     "pr_gate_create": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, C.POINTER(_vp)]),
     "pr_gate_run_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pr_gate_run": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -2221,6 +2221,134 @@ class MapLocalizer:
             pass
 
 
+class PlaneLocalizer:
+    """pr_mapplane: point-to-plane scan-to-map registration over a MapLocalizer.  normals_torch estimates one normal per
+    world row through the localiser's voxel index (call it behind index_torch); refine_torch is MapLocalizer.refine_torch with the plane
+    metric - the same correspondence search, fitness and rmse, an update from the correspondents whose row has a normal.  It borrows the
+    localiser's table and sizes and owns one allocation; every device call is enqueued on the context's stream, reads nothing back and can
+    be captured.  Close it before its localiser."""
+
+    def __init__(self, ctx: Context | None, ml):
+        self.ctx = ctx or default_context()
+        self.h = None
+        if ml.ctx is not self.ctx:
+            raise ValueError("PlaneLocalizer: the plane localiser and the localiser must share one context (one stream)")
+        self.lib = self.ctx.lib
+        self.ml = ml
+        self.wm = ml.wm
+        self.pair_capacity, self.max_src_pts = ml.pair_capacity, ml.max_src_pts
+        h = C.c_void_p()
+        self.ctx.check(self.lib.pr_mapplane_create(self.ctx.h, ml.h, C.byref(h)))
+        self.h = h
+
+    _t = MapLocalizer._t
+    _pairs = MapLocalizer._pairs
+    _p = staticmethod(MapLocalizer._p)
+    _host_pairs = MapLocalizer._host_pairs
+
+    def _normals_args(self, who, normals, ninfo):
+        import torch
+        oc = self.wm.out_capacity
+        self._t(who, "normals", normals, torch.float64, (oc, 3))
+        self._t(who, "ninfo", ninfo, torch.int32, (oc,))
+
+    def normals_torch(self, radius: float, min_nbrs: int = 5, max_ratio: float = 0.1, out=None):
+        """Device form (pr_mapplane_normals_dev): (normals f64 [out_capacity, 3], ninfo i32 [out_capacity]) of the world rows as they are
+        on the stream, through the last index.  ninfo > 0: a valid normal from that many neighbours (the row included) within `radius`;
+        < 0: processed and invalid; 0: not an indexed row.  out: the pair an earlier call returned (fixed addresses for a capture)."""
+        import torch
+        who = "PlaneLocalizer.normals_torch"
+        dev, oc = self.wm.state.device, self.wm.out_capacity
+        if out is None:
+            out = (torch.empty((oc, 3), dtype=torch.float64, device=dev), torch.empty(oc, dtype=torch.int32, device=dev))
+        else:
+            self._normals_args(who, out[0], out[1])
+        p = self._p
+        self.ctx.check(self.lib.pr_mapplane_normals_dev(self.h, float(radius), int(min_nbrs), float(max_ratio), p(out[0]), p(out[1])))
+        return out
+
+    def refine_torch(self, xyz_q, offs_q, pair_src, T0, normals, ninfo, excl=None, max_iter: int = 30, max_corr: float = 0.9,
+                     tol_rmse: float = 1e-6, tol_fitness: float = 1e-6, min_inliers: int = 6, out=None):
+        """Device form (pr_mapplane_refine_dev): point-to-plane ICP of every pair from its seed T0 f64 [c, 3, 4] against the world rows
+        and their normals (normals_torch's pair).  Returns (T f64 [c, 3, 4], stats u8 [c, 32] - ICP_STATS on the host); out as for
+        MapLocalizer.refine_torch; out[0] may be T0."""
+        import torch
+        who = "PlaneLocalizer.refine_torch"
+        c = self._pairs(who, xyz_q, offs_q, pair_src, T0, excl)
+        self._normals_args(who, normals, ninfo)
+        dev = self.wm.state.device
+        if out is None:
+            out = (torch.empty((c, 3, 4), dtype=torch.float64, device=dev), torch.zeros((c, ICP_STATS.itemsize), dtype=torch.uint8, device=dev))
+        else:
+            self._t(who, "out[0]", out[0], torch.float64, (c, 3, 4))
+            self._t(who, "out[1]", out[1], torch.uint8, (c, ICP_STATS.itemsize))
+        p = self._p
+        self.ctx.check(self.lib.pr_mapplane_refine_dev(self.h, p(xyz_q), p(offs_q), offs_q.numel() - 1, p(pair_src), c, p(T0), p(excl),
+                                                       int(max_iter), float(max_corr), float(tol_rmse), float(tol_fitness), int(min_inliers),
+                                                       p(normals), p(ninfo), p(out[0]), p(out[1])))
+        return out
+
+    def localize_torch(self, xyz_q, offs_q, poses, n, idx, normals, ninfo, accepted=None, T_rel=None, src=None, excl=None, max_iter: int = 30,
+                       max_corr: float = 0.9, tol_rmse: float = 1e-6, tol_fitness: float = 1e-6, min_inliers: int = 6,
+                       min_fitness: float = 0.5, max_rmse: float = 0.5, out=None):
+        """MapLocalizer.localize_torch with the plane metric: the localiser's seed_torch -> refine_torch -> pr_verify_select_dev with one
+        hypothesis, on the context's stream without read-back.  Returns (T f64 [c, 3, 4], stats u8 [c, 32], accepted bool [c]); out: the
+        dict an earlier call left in .last_localize for the same c."""
+        import torch
+        who = "PlaneLocalizer.localize_torch"
+        c = idx.numel()
+        dev = self.wm.state.device
+        if out is None:
+            out = dict(seed=None, refine=None, T=torch.empty((c, 3, 4), dtype=torch.float64, device=dev),
+                       stats=torch.zeros((c, ICP_STATS.itemsize), dtype=torch.uint8, device=dev),
+                       accepted=torch.zeros(c, dtype=torch.bool, device=dev), hyp=torch.zeros(c, dtype=torch.int32, device=dev))
+        elif out["T"].shape != (c, 3, 4):
+            raise ValueError(f"{who}: out belongs to another c")
+        out["seed"] = self.ml.seed_torch(poses, n, idx, accepted, T_rel, src, out=out["seed"])
+        T0, pair_src = out["seed"]
+        out["refine"] = self.refine_torch(xyz_q, offs_q, pair_src, T0, normals, ninfo, excl, max_iter, max_corr, tol_rmse, tol_fitness,
+                                          min_inliers, out=out["refine"])
+        p = self._p
+        self.ctx.check(self.lib.pr_verify_select_dev(self.ctx.h, p(out["refine"][0]), p(out["refine"][1]), c, 1, float(min_fitness), float(max_rmse),
+                                                     p(out["T"]), p(out["stats"]), p(out["accepted"]), p(out["hyp"])))
+        self.last_localize = out
+        return out["T"], out["stats"], out["accepted"]
+
+    # ---- host forms (synchronise)
+    def normals(self, radius: float, min_nbrs: int = 5, max_ratio: float = 0.1):
+        """Host form (pr_mapplane_normals): (normals f64 [out_capacity, 3], ninfo i32 [out_capacity]) as numpy arrays."""
+        oc = self.wm.out_capacity
+        nrm = np.zeros((oc, 3), np.float64); info = np.zeros(oc, np.int32)
+        self.ctx.check(self.lib.pr_mapplane_normals(self.h, float(radius), int(min_nbrs), float(max_ratio), _ptr(nrm), _ptr(info)))
+        return nrm, info
+
+    def refine(self, xyz_q, offs_q, pair_src, T0, normals, ninfo, excl=None, max_iter: int = 30, max_corr: float = 0.9, tol_rmse: float = 1e-6,
+               tol_fitness: float = 1e-6, min_inliers: int = 6):
+        """Host form (pr_mapplane_refine) over numpy arrays: (T f64 [c, 3, 4], stats [c] of dtype ICP_STATS)."""
+        who = "PlaneLocalizer.refine"
+        xq, oq, ps, c, T0, ex = self._host_pairs(who, xyz_q, offs_q, pair_src, T0, excl)
+        oc = self.wm.out_capacity
+        nrm = np.ascontiguousarray(normals, np.float64); info = np.ascontiguousarray(ninfo, np.int32)
+        if nrm.shape != (oc, 3) or info.shape != (oc,):
+            raise ValueError(f"{who}: normals must be [out_capacity, 3] and ninfo [out_capacity]")
+        T = np.empty((c, 3, 4)); stats = np.zeros(c, ICP_STATS)
+        self.ctx.check(self.lib.pr_mapplane_refine(self.h, _ptr(xq), _ptr(oq), len(oq) - 1, _ptr(ps), c, _ptr(T0), _ptr(ex), int(max_iter),
+                                                   float(max_corr), float(tol_rmse), float(tol_fitness), int(min_inliers), _ptr(nrm), _ptr(info),
+                                                   _ptr(T), _ptr(stats)))
+        return T, stats
+
+    def close(self):
+        if getattr(self, "h", None) and getattr(self.ctx, "h", None):
+            self.lib.pr_mapplane_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def split_points_by_pose(pose_ids, point_ids) -> np.ndarray:
     """The reference's cursor rule (utils/pts_preprocess.h:196-200) as per-pose pushes: at pose p the cursor takes points while
     id <= pose id, so an out-of-order id makes it wait.  Returns cuts int64 [len(pose_ids) + 1]: pose p is pushed the points

@@ -517,5 +517,21 @@ void launch_maploc_probe(hipStream_t st, const MapLocView& v, const IcpClouds& A
                          const long long* base, double* nn_d, int* nn_j, double mc2, double* part);
 void launch_maploc_seed(hipStream_t st, const double* poses, const int* n, int kcap, const int32_t* idx, const unsigned char* accepted,
                         const double* T_rel, const int32_t* src, int c, double* T0, int32_t* pair_src);
+// mapplane.hip — world-map normals through the localiser's index and the plane-metric refinement behind its probe.
+// A chunk's record: inliers, sum d2, plane correspondents, the 21 entries of sum J J^T (upper triangle, row-major), the 6 of sum J r.
+constexpr int MAPPLANE_SUMS = 30;
+}  // namespace pr
+struct pr_maploc;
+namespace pr {
+// maploc.cpp: what a pr_mapplane borrows of its localiser (the view's table, sizes and world record; its context)
+const MapLocView* maploc_view(pr_maploc* ml);
+pr_ctx* maploc_ctx(pr_maploc* ml);
+// one lane per row of out_capacity: normals [out_capacity][3], ninfo [out_capacity]; r2 = fl(radius^2)
+void launch_mapplane_normals(hipStream_t st, const MapLocView& v, double r2, int min_nbrs, double max_ratio, double* normals, int* ninfo);
+// behind launch_maploc_probe with rows at pair * ld: part [c][nchunks][MAPPLANE_SUMS]
+void launch_mapplane_sums(hipStream_t st, const IcpClouds& A, const double* T, const int* done, const double* nn_d, const int* nn_j, int ld,
+                          int nchunks, double mc2, const double* normals, const int* ninfo, double* part);
+void launch_mapplane_update(hipStream_t st, const IcpClouds& A, const double* part, int nchunks, const IcpParams& P, int final_pass, double* T,
+                            IcpStats* stats, int* done, double* prev);
 
 }  // namespace pr

@@ -107,6 +107,11 @@ hipError_t upload_pairs(pr_maploc* ml, hipStream_t st, const double* xyz_q, cons
 
 }  // namespace
 
+namespace pr {
+const MapLocView* maploc_view(pr_maploc* ml) { return ml ? &ml->v : nullptr; }
+pr_ctx* maploc_ctx(pr_maploc* ml) { return ml ? ml->ctx : nullptr; }
+}  // namespace pr
+
 extern "C" {
 
 int64_t pr_maploc_scratch_bytes(int64_t out_capacity, int32_t pair_capacity, int32_t max_src_pts) {
