@@ -1341,6 +1341,100 @@ int pr_gate_run_dev(pr_gate* g, const double* d_poses, const int32_t* d_n, uint8
 int pr_gate_run(pr_gate* g, const double* d_poses, const int32_t* d_n, uint8_t* keep, int32_t* support, int32_t* map, int32_t* info);
 size_t pr_gate_scratch_bytes(int32_t node_capacity, int32_t edge_capacity, int32_t max_gap);
 void pr_gate_destroy(pr_gate* g);
+
+/* ---- sequence matching: trajectory-summed scores and their top-k (seqmatch.hip) ------------------------------------------
+ * Every other matcher answers one keyframe at a time: the row minimum of run_test.m:57.  A drive is a sequence: a true revisit is a LINE in
+ * the distance matrix (query i - l matches DB row j -/+ l), a perceptual alias an isolated low cell.  The sequence form sums the fused
+ * scores along short DB trajectories (SeqSLAM; Milford & Wyeth 2012) and selects on the sums, which removes aliases before any
+ * verification is spent on them.
+ *
+ * The step table.  steps is i32 [V][L], 1 <= L <= PR_SEQ_MAX_L, 1 <= V <= PR_SEQ_MAX_V, steps[v][0] == 0, |steps[v][l]| <=
+ * PR_SEQ_MAX_STEP: steps[v][l] is how many DB rows BEHIND the candidate the trajectory of velocity v lies at query lag l (negative: a
+ * reverse traversal; all zeros: a standstill).  The device only indexes with it; no velocity arithmetic happens there.  A host table that
+ * breaks a limit is PR_EINVAL ("bad step table"); a row of a DEVICE table that does is a dropped velocity for every cell.
+ *
+ *   pr_seq_select_dev   d_p, d_i f32 [m][n] and mom f64 [m][2][3]: what pr_distances_dev and pr_row_moments_dev wrote; d_steps i32 [V][L];
+ *                       idx i32, score f64, vel i32 [m][k], 1 <= k <= PR_SEQ_MAX_K; d_S NULL or f64 [m][n].  All pointers are device
+ *                       memory.  Stream-ordered, capturable, no read-back, no allocation: the lists of the column parts live in a block the
+ *                       context allocated at create.  One launch, or two when few query rows are cut into column parts; every grid
+ *                       depends on (m, n) only.  m == 0 launches nothing.
+ *   pr_seq_tile         the kernel's tile: rows query rows by cols columns per workgroup and slab.
+ *   pr_match_topk_seq_f64   host buffers: the shared top-k pipeline's pack + distances + moments (PR_TYPE_SC, PR_TYPE_M2DP; PR_TYPE_DELIGHT:
+ *                       one matrix, the d_i == NULL form), then pr_seq_select_dev with q_row0 = db_row0 = 0.  steps is a HOST table.
+ *
+ * The rule (restated in tests/seqmatch_np.py; the device equals it bit for bit; fp64, no contraction).
+ *   1. Cell score.  f(i, j) = p_weight * (((double)d_p[i][j] - mean_p) / sd_p) + ((double)d_i[i][j] - mean_i) / sd_i with mean = mom[i][c][1]
+ *      and sd = sqrt(M2 / (count - 1.0)) = sqrt(mom[i][c][2] / (mom[i][c][0] - 1.0)): IEEE operations, every division correctly rounded.
+ *      With d_i == NULL there is no normalisation: f = (double)d_p[i][j] and mom is not read (DELIGHT, GIST and BoW distance matrices).
+ *   2. Masked cells.  Cell (a, c) is masked iff |(q_row0 + a) - (db_row0 + c)| < mask_width.
+ *   3. Lags.  For query row i, L_i = min(L, i + 1): lags reach local rows i - l >= 0 only.  A query shard does not see earlier shards.
+ *   4. Sum per velocity.  S_v(i, j) = sum over l = 0 .. L_i - 1, added in ascending l from 0.0, of f(i - l, j - steps[v][l]).
+ *   5. Dropped velocities.  A velocity is dropped for the cell if any term's column lies outside 0 .. n - 1, any term's own cell is
+ *      masked, any term is NaN, or the sum is NaN.  +/-Inf terms add by IEEE.
+ *   6. Cell result.  S(i, j) = min over the kept v of S_v / (double)L_i, strict <, so the first v wins a tie.  A masked (i, j), or one
+ *      with no kept velocity, is not a candidate; its d_S entry is +Inf.
+ *   7. Selection.  Per row the k smallest candidates by (S, j), so the smaller j wins a tie: idx = db_row0 + j, score = S, vel = v.
+ *      Missing slots are -1 / NaN / -1.
+ * Scope.  The sequence form is a function of the f32 matrices pr_distances_dev wrote: it has NO fp64 re-evaluation and NO containment
+ * check (pr_rerank_dev, pr_order_resolve_dev have no counterpart here), so its scores are fp32-grade in the distances.  There is no
+ * velocity search beyond the table, no sharded form, and lags do not cross query shards.
+ * PR_EINVAL (text: pr_last_error) before any device is touched for a NULL pointer (d_p, d_steps, idx, score, vel; mom with d_i given),
+ * m < 0, n < 1, V outside 1 .. 16, L outside 1 .. 32, k outside 1 .. 32, mask_width < 0. */
+#define PR_SEQ_MAX_L 32
+#define PR_SEQ_MAX_V 16
+#define PR_SEQ_MAX_STEP 64
+#define PR_SEQ_MAX_K 32
+int pr_seq_select_dev(pr_ctx* ctx, const float* d_p, const float* d_i, int32_t m, int32_t n, const double* mom, const int32_t* d_steps,
+                      int32_t V, int32_t L, int32_t q_row0, int32_t db_row0, int32_t mask_width, double p_weight, int32_t k, int32_t* idx,
+                      double* score, int32_t* vel, double* d_S);
+void pr_seq_tile(int32_t* rows, int32_t* cols);
+int pr_match_topk_seq_f64(pr_ctx* ctx, int type, const double* h1, int32_t m, const double* h2, int32_t n, int32_t mask_width, double p_weight,
+                          int32_t k, const int32_t* steps, int32_t V, int32_t L, int32_t* idx, double* score, int32_t* vel);
+
+/* The online form: one keyframe per captured step.  A pr_seqmatch is a handle over a ring of the last L fused score rows.
+ *   pr_seqmatch_create     makes ONE allocation (steps is a HOST table); no later call allocates, every grid depends on the create sizes
+ *                          only.  With B = ceil(capacity / 256) and K = max_k the parts are, each rounded up to 16 bytes:
+ *                            8 L capacity (the ring [L][capacity] f64) | 4 L (the slots' row ids) | 16 (the push counter) | 64 (row
+ *                            statistics) | 16 (control) | 4 V L (the step table) | 8 B K | 4 B K | 4 B K (the workgroups' lists)
+ *                            | staging of the host form: 8 channels capacity | 16 | 8 K | 4 K | 4 K | 16
+ *                          pr_seqmatch_scratch_bytes returns the sum (0 for sizes create refuses).
+ *   pr_seqmatch_push_dev   three launches, no read-back.  d_rows f64 [channels][capacity] is exactly what pr_online_match_dev /
+ *                          pr_onlineset_match_dev write as their rows; d_count [>= 1] i32 is the database's state (word 0: its count);
+ *                          d_emitted NULL or [>= 1] i32; weights is a HOST array [channels] (its values enter the launch: a captured push
+ *                          keeps them); d_idx i32, d_score f64, d_vel i32 [k]; d_info i32 [4].
+ *   pr_seqmatch_push       the same over HOST rows [channels][capacity], a host count and host outputs; synchronises.
+ *   pr_seqmatch_reset      stream-ordered: ring, row ids and counter back to zero bytes.
+ *   pr_seqmatch_read       ring [L][capacity], row ids [L] and the counter to the host (any may be NULL); synchronises.
+ * The rule (tests/seqmatch_np.py SeqFilter restates it):
+ *   1. Switched off.  d_emitted != NULL && d_emitted[0] == 0 writes -1 / NaN / -1 and info = {0, 0, pushes, 0}.  The ring, the row ids
+ *      and the counter do not change by a byte.
+ *   2. Row formed and stored.  Otherwise n = count clamped into 0 .. capacity before any address is formed from it.  The fused row is
+ *      F_n[j] for j < n.  normalize = 1: F = sum_c weights[c] * z_c, added in ascending c from 0.0, z_c = (rows[c][j] - mean_c) / sd_c, the
+ *      row z-score over the non-NaN j < n: count_c of them, mean_c = sum / count_c, M2_c = sum of (x - mean_c)^2, sd_c = sqrt(M2_c /
+ *      (count_c - 1.0)).  The order of both sums is fixed by n alone: partial sum t of 256 adds the non-NaN entries j = t, t + 256, ..
+ *      in ascending j from 0.0; then p[t] += p[t + s] for s = 128, 64, .. 1; the sum is p[0].  normalize = 0 needs channels == 1 and gives
+ *      F = rows[0].  The row is stored in slot (pushes mod L) - columns >= n of the slot keep their bytes - together with n; the counter
+ *      is committed by one thread.  The payload of a NaN that arithmetic produced is not specified.
+ *   3. Sequence score.  L_n = min(L, pushes so far including this one).  S(n, j) follows the batch rule 4 - 6 with lag l the l-th earlier
+ *      PUSHED row, of row id n_l: its term needs 0 <= c < n_l and |n_l - c| >= mask_width with c = j - steps[v][l]; lag 0 is F_n[j].  The
+ *      query is row n, as in pr_online: selection is the k smallest by (S, j) over j < n with n - j >= mask_width; idx = j.
+ *   4. Info.  info = {pushed, L_n, pushes after, 0}.  n < 2 with normalize = 1 leaves every slot -1 / NaN / -1 and still counts as a push
+ *      (of an all-NaN row).
+ * PR_EINVAL before any device is touched for NULL pointers, capacity outside 1 .. 2^24, channels outside {1, 2, 4}, a bad step table, k
+ * outside 1 .. max_k or max_k outside 1 .. PR_SEQMATCH_MAX_K, a non-finite weight, mask_width < 0, normalize outside {0, 1}, and
+ * normalize = 0 with channels != 1. */
+#define PR_SEQMATCH_MAX_K 128
+typedef struct pr_seqmatch pr_seqmatch;
+int pr_seqmatch_create(pr_ctx* ctx, int32_t capacity, int32_t channels, const int32_t* steps, int32_t V, int32_t L, int32_t max_k,
+                       pr_seqmatch** out);
+int pr_seqmatch_push_dev(pr_seqmatch* s, const double* d_rows, const int32_t* d_count, const int32_t* d_emitted, const double* weights,
+                         int32_t normalize, int32_t mask_width, int32_t k, int32_t* d_idx, double* d_score, int32_t* d_vel, int32_t* d_info);
+int pr_seqmatch_push(pr_seqmatch* s, const double* rows, int32_t count, const double* weights, int32_t normalize, int32_t mask_width, int32_t k,
+                     int32_t* idx, double* score, int32_t* vel, int32_t* info);
+int pr_seqmatch_reset(pr_seqmatch* s);
+int pr_seqmatch_read(pr_seqmatch* s, double* ring, int32_t* ids, int32_t* pushes);
+size_t pr_seqmatch_scratch_bytes(int32_t capacity, int32_t channels, int32_t V, int32_t L, int32_t max_k);
+void pr_seqmatch_destroy(pr_seqmatch* s);
 const char* pr_host_last_error(void);
 
 #ifdef __cplusplus

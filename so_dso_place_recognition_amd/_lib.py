@@ -33,6 +33,8 @@ POSEGRAPH_MAX_K = 128                               # most slots of one pr_poseg
 WORLDMAP_OVERFLOW, WORLDMAP_SKIPPED, WORLDMAP_RANGE, WORLDMAP_TABLE = 1, 2, 4, 8   # flags of a pr_worldmap fuse (state[1], info[3])
 MAPLOC_SKIPPED, MAPLOC_RANGE, MAPLOC_DUPLICATE, MAPLOC_TABLE = 1, 2, 4, 8           # flags of a pr_maploc index (info[2])
 GATE_SRC_OVERFLOW, GATE_UNSETTLED = 1, 2            # flags of a pr_gate run (info[3])
+SEQ_MAX_L, SEQ_MAX_V, SEQ_MAX_STEP, SEQ_MAX_K = 32, 16, 64, 32   # limits of a sequence-matching step table and call (PR_SEQ_*)
+SEQMATCH_MAX_K = 128                                # most slots of one pr_seqmatch push
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PR_AMD_LIB") or os.path.join(_HERE, "libpr_amd.so")   # PR_AMD_LIB: experiment builds only
@@ -282,6 +284,16 @@ SYMBOLS = {
     "pr_gate_run": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pr_gate_scratch_bytes": (C.c_size_t, [_i32, _i32, _i32]),
     "pr_gate_destroy": (None, [_vp]),
+    "pr_seq_select_dev": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _dbl, _i32, _vp, _vp, _vp, _vp]),
+    "pr_seq_tile": (None, [C.POINTER(_i32), C.POINTER(_i32)]),
+    "pr_match_topk_seq_f64": (C.c_int, [_vp, C.c_int, _vp, _i32, _vp, _i32, _i32, _dbl, _i32, _vp, _i32, _i32, _vp, _vp, _vp]),
+    "pr_seqmatch_create": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i32, _i32, C.POINTER(_vp)]),
+    "pr_seqmatch_push_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "pr_seqmatch_push": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "pr_seqmatch_reset": (C.c_int, [_vp]),
+    "pr_seqmatch_read": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "pr_seqmatch_scratch_bytes": (C.c_size_t, [_i32, _i32, _i32, _i32, _i32]),
+    "pr_seqmatch_destroy": (None, [_vp]),
     "pr_host_last_error": (C.c_char_p, []),
 }
 

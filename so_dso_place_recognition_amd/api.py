@@ -782,6 +782,106 @@ def match_topk_fused(sc1, m2dp1, sc2, m2dp2, mask_width=0, p_weight=2.0, k=1, ct
     return idx, sc
 
 
+def seq_steps(L: int, velocities) -> np.ndarray:
+    """The step table of the sequence matcher, i32 [V, L]: row v holds, for query lag l, how many DB rows behind the
+    candidate the trajectory of velocity velocities[v] lies: sign(v) * floor(|v| l + 0.5).  Negative velocities are a reverse traversal,
+    0 a standstill.  Identical rows are dropped, keeping the first."""
+    L = int(L)
+    if not 1 <= L <= _lib.SEQ_MAX_L:
+        raise ValueError(f"seq_steps: L must be in 1 .. {_lib.SEQ_MAX_L}")
+    rows = []
+    for v in velocities:
+        v = float(v)
+        if not np.isfinite(v):
+            raise ValueError("seq_steps: a velocity is not finite")
+        sg = (v > 0) - (v < 0)
+        row = [int(sg * np.floor(abs(v) * l + 0.5)) for l in range(L)]
+        if max(abs(s) for s in row) > _lib.SEQ_MAX_STEP:
+            raise ValueError(f"seq_steps: velocity {v} reaches beyond {_lib.SEQ_MAX_STEP} rows within {L} lags")
+        if row not in rows:
+            rows.append(row)
+    if not 1 <= len(rows) <= _lib.SEQ_MAX_V:
+        raise ValueError(f"seq_steps: 1 .. {_lib.SEQ_MAX_V} distinct velocities")
+    return np.array(rows, np.int32).reshape(len(rows), L)
+
+
+def seq_tile():
+    """(rows, cols) of the batch kernel's tile (pr_seq_tile); needs no device."""
+    lib = _lib.load()
+    r, c = C.c_int32(), C.c_int32()
+    lib.pr_seq_tile(C.byref(r), C.byref(c))
+    return int(r.value), int(c.value)
+
+
+def _check_steps(steps, who):
+    st = np.ascontiguousarray(steps, np.int32)
+    if st.ndim != 2 or not (1 <= st.shape[0] <= _lib.SEQ_MAX_V and 1 <= st.shape[1] <= _lib.SEQ_MAX_L) or (st[:, 0] != 0).any() \
+            or np.abs(st).max() > _lib.SEQ_MAX_STEP:
+        raise ValueError(f"{who}: steps must be i32 [V <= {_lib.SEQ_MAX_V}, L <= {_lib.SEQ_MAX_L}] with steps[:, 0] == 0 and "
+                         f"|steps| <= {_lib.SEQ_MAX_STEP} (api.seq_steps builds one)")
+    return st
+
+
+def seq_select_torch(d_p, d_i, mom, steps, q_row0: int = 0, db_row0: int = 0, mask_width: int = 0, p_weight: float = 2.0, k: int = 1,
+                     dense: bool = False, ctx: Context | None = None, out=None):
+    """Device form of the sequence selection (pr_seq_select_dev): d_p, d_i f32 [m, n] and mom f64 [m, 2, 3] as
+    pr_distances_dev / pr_row_moments_dev wrote them (d_i = None: one matrix, no normalisation, mom unused), steps a CUDA i32 [V, L]
+    tensor.  Returns (idx i32 [m, k] global DB rows, score f64 [m, k], vel i32 [m, k][, S f64 [m, n] with dense=True]); out: an earlier
+    call's tuple, written again.  Enqueued on the context's stream; nothing synchronises or, given out=, allocates."""
+    import torch
+    ctx = ctx or _torch_default_context(d_p.device.index)
+    who = "seq_select_torch"
+    if (not d_p.is_cuda) or d_p.dtype != torch.float32 or d_p.dim() != 2 or not d_p.is_contiguous():
+        raise ValueError(f"{who}: d_p must be a contiguous CUDA tensor f32 [m, n]")
+    m, n = d_p.shape
+    if d_i is not None:
+        if (not d_i.is_cuda) or d_i.dtype != torch.float32 or tuple(d_i.shape) != (m, n) or not d_i.is_contiguous():
+            raise ValueError(f"{who}: d_i must be a contiguous CUDA tensor f32 [m, n]")
+        if mom is None or (not mom.is_cuda) or mom.dtype != torch.float64 or mom.numel() != 6 * m or not mom.is_contiguous():
+            raise ValueError(f"{who}: mom must be a contiguous CUDA tensor f64 [m, 2, 3]")
+    if (not steps.is_cuda) or steps.dtype != torch.int32 or steps.dim() != 2 or not steps.is_contiguous():
+        raise ValueError(f"{who}: steps must be a contiguous CUDA tensor i32 [V, L]")
+    V, L = steps.shape
+    k = int(k)
+    dev = d_p.device
+    if out is None:
+        out = (torch.empty((m, max(k, 0)), dtype=torch.int32, device=dev), torch.empty((m, max(k, 0)), dtype=torch.float64, device=dev),
+               torch.empty((m, max(k, 0)), dtype=torch.int32, device=dev)) + ((torch.empty((m, n), dtype=torch.float64, device=dev),) if dense else ())
+    elif len(out) != (4 if dense else 3) or any(tuple(t.shape) != (m, k) or not t.is_contiguous() or not t.is_cuda for t in out[:3]) \
+            or (out[0].dtype, out[1].dtype, out[2].dtype) != (torch.int32, torch.float64, torch.int32) \
+            or (dense and (tuple(out[3].shape) != (m, n) or out[3].dtype != torch.float64 or not out[3].is_contiguous())):
+        raise ValueError(f"{who}: out must be (idx i32 [m, k], score f64 [m, k], vel i32 [m, k][, S f64 [m, n]]) CUDA tensors")
+    if m == 0:
+        return out
+    p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+    ctx.check(ctx.lib.pr_seq_select_dev(ctx.h, p(d_p), p(d_i), m, n, p(mom) if d_i is not None else None, p(steps), V, L, int(q_row0),
+                                        int(db_row0), int(mask_width), float(p_weight), k, p(out[0]), p(out[1]), p(out[2]),
+                                        p(out[3]) if dense else None))
+    return out
+
+
+def match_topk_seq(type_, hist1, hist2, steps, mask_width=0, p_weight=2.0, k=1, ctx: Context | None = None):
+    """Sequence matching over host buffers (pr_match_topk_seq_f64): hist1's rows are consecutive keyframes of a drive.  type_ 'sc',
+    'm2dp' or 'delight'; steps as api.seq_steps builds it.  Returns (idx int32 [m, k], score float64 [m, k], vel int32 [m, k])."""
+    ctx = ctx or default_context()
+    t = {"sc": TYPE_SC, "m2dp": TYPE_M2DP, "delight": TYPE_DELIGHT}.get(type_, type_)
+    if t not in (TYPE_SC, TYPE_M2DP, TYPE_DELIGHT):
+        raise ValueError("type must be 'sc', 'm2dp' or 'delight'")
+    st = _check_steps(steps, "match_topk_seq")
+    div, width = {TYPE_SC: (1, 2400), TYPE_M2DP: (4, 384), TYPE_DELIGHT: (16, 256)}[t]
+    h1 = np.ascontiguousarray(hist1, np.float64)
+    h2 = np.ascontiguousarray(hist2, np.float64)
+    if h1.ndim != 2 or h2.ndim != 2 or h1.shape[1] != width or h2.shape[1] != width:
+        raise ValueError(f"signature width must be {width}")
+    if h1.shape[0] % div or h2.shape[0] % div:
+        raise ValueError(f"signature matrices of this type hold {div} rows per signature")
+    m, n = h1.shape[0] // div, h2.shape[0] // div
+    idx, sc, vel = np.empty((m, k), np.int32), np.empty((m, k), np.float64), np.empty((m, k), np.int32)
+    ctx.check(ctx.lib.pr_match_topk_seq_f64(ctx.h, t, _ptr(h1), m, _ptr(h2), n, int(mask_width), float(p_weight), int(k), _ptr(st),
+                                            st.shape[0], st.shape[1], _ptr(idx), _ptr(sc), _ptr(vel)))
+    return idx, sc, vel
+
+
 def match_align(type_, hist1, hist2, idx, ctx: Context | None = None):
     """The best-aligning variant of every matched pair (pr_match_align): idx [m,k] as match_topk returns it (-1 = none).  Returns
     (variant int32 [m,k,2], dist float64 [m,k,2]) per channel - SC: structure, intensity, v = 2 * shift + mirror; M2DP: count, intensity,
@@ -1856,6 +1956,93 @@ class ClosureGate:
     def close(self):
         if getattr(self, "h", None) and getattr(self.ctx, "h", None):
             self.lib.pr_gate_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class SequenceFilter:
+    """pr_seqmatch: the online form of the sequence matcher - a ring of the last L fused score rows of a drive.  Every
+    keyframe, push_torch takes the distance rows an OnlineDatabase / OnlineSet match wrote (rows=) and the database's .state, fuses them
+    into one row (the row z-scores weighted, or the one row as it is with normalize=False), stores it and returns the k rows whose
+    scores summed along the step table's trajectories over the earlier pushed rows are smallest.  steps: api.seq_steps(L, velocities).
+    Calls are enqueued on the context's stream, read the count on the device and allocate nothing; ONE captured push_torch serves every
+    keyframe (the weights' values are part of the capture)."""
+
+    def __init__(self, ctx: Context | None, capacity: int, channels: int, steps, max_k: int = 8):
+        self.ctx = ctx or default_context()
+        self.lib = self.ctx.lib
+        self.h = None
+        self.steps = _check_steps(steps, "SequenceFilter")
+        self.capacity, self.channels, self.max_k = int(capacity), int(channels), int(max_k)
+        self.V, self.L = self.steps.shape
+        h = C.c_void_p()
+        self.ctx.check(self.lib.pr_seqmatch_create(self.ctx.h, self.capacity, self.channels, _ptr(self.steps), self.V, self.L, self.max_k,
+                                                   C.byref(h)))
+        self.h = h
+
+    def _weights(self, weights, who):
+        w = np.ascontiguousarray(weights, np.float64).reshape(-1)
+        if len(w) != self.channels:
+            raise ValueError(f"{who}: weights must hold {self.channels} numbers")
+        return w
+
+    def push_torch(self, rows, state, weights, normalize: bool = True, mask_width: int = 0, k: int = 1, emitted=None, out=None):
+        """Device form (pr_seqmatch_push_dev): rows f64 [channels, capacity], state i32 [>= 1] (word 0: the database's count = this
+        keyframe's row id), weights [channels] host numbers (SC / M2DP rows: (p_weight, 1)).  emitted i32 [>= 1] | None: emitted[0] == 0
+        switches the push off on the device.  Returns (idx i32 [1, k], score f64 [1, k], vel i32 [1, k], info i32 [4] = pushed, lags used,
+        pushes after, 0); out: an earlier call's tuple, written again."""
+        import torch
+        who = "SequenceFilter.push_torch"
+        k = int(k)
+        if (not rows.is_cuda) or rows.dtype != torch.float64 or not rows.is_contiguous() or rows.numel() != self.channels * self.capacity:
+            raise ValueError(f"{who}: rows must be a contiguous CUDA tensor f64 [{self.channels}, {self.capacity}]")
+        for name, t in (("state", state), ("emitted", emitted)):
+            if t is not None and ((not t.is_cuda) or t.dtype != torch.int32 or not t.is_contiguous() or t.numel() < 1):
+                raise ValueError(f"{who}: {name} must be a CUDA tensor i32 [>= 1]")
+        w = self._weights(weights, who)
+        dev = rows.device
+        if out is None:
+            out = (torch.empty((1, max(k, 0)), dtype=torch.int32, device=dev), torch.empty((1, max(k, 0)), dtype=torch.float64, device=dev),
+                   torch.empty((1, max(k, 0)), dtype=torch.int32, device=dev), torch.empty(4, dtype=torch.int32, device=dev))
+        elif len(out) != 4 or any(tuple(t.shape) != (1, k) or not t.is_cuda or not t.is_contiguous() for t in out[:3]) or out[3].numel() != 4 \
+                or [t.dtype for t in out] != [torch.int32, torch.float64, torch.int32, torch.int32] or not out[3].is_cuda:
+            raise ValueError(f"{who}: out must be (idx i32 [1, k], score f64 [1, k], vel i32 [1, k], info i32 [4]) CUDA tensors")
+        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        self.ctx.check(self.lib.pr_seqmatch_push_dev(self.h, p(rows), p(state), p(emitted), _ptr(w), int(bool(normalize)), int(mask_width), k,
+                                                     p(out[0]), p(out[1]), p(out[2]), p(out[3])))
+        return out
+
+    def push(self, rows, count: int, weights, normalize: bool = True, mask_width: int = 0, k: int = 1):
+        """Host form (pr_seqmatch_push; synchronises): rows a NumPy array [channels, capacity].  Returns NumPy (idx [k], score [k],
+        vel [k], info [4])."""
+        who = "SequenceFilter.push"
+        r = np.ascontiguousarray(rows, np.float64).reshape(-1)
+        if len(r) != self.channels * self.capacity:
+            raise ValueError(f"{who}: rows must hold {self.channels} x {self.capacity} numbers")
+        w = self._weights(weights, who)
+        k = int(k)
+        idx, score, vel, info = np.empty(max(k, 0), np.int32), np.empty(max(k, 0), np.float64), np.empty(max(k, 0), np.int32), np.empty(4, np.int32)
+        self.ctx.check(self.lib.pr_seqmatch_push(self.h, _ptr(r), int(count), _ptr(w), int(bool(normalize)), int(mask_width), k, _ptr(idx),
+                                                 _ptr(score), _ptr(vel), _ptr(info)))
+        return idx, score, vel, info
+
+    def read(self):
+        """(ring f64 [L, capacity], row ids i32 [L], pushes) on the host; synchronises (pr_seqmatch_read)."""
+        ring, ids, n = np.empty((self.L, self.capacity), np.float64), np.empty(self.L, np.int32), C.c_int32()
+        self.ctx.check(self.lib.pr_seqmatch_read(self.h, _ptr(ring), _ptr(ids), C.byref(n)))
+        return ring, ids, int(n.value)
+
+    def reset(self):
+        self.ctx.check(self.lib.pr_seqmatch_reset(self.h))
+
+    def close(self):
+        if getattr(self, "h", None) and getattr(self.ctx, "h", None):
+            self.lib.pr_seqmatch_destroy(self.h)
         self.h = None
 
     def __del__(self):

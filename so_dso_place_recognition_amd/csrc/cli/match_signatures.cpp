@@ -27,12 +27,18 @@
 //   [--icp_hyp 2]                     (--type sc) also refine the intensity channel's variant where it differs from the structure channel's and
 //                                     keep the better result (larger fitness, then smaller rmse, among status converged / max_iter; DESIGN.md
 //                                     4.12); the line then ends with the kept hypothesis "hyp" (0 | 1)
+//   [--seq_len L --seq_vel "1,-1,0.75,-0.75"]   sequence matching (sc | m2dp | delight): hist1's rows are consecutive keyframes of a
+//                                     drive; the scores are summed along L lags of DB trajectories of the listed velocities (rows of DB per query
+//                                     row; negative: a reverse traversal; default "1,-1") and the K smallest means are returned
+//                                     (pr_match_topk_seq_f64).  Refused together with --online, --icp_out, --align_out or --devices
 //   [--icp_search brute|grid]         the correspondence search of the refinement (pr_set_icp_search; default: the context's mode, i.e. brute
 //                                     force unless PR_ICP_SEARCH says otherwise).  grid: the exact uniform-grid search
 // Output: one line per query: K pairs "index score" (0-based indices unless --one_based 1), and the reference's
 // console lines `type` / `tm` (ms per query, run_test.m:42-44).  Scores are doubles, as MATLAB holds them.
+#include <algorithm>
 #include <chrono>
 #include <cmath>
+#include <cstdlib>
 #include <vector>
 
 #include <hip/hip_runtime.h>
@@ -66,6 +72,36 @@ int main(int argc, char** argv) {
   std::string icp_search;
   const bool has_icp_search = prm.get("icp_search", icp_search);
   if (has_icp_search && icp_search != "brute" && icp_search != "grid") { fprintf(stderr, "--icp_search is brute or grid, not %s\n", icp_search.c_str()); return 1; }
+  // --seq_len L [--seq_vel "1,-1,..."]: the sequence form; the step table is api.seq_steps' (sign(v) floor(|v| l + 0.5), identical rows dropped)
+  const int seq_len = (int)prm.num("seq_len", 0);
+  std::vector<int32_t> seq_steps;
+  int seq_V = 0;
+  if (seq_len != 0) {
+    std::string a;
+    if (prm.num("online", 0) != 0 || want_icp || want_align || prm.get("devices", a)) {
+      fprintf(stderr, "--seq_len (sequence matching, one device, whole drive) cannot be combined with --online, --icp_out, --align_out or --devices\n");
+      return 1;
+    }
+    if (cols_type) { fprintf(stderr, "--seq_len needs --type sc|m2dp|delight\n"); return 1; }
+    if (seq_len < 1 || seq_len > PR_SEQ_MAX_L) { fprintf(stderr, "--seq_len is 1 .. %d, not %d\n", PR_SEQ_MAX_L, seq_len); return 1; }
+    std::string vels = "1,-1";
+    (void)prm.get("seq_vel", vels);
+    for (size_t p = 0; p < vels.size();) {
+      char* end = nullptr;
+      const double v = strtod(vels.c_str() + p, &end);
+      if (end == vels.c_str() + p || !std::isfinite(v)) { fprintf(stderr, "--seq_vel is a comma-separated list of numbers, not %s\n", vels.c_str()); return 1; }
+      std::vector<int32_t> row(seq_len);
+      for (int l = 0; l < seq_len; l++) row[l] = (int32_t)((v > 0 ? 1 : v < 0 ? -1 : 0) * std::floor(std::fabs(v) * l + 0.5));
+      if (std::abs(row[seq_len - 1]) > PR_SEQ_MAX_STEP) { fprintf(stderr, "--seq_vel: velocity %g reaches beyond %d rows within %d lags\n", v, PR_SEQ_MAX_STEP, seq_len); return 1; }
+      bool dup = false;
+      for (int u = 0; u < seq_V && !dup; u++) dup = std::equal(row.begin(), row.end(), seq_steps.begin() + (size_t)u * seq_len);
+      if (!dup) { seq_steps.insert(seq_steps.end(), row.begin(), row.end()); seq_V++; }
+      p = (size_t)(end - vels.c_str());
+      if (p < vels.size() && vels[p] != ',') { fprintf(stderr, "--seq_vel is a comma-separated list of numbers, not %s\n", vels.c_str()); return 1; }
+      p++;
+    }
+    if (seq_V < 1 || seq_V > PR_SEQ_MAX_V) { fprintf(stderr, "--seq_vel holds 1 .. %d distinct velocities\n", PR_SEQ_MAX_V); return 1; }
+  }
   const int div = t == PR_TYPE_SC ? 1 : t == PR_TYPE_M2DP ? 4 : t == PR_TYPE_DELIGHT ? 16 : t == PR_TYPE_BOW ? 2 : 1;
   int64_t width = t == PR_TYPE_SC ? PR_SC_SIG_LEN : (t == PR_TYPE_M2DP ? PR_M2DP_SIG_LEN : PR_DELIGHT_SIG_LEN);
   double *h1 = nullptr, *h2 = nullptr;
@@ -134,6 +170,11 @@ int main(int argc, char** argv) {
   } else if (grp) {
     rc = pr_group_match_topk(grp, h1, m, (int32_t)prm.num("mask_width", 0), prm.num("p_weight", 2.0), k, idx.data(), score.data());
     if (rc != PR_OK) { fprintf(stderr, "match failed (%d): %s\n", rc, pr_group_last_error(grp)); return 4; }
+  } else if (seq_len) {
+    std::vector<int32_t> vel((size_t)m * k);
+    rc = pr_match_topk_seq_f64(ctx, t, h1, m, h2, n, (int32_t)prm.num("mask_width", 0), prm.num("p_weight", 2.0), k, seq_steps.data(), seq_V, seq_len,
+                               idx.data(), score.data(), vel.data());
+    printf("seq_len = %d\nseq_velocities = %d\n", seq_len, seq_V);
   } else if (cols_type) {
     score32.resize(score.size());
     rc = pr_match_topk_cols(ctx, t, h1, m, h2, n, (int32_t)width, (int32_t)prm.num("mask_width", 0), k, idx.data(), score32.data());

@@ -401,6 +401,7 @@ void*& ctx_bow(pr_ctx* ctx);
 void*& ctx_eval(pr_ctx* ctx);
 void*& ctx_icp(pr_ctx* ctx);
 void*& ctx_pose(pr_ctx* ctx);
+void* ctx_seq_scratch(pr_ctx* ctx);           // the lists of pr_seq_select_dev's column parts (seqmatch.hpp: seq_scratch_bytes)
 int* ctx_bow_flag(pr_ctx* ctx);                 // [1] device word: a BoW row was truncated (PR_WARN_BOW_TRUNCATED at pr_take_warnings)
 int* ctx_bow_rows_flag(pr_ctx* ctx);            // [1] device word: a non-conforming BoW query row (PR_WARN_BOW_ROWS at pr_take_warnings)
 

@@ -17,6 +17,7 @@
 #include "kernels.hpp"
 #include "hash_order.hpp"
 #include "records.hpp"
+#include "seqmatch.hpp"
 #include <chrono>
 #include <unordered_map>
 
@@ -31,6 +32,7 @@ struct pr_ctx {
   hipEvent_t ev_b = nullptr;
   char* sc_scratch = nullptr;    // tickets + partial moments / bin grids of the split SC generation, one half per stream
   void* sel_scratch = nullptr;   // slice lists / partial moments of calls with few query rows (fuse_select.hip)
+  void* seq_scratch = nullptr;   // the column parts' candidate lists of pr_seq_select_dev (seqmatch.hip)
   unsigned long long* d_sel_fell = nullptr;   // rows moments_select_kernel answered through a second sweep (pr_select_fallback_rows)
   double* rr_scratch = nullptr;  // candidate scores of pr_rerank_dev (grow-only: a steady-state call allocates nothing and can be graph-captured)
   size_t rr_cap = 0;
@@ -239,6 +241,7 @@ static int create_common(int device_id, hipStream_t external, bool use_external,
     TRY(hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming));
     for (auto& e : ctx->ev_m2) TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     TRY(hipMalloc(&ctx->sel_scratch, pr::select_scratch_bytes()));
+    TRY(hipMalloc(&ctx->seq_scratch, pr::seq_scratch_bytes()));
     TRY(hipMalloc((void**)&ctx->d_sel_fell, sizeof(unsigned long long)));
     TRY(hipMemset(ctx->d_sel_fell, 0, sizeof(unsigned long long)));
     TRY(hipMalloc((void**)&ctx->d_flags, 8 * sizeof(int)));        // [4]: the binary-channel pass's violation flag (kernels.hpp: ScBin), not a deferred bit
@@ -375,6 +378,7 @@ void pr_destroy(pr_ctx* ctx) {
   if (ctx->xqspec) (void)hipFree(ctx->xqspec);
   if (ctx->xpart) (void)hipFree(ctx->xpart);
   if (ctx->sel_scratch) (void)hipFree(ctx->sel_scratch);
+  if (ctx->seq_scratch) (void)hipFree(ctx->seq_scratch);
   if (ctx->d_sel_fell) (void)hipFree(ctx->d_sel_fell);
   if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
   if (ctx->ev_join) (void)hipEventDestroy(ctx->ev_join);
@@ -1578,6 +1582,45 @@ int pr_match_topk_fused_f64(pr_ctx* ctx, const double* sc1, const double* m2dp1,
   return topk_host(ctx, "pr_match_topk_fused_f64", -1, sc1, m2dp1, m, sc2, m2dp2, n, mask_width, p_weight, k, idx, score);
 }
 
+// sequence matching over host buffers: the shared pipeline's pack + distances + moments, then pr_seq_select_dev
+int pr_match_topk_seq_f64(pr_ctx* ctx, int type, const double* h1, int32_t m, const double* h2, int32_t n, int32_t mask_width, double p_weight,
+                          int32_t k, const int32_t* steps, int32_t V, int32_t L, int32_t* idx, double* score, int32_t* vel) {
+  const char* who = "pr_match_topk_seq_f64";
+  if (!ctx) return PR_EINVAL;
+  const bool plain = type == PR_TYPE_DELIGHT;
+  if (type != PR_TYPE_SC && type != PR_TYPE_M2DP && !plain) PR_FAIL(ctx, PR_EINVAL, "%s: unknown type %d", who, type);
+  if (!idx || !score || !vel || !steps) PR_FAIL(ctx, PR_EINVAL, "%s: a required pointer is NULL (steps, idx, score, vel)", who);
+  if (m < 0 || n < 0 || (m > 0 && !h1) || (n > 0 && !h2)) PR_FAIL(ctx, PR_EINVAL, "%s: bad signature buffers (m=%d, n=%d)", who, m, n);
+  if (k < 1 || k > pr::SEQ_MAX_K) PR_FAIL(ctx, PR_EINVAL, "%s: k=%d outside 1 .. %d", who, k, pr::SEQ_MAX_K);
+  if (mask_width < 0) PR_FAIL(ctx, PR_EINVAL, "%s: mask_width=%d is negative", who, mask_width);
+  if (int bad = pr::seq_steps_bad(steps, V, L))
+    PR_FAIL(ctx, PR_EINVAL, "%s: bad step table (V=%d, L=%d): %s", who, V, L,
+            bad == 1 ? "V outside 1 .. 16 or L outside 1 .. 32" : bad == 2 ? "steps[v][0] != 0" : "|steps[v][l]| > 64");
+  if (n == 0) {
+    for (size_t i = 0; i < (size_t)m * k; i++) { idx[i] = -1; score[i] = NAN; vel[i] = -1; }
+    return PR_OK;
+  }
+  if (!plain && n < 2) PR_FAIL(ctx, PR_EINVAL, "%s needs n >= 2 (N-1 standard deviation)", who);
+  if (m == 0) return PR_OK;
+  if (int rc = set_device(ctx)) return rc;
+  DevScope scope_(ctx);
+  Types T;
+  Desc& d = T.add(type, h1, h2);
+  if (int rc = T.prepare(ctx, m, n, plain ? DISTANCES : MOMENTS)) return rc;
+  DevBuf dsteps, didx, dsc, dvel;
+  PR_HIP(ctx, dsteps.alloc((size_t)V * L * 4));
+  PR_HIP(ctx, didx.alloc((size_t)m * k * 4));
+  PR_HIP(ctx, dsc.alloc((size_t)m * k * 8));
+  PR_HIP(ctx, dvel.alloc((size_t)m * k * 4));
+  PR_HIP(ctx, hipMemcpyAsync(dsteps.p, steps, (size_t)V * L * 4, hipMemcpyHostToDevice, ctx->stream));
+  if (int rc = pr_seq_select_dev(ctx, d.dp.as<float>(), plain ? nullptr : d.di.as<float>(), m, n, plain ? nullptr : d.mom.as<double>(),
+                                 dsteps.as<int32_t>(), V, L, 0, 0, mask_width, p_weight, k, didx.as<int32_t>(), dsc.as<double>(),
+                                 dvel.as<int32_t>(), nullptr))
+    return rc;
+  PR_HIP(ctx, hipMemcpyAsync(vel, dvel.p, (size_t)m * k * 4, hipMemcpyDeviceToHost, ctx->stream));
+  return download_topk(ctx, didx.as<int32_t>(), dsc.as<double>(), (size_t)m * k, idx, score);
+}
+
 // pr_match_align / pr_match_align_fused.  type: PR_TYPE_SC | PR_TYPE_M2DP | PR_TYPE_DELIGHT with h1 = a1, h2 = a2, or -1 = fused (a: SC,
 // b: M2DP).  Only the DB rows that idx references go to the device - at most m * k distinct ones, renumbered in ascending order - so the
 // cost does not grow with n; the device forms then run on that compacted shard.  var_out / dist_out: [m][k][S], S = 4 (fused) or 2.
@@ -2082,6 +2125,7 @@ void*& ctx_bow(pr_ctx* ctx) { return ctx->bow; }
 void*& ctx_eval(pr_ctx* ctx) { return ctx->eval; }
 void*& ctx_icp(pr_ctx* ctx) { return ctx->icp; }
 void*& ctx_pose(pr_ctx* ctx) { return ctx->pose; }
+void* ctx_seq_scratch(pr_ctx* ctx) { return ctx->seq_scratch; }
 int* ctx_bow_flag(pr_ctx* ctx) { return ctx->d_flags + 5; }
 int* ctx_bow_rows_flag(pr_ctx* ctx) { return ctx->d_flags + 6; }
 }  // namespace pr

@@ -635,6 +635,23 @@ class Matcher(_Base):
         False skips the resolution (the answer of the re-evaluated candidate list; the flags are simply dropped)."""
         return self._match((queries,), mask_width, p_weight, k, db_row0, q_row0, group, force_exchange, f16_fallback, exact_order, mark)
 
+    def match_sequence(self, queries: torch.Tensor, steps, mask_width: int = 0, p_weight: float = 2.0, k: int = 1, db_row0: int = 0,
+                       q_row0: int = 0, dense: bool = False):
+        """Sequence matching (pr_seq_select_dev): `queries` are consecutive keyframes of a drive; local_phase1() and then
+        the trajectory-summed selection over this matcher's own distance matrices.  steps: api.seq_steps(L, velocities), a NumPy table
+        or a CUDA i32 [V, L] tensor (uploaded once per call otherwise).  Returns (idx i32 [m, k] GLOBAL DB rows, score f64 [m, k],
+        vel i32 [m, k][, S f64 [m, n] with dense=True]) device tensors; evaluate() takes idx and score as they are.  One shard only:
+        the lags do not cross query shards and there is no sharded form."""
+        from . import api
+        if not (torch.is_tensor(steps) and steps.is_cuda):
+            steps = torch.from_numpy(api._check_steps(steps, "Matcher.match_sequence")).to(self.dev)
+        mom = self.local_phase1(queries)
+        d_p, d_i = self.distances()
+        self._enter()
+        out = api.seq_select_torch(d_p, d_i, None if self.plain else mom, steps, q_row0, db_row0, mask_width, p_weight, k, dense=dense, ctx=self.ctx)
+        self._leave()
+        return out
+
     def distances(self):
         """The last distance matrices (device, float32 [m, n_local])."""
         return self._bufs["d_p"], self._bufs.get("d_i")
