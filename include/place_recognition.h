@@ -1283,6 +1283,79 @@ int pr_mapplane_refine(pr_mapplane* mp, const double* xyz_q, const int64_t* offs
                        const double* T0, const int32_t* excl, int32_t max_iter, double max_corr, double tol_rmse, double tol_fitness,
                        int32_t min_inliers, const double* normals, const int32_t* ninfo, double* T_out, pr_icp_stats* stats);
 
+/* ---- the world map, its voxel index and its normals grown one keyframe at a time (mapgrow.hip) -----------------------
+ * pr_worldmap_fuse_dev is a full rebuild, and pr_maploc_index_dev and pr_mapplane_normals_dev run one lane per row of out_capacity: their
+ * cost follows the drive, not the keyframe.  With keep = 0 (first observation) and min_count = 1 the world rows are a subsequence of the
+ * map's points in map order, so a new keyframe's new voxels are new rows at the end, its points in known voxels only raise a count, the
+ * index only gains keys, and a normal changes only for the rows the index holds in the 27 voxels around a new row.  A pr_mapgrow over an
+ * existing pr_worldmap and the pr_maploc created over the same world buffer record takes in ONE map row a call and leaves THE REBUILD'S
+ * BYTES.  It BORROWS both handles (their buffers, the map's arrays, the localiser's table, cell and control words) and makes ONE
+ * allocation of its own at create; destroy it before them.  Every device call is stream-ordered on the context's stream, reads its counts
+ * and makes its decisions - the refusals included - on the device, allocates nothing, reads nothing back, and its launch geometry depends
+ * on the map's max_cloud_points only, so one captured call serves every keyframe.  fp64 without contraction; integer atomics and integer
+ * scans only; no workgroup waits for another; every probe is a bounded loop of at most T steps.
+ * Names: kcap, pcap and mcp are the keyframe_capacity, point_capacity and max_cloud_points of the map the world map was created over; ocap,
+ * cell and T are the localiser's; the handle's own device words are fused, rows_seen and the last range [a, b).
+ *
+ *   pr_mapgrow_create     refuses a world map and a localiser over different buffer records (xyz, row, state) or out_capacity, or of
+ *                         another context.  With nblk = ceil(mcp / 256) the parts of the allocation are, each rounded up to 16 bytes:
+ *                           64 (control words) | 4 mcp (slot_of) | 8 nblk (block counts) | staging of the host forms: 96 (pose row) | 16
+ *                           (row) | 32 (info) | 648 mcp (normals, 27 per point) | 108 mcp (ninfo) | 108 mcp (rows)
+ *                         pr_mapgrow_scratch_bytes(max_cloud_points) returns the sum (0 for mcp < 1 or > 2^26).  It zeroes its words.
+ *   pr_mapgrow_sync_dev   one small launch: fused = d_n[0] clamped into 0 .. kcap (NULL = the map's state), rows_seen = world.state[0]
+ *                         clamped into 0 .. ocap, a = b = rows_seen.  Issue it behind pr_worldmap_fuse_dev(keep 0, min_count 1, the
+ *                         localiser's cell) + pr_maploc_index_dev: from then on extends follow that fuse.
+ *   pr_mapgrow_extend_dev six launches.  r = d_row[0] - word 1 of pr_map_append_dev's info, "first row or -1", taken as
+ *                         pr_posegraph_add_dev takes d_query_row; n = the map's state[0] clamped into 0 .. kcap; R = world.state[0]
+ *                         clamped into 0 .. ocap.  d_poses [kcap][12] f64 device, NULL = the map's poses; d_info [4] i64 device.
+ *     r < 0: the call is off.  d_info = {0, R, 0, 0}; no other byte changes anywhere, the handle's words included.
+ *     Refusals, decided on the device and OR-ed; nothing changes and d_info = {0, R, 0, flags}: r != fused or r >= n gives
+ *     PR_MAPGROW_ORDER; R != rows_seen gives PR_MAPGROW_STALE (somebody fused without a sync); world.state[1] & PR_WORLDMAP_OVERFLOW
+ *     gives PR_MAPGROW_FULL.
+ *     Otherwise the points g in [offs[r], offs[r + 1]) clamped as the fuse at n = r + 1 clamps them (P = offs[r + 1] into 0 .. pcap,
+ *     offs[r] into 0 .. P; at most mcp points, which is all a stored cloud has) are taken.  World position and validity are steps 1 and 2
+ *     of pr_worldmap_fuse_dev's rule under pose row r of d_poses, the cell the localiser's - the SAME inlined code as the fuse.
+ *     A valid point whose key the index holds at row j does count[j] += 1.  The other valid points form new voxels by key; the
+ *     representative is the smallest g; in ascending representative g the new voxels receive the rows R, R + 1, ...  A row below ocap
+ *     is stored - xyz, inten, src = g, row = r, count = the voxel's points - and the index gains key -> row.  Voxels past ocap are not
+ *     stored and the index does not hold them (a lookup returns "no row"); PR_WORLDMAP_OVERFLOW is set.  The new keys enter the
+ *     localiser's table by a probe of at most T steps.  A key that finds no slot - only a call with more than T - R >= ocap new voxels
+ *     can fill the table - turns the call into a refusal with PR_WORLDMAP_TABLE: d_info = {0, R, 0, the call's flags}, no row is
+ *     stored, no count raised and no word changed; rebuild with a larger out_capacity.
+ *     Afterwards world.state[0] = R' = min(R + new voxels, ocap), state[1] |= the call's world-map flags (PR_WORLDMAP_*), words 2 and 3
+ *     stay 0; the localiser's rows-indexed count rises by the stored rows and its one-cloud target becomes {0, R'}, so
+ *     pr_maploc_nn_dev, pr_maploc_refine_dev, pr_mapplane_refine_dev and pr_maploc_count see the grown map; fused = r + 1, rows_seen =
+ *     R', [a, b) = [R, R').  d_info = {rows stored, R', valid points of the row, the call's world-map flags}.  A row that is empty or
+ *     dropped, or whose pose is not finite, advances fused and stores nothing.
+ *   pr_mapgrow_normals_dev   one launch, 27 mcp lanes.  For every row in [a, b): the normal and ninfo of each row the index holds for the 27
+ *                         keys around that row's voxel - the row itself included - are recomputed by pr_mapplane_normals_dev's rule, the
+ *                         SAME per-row device function.  No other entry of d_normals [ocap][3] / d_ninfo [ocap] is written.  Several
+ *                         lanes may recompute one row; they store equal bytes.  The refusals are pr_mapplane_normals_dev's.
+ *   The contract.  Let the world buffers, the index and the normal arrays hold a rebuild at n = r under poses P - fuse(P, n, cell, 1,
+ *   keep 0), then index, then normals(radius, ...).  After extend(P, r) and normals(radius, ...): the five world arrays hold the rebuild at
+ *   n = r + 1 byte for byte, also when the call overflows; so do state and the two normal arrays; the index agrees with a fresh
+ *   pr_maploc_index_dev as a map from keys to rows (the slot order may differ; a key past ocap may sit in the table without a row) - the
+ *   observable is pr_maploc_nn_dev and the two refines, bit for bit.
+ *   Out of scope: keep = 1 and min_count > 1 (they would move or insert rows in the middle of the arrays); more than one row a call;
+ *   re-extending under changed poses - after a relaxation the caller rebuilds and syncs.
+ *   pr_mapgrow_extend / _normals   the host forms: upload, run the device form, synchronise, read back.  poses [kcap][12] is a HOST array
+ *                         (NULL = the map's) of which row `row` is uploaded; normals [ocap][3] and ninfo [ocap] are HOST arrays holding
+ *                         the earlier normals, of which only the recomputed rows are overwritten.
+ *   pr_mapgrow_count      synchronising read of fused, rows_seen and the last extend's info[3] (diagnostics).
+ * PR_EINVAL (text: pr_last_error) before any device is touched for NULL handles and required pointers, handles of another context or over
+ * different records, and for everything pr_mapplane_normals_dev refuses. */
+typedef struct pr_mapgrow pr_mapgrow;
+enum { PR_MAPGROW_ORDER = 16, PR_MAPGROW_STALE = 32, PR_MAPGROW_FULL = 64 };   /* beside PR_WORLDMAP_OVERFLOW/SKIPPED/RANGE/TABLE = 1/2/4/8 */
+int pr_mapgrow_create(pr_ctx* ctx, pr_worldmap* wm, pr_maploc* ml, pr_mapgrow** out);
+void pr_mapgrow_destroy(pr_mapgrow* mg);
+int64_t pr_mapgrow_scratch_bytes(int32_t max_cloud_points);
+int pr_mapgrow_sync_dev(pr_mapgrow* mg, const int32_t* d_n);
+int pr_mapgrow_extend_dev(pr_mapgrow* mg, const double* d_poses, const int32_t* d_row, int64_t* d_info);
+int pr_mapgrow_normals_dev(pr_mapgrow* mg, double radius, int32_t min_nbrs, double max_ratio, double* d_normals, int32_t* d_ninfo);
+int pr_mapgrow_extend(pr_mapgrow* mg, const double* poses, int32_t row, int64_t* info);
+int pr_mapgrow_normals(pr_mapgrow* mg, double radius, int32_t min_nbrs, double max_ratio, double* normals, int32_t* ninfo);
+int pr_mapgrow_count(pr_mapgrow* mg, int32_t* fused, int64_t* rows, int32_t* flags);
+
 /* ---- the closure consistency gate in front of the pose-graph relaxation (gate.hip) -------------------------------------
  * pr_posegraph_relax_dev has no robust kernel: one wrong closure that passed verify pulls the whole graph.  What exposes such a closure is
  * that it disagrees with the other closures and with the odometry between them.  A pr_gate checks every ordered pair of logged closures

@@ -32,7 +32,8 @@ POSEGRAPH_OVERFLOW = 1                              # info[3] of a pr_posegraph 
 POSEGRAPH_MAX_K = 128                               # most slots of one pr_posegraph add
 WORLDMAP_OVERFLOW, WORLDMAP_SKIPPED, WORLDMAP_RANGE, WORLDMAP_TABLE = 1, 2, 4, 8   # flags of a pr_worldmap fuse (state[1], info[3])
 MAPLOC_SKIPPED, MAPLOC_RANGE, MAPLOC_DUPLICATE, MAPLOC_TABLE = 1, 2, 4, 8           # flags of a pr_maploc index (info[2])
-GATE_SRC_OVERFLOW, GATE_UNSETTLED = 1, 2            # flags of a pr_gate run (info[3])
+MAPGROW_ORDER, MAPGROW_STALE, MAPGROW_FULL = 16, 32, 64            # refusals of a pr_mapgrow extend (info[3]), beside the WORLDMAP_* bits
+GATE_SRC_OVERFLOW, GATE_UNSETTLED = 1, 2           # flags of a pr_gate run (info[3])
 SEQ_MAX_L, SEQ_MAX_V, SEQ_MAX_STEP, SEQ_MAX_K = 32, 16, 64, 32   # limits of a sequence-matching step table and call (PR_SEQ_*)
 SEQMATCH_MAX_K = 128                                # most slots of one pr_seqmatch push
 
@@ -279,6 +280,15 @@ SYMBOLS = {
     "pr_mapplane_refine_dev": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _dbl, _dbl, _dbl, _i32, _vp, _vp, _vp, _vp]),
     "pr_mapplane_normals": (C.c_int, [_vp, _dbl, _i32, _dbl, _vp, _vp]),
     "pr_mapplane_refine": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _dbl, _dbl, _dbl, _i32, _vp, _vp, _vp, _vp]),
+    "pr_mapgrow_create": (C.c_int, [_vp, _vp, _vp, C.POINTER(_vp)]),
+    "pr_mapgrow_destroy": (None, [_vp]),
+    "pr_mapgrow_scratch_bytes": (C.c_int64, [_i32]),
+    "pr_mapgrow_sync_dev": (C.c_int, [_vp, _vp]),
+    "pr_mapgrow_extend_dev": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "pr_mapgrow_normals_dev": (C.c_int, [_vp, _dbl, _i32, _dbl, _vp, _vp]),
+    "pr_mapgrow_extend": (C.c_int, [_vp, _vp, _i32, _vp]),
+    "pr_mapgrow_normals": (C.c_int, [_vp, _dbl, _i32, _dbl, _vp, _vp]),
+    "pr_mapgrow_count": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(C.c_int64), C.POINTER(_i32)]),
     "pr_gate_create": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, C.POINTER(_vp)]),
     "pr_gate_run_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pr_gate_run": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -2536,6 +2536,121 @@ class PlaneLocalizer:
             pass
 
 
+class MapGrower:
+    """pr_mapgrow: the world map, the localiser's voxel index and the world-map normals grown by ONE keyframe a call.
+    After a rebuild - WorldMap.fuse_torch(keep='first', min_count=1, cell=the localiser's) -> MapLocalizer.index_torch ->
+    PlaneLocalizer.normals_torch -> sync_torch, which rebuild_torch issues in that order - extend_torch(row) takes in map row `row` (word
+    1 of KeyframeMap.append's info) and normals_torch recomputes the normals around its new rows; both leave the rebuild's bytes at a cost
+    that follows the cloud, not the map.  Rebuild again when the poses change (after a relaxation).  It borrows the world map and the
+    localiser and owns one allocation; every device call is enqueued on the context's stream, decides on the device, reads nothing back
+    and can be captured.  Close it before them."""
+
+    def __init__(self, ctx: Context | None, wm, ml):
+        self.ctx = ctx or default_context()
+        self.h = None
+        if wm.ctx is not self.ctx or ml.ctx is not self.ctx:
+            raise ValueError("MapGrower: the grower, the world map and the localiser must share one context (one stream)")
+        if ml.wm is not wm:
+            raise ValueError("MapGrower: the localiser must have been created over this world map")
+        self.lib = self.ctx.lib
+        self.wm, self.ml = wm, ml
+        h = C.c_void_p()
+        self.ctx.check(self.lib.pr_mapgrow_create(self.ctx.h, wm.h, ml.h, C.byref(h)))
+        self.h = h
+
+    _t = MapLocalizer._t
+    _p = staticmethod(MapLocalizer._p)
+
+    def sync_torch(self, n=None):
+        """Device form (pr_mapgrow_sync_dev): from here on extends follow the fuse + index that lie in front on the stream.  n i32 [>= 1]
+        whose word 0 is the keyframe count that fuse took (None = the map's state)."""
+        import torch
+        if n is not None:
+            self._t("MapGrower.sync_torch", "n", n, torch.int32, numel_min=1)
+        self.ctx.check(self.lib.pr_mapgrow_sync_dev(self.h, self._p(n)))
+
+    def extend_torch(self, row, poses=None, info=None):
+        """Device form (pr_mapgrow_extend_dev): row i32 [>= 1] whose word 0 is the map row to take in or -1 (the call is off) - a view of
+        word 1 of an append's info; poses f64 [keyframe_capacity, 12] (None = the map's own).  Returns info (device i64 [4]) = rows
+        stored, rows after, valid points of the row, flags: WORLDMAP_* of the call, or MAPGROW_ORDER | STALE | FULL when it was refused
+        and nothing changed."""
+        import torch
+        who = "MapGrower.extend_torch"
+        self._t(who, "row", row, torch.int32, numel_min=1)
+        if poses is not None:
+            self._t(who, "poses", poses, torch.float64, (self.wm.km.keyframe_capacity, 12))
+        if info is None:
+            info = torch.empty(4, dtype=torch.int64, device=self.wm.state.device)
+        else:
+            self._t(who, "info", info, torch.int64, (4,))
+        p = self._p
+        self.ctx.check(self.lib.pr_mapgrow_extend_dev(self.h, p(poses), p(row), p(info)))
+        return info
+
+    def normals_torch(self, radius: float, min_nbrs: int, max_ratio: float, normals, ninfo):
+        """Device form (pr_mapgrow_normals_dev): recomputes, in place, the entries of normals f64 [out_capacity, 3] / ninfo i32
+        [out_capacity] (a PlaneLocalizer.normals_torch pair, kept up to date since the rebuild) around the rows the last extend stored."""
+        import torch
+        who = "MapGrower.normals_torch"
+        oc = self.wm.out_capacity
+        self._t(who, "normals", normals, torch.float64, (oc, 3))
+        self._t(who, "ninfo", ninfo, torch.int32, (oc,))
+        p = self._p
+        self.ctx.check(self.lib.pr_mapgrow_normals_dev(self.h, float(radius), int(min_nbrs), float(max_ratio), p(normals), p(ninfo)))
+        return normals, ninfo
+
+    def rebuild_torch(self, plane, poses=None, n=None, radius: float = 0.4, min_nbrs: int = 5, max_ratio: float = 0.1, out=None, infos=None):
+        """The rebuild, in the one order that is right: fuse(keep='first', min_count=1, the localiser's cell) -> index -> normals -> sync.
+        plane: the PlaneLocalizer over the same localiser; out: a (normals, ninfo) pair to write; infos: a (fuse info, index info) pair.
+        Returns (normals, ninfo, fuse info, index info)."""
+        if plane.ml is not self.ml:
+            raise ValueError("MapGrower.rebuild_torch: the plane localiser must lie over this grower's localiser")
+        finfo = self.wm.fuse_torch(poses, n, self.ml.cell, 1, "first", info=None if infos is None else infos[0])
+        iinfo = self.ml.index_torch(info=None if infos is None else infos[1])
+        out = plane.normals_torch(radius, min_nbrs, max_ratio, out=out)
+        self.sync_torch(n)
+        return out[0], out[1], finfo, iinfo
+
+    # ---- host forms (synchronise)
+    def extend(self, row: int, poses=None):
+        """Host form (pr_mapgrow_extend): row an int, poses a numpy array [keyframe_capacity, 12] or None.  Returns info [4] i64."""
+        po = None
+        if poses is not None:
+            po = np.ascontiguousarray(poses, np.float64)
+            if po.shape != (self.wm.km.keyframe_capacity, 12):
+                raise ValueError("MapGrower.extend: poses must be [keyframe_capacity, 12]")
+        info = np.zeros(4, np.int64)
+        self.ctx.check(self.lib.pr_mapgrow_extend(self.h, _ptr(po), int(row), _ptr(info)))
+        return info
+
+    def normals(self, radius: float, min_nbrs: int, max_ratio: float, normals, ninfo):
+        """Host form (pr_mapgrow_normals): normals f64 [out_capacity, 3] and ninfo i32 [out_capacity] are contiguous numpy arrays holding
+        the earlier normals; the recomputed rows are overwritten in place.  Returns the pair."""
+        oc = self.wm.out_capacity
+        if not (isinstance(normals, np.ndarray) and normals.dtype == np.float64 and normals.flags.c_contiguous and normals.shape == (oc, 3)
+                and isinstance(ninfo, np.ndarray) and ninfo.dtype == np.int32 and ninfo.flags.c_contiguous and ninfo.shape == (oc,)):
+            raise ValueError("MapGrower.normals: normals must be a contiguous f64 [out_capacity, 3] and ninfo a contiguous i32 [out_capacity] array")
+        self.ctx.check(self.lib.pr_mapgrow_normals(self.h, float(radius), int(min_nbrs), float(max_ratio), _ptr(normals), _ptr(ninfo)))
+        return normals, ninfo
+
+    def count(self):
+        """(keyframes fused, world rows seen, the last extend's flags); synchronises (pr_mapgrow_count)."""
+        f, r, fl = C.c_int32(), C.c_int64(), C.c_int32()
+        self.ctx.check(self.lib.pr_mapgrow_count(self.h, C.byref(f), C.byref(r), C.byref(fl)))
+        return int(f.value), int(r.value), int(fl.value)
+
+    def close(self):
+        if getattr(self, "h", None) and getattr(self.ctx, "h", None):
+            self.lib.pr_mapgrow_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def split_points_by_pose(pose_ids, point_ids) -> np.ndarray:
     """The reference's cursor rule (utils/pts_preprocess.h:196-200) as per-pose pushes: at pose p the cursor takes points while
     id <= pose id, so an out-of-order id makes it wait.  Returns cuts int64 [len(pose_ids) + 1]: pose p is pushed the points

@@ -534,5 +534,38 @@ void launch_mapplane_sums(hipStream_t st, const IcpClouds& A, const double* T, c
                           int nchunks, double mc2, const double* normals, const int* ninfo, double* part);
 void launch_mapplane_update(hipStream_t st, const IcpClouds& A, const double* part, int nchunks, const IcpParams& P, int final_pass, double* T,
                             IcpStats* stats, int* done, double* prev);
+}  // namespace pr
+struct pr_worldmap;
+namespace pr {
+// worldmap.cpp: what a pr_mapgrow borrows of its world map (the view's buffers, map arrays and capacities; the map's max_cloud_points;
+// its context)
+const WorldMapView* worldmap_view(pr_worldmap* wm);
+int worldmap_max_cloud(pr_worldmap* wm);
+pr_ctx* worldmap_ctx(pr_worldmap* wm);
+
+// mapgrow.hip — the world map, its voxel index and its normals grown by ONE keyframe a call.  MapGrowView: the world
+// map's view, the localiser's table and control words, and the scratch of a pr_mapgrow (mapgrow.cpp), ONE allocation:
+//   ctl [16] i32 (MAPGROW_* words below) | slot_of [mcp] i32 (the point's slot in the localiser's table, -1: not valid) | blk [2][nblk] i32
+//   (per 256 points: representatives of new voxels, valid points; after the scan the first half holds the exclusive prefix) | the staging
+//   of the host forms.  mcp = the map's max_cloud_points, nblk = ceil(mcp / 256).
+constexpr int MAPGROW_ORDER = 16, MAPGROW_STALE = 32, MAPGROW_FULL = 64;                              // = PR_MAPGROW_*
+constexpr int MAPGROW_MAX_CLOUD = 1 << 26;
+// ctl words: the handle's four (fused, rows_seen, the last range [a, b)), the call's world-map flags (zero between calls), what the scan
+// hands to finish (new voxels, valid points) and the last call's info[3]
+constexpr int MG_FUSED = 0, MG_SEEN = 1, MG_A = 2, MG_B = 3, MG_FLAGS = 4, MG_NEW = 5, MG_VALID = 6, MG_LAST = 7;
+struct MapGrowView {
+  WorldMapView w;                                                 // the six world buffers, the map's arrays, kcap, pcap, ocap
+  unsigned long long* table; int* ml_ctl; int64_t* offs2;         // the localiser's
+  double cell;
+  int log2T, mcp, nblk;
+  int* ctl; int* slot_of; int* blk;
+};
+void launch_mapgrow_sync(hipStream_t st, const MapGrowView& v, const int* n);
+// pose_is_row: poses holds the 12 entries of the call's pose row alone (the host form's staging) instead of [keyframe_capacity][12]
+void launch_mapgrow_extend(hipStream_t st, const MapGrowView& v, const double* poses, int pose_is_row, const int* row, int64_t* info);
+// one lane per (row of the last range, one of the 27 keys around it).  out_rows == NULL: the row a lane recomputes is written at its own
+// index of normals / ninfo.  Otherwise lane L writes at L and leaves the row (or -1) in out_rows[L]: the compact form of the host call.
+void launch_mapgrow_normals(hipStream_t st, const MapGrowView& v, double r2, int min_nbrs, double max_ratio, double* normals, int* ninfo,
+                            int* out_rows);
 
 }  // namespace pr

@@ -29,6 +29,7 @@ struct pr_worldmap {
   double* stage_poses = nullptr;      // [keyframe_capacity][12]
   int32_t* stage_n = nullptr;         // [4]
   int64_t* stage_info = nullptr;      // [4]
+  int32_t max_cloud = 0;              // the map's max_cloud_points (what a pr_mapgrow sizes its launches by)
 };
 
 namespace {
@@ -61,6 +62,12 @@ Layout layout_of(int32_t kcap, int64_t pcap) {
 
 }  // namespace
 
+namespace pr {
+const WorldMapView* worldmap_view(pr_worldmap* wm) { return wm ? &wm->v : nullptr; }
+int worldmap_max_cloud(pr_worldmap* wm) { return wm ? wm->max_cloud : 0; }
+pr_ctx* worldmap_ctx(pr_worldmap* wm) { return wm ? wm->ctx : nullptr; }
+}  // namespace pr
+
 extern "C" {
 
 int64_t pr_worldmap_scratch_bytes(int32_t keyframe_capacity, int64_t point_capacity) {
@@ -86,6 +93,7 @@ int pr_worldmap_create(pr_ctx* ctx, pr_map* map, const pr_worldmap_buffers* buff
   pr_worldmap* wm = new (std::nothrow) pr_worldmap;
   if (!wm) return fail(ctx, PR_ENOMEM, "out of host memory");
   wm->ctx = ctx;
+  wm->max_cloud = m.max_cloud;
   pr::WorldMapView& v = wm->v;
   memset(&v, 0, sizeof v);
   v.xyz = buffers->xyz; v.inten = buffers->inten; v.src = buffers->src; v.row = buffers->row; v.count = buffers->count; v.state = buffers->state;

@@ -35,14 +35,14 @@
 #include <stdint.h>
 
 #include "kernels.hpp"
+#include "worldmap_common.hpp"
 
 namespace pr {
 namespace {
 
-typedef unsigned long long u64;
-
-constexpr u64 EMPTY = ~(u64)0;
-constexpr double CELL_LIM = 1048576.0;                           // 2^20
+// world_of, key_of, home_slot: shared with mapgrow.hip.  world_of is step 1, w[a] = (q[a] * d0 + q[4 + a] * d1) + q[8 + a] * d2 with
+// d = p - t, and the finiteness half of step 2; key_of is the range half and the packing.
+using namespace worldmap_dev;
 
 struct Head { int n; int64_t P; };
 
@@ -62,21 +62,6 @@ __device__ __forceinline__ int row_of(const int64_t* __restrict__ offs, int n, i
     if (offs[mid] <= g) lo = mid; else hi = mid;
   }
   return lo;
-}
-
-// step 1 and the finiteness half of step 2
-__device__ __forceinline__ bool world_of(const double* __restrict__ pose, const double* __restrict__ p, double w[3]) {
-  double q[12];
-  bool fin = true;
-#pragma unroll
-  for (int i = 0; i < 12; i++) { q[i] = pose[i]; fin = fin && __builtin_isfinite(q[i]); }
-  const double d0 = p[0] - q[3], d1 = p[1] - q[7], d2 = p[2] - q[11];
-#pragma unroll
-  for (int a = 0; a < 3; a++) {
-    w[a] = (q[a] * d0 + q[4 + a] * d1) + q[8 + a] * d2;
-    fin = fin && __builtin_isfinite(w[a]);
-  }
-  return fin;
 }
 
 __device__ __forceinline__ int64_t rep_of(u64 word, int keep) { return (int64_t)(keep ? ~word : word); }
@@ -104,14 +89,12 @@ __global__ __launch_bounds__(256) void worldmap_insert_kernel(WorldMapView v, co
     if (!world_of(poses + 12 * (size_t)r, v.m_xyz + 3 * (size_t)g, w)) {
       flags = WORLDMAP_SKIPPED;
     } else {
-      const double c0 = floor(w[0] / cell), c1 = floor(w[1] / cell), c2 = floor(w[2] / cell);
-      const bool in = c0 >= -CELL_LIM && c0 < CELL_LIM && c1 >= -CELL_LIM && c1 < CELL_LIM && c2 >= -CELL_LIM && c2 < CELL_LIM;
-      if (!in) {
+      u64 key = 0;
+      if (!key_of(w, cell, &key)) {
         flags = WORLDMAP_RANGE;
       } else {
-        const u64 key = ((u64)((int64_t)c0 + 1048576) << 42) | ((u64)((int64_t)c1 + 1048576) << 21) | (u64)((int64_t)c2 + 1048576);
         const u64 T = (u64)1 << v.log2T;
-        u64 at = (key * 0x9E3779B97F4A7C15ull) >> (64 - v.log2T);
+        u64 at = home_slot(key, v.log2T);
         for (u64 step = 0; step < T; step++, at = (at + 1) & (T - 1)) {          // at most T steps: no input makes a lane spin
           const u64 prev = atomicCAS(&v.slots[2 * at], EMPTY, key);
           if (prev == EMPTY || prev == key) { slot = (int)at; break; }
