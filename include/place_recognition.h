@@ -1510,6 +1510,114 @@ size_t pr_seqmatch_scratch_bytes(int32_t capacity, int32_t channels, int32_t V, 
 void pr_seqmatch_destroy(pr_seqmatch* s);
 const char* pr_host_last_error(void);
 
+/* ---- registration information: covariance, weak directions, edge weights (reginfo.hip; no reference counterpart) ------
+ * A registration result is a pose and two scalars, fitness and rmse; how well the geometry constrains that pose is not in them.  A
+ * pr_reginfo reports it: the 6 x 6 normal matrix H of the metric at the pose T that is to be judged, Sigma = H^-1, the spectra of the
+ * marginal covariances of rotation and translation with their weakest directions, a graded weakness test and a per-slot (w_rot, w_trans)
+ * that pr_posegraphw_add_dev takes from device memory.  It runs BEHIND a correspondence pass the caller has already made at T:
+ * the CSR triple (d_out_offs [c + 1], d_nn_idx, d_nn_d2) that pr_icp_nn_radius_dev, pr_icp_nn_dev or pr_maploc_nn_dev wrote.  Every
+ * device call is stream-ordered on the context's stream, reads nothing back, allocates nothing and can be captured: two launches whose
+ * grids depend on the create sizes and c only.  fp64 without contraction; no floating-point atomics; no workgroup waits for another.
+ *
+ *   pr_reginfo_create     ONE allocation; no later call allocates.  With ld = max(max_src_pts, 1), nchunks = ceil(ld / 256) and pc =
+ *                         pair_capacity the parts are, each rounded up to 16 bytes:
+ *                           200 pc nchunks (chunk partials [pc][nchunks][25] f64) | staging of the host forms: 24 pc ld (xyz_q) |
+ *                           8 (pc + 1) (offs_q) | 4 pc (pair_src) | 96 pc (T) | pc (accepted) | 8 (pc + 1) (out_offs) | 4 pc ld (nn_idx)
+ *                           | 8 pc ld (nn_d2) | 24 pc ld (world_xyz) | 24 pc ld (normals) | 4 pc ld (ninfo) | 288 pc (H) | 288 pc (cov)
+ *                           | 128 pc (spec) | 16 pc (w) | 16 pc (stat) | pc (ok)
+ *                         pr_reginfo_scratch_bytes(pair_capacity, max_src_pts) returns the sum (0 for sizes create refuses:
+ *                         pair_capacity outside 1 .. 65535, max_src_pts outside 0 .. 2^26).  pr_reginfo_destroy frees the handle.
+ *   pr_reginfo_point_dev  the point metric e = p' - q; it needs no target cloud.
+ *   pr_reginfo_plane_dev  the plane metric r = n . (p' - q); the same arguments plus d_world_xyz [out_capacity][3], out_capacity and the
+ *                         d_normals [out_capacity][3] f64 / d_ninfo [out_capacity] i32 that pr_mapplane_normals_dev wrote.
+ *   pr_reginfo_point / _plane   the host forms: upload, run the device form, synchronise, read back.  They stage through the handle's
+ *                         allocation, so Nq <= pair_capacity, offs_q[Nq] <= pair_capacity x ld, out_offs[c] <= pair_capacity x ld and
+ *                         out_capacity <= pair_capacity x ld are required, and offs_q and out_offs ascend from a value >= 0.
+ *
+ * The rule (restated in fp64 in tests/reginfo_np.py).
+ *   Points read.  Slot p with src = d_pair_src[p] reads ns = min(out_offs[p + 1] - out_offs[p], offs_q[src + 1] - offs_q[src],
+ *     max_src_pts) points, never less than 0: source row offs_q[src] + i with the correspondence at out_offs[p] + i.
+ *   Inliers.  Point i is an inlier iff nn_idx >= 0 and nn_d2 < fl(max_corr^2) - and, for the plane metric, nn_idx < out_capacity, which
+ *     is checked before an address is formed.  For an inlier, with T = d_T[p] = [R | t]: p' = T s in pr_icp_pairs_dev's association,
+ *     p'_a = ((R_a0 x + R_a1 y) + R_a2 z) + t_a; u = p' - t, the lever arm about the sensor position (no world-sized coordinate enters a
+ *     product).
+ *   Point sums (11): the count n, sum d2 (the pass's nn_d2), sum u_a (3) and sum u_a u_b (6: 00 01 02 11 12 22).  With e = p' - q and
+ *     J = [-[u]x | I] in the order (w0, w1, w2, v0, v1, v2) the finish assembles H = sum J^T J from them: H_ww = (tr S) I - S with S =
+ *     sum u u^T - a diagonal entry is the sum of the OTHER two diagonal sums, H_00 = S_11 + S_22, H_11 = S_00 + S_22, H_22 = S_00 + S_11,
+ *     an off-diagonal entry -S_ab -; H_wv = [sum u]x (H_vw its transpose); H_vv = n I.  SSE = sum d2, n_used = n, dof = 3 n - 6.
+ *   Plane sums (25): the inliers n_inl, sum d2, the plane correspondents n_pl (inliers with ninfo[j] > 0), sum r^2 and the 21 entries
+ *     of sum J J^T (upper triangle, row-major), with q = world_xyz[j], n = normals[j], e = p' - q, r = (n_0 e_0 + n_1 e_1) + n_2 e_2
+ *     and J = [u x n, n] exactly as pr_mapplane_refine_dev forms them.  H = sum J J^T, SSE = sum r^2, n_used = n_pl, dof = n_pl - 6.
+ *   Reduction.  The project's fixed tree: a chunk is 256 source points; within a wave a 64-lane shuffle tree (v += the value of lane + d for d = 32,
+ *     16, .. 1), then the four waves in order ((w0 + w1) + w2) + w3; the chunk results go to the handle's partials and are added from
+ *     0.0 in chunk index order.
+ *   Finish, per slot, in this order; the first rule that applies ends it, and what later steps would have produced is zero:
+ *     1. PR_REGINFO_OFF when pair_src[p] is outside 0 .. Nq - 1, when d_accepted != NULL and d_accepted[p] == 0, or when the slot's
+ *        span out_offs[p + 1] - out_offs[p] is <= 0 (the pass switched it off, or its cloud is empty).  stat = {0, 0, 0, OFF}.
+ *     2. PR_REGINFO_NONFINITE when one of the 12 entries of T or one of the sums is not finite.  stat carries n_inl, n_used and dof
+ *        (counts are always finite); H and SSE are zero.
+ *     3. H and SSE are written.  PR_REGINFO_TOO_FEW when n_used < min_inliers or dof <= 0.
+ *     4. L D L^T of H without pivoting in pr_mapplane_refine_dev's order: d_k = H_kk - sum_m<k (L_km d_m) L_km, L_ik = (H_ik - sum_m<k
+ *        (L_im d_m) L_km) / d_k, every sum subtracted term by term with m ascending.  PR_REGINFO_SINGULAR when a d_k is not finite or
+ *        not d_k > 1e-12 H_kk (the original diagonal entry), or when an entry of Sigma below is not finite.
+ *     5. Sigma = H^-1 by six solves; column j from the unit vector e_j: y_i = (e_j)_i - sum_m<i L_im y_m (m ascending), z_i = y_i / d_i,
+ *        x_i = z_i - sum_m>i L_mi x_m for i = 5 .. 0 (m ascending); Sigma_ij = x_i.  cov holds Sigma as computed, row-major.
+ *     6. The marginal covariances are the blocks Sigma_ww (rows and columns 0 .. 2) and Sigma_vv (3 .. 5): they are the inverses of the
+ *        marginal informations, so no Schur complement is formed.  Each block's upper triangle, mirrored, is decomposed by
+ *        pr_mapplane_normals_dev's cyclic Jacobi (8 sweeps, pivots (0,1), (0,2), (1,2), V = I at the start, the same rotation and the
+ *        same stable ascending sort by three compare-exchanges): cr0 <= cr1 <= cr2 and ct0 <= ct1 <= ct2.  The weakest directions dir_r
+ *        and dir_t are the eigenvectors (columns of V) of cr2 and ct2, every component divided by sqrt((e0 e0 + e1 e1) + e2 e2), the sign
+ *        chosen so that the component of largest magnitude is positive (the lowest index wins a tie).
+ *     7. PR_REGINFO_WEAK_ROT iff NOT cr0 >= min_ratio cr2; PR_REGINFO_WEAK_TRANS iff NOT ct0 >= min_ratio ct2.
+ *     8. s2 = max(SSE / dof, sigma_min^2) (q > sigma_min^2 ? q : sigma_min^2).  w_rot = x < w_max ? x : w_max with x = 1 / (s2 cr2);
+ *        w_trans the same with ct2.  Both are exactly 0.0 when any flag is set.  The weights are in the units of the pose graph's
+ *        residual (rad^-2 and length^-2): with u about the sensor position a perturbation Z' = [Exp(w) R | t + v] moves the residual of
+ *        pr_posegraph_relax_dev by -R^T w and -R^T v at first order, a rotation of each block, so a scalar per block is frame-correct;
+ *        the largest marginal eigenvalue is the conservative scalar.
+ *   Outputs (the caller's arrays; every entry of rows < c is written): d_H [c][36] and d_cov [c][36] row-major; d_spec [c][16] = {cr0,
+ *     cr1, cr2, ct0, ct1, ct2, dir_r (3), dir_t (3), SSE, s2, 0, 0}; d_w [c][2] = {w_rot, w_trans}; d_stat [c][4] i32 = {n_inl, n_used,
+ *     dof, flags}; d_ok [c] u8 = (flags == 0).
+ * PR_EINVAL (text: pr_last_error) before any device is touched for a NULL handle or required pointer, c outside 0 .. pair_capacity,
+ * Nq < 0, max_corr or sigma_min not positive and finite, min_ratio outside [0, 1], w_max not positive or NaN (+Inf is allowed),
+ * min_inliers < 3 for the point metric and < 6 for the plane metric, out_capacity outside 1 .. 2^29 (plane).  c = 0 is valid. */
+typedef struct pr_reginfo pr_reginfo;
+enum { PR_REGINFO_OFF = 1, PR_REGINFO_NONFINITE = 2, PR_REGINFO_TOO_FEW = 4, PR_REGINFO_SINGULAR = 8, PR_REGINFO_WEAK_ROT = 16,
+       PR_REGINFO_WEAK_TRANS = 32 };
+int pr_reginfo_create(pr_ctx* ctx, int32_t pair_capacity, int32_t max_src_pts, pr_reginfo** out);
+void pr_reginfo_destroy(pr_reginfo* ri);
+int64_t pr_reginfo_scratch_bytes(int32_t pair_capacity, int32_t max_src_pts);
+int pr_reginfo_point_dev(pr_reginfo* ri, const double* d_xyz_q, const int64_t* d_offs_q, int32_t Nq, const int32_t* d_pair_src, int32_t c,
+                         const double* d_T, const uint8_t* d_accepted, const int64_t* d_out_offs, const int32_t* d_nn_idx, const double* d_nn_d2,
+                         double max_corr, int32_t min_inliers, double min_ratio, double sigma_min, double w_max, double* d_H, double* d_cov,
+                         double* d_spec, double* d_w, int32_t* d_stat, uint8_t* d_ok);
+int pr_reginfo_plane_dev(pr_reginfo* ri, const double* d_xyz_q, const int64_t* d_offs_q, int32_t Nq, const int32_t* d_pair_src, int32_t c,
+                         const double* d_T, const uint8_t* d_accepted, const int64_t* d_out_offs, const int32_t* d_nn_idx, const double* d_nn_d2,
+                         const double* d_world_xyz, int64_t out_capacity, const double* d_normals, const int32_t* d_ninfo, double max_corr,
+                         int32_t min_inliers, double min_ratio, double sigma_min, double w_max, double* d_H, double* d_cov, double* d_spec,
+                         double* d_w, int32_t* d_stat, uint8_t* d_ok);
+int pr_reginfo_point(pr_reginfo* ri, const double* xyz_q, const int64_t* offs_q, int32_t Nq, const int32_t* pair_src, int32_t c, const double* T,
+                     const uint8_t* accepted, const int64_t* out_offs, const int32_t* nn_idx, const double* nn_d2, double max_corr,
+                     int32_t min_inliers, double min_ratio, double sigma_min, double w_max, double* H, double* cov, double* spec, double* w,
+                     int32_t* stat, uint8_t* ok);
+int pr_reginfo_plane(pr_reginfo* ri, const double* xyz_q, const int64_t* offs_q, int32_t Nq, const int32_t* pair_src, int32_t c, const double* T,
+                     const uint8_t* accepted, const int64_t* out_offs, const int32_t* nn_idx, const double* nn_d2, const double* world_xyz,
+                     int64_t out_capacity, const double* normals, const int32_t* ninfo, double max_corr, int32_t min_inliers, double min_ratio,
+                     double sigma_min, double w_max, double* H, double* cov, double* spec, double* w, int32_t* stat, uint8_t* ok);
+
+/* The pose-graph log with weights from the device (posegraph.hip): two more calls on a pr_posegraph, named
+ * pr_posegraphw_* as pr_onlineset_* stands beside pr_online_* - the pr_posegraph_* family above is closed.
+ *   pr_posegraphw_add_dev   pr_posegraph_add_dev's rule slot for slot - the same launch geometry, overflow rule, info, switch-off
+ *                         by a negative query_row and clamp of a scribbled count - with (w_rot, w_trans) = d_w[p] ([k][2] f64 in DEVICE
+ *                         memory: pr_reginfo's d_w) and ONE more condition for logging slot p: both of its weights are finite and >= 0.
+ *                         With every d_w[p] = (w_rot, w_trans) it leaves the bytes pr_posegraph_add_dev leaves.
+ *   pr_posegraphw_add       the host form: host arrays, query_row by value, w [k][2] host; uploads, runs the device path,
+ *                         synchronises.
+ * PR_EINVAL before any device is touched for a NULL handle or pointer and k outside 1 .. 128. */
+int pr_posegraphw_add_dev(pr_posegraph* g, const int32_t* d_idx, const double* d_T, const uint8_t* d_accepted, const int32_t* d_query_row,
+                                  int32_t k, const double* d_w, int32_t* d_info);
+int pr_posegraphw_add(pr_posegraph* g, const int32_t* idx, const double* T, const uint8_t* accepted, int32_t query_row, int32_t k,
+                              const double* w, int32_t* info);
+
 #ifdef __cplusplus
 }
 #endif

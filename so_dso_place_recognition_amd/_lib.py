@@ -36,6 +36,7 @@ MAPGROW_ORDER, MAPGROW_STALE, MAPGROW_FULL = 16, 32, 64            # refusals of
 GATE_SRC_OVERFLOW, GATE_UNSETTLED = 1, 2           # flags of a pr_gate run (info[3])
 SEQ_MAX_L, SEQ_MAX_V, SEQ_MAX_STEP, SEQ_MAX_K = 32, 16, 64, 32   # limits of a sequence-matching step table and call (PR_SEQ_*)
 SEQMATCH_MAX_K = 128                                # most slots of one pr_seqmatch push
+REGINFO_OFF, REGINFO_NONFINITE, REGINFO_TOO_FEW, REGINFO_SINGULAR, REGINFO_WEAK_ROT, REGINFO_WEAK_TRANS = 1, 2, 4, 8, 16, 32   # stat[3] of a pr_reginfo call
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PR_AMD_LIB") or os.path.join(_HERE, "libpr_amd.so")   # PR_AMD_LIB: experiment builds only
@@ -255,6 +256,8 @@ SYMBOLS = {
     "pr_posegraph_count": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32)]),
     "pr_posegraph_add_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _dbl, _dbl, _vp]),
     "pr_posegraph_add": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _dbl, _dbl, _vp]),
+    "pr_posegraphw_add_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp]),
+    "pr_posegraphw_add": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp]),
     "pr_posegraph_relax_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "pr_worldmap_create": (C.c_int, [_vp, _vp, _vp, C.c_int64, C.POINTER(_vp)]),
     "pr_worldmap_destroy": (None, [_vp]),
@@ -280,6 +283,15 @@ SYMBOLS = {
     "pr_mapplane_refine_dev": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _dbl, _dbl, _dbl, _i32, _vp, _vp, _vp, _vp]),
     "pr_mapplane_normals": (C.c_int, [_vp, _dbl, _i32, _dbl, _vp, _vp]),
     "pr_mapplane_refine": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _dbl, _dbl, _dbl, _i32, _vp, _vp, _vp, _vp]),
+    "pr_reginfo_create": (C.c_int, [_vp, _i32, _i32, C.POINTER(_vp)]),
+    "pr_reginfo_destroy": (None, [_vp]),
+    "pr_reginfo_scratch_bytes": (C.c_int64, [_i32, _i32]),
+    "pr_reginfo_point_dev": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _dbl, _i32, _dbl, _dbl, _dbl, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pr_reginfo_plane_dev": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, _vp, _vp, _dbl, _i32, _dbl, _dbl, _dbl,
+                                       _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pr_reginfo_point": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _dbl, _i32, _dbl, _dbl, _dbl, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pr_reginfo_plane": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, _vp, _vp, _dbl, _i32, _dbl, _dbl, _dbl,
+                                   _vp, _vp, _vp, _vp, _vp, _vp]),
     "pr_mapgrow_create": (C.c_int, [_vp, _vp, _vp, C.POINTER(_vp)]),
     "pr_mapgrow_destroy": (None, [_vp]),
     "pr_mapgrow_scratch_bytes": (C.c_int64, [_i32]),

@@ -1811,6 +1811,40 @@ class PoseGraph:
         self.ctx.check(self.lib.pr_posegraph_add(self.h, _ptr(i), _ptr(t), _ptr(a), int(query_row), k, float(w_rot), float(w_trans), _ptr(info)))
         return info
 
+    def add_weighted_torch(self, idx, T, accepted, query_row, w, info=None):
+        """Device form (pr_posegraphw_add_dev): add_torch with per-slot weights w f64 [k, 2] = (w_rot, w_trans) in device memory -
+        RegistrationInfo's .w.  A slot is logged under add_torch's conditions and only if both of its weights are finite and >= 0.
+        Returns info (device i32 [4]); nothing synchronises, nothing is allocated when info= is given."""
+        import torch
+        who = "PoseGraph.add_weighted_torch"
+        k = idx.numel()
+        self._dev(idx, torch.int32, k, who, "idx must be a contiguous CUDA tensor i32 [k]")
+        self._dev(T, torch.float64, 12 * k, who, "T must be a contiguous CUDA tensor f64 [k, 3, 4]")
+        self._dev(accepted, torch.bool if accepted.dtype == torch.bool else torch.uint8, k, who,
+                  "accepted must be a contiguous CUDA tensor bool or u8 [k]")
+        self._dev(query_row, torch.int32, 1, who, "query_row must be a CUDA tensor i32 [>= 1]", exact=False)
+        self._dev(w, torch.float64, 2 * k, who, "w must be a contiguous CUDA tensor f64 [k, 2]")
+        if info is None:
+            info = torch.empty(4, dtype=torch.int32, device=idx.device)
+        else:
+            self._dev(info, torch.int32, 4, who, "info must be a CUDA tensor i32 [4]")
+        p = lambda t: C.c_void_p(t.data_ptr())
+        self.ctx.check(self.lib.pr_posegraphw_add_dev(self.h, p(idx), p(T), p(accepted), p(query_row), k, p(w), p(info)))
+        return info
+
+    def add_weighted(self, idx, T, accepted, query_row: int, w):
+        """Host form (pr_posegraphw_add; synchronises): numpy arrays of the same meaning, w [k, 2].  Returns info int32 [4]."""
+        i = np.ascontiguousarray(idx, np.int32).reshape(-1)
+        k = len(i)
+        t = np.ascontiguousarray(T, np.float64).reshape(-1)
+        a = np.ascontiguousarray(accepted, np.uint8).reshape(-1)
+        ww = np.ascontiguousarray(w, np.float64).reshape(-1)
+        if len(t) != 12 * k or len(a) != k or len(ww) != 2 * k:
+            raise ValueError("PoseGraph.add_weighted: idx [k], T [k, 3, 4], accepted [k], w [k, 2]")
+        info = np.empty(4, np.int32)
+        self.ctx.check(self.lib.pr_posegraphw_add(self.h, _ptr(i), _ptr(t), _ptr(a), int(query_row), k, _ptr(ww), _ptr(info)))
+        return info
+
     def relax_torch(self, poses, n, outer: int = 5, inner: int = 64, lam: float = 1e-9, w_odo_rot: float = 1.0, w_odo_trans: float = 1.0,
                     out=None, report=None):
         """Device form (pr_posegraph_relax_dev): poses f64 [node_capacity, 12] (world to camera), n i32 [>= 1] whose word 0 is the node
@@ -2536,8 +2570,254 @@ class PlaneLocalizer:
             pass
 
 
+class RegInfo(NamedTuple):
+    """What a RegistrationInfo call returns, row p = slot p: H f64 [c, 6, 6] the normal matrix in the order (w0, w1, w2, v0, v1, v2), cov f64
+    [c, 6, 6] its inverse, spec f64 [c, 16] = cr0 <= cr1 <= cr2, ct0 <= ct1 <= ct2 (the marginal covariance spectra), dir_r, dir_t (the
+    weakest directions), SSE, s2, 0, 0; w f64 [c, 2] = (w_rot, w_trans), exactly 0 where a flag is set; stat i32 [c, 4] = n_inl, n_used,
+    dof, flags (_lib.REGINFO_*); ok bool [c] = no flag."""
+    H: object
+    cov: object
+    spec: object
+    w: object
+    stat: object
+    ok: object
+
+
+class RegistrationInfo:
+    """pr_reginfo: how well the geometry constrains a registered pose.  Behind a correspondence pass at the pose T that is
+    to be judged - icp_nn_radius / icp_nn (point metric) or MapLocalizer.nn_torch (plane metric) - it gives the normal matrix, its
+    inverse, the marginal spectra of rotation and translation with their weakest directions, the flags (too few, singular, weak rotation,
+    weak translation) and a per-slot (w_rot, w_trans) for PoseGraph.add_weighted_torch.  One allocation at create; every *_torch call is
+    enqueued on the context's stream, reads nothing back and can be captured (out= keeps the result's addresses fixed).  pairs_torch and
+    maploc_torch run the pass themselves into work tensors the first call for a given c allocates - make that call before a capture."""
+
+    def __init__(self, ctx: Context | None, pair_capacity: int, max_src_pts: int):
+        self.ctx = ctx or default_context()
+        self.lib = self.ctx.lib
+        self.pair_capacity, self.max_src_pts = int(pair_capacity), int(max_src_pts)
+        self.h = None
+        self._work = {}
+        h = C.c_void_p()
+        self.ctx.check(self.lib.pr_reginfo_create(self.ctx.h, self.pair_capacity, self.max_src_pts, C.byref(h)))
+        self.h = h
+
+    # ---- checks made before the library is called
+    def _t(self, who, name, t, dtype, shape=None, numel_min=None):
+        if (not t.is_cuda) or t.device.index != self.ctx.device or t.dtype != dtype or not t.is_contiguous():
+            raise ValueError(f"{who}: {name} must be a contiguous CUDA tensor {dtype} on the context's device")
+        if shape is not None and tuple(t.shape) != tuple(shape):
+            raise ValueError(f"{who}: {name} must be {list(shape)}")
+        if numel_min is not None and t.numel() < numel_min:
+            raise ValueError(f"{who}: {name} must have at least {numel_min} elements")
+        return t
+
+    @staticmethod
+    def _p(t):
+        return None if t is None else C.c_void_p(t.data_ptr())
+
+    def _args(self, who, xyz_q, offs_q, pair_src, T, accepted, nn):
+        import torch
+        self._t(who, "xyz_q", xyz_q, torch.float64)
+        self._t(who, "offs_q", offs_q, torch.int64, numel_min=1)
+        self._t(who, "pair_src", pair_src, torch.int32)
+        if xyz_q.dim() != 2 or xyz_q.shape[1] != 3 or offs_q.dim() != 1 or pair_src.dim() != 1:
+            raise ValueError(f"{who}: xyz_q must be [*, 3], offs_q [Nq + 1] and pair_src [c]")
+        c = pair_src.numel()
+        if c > self.pair_capacity:
+            raise ValueError(f"{who}: c={c} exceeds pair_capacity={self.pair_capacity}")
+        if T.numel() != 12 * c:
+            raise ValueError(f"{who}: T must be [c, 3, 4]")
+        self._t(who, "T", T, torch.float64)
+        if accepted is not None:
+            if accepted.dtype == torch.bool:
+                accepted = accepted.view(torch.uint8)
+            if accepted.numel() != c:
+                raise ValueError(f"{who}: accepted must be [c]")
+            self._t(who, "accepted", accepted, torch.uint8)
+        if len(nn) != 3:
+            raise ValueError(f"{who}: nn must be the triple (out_offs, nn_idx, nn_d2) of a correspondence pass")
+        self._t(who, "nn[0]", nn[0], torch.int64, (c + 1,))
+        self._t(who, "nn[1]", nn[1], torch.int32)
+        self._t(who, "nn[2]", nn[2], torch.float64)
+        if nn[1].numel() != nn[2].numel():
+            raise ValueError(f"{who}: nn_idx and nn_d2 must have the same length")
+        return c, accepted
+
+    def _out(self, who, c, out):
+        import torch
+        if out is None:
+            dev = torch.device("cuda", self.ctx.device)
+            return RegInfo(torch.empty((c, 6, 6), dtype=torch.float64, device=dev), torch.empty((c, 6, 6), dtype=torch.float64, device=dev),
+                           torch.empty((c, 16), dtype=torch.float64, device=dev), torch.empty((c, 2), dtype=torch.float64, device=dev),
+                           torch.empty((c, 4), dtype=torch.int32, device=dev), torch.empty(c, dtype=torch.bool, device=dev))
+        want = ((torch.float64, (c, 6, 6)), (torch.float64, (c, 6, 6)), (torch.float64, (c, 16)), (torch.float64, (c, 2)), (torch.int32, (c, 4)),
+                (torch.bool, (c,)))
+        if len(out) != 6:
+            raise ValueError(f"{who}: out must be an earlier result")
+        for name, t, (dt, sh) in zip(RegInfo._fields, out, want):
+            self._t(who, f"out.{name}", t, dt, sh)
+        return RegInfo(*out)
+
+    def point_torch(self, xyz_q, offs_q, pair_src, T, nn, accepted=None, max_corr: float = 1.0, min_inliers: int = 10, min_ratio: float = 1e-4,
+                    sigma_min: float = 0.01, w_max: float = 1e6, out=None):
+        """Device form (pr_reginfo_point_dev): the clouds (xyz_q f64 [*, 3], offs_q i64 [Nq + 1]) of pair_src i32 [c] under T f64 [c, 3, 4],
+        accepted bool / u8 [c] or None, nn = (out_offs i64 [c + 1], nn_idx i32, nn_d2 f64) of the pass at T.  Returns a RegInfo of device
+        tensors; out: an earlier result for the same c, written again."""
+        who = "RegistrationInfo.point_torch"
+        c, accepted = self._args(who, xyz_q, offs_q, pair_src, T, accepted, nn)
+        out = self._out(who, c, out)
+        p = self._p
+        self.ctx.check(self.lib.pr_reginfo_point_dev(self.h, p(xyz_q), p(offs_q), offs_q.numel() - 1, p(pair_src), c, p(T), p(accepted), p(nn[0]),
+                                                     p(nn[1]), p(nn[2]), float(max_corr), int(min_inliers), float(min_ratio), float(sigma_min),
+                                                     float(w_max), *(p(t) for t in out)))
+        return out
+
+    def plane_torch(self, xyz_q, offs_q, pair_src, T, nn, world_xyz, normals, ninfo, accepted=None, max_corr: float = 0.9, min_inliers: int = 10,
+                    min_ratio: float = 1e-4, sigma_min: float = 0.01, w_max: float = 1e6, out=None):
+        """Device form (pr_reginfo_plane_dev): point_torch's arguments with nn from MapLocalizer.nn_torch at T, plus world_xyz f64
+        [out_capacity, 3] (WorldMap.xyz) and PlaneLocalizer.normals_torch's (normals f64 [out_capacity, 3], ninfo i32 [out_capacity])."""
+        import torch
+        who = "RegistrationInfo.plane_torch"
+        c, accepted = self._args(who, xyz_q, offs_q, pair_src, T, accepted, nn)
+        self._t(who, "world_xyz", world_xyz, torch.float64)
+        if world_xyz.dim() != 2 or world_xyz.shape[1] != 3 or world_xyz.shape[0] < 1:
+            raise ValueError(f"{who}: world_xyz must be [out_capacity, 3]")
+        oc = world_xyz.shape[0]
+        self._t(who, "normals", normals, torch.float64, (oc, 3))
+        self._t(who, "ninfo", ninfo, torch.int32, (oc,))
+        out = self._out(who, c, out)
+        p = self._p
+        self.ctx.check(self.lib.pr_reginfo_plane_dev(self.h, p(xyz_q), p(offs_q), offs_q.numel() - 1, p(pair_src), c, p(T), p(accepted), p(nn[0]),
+                                                     p(nn[1]), p(nn[2]), p(world_xyz), oc, p(normals), p(ninfo), float(max_corr),
+                                                     int(min_inliers), float(min_ratio), float(sigma_min), float(w_max), *(p(t) for t in out)))
+        return out
+
+    def pairs_torch(self, clouds_q, clouds_db, idx, T, accepted, max_src_pts: int, max_dst_pts: int, max_corr: float = 1.0, min_inliers: int = 10,
+                    min_ratio: float = 1e-4, sigma_min: float = 0.01, w_max: float = 1e6, out=None):
+        """The information of a verify's result: clouds_q = (xyz, offs) of the m queries, clouds_db = (xyz, offs) of the DB side or a
+        KeyframeMap, idx i32 [m, k], T f64 [m, k, 3, 4] and accepted bool / u8 [m, k] as verify returns them.  pair_dst = where(accepted,
+        idx, -1) on the device, then pr_icp_nn_radius_dev at T (the context's search mode), then point_torch with the same accepted;
+        slot p = q k + j reads query cloud q.  Returns a RegInfo over c = m k slots; out as for point_torch."""
+        import torch
+        who = "RegistrationInfo.pairs_torch"
+        if hasattr(clouds_db, "clouds"):
+            if clouds_db.ctx is not self.ctx:
+                raise ValueError(f"{who}: the map must live on this handle's context (one stream)")
+            clouds_db = clouds_db.clouds
+        xq, oq = clouds_q
+        xd, od = clouds_db
+        if idx.dim() != 2:
+            raise ValueError(f"{who}: idx must be [m, k]")
+        m, k = idx.shape
+        c = m * k
+        if c > self.pair_capacity:
+            raise ValueError(f"{who}: c={c} exceeds pair_capacity={self.pair_capacity}")
+        if int(max_src_pts) > self.max_src_pts:
+            raise ValueError(f"{who}: max_src_pts={max_src_pts} exceeds the handle's {self.max_src_pts}")
+        self._t(who, "idx", idx, torch.int32)
+        self._t(who, "xyz_db", xd, torch.float64)
+        self._t(who, "offs_db", od, torch.int64, numel_min=1)
+        if accepted.dtype == torch.bool:
+            accepted = accepted.view(torch.uint8)
+        self._t(who, "accepted", accepted, torch.uint8, (m, k))
+        dev = idx.device
+        wk = self._work.get(("pairs", m, k))
+        if wk is None:
+            rows = c * max(self.max_src_pts, 1)
+            wk = dict(src=torch.arange(m, dtype=torch.int32, device=dev).repeat_interleave(k).contiguous(),
+                      dst=torch.empty(c, dtype=torch.int32, device=dev), minus1=torch.full((m, k), -1, dtype=torch.int32, device=dev),
+                      nn=(torch.zeros(c + 1, dtype=torch.int64, device=dev), torch.empty(rows, dtype=torch.int32, device=dev),
+                          torch.empty(rows, dtype=torch.float64, device=dev)))
+            self._work[("pairs", m, k)] = wk
+        torch.where(accepted != 0, idx, wk["minus1"], out=wk["dst"].view(m, k))
+        Tc = T.reshape(c, 3, 4) if T.is_contiguous() else T
+        self._t(who, "T", Tc, torch.float64, (c, 3, 4))
+        self._t(who, "xyz_q", xq, torch.float64)
+        self._t(who, "offs_q", oq, torch.int64, numel_min=1)
+        p = self._p
+        nn = wk["nn"]
+        self.ctx.check(self.lib.pr_icp_nn_radius_dev(self.ctx.h, p(xq), p(oq), oq.numel() - 1, p(xd), p(od), od.numel() - 1, p(wk["src"]), p(wk["dst"]),
+                                                     c, p(Tc), int(max_src_pts), int(max_dst_pts), float(max_corr), p(nn[0]), p(nn[1]), p(nn[2])))
+        return self.point_torch(xq, oq, wk["src"], Tc, nn, accepted.reshape(c), max_corr, min_inliers, min_ratio, sigma_min, w_max, out=out)
+
+    def maploc_torch(self, plane_localizer, xyz_q, offs_q, pair_src, T, normals, ninfo, accepted=None, excl=None, max_corr: float = 0.9,
+                     min_inliers: int = 10, min_ratio: float = 1e-4, sigma_min: float = 0.01, w_max: float = 1e6, out=None):
+        """The information of a scan-to-map result: pr_maploc_nn_dev at T through plane_localizer's localiser (its index, excl as there),
+        then plane_torch against its world rows.  The localiser must live on this handle's context and have its pair_capacity and
+        max_src_pts within this handle's."""
+        who = "RegistrationInfo.maploc_torch"
+        ml = plane_localizer.ml
+        if plane_localizer.ctx is not self.ctx:
+            raise ValueError(f"{who}: the plane localiser must live on this handle's context (one stream)")
+        if ml.max_src_pts > self.max_src_pts:
+            raise ValueError(f"{who}: the localiser's max_src_pts={ml.max_src_pts} exceeds the handle's {self.max_src_pts}")
+        c = pair_src.numel()
+        wk = self._work.get(("maploc", c))
+        wk = ml.nn_torch(xyz_q, offs_q, pair_src, T, excl, max_corr, out=wk)
+        self._work[("maploc", c)] = wk
+        return self.plane_torch(xyz_q, offs_q, pair_src, T, wk, ml.wm.xyz, normals, ninfo, accepted, max_corr, min_inliers, min_ratio, sigma_min,
+                                w_max, out=out)
+
+    # ---- host forms (synchronise)
+    def _host(self, who, xyz_q, offs_q, pair_src, T, accepted, nn):
+        xq = np.ascontiguousarray(xyz_q, np.float64).reshape(-1, 3); oq = np.ascontiguousarray(offs_q, np.int64).reshape(-1)
+        ps = np.ascontiguousarray(pair_src, np.int32).reshape(-1)
+        if len(oq) < 1 or oq[-1] != len(xq):
+            raise ValueError(f"{who}: the clouds are a CSR set: xyz [offs[-1], 3] and offs [Nq + 1]")
+        c = len(ps)
+        T = np.ascontiguousarray(T, np.float64)
+        if T.size != 12 * c:
+            raise ValueError(f"{who}: T must be [c, 3, 4]")
+        acc = None
+        if accepted is not None:
+            acc = np.ascontiguousarray(accepted, np.uint8).reshape(-1)
+            if len(acc) != c:
+                raise ValueError(f"{who}: accepted must be [c]")
+        oo = np.ascontiguousarray(nn[0], np.int64).reshape(-1); ni = np.ascontiguousarray(nn[1], np.int32).reshape(-1)
+        nd = np.ascontiguousarray(nn[2], np.float64).reshape(-1)
+        if len(oo) != c + 1 or len(ni) != len(nd) or (c > 0 and oo[-1] > len(ni)):
+            raise ValueError(f"{who}: nn must be (out_offs [c + 1], nn_idx, nn_d2 [>= out_offs[-1]])")
+        out = RegInfo(np.zeros((c, 6, 6)), np.zeros((c, 6, 6)), np.zeros((c, 16)), np.zeros((c, 2)), np.zeros((c, 4), np.int32), np.zeros(c, np.uint8))
+        return xq, oq, ps, c, T, acc, oo, ni, nd, out
+
+    def point(self, xyz_q, offs_q, pair_src, T, nn, accepted=None, max_corr: float = 1.0, min_inliers: int = 10, min_ratio: float = 1e-4,
+              sigma_min: float = 0.01, w_max: float = 1e6):
+        """Host form (pr_reginfo_point) over numpy arrays: a RegInfo of numpy arrays (ok as bool)."""
+        xq, oq, ps, c, T, acc, oo, ni, nd, out = self._host("RegistrationInfo.point", xyz_q, offs_q, pair_src, T, accepted, nn)
+        self.ctx.check(self.lib.pr_reginfo_point(self.h, _ptr(xq), _ptr(oq), len(oq) - 1, _ptr(ps), c, _ptr(T), _ptr(acc), _ptr(oo), _ptr(ni), _ptr(nd),
+                                                 float(max_corr), int(min_inliers), float(min_ratio), float(sigma_min), float(w_max),
+                                                 *(_ptr(a) for a in out)))
+        return out._replace(ok=out.ok.astype(bool))
+
+    def plane(self, xyz_q, offs_q, pair_src, T, nn, world_xyz, normals, ninfo, accepted=None, max_corr: float = 0.9, min_inliers: int = 10,
+              min_ratio: float = 1e-4, sigma_min: float = 0.01, w_max: float = 1e6):
+        """Host form (pr_reginfo_plane) over numpy arrays: a RegInfo of numpy arrays (ok as bool)."""
+        who = "RegistrationInfo.plane"
+        xq, oq, ps, c, T, acc, oo, ni, nd, out = self._host(who, xyz_q, offs_q, pair_src, T, accepted, nn)
+        wx = np.ascontiguousarray(world_xyz, np.float64).reshape(-1, 3)
+        oc = len(wx)
+        nrm = np.ascontiguousarray(normals, np.float64); info = np.ascontiguousarray(ninfo, np.int32)
+        if nrm.shape != (oc, 3) or info.shape != (oc,):
+            raise ValueError(f"{who}: normals must be [out_capacity, 3] and ninfo [out_capacity]")
+        self.ctx.check(self.lib.pr_reginfo_plane(self.h, _ptr(xq), _ptr(oq), len(oq) - 1, _ptr(ps), c, _ptr(T), _ptr(acc), _ptr(oo), _ptr(ni), _ptr(nd),
+                                                 _ptr(wx), oc, _ptr(nrm), _ptr(info), float(max_corr), int(min_inliers), float(min_ratio),
+                                                 float(sigma_min), float(w_max), *(_ptr(a) for a in out)))
+        return out._replace(ok=out.ok.astype(bool))
+
+    def close(self):
+        if getattr(self, "h", None) and getattr(self.ctx, "h", None):
+            self.lib.pr_reginfo_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class MapGrower:
-    """pr_mapgrow: the world map, the localiser's voxel index and the world-map normals grown by ONE keyframe a call.
+    """pr_mapgrow:the world map, the localiser's voxel index and the world-map normals grown by ONE keyframe a call.
     After a rebuild - WorldMap.fuse_torch(keep='first', min_count=1, cell=the localiser's) -> MapLocalizer.index_torch ->
     PlaneLocalizer.normals_torch -> sync_torch, which rebuild_torch issues in that order - extend_torch(row) takes in map row `row` (word
     1 of KeyframeMap.append's info) and normals_torch recomputes the normals around its new rows; both leave the rebuild's bytes at a cost

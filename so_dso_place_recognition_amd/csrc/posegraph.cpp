@@ -24,6 +24,7 @@ struct pr_posegraph {
   uint8_t* stage_acc = nullptr;       // [128]
   int32_t* stage_row = nullptr;       // [4]
   int32_t* stage_info = nullptr;      // [4]
+  double* stage_w = nullptr;          // [128][2]
 };
 
 namespace {
@@ -70,7 +71,7 @@ int pr_posegraph_create(pr_ctx* ctx, const pr_posegraph_buffers* buffers, int32_
                o_r = take(NC * 6 * 8), o_z = take(NC * 6 * 8), o_p = take(NC * 6 * 8), o_q = take(NC * 6 * 8), o_dinv = take(NC * 36 * 8),
                o_valid = take(S * 4), o_fin = take(NC * 4), o_deg = take(NC * 4), o_cur = take(NC * 4), o_off = take((NC + 1) * 4),
                o_raw = take(2 * EC * 4), o_inc = take(2 * EC * 4), o_ctl = take(16), o_sidx = take(pr::POSEGRAPH_MAX_K * 4), o_sT = take(pr::POSEGRAPH_MAX_K * 12 * 8),
-               o_sacc = take(pr::POSEGRAPH_MAX_K), o_srow = take(16), o_sinfo = take(16);
+               o_sacc = take(pr::POSEGRAPH_MAX_K), o_srow = take(16), o_sinfo = take(16), o_sw = take(pr::POSEGRAPH_MAX_K * 2 * 8);
   hipError_t e = hipMalloc(&g->scratch, total);
   if (e != hipSuccess) {
     delete g;
@@ -83,7 +84,7 @@ int pr_posegraph_create(pr_ctx* ctx, const pr_posegraph_buffers* buffers, int32_
   v.g = dp(o_g); v.x = dp(o_x); v.r = dp(o_r); v.z = dp(o_z); v.p = dp(o_p); v.q = dp(o_q); v.dinv = dp(o_dinv);
   v.valid = ip(o_valid); v.finite = ip(o_fin); v.deg = ip(o_deg); v.cursor = ip(o_cur); v.inc_off = ip(o_off); v.inc_raw = ip(o_raw); v.inc = ip(o_inc); v.ctl = ip(o_ctl);
   g->stage_idx = ip(o_sidx); g->stage_T = dp(o_sT); g->stage_acc = reinterpret_cast<uint8_t*>(b + o_sacc); g->stage_row = ip(o_srow);
-  g->stage_info = ip(o_sinfo);
+  g->stage_info = ip(o_sinfo); g->stage_w = dp(o_sw);
   hipStream_t st = pr::ctx_stream(ctx);
   e = hipMemsetAsync(v.state, 0, 4 * sizeof(int32_t), st);
   if (e == hipSuccess) e = hipMemsetAsync(g->scratch, 0, total, st);
@@ -156,6 +157,44 @@ int pr_posegraph_add(pr_posegraph* g, const int32_t* idx, const double* T, const
   if (e == hipSuccess) e = hipMemcpyAsync(g->stage_row, row, sizeof row, hipMemcpyHostToDevice, st);
   int rc = PR_OK;
   if (e == hipSuccess) rc = pr_posegraph_add_dev(g, g->stage_idx, g->stage_T, g->stage_acc, g->stage_row, k, w_rot, w_trans, g->stage_info);
+  if (e == hipSuccess && rc == PR_OK) e = hipMemcpyAsync(info, g->stage_info, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, st);
+  const hipError_t e2 = hipStreamSynchronize(st);     // the host arrays are in flight until here
+  if (rc != PR_OK) return rc;
+  PR_CHECK_HIP(ctx, e);
+  PR_CHECK_HIP(ctx, e2);
+  return PR_OK;
+}
+
+int pr_posegraphw_add_dev(pr_posegraph* g, const int32_t* d_idx, const double* d_T, const uint8_t* d_accepted, const int32_t* d_query_row,
+                                  int32_t k, const double* d_w, int32_t* d_info) {
+  pr_ctx* ctx = g ? g->ctx : nullptr;
+  if (k < 1 || k > pr::POSEGRAPH_MAX_K) return fail(ctx, PR_EINVAL, "pr_posegraphw_add_dev: k=%d outside 1 .. %d", k, pr::POSEGRAPH_MAX_K);
+  if (!g) return fail(nullptr, PR_EINVAL, "pr_posegraphw_add_dev: graph is NULL");
+  if (!d_idx || !d_T || !d_accepted || !d_query_row || !d_w || !d_info)
+    return fail(ctx, PR_EINVAL, "pr_posegraphw_add_dev: a required pointer is NULL (d_idx, d_T, d_accepted, d_query_row, d_w, d_info)");
+  PR_CHECK_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
+  pr::launch_posegraph_add_weighted(pr::ctx_stream(ctx), g->v, d_idx, d_T, d_accepted, d_query_row, k, d_w, d_info);
+  PR_CHECK_HIP(ctx, hipGetLastError());
+  return PR_OK;
+}
+
+int pr_posegraphw_add(pr_posegraph* g, const int32_t* idx, const double* T, const uint8_t* accepted, int32_t query_row, int32_t k,
+                              const double* w, int32_t* info) {
+  pr_ctx* ctx = g ? g->ctx : nullptr;
+  if (k < 1 || k > pr::POSEGRAPH_MAX_K) return fail(ctx, PR_EINVAL, "pr_posegraphw_add: k=%d outside 1 .. %d", k, pr::POSEGRAPH_MAX_K);
+  if (!g) return fail(nullptr, PR_EINVAL, "pr_posegraphw_add: graph is NULL");
+  if (!idx || !T || !accepted || !w || !info)
+    return fail(ctx, PR_EINVAL, "pr_posegraphw_add: a required pointer is NULL (idx, T, accepted, w, info)");
+  PR_CHECK_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
+  hipStream_t st = pr::ctx_stream(ctx);
+  const int32_t row[4] = {query_row, 0, 0, 0};
+  hipError_t e = hipMemcpyAsync(g->stage_idx, idx, (size_t)k * 4, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(g->stage_T, T, (size_t)k * 12 * 8, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(g->stage_acc, accepted, (size_t)k, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(g->stage_row, row, sizeof row, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(g->stage_w, w, (size_t)k * 2 * 8, hipMemcpyHostToDevice, st);
+  int rc = PR_OK;
+  if (e == hipSuccess) rc = pr_posegraphw_add_dev(g, g->stage_idx, g->stage_T, g->stage_acc, g->stage_row, k, g->stage_w, g->stage_info);
   if (e == hipSuccess && rc == PR_OK) e = hipMemcpyAsync(info, g->stage_info, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, st);
   const hipError_t e2 = hipStreamSynchronize(st);     // the host arrays are in flight until here
   if (rc != PR_OK) return rc;

@@ -62,6 +62,46 @@ __global__ __launch_bounds__(128) void posegraph_add_kernel(PoseGraphView v, con
   }
 }
 
+// posegraph_add_kernel's rule slot for slot with (w_rot, w_trans) = w[p] read from device memory (pr_reginfo's d_w); a slot is logged
+// only if both of its weights are finite and >= 0
+__global__ __launch_bounds__(128) void posegraph_add_weighted_kernel(PoseGraphView v, const int* __restrict__ idx, const double* __restrict__ T,
+                                                                     const unsigned char* __restrict__ accepted, const int* __restrict__ query_row,
+                                                                     int k, const double* __restrict__ w, int* __restrict__ info) {
+  __shared__ int ok[POSEGRAPH_MAX_K];
+  if (blockIdx.x != 0) return;
+  const int tid = threadIdx.x;                                   // k <= 128 = the block
+  const int e0 = clampi(v.state[0], v.edge_capacity);            // a scribbled count never forms an address
+  int flags = v.state[1] & POSEGRAPH_OVERFLOW;
+  const int row = query_row[0];
+  bool mine = false;
+  double wr = 0.0, wt = 0.0;
+  if (tid < k && row >= 0) {
+    mine = accepted[tid] != 0 && idx[tid] >= 0 && idx[tid] != row;
+    for (int c = 0; c < 12; c++) mine = mine && fin(T[(size_t)tid * 12 + c]);
+    wr = w[2 * (size_t)tid]; wt = w[2 * (size_t)tid + 1];
+    mine = mine && fin(wr) && fin(wt) && wr >= 0.0 && wt >= 0.0;
+  }
+  ok[tid] = mine ? 1 : 0;
+  __syncthreads();                                               // every thread has read state
+  int before = 0, total = 0;
+  for (int q = 0; q < POSEGRAPH_MAX_K; q++) { before += q < tid ? ok[q] : 0; total += ok[q]; }
+  const int room = v.edge_capacity - e0, stored = total < room ? total : room;
+  if (mine && before < room) {                                   // row e0 + before < edge_capacity
+    const size_t e = (size_t)e0 + before;
+    v.edge_ij[e * 2] = idx[tid]; v.edge_ij[e * 2 + 1] = row;
+    for (int c = 0; c < 12; c++) v.edge_Z[e * 12 + c] = T[(size_t)tid * 12 + c];
+    v.edge_w[e * 2] = wr; v.edge_w[e * 2 + 1] = wt;
+  }
+  if (tid == 0) {
+    if (row >= 0) {
+      if (total > room) flags |= POSEGRAPH_OVERFLOW;
+      v.state[0] = e0 + stored;
+      v.state[1] = flags;
+    }
+    info[0] = stored; info[1] = stored > 0 ? e0 : -1; info[2] = e0 + stored; info[3] = flags;
+  }
+}
+
 // ------------------------------------------------------------------------------------------------ 3 x 3 helpers (row-major)
 __device__ __forceinline__ void mul33(const double* A, const double* B, double* C) {
 #pragma unroll
@@ -508,6 +548,11 @@ __global__ __launch_bounds__(256) void posegraph_finish_kernel(PoseGraphView v, 
 void launch_posegraph_add(hipStream_t st, const PoseGraphView& v, const int* idx, const double* T, const unsigned char* accepted,
                           const int* query_row, int k, double w_rot, double w_trans, int* info) {
   hipLaunchKernelGGL(posegraph_add_kernel, dim3(1), dim3(128), 0, st, v, idx, T, accepted, query_row, k, w_rot, w_trans, info);
+}
+
+void launch_posegraph_add_weighted(hipStream_t st, const PoseGraphView& v, const int* idx, const double* T, const unsigned char* accepted,
+                                   const int* query_row, int k, const double* w, int* info) {
+  hipLaunchKernelGGL(posegraph_add_weighted_kernel, dim3(1), dim3(128), 0, st, v, idx, T, accepted, query_row, k, w, info);
 }
 
 void launch_posegraph_relax(hipStream_t st, const PoseGraphView& v, const double* poses_in, const int* n, const PoseGraphParams& prm,

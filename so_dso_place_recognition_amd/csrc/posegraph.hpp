@@ -34,6 +34,9 @@ struct PoseGraphParams { int outer, inner; double lambda, w_odo_rot, w_odo_trans
 
 void launch_posegraph_add(hipStream_t st, const PoseGraphView& v, const int* idx, const double* T, const unsigned char* accepted,
                           const int* query_row, int k, double w_rot, double w_trans, int* info);
+// the add with per-slot weights w [k][2] in device memory
+void launch_posegraph_add_weighted(hipStream_t st, const PoseGraphView& v, const int* idx, const double* T, const unsigned char* accepted,
+                                   const int* query_row, int k, const double* w, int* info);
 void launch_posegraph_relax(hipStream_t st, const PoseGraphView& v, const double* poses_in, const int* n, const PoseGraphParams& prm,
                             double* poses_out, double* report);
 
