@@ -121,7 +121,10 @@ size_t sc_match_h_lds_bytes();
 // sc_match_e.hip — the pair-walk form (no row-exchanged query operand; see the file): single = 0: split-f16 (three products, 4 waves),
 // single = 1: one f16 product per term (PR_SC_ARITH_F16), 8 waves = two per SIMD; same packed images and constants as sc_match_h.hip
 void launch_sc_match_e(hipStream_t st, const void* qpk, int m, const void* dpk, int n, const void* cst, float* d_p, float* d_i,
-                       int nsplit_override, int single, int dgs = 0 /* channel stride of the DB image in 16-entry groups when it is not sc_dgroups(n): an appendable set */);
+                       int nsplit_override, int single, int dgs = 0 /* channel stride of the DB image in 16-entry groups when it is not sc_dgroups(n): an appendable set */,
+                       int sweep = 1 /* split-f16, m > 8: 1 = query groups resident in LDS, DB tiles streamed; 2 = one DB group resident, query tiles streamed; 0 = by shape */);
+int sc_dbr_ranges(int m, int DG, int chans, int cus);     // query ranges of the DB-resident sweep (the tail rule, sc_match_e.hip)
+bool sc_dbr_auto(int m, int n);                          // the shapes at which `auto` takes the DB-resident sweep
 // split-f16 images whose channel 1 may be binary (ScBin above): channel 0 in split-f16; channel 1 by the single-product kernel on the hi
 // halves with integer rounding when the sets' statistics allow it, in split-f16 otherwise - the decision is taken ON THE DEVICE by every
 // workgroup from the same numbers (no host round trip: the two channel-1 launches are both issued, one of them leaves at once).
@@ -129,7 +132,7 @@ void launch_sc_match_e(hipStream_t st, const void* qpk, int m, const void* dpk, 
 // (Measured and dropped: the channel-0 launch of an online call and the binary pass on two streams at once - 0.302 -> 0.308 ms at m = 1,
 // 0.310 -> 0.337 at m = 8: sc_match_h's workgroups fill the LDS of their CUs, the two kernels do not run side by side, and the event hand-offs cost.)
 void launch_sc_match_e_bin(hipStream_t st, const void* qpk, int m, const void* dpk, int n, const void* cst, float* d_p, float* d_i,
-                           int nsplit_override, ScBin bin, hipEvent_t* ev, int online_h = 0 /* m <= 8: sc_match_h.hip's one-group form (PR_SC_ONLINE=h, read once at pr_create) */, int dgs = 0 /* as in launch_sc_match_e */);
+                           int nsplit_override, ScBin bin, hipEvent_t* ev, int online_h = 0 /* m <= 8: sc_match_h.hip's one-group form (PR_SC_ONLINE=h, read once at pr_create) */, int dgs = 0 /* as in launch_sc_match_e */, int sweep = 1 /* as in launch_sc_match_e */);
 
 // m2dp_match.hip — processM2DP.m:12-22 for both channels.
 void launch_m2dp_pack(hipStream_t st, const void* sig, int dtype, int sigs, float* packed, int tiles);

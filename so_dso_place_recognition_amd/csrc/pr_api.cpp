@@ -63,6 +63,7 @@ struct pr_ctx {
   int sc_kernel = 2;             // split-f16 SC matcher for m > 8: 2 = sc_match_e.hip (default); PR_SC_KERNEL=h selects sc_match_h.hip (0, round 1; always the kernel for m <= 8)
   int sc_mode = PR_SC_ARITH_F16X2;   // PR_SC_ARITH_*: split-f16 MFMA (sc_match_h.hip) | fp32 MFMA (sc_match.hip); PR_SC_MATCH=f32 selects the latter
   double* d_planes = nullptr;    // M2DP xProj[64][3], yProj[64][3]
+  int sc_sweep = 0;              // split-f16 sweep of sc_match_e.hip for m > 8: 0 = by shape (sc_dbr_auto), 1 = query groups resident (PR_SC_SWEEP=q), 2 = DB group resident (PR_SC_SWEEP=d)
   int sc_nsplit = 0;             // PR_SC_NSPLIT override (experiments)
   bool force_order = false;      // PR_FORCE_ORDER_FLAGS=1 (tests): every query counts as flagged by the order check, i.e. every query gets fp64 row statistics
   bool sc_binary = true;         // split-f16 arithmetic: a binary intensity channel goes through the single-product kernel with integer rounding (kernels.hpp: ScBin); PR_SC_BINARY=0 / pr_set_sc_binary turn it off
@@ -347,6 +348,7 @@ static int create_common(int device_id, hipStream_t external, bool use_external,
   if (const char* s = getenv("PR_SC_MATCH")) ctx->sc_mode = (strcmp(s, "f32") == 0) ? PR_SC_ARITH_F32 : (strcmp(s, "f16") == 0) ? PR_SC_ARITH_F16 : PR_SC_ARITH_F16X2;
   if (const char* s = getenv("PR_ICP_SEARCH")) (void)pr_set_icp_search(ctx, strcmp(s, "grid") == 0 ? PR_ICP_SEARCH_GRID : PR_ICP_SEARCH_BRUTE);
   if (const char* s = getenv("PR_SC_KERNEL")) ctx->sc_kernel = (strcmp(s, "h") == 0) ? 0 : 2;
+  if (const char* s = getenv("PR_SC_SWEEP")) ctx->sc_sweep = (strcmp(s, "q") == 0) ? 1 : (strcmp(s, "d") == 0) ? 2 : 0;
   if (const char* s = getenv("PR_SC_BINARY")) ctx->sc_binary = atoi(s) != 0;
   if (const char* s = getenv("PR_SC_BINARY_PAIR_SCALE")) ctx->sc_pair_scale = (float)atof(s);
   if (const char* s = getenv("PR_XROW")) ctx->xrow_direct = strcmp(s, "direct") == 0;
@@ -797,11 +799,11 @@ int pr_distances_dev(pr_ctx* ctx, const pr_sigset* q, const pr_sigset* db, float
     ctx->bin_gen = ctx->bin_gen == 0x7fffffff ? 1 : ctx->bin_gen + 1;
     const pr::ScBin bin = {sigset_bstat(q), sigset_bstat(db), q->binfo, db->binfo, ctx->d_flags + 4, ctx->bin_gen, ctx->sc_bconst, ctx->sc_pair_scale, 0, -1};
     pr::launch_sc_match_e_bin(ctx->stream, q->packed, q->count, db->packed, db->count, ctx->d_cst_h, d_p, d_i, ctx->sc_nsplit, bin,
-                              ctx->timing ? ctx->ev_t : nullptr, ctx->sc_online_h ? 1 : 0, dgs);
+                              ctx->timing ? ctx->ev_t : nullptr, ctx->sc_online_h ? 1 : 0, dgs, ctx->sc_sweep);
     if (ctx->timing) ctx->timing_valid = 3;
   }
   else if (q->type == PR_TYPE_SC && q->sc_mode == 0 && ctx->sc_kernel == 2 && (q->count > 8 || !ctx->sc_online_h))
-    pr::launch_sc_match_e(ctx->stream, q->packed, q->count, db->packed, db->count, ctx->d_cst_h, d_p, d_i, ctx->sc_nsplit, 0, dgs);
+    pr::launch_sc_match_e(ctx->stream, q->packed, q->count, db->packed, db->count, ctx->d_cst_h, d_p, d_i, ctx->sc_nsplit, 0, dgs, ctx->sc_sweep);
   else if (q->type == PR_TYPE_SC && q->sc_mode == 0)
     pr::launch_sc_match_h(ctx->stream, q->packed, q->count, db->packed, db->count, ctx->d_cst_h, d_p, d_i, ctx->sc_nsplit);
   else if (q->type == PR_TYPE_SC)

@@ -55,6 +55,12 @@
 #ifndef E_BD
 #define E_BD 4          // depth of the DB operand ring, split-f16 form (-DE_NO_ACC_OPERANDS; 6 with the operands in AccVGPRs, above)
 #endif
+#ifndef E_DBR_AD
+#define E_DBR_AD E_BD   // DB-resident sweep: depth of the query operand ring (the vector-memory side there)
+#endif
+#ifndef E_DBR_BD
+#define E_DBR_BD E_AD   // ... and of the DB operand ring (read from LDS)
+#endif
 #ifndef E_BD1
 #define E_BD1 8         // the same, single-product form (a position is only two MFMAs long); round 6: 6 -> 8, binary launch 9.06 -> 8.90 ms (-1.8 %, alternating
                         // runs); 252 of the 256 registers a wave has at two per SIMD - 9 spills
@@ -105,6 +111,24 @@ __device__ __forceinline__ void load_b(BOps& b, __amdgpu_buffer_rsrc_t rs, int v
 #else
   const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rs, voff + ioff, soff, 0);
 #endif
+  if (T == B_REH) b.reh = v; else if (T == B_REL) b.rel = v; else if (T == B_IMH) b.imh = v; else b.iml = v;
+}
+
+// DB-resident sweep (DBR, split-f16 form): the roles of the two memories are exchanged - the query tiles come through the vector memory path
+// (the frequency in the scalar offset, off = sch_qrow_byte(row) + sch_a1_byte / sch_a2_byte of the lane) and the DB tiles from the group image
+// the workgroup holds in LDS.  The image (95 232 B) is longer than the 16-bit immediate of a DS instruction: one base register per half of
+// the frequencies.  Same bytes into the same operand tuples as load_a / load_b.
+template <int T, int F>
+__device__ __forceinline__ void load_a_g(AOps& a, __amdgpu_buffer_rsrc_t rq, int off) {
+  const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rq, off, F * SCH_QBLK, 0);
+  if (T == A_H) a.h = v; else a.l = v;
+}
+constexpr int E_DBR_FH = 16;                                   // frequencies below read at the first base register, the others at the second
+template <int F, int T>
+__device__ __forceinline__ void load_b_l(BOps& b, unsigned addr) {      // addr = this lane's piece of the pair's tiles of frequency 0 | E_DBR_FH
+  constexpr int ioff = (F % E_DBR_FH) * SCH_DFREQ + ((T == B_IMH || T == B_IML) ? 2 * SCH_DTILE : 0);
+  static_assert(ioff + SCH_DTILE + 16 * 16 < 65536, "DS immediate offset");
+  const u32x4 v = *reinterpret_cast<lds_tile_p>(addr + ioff);
   if (T == B_REH) b.reh = v; else if (T == B_REL) b.rel = v; else if (T == B_IMH) b.imh = v; else b.iml = v;
 }
 
@@ -326,7 +350,11 @@ __device__ __forceinline__ void valu_slot(f32x4 (&T)[2][8], Half<LO> (&hbs)[2]) 
 // eight waves share the one group and split the DB groups, 20 KB of LDS, several workgroups per CU)
 // SV (single-product form only): the kernel reads the hi halves of SPLIT-f16 images (the query groups are gathered into the compact LDS
 // image, the DB loads address the hi tiles) and rounds the result to the integer count of a binary channel (ep_store_round)
-template <bool LO, int NW, int NQG, bool SV = false>
+// DBR (split-f16 form, four waves): the DB-resident sweep.  A workgroup is (DB group, query range): it copies ONE DB group image into LDS,
+// and wave w walks the query groups w, w + 4, ... of the range, streaming their tiles (load_a_g); `nsplit` is the number of query ranges.
+// Nothing is published inside the unit loop and the waves are not coupled.  Stage 1's MFMAs, the VALU schedule, stage 2 and the reduction
+// are the same statements - the distances are the same bits.
+template <bool LO, int NW, int NQG, bool SV = false, bool DBR = false>
 __global__ __launch_bounds__(64 * NW, NW / 4) void sc_match_e_kernel(const char* __restrict__ qpk,   // [2][QG32][4][31][1280 B]
                                                             const char* __restrict__ dpk,   // [2][DG][31][4][768 B] + zero groups
                                                             const u32x4* __restrict__ cst,  // [2][2][2][64] x 16 B
@@ -335,6 +363,7 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void sc_match_e_kernel(const char*
                                                             int DGS /* channel stride of the DB image in groups: DG, or the capacity's of an appendable set */) {
   extern __shared__ __attribute__((aligned(16))) char lds[];
   static_assert(!SV || !LO, "SV: single-product form");
+  static_assert(!DBR || (LO && NW == 4 && NQG == 4), "DB-resident sweep: split-f16 form, one wave per SIMD");
   float bbound = 0.f;
   // the channel-0 launch of a binary-channel call clears the violation word the two channel-1 launches behind it speak through: `gen` is a
   // kernel argument, i.e. frozen inside a captured hipGraph - without this a replay that once failed a pair would keep finding its own
@@ -355,6 +384,13 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void sc_match_e_kernel(const char*
   const int range = (bin.chsel < 0 ? (xcd >> 1) + 4 * (idx % nsplit) : xcd + 8 * (idx % nsplit)), qg32 = idx / nsplit;
   const int nrange = (bin.chsel < 0 ? 4 : 8) * nsplit;
   const int g0 = (int)((long long)DG * range / nrange), g1 = (int)((long long)DG * (range + 1) / nrange);
+  // DB-resident sweep: the XCD's share of the DB groups is every NX-th one; the workgroups of an XCD are range-major, so the 32 resident
+  // ones walk the same query range in the same order and the query image passes through the XCD's L2 once per round
+  const int NX = bin.chsel < 0 ? 4 : 8, xq = bin.chsel < 0 ? (xcd >> 1) : xcd, GX = (DG + NX - 1) / NX;
+  const int qrange = idx / GX, gfix = xq + NX * (idx - qrange * GX);
+  const int QGr = (m + 7) >> 3, Q4 = (QGr + 3) >> 2;                   // query groups that hold queries; fours of them
+  const int q0 = 4 * (int)((long long)Q4 * qrange / nsplit), q1r = 4 * (int)((long long)Q4 * (qrange + 1) / nsplit), q1 = q1r < QGr ? q1r : QGr;
+  if constexpr (DBR) { if (gfix >= DG) return; }
 
   // image geometry: split-f16 (4 query groups per workgroup) | single product (hi halves only: 8 query groups, kernels.hpp SCF_*)
   constexpr int QBLK = LO ? SCH_QBLK : SCF_QBLK, QIMG = LO ? SCH_QIMG : SCF_QIMG, DIMG = (LO || SV) ? SCH_DIMG : SCF_DIMG;
@@ -380,6 +416,22 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void sc_match_e_kernel(const char*
       qi[2 * i] = r < m ? bin.qinfo[2 * r] * 0x1p-25f : 0.f;
       qi[2 * i + 1] = r < m ? bin.qinfo[2 * r + 1] : 0.f;
     }
+  } else if constexpr (DBR) {  // the DB group of this workgroup -> LDS (linear copy of the packed image) + zeroed tail
+    // A workgroup runs few units behind this copy when the queries are cut into many ranges, so the copy is not left to a loop of
+    // dependent load -> store steps: twelve loads of every lane are in flight at once (two rounds for the 5952 + 4 pieces; the pieces past
+    // the image are outside the resource and read as zeros)
+    const __amdgpu_buffer_rsrc_t rg =
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(dpk + ((size_t)ch * DGS + gfix) * DIMG), 0, DIMG, 0x00020000);
+    u32x4* dst = reinterpret_cast<u32x4*>(lds);
+    constexpr int NV = DIMG / 16, CPY = 12;
+    static_assert(2 * CPY * 64 * NW >= NV + 4, "two rounds of the copy cover the image");
+    for (int i0 = tid; i0 < NV + 4; i0 += CPY * 64 * NW) {
+      u32x4 v[CPY];
+#pragma unroll
+      for (int c = 0; c < CPY; c++) v[c] = __builtin_amdgcn_raw_buffer_load_b128(rg, (i0 + c * 64 * NW) * 16, 0, 0);
+#pragma unroll
+      for (int c = 0; c < CPY; c++) if (i0 + c * 64 * NW < NV + 4) dst[i0 + c * 64 * NW] = v[c];
+    }
   } else {  // the query groups of this workgroup -> LDS (linear copy; the packed image IS the LDS image) + zeroed tail
     const u32x4* src = reinterpret_cast<const u32x4*>(qpk + ((size_t)ch * QG8 + (size_t)qg32 * NQG) * QIMG);
     u32x4* dst = reinterpret_cast<u32x4*>(lds);
@@ -394,8 +446,9 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void sc_match_e_kernel(const char*
   const int wq = w & (NQG - 1), dpar = (NW > NQG) ? (w / NQG) : 0;
   constexpr int GSTEP = NW / NQG;
   const int gcnt = g1 - g0;
-  constexpr int BD = LO ? E_BD : E_BD1;            // depth of the DB operand ring: the tiles of BD - 1 walk positions are in flight
-  constexpr int AD = LO ? E_AD : 3;                // the same for the query tiles
+  // (DB-resident sweep: the ring depths swap with the roles - the deep ring is on the vector-memory side)
+  constexpr int BD = DBR ? E_DBR_BD : LO ? E_BD : E_BD1;   // depth of the DB operand ring: the tiles of BD - 1 walk positions are in flight
+  constexpr int AD = DBR ? E_DBR_AD : LO ? E_AD : 3;       // the same for the query tiles
   // split-f16 form: the two operand pairs of a frequency (kernels.hpp) - this lane's 16 bytes of its query row, and of the DB tiles below
   static_assert(!LO || (QIMG % 16 == 0 && QBLK % 16 == 0 && QROW % 16 == 0), "split-f16 query tiles are read with ds_read_b128");
   const unsigned natr = lds0 + wq * QIMG + (LO ? sch_qrow_byte(row) : row * QROW);
@@ -403,23 +456,30 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void sc_match_e_kernel(const char*
   [[maybe_unused]] const unsigned nat1 = natr + sch_a2_byte(kg);
   const int voff = LO ? sch_b1_byte(lane) : ((lane < 48) ? lane * 16 : (int)0x80000000);     // single product, lanes 48-63: out of range -> zeros (K = 24..31)
   [[maybe_unused]] const int voff2 = sch_b2_byte(lane);
+  // DB-resident sweep: the lane's byte in a query block for the two operand pairs, and its LDS addresses in the DB tiles of the two halves
+  [[maybe_unused]] const int aoff1 = sch_qrow_byte(row) + sch_a1_byte(kg), aoff2 = sch_qrow_byte(row) + sch_a2_byte(kg);
+  [[maybe_unused]] unsigned lb1 = lds0 + sch_b1_byte(lane), lb2 = lds0 + sch_b2_byte(lane);
+  [[maybe_unused]] unsigned lb1h = lb1 + E_DBR_FH * SCH_DFREQ, lb2h = lb2 + E_DBR_FH * SCH_DFREQ;
+  if constexpr (DBR) asm volatile("" : "+v"(lb1), "+v"(lb2), "+v"(lb1h), "+v"(lb2h));      // four base registers, not one and an add per read
+  const char* qbase = qpk + (size_t)ch * QG8 * QIMG;
   float* dist = ch ? dist_i : dist_p;
   const char* dbase = dpk + ((size_t)ch * DGS) * DIMG;
-  const int qrow0 = qg32 * (8 * NQG) + wq * 8;
-  const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc(
-      dist + (size_t)qrow0 * n, 0, (qrow0 < m ? (m - qrow0 < 8 ? m - qrow0 : 8) : 0) * n * 4, 0x00020000);
+  const int qrow0 = DBR ? 0 : qg32 * (8 * NQG) + wq * 8;
+  __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc(
+      dist + (size_t)qrow0 * n, 0, (qrow0 < m ? (m - qrow0 < 8 ? m - qrow0 : 8) : 0) * n * 4, 0x00020000);     // (DB-resident sweep: per unit, below)
   // this wave's share of the group(s) it helps to prefetch: the 32 workgroups resident on an XCD are consecutive idx, i.e. rsd = 32 / nsplit
   // consecutive query blocks per range.  Split-f16 form (nsplit = 1 on the metric workload): 32 NW waves x 6 lines >= the 744 lines of a
   // group, as tuned.  Single-product form with several query groups per workgroup: rsd NW waves share the GSTEP x 372 lines (hi tiles only
   // in the SV view) - with the fixed two lines per wave of round 3, nsplit = 2 left half of every group to demand misses.
   constexpr int GLINES = SC_NF * 12;                                         // 128-byte lines of the Re / Im (hi) tiles of one group
   const int rsd = (LO || NQG == 1) ? 32 : (nsplit >= 32 ? 1 : 32 / nsplit);
-  const int pf_slot = (LO || NQG == 1) ? (qg32 & 31) * NW + w : (qg32 % rsd) * NW + w;
-  constexpr int PFL = LO ? 6 : 2;
+  const int pf_slot = DBR ? (idx & 31) * NW + w : (LO || NQG == 1) ? (qg32 & 31) * NW + w : (qg32 % rsd) * NW + w;
+  constexpr int PFL = DBR ? 10 : LO ? 6 : 2;           // DB-resident sweep: 32 NW waves x 10 lines >= the 1240 lines of the NW query groups of a step
   const int pfl = (LO || NQG == 1) ? PFL : ((NW / NQG) * GLINES + rsd * NW - 1) / (rsd * NW);
   unsigned pf_sink = 0;
   const __amdgpu_buffer_rsrc_t rc = __builtin_amdgcn_make_buffer_rsrc(const_cast<u32x4*>(cst), 0, 8192, 0x00020000);
-  if (dpar >= gcnt) return;
+  if constexpr (DBR) { if (q0 + w >= q1) return; }
+  else if (dpar >= gcnt) return;
   f32x2 qinf[4] = {{0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}};      // SV: of this lane's query of store R: row R (lanes 0-15) | 4 + R (16-31)
   if constexpr (SV) {
     const f32x2* qi = reinterpret_cast<const f32x2*>(lds + NQG * QIMG + 64);
@@ -434,13 +494,29 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void sc_match_e_kernel(const char*
   if constexpr (LO) { load_consts<0, LO>(c0, rc, lane * 16); load_consts<1, LO>(c1, rc, lane * 16); }
   AOps At[AD];
   BOps Bt[BD];
-  __amdgpu_buffer_rsrc_t rs =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(dbase + (size_t)(g0 + dpar) * DIMG), 0, DIMG, 0x00020000);
+  // the streamed operand's image of the first unit: a DB group | (DB-resident sweep) a query group
+  __amdgpu_buffer_rsrc_t rs = DBR ? __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(qbase + (size_t)(q0 + w) * QIMG), 0, QIMG, 0x00020000)
+                                  : __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(dbase + (size_t)(g0 + dpar) * DIMG), 0, DIMG, 0x00020000);
 // request K of the first ones of a unit (issued before the loop for the first unit, in the stage-2 gaps of the previous unit otherwise):
 // the DB tiles of walk positions 0 .. BD - 2 (TPB tiles each), then the query tiles of positions 0 .. AD - 2
   constexpr int TPB = LO ? 4 : 2, TPA = LO ? 2 : 1, NREQ = (BD - 1) * TPB + (AD - 1) * TPA;
+// (DB-resident sweep: the query tiles - the vector-memory side - first)
+#define REQ_A(P_, TT, RSRC) { if constexpr (DBR) load_a_g<TT, seqf(P_)>(At[(P_) % AD], RSRC, (TT == A_L) ? aoff2 : aoff1);                       \
+                              else load_a<TT, LO>(At[(P_) % AD], (TT == A_L ? nat1 : nat0) + seqf(P_) * QBLK); }
+#define REQ_B(P_, TT, RSRC) { if constexpr (DBR) load_b_l<seqf(P_), TT>(Bt[(P_) % BD], (TT == B_REL || TT == B_IML) ? (seqf(P_) < E_DBR_FH ? lb2 : lb2h) \
+                                                                                                                  : (seqf(P_) < E_DBR_FH ? lb1 : lb1h)); \
+                              else load_b<LO, seqf(P_), TT, SV>(Bt[(P_) % BD], RSRC, (LO && (TT == B_REL || TT == B_IML)) ? voff2 : voff); }
 #define FIRST_REQ(K, RSRC)                                                                                         \
-  { if constexpr ((K) < (BD - 1) * TPB) {                                                                          \
+  { if constexpr (DBR) {                                                                                           \
+      if constexpr ((K) < (AD - 1) * TPA) {                                                                        \
+        constexpr int _p = (K) / TPA, _t = (K) % TPA;                                                              \
+        REQ_A(_p, _t, RSRC);                                                                                       \
+      } else if constexpr ((K) < NREQ) {                                                                           \
+        constexpr int _k = (K) - (AD - 1) * TPA, _p = _k / TPB, _t = _k % TPB;                                     \
+        constexpr int _tt = _t == 1 ? B_IMH : _t == 2 ? B_REL : _t == 3 ? B_IML : B_REH;                           \
+        REQ_B(_p, _tt, RSRC);                                                                                      \
+      }                                                                                                            \
+    } else if constexpr ((K) < (BD - 1) * TPB) {                                                                          \
       constexpr int _p = (K) / TPB, _t = LO ? (K) % TPB : 2 * ((K) % TPB);      /* order Re hi, (Re lo), Im hi, (Im lo) */ \
       constexpr int _tt = LO ? (_t == 1 ? B_IMH : _t == 2 ? B_REL : _t == 3 ? B_IML : B_REH) : _t;                 \
       load_b<LO, seqf(_p), _tt, SV>(Bt[_p % BD], RSRC, (LO && (_tt == B_REL || _tt == B_IML)) ? voff2 : voff);        \
@@ -453,18 +529,25 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void sc_match_e_kernel(const char*
   FIRST_REQ(16, rs) FIRST_REQ(17, rs) FIRST_REQ(18, rs) FIRST_REQ(19, rs) FIRST_REQ(20, rs) FIRST_REQ(21, rs) FIRST_REQ(22, rs) FIRST_REQ(23, rs)
   static_assert(NREQ <= 24, "FIRST_REQ list too short");
 
-  for (int g = g0 + dpar; g < g1; g += GSTEP) {
-    const int gn = g + GSTEP;                       // (the image ends with zero groups: the requests past the last group are harmless)
+  // a unit per iteration: the DB groups of the range | (DB-resident sweep) the query groups of the range against the one DB group
+  constexpr int USTEP = DBR ? NW : GSTEP;
+  for (int u = DBR ? q0 + w : g0 + dpar; u < (DBR ? q1 : g1); u += USTEP) {
+    const int g = DBR ? gfix : u;
+    const int gn = u + USTEP;                       // (the image ends with zero groups: the requests past the last group are harmless)
+    // (DB-resident sweep: the query image is padded to fours of groups and ends there - a zero-length resource past it)
     const __amdgpu_buffer_rsrc_t rsn =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(dbase + (size_t)gn * DIMG), 0, DIMG, 0x00020000);
+        DBR ? __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(qbase + (size_t)gn * QIMG), 0, gn < QG8 ? QIMG : 0, 0x00020000)
+            : __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(dbase + (size_t)gn * DIMG), 0, DIMG, 0x00020000);
+    if constexpr (DBR)                              // the unit's 8 distance rows (rows past m: outside the resource)
+      rd = __builtin_amdgcn_make_buffer_rsrc(dist + (size_t)u * 8 * n, 0, (m - u * 8 < 8 ? m - u * 8 : 8) * n * 4, 0x00020000);
     Half<LO> hbs[2];
     f32x4 T[2][8];
     if constexpr (LO)      // (pins the resident constants in their AccVGPR tuples across the back edge, as park_half does)
       asm volatile("" : "+a"(c0.ch), "+a"(c0.cl), "+a"(c0.sh), "+a"(c0.sl), "+a"(c1.ch), "+a"(c1.cl), "+a"(c1.sh), "+a"(c1.sl));
 
 // request tile T of walk position Q of this unit (Q >= 31: nothing)
-#define LDB(Q, TT) { if constexpr ((Q) < 32 && seqf((Q) < 32 ? (Q) : 0) < SC_NF && (LO || (TT == B_REH || TT == B_IMH))) load_b<LO, seqf((Q) < 32 ? (Q) : 0), TT, SV>(Bt[(Q) % BD], rs, (LO && (TT == B_REL || TT == B_IML)) ? voff2 : voff); }
-#define LDA(Q, TT) { if constexpr ((Q) < 32 && seqf((Q) < 32 ? (Q) : 0) < SC_NF && (LO || TT == A_H)) load_a<TT, LO>(At[(Q) % AD], (TT == A_L ? nat1 : nat0) + seqf((Q) < 32 ? (Q) : 0) * QBLK); }
+#define LDB(Q, TT) { if constexpr ((Q) < 32 && seqf((Q) < 32 ? (Q) : 0) < SC_NF && (LO || (TT == B_REH || TT == B_IMH))) REQ_B((Q) < 32 ? (Q) : 0, TT, rs); }
+#define LDA(Q, TT) { if constexpr ((Q) < 32 && seqf((Q) < 32 ? (Q) : 0) < SC_NF && (LO || TT == A_H)) REQ_A((Q) < 32 ? (Q) : 0, TT, rs); }
 #define VS(P, G) valu_slot<LO, ((P) >> 2), (((P) & 3) * 6 + (G))>(T, hbs)
 // one walk position: its 6 (LO) or 2 MFMAs, the requests for positions P + AD - 1 (query tiles) and P + BD - 1 (DB tiles), the quad's VALU
 // work of its six slots
@@ -560,9 +643,12 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void sc_match_e_kernel(const char*
     {  // L2 prefetch for the whole XCD: the 32 NW waves that sweep this range on this XCD cover the group(s) of the iteration after next
        // with 6 cache lines each, one dword per line into a register nobody reads before the same point of the next unit
       asm volatile("" : : "v"(pf_sink));
-      const int gp = (g - dpar) + 2 * GSTEP;
-      const int pf_bytes = (gp + GSTEP <= DG) ? GSTEP * DIMG : (gp < DG ? (DG - gp) * DIMG : 0);
-      const __amdgpu_buffer_rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(dbase + (size_t)gp * DIMG), 0, pf_bytes, 0x00020000);
+      // (DB-resident sweep: the same for the NW query groups of the iteration after next; the image ends with the padded fours of groups)
+      const int gp = DBR ? (u - w) + 2 * NW : (g - dpar) + 2 * GSTEP;
+      const int pf_bytes = DBR ? (gp + NW <= QG8 ? NW * QIMG : (gp < QG8 ? (QG8 - gp) * QIMG : 0))
+                               : (gp + GSTEP <= DG) ? GSTEP * DIMG : (gp < DG ? (DG - gp) * DIMG : 0);
+      const __amdgpu_buffer_rsrc_t rp = DBR ? __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(qbase + (size_t)gp * QIMG), 0, pf_bytes, 0x00020000)
+                                            : __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(dbase + (size_t)gp * DIMG), 0, pf_bytes, 0x00020000);
       int lp = lane;
       asm volatile("" : "+v"(lp));
       int pf_off = (lp < pfl) ? (pf_slot * pfl + lp) * 128 : (int)0x80000000;   // waves x lines >= the lines of the step's group(s); past the end: out of range
@@ -629,10 +715,63 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void sc_match_e_kernel(const char*
 
 size_t sc_match_e_lds_bytes(int single, int nqg) { return (single ? (size_t)nqg * SCF_QIMG : (size_t)nqg * SCH_QIMG) + 64 + (single ? 64 * nqg : 0); }
 
+// ---------------------------------------------------------------------------------------------------------------- DB-resident sweep
+// Query ranges: a launch is chans x DG x nq workgroups of one per CU, i.e. R = chans DG nq / CUs rounds, and the CUs that get no workgroup
+// in the last round idle for tail(nq) = (ceil R - R) / ceil R of the launch.  Every workgroup also pays the copy of its DB group image
+// (about one unit), so a wave must keep at least 16 units: nq <= max(1, Q4 / 16), Q4 = fours of query groups.  The rule: the smallest such
+// nq with tail(nq) < 1 %, or the smallest nq of the smallest tail when none reaches that.  4096 x 100 000 (DG = 6250, Q4 = 128, 256 CUs,
+// one channel per launch): nq = 1: 24.4 rounds, 2.3 %; nq = 2: 48.8 rounds, 0.35 % -> 2.  3475 x 3475 (DG = 218, Q4 = 109): nq <= 6 and
+// 218 nq workgroups leave 14.8 % of the CUs of the last round idle for every such nq -> 1 (nq = 7 would reach 0.65 % with 16 units per
+// wave and measured no faster: DESIGN.md 4.0).
+int sc_dbr_ranges(int m, int DG, int chans, int cus) {
+  const int Q4 = (((m + 7) / 8) + 3) / 4, nqmax = Q4 / 16 > 1 ? Q4 / 16 : 1;
+  int best = 1;
+  double best_tail = 2.;
+  for (int nq = 1; nq <= nqmax; nq++) {
+    const long long wg = (long long)chans * DG * nq, rounds = (wg + cus - 1) / cus;
+    const double tail = (double)(rounds * cus - wg) / (double)(rounds * cus);
+    if (tail < 0.01) return nq;
+    if (tail < best_tail - 1e-9) { best_tail = tail; best = nq; }
+  }
+  return best;
+}
+// Where the DB-resident sweep is taken on `auto`: the shapes at which it won the measurement (256 .. 4096 queries against
+// 3475 and 100 000 entries; it loses at 64 queries, where a wave runs two units behind the copy of the DB group)
+bool sc_dbr_auto(int m, int n) { return m >= 256 && n >= 3475; }
+namespace {
+int device_cus() {
+  static const int cus = [] {
+    int dev = 0, v = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
+    return v;
+  }();
+  return cus;
+}
+// one split-f16 launch of the DB-resident sweep: channel b.chsel (< 0: both), m > 8
+void launch_dbr(hipStream_t st, const void* qpk, int m, const void* dpk, int n, const void* cst, float* d_p, float* d_i, int nsplit_override,
+                const ScBin& b, int DGS) {
+  const int QG8 = sc_qgroups8(m), DG = sc_dgroups(n), NX = b.chsel < 0 ? 4 : 8, GX = (DG + NX - 1) / NX, Q4 = (((m + 7) / 8) + 3) / 4;
+  int nq = sc_dbr_ranges(m, DG, b.chsel < 0 ? 2 : 1, device_cus());
+  if (nsplit_override > 0) nq = nsplit_override < Q4 ? nsplit_override : Q4;
+  auto kern = sc_match_e_kernel<true, 4, 4, false, true>;
+  const size_t lds_bytes = (size_t)SCH_DIMG + 64;
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+  hipLaunchKernelGGL(kern, dim3(8 * GX * nq), dim3(256), lds_bytes, st, static_cast<const char*>(qpk), static_cast<const char*>(dpk),
+                     static_cast<const u32x4*>(cst), d_p, d_i, m, n, QG8, DG, nq, b, DGS);
+}
+// (the m <= 8 online forms have no DB-resident counterpart; forced, it serves 9 .. 16 queries too, with two idle waves)
+bool use_dbr(int sweep, int m, int n) { return m > 8 && (sweep == 2 || (sweep == 0 && m > 16 && sc_dbr_auto(m, n))); }
+}  // namespace
+
 void launch_sc_match_e(hipStream_t st, const void* qpk, int m, const void* dpk, int n, const void* cst, float* d_p, float* d_i,
-                       int nsplit_override, int single, int dgs) {
+                       int nsplit_override, int single, int dgs, int sweep) {
   if (m <= 0 || n <= 0) return;
   const int QG8 = single ? sc_qgroups8_f16(m) : sc_qgroups8(m), DG = sc_dgroups(n), DGS = dgs > 0 ? dgs : DG;
+  if (!single && use_dbr(sweep, m, n)) {
+    const ScBin none = {nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0.f, 1.f, 0, -1};
+    launch_dbr(st, qpk, m, dpk, n, cst, d_p, d_i, nsplit_override, none, DGS);
+    return;
+  }
   // query groups per workgroup: as many as hold queries (an online batch of 9 .. 16 | .. 32 keyframes: the waves a group would leave to the
   // padding of the image take other DB groups instead)
   const int QGr = (m + 7) / 8;
@@ -670,7 +809,7 @@ void launch_sc_match_e(hipStream_t st, const void* qpk, int m, const void* dpk, 
 // the single-product kernel on the hi halves with integer rounding (leaves at once when the bound does not hold), then the split-f16 kernel
 // (leaves at once when that pass ran and every pair passed its rounding test)
 void launch_sc_match_e_bin(hipStream_t st, const void* qpk, int m, const void* dpk, int n, const void* cst, float* d_p, float* d_i,
-                           int nsplit_override, ScBin bin, hipEvent_t* ev, int online_h, int dgs) {
+                           int nsplit_override, ScBin bin, hipEvent_t* ev, int online_h, int dgs, int sweep) {
   if (m <= 0 || n <= 0) return;
   const int QG8 = sc_qgroups8(m), DG = sc_dgroups(n), DGS = dgs > 0 ? dgs : DG;
   auto grid = [&](int QGW) {     // ranges per XCD: >= ~4 workgroups per CU in total, >= 8 DB groups per workgroup (an eighth of the ranges per XCD)
@@ -736,15 +875,22 @@ void launch_sc_match_e_bin(hipStream_t st, const void* qpk, int m, const void* d
     if (ev) (void)hipEventRecord(ev[3], st);
     return;
   }
+  const bool dbr = use_dbr(sweep, m, n);                             // the two split-f16 launches in the DB-resident sweep
+  auto split = [&](int chsel, int gate) {
+    if (!dbr) { go(sc_match_e_kernel<true, 4, 4>, 4, 4, 0, chsel, gate); return; }
+    ScBin b = bin;
+    b.chsel = chsel; b.gate = gate;
+    launch_dbr(st, qpk, m, dpk, n, cst, d_p, d_i, nsplit_override, b, DGS);
+  };
   if (ev) (void)hipEventRecord(ev[0], st);
-  go(sc_match_e_kernel<true, 4, 4>, 4, 4, 0, 0, 0);                 // channel 0
+  split(0, 0);                                                      // channel 0
   if (ev) (void)hipEventRecord(ev[1], st);
   // channel 1, one product per term + rounding: runs when the bound predicts success (up to 32 queries: four query groups per workgroup,
   // two DB groups at a time - with eight, half of the waves would multiply padding)
   if (QG8 <= 4) go(sc_match_e_kernel<false, 8, 4, true>, 8, 4, 1, 1, 1);
   else go(sc_match_e_kernel<false, 8, 8, true>, 8, 8, 1, 1, 1);
   if (ev) (void)hipEventRecord(ev[2], st);
-  go(sc_match_e_kernel<true, 4, 4>, 4, 4, 0, 1, 2);                 // channel 1 in split-f16: runs when it did not run, or a pair failed its test
+  split(1, 2);                                                      // channel 1 in split-f16: runs when it did not run, or a pair failed its test
   if (ev) (void)hipEventRecord(ev[3], st);
 }
 

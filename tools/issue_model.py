@@ -34,7 +34,8 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "so_dso_place_recognition_amd", "csrc", "sc_match_e.hip")
 COSTS = os.path.join(ROOT, "tools", "issue_model_costs.json")
-KERNELS = {"split": "ILb1ELi4ELi4E", "single": "ILb0ELi8ELi8E", "online": "ILb0ELi8ELi1E"}
+# <LO, NW, NQG, SV, DBR> (the tags end at a template argument, so a prefix cannot pick the DB-resident twin of an instantiation)
+KERNELS = {"split": "ILb1ELi4ELi4ELb0ELb0E", "split_dbr": "ILb1ELi4ELi4ELb0ELb1E", "single": "ILb0ELi8ELi8ELb0ELb0E", "online": "ILb0ELi8ELi1ELb0ELb0E"}
 
 
 def classify(op):
@@ -215,7 +216,7 @@ def main():
     st = unit_stream(KERNELS[a.kernel])
     base_chain = None
     if a.hypothetical == "coarse-stage2":
-        assert a.kernel == "split"
+        assert a.kernel in ("split", "split_dbr")
         base_chain = simulate(st, c)[0]
         st = coarse_stage2(st, a.refine_candidates)
     chain, pipe, hist = simulate(st, c)

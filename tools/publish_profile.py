@@ -36,7 +36,7 @@ json.dump(d, open(os.path.join(ROOT, "profiles", tag + "_derived.json"), "w"), i
 res = {"source": f"profiles/{tag}.txt via profiles/derive.py: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes of `python bench.py --steps 3 --warmup 1 "
                  "--full --no-cpu-baseline --no-kitti-shape` (with the extra workloads); per launch, per (kernel, grid, duration cluster); FETCH_SIZE x2 (gfx950 wide-read "
                  "correction, MI355X_MICROARCH.md)", "workload": {"db": 100000, "queries": 4096, "n_gpus": 1}}
-struct = sorted([k for k in d["kernels"] if k.startswith("sc_match_e_kernel<true, 4, 4, false> @ 262144")], key=lambda k: d["kernels"][k]["ms_per_launch"])
+struct = sorted([k for k in d["kernels"] if k.startswith(("sc_match_e_kernel<true, 4, 4, false> @ 262144", "sc_match_e_kernel<true, 4, 4, false, false> @ 262144", "sc_match_e_kernel<true, 4, 4, false, true> @"))], key=lambda k: d["kernels"][k]["ms_per_launch"])
 struct = [k for k in struct if d["kernels"][k]["ms_per_launch"] > 1.0]
 for k, e in d["kernels"].items():
     if "hbm_bytes" not in e:
