@@ -1618,6 +1618,117 @@ int pr_posegraphw_add_dev(pr_posegraph* g, const int32_t* d_idx, const double* d
 int pr_posegraphw_add(pr_posegraph* g, const int32_t* idx, const double* T, const uint8_t* accepted, int32_t query_row, int32_t k,
                               const double* w, int32_t* info);
 
+/* ---- trajectory evaluation against ground truth (trajeval.hip) ------------------------------------------------------------
+ * What the loop-closure back end is for is a better trajectory; a pr_trajeval measures one: the absolute trajectory error (ATE) under an
+ * alignment, the relative pose error (RPE) per row delta, KITTI's odometry metric over segments of given path lengths, and the error of
+ * every logged closure against the ground truth - for B candidate pose arrays a call.  Everything is stream-ordered, reads every count on
+ * the device, allocates nothing after create and uses no floating-point atomics; every grid is a function of the create sizes only, so one
+ * capture made at n = 0 serves every count, and one graph gate -> relax -> evaluate can be replayed per parameter setting.
+ *
+ *   pr_trajeval_create   params: node_capacity (cap) 1 .. 2^20, batch (B) 1 .. 64, align PR_TRAJ_ALIGN_*, gt_kind PR_TRAJ_GT_*, n_deltas (K)
+ *                        0 .. 8, n_lengths (L) 0 .. 8, step >= 1 (rows between segment starts), edge_capacity (EC) 0 .. 65536 (0: no closure
+ *                        metric), rot_thr (radians) and trans_thr of a WRONG closure.  deltas [K] i32, each >= 1, and lengths [L] f64, each
+ *                        finite and > 0, are HOST tables; create uploads them and allocates ALL scratch in one block.  With
+ *                        slots = ceil(cap / step) the parts are, each rounded up to 16 bytes:
+ *                          4 B cap (used) | 4 cap (gt used) | 24 (B + 1) cap (centres) | 16 B cap (prefixes) | 128 B (S)
+ *                          | 32 B L (the lengths' segment sums) | 32 | 64 (tables)
+ *                          | staging of the host form: 192 B (ate) | 64 B K (rpe) | 32 B (L + 1) (seg) | 64 (clo) | 8 B cap (err)
+ *                          | 4 B slots L (seg_end) | 16 EC (edge_err)
+ *                        pr_trajeval_scratch_bytes returns the sum (0 for sizes create refuses).
+ *   pr_trajeval_run_dev  2 launches, + 1 with K > 0, + 2 with L > 0, + 1 with a log.  d_est [B][cap][12] f64: rows as pr_map_buffers.poses
+ *                        (world to camera, row-major [R | t]).  d_n [>= 1] i32: a pr_map's state.  d_gt: [cap][12] f64 in the est's
+ *                        convention (PR_TRAJ_GT_W2C), [cap][12] camera to world - KITTI's file rows - (PR_TRAJ_GT_C2W) or [cap][3]
+ *                        positions (PR_TRAJ_GT_POSITIONS).  d_valid [cap] u8 or NULL (every row valid).  log: the buffer record of a
+ *                        pr_posegraph (edge_ij, edge_Z, state are read; edge_w is not) or NULL: no closure metric in this call; it needs
+ *                        EC > 0 and at most EC edges are read.  out: a record of DEVICE pointers.  ate is required, rpe with K > 0, seg with
+ *                        L > 0, clo with a log; the other five may be NULL.  Every entry of every given array is written.  No read-back.
+ *   pr_trajeval_run      the same with HOST arrays in `out` (d_est, d_n, d_gt, d_valid and the log stay device memory); synchronises.
+ *
+ * The rule (restated operation by operation in tests/trajeval_np.py; the device equals it bit for bit except where atan2 enters).
+ * Conventions as for pr_gate: A B = [R_A R_B | R_A t_B + t_A]; A^-1 = [R^T | -(R^T t)]; fp64, no contraction; a 3 x 3 product entry is
+ * (a0 b0 + a1 b1) + a2 b2, the translation of a product ((r0 t0 + r1 t1) + r2 t2) + t_A, of an inverse -((R0r t0 + R1r t1) + R2r t2);
+ * |x| = sqrt((x0 x0 + x1 x1) + x2 x2); a cross product entry is a b - c d.
+ *   THE TREE.  Every floating-point sum over rows (pairs, slots, edges) i = 0 .. M - 1 is formed as: 256 lane sums, lane t adding its terms
+ *      i = t, t + 256, t + 512, ... in that order to +0.0, a term that does not count adding +0.0; then for s = 128, 64, .. 1 lane t < s
+ *      becomes lane t + lane (t + s); the sum is lane 0.  A maximum starts at 0.0.
+ *   0. Counts and rows.  n = d_n[0] clamped into 0 .. cap, E = log.state[0] clamped into 0 .. EC, both before any address is formed.
+ *      gt row i is USED iff i < n, valid[i] != 0 (or valid is NULL) and its 12 (3) entries are finite; row i of candidate b is used iff
+ *      its gt row is used and the 12 entries of est row (b, i) are finite.
+ *   1. Centres.  Of a W2C row -(R^T t); of a C2W row t; of a position row the row.  out.centres [B + 1][cap][3]: the est centres of every
+ *      b, then the gt centres; zeros for a row that is not used.
+ *   2. Alignment S = (s, R, t) per b over its N used rows; x = est centre, y = gt centre.  flags: PR_TRAJ_FEW iff N < 3.
+ *      NONE: S = (1, I, 0).  FIRST: with f the first used row, (R, t) = G_f^-1 P_f (W2C gt) or G_f P_f (C2W gt), s = 1; the identity if
+ *      N = 0.  SE3, SIM3 with N < 3: the identity.  SE3, SIM3 with N >= 3 (Umeyama):
+ *        mx = (tree sum of x) / N, my likewise; then A = (tree sum of (y - my)(x - mx)^T) / N entry by entry and
+ *        var_x = (tree sum of ((dx0 dx0 + dx1 dx1) + dx2 dx2)) / N with dx = x - mx: the second pass is centred, a route at a UTM northing
+ *        does not cancel.
+ *        hmax = max |A_rc|.  If hmax is 0 or not finite: R = I, sigma = 0, DEGENERATE.  Else G = A / hmax, V = I and 10 sweeps, each:
+ *        W = G V (formed afresh), then for (p, q) = (0, 1), (0, 2), (1, 2): al = |w_p|^2, be = |w_q|^2, ga = w_p . w_q (all three
+ *        (a + b) + c); skipped unless ga ga > 1e-31 (al be); zeta = (be - al) / (2 ga); t = sign(zeta) / (|zeta| + sqrt(zeta zeta + 1))
+ *        (sign(0) = +1); cs = 1 / sqrt(t t + 1); sn = t cs; columns p, q of W and of V become (cs x - sn y, sn x + cs y).  After the
+ *        sweeps W = G V once more, m_k = |w_k|^2, and the columns of W and V are ordered by exchanging (0, 1), (1, 2), (0, 1), each iff
+ *        m_j < m_k.  n_k = sqrt(m_k), sigma_k = n_k hmax.  PR_TRAJ_DEGENERATE iff not n_2 > 1e-12 n_1 (a straight road, a standstill).
+ *        u_1 = w_1 / n_1.  u_2 = w_2 - (w_2 . u_1) u_1, divided by its norm; when DEGENERATE w_2 is replaced by the unit vector of the
+ *        axis k on which |u_1[k]| is smallest (the lowest k on a tie), so S is still a rigid map taking the line onto the line.
+ *        u_3 = u_1 x u_2; v_3' = v_1 x v_2 divided by its norm.  d = -1 iff not DEGENERATE and (u_3 . w_3)(v_3' . v_3) < 0, else +1: the
+ *        sign of det U det V, D = diag(1, 1, d).  R_ab = (u_1a v_1b + u_2a v_2b) + u_3a v_3'b  (= U D V^T).
+ *        PR_TRAJ_NO_SCALE iff not var_x > 0; s = ((sigma_1 + sigma_2) + d sigma_3) / var_x for SIM3 without NO_SCALE, else 1.
+ *        t = my - s (R mx).
+ *   3. ATE.  e_i = |y_i - (s (R x_i) + t)| with the parenthesis formed entry by entry as written.  out.err [B][cap]: e_i, -1 for a row
+ *      that is not used.  out.ate [B][24] = N, sse (tree sum of e_i^2 BEFORE the square root), rmse = sqrt(sse / N), mean = (tree sum of
+ *      e_i) / N, max, argmax (the lowest row on a tie; -1 with N = 0), s, R (9), t (3), flags, sigma_1 .. sigma_3, var_x; statistics of
+ *      N = 0 are zeros.
+ *   4. RPE per b and delta.  Pairs (i, i + delta), i + delta < n, both rows used.  rel_est = P_i P_j^-1 with its translation multiplied
+ *      by s entry by entry (s = 1 unless SIM3); rel_gt = G_i G_j^-1 (W2C) or G_i^-1 G_j (C2W); E = rel_gt^-1 rel_est.  tr = (E00 + E11) +
+ *      E22; c_rot = 3 - tr; v = (0.5 (E21 - E12), 0.5 (E02 - E20), 0.5 (E10 - E01)); theta = atan2(|v|, 0.5 (tr - 1)); d = |t_E|.
+ *      out.rpe [B][K][8] = pairs, sqrt((tree sum of d d) / pairs), mean d, max d, sqrt((tree sum of theta theta) / pairs), mean theta,
+ *      max theta, mean c_rot; zeros without a pair.
+ *   5. Segments per b.  Over the used rows dist[i] = dist[i - 1] + |y_i - y_prev used| (an unused row and the first used row add nothing)
+ *      and the same over x, in a BLOCKED order: C = ceil(cap / 256); block t holds rows t C .. t C + C - 1; w[i] is the running sum inside
+ *      the block from +0.0 in row order; base[t] the running sum of the totals of blocks 0 .. t - 1 from +0.0 in block order; dist[i] =
+ *      base[t] + w[i].  out.prefix [B][2][cap]: gt, then est.  For every start row f = 0, step, 2 step, .. that is used and every length:
+ *      the end is the FIRST row j > f, j < n, with dist[j] > dist[f] + len (strict: a standstill never ends a segment); the segment is
+ *      dropped if there is no such row or the row is not used.  With E of 4 between f and j: t_err = d / len, r_err = theta / len,
+ *      ratio = (dist_est[j] - dist_est[f]) / (dist[j] - dist[f]).  out.seg [B][L + 1][4] = segments, mean t_err, mean r_err, mean ratio
+ *      per length (tree sums over the slots f / step), and in row L over all segments: the lengths' tree sums added in table order from
+ *      +0.0, divided by the total count; zeros without a segment.  out.seg_end [B][slots][L] i32: the end row or -1.
+ *   6. Closures, once.  Edge a < E is evaluated iff 0 <= i, j < n, i != j, both gt rows are used and the 12 entries of Z are finite.
+ *      Z_gt = rel_gt of 4 between i and j; E = Z_gt^-1 Z; theta and d as in 4.  out.edge_err [EC][2] = (theta, d) or (-1, -1).
+ *      out.clo [8] = evaluated, wrong = #{theta > rot_thr or d > trans_thr}, sqrt((tree sum of theta theta) / evaluated), max theta,
+ *      sqrt((tree sum of d d) / evaluated), max d, E, 0.
+ * PR_EINVAL (text: pr_last_error) before any device is touched for a NULL handle, params, required pointer, table or log buffer, a size
+ * outside the ranges above, a delta < 1, a length that is not finite and > 0, a threshold that is NaN or negative, PR_TRAJ_GT_POSITIONS
+ * with K > 0, L > 0, EC > 0 or PR_TRAJ_ALIGN_FIRST (positions carry no rotation), and a log with EC = 0. */
+typedef struct pr_trajeval pr_trajeval;
+typedef struct pr_trajeval_params {
+  int32_t node_capacity, batch, align, gt_kind, n_deltas, n_lengths, step, edge_capacity;
+  double rot_thr, trans_thr;
+} pr_trajeval_params;
+typedef struct pr_trajeval_out {
+  double* ate; double* rpe; double* seg; double* clo; double* err; int32_t* seg_end; double* edge_err; double* centres; double* prefix;
+} pr_trajeval_out;
+#define PR_TRAJ_ALIGN_NONE 0
+#define PR_TRAJ_ALIGN_FIRST 1
+#define PR_TRAJ_ALIGN_SE3 2
+#define PR_TRAJ_ALIGN_SIM3 3
+#define PR_TRAJ_GT_W2C 0
+#define PR_TRAJ_GT_C2W 1
+#define PR_TRAJ_GT_POSITIONS 2
+#define PR_TRAJ_FEW 1
+#define PR_TRAJ_DEGENERATE 2
+#define PR_TRAJ_NO_SCALE 4
+#define PR_TRAJ_ATE_STATS 24
+#define PR_TRAJ_RPE_STATS 8
+#define PR_TRAJ_SEG_STATS 4
+#define PR_TRAJ_CLO_STATS 8
+int pr_trajeval_create(pr_ctx* ctx, const pr_trajeval_params* params, const int32_t* deltas, const double* lengths, pr_trajeval** out);
+int pr_trajeval_run_dev(pr_trajeval* te, const double* d_est, const int32_t* d_n, const void* d_gt, const uint8_t* d_valid,
+                        const pr_posegraph_buffers* log, const pr_trajeval_out* out);
+int pr_trajeval_run(pr_trajeval* te, const double* d_est, const int32_t* d_n, const void* d_gt, const uint8_t* d_valid,
+                    const pr_posegraph_buffers* log, const pr_trajeval_out* out);
+size_t pr_trajeval_scratch_bytes(const pr_trajeval_params* params);
+void pr_trajeval_destroy(pr_trajeval* te);
+
 #ifdef __cplusplus
 }
 #endif

@@ -36,6 +36,10 @@ MAPGROW_ORDER, MAPGROW_STALE, MAPGROW_FULL = 16, 32, 64            # refusals of
 GATE_SRC_OVERFLOW, GATE_UNSETTLED = 1, 2           # flags of a pr_gate run (info[3])
 SEQ_MAX_L, SEQ_MAX_V, SEQ_MAX_STEP, SEQ_MAX_K = 32, 16, 64, 32   # limits of a sequence-matching step table and call (PR_SEQ_*)
 SEQMATCH_MAX_K = 128                                # most slots of one pr_seqmatch push
+TRAJ_ALIGN_NONE, TRAJ_ALIGN_FIRST, TRAJ_ALIGN_SE3, TRAJ_ALIGN_SIM3 = 0, 1, 2, 3   # pr_trajeval_params.align
+TRAJ_GT_W2C, TRAJ_GT_C2W, TRAJ_GT_POSITIONS = 0, 1, 2                         # pr_trajeval_params.gt_kind
+TRAJ_FEW, TRAJ_DEGENERATE, TRAJ_NO_SCALE = 1, 2, 4                            # flags of a pr_trajeval alignment (ate[19])
+TRAJ_ATE_STATS, TRAJ_RPE_STATS, TRAJ_SEG_STATS, TRAJ_CLO_STATS = 24, 8, 4, 8   # doubles of one statistics row of a pr_trajeval run
 REGINFO_OFF, REGINFO_NONFINITE, REGINFO_TOO_FEW, REGINFO_SINGULAR, REGINFO_WEAK_ROT, REGINFO_WEAK_TRANS = 1, 2, 4, 8, 16, 32   # stat[3] of a pr_reginfo call
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -317,6 +321,11 @@ SYMBOLS = {
     "pr_seqmatch_scratch_bytes": (C.c_size_t, [_i32, _i32, _i32, _i32, _i32]),
     "pr_seqmatch_destroy": (None, [_vp]),
     "pr_host_last_error": (C.c_char_p, []),
+    "pr_trajeval_create": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(_vp)]),
+    "pr_trajeval_run_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pr_trajeval_run": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pr_trajeval_scratch_bytes": (C.c_size_t, [_vp]),
+    "pr_trajeval_destroy": (None, [_vp]),
 }
 
 
@@ -354,6 +363,17 @@ class PoseGraphParams(C.Structure):
 class GateParams(C.Structure):
     """pr_gate_params: what a pr_gate fixes at create."""
     _fields_ = [("max_gap", _i32), ("min_support", _i32), ("rounds", _i32)]
+
+
+class TrajEvalParams(C.Structure):
+    """pr_trajeval_params: what a pr_trajeval fixes at create."""
+    _fields_ = [(n, _i32) for n in ("node_capacity", "batch", "align", "gt_kind", "n_deltas", "n_lengths", "step", "edge_capacity")] + \
+               [("rot_thr", _dbl), ("trans_thr", _dbl)]
+
+
+class TrajEvalOut(C.Structure):
+    """pr_trajeval_out: the nine output arrays of a pr_trajeval run (device pointers for run_dev, host pointers for run)."""
+    _fields_ = [(n, _vp) for n in ("ate", "rpe", "seg", "clo", "err", "seg_end", "edge_err", "centres", "prefix")]
 
 
 _lib = None

@@ -1999,6 +1999,176 @@ class ClosureGate:
             pass
 
 
+class TrajEval(NamedTuple):
+    """What a TrajectoryEval run returns (torch tensors from run_torch / run_map, NumPy arrays from run); the parts a run does not have
+    are None.  ate [B, 24] = N, sse, rmse, mean, max, argmax, s, R (9), t (3), flags, sigma (3), var_x; rpe [B, K, 8] = pairs, rmse / mean /
+    max of d, rmse / mean / max of theta, mean c_rot; seg [B, L + 1, 4] = segments, mean t_err, mean r_err, mean path ratio (row L: all
+    lengths); clo [8] = evaluated, wrong, rmse / max of theta, rmse / max of d, edges read, 0; err [B, cap]; seg_end [B, slots, L] i32;
+    edge_err [EC, 2]; centres [B + 1, cap, 3]; prefix [B, 2, cap]."""
+    ate: object
+    rpe: object
+    seg: object
+    clo: object
+    err: object
+    seg_end: object
+    edge_err: object
+    centres: object
+    prefix: object
+
+
+class AteStats(NamedTuple):
+    """The columns of TrajEval.ate by name (TrajectoryEval.ate_stats)."""
+    N: object
+    sse: object
+    rmse: object
+    mean: object
+    max: object
+    argmax: object
+    s: object
+    R: object
+    t: object
+    flags: object
+    sigma: object
+    var_x: object
+
+
+class TrajectoryEval:
+    """pr_trajeval: a trajectory against ground truth on the device - ATE under an alignment ("none", "first", "se3",
+    "sim3"), RPE per row delta, KITTI's segment metric per path length and the error of logged closures - for B candidate pose arrays a
+    call.  est f64 [B, node_capacity, 12] (or [node_capacity, 12] with B = 1): rows as KeyframeMap.poses (world to camera); gt by gt_kind:
+    "w2c" [node_capacity, 12], "c2w" [node_capacity, 12] (KITTI's file rows) or "positions" [node_capacity, 3] (ATE only).  Calls are
+    enqueued on the context's stream, read every count on the device and allocate no device scratch; ONE captured run_torch serves every
+    count.  The rule is in include/place_recognition.h."""
+
+    ALIGN = dict(none=_lib.TRAJ_ALIGN_NONE, first=_lib.TRAJ_ALIGN_FIRST, se3=_lib.TRAJ_ALIGN_SE3, sim3=_lib.TRAJ_ALIGN_SIM3)
+    GT = dict(w2c=_lib.TRAJ_GT_W2C, c2w=_lib.TRAJ_GT_C2W, positions=_lib.TRAJ_GT_POSITIONS)
+    NAMES = TrajEval._fields
+
+    def __init__(self, ctx: Context | None, node_capacity: int, B: int = 1, align: str = "sim3", gt_kind: str = "c2w", deltas=(1, 10),
+                 lengths=(100.0, 200.0, 300.0, 400.0, 500.0, 600.0, 700.0, 800.0), step: int = 1, edge_capacity: int = 0,
+                 rot_thr: float = float(np.radians(5.0)), trans_thr: float = 2.0):
+        self.h = None
+        if align not in self.ALIGN:
+            raise ValueError(f"TrajectoryEval: align must be one of {sorted(self.ALIGN)}")
+        if gt_kind not in self.GT:
+            raise ValueError(f"TrajectoryEval: gt_kind must be one of {sorted(self.GT)}")
+        self.ctx = ctx or default_context()
+        self.lib = self.ctx.lib
+        self.node_capacity, self.B, self.align, self.gt_kind = int(node_capacity), int(B), align, gt_kind
+        self.deltas = np.ascontiguousarray(deltas, np.int32).reshape(-1)
+        self.lengths = np.ascontiguousarray(lengths, np.float64).reshape(-1)
+        self.K, self.L, self.step, self.edge_capacity = len(self.deltas), len(self.lengths), int(step), int(edge_capacity)
+        self.gt_cols = 3 if gt_kind == "positions" else 12
+        self.slots = -(-self.node_capacity // self.step) if self.step >= 1 and self.node_capacity >= 1 else 0
+        self.params = _lib.TrajEvalParams(self.node_capacity, self.B, self.ALIGN[align], self.GT[gt_kind], self.K, self.L, self.step,
+                                          self.edge_capacity, float(rot_thr), float(trans_thr))
+        h = C.c_void_p()
+        self.ctx.check(self.lib.pr_trajeval_create(self.ctx.h, C.byref(self.params), _ptr(self.deltas) if self.K else None,
+                                                   _ptr(self.lengths) if self.L else None, C.byref(h)))
+        self.h = h
+
+    def scratch_bytes(self) -> int:
+        return int(self.lib.pr_trajeval_scratch_bytes(C.byref(self.params)))
+
+    def shapes(self, log: bool = True):
+        """name -> (shape, NumPy dtype) of every output this handle can write (clo and edge_err only with a closure log)."""
+        B, cap, K, L = self.B, self.node_capacity, self.K, self.L
+        s = dict(ate=((B, _lib.TRAJ_ATE_STATS), np.float64), err=((B, cap), np.float64), centres=((B + 1, cap, 3), np.float64),
+                 prefix=((B, 2, cap), np.float64))
+        if K:
+            s["rpe"] = ((B, K, _lib.TRAJ_RPE_STATS), np.float64)
+        if L:
+            s["seg"] = ((B, L + 1, _lib.TRAJ_SEG_STATS), np.float64)
+            s["seg_end"] = ((B, self.slots, L), np.int32)
+        if log and self.edge_capacity:
+            s["clo"] = ((_lib.TRAJ_CLO_STATS,), np.float64)
+            s["edge_err"] = ((self.edge_capacity, 2), np.float64)
+        return s
+
+    @staticmethod
+    def ate_stats(ate) -> AteStats:
+        """TrajEval.ate [B, 24] split into its named columns (views)."""
+        return AteStats(ate[:, 0], ate[:, 1], ate[:, 2], ate[:, 3], ate[:, 4], ate[:, 5], ate[:, 6], ate[:, 7:16].reshape(-1, 3, 3), ate[:, 16:19],
+                        ate[:, 19], ate[:, 20:23], ate[:, 23])
+
+    def _t(self, who, name, t, dtype, numel, exact=True):
+        import torch
+        dev = torch.device("cuda", self.ctx.device)
+        if (not t.is_cuda) or t.device != dev or t.dtype != dtype or not t.is_contiguous() or (t.numel() != numel if exact else t.numel() < numel):
+            raise ValueError(f"{who}: {name} must be a contiguous CUDA tensor {dtype} of {'' if exact else 'at least '}{numel} elements on the "
+                             "context's device")
+        return t
+
+    def _inputs(self, who, est, n, gt, valid, log):
+        import torch
+        cap = self.node_capacity
+        self._t(who, "est", est, torch.float64, 12 * self.B * cap)
+        self._t(who, "n", n, torch.int32, 1, exact=False)
+        self._t(who, "gt", gt, torch.float64, self.gt_cols * cap)
+        if valid is not None:
+            self._t(who, "valid", valid, torch.bool if valid.dtype == torch.bool else torch.uint8, cap)
+        rec = None
+        if log is not None:
+            if log.ctx is not self.ctx:
+                raise ValueError(f"{who}: the closure log and the evaluation must share one context (one stream)")
+            if self.edge_capacity < 1 or self.edge_capacity > log.edge_capacity:        # the rows [0, edge_capacity) of the log must exist
+                raise ValueError(f"{who}: edge_capacity must lie between 1 and the log's edge_capacity")
+            rec = _lib.PoseGraphBuffers(*(C.c_void_p(getattr(log, nm).data_ptr()) for nm in log.NAMES))
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        return p(est), p(n), p(gt), p(valid), rec
+
+    def run_torch(self, est, n, gt, valid=None, log=None, out: dict | None = None, optional=("err", "seg_end", "edge_err")) -> TrajEval:
+        """Device form (pr_trajeval_run_dev).  n i32 [>= 1] whose word 0 is the row count (a KeyframeMap's .state); valid bool | u8
+        [node_capacity] or None; log a PoseGraph whose logged closures are evaluated, or None.  out: a dict name -> preallocated tensor
+        (shapes()); the statistics blocks are allocated when absent, the arrays named in `optional` too ("centres", "prefix" may be
+        added), the others stay NULL.  Returns TrajEval.  Nothing synchronises; nothing is allocated when `out` holds every array wanted."""
+        import torch
+        who = "TrajectoryEval.run_torch"
+        pe, pn, pg, pv, rec = self._inputs(who, est, n, gt, valid, log)
+        dev = torch.device("cuda", self.ctx.device)
+        out = dict(out or {})
+        got = {}
+        for name, (shape, dt) in self.shapes(log is not None).items():
+            tdt = torch.int32 if dt == np.int32 else torch.float64
+            if name in out:
+                got[name] = self._t(who, name, out[name], tdt, int(np.prod(shape)))
+            elif name in ("ate", "rpe", "seg", "clo") or name in optional:
+                got[name] = torch.empty(shape, dtype=tdt, device=dev)
+        o = _lib.TrajEvalOut(*(C.c_void_p(got[nm].data_ptr()) if nm in got else None for nm in self.NAMES))
+        self.ctx.check(self.lib.pr_trajeval_run_dev(self.h, pe, pn, pg, pv, C.byref(rec) if rec is not None else None, C.byref(o)))
+        return TrajEval(*(got.get(nm) for nm in self.NAMES))
+
+    def run_map(self, km, gt, poses=None, **kw) -> TrajEval:
+        """run_torch for a KeyframeMap: its .state as the count and its .poses - or `poses` [node_capacity, 12], e.g. the out of
+        PoseGraph.relax_torch - as the estimate (B = 1).  The map must live on this handle's context."""
+        if km.ctx is not self.ctx:
+            raise ValueError("TrajectoryEval.run_map: the evaluation and the map must share one context (one stream)")
+        if km.keyframe_capacity != self.node_capacity or self.B != 1:
+            raise ValueError("TrajectoryEval.run_map: node_capacity must equal the map's keyframe_capacity and B must be 1")
+        return self.run_torch(km.poses if poses is None else poses, km.state, gt, **kw)
+
+    def run(self, est, n, gt, valid=None, log=None, optional=("err", "seg_end", "edge_err", "centres", "prefix")) -> TrajEval:
+        """Host form (pr_trajeval_run; synchronises): inputs as for run_torch (device tensors); returns TrajEval of NumPy arrays."""
+        who = "TrajectoryEval.run"
+        pe, pn, pg, pv, rec = self._inputs(who, est, n, gt, valid, log)
+        got = {name: np.empty(shape, dt) for name, (shape, dt) in self.shapes(log is not None).items()
+               if name in ("ate", "rpe", "seg", "clo") or name in optional}
+        o = _lib.TrajEvalOut(*(_ptr(got[nm]) if nm in got else None for nm in self.NAMES))
+        self.ctx.check(self.lib.pr_trajeval_run(self.h, pe, pn, pg, pv, C.byref(rec) if rec is not None else None, C.byref(o)))
+        return TrajEval(*(got.get(nm) for nm in self.NAMES))
+
+    def close(self):
+        if getattr(self, "h", None) and getattr(self.ctx, "h", None):
+            self.lib.pr_trajeval_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class SequenceFilter:
     """pr_seqmatch: the online form of the sequence matcher - a ring of the last L fused score rows of a drive.  Every
     keyframe, push_torch takes the distance rows an OnlineDatabase / OnlineSet match wrote (rows=) and the database's .state, fuses them

@@ -205,6 +205,23 @@ def load_robotcar_ground_truth(run_dir: str) -> np.ndarray:
     return _load(os.path.join(run_dir, "gps.txt"))[ids]
 
 
+def load_pose_history(seq_dir: str):
+    """poses_history_file.txt of a sequence: (ids int64 [m], poses float64 [m, 12]).  Column 0 is the frame id, columns 1 .. 12 a
+    world-to-camera [R | t], row-major - the rows api.TrajectoryEval takes as the estimate."""
+    import os
+    a = _load(os.path.join(seq_dir, "poses_history_file.txt"))
+    return a[:, 0].astype(np.int64), np.ascontiguousarray(a[:, 1:13])
+
+
+def load_kitti_gt_poses(seq_dir: str, ids=None) -> np.ndarray:
+    """KITTI's gt.txt rows (camera to world, row-major 3 x 4: api.TrajectoryEval's gt_kind "c2w") of the poses that became clouds - rows
+    `incoming_id` as in load_kitti_ground_truth - or of the frame ids given.  Rows are matched by index, never by time."""
+    import os
+    if ids is None:
+        ids = _load(os.path.join(seq_dir, "incoming_id_file.txt")).astype(np.int64).ravel()
+    return np.ascontiguousarray(_load(os.path.join(seq_dir, "gt.txt"))[np.asarray(ids, np.int64)])
+
+
 def run_kitti(seq_dir: str, type_: str, hist=None, ctx=None):
     """run_kitti of test_kitti.m:17-29: a sequence against itself, mask_width 100, loop_diff 10 m.  `hist` defaults to
     `<seq_dir>/history_<type>.txt` (or .bin).  Returns (AUC, top_recall, lp_detected)."""
