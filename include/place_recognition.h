@@ -1729,6 +1729,88 @@ int pr_trajeval_run(pr_trajeval* te, const double* d_est, const int32_t* d_n, co
 size_t pr_trajeval_scratch_bytes(const pr_trajeval_params* params);
 void pr_trajeval_destroy(pr_trajeval* te);
 
+/* ---- pose-proximity loop-closure candidates (proximity.hip) -----------------------------------------------------------------
+ * The appearance matchers propose closures from signatures; a pr_proximity proposes them from the poses: for every query row the EARLIER
+ * keyframes whose camera centre lies within a radius that grows with the path driven between the two rows (drift) and whose viewing axis
+ * agrees, one per bucket of `stride` rows (one per earlier pass of the place), the k nearest of those - with the seed T0 and the pair
+ * lists pr_icp_pairs_dev takes, so that search -> pr_icp_pairs_dev (the map's CSR on both sides) -> pr_verify_select_dev ->
+ * pr_posegraphb_add_dev is a chain on one stream.  Pairs the closure log already holds are marked KNOWN and switched off.
+ *
+ *   pr_proximity_create      node_capacity 1 .. 2^20, k_max 1 .. 32, query_capacity >= 1 with query_capacity x k_max <= 65535
+ *                            (pr_icp_pairs_dev's slot limit: one search feeds one ICP call).  ONE allocation; no later call allocates:
+ *                            centres and axes 24 node_capacity each, path length 8 node_capacity, validity 4 node_capacity, the runs'
+ *                            lists 8 P and 4 P with P = query_capacity k_max runs, the staging of the host form 4 QK + 8 QK + 96 QK +
+ *                            4 QK + 4 QK + QK + 16 with QK = query_capacity k_max, each part rounded up to 16.  runs = 1 when
+ *                            ceil(query_capacity / rows) >= 128, else min(16, ceil(node_capacity / cols)), (rows, cols) =
+ *                            pr_proximity_tile.  pr_proximity_scratch_bytes returns the sum (0 for sizes create refuses).
+ *   pr_proximity_tile        the search kernel's tile: rows query rows per workgroup, cols DB rows per slab.
+ *   pr_proximity_search_dev  4 launches on the context's stream.  d_poses [node_capacity][12] f64 (pr_map_buffers.poses), d_n i32 [>= 1]
+ *                            (pr_map_buffers.state), d_qrange i32 [2] = {q0, mq}; log = the closure log or NULL, log_edge_capacity its
+ *                            edge_capacity (0 .. 2^20).  Outputs: d_idx i32, d_d2 f64 [query_capacity][k]; d_T0 f64 [query_capacity k][12];
+ *                            d_pair_src, d_pair_dst i32, d_known u8 [query_capacity k] (d_known may be NULL without a log); d_info i32
+ *                            [4] = {rows searched, slots filled, slots known, flags}.  Every grid depends on the create sizes only;
+ *                            d_n, d_qrange and the log's count are read on the device: one capture made at n = 0 serves every count
+ *                            and every query range.  No floating-point atomics; two runs give the same bytes.
+ *   pr_proximity_search      the same with HOST outputs (d_poses, d_n, d_qrange and the log stay device memory); synchronises.
+ *
+ * The rule (restated operation by operation in tests/proximity_np.py; the device equals it bit for bit).  A pose is a world-to-camera row
+ * [R | t]; a 3 x 3 product entry is (a0 b0 + a1 b1) + a2 b2, the translation of a product ((r0 t0 + r1 t1) + r2 t2) + t_A, the translation
+ * of an inverse -((R0a t0 + R1a t1) + R2a t2); everything is fp64 without contraction.
+ *  0. n = d_n[0] clamped into 0 .. node_capacity before any address is formed; q0 = d_qrange[0], mq = d_qrange[1] clamped into
+ *     0 .. query_capacity.  Output row r stands for query row q = q0 + r (64 bits).  A row is VALID iff it is < n and its 12 entries are
+ *     finite.  Row r is SEARCHED iff r < mq, 0 <= q < n and row q is valid.  PR_PROXIMITY_QRANGE_CLAMPED iff d_qrange[1] was clamped or
+ *     some r < mq has q outside 0 .. n - 1.
+ *  1. Per valid row: centre c_i = -(R^T t), viewing axis a_i = (R[2][0], R[2][1], R[2][2]).
+ *  2. Path length s[i] over the valid rows, as pr_trajeval forms dist: the first valid row and every invalid row add nothing, a valid
+ *     row adds |c_i - c_prev valid| = sqrt((x x + y y) + z z); BLOCKED order: 256 blocks of C = ceil(node_capacity / 256) rows, a running
+ *     sum from +0.0 inside a block, the blocks' totals summed in block order, s = base of the block + running sum.
+ *  3. DB row i is a CANDIDATE of q iff both rows are valid, i + min_gap <= q, d2 < rad rad (strict) with dx = c_i - c_q,
+ *     d2 = (dx0 dx0 + dx1 dx1) + dx2 dx2, rad = radius + growth (s[q] - s[i]) replaced by radius_max unless rad < radius_max (a NaN too),
+ *     and, when cos_min > -1, (a_i0 a_q0 + a_i1 a_q1) + a_i2 a_q2 >= cos_min (cos_min == -1 forms no dot product).
+ *  4. Bucket b = i / stride.  A bucket's representative is its candidate of smallest d2, the lowest i on a tie.  The row's result is the
+ *     k representatives of smallest d2 (lowest i on a tie), ascending, in slots 0 ..; the other slots hold idx = -1, d2 = +Inf.
+ *  5. A filled slot with i = idx gets T0 = P_i P_q^-1 (query-camera points into DB row i's camera frame: verify's T, the log's Z_ij),
+ *     pair_src = q, pair_dst = i.  With a log: E = log.state[0] clamped into 0 .. log_edge_capacity; the slot is KNOWN iff some edge
+ *     a < E has both indices >= 0 and, with lo = min(i_a, j_a), hi = max(i_a, j_a), |lo - i| <= known_window and |hi - q| <=
+ *     known_window.  A KNOWN slot keeps idx and d2 but gets pair_src = pair_dst = -1, T0 = identity, known = 1 (pr_icp_pairs_dev answers
+ *     PR_ICP_NO_PAIR: nothing is logged twice).  An empty slot, and every slot of a row that is not searched, is
+ *     -1 / +Inf / identity / -1 / -1 / 0.
+ *  6. EVERY entry of the outputs' extents above is written, nothing beyond them.
+ * PR_EINVAL (text: pr_last_error) before any device is touched: a NULL handle, params or required pointer ("pr_proximity_search_dev: a
+ * required pointer is NULL ..."), sizes outside the limits above, radius not finite and positive, growth negative or not finite,
+ * radius_max not finite or below radius, cos_min outside -1 .. 1, min_gap < 1, stride < 1, k outside 1 .. k_max, known_window < 0,
+ * log_edge_capacity outside 0 .. 2^20, a log with a NULL buffer or without d_known. */
+typedef struct pr_proximity pr_proximity;
+typedef struct pr_proximity_params {
+  double radius, growth, radius_max, cos_min;
+  int32_t min_gap, stride, k, known_window;
+} pr_proximity_params;
+enum { PR_PROXIMITY_QRANGE_CLAMPED = 1 };
+int pr_proximity_create(pr_ctx* ctx, int32_t node_capacity, int32_t query_capacity, int32_t k_max, pr_proximity** out);
+void pr_proximity_destroy(pr_proximity* px);
+int64_t pr_proximity_scratch_bytes(int32_t node_capacity, int32_t query_capacity, int32_t k_max);
+void pr_proximity_tile(int32_t* rows, int32_t* cols);
+int pr_proximity_search_dev(pr_proximity* px, const double* d_poses, const int32_t* d_n, const int32_t* d_qrange, const pr_proximity_params* params,
+                            const pr_posegraph_buffers* log, int32_t log_edge_capacity, int32_t* d_idx, double* d_d2, double* d_T0,
+                            int32_t* d_pair_src, int32_t* d_pair_dst, uint8_t* d_known, int32_t* d_info);
+int pr_proximity_search(pr_proximity* px, const double* d_poses, const int32_t* d_n, const int32_t* d_qrange, const pr_proximity_params* params,
+                        const pr_posegraph_buffers* log, int32_t log_edge_capacity, int32_t* idx, double* d2, double* T0, int32_t* pair_src,
+                        int32_t* pair_dst, uint8_t* known, int32_t* info);
+
+/* The batch add of the closure log (posegraph_batch.hpp, compiled into posegraph.hip): slot p = 0 .. c - 1 carries its own rows, so the pair lists of a pr_proximity search
+ * (d_pair_dst as d_i, d_pair_src as d_j) are logged by ONE call.  Slot p is logged iff accepted[p] != 0, d_i[p] >= 0, d_j[p] >= 0,
+ * d_i[p] != d_j[p], the 12 entries of T[p] are finite and its weights - d_w[p] = (w_rot, w_trans), or the host pair when d_w == NULL - are
+ * finite and >= 0; a logged slot stores (d_i[p], d_j[p]), T[p] and its weights at row `edges`, in the order of p.  Overflow, the
+ * clamping of a scribbled state[0], info = {logged by this call, first row or -1, edges after, flags} and PR_POSEGRAPH_OVERFLOW are
+ * pr_posegraph_add_dev's: the call leaves the bytes that c calls of pr_posegraphw_add_dev (k = 1) with query_row = d_j[p] leave (so state is
+ * rewritten only if some d_j[p] >= 0).  One workgroup, ascending chunks with an integer scan; capturable; the device form allocates
+ * nothing.  The host form stages c slots in an allocation of its own for the call and synchronises.  PR_EINVAL: c outside 1 .. 65535,
+ * a negative or non-finite w_rot / w_trans, a NULL handle or required pointer. */
+int pr_posegraphb_add_dev(pr_posegraph* g, const int32_t* d_i, const int32_t* d_j, const double* d_T, const uint8_t* d_accepted,
+                          const double* d_w, double w_rot, double w_trans, int32_t c, int32_t* d_info);
+int pr_posegraphb_add(pr_posegraph* g, const int32_t* i, const int32_t* j, const double* T, const uint8_t* accepted, const double* w, double w_rot,
+                      double w_trans, int32_t c, int32_t* info);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1845,6 +1845,44 @@ class PoseGraph:
         self.ctx.check(self.lib.pr_posegraphw_add(self.h, _ptr(i), _ptr(t), _ptr(a), int(query_row), k, _ptr(ww), _ptr(info)))
         return info
 
+    def add_batch_torch(self, i, j, T, accepted, w=None, w_rot: float = 1.0, w_trans: float = 1.0, info=None):
+        """Device form (pr_posegraphb_add_dev): c slots that carry their own rows - i i32 [c] the DB rows, j i32 [c] the query rows (a
+        ProximitySearch's pair_dst and pair_src), T f64 [c, 3, 4], accepted bool | u8 [c], w f64 [c, 2] or None (then w_rot, w_trans for
+        every slot).  Slot p is logged iff accepted, i >= 0, j >= 0, i != j, T finite and its weights finite and >= 0, in the order of p:
+        what c calls of add_weighted_torch with one slot each leave.  Returns info (device i32 [4]); nothing synchronises, nothing is
+        allocated when info= is given."""
+        import torch
+        who = "PoseGraph.add_batch_torch"
+        c = i.numel()
+        self._dev(i, torch.int32, c, who, "i must be a contiguous CUDA tensor i32 [c]")
+        self._dev(j, torch.int32, c, who, "j must be a contiguous CUDA tensor i32 [c]")
+        self._dev(T, torch.float64, 12 * c, who, "T must be a contiguous CUDA tensor f64 [c, 3, 4]")
+        self._dev(accepted, torch.bool if accepted.dtype == torch.bool else torch.uint8, c, who,
+                  "accepted must be a contiguous CUDA tensor bool or u8 [c]")
+        if w is not None:
+            self._dev(w, torch.float64, 2 * c, who, "w must be a contiguous CUDA tensor f64 [c, 2]")
+        if info is None:
+            info = torch.empty(4, dtype=torch.int32, device=i.device)
+        else:
+            self._dev(info, torch.int32, 4, who, "info must be a CUDA tensor i32 [4]")
+        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        self.ctx.check(self.lib.pr_posegraphb_add_dev(self.h, p(i), p(j), p(T), p(accepted), p(w), float(w_rot), float(w_trans), c, p(info)))
+        return info
+
+    def add_batch(self, i, j, T, accepted, w=None, w_rot: float = 1.0, w_trans: float = 1.0):
+        """Host form (pr_posegraphb_add; synchronises): numpy arrays of the same meaning.  Returns info int32 [4]."""
+        ii = np.ascontiguousarray(i, np.int32).reshape(-1)
+        jj = np.ascontiguousarray(j, np.int32).reshape(-1)
+        c = len(ii)
+        t = np.ascontiguousarray(T, np.float64).reshape(-1)
+        a = np.ascontiguousarray(accepted, np.uint8).reshape(-1)
+        ww = None if w is None else np.ascontiguousarray(w, np.float64).reshape(-1)
+        if len(jj) != c or len(t) != 12 * c or len(a) != c or (ww is not None and len(ww) != 2 * c):
+            raise ValueError("PoseGraph.add_batch: i [c], j [c], T [c, 3, 4], accepted [c], w [c, 2]")
+        info = np.empty(4, np.int32)
+        self.ctx.check(self.lib.pr_posegraphb_add(self.h, _ptr(ii), _ptr(jj), _ptr(t), _ptr(a), _ptr(ww), float(w_rot), float(w_trans), c, _ptr(info)))
+        return info
+
     def relax_torch(self, poses, n, outer: int = 5, inner: int = 64, lam: float = 1e-9, w_odo_rot: float = 1.0, w_odo_trans: float = 1.0,
                     out=None, report=None):
         """Device form (pr_posegraph_relax_dev): poses f64 [node_capacity, 12] (world to camera), n i32 [>= 1] whose word 0 is the node
@@ -2160,6 +2198,163 @@ class TrajectoryEval:
     def close(self):
         if getattr(self, "h", None) and getattr(self.ctx, "h", None):
             self.lib.pr_trajeval_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Proximity(NamedTuple):
+    """The outputs of a ProximitySearch search: idx i32, d2 f64 [query_capacity, k]; T0 f64 [query_capacity k, 3, 4]; pair_src, pair_dst
+    i32 and known u8 [query_capacity k]; info i32 [4] = rows searched, slots filled, slots known, flags."""
+    idx: object
+    d2: object
+    T0: object
+    pair_src: object
+    pair_dst: object
+    known: object
+    info: object
+
+
+class ProximitySearch:
+    """pr_proximity: loop-closure candidates from the poses - for every query row q0 + r the earlier keyframes within
+    radius + growth x (path between the rows), capped at radius_max, that look the same way (cos_min), one per bucket of `stride` rows,
+    the k nearest - with the seeds and pair lists of verify_map_torch and PoseGraph.add_batch_torch.  Calls are enqueued on the context's
+    stream, read n, qrange and the log's count on the device and allocate no device scratch: ONE captured search_torch serves every
+    count and every query range.  The rule is in include/place_recognition.h."""
+
+    def __init__(self, ctx: Context | None, node_capacity: int, query_capacity: int, k_max: int):
+        self.h = None
+        self.ctx = ctx or default_context()
+        self.lib = self.ctx.lib
+        self.node_capacity, self.query_capacity, self.k_max = int(node_capacity), int(query_capacity), int(k_max)
+        self.last_verify = None
+        h = C.c_void_p()
+        self.ctx.check(self.lib.pr_proximity_create(self.ctx.h, self.node_capacity, self.query_capacity, self.k_max, C.byref(h)))
+        self.h = h
+
+    def scratch_bytes(self) -> int:
+        return int(self.lib.pr_proximity_scratch_bytes(self.node_capacity, self.query_capacity, self.k_max))
+
+    @staticmethod
+    def tile():
+        """(rows, cols) of the search kernel's tile (pr_proximity_tile)."""
+        r, c = C.c_int32(), C.c_int32()
+        _lib.load().pr_proximity_tile(C.byref(r), C.byref(c))
+        return int(r.value), int(c.value)
+
+    def _t(self, who, name, t, dtype, numel, exact=True):
+        import torch
+        dev = torch.device("cuda", self.ctx.device)
+        if (not t.is_cuda) or t.device != dev or t.dtype != dtype or not t.is_contiguous() or (t.numel() != numel if exact else t.numel() < numel):
+            raise ValueError(f"{who}: {name} must be a contiguous CUDA tensor {dtype} of {'' if exact else 'at least '}{numel} elements on the "
+                             "context's device")
+        return t
+
+    def shapes(self, k: int):
+        Q = self.query_capacity
+        return dict(idx=((Q, k), np.int32), d2=((Q, k), np.float64), T0=((Q * k, 3, 4), np.float64), pair_src=((Q * k,), np.int32),
+                    pair_dst=((Q * k,), np.int32), known=((Q * k,), np.uint8), info=((4,), np.int32))
+
+    def _args(self, who, poses, n, qrange, radius, growth, radius_max, cos_min, min_gap, stride, k, log, known_window):
+        import torch
+        self._t(who, "poses", poses, torch.float64, 12 * self.node_capacity)
+        self._t(who, "n", n, torch.int32, 1, exact=False)
+        self._t(who, "qrange", qrange, torch.int32, 2)
+        k = int(k)
+        if k < 1 or k > self.k_max:
+            raise ValueError(f"{who}: k must lie in 1 .. k_max")
+        rec, ec = None, 0
+        if log is not None:
+            if log.ctx is not self.ctx:
+                raise ValueError(f"{who}: the closure log and the search must share one context (one stream)")
+            rec = _lib.PoseGraphBuffers(*(C.c_void_p(getattr(log, nm).data_ptr()) for nm in log.NAMES))
+            ec = log.edge_capacity
+        prm = _lib.ProximityParams(float(radius), float(growth), float(radius if radius_max is None else radius_max), float(cos_min), int(min_gap),
+                                   int(stride), k, int(known_window))
+        return k, prm, rec, ec
+
+    def search_torch(self, poses, n, qrange, *, radius, growth=0.0, radius_max=None, cos_min=-1.0, min_gap, stride=1, k=1, log=None,
+                     known_window=0, out=None) -> Proximity:
+        """Device form (pr_proximity_search_dev): poses f64 [node_capacity, 12] and n i32 [>= 1] - a KeyframeMap's .poses and .state - and
+        qrange i32 [2] = (q0, mq): output row r stands for query row q0 + r, r < mq.  radius_max None: radius.  log: a PoseGraph whose
+        logged pairs (within known_window rows at both ends) come back known = 1 and switched off.  out: the Proximity an earlier call
+        returned for the same k (fixed addresses: what a captured graph needs).  Nothing synchronises; nothing is allocated with out=."""
+        import torch
+        who = "ProximitySearch.search_torch"
+        k, prm, rec, ec = self._args(who, poses, n, qrange, radius, growth, radius_max, cos_min, min_gap, stride, k, log, known_window)
+        dev = torch.device("cuda", self.ctx.device)
+        got = {}
+        for name, (shape, dt) in self.shapes(k).items():
+            tdt = {np.int32: torch.int32, np.float64: torch.float64, np.uint8: torch.uint8}[dt]
+            if out is not None:
+                got[name] = self._t(who, name, getattr(out, name), tdt, int(np.prod(shape)))
+            else:
+                got[name] = torch.empty(shape, dtype=tdt, device=dev)
+        p = lambda t: C.c_void_p(t.data_ptr())
+        self.ctx.check(self.lib.pr_proximity_search_dev(self.h, p(poses), p(n), p(qrange), C.byref(prm), C.byref(rec) if rec is not None else None,
+                                                        ec, *(p(got[nm]) for nm in Proximity._fields)))
+        return Proximity(*(got[nm] for nm in Proximity._fields))
+
+    def _map(self, who, km):
+        if km.ctx is not self.ctx:
+            raise ValueError(f"{who}: the search and the map must share one context (one stream)")
+        if km.keyframe_capacity != self.node_capacity:
+            raise ValueError(f"{who}: node_capacity must equal the map's keyframe_capacity")
+
+    def search_map(self, km, qrange, **kw) -> Proximity:
+        """search_torch(km.poses, km.state, qrange, ...) for a KeyframeMap on this handle's context with node_capacity keyframes; anything
+        else is refused before the library is called."""
+        self._map("ProximitySearch.search_map", km)
+        return self.search_torch(km.poses, km.state, qrange, **kw)
+
+    def search(self, poses, n, qrange, *, radius, growth=0.0, radius_max=None, cos_min=-1.0, min_gap, stride=1, k=1, log=None,
+               known_window=0) -> Proximity:
+        """Host form (pr_proximity_search; synchronises): inputs as for search_torch (device tensors); returns Proximity of NumPy arrays."""
+        who = "ProximitySearch.search"
+        k, prm, rec, ec = self._args(who, poses, n, qrange, radius, growth, radius_max, cos_min, min_gap, stride, k, log, known_window)
+        got = {name: np.empty(shape, dt) for name, (shape, dt) in self.shapes(k).items()}
+        p = lambda t: C.c_void_p(t.data_ptr())
+        self.ctx.check(self.lib.pr_proximity_search(self.h, p(poses), p(n), p(qrange), C.byref(prm), C.byref(rec) if rec is not None else None, ec,
+                                                    *(_ptr(got[nm]) for nm in Proximity._fields)))
+        return Proximity(*(got[nm] for nm in Proximity._fields))
+
+    def verify_map_torch(self, km, cand: Proximity, max_src_pts: int, *, max_iter: int = 30, max_corr: float = 1.0, min_fitness: float = 0.5,
+                         max_rmse: float = 0.5, tol_rmse: float = 1e-6, tol_fitness: float = 1e-6, min_inliers: int = 3, search=None, out=None):
+        """The candidates of a search refined and judged on the stream: pr_icp_pairs_dev with the map's own CSR on BOTH sides (N =
+        keyframe_capacity: cloud pair_src onto cloud pair_dst from T0; a slot switched off answers ICP_NO_PAIR), then
+        pr_verify_select_dev with one hypothesis - verify's accept rule.  Returns (T f64 [c, 3, 4], stats u8 [c, 32], accepted bool [c]), c =
+        query_capacity k: what PoseGraph.add_batch_torch(cand.pair_dst, cand.pair_src, T, accepted) logs.  out: the dict an earlier call
+        left in .last_verify for the same c (fixed addresses for a capture)."""
+        import torch
+        who = "ProximitySearch.verify_map_torch"
+        self._map(who, km)
+        c = cand.pair_src.numel()
+        dev = cand.pair_src.device
+        if out is None:
+            out = dict(refine=(torch.empty((c, 3, 4), dtype=torch.float64, device=dev), torch.zeros((c, ICP_STATS.itemsize), dtype=torch.uint8, device=dev)),
+                       T=torch.empty((c, 3, 4), dtype=torch.float64, device=dev), stats=torch.empty((c, ICP_STATS.itemsize), dtype=torch.uint8, device=dev),
+                       accepted=torch.empty(c, dtype=torch.bool, device=dev), hyp=torch.empty(c, dtype=torch.int32, device=dev))
+            torch.cuda.synchronize(dev)                   # torch's fill (its stream) before the library's stream writes the buffers
+        elif out["T"].shape != (c, 3, 4):
+            raise ValueError(f"{who}: out belongs to another c")
+        p = lambda t: C.c_void_p(t.data_ptr())
+        N = km.keyframe_capacity
+        with icp_search(self.ctx, search):
+            self.ctx.check(self.lib.pr_icp_pairs_dev(self.ctx.h, p(km.xyz), p(km.offs), N, p(km.xyz), p(km.offs), N, p(cand.pair_src), p(cand.pair_dst),
+                                                     c, p(cand.T0), int(max_src_pts), int(km.max_cloud_points), int(max_iter), float(max_corr),
+                                                     float(tol_rmse), float(tol_fitness), int(min_inliers), p(out["refine"][0]), p(out["refine"][1])))
+        self.ctx.check(self.lib.pr_verify_select_dev(self.ctx.h, p(out["refine"][0]), p(out["refine"][1]), c, 1, float(min_fitness), float(max_rmse),
+                                                     p(out["T"]), p(out["stats"]), p(out["accepted"]), p(out["hyp"])))
+        self.last_verify = out
+        return out["T"], out["stats"], out["accepted"]
+
+    def close(self):
+        if getattr(self, "h", None) and getattr(self.ctx, "h", None):
+            self.lib.pr_proximity_destroy(self.h)
         self.h = None
 
     def __del__(self):

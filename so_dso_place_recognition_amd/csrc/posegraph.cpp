@@ -32,6 +32,7 @@ namespace {
 using pr::fail;
 
 constexpr int32_t MAX_NODES = 1 << 20, MAX_EDGES = 1 << 20, MAX_OUTER = 64, MAX_INNER = 1 << 16;
+constexpr int32_t MAX_BATCH = 65535;          // most slots of one batch add: pr_icp_pairs_dev's slot limit
 
 bool weight_ok(double w) { return std::isfinite(w) && w >= 0.0; }
 
@@ -197,6 +198,56 @@ int pr_posegraphw_add(pr_posegraph* g, const int32_t* idx, const double* T, cons
   if (e == hipSuccess) rc = pr_posegraphw_add_dev(g, g->stage_idx, g->stage_T, g->stage_acc, g->stage_row, k, g->stage_w, g->stage_info);
   if (e == hipSuccess && rc == PR_OK) e = hipMemcpyAsync(info, g->stage_info, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, st);
   const hipError_t e2 = hipStreamSynchronize(st);     // the host arrays are in flight until here
+  if (rc != PR_OK) return rc;
+  PR_CHECK_HIP(ctx, e);
+  PR_CHECK_HIP(ctx, e2);
+  return PR_OK;
+}
+
+int pr_posegraphb_add_dev(pr_posegraph* g, const int32_t* d_i, const int32_t* d_j, const double* d_T, const uint8_t* d_accepted, const double* d_w,
+                          double w_rot, double w_trans, int32_t c, int32_t* d_info) {
+  pr_ctx* ctx = g ? g->ctx : nullptr;
+  if (c < 1 || c > MAX_BATCH) return fail(ctx, PR_EINVAL, "pr_posegraphb_add_dev: c=%d outside 1 .. %d", c, MAX_BATCH);
+  if (!weight_ok(w_rot)) return fail(ctx, PR_EINVAL, "pr_posegraphb_add_dev: w_rot is negative or not finite");
+  if (!weight_ok(w_trans)) return fail(ctx, PR_EINVAL, "pr_posegraphb_add_dev: w_trans is negative or not finite");
+  if (!g) return fail(nullptr, PR_EINVAL, "pr_posegraphb_add_dev: graph is NULL");
+  if (!d_i || !d_j || !d_T || !d_accepted || !d_info)
+    return fail(ctx, PR_EINVAL, "pr_posegraphb_add_dev: a required pointer is NULL (d_i, d_j, d_T, d_accepted, d_info)");
+  PR_CHECK_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
+  pr::launch_posegraph_add_batch(pr::ctx_stream(ctx), g->v, d_i, d_j, d_T, d_accepted, d_w, w_rot, w_trans, c, d_info);
+  PR_CHECK_HIP(ctx, hipGetLastError());
+  return PR_OK;
+}
+
+// the host form stages c slots, more than the create-time staging of the single adds holds: it allocates for the call and frees behind
+// its synchronise (the device form allocates nothing)
+int pr_posegraphb_add(pr_posegraph* g, const int32_t* i, const int32_t* j, const double* T, const uint8_t* accepted, const double* w, double w_rot,
+                      double w_trans, int32_t c, int32_t* info) {
+  pr_ctx* ctx = g ? g->ctx : nullptr;
+  if (c < 1 || c > MAX_BATCH) return fail(ctx, PR_EINVAL, "pr_posegraphb_add: c=%d outside 1 .. %d", c, MAX_BATCH);
+  if (!weight_ok(w_rot)) return fail(ctx, PR_EINVAL, "pr_posegraphb_add: w_rot is negative or not finite");
+  if (!weight_ok(w_trans)) return fail(ctx, PR_EINVAL, "pr_posegraphb_add: w_trans is negative or not finite");
+  if (!g) return fail(nullptr, PR_EINVAL, "pr_posegraphb_add: graph is NULL");
+  if (!i || !j || !T || !accepted || !info) return fail(ctx, PR_EINVAL, "pr_posegraphb_add: a required pointer is NULL (i, j, T, accepted, info)");
+  PR_CHECK_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
+  hipStream_t st = pr::ctx_stream(ctx);
+  const size_t C = (size_t)c, o_T = 0, o_w = o_T + C * 96, o_i = o_w + C * 16, o_j = o_i + C * 4, o_info = o_j + C * 4, o_acc = o_info + 16;
+  char* b = nullptr;
+  hipError_t e = hipMalloc(reinterpret_cast<void**>(&b), o_acc + C);
+  if (e != hipSuccess) return fail(ctx, e == hipErrorOutOfMemory ? PR_ENOMEM : PR_EHIP, "pr_posegraphb_add: staging: %s", hipGetErrorString(e));
+  e = hipMemcpyAsync(b + o_T, T, C * 96, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess && w) e = hipMemcpyAsync(b + o_w, w, C * 16, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(b + o_i, i, C * 4, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(b + o_j, j, C * 4, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(b + o_acc, accepted, C, hipMemcpyHostToDevice, st);
+  int rc = PR_OK;
+  if (e == hipSuccess)
+    rc = pr_posegraphb_add_dev(g, reinterpret_cast<int32_t*>(b + o_i), reinterpret_cast<int32_t*>(b + o_j), reinterpret_cast<double*>(b + o_T),
+                               reinterpret_cast<uint8_t*>(b + o_acc), w ? reinterpret_cast<double*>(b + o_w) : nullptr, w_rot, w_trans, c,
+                               reinterpret_cast<int32_t*>(b + o_info));
+  if (e == hipSuccess && rc == PR_OK) e = hipMemcpyAsync(info, b + o_info, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, st);
+  const hipError_t e2 = hipStreamSynchronize(st);     // the host arrays are in flight until here
+  (void)hipFree(b);
   if (rc != PR_OK) return rc;
   PR_CHECK_HIP(ctx, e);
   PR_CHECK_HIP(ctx, e2);

@@ -102,6 +102,8 @@ __global__ __launch_bounds__(128) void posegraph_add_weighted_kernel(PoseGraphVi
   }
 }
 
+#include "posegraph_batch.hpp"                                   // posegraph_add_batch_kernel (pr_posegraphb_add_dev)
+
 // ------------------------------------------------------------------------------------------------ 3 x 3 helpers (row-major)
 __device__ __forceinline__ void mul33(const double* A, const double* B, double* C) {
 #pragma unroll
@@ -553,6 +555,11 @@ void launch_posegraph_add(hipStream_t st, const PoseGraphView& v, const int* idx
 void launch_posegraph_add_weighted(hipStream_t st, const PoseGraphView& v, const int* idx, const double* T, const unsigned char* accepted,
                                    const int* query_row, int k, const double* w, int* info) {
   hipLaunchKernelGGL(posegraph_add_weighted_kernel, dim3(1), dim3(128), 0, st, v, idx, T, accepted, query_row, k, w, info);
+}
+
+void launch_posegraph_add_batch(hipStream_t st, const PoseGraphView& v, const int* i, const int* j, const double* T, const unsigned char* accepted,
+                                const double* w, double w_rot, double w_trans, int c, int* info) {
+  hipLaunchKernelGGL(posegraph_add_batch_kernel, dim3(1), dim3(256), 0, st, v, i, j, T, accepted, w, w_rot, w_trans, c, info);
 }
 
 void launch_posegraph_relax(hipStream_t st, const PoseGraphView& v, const double* poses_in, const int* n, const PoseGraphParams& prm,

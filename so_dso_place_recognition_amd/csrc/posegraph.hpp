@@ -37,6 +37,9 @@ void launch_posegraph_add(hipStream_t st, const PoseGraphView& v, const int* idx
 // the add with per-slot weights w [k][2] in device memory
 void launch_posegraph_add_weighted(hipStream_t st, const PoseGraphView& v, const int* idx, const double* T, const unsigned char* accepted,
                                    const int* query_row, int k, const double* w, int* info);
+// the batch add: rows (i[p], j[p]) per slot, weights w [c][2] in device memory or, with w == NULL, the pair (w_rot, w_trans); c <= 65535
+void launch_posegraph_add_batch(hipStream_t st, const PoseGraphView& v, const int* i, const int* j, const double* T, const unsigned char* accepted,
+                                const double* w, double w_rot, double w_trans, int c, int* info);
 void launch_posegraph_relax(hipStream_t st, const PoseGraphView& v, const double* poses_in, const int* n, const PoseGraphParams& prm,
                             double* poses_out, double* report);
 
