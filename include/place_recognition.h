@@ -1811,6 +1811,64 @@ int pr_posegraphb_add_dev(pr_posegraph* g, const int32_t* d_i, const int32_t* d_
 int pr_posegraphb_add(pr_posegraph* g, const int32_t* i, const int32_t* j, const double* T, const uint8_t* accepted, const double* w, double w_rot,
                       double w_trans, int32_t c, int32_t* info);
 
+/* ---- local submaps: several keyframes gathered into one cloud for ICP (submap.hip) -----------------------------------------
+ * Every registration between keyframes takes one keyframe cloud per side, and SO-DSO's clouds are sparse.  A pr_submap gathers, for every
+ * slot of a pair list, the clouds of the map rows centre - w .. centre + w into ONE cloud in the centre row's camera frame, with the poses
+ * the map holds (or relaxed ones).  The output is a CSR set pr_icp_pairs_dev reads as it stands (slot p is cloud p); both sides of a pair
+ * are expressed in their centre frames, so the seed T0 = P_i P_q^-1 of a pr_proximity search and the meaning of T (query camera to DB
+ * camera) do not change.  One device; no voxel de-duplication (points that several rows hold are kept); the poses are taken as given.
+ *
+ *   pr_submap_create      slot_capacity 1 .. 65535 (pr_icp_pairs_dev's slot limit), w_max 0 .. 31, point_capacity 1 .. 2^40 (rows of out_xyz),
+ *                         max_cloud_points 1 .. 2^26 and keyframe_capacity 1 .. 2^24 (the map's).  ONE allocation; no later call of the device
+ *                         form allocates: with S = slot_capacity and L = 2 w_max + 1 the entry lists 4 S L (rows) + 4 S L (starts inside the
+ *                         slot) + 4 S L (lengths) + 8 S L (source starts), per slot 4 S (total) + 4 S (flags) + 4 S (rows taken) + 8 S (base),
+ *                         each part rounded up to 16.  pr_submap_scratch_bytes returns the sum (0 for sizes create refuses).
+ *   pr_submap_build_dev   3 launches (plan, scan, gather) on the context's stream.  map: xyz and offs are read (pr_map_buffers of the resident
+ *                         map); d_poses [>= n][12] f64 world to camera, row-major [R | t]: the map's own or a relaxed array; d_n i32 [>= 1]
+ *                         (pr_map_buffers.state); d_center i32 [c] (NULL with c = 0 is fine); d_avoid i32 [c] or NULL.  CALLER-OWNED outputs: out_xyz [point_capacity][3]
+ *                         f64, out_offs [slot_capacity + 1] i64, out_rows [slot_capacity][2] i32 = {rows taken, flags}, d_info [4] i32 =
+ *                         {slots non-empty, points written as two words (low, high), flags OR-ed}.  Every grid depends on the create sizes
+ *                         only and d_n is read on the device: one capture made at n = 0 serves every count.  No read-back, no floating-point
+ *                         atomics; two runs give the same bytes.
+ *   pr_submap_build       the same with HOST center / avoid and HOST outputs (map, d_poses and d_n stay device memory); stages in an
+ *                         allocation of its own for the call and synchronises.
+ *
+ * The rule (restated in fp64 in tests/submap_np.py; the device equals it byte for byte).
+ *  0. n = d_n[0] clamped into 0 .. keyframe_capacity before any address is formed.  Slot p < c has centre = d_center[p].
+ *  1. The walk of slot p: r_0 = centre, then centre - 1, centre + 1, centre - 2, centre + 2, ... up to distance w = half_window (64-bit
+ *     row numbers).  With past_only != 0 only rows <= centre are walked.
+ *  2. Row r is ELIGIBLE iff 0 <= r < n; all 12 entries of poses[r] are finite; d_avoid is NULL or |r - avoid[p]| > avoid_gap (64-bit
+ *     integers: the difference cannot wrap; the centre is exempt); and offs[r] >= 0 with len_r = offs[r + 1] - offs[r] in
+ *     0 .. max_cloud_points.  A length outside that range counts as not eligible, and no address is formed from it.  An ineligible row is
+ *     skipped and the walk goes on.
+ *  3. An eligible row whose points would take the slot above max_pts is not taken, sets PR_SUBMAP_TRUNCATED on the slot, and ends the
+ *     walk: a submap never holds part of a cloud.  `rows taken` counts the eligible rows in front of that one (empty clouds included).
+ *  4. centre < 0 switches the slot off: it is empty and no flag is set.  centre >= n, or a centre whose pose is not finite: the slot is
+ *     empty with PR_SUBMAP_NO_CENTER.  A centre that fails only the length test is skipped like any other row.
+ *  5. Placement: the slots' lengths are scanned exclusively in slot order.  A slot whose end would pass point_capacity becomes empty
+ *     (rows taken = 0) with PR_SUBMAP_OVERFLOW, and later slots are placed behind the last one that fits: a slot is never partial.
+ *     out_offs[0 .. c] is always written, entries c + 1 .. slot_capacity are set to out_offs[c]; out_rows[p] = {0, 0} for p >= c.
+ *     Rows of out_xyz at or behind out_offs[c] are not written.  `slots non-empty` counts the slots with rows taken > 0.
+ *  6. Rows are written in walk order, and points in row order.  The centre row's points are copied bit for bit.  A point x of row
+ *     r != centre becomes y = R_c (R_r^T (x - t_r)) + t_c, in exactly this order: d = x - t_r; u_k = (R_r[0][k] d_0 + R_r[1][k] d_1) +
+ *     R_r[2][k] d_2; v_k = (R_c[k][0] u_0 + R_c[k][1] u_1) + R_c[k][2] u_2; y_k = v_k + t_c[k]; every operation rounded, no contraction.
+ *     A non-finite point goes through the same arithmetic and is written as it comes out (the ICP stage leaves it out).
+ * PR_EINVAL (text: pr_last_error) before any device is touched: a NULL handle, map record, params or required pointer, sizes outside the
+ * limits above, c outside 0 .. slot_capacity, half_window outside 0 .. w_max, max_pts < 1, avoid_gap < 0.  c = 0 is a valid empty call
+ * that still writes out_offs and d_info. */
+typedef struct pr_submap pr_submap;
+typedef struct pr_submap_params { int32_t half_window, past_only, avoid_gap, max_pts; } pr_submap_params;
+enum { PR_SUBMAP_TRUNCATED = 1, PR_SUBMAP_NO_CENTER = 2, PR_SUBMAP_OVERFLOW = 4 };
+int pr_submap_create(pr_ctx* ctx, int32_t slot_capacity, int32_t w_max, int64_t point_capacity, int32_t max_cloud_points, int32_t keyframe_capacity,
+                     pr_submap** out);
+void pr_submap_destroy(pr_submap* sm);
+int64_t pr_submap_scratch_bytes(int32_t slot_capacity, int32_t w_max);
+int pr_submap_build_dev(pr_submap* sm, const pr_map_buffers* map, const double* d_poses, const int32_t* d_n, const int32_t* d_center,
+                        const int32_t* d_avoid, int32_t c, const pr_submap_params* params, double* out_xyz, int64_t* out_offs, int32_t* out_rows,
+                        int32_t* d_info);
+int pr_submap_build(pr_submap* sm, const pr_map_buffers* map, const double* d_poses, const int32_t* d_n, const int32_t* center, const int32_t* avoid,
+                    int32_t c, const pr_submap_params* params, double* out_xyz, int64_t* out_offs, int32_t* out_rows, int32_t* info);
+
 #ifdef __cplusplus
 }
 #endif

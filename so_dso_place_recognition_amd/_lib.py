@@ -40,6 +40,7 @@ TRAJ_ALIGN_NONE, TRAJ_ALIGN_FIRST, TRAJ_ALIGN_SE3, TRAJ_ALIGN_SIM3 = 0, 1, 2, 3 
 TRAJ_GT_W2C, TRAJ_GT_C2W, TRAJ_GT_POSITIONS = 0, 1, 2                         # pr_trajeval_params.gt_kind
 TRAJ_FEW, TRAJ_DEGENERATE, TRAJ_NO_SCALE = 1, 2, 4                            # flags of a pr_trajeval alignment (ate[19])
 PROXIMITY_QRANGE_CLAMPED = 1                                                   # flags of a pr_proximity search (info[3])
+SUBMAP_TRUNCATED, SUBMAP_NO_CENTER, SUBMAP_OVERFLOW = 1, 2, 4                  # flags of a pr_submap slot (out_rows[p][1], OR-ed in info[3])
 TRAJ_ATE_STATS, TRAJ_RPE_STATS, TRAJ_SEG_STATS, TRAJ_CLO_STATS = 24, 8, 4, 8   # doubles of one statistics row of a pr_trajeval run
 REGINFO_OFF, REGINFO_NONFINITE, REGINFO_TOO_FEW, REGINFO_SINGULAR, REGINFO_WEAK_ROT, REGINFO_WEAK_TRANS = 1, 2, 4, 8, 16, 32   # stat[3] of a pr_reginfo call
 
@@ -335,6 +336,11 @@ SYMBOLS = {
     "pr_proximity_search": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pr_posegraphb_add_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _dbl, _dbl, _i32, _vp]),
     "pr_posegraphb_add": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _dbl, _dbl, _i32, _vp]),
+    "pr_submap_create": (C.c_int, [_vp, _i32, _i32, C.c_int64, _i32, _i32, C.POINTER(_vp)]),
+    "pr_submap_destroy": (None, [_vp]),
+    "pr_submap_scratch_bytes": (C.c_int64, [_i32, _i32]),
+    "pr_submap_build_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "pr_submap_build": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
 }
 
 
@@ -383,6 +389,11 @@ class TrajEvalParams(C.Structure):
 class ProximityParams(C.Structure):
     """pr_proximity_params: the rule's numbers of one pr_proximity search."""
     _fields_ = [(n, _dbl) for n in ("radius", "growth", "radius_max", "cos_min")] + [(n, _i32) for n in ("min_gap", "stride", "k", "known_window")]
+
+
+class SubmapParams(C.Structure):
+    """pr_submap_params: the rule's numbers of one pr_submap build."""
+    _fields_ = [(n, _i32) for n in ("half_window", "past_only", "avoid_gap", "max_pts")]
 
 
 class TrajEvalOut(C.Structure):

@@ -2364,6 +2364,167 @@ class ProximitySearch:
             pass
 
 
+class Submaps(NamedTuple):
+    """The outputs of a SubmapBuilder build: a CSR set of slot_capacity clouds - xyz f64 [point_capacity, 3] (rows at or behind
+    offs[c] are not written), offs i64 [slot_capacity + 1] - with rows i32 [slot_capacity, 2] = rows taken, flags and info i32 [4] =
+    slots non-empty, points written (low word, high word), flags OR-ed."""
+    xyz: object
+    offs: object
+    rows: object
+    info: object
+
+
+class SubmapBuilder:
+    """pr_submap: local submaps - for every slot the clouds of the map rows centre - w .. centre + w gathered into ONE
+    cloud in the centre row's camera frame, with the poses the map holds or relaxed ones; a CSR set icp_refine_torch reads as it stands.
+    Calls are enqueued on the context's stream, read the map's count on the device and allocate no device scratch: ONE captured
+    build_torch serves every count.  keyframe_capacity and max_cloud_points are the map's.  buffers: dict of xyz, offs, rows, info
+    (the shapes of Submaps) to build into by default; otherwise allocated here.  The rule is in include/place_recognition.h."""
+
+    NAMES = Submaps._fields
+
+    def __init__(self, ctx: Context | None, slot_capacity: int, w_max: int, point_capacity: int, max_cloud_points: int,
+                 keyframe_capacity: int | None = None, buffers: dict | None = None):
+        """keyframe_capacity None: the handle is created by the first call that names a map, with that map's keyframe_capacity (an
+        eager call in front of a capture, as every capture here has)."""
+        self.h = None
+        self.ctx = ctx or default_context()
+        self.lib = self.ctx.lib
+        self.slot_capacity, self.w_max, self.point_capacity = int(slot_capacity), int(w_max), int(point_capacity)
+        self.max_cloud_points, self.keyframe_capacity = int(max_cloud_points), None
+        self.last_pair = None
+        if keyframe_capacity is not None:
+            self._create(int(keyframe_capacity))
+        self.out = self.new_out() if buffers is None else self._out("SubmapBuilder", Submaps(*(buffers[n] for n in self.NAMES)))
+        import torch
+        self.identity = torch.arange(self.slot_capacity, dtype=torch.int32, device=torch.device("cuda", self.ctx.device))
+        torch.cuda.synchronize(self.identity.device)      # torch's fills (its stream) before the library's stream reads the buffers
+
+    def _create(self, keyframe_capacity: int):
+        h = C.c_void_p()
+        self.ctx.check(self.lib.pr_submap_create(self.ctx.h, self.slot_capacity, self.w_max, self.point_capacity, self.max_cloud_points,
+                                                 keyframe_capacity, C.byref(h)))
+        self.h, self.keyframe_capacity = h, keyframe_capacity
+
+    def scratch_bytes(self) -> int:
+        return int(self.lib.pr_submap_scratch_bytes(self.slot_capacity, self.w_max))
+
+    def shapes(self):
+        S = self.slot_capacity
+        return dict(xyz=((self.point_capacity, 3), np.float64), offs=((S + 1,), np.int64), rows=((S, 2), np.int32), info=((4,), np.int32))
+
+    def new_out(self) -> Submaps:
+        """A fresh set of output tensors (zeroed) on the context's device."""
+        import torch
+        dev = torch.device("cuda", self.ctx.device)
+        tdt = {np.int32: torch.int32, np.float64: torch.float64, np.int64: torch.int64}
+        return Submaps(*(torch.zeros(s, dtype=tdt[dt], device=dev) for s, dt in self.shapes().values()))
+
+    def _t(self, who, name, t, dtype, numel, exact=True):
+        import torch
+        dev = torch.device("cuda", self.ctx.device)
+        if (not t.is_cuda) or t.device != dev or t.dtype != dtype or not t.is_contiguous() or (t.numel() != numel if exact else t.numel() < numel):
+            raise ValueError(f"{who}: {name} must be a contiguous CUDA tensor {dtype} of {'' if exact else 'at least '}{numel} elements on the "
+                             "context's device")
+        return t
+
+    def _out(self, who, out: Submaps) -> Submaps:
+        import torch
+        tdt = {np.int32: torch.int32, np.float64: torch.float64, np.int64: torch.int64}
+        for name, (shape, dt) in self.shapes().items():
+            self._t(who, name, getattr(out, name), tdt[dt], int(np.prod(shape)))
+        return out
+
+    def _map(self, who, km):
+        if km.ctx is not self.ctx:
+            raise ValueError(f"{who}: the builder and the map must share one context (one stream)")
+        if self.keyframe_capacity is None:
+            self._create(int(km.keyframe_capacity))
+        if km.keyframe_capacity != self.keyframe_capacity:
+            raise ValueError(f"{who}: keyframe_capacity must equal the map's")
+
+    def _params(self, who, c, w, past_only, avoid_gap, max_pts):
+        if c < 0 or c > self.slot_capacity:
+            raise ValueError(f"{who}: the centre list must hold 0 .. slot_capacity rows")
+        w = int(w)
+        if w < 0 or w > self.w_max:
+            raise ValueError(f"{who}: w must lie in 0 .. w_max")
+        return _lib.SubmapParams(w, 1 if past_only else 0, int(avoid_gap),
+                                 int(min(self.point_capacity, 2 ** 31 - 1) if max_pts is None else max_pts))
+
+    def build_torch(self, km, centers, avoid=None, poses=None, n=None, *, w: int, past_only: bool = False, avoid_gap: int = 0, max_pts=None,
+                    out: Submaps | None = None) -> Submaps:
+        """Device form (pr_submap_build_dev): km a KeyframeMap on this builder's context, centers i32 [c] the slots' centre rows (negative:
+        the slot is switched off), avoid i32 [c] | None - rows within avoid_gap of avoid[p] stay out of slot p (the other end of the pair),
+        poses f64 [>= keyframe_capacity, 12] | None (the map's own; or PoseGraph.relax_torch's out), n i32 [>= 1] | None (the map's state).
+        max_pts: the most points of one submap (default point_capacity) - what icp_refine_torch takes as max_src_pts / max_dst_pts.
+        out: the Submaps to write (default: the builder's own; fixed addresses are what a captured graph needs).  Nothing synchronises,
+        nothing is allocated."""
+        import torch
+        who = "SubmapBuilder.build_torch"
+        self._map(who, km)
+        c = centers.numel()
+        prm = self._params(who, c, w, past_only, avoid_gap, max_pts)
+        self._t(who, "centers", centers, torch.int32, c)
+        if avoid is not None:
+            self._t(who, "avoid", avoid, torch.int32, c)
+        poses = km.poses if poses is None else self._t(who, "poses", poses, torch.float64, 12 * self.keyframe_capacity, exact=False)
+        n = km.state if n is None else self._t(who, "n", n, torch.int32, 1, exact=False)
+        out = self.out if out is None else self._out(who, out)
+        rec = _lib.MapBuffers(*(C.c_void_p(getattr(km, nm).data_ptr()) for nm in km.NAMES))
+        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        self.ctx.check(self.lib.pr_submap_build_dev(self.h, C.byref(rec), p(poses), p(n), p(centers), p(avoid), c, C.byref(prm), p(out.xyz), p(out.offs),
+                                                    p(out.rows), p(out.info)))
+        return out
+
+    def build(self, km, centers, avoid=None, poses=None, n=None, *, w: int, past_only: bool = False, avoid_gap: int = 0, max_pts=None) -> Submaps:
+        """Host form (pr_submap_build; synchronises): centers / avoid are NumPy arrays, the map, poses and n stay device memory.  Returns
+        Submaps of NumPy arrays; xyz holds the offs[c] rows that were written."""
+        who = "SubmapBuilder.build"
+        self._map(who, km)
+        cen = np.ascontiguousarray(centers, np.int32).reshape(-1)
+        c = len(cen)
+        av = None if avoid is None else np.ascontiguousarray(avoid, np.int32).reshape(-1)
+        if av is not None and len(av) != c:
+            raise ValueError(f"{who}: centers [c] and avoid [c] disagree")
+        prm = self._params(who, c, w, past_only, avoid_gap, max_pts)
+        got = {name: np.empty(shape, dt) for name, (shape, dt) in self.shapes().items()}
+        poses = km.poses if poses is None else poses
+        n = km.state if n is None else n
+        rec = _lib.MapBuffers(*(C.c_void_p(getattr(km, nm).data_ptr()) for nm in km.NAMES))
+        self.ctx.check(self.lib.pr_submap_build(self.h, C.byref(rec), C.c_void_p(poses.data_ptr()), C.c_void_p(n.data_ptr()), _ptr(cen), _ptr(av), c,
+                                                C.byref(prm), *(_ptr(got[nm]) for nm in self.NAMES)))
+        got["xyz"] = got["xyz"][:int(got["offs"][c])]
+        return Submaps(*(got[nm] for nm in self.NAMES))
+
+    def pair_torch(self, km, idx_db, idx_q, poses=None, n=None, *, w: int, avoid_gap: int = 0, max_pts=None, out=None):
+        """Both sides of a pair list in two builds: the DB side centred on idx_db avoiding idx_q, the query side centred on idx_q avoiding
+        idx_db with past_only (online the query has no future).  idx_db, idx_q i32 [c] - a ProximitySearch's pair_dst and pair_src.  Returns
+        (db: Submaps, q: Submaps, pair_src i32 [c], pair_dst i32 [c]) with identity pair lists, so that
+        icp_refine_torch(q.xyz, q.offs, db.xyz, db.offs, pair_src, pair_dst, T0, max_pts, max_pts) runs on them unchanged (a slot switched
+        off holds two empty clouds: ICP_TOO_FEW).  out: the (db, q) pair an earlier call returned - kept in .last_pair - for a capture."""
+        if out is None:
+            out = (self.out, self.new_out())
+            import torch
+            torch.cuda.synchronize(self.identity.device)
+        c = idx_db.numel()
+        db = self.build_torch(km, idx_db, idx_q, poses, n, w=w, past_only=False, avoid_gap=avoid_gap, max_pts=max_pts, out=out[0])
+        q = self.build_torch(km, idx_q, idx_db, poses, n, w=w, past_only=True, avoid_gap=avoid_gap, max_pts=max_pts, out=out[1])
+        self.last_pair = (db, q)
+        return db, q, self.identity[:c], self.identity[:c]
+
+    def close(self):
+        if getattr(self, "h", None) and getattr(self.ctx, "h", None):
+            self.lib.pr_submap_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class SequenceFilter:
     """pr_seqmatch: the online form of the sequence matcher - a ring of the last L fused score rows of a drive.  Every
     keyframe, push_torch takes the distance rows an OnlineDatabase / OnlineSet match wrote (rows=) and the database's .state, fuses them
