@@ -5,6 +5,8 @@ from __future__ import annotations
 
 import numpy as np
 
+from ._handle import ptr
+
 
 def ground_truth_pairs(gt1, gt2, loop_diff: float, mask_width: int) -> np.ndarray:
     """run_test.m:3-22: for every i the closest j with |i-j| >= mask_width (first minimum), kept when closer than
@@ -103,11 +105,6 @@ class _on_stream:
                 t.record_stream(self.lib_stream)
 
 
-def _p(t):
-    import ctypes as C
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
 def ground_truth_pairs_torch(gt1, gt2, loop_diff: float, mask_width: int, ctx=None):
     """run_test.m:3-22 on the device (pr_ground_truth_pairs_dev): gt1 [m, cols], gt2 [n, cols] CUDA tensors ->
     (lp_gt int32 [m, 2], n_gt int32 [1], min_j int32 [m], min_d float64 [m]), all on the device; the first n_gt rows of lp_gt are the
@@ -121,8 +118,8 @@ def ground_truth_pairs_torch(gt1, gt2, loop_diff: float, mask_width: int, ctx=No
     min_j = torch.empty(m, dtype=torch.int32, device=dev)
     min_d = torch.empty(m, dtype=torch.float64, device=dev)
     with _on_stream(ctx, dev, (g1, g2, lp, n_gt, min_j, min_d)) as c:
-        c.check(c.lib.pr_ground_truth_pairs_dev(c.h, _p(g1), m, _p(g2), n, cols, float(loop_diff), int(mask_width), _p(min_j), _p(min_d),
-                                                _p(lp), _p(n_gt)))
+        c.check(c.lib.pr_ground_truth_pairs_dev(c.h, ptr(g1), m, ptr(g2), n, cols, float(loop_diff), int(mask_width), ptr(min_j), ptr(min_d),
+                                                ptr(lp), ptr(n_gt)))
     return lp, n_gt, min_j, min_d
 
 
@@ -149,9 +146,9 @@ def precision_recall_torch(score, idx, gt1, gt2, loop_diff: float, mask_width: i
     elif out["precision"].shape[0] != m:
         raise ValueError("precision_recall_torch: out belongs to another m")
     with _on_stream(ctx, dev, (score, idx, g1, g2, out["_record"], out["lp_gt"], out["lp_detected"], out["precision"], out["recall"])) as c:
-        c.check(c.lib.pr_precision_recall_dev(c.h, _p(score), _p(idx), ld, m, _p(g1), _p(g2), n, cols, float(loop_diff), int(mask_width),
-                                              _p(out["_record"]), _p(out["lp_gt"]), _p(out["lp_detected"]), _p(out["precision"]),
-                                              _p(out["recall"])))
+        c.check(c.lib.pr_precision_recall_dev(c.h, ptr(score), ptr(idx), ld, m, ptr(g1), ptr(g2), n, cols, float(loop_diff), int(mask_width),
+                                              ptr(out["_record"]), ptr(out["lp_gt"]), ptr(out["lp_detected"]), ptr(out["precision"]),
+                                              ptr(out["recall"])))
     return out
 
 
