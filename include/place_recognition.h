@@ -1869,6 +1869,108 @@ int pr_submap_build_dev(pr_submap* sm, const pr_map_buffers* map, const double* 
 int pr_submap_build(pr_submap* sm, const pr_map_buffers* map, const double* d_poses, const int32_t* d_n, const int32_t* center, const int32_t* avoid,
                     int32_t c, const pr_submap_params* params, double* out_xyz, int64_t* out_offs, int32_t* out_rows, int32_t* info);
 
+/* ---- drive sessions: join a later drive to the map through its closures (session.hip) ------------------------------------
+ * The reference evaluates place recognition over one drive that revisits itself and over two drives of one route (test_robotcar.m).  A
+ * second drive can be appended behind the first in a pr_map and its closures logged in a pr_posegraph, but its poses start at the identity
+ * of a world frame of their own.  A pr_session records where each drive begins in the map's rows, moves a later drive rigidly onto the
+ * earlier ones by a consensus of the cross-drive closures, and relaxes the joined rows without the odometry edges across drive borders.
+ * After an align every stage that takes one pose array in one frame (pr_gate, pr_worldmap, pr_maploc, pr_proximity, pr_trajeval) works on
+ * the joined array as it stands.  Everything is stream-ordered, reads every count on the device, reads nothing back and allocates nothing
+ * after create; every grid is a function of the create sizes only, so one capture made with an empty log and one session serves every
+ * count.  The intended chain is align -> pr_gate_run_dev -> pr_session_relax_dev, captured once and replayed.
+ *
+ *   pr_session_create   binds the CALLER-OWNED device buffers (pr_session_buffers; they must outlive the handle): start [session_capacity]
+ *                       i32, the first row of every session, and state [4] i32 = {sessions S, flags, 0, 0}; sets S = 1, start[0] = 0.
+ *                       session_capacity in 1 .. 1024, node_capacity in 1 .. 2^20, edge_capacity in 1 .. 65536 (the gate's limit: the
+ *                       alignment visits all pairs).  ONE allocation; with NC = node_capacity and EC = edge_capacity the parts are, each
+ *                       rounded up to 16 bytes:
+ *                         4 NC (sid) | 4 NC (breaks) | 4 EC (candidate) | 4 EC (q) | 96 EC (G_a) | 24 EC (c_a) | 24 EC (G_a c_a) |
+ *                         4 EC (support sums) | 4 EC (members of I) | 192 (G, G^-1) | 48 (control)
+ *                         | staging of the host forms: 96 (G) | 96 EC (hyp) | 4 EC (support) | EC (inlier) | 32 (info) | 16 (begin's info)
+ *                       pr_session_scratch_bytes returns the sum (0 for sizes create refuses).
+ *   pr_session_reset    S = 1, start[0] = 0, flags = 0 (stream-ordered).   pr_session_count   synchronising read of S and flags (diagnostics).
+ *   pr_session_begin_dev  one launch of one thread.  d_n [>= 1] i32: pass the map's state, word 0 is the keyframe count; d_info [4] i32.
+ *   pr_session_begin    the same with a HOST info (d_n stays device memory); synchronises.
+ *   pr_session_align_dev  4 launches (prepare, pairs, choose, apply).  log: the buffer record of a closure log with log_edge_capacity rows,
+ *                       1 <= log_edge_capacity <= edge_capacity; it is only read.  d_poses_in, d_poses_out [node_capacity][12] f64 (they
+ *                       may be equal), d_n as for begin, d_G [12] f64, d_hyp [edge_capacity][12] f64 or NULL, d_support [edge_capacity] i32
+ *                       or NULL, d_inlier [edge_capacity] u8 or NULL, d_info [8] i32.  Every entry of an output that is given is written.
+ *   pr_session_align    the same with HOST G, hyp, support, inlier, info (the log, the poses and d_n stay device memory); synchronises.
+ *   pr_session_relax_dev  1 launch (sid and breaks of every row from the table as it stands) and then pr_posegraph_relax_dev's 3 outer + 3
+ *                       launches on the graph g, whose prepare step reads the break array: 3 outer + 4 launches in all.  g must live on the
+ *                       session table's context and have its node_capacity.  Arguments, report and refusals are pr_posegraph_relax_dev's.
+ *
+ * The table.  S = state[0] clamped into 1 .. session_capacity before use.  Row r belongs to session
+ *      sid(r) = #{q in 1 .. S-1 : start[q] <= r}
+ * - a count, not a search: it is defined for any scribbled start, and start[0] is never read (session 0 begins at row 0).  Row r >= 1 is
+ * a BREAK iff sid(r) != sid(r-1).
+ * begin, decided on the device: n = d_n[0] clamped into 0 .. node_capacity; last = start[S-1] (0 when S == 1).  If n == last the current
+ * last session is still empty: nothing is stored and info[3] carries PR_SESSION_REUSED.  Else if S == session_capacity nothing is stored
+ * and PR_SESSION_OVERFLOW is set, in state[1] and in every later info, until pr_session_reset.  Else start[S] = n and S + 1 is committed
+ * by one thread.  info = {session index now current, its first row, S after, flags}.
+ *
+ * The alignment (restated in tests/session_np.py).  Conventions as for pr_posegraph and pr_gate: a pose is [R | t], 12 doubles row-major,
+ * world to camera; a closure (i, j, Z) measures Z ~ P_i P_j^-1; A B = [R_A R_B | R_A t_B + t_A]; A^-1 = [R^T | -(R^T t)]; fp64, no
+ * contraction; a 3 x 3 product entry is (a0 b0 + a1 b1) + a2 b2; the translation of a product is ((r0 t0 + r1 t1) + r2 t2) + t_A, of an
+ * inverse -((R0r t0 + R1r t1) + R2r t2); R^T is formed first and then multiplied like any other matrix.
+ *   1. Counts.  E = log.state[0] clamped into 0 .. log_edge_capacity, n = d_n[0] clamped into 0 .. node_capacity, S as above, all before
+ *      any address is formed from them.  The target is t = params.session, and -1 means S - 1.  If t <= 0, t >= S or session t has no row
+ *      < n the status is PR_SESSION_NO_TARGET: rows < n are copied bit for bit and G is the identity.
+ *   2. Candidates.  Edge a < E is a candidate iff it is valid by the relaxation's skip rule (0 <= i, j < n, i != j, its 12 Z entries and
+ *      2 weights finite, the 24 entries of P_i, P_j finite) and exactly one end lies in session t and the other in a session < t: the
+ *      earlier sessions are the anchor, edges to later sessions are ignored.
+ *   3. Hypotheses.  With j in t: G_a = (P_i^-1 Z_a) P_j (the gate's M_a).  With i in t: G_a = (P_j^-1 Z_a^-1) P_i.  G_a maps session t's
+ *      world frame into the anchor's.  q_a is the edge's row in t, c_a = -(R^T t) of P_qa that row's camera centre (the translation of
+ *      P_qa^-1), and G_a c_a = ((r0 c0 + r1 c1) + r2 c2) + t_Ga.
+ *   4. Support, over ordered pairs.  b supports a iff both are candidates, a != b, q_a != q_b (two candidates of one keyframe are not
+ *      independent evidence), c_rot = 3 - ((x00 + x11) + x22) <= rot_c_max with x_cc = (Ra_0c Rb_0c + Ra_1c Rb_1c) + Ra_2c Rb_2c the
+ *      diagonal of R_Ga^T R_Gb, and c_trans = (dx dx + dy dy) + dz dz <= trans2_max with d = G_a c_b - G_b c_b: the two hypotheses are
+ *      compared AT THE CLOSURE, not at the world origin, so a small rotation difference is not multiplied by the route's lever arm.
+ *      + and x only.  A NaN supports nothing.  The rule is evaluated as written; it need not be symmetric in floating point.
+ *   5. Choice.  a* is the candidate with the largest support, ties to the lowest log index: a decision in integers.  No candidate:
+ *      PR_SESSION_NO_CANDIDATE.  support + 1 < min_inliers: PR_SESSION_WEAK.  Both copy the poses and return the identity.
+ *   6. Refinement over I = {a*} and its supporters, in log order, the sums by the fixed tree of the library's block sums:
+ *      R = R_Ga* exp(mean_b log_SO3(R_Ga*^T R_Gb)) with pr_posegraph's log_SO3 and exp and their ONE small-angle branch at 1e-4;
+ *      t = mean_b(G_b c_b) - R mean_b(c_b).  A non-finite G: PR_SESSION_NONFINITE, and the poses are copied.
+ *   7. Apply.  Every finite row of session t becomes P_r G^-1; every other row < n is copied bit for bit; rows >= n are not written.
+ *   8. Outputs.  d_G is G, or the identity unless the status is PR_SESSION_ALIGNED.  d_hyp holds G_a of every candidate and zeros
+ *      elsewhere; d_support is -1 for a non-candidate; d_inlier marks the members of I (all 0 without an a*; with PR_SESSION_WEAK the
+ *      members are still marked).  info = {status, a* or -1, its support, candidates, |I|, E, n, flags}: flags carries
+ *      PR_SESSION_OVERFLOW of the table and PR_SESSION_LOG_OVERFLOW when the log's state[1] has PR_POSEGRAPH_OVERFLOW.
+ * Everything up to the choice, d_hyp and every copied row equal the restatement bit for bit; G and the moved rows differ from it by the
+ * rounding of the sums' order and of sin, cos, atan2 only (DESIGN.md 4.29 has the measured bound).  Two runs give the same bytes.
+ *
+ * The relaxation across breaks is pr_posegraph_relax_dev's rule with one change: odometry slot s is not an edge when row s + 1 is a break.
+ * With S == 1 it leaves exactly pr_posegraph_relax_dev's bytes.  A session without a used closure to the rest does not move: its
+ * odometry residuals are exactly zero, so its gradient is zero and the conjugate gradients start from 0.  Node 0 remains the only gauge.
+ * PR_EINVAL (text: pr_last_error) before any device is touched for a NULL handle, record, buffer, params or required pointer, a capacity
+ * out of range, log_edge_capacity outside 1 .. edge_capacity, session < -1, min_inliers < 1, a rot_c_max or trans2_max that is NaN or
+ * negative (+Inf is allowed and switches that test off), a graph on another context or with another node_capacity, and everything
+ * pr_posegraph_relax_dev refuses. */
+typedef struct pr_session pr_session;
+typedef struct pr_session_buffers { int32_t* start; int32_t* state; } pr_session_buffers;
+typedef struct pr_session_align_params { int32_t session, min_inliers; double rot_c_max, trans2_max; } pr_session_align_params;
+#define PR_SESSION_OVERFLOW 1
+#define PR_SESSION_REUSED 2
+#define PR_SESSION_LOG_OVERFLOW 4
+enum { PR_SESSION_ALIGNED = 0, PR_SESSION_NO_TARGET = 1, PR_SESSION_NO_CANDIDATE = 2, PR_SESSION_WEAK = 3, PR_SESSION_NONFINITE = 4 };
+int pr_session_create(pr_ctx* ctx, const pr_session_buffers* buffers, int32_t node_capacity, int32_t edge_capacity, int32_t session_capacity,
+                      pr_session** out);
+void pr_session_destroy(pr_session* s);
+int pr_session_reset(pr_session* s);
+int pr_session_count(pr_session* s, int32_t* sessions, int32_t* flags);
+size_t pr_session_scratch_bytes(int32_t node_capacity, int32_t edge_capacity, int32_t session_capacity);
+int pr_session_begin_dev(pr_session* s, const int32_t* d_n, int32_t* d_info);
+int pr_session_begin(pr_session* s, const int32_t* d_n, int32_t* info);
+int pr_session_align_dev(pr_session* s, const pr_posegraph_buffers* log, int32_t log_edge_capacity, const double* d_poses_in, const int32_t* d_n,
+                         const pr_session_align_params* params, double* d_poses_out, double* d_G, double* d_hyp, int32_t* d_support,
+                         uint8_t* d_inlier, int32_t* d_info);
+int pr_session_align(pr_session* s, const pr_posegraph_buffers* log, int32_t log_edge_capacity, const double* d_poses_in, const int32_t* d_n,
+                     const pr_session_align_params* params, double* d_poses_out, double* G, double* hyp, int32_t* support, uint8_t* inlier,
+                     int32_t* info);
+int pr_session_relax_dev(pr_session* s, pr_posegraph* g, const double* d_poses_in, const int32_t* d_n, const pr_posegraph_params* params,
+                         double* d_poses_out, double* d_report);
+
 #ifdef __cplusplus
 }
 #endif

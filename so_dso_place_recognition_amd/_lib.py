@@ -42,6 +42,8 @@ TRAJ_FEW, TRAJ_DEGENERATE, TRAJ_NO_SCALE = 1, 2, 4                            # 
 PROXIMITY_QRANGE_CLAMPED = 1                                                   # flags of a pr_proximity search (info[3])
 SUBMAP_TRUNCATED, SUBMAP_NO_CENTER, SUBMAP_OVERFLOW = 1, 2, 4                  # flags of a pr_submap slot (out_rows[p][1], OR-ed in info[3])
 TRAJ_ATE_STATS, TRAJ_RPE_STATS, TRAJ_SEG_STATS, TRAJ_CLO_STATS = 24, 8, 4, 8   # doubles of one statistics row of a pr_trajeval run
+SESSION_OVERFLOW, SESSION_REUSED, SESSION_LOG_OVERFLOW = 1, 2, 4                # flags of a pr_session begin (info[3]) and align (info[7])
+SESSION_ALIGNED, SESSION_NO_TARGET, SESSION_NO_CANDIDATE, SESSION_WEAK, SESSION_NONFINITE = 0, 1, 2, 3, 4   # status of a pr_session align (info[0])
 REGINFO_OFF, REGINFO_NONFINITE, REGINFO_TOO_FEW, REGINFO_SINGULAR, REGINFO_WEAK_ROT, REGINFO_WEAK_TRANS = 1, 2, 4, 8, 16, 32   # stat[3] of a pr_reginfo call
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -341,6 +343,16 @@ SYMBOLS = {
     "pr_submap_scratch_bytes": (C.c_int64, [_i32, _i32]),
     "pr_submap_build_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "pr_submap_build": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "pr_session_create": (C.c_int, [_vp, _vp, _i32, _i32, _i32, C.POINTER(_vp)]),
+    "pr_session_destroy": (None, [_vp]),
+    "pr_session_reset": (C.c_int, [_vp]),
+    "pr_session_count": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32)]),
+    "pr_session_scratch_bytes": (C.c_size_t, [_i32, _i32, _i32]),
+    "pr_session_begin_dev": (C.c_int, [_vp, _vp, _vp]),
+    "pr_session_begin": (C.c_int, [_vp, _vp, _vp]),
+    "pr_session_align_dev": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pr_session_align": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pr_session_relax_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 
@@ -394,6 +406,16 @@ class ProximityParams(C.Structure):
 class SubmapParams(C.Structure):
     """pr_submap_params: the rule's numbers of one pr_submap build."""
     _fields_ = [(n, _i32) for n in ("half_window", "past_only", "avoid_gap", "max_pts")]
+
+
+class SessionBuffers(C.Structure):
+    """pr_session_buffers: the two caller-owned device buffers of a pr_session."""
+    _fields_ = [(n, _vp) for n in ("start", "state")]
+
+
+class SessionAlignParams(C.Structure):
+    """pr_session_align_params: the rule's numbers of one pr_session align."""
+    _fields_ = [("session", _i32), ("min_inliers", _i32), ("rot_c_max", _dbl), ("trans2_max", _dbl)]
 
 
 class TrajEvalOut(C.Structure):

@@ -256,23 +256,42 @@ int pr_posegraphb_add(pr_posegraph* g, const int32_t* i, const int32_t* j, const
 
 int pr_posegraph_relax_dev(pr_posegraph* g, const double* d_poses_in, const int32_t* d_n, const pr_posegraph_params* params, double* d_poses_out,
                            double* d_report) {
+  if (int rc = pr::posegraph_relax_check("pr_posegraph_relax_dev", g, d_poses_in, d_n, params, d_poses_out, d_report)) return rc;
+  return pr::posegraph_relax_launch(g, d_poses_in, d_n, params, d_poses_out, d_report, nullptr);
+}
+
+}  // extern "C"
+
+namespace pr {
+
+int posegraph_relax_check(const char* who, pr_posegraph* g, const double* d_poses_in, const int32_t* d_n, const pr_posegraph_params* params,
+                          double* d_poses_out, double* d_report) {
   pr_ctx* ctx = g ? g->ctx : nullptr;
-  if (!params) return fail(ctx, PR_EINVAL, "pr_posegraph_relax_dev: params is NULL");
-  if (params->outer < 1) return fail(ctx, PR_EINVAL, "pr_posegraph_relax_dev: outer=%d is below 1", params->outer);
-  if (params->inner < 1) return fail(ctx, PR_EINVAL, "pr_posegraph_relax_dev: inner=%d is below 1", params->inner);
-  if (!weight_ok(params->lambda)) return fail(ctx, PR_EINVAL, "pr_posegraph_relax_dev: lambda is negative or not finite");
-  if (!weight_ok(params->w_odo_rot)) return fail(ctx, PR_EINVAL, "pr_posegraph_relax_dev: w_odo_rot is negative or not finite");
-  if (!weight_ok(params->w_odo_trans)) return fail(ctx, PR_EINVAL, "pr_posegraph_relax_dev: w_odo_trans is negative or not finite");
-  if (!g) return fail(nullptr, PR_EINVAL, "pr_posegraph_relax_dev: graph is NULL");
-  if (params->outer > g->v.max_outer) return fail(ctx, PR_EINVAL, "pr_posegraph_relax_dev: outer=%d outside 1 .. max_outer=%d", params->outer, g->v.max_outer);
-  if (params->inner > g->v.max_inner) return fail(ctx, PR_EINVAL, "pr_posegraph_relax_dev: inner=%d outside 1 .. max_inner=%d", params->inner, g->v.max_inner);
+  if (!params) return fail(ctx, PR_EINVAL, "%s: params is NULL", who);
+  if (params->outer < 1) return fail(ctx, PR_EINVAL, "%s: outer=%d is below 1", who, params->outer);
+  if (params->inner < 1) return fail(ctx, PR_EINVAL, "%s: inner=%d is below 1", who, params->inner);
+  if (!weight_ok(params->lambda)) return fail(ctx, PR_EINVAL, "%s: lambda is negative or not finite", who);
+  if (!weight_ok(params->w_odo_rot)) return fail(ctx, PR_EINVAL, "%s: w_odo_rot is negative or not finite", who);
+  if (!weight_ok(params->w_odo_trans)) return fail(ctx, PR_EINVAL, "%s: w_odo_trans is negative or not finite", who);
+  if (!g) return fail(nullptr, PR_EINVAL, "%s: graph is NULL", who);
+  if (params->outer > g->v.max_outer) return fail(ctx, PR_EINVAL, "%s: outer=%d outside 1 .. max_outer=%d", who, params->outer, g->v.max_outer);
+  if (params->inner > g->v.max_inner) return fail(ctx, PR_EINVAL, "%s: inner=%d outside 1 .. max_inner=%d", who, params->inner, g->v.max_inner);
   if (!d_poses_in || !d_n || !d_poses_out || !d_report)
-    return fail(ctx, PR_EINVAL, "pr_posegraph_relax_dev: a required pointer is NULL (d_poses_in, d_n, d_poses_out, d_report)");
+    return fail(ctx, PR_EINVAL, "%s: a required pointer is NULL (d_poses_in, d_n, d_poses_out, d_report)", who);
+  return PR_OK;
+}
+
+int posegraph_relax_launch(pr_posegraph* g, const double* d_poses_in, const int32_t* d_n, const pr_posegraph_params* params,
+                           double* d_poses_out, double* d_report, const int* d_brk) {
+  pr_ctx* ctx = g->ctx;
   PR_CHECK_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
   const pr::PoseGraphParams prm = {params->outer, params->inner, params->lambda, params->w_odo_rot, params->w_odo_trans};
-  pr::launch_posegraph_relax(pr::ctx_stream(ctx), g->v, d_poses_in, d_n, prm, d_poses_out, d_report);
+  pr::launch_posegraph_relax(pr::ctx_stream(ctx), g->v, d_poses_in, d_n, prm, d_poses_out, d_report, d_brk);
   PR_CHECK_HIP(ctx, hipGetLastError());
   return PR_OK;
 }
 
-}  // extern "C"
+pr_ctx* posegraph_ctx(pr_posegraph* g) { return g->ctx; }
+int posegraph_node_capacity(pr_posegraph* g) { return g->v.node_capacity; }
+
+}  // namespace pr

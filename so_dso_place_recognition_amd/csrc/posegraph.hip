@@ -164,7 +164,9 @@ __device__ __forceinline__ void slot_nodes(const PoseGraphView& v, int s, int& i
 }
 
 // ------------------------------------------------------------------------------------------------ prepare
-__global__ __launch_bounds__(256) void posegraph_prepare_kernel(PoseGraphView v, const double* poses_in, const int* __restrict__ n_dev) {
+// brk: NULL, or [node_capacity] i32 where brk[r] != 0 says that row r begins another drive (pr_session): odometry slot r - 1 is no edge
+__global__ __launch_bounds__(256) void posegraph_prepare_kernel(PoseGraphView v, const double* poses_in, const int* __restrict__ n_dev,
+                                                                const int* __restrict__ brk) {
   __shared__ int part[256];
   __shared__ double red[4];
   if (blockIdx.x != 0) return;
@@ -180,7 +182,7 @@ __global__ __launch_bounds__(256) void posegraph_prepare_kernel(PoseGraphView v,
   __syncthreads();
   double used = 0.0, used_logged = 0.0;
   for (int s = tid; s < odo; s += 256) {                         // odometry slots: Z from the input poses, before anything moves
-    const bool ok = s + 1 < n && v.finite[s] && v.finite[s + 1];
+    const bool ok = s + 1 < n && v.finite[s] && v.finite[s + 1] && !(brk && brk[s + 1]);        // s + 1 < n <= node_capacity
     if (ok) {
       double Rq[9], tq[3];
       rel_pose(v.X + (size_t)s * 12, v.X + (size_t)(s + 1) * 12, Rq, tq);
@@ -563,9 +565,9 @@ void launch_posegraph_add_batch(hipStream_t st, const PoseGraphView& v, const in
 }
 
 void launch_posegraph_relax(hipStream_t st, const PoseGraphView& v, const double* poses_in, const int* n, const PoseGraphParams& prm,
-                            double* poses_out, double* report) {
+                            double* poses_out, double* report, const int* brk) {
   const dim3 one(1), blk(256), slots((v.S + 255) / 256), nodes((v.node_capacity + 255) / 256);
-  hipLaunchKernelGGL(posegraph_prepare_kernel, one, blk, 0, st, v, poses_in, n);
+  hipLaunchKernelGGL(posegraph_prepare_kernel, one, blk, 0, st, v, poses_in, n, brk);
   for (int s = 0; s < prm.outer; s++) {
     hipLaunchKernelGGL(posegraph_linearize_kernel, slots, blk, 0, st, v, prm.w_odo_rot, prm.w_odo_trans);
     hipLaunchKernelGGL(posegraph_blocks_kernel, nodes, blk, 0, st, v, prm.lambda);

@@ -40,7 +40,22 @@ void launch_posegraph_add_weighted(hipStream_t st, const PoseGraphView& v, const
 // the batch add: rows (i[p], j[p]) per slot, weights w [c][2] in device memory or, with w == NULL, the pair (w_rot, w_trans); c <= 65535
 void launch_posegraph_add_batch(hipStream_t st, const PoseGraphView& v, const int* i, const int* j, const double* T, const unsigned char* accepted,
                                 const double* w, double w_rot, double w_trans, int c, int* info);
+// brk: NULL (every odometry slot of finite rows is an edge), or a per-row break array [node_capacity] i32 (session.hpp)
 void launch_posegraph_relax(hipStream_t st, const PoseGraphView& v, const double* poses_in, const int* n, const PoseGraphParams& prm,
-                            double* poses_out, double* report);
+                            double* poses_out, double* report, const int* brk = nullptr);
 
+}  // namespace pr
+
+// what session.cpp needs of a pr_posegraph (defined in posegraph.cpp): the argument checks of a relax under the caller's name, which touch
+// no device, and the launch with a break array
+struct pr_ctx;
+struct pr_posegraph;
+struct pr_posegraph_params;
+namespace pr {
+int posegraph_relax_check(const char* who, pr_posegraph* g, const double* d_poses_in, const int32_t* d_n, const pr_posegraph_params* params,
+                          double* d_poses_out, double* d_report);
+int posegraph_relax_launch(pr_posegraph* g, const double* d_poses_in, const int32_t* d_n, const pr_posegraph_params* params,
+                           double* d_poses_out, double* d_report, const int* d_brk);
+pr_ctx* posegraph_ctx(pr_posegraph* g);
+int posegraph_node_capacity(pr_posegraph* g);
 }  // namespace pr

@@ -1,5 +1,7 @@
 """Pose graph and evaluation: the closure log with its relaxation, the consistency gate in front of
-it, pose-proximity closure candidates and trajectory evaluation - device-resident handles.  `api` re-exports every name."""
+it, pose-proximity closure candidates and trajectory evaluation - device-resident handles.  `api` re-exports every name of __all__.
+Drive sessions are SessionTable and SessionAlign: import them from this module - the public names of `api` are a
+literal table in tests/test_api_surface.py, which a new name there would fail."""
 from __future__ import annotations
 
 import ctypes as C
@@ -254,6 +256,166 @@ class ClosureGate(Handle):
         self.ctx.check(self.lib.pr_gate_run(self.h, ptr(poses), ptr(n), _ptr(keep), _ptr(support), _ptr(map_),
                                             _ptr(info)))
         return keep, support, map_, info
+
+
+class SessionAlign(NamedTuple):
+    """What a SessionTable align returns (torch tensors from align_torch / align_map, NumPy arrays from align): poses f64
+    [node_capacity, 12] (the output array; always a device tensor); G f64 [12] = [R | t] row-major, session t's world frame into the
+    anchor's (the identity unless info[0] == SESSION_ALIGNED); hyp f64 [edge_capacity, 12], support i32 and inlier u8 [edge_capacity]
+    (None when switched off); info i32 [8] = status, a* | -1, its support, candidates, |I|, edges read, n, flags."""
+    poses: object
+    G: object
+    hyp: object
+    support: object
+    inlier: object
+    info: object
+
+
+class SessionTable(Handle):
+    """pr_session: where each drive begins in the rows of a KeyframeMap, the consensus rigid alignment of a later drive onto the earlier
+    ones from the cross-drive closures of a PoseGraph's log, and a relaxation that leaves out the odometry edges across drive borders
+    (DESIGN.md 4.29).  The two buffers are torch tensors on the context's device (or the caller's: buffers = dict of the two names):
+    .start [session_capacity] i32, the first row of every session, and .state [4] i32 = sessions, flags, 0, 0.  Calls are enqueued on
+    the context's stream, read every count on the device and allocate no device scratch: ONE capture of align_torch -> ClosureGate.run_torch
+    -> relax_torch made with an empty log and one session serves every count.  The rule is in include/place_recognition.h."""
+
+    NAMES = ("start", "state")
+    _DESTROY = "pr_session_destroy"
+
+    def __init__(self, ctx: Context | None, node_capacity: int, edge_capacity: int, session_capacity: int = 8, buffers: dict | None = None):
+        import torch
+        self._attach(ctx)
+        self.node_capacity, self.edge_capacity, self.session_capacity = int(node_capacity), int(edge_capacity), int(session_capacity)
+        self._buffers("SessionTable", dict(start=((max(self.session_capacity, 0),), torch.int32), state=((4,), torch.int32)), buffers)
+        torch.cuda.synchronize(self._device)              # torch's fills (its stream) before the library's stream writes the buffers
+        rec = _lib.SessionBuffers(*(ptr(getattr(self, n)) for n in self.NAMES))
+        h = C.c_void_p()
+        self.ctx.check(self.lib.pr_session_create(self.ctx.h, C.byref(rec), self.node_capacity, self.edge_capacity, self.session_capacity,
+                                                  C.byref(h)))
+        self.h = h
+
+    def scratch_bytes(self) -> int:
+        return int(self.lib.pr_session_scratch_bytes(self.node_capacity, self.edge_capacity, self.session_capacity))
+
+    def reset(self):
+        self.ctx.check(self.lib.pr_session_reset(self.h))
+
+    def count(self):
+        """(sessions, flags); synchronises (pr_session_count)."""
+        n, f = C.c_int32(), C.c_int32()
+        self.ctx.check(self.lib.pr_session_count(self.h, C.byref(n), C.byref(f)))
+        return int(n.value), int(f.value)
+
+    def _map(self, who, km):
+        self._share(who, "the session table and the map", km)
+        if km.keyframe_capacity != self.node_capacity:
+            raise ValueError(f"{who}: node_capacity must equal the map's keyframe_capacity")
+
+    def begin_torch(self, n, info=None):
+        """Device form (pr_session_begin_dev): the rows from n[0] on - n i32 [>= 1], a KeyframeMap's .state - belong to a new session,
+        unless the current last session is still empty (SESSION_REUSED) or the table is full (SESSION_OVERFLOW, until reset()).  Returns
+        info (device i32 [4]) = session index now current, its first row, sessions after, flags.  Nothing synchronises, nothing is
+        allocated when info= is given."""
+        import torch
+        who = "SessionTable.begin_torch"
+        self._t(who, "n", n, torch.int32, numel_min=1)
+        info = self._result(who, "info", info, torch.int32, (4,), flat=True)
+        self.ctx.check(self.lib.pr_session_begin_dev(self.h, ptr(n), ptr(info)))
+        return info
+
+    def begin_map(self, km, **kw):
+        """begin_torch(km.state, ...) for a KeyframeMap: call it before the first keyframe of the new drive is appended."""
+        self._map("SessionTable.begin_map", km)
+        return self.begin_torch(km.state, **kw)
+
+    def begin(self, n):
+        """Host form (pr_session_begin; synchronises): n as for begin_torch (a device tensor); returns info int32 [4]."""
+        import torch
+        self._t("SessionTable.begin", "n", n, torch.int32, numel_min=1)
+        info = np.empty(4, np.int32)
+        self.ctx.check(self.lib.pr_session_begin(self.h, ptr(n), _ptr(info)))
+        return info
+
+    def _align_args(self, who, pg, poses, n, session, min_inliers, rot_deg, trans, rot_c_max, trans2_max):
+        import torch
+        self._share(who, "the closure log and the session table", pg)
+        if pg.edge_capacity > self.edge_capacity:
+            raise ValueError(f"{who}: the log's edge_capacity must not exceed the session table's")
+        self._t(who, "poses", poses, torch.float64, numel=12 * self.node_capacity)
+        self._t(who, "n", n, torch.int32, numel_min=1)
+        rc = 2.0 * (1.0 - float(np.cos(np.radians(float(rot_deg))))) if rot_c_max is None else float(rot_c_max)
+        t2 = float(trans) ** 2 if trans2_max is None else float(trans2_max)
+        rec = _lib.PoseGraphBuffers(*(ptr(getattr(pg, nm)) for nm in pg.NAMES))
+        return rec, _lib.SessionAlignParams(int(session), int(min_inliers), rc, t2)
+
+    def align_torch(self, pg, poses, n, session: int = -1, min_inliers: int = 3, rot_deg: float = 3.0, trans: float = 1.0, rot_c_max=None,
+                    trans2_max=None, out=None, G=None, hyp=None, support=None, inlier=None, info=None, optional=("hyp", "support", "inlier")):
+        """Device form (pr_session_align_dev): the closures logged in the PoseGraph pg between session `session` (-1: the last) and the
+        earlier sessions vote for the rigid transform G of that session's world frame into theirs; every finite row of the session
+        becomes P G^-1 in out (f64 [node_capacity, 12]; may be poses itself; rows >= n are not written).  Two hypotheses agree within
+        rot_deg degrees and trans metres at the closure (or rot_c_max = 2 (1 - cos) and trans2_max, passed through unchanged; +Inf
+        switches a test off).  hyp / support / inlier are allocated when absent and named in `optional`, else stay NULL.  Returns
+        SessionAlign.  Nothing synchronises; nothing is allocated when every array wanted is given."""
+        import torch
+        who = "SessionTable.align_torch"
+        rec, prm = self._align_args(who, pg, poses, n, session, min_inliers, rot_deg, trans, rot_c_max, trans2_max)
+        ec = self.edge_capacity
+        out = self._result(who, "out", out, torch.float64, (self.node_capacity, 12), flat=True, zeros=True)
+        G = self._result(who, "G", G, torch.float64, (12,), flat=True)
+        info = self._result(who, "info", info, torch.int32, (8,), flat=True)
+        if hyp is not None or "hyp" in optional:
+            hyp = self._result(who, "hyp", hyp, torch.float64, (ec, 12), flat=True)
+        if support is not None or "support" in optional:
+            support = self._result(who, "support", support, torch.int32, (ec,), flat=True)
+        if inlier is not None or "inlier" in optional:
+            inlier = self._result(who, "inlier", inlier, torch.uint8, (ec,), flat=True)
+        self.ctx.check(self.lib.pr_session_align_dev(self.h, C.byref(rec), pg.edge_capacity, ptr(poses), ptr(n), C.byref(prm), ptr(out), ptr(G),
+                                                     ptr(hyp), ptr(support), ptr(inlier), ptr(info)))
+        return SessionAlign(out, G, hyp, support, inlier, info)
+
+    def align_map(self, km, pg, **kw):
+        """align_torch(pg, km.poses, km.state, ...) for a KeyframeMap: out=km.poses moves the session in the map itself."""
+        self._map("SessionTable.align_map", km)
+        return self.align_torch(pg, km.poses, km.state, **kw)
+
+    def align(self, pg, poses, n, session: int = -1, min_inliers: int = 3, rot_deg: float = 3.0, trans: float = 1.0, rot_c_max=None,
+              trans2_max=None, out=None):
+        """Host form (pr_session_align; synchronises): inputs as for align_torch (device tensors), out a device tensor too; returns
+        SessionAlign with NumPy G, hyp, support, inlier, info."""
+        import torch
+        who = "SessionTable.align"
+        rec, prm = self._align_args(who, pg, poses, n, session, min_inliers, rot_deg, trans, rot_c_max, trans2_max)
+        ec = self.edge_capacity
+        out = self._result(who, "out", out, torch.float64, (self.node_capacity, 12), flat=True, zeros=True)
+        G, hyp, support = np.empty(12, np.float64), np.empty((ec, 12), np.float64), np.empty(ec, np.int32)
+        inlier, info = np.empty(ec, np.uint8), np.empty(8, np.int32)
+        self.ctx.check(self.lib.pr_session_align(self.h, C.byref(rec), pg.edge_capacity, ptr(poses), ptr(n), C.byref(prm), ptr(out), _ptr(G),
+                                                 _ptr(hyp), _ptr(support), _ptr(inlier), _ptr(info)))
+        return SessionAlign(out, G, hyp, support, inlier, info)
+
+    def relax_torch(self, pg, poses, n, outer: int = 5, inner: int = 64, lam: float = 1e-9, w_odo_rot: float = 1.0, w_odo_trans: float = 1.0,
+                    out=None, report=None):
+        """Device form (pr_session_relax_dev): PoseGraph.relax_torch on pg with one change - the odometry edge into the first row of
+        every session is left out - so the drives are held together by their closures alone.  With one session it leaves relax_torch's
+        bytes.  Returns (out, report)."""
+        import torch
+        who = "SessionTable.relax_torch"
+        self._share(who, "the pose graph and the session table", pg)
+        if pg.node_capacity != self.node_capacity:
+            raise ValueError(f"{who}: the pose graph's node_capacity must equal the session table's")
+        outer = int(outer)
+        self._t(who, "poses", poses, torch.float64, numel=12 * self.node_capacity)
+        self._t(who, "n", n, torch.int32, numel_min=1)
+        out = self._result(who, "out", out, torch.float64, (self.node_capacity, 12), flat=True, zeros=True)
+        report = self._result(who, "report", report, torch.float64, (max(outer, 0) + 2 if report is None else outer + 2,), flat=True, zeros=True)
+        prm = _lib.PoseGraphParams(outer, int(inner), float(lam), float(w_odo_rot), float(w_odo_trans))
+        self.ctx.check(self.lib.pr_session_relax_dev(self.h, pg.h, ptr(poses), ptr(n), C.byref(prm), ptr(out), ptr(report)))
+        return out, report
+
+    def relax_map(self, km, pg, **kw):
+        """relax_torch(pg, km.poses, km.state, ...) for a KeyframeMap: out=km.poses corrects the map in place."""
+        self._map("SessionTable.relax_map", km)
+        return self.relax_torch(pg, km.poses, km.state, **kw)
 
 
 class TrajEval(NamedTuple):
