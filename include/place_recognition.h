@@ -1971,6 +1971,102 @@ int pr_session_align(pr_session* s, const pr_posegraph_buffers* log, int32_t log
 int pr_session_relax_dev(pr_session* s, pr_posegraph* g, const double* d_poses_in, const int32_t* d_n, const pr_posegraph_params* params,
                          double* d_poses_out, double* d_report);
 
+/* ---- snapshots: the resident map, databases, closure logs and session table saved and restored (snapshot.hip) -----------
+ * All resident state lives in caller-owned device buffers that die with the process.  A pr_snapshot packs the live rows of those buffers
+ * into ONE self-describing blob on the device, validates such a blob and unpacks it into buffers of the same or LARGER capacities, also on
+ * the device, and has host forms that write and read a file, so a map built by one process is continued by another.  Counts are read on
+ * the device, a scribbled count never forms an address, a blob that does not fit or does not check out changes no byte, and a restored
+ * state continues a drive to the same bytes as an uninterrupted run.
+ * OUT OF SCOPE: the pre-stage point window (pr_window), the sequence filter's ring (pr_seqmatch), the world map with its index and normals
+ * (pr_worldmap, pr_maploc, pr_mapplane, pr_mapgrow) and all scratch.  A later drive starts the window and the ring afresh; the world map,
+ * index and normals are rebuilt by one fuse -> index -> normals from the restored map.
+ *
+ * The parts.  Each is optional; a desc names the buffer records of the parts it covers and the capacities they were created with.
+ *   kind                   sections (array: bytes per row; rows)                                          count, clamped
+ *   PR_SNAPSHOT_MAP        xyz 24, inten 4: points | offs 8: keyframes + 1 | frames 128, poses 96, ids 4: keyframes
+ *                                                                          keyframes = state[0] in 0 .. keyframe_capacity,
+ *                                                                          points = offs[keyframes] in 0 .. point_capacity
+ *   PR_SNAPSHOT_ONLINE     sig 19200 (PR_TYPE_SC) or 12288 (PR_TYPE_M2DP)  state[0] in 0 .. capacity;  subtype = the type; up to two
+ *   PR_SNAPSHOT_ONLINESET  fused: sc 19200, m2dp 12288; DELIGHT: delight 32768   state[0] in 0 .. capacity;  subtype = the kind
+ *   PR_SNAPSHOT_GRAPH      edge_ij 8, edge_Z 96, edge_w 16                  state[0] in 0 .. edge_capacity;  subtype = 0 (the raw log), 1 (a gated one)
+ *   PR_SNAPSHOT_SESSION    start 4                                          state[0] in 1 .. session_capacity
+ * Sections come in this order (map, online[0], online[1], online set, graph[0], graph[1], sessions; the arrays of a part in the order
+ * above): at most 17.
+ *
+ * The blob, little-endian, every value as its raw bytes.  With NS sections:
+ *   header   8 x i64 = 64 bytes: magic "PRASNAP1", version 1, NS, total bytes, 64 + 128 NS, the table's checksum, 0, 0
+ *   table    NS entries of 16 x i64 = 128 bytes: kind, subtype, array, rows, bytes per row, byte offset, byte length, checksum, the part's
+ *            four state words verbatim (2 x i64; sticky flags included), the capacities the part was saved from (4 x i64: map
+ *            keyframe_capacity, point_capacity, max_cloud_points, 0; else the capacity, 0, 0, 0), the part's index, 0
+ *   sections the live rows of every section, compacted: byte length = rows x bytes per row, each section on a 64-byte boundary, the pad
+ *            behind it zero; total bytes = the end of the last pad
+ *   pr_snapshot_bound = 64 + 128 NS + sum over the sections of pad64(capacity rows x bytes per row), pad64(b) = (b + 63) & ~63, with
+ *            capacity rows = point_capacity (xyz, inten), keyframe_capacity + 1 (offs), else the part's capacity.
+ * The checksum of a section is the wrap-around uint64 sum over its 8-byte words w_i, i = 0, 1, ..., of mix(w_i, i); a 4-byte tail is
+ * zero-extended.  mix(w, i): x = w ^ ((i + 1) * 0x9E3779B97F4A7C15); x ^= x >> 30; x *= 0xBF58476D1CE4E5B9; x ^= x >> 27;
+ * x *= 0x94D049BB133111EB; x ^= x >> 31 (all mod 2^64).  For every i it is a bijection of w, so a changed word changes its term: every
+ * single-bit flip is caught.  The table's checksum is the same sum over its 16 NS words.  The sum does not depend on the order of its
+ * terms: workgroup sums are combined by 64-bit integer atomic adds.  No floating-point operation anywhere.
+ *
+ *   pr_snapshot_create    the desc's records and capacities are copied (the buffers must outlive the handle; it never owns them).  ONE
+ *                         allocation: the control words, the per-section checksum partials and the info of the host forms.  No later
+ *                         call of a device form allocates.  Bound to ctx and its stream; destroy before ctx.
+ *   pr_snapshot_bound     the largest blob these capacities can produce.  pr_snapshot_desc_bound: the same from a desc, without a handle.
+ *   pr_snapshot_pack_dev  stream-ordered, capturable, no read-back: 3 launches (plan, copy, finish) whose geometry is fixed by the create
+ *                         capacities.  d_blob DEVICE [blob_capacity] bytes on a 16-byte boundary; d_info DEVICE [4] i64.  Every count is
+ *                         clamped into its capacity before an address is formed from it.  info = {bytes written, sections, flags, 0}.
+ *                         If the blob would not fit, PR_SNAPSHOT_OVERFLOW is set, the header and table (checksums 0) are written when
+ *                         THEY fit and nothing past the header's extent 64 + 128 NS is written; bytes written is then the size that
+ *                         would have been needed.  The data is read ONCE: the copy's lanes mix the words they move.
+ *   pr_snapshot_unpack_dev  stream-ordered, capturable: 4 launches (header, sum, verify, scatter).  d_blob DEVICE [blob_bytes] on a
+ *                         16-byte boundary.  VALIDATE, decided on the device; a failed check sets its flag and names its section:
+ *                           PR_SNAPSHOT_TRUNCATED    blob_bytes < 64, NS outside 0 .. 17, the table or a section not inside blob_bytes, an
+ *                                                    offset that is not a multiple of 64 or lies before the previous section's end, a length
+ *                                                    that is not rows x bytes per row, sections of one part that disagree on its count
+ *                           PR_SNAPSHOT_BAD_MAGIC / PR_SNAPSHOT_BAD_VERSION   nothing else of the blob is read then
+ *                           PR_SNAPSHOT_MISSING      entry s is not the handle's section s (kind, subtype, array, bytes per row), or the blob
+ *                                                    has another number of sections (named: the smaller of the two numbers)
+ *                           PR_SNAPSHOT_CAPACITY     rows outside 0 .. the DESTINATION's capacity rows; a cloud of the map above the
+ *                                                    destination's max_cloud_points
+ *                           PR_SNAPSHOT_CHECKSUM     a section's checksum, or the table's own (which names no section)
+ *                           PR_SNAPSHOT_OFFSETS      the map's offs: offs[0] != 0, descending at a row, offs[keyframes] != the rows of xyz
+ *                           PR_SNAPSHOT_SESSIONS     start[0] != 0 or start not strictly ascending: not an order pr_session_begin_dev
+ *                                                    produces over a growing map
+ *                         Only extents that passed form an address.  SCATTER is switched off on the device by any failed check; else it
+ *                         copies the saved rows into the destination buffers and writes each part's four state words as saved.  Rows at
+ *                         or above the saved count are left exactly as the destination held them: restore into freshly created or reset
+ *                         buffers.  info = {sections restored (NS or 0), first failing section or -1, flags, 0}.  On any failure NO BYTE
+ *                         of any destination buffer changes.
+ *   pr_snapshot_save      the host form: packs into a staging blob of pr_snapshot_bound bytes, ONE synchronising read of info, ONE
+ *                         device-to-host copy of exactly `bytes written`, written to path + ".tmp" and renamed to path.
+ *   pr_snapshot_load      the host form: reads the file and refuses on the host, no device touched: a missing or unreadable file
+ *                         (PR_EIO), a file shorter than a header, a header cut inside its table, a table entry that points outside the
+ *                         file (PR_EINVAL).  Then uploads, runs pr_snapshot_unpack_dev and synchronises; info HOST [4] i64 as above.
+ *                         The two host forms take and free their staging themselves and are not capturable.
+ * Two runs give the same bytes.  Nothing is written outside the blob's reported extent or the destination buffers' stated extents.
+ * PR_EINVAL (text: pr_last_error) before any device is touched for a NULL handle, desc, blob, info or path, a blob off a 16-byte boundary,
+ * a negative size, a desc with no part, a NULL buffer of a named part, a non-positive or too large capacity, max_cloud_points >
+ * point_capacity, an online type or set kind the library does not know, a set's buffers that do not fit its kind. */
+typedef struct pr_snapshot pr_snapshot;
+typedef struct pr_snapshot_desc {
+  const pr_map_buffers* map; int32_t keyframe_capacity, max_cloud_points; int64_t point_capacity;
+  const pr_online_buffers* online[2]; int32_t online_type[2]; int32_t online_capacity[2];
+  const pr_onlineset_buffers* onlineset; int32_t onlineset_kind, onlineset_capacity;
+  const pr_posegraph_buffers* graph[2]; int32_t edge_capacity[2];
+  const pr_session_buffers* sessions; int32_t session_capacity, reserved;
+} pr_snapshot_desc;
+enum { PR_SNAPSHOT_MAP = 1, PR_SNAPSHOT_ONLINE = 2, PR_SNAPSHOT_ONLINESET = 3, PR_SNAPSHOT_GRAPH = 4, PR_SNAPSHOT_SESSION = 5 };
+enum { PR_SNAPSHOT_OVERFLOW = 1, PR_SNAPSHOT_BAD_MAGIC = 2, PR_SNAPSHOT_BAD_VERSION = 4, PR_SNAPSHOT_TRUNCATED = 8, PR_SNAPSHOT_MISSING = 16,
+       PR_SNAPSHOT_CAPACITY = 32, PR_SNAPSHOT_CHECKSUM = 64, PR_SNAPSHOT_OFFSETS = 128, PR_SNAPSHOT_SESSIONS = 256 };
+int pr_snapshot_create(pr_ctx* ctx, const pr_snapshot_desc* desc, pr_snapshot** out);
+void pr_snapshot_destroy(pr_snapshot* s);
+int pr_snapshot_bound(pr_snapshot* s, int64_t* bytes);
+int pr_snapshot_desc_bound(const pr_snapshot_desc* desc, int64_t* bytes);
+int pr_snapshot_pack_dev(pr_snapshot* s, void* d_blob, int64_t blob_capacity, int64_t* d_info);
+int pr_snapshot_unpack_dev(pr_snapshot* s, const void* d_blob, int64_t blob_bytes, int64_t* d_info);
+int pr_snapshot_save(pr_snapshot* s, const char* path);
+int pr_snapshot_load(pr_snapshot* s, const char* path, int64_t* info);
+
 #ifdef __cplusplus
 }
 #endif

@@ -44,6 +44,9 @@ SUBMAP_TRUNCATED, SUBMAP_NO_CENTER, SUBMAP_OVERFLOW = 1, 2, 4                  #
 TRAJ_ATE_STATS, TRAJ_RPE_STATS, TRAJ_SEG_STATS, TRAJ_CLO_STATS = 24, 8, 4, 8   # doubles of one statistics row of a pr_trajeval run
 SESSION_OVERFLOW, SESSION_REUSED, SESSION_LOG_OVERFLOW = 1, 2, 4                # flags of a pr_session begin (info[3]) and align (info[7])
 SESSION_ALIGNED, SESSION_NO_TARGET, SESSION_NO_CANDIDATE, SESSION_WEAK, SESSION_NONFINITE = 0, 1, 2, 3, 4   # status of a pr_session align (info[0])
+SNAPSHOT_MAP, SNAPSHOT_ONLINE, SNAPSHOT_ONLINESET, SNAPSHOT_GRAPH, SNAPSHOT_SESSION = 1, 2, 3, 4, 5   # section kinds of a pr_snapshot blob
+SNAPSHOT_OVERFLOW, SNAPSHOT_BAD_MAGIC, SNAPSHOT_BAD_VERSION, SNAPSHOT_TRUNCATED, SNAPSHOT_MISSING = 1, 2, 4, 8, 16   # flags of a pr_snapshot pack / unpack (info[2])
+SNAPSHOT_CAPACITY, SNAPSHOT_CHECKSUM, SNAPSHOT_OFFSETS, SNAPSHOT_SESSIONS = 32, 64, 128, 256
 REGINFO_OFF, REGINFO_NONFINITE, REGINFO_TOO_FEW, REGINFO_SINGULAR, REGINFO_WEAK_ROT, REGINFO_WEAK_TRANS = 1, 2, 4, 8, 16, 32   # stat[3] of a pr_reginfo call
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -353,6 +356,14 @@ SYMBOLS = {
     "pr_session_align_dev": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pr_session_align": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pr_session_relax_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pr_snapshot_create": (C.c_int, [_vp, _vp, C.POINTER(_vp)]),
+    "pr_snapshot_destroy": (None, [_vp]),
+    "pr_snapshot_bound": (C.c_int, [_vp, C.POINTER(C.c_int64)]),
+    "pr_snapshot_desc_bound": (C.c_int, [_vp, C.POINTER(C.c_int64)]),
+    "pr_snapshot_pack_dev": (C.c_int, [_vp, _vp, C.c_int64, _vp]),
+    "pr_snapshot_unpack_dev": (C.c_int, [_vp, _vp, C.c_int64, _vp]),
+    "pr_snapshot_save": (C.c_int, [_vp, C.c_char_p]),
+    "pr_snapshot_load": (C.c_int, [_vp, C.c_char_p, _vp]),
 }
 
 
@@ -416,6 +427,14 @@ class SessionBuffers(C.Structure):
 class SessionAlignParams(C.Structure):
     """pr_session_align_params: the rule's numbers of one pr_session align."""
     _fields_ = [("session", _i32), ("min_inliers", _i32), ("rot_c_max", _dbl), ("trans2_max", _dbl)]
+
+
+class SnapshotDesc(C.Structure):
+    """pr_snapshot_desc: pointers to the buffer records of the parts a pr_snapshot covers (NULL: not covered) and their create capacities."""
+    _fields_ = [("map", _vp), ("keyframe_capacity", _i32), ("max_cloud_points", _i32), ("point_capacity", C.c_int64),
+                ("online", _vp * 2), ("online_type", _i32 * 2), ("online_capacity", _i32 * 2),
+                ("onlineset", _vp), ("onlineset_kind", _i32), ("onlineset_capacity", _i32),
+                ("graph", _vp * 2), ("edge_capacity", _i32 * 2), ("sessions", _vp), ("session_capacity", _i32), ("reserved", _i32)]
 
 
 class TrajEvalOut(C.Structure):
