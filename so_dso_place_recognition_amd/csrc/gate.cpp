@@ -1,25 +1,23 @@
 // gate.cpp — host side of the closure consistency gate (gate.hip): the opaque pr_gate over the buffer records of two
-// loop-closure logs, its ONE scratch allocation with the two tables, the argument checks, the stream-ordered run and its host form.
+// loop-closure logs, its ONE scratch allocation with the two tables, the argument checks, the stream-ordered run and its host form, on the
+// shared handle core (handle_core.hpp).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstdio>
 #include <cstring>
-#include <new>
 
 #include "../../include/place_recognition.h"
 #include "gate.hpp"
-#include "host_common.hpp"
+#include "handle_core.hpp"
 #include "kernels.hpp"
 
 static_assert(pr::GATE_SRC_OVERFLOW == PR_GATE_SRC_OVERFLOW && pr::GATE_UNSETTLED == PR_GATE_UNSETTLED, "flag bits");
 static_assert(pr::GATE_LOG_OVERFLOW == PR_POSEGRAPH_OVERFLOW, "the source log's flag bit");
 static_assert(sizeof(pr_gate_params) == 12, "three int32, no padding");
 
-struct pr_gate {
-  pr_ctx* ctx = nullptr;
+struct pr_gate : pr::Handle {        // scratch: everything GateView names and the staging of the host form
   pr::GateView v;
-  void* scratch = nullptr;            // one allocation: everything GateView names and the staging of the host form
   uint8_t* stage_keep = nullptr;      // [edge_capacity]
   int32_t* stage_support = nullptr;   // [edge_capacity]
   int32_t* stage_map = nullptr;       // [edge_capacity]
@@ -28,23 +26,22 @@ struct pr_gate {
 
 namespace {
 
+using pr::at;
 using pr::fail;
 
 constexpr int32_t MAX_NODES = 1 << 20, MAX_EDGES = 65536, MAX_GAP = 65535, MAX_ROUNDS = 64;
 
 // where the parts of the one scratch allocation lie (each on a 16-byte boundary); the formula of the header
-struct Layout {
-  size_t lmn, eij, valid, keep0, keep1, sup, map, rot, trans, ctl, s_keep, s_support, s_map, s_info, total;
+struct Layout : pr::Arena {
+  size_t lmn, eij, valid, keep0, keep1, sup, map, rot, trans, ctl, s_keep, s_support, s_map, s_info;
 };
 
 Layout layout_of(int32_t edge_capacity, int32_t max_gap) {
   const size_t EC = (size_t)edge_capacity, G = (size_t)max_gap + 1;
   Layout l;
-  l.total = 0;
-  auto take = [&l](size_t bytes) { const size_t o = l.total; l.total += (bytes + 15) & ~(size_t)15; return o; };
-  l.lmn = take(8 * pr::GATE_LMN * EC); l.eij = take(8 * EC); l.valid = take(4 * EC); l.keep0 = take(4 * EC); l.keep1 = take(4 * EC);
-  l.sup = take(4 * EC); l.map = take(4 * EC); l.rot = take(8 * G); l.trans = take(8 * G); l.ctl = take(16);
-  l.s_keep = take(EC); l.s_support = take(4 * EC); l.s_map = take(4 * EC); l.s_info = take(16);
+  l.lmn = l.take(8 * pr::GATE_LMN * EC); l.eij = l.take(8 * EC); l.valid = l.take(4 * EC); l.keep0 = l.take(4 * EC); l.keep1 = l.take(4 * EC);
+  l.sup = l.take(4 * EC); l.map = l.take(4 * EC); l.rot = l.take(8 * G); l.trans = l.take(8 * G); l.ctl = l.take(16);
+  l.s_keep = l.take(EC); l.s_support = l.take(4 * EC); l.s_map = l.take(4 * EC); l.s_info = l.take(16);
   return l;
 }
 
@@ -89,54 +86,32 @@ int pr_gate_create(pr_ctx* ctx, const pr_posegraph_buffers* src, const pr_posegr
     if (std::isnan(trans2_tab[g]) || trans2_tab[g] < 0.0) return fail(ctx, PR_EINVAL, "pr_gate_create: trans2_tab[%d] is NaN or negative", g);
   }
   if (!ctx) return fail(nullptr, PR_EINVAL, "pr_gate_create: ctx is NULL");
-  PR_CHECK_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
-  pr_gate* g = new (std::nothrow) pr_gate;
-  if (!g) return fail(ctx, PR_ENOMEM, "out of host memory");
-  g->ctx = ctx;
+  const Layout l = layout_of(edge_capacity, params->max_gap);
+  pr::Owned<pr_gate> g;
+  if (int rc = pr::make(ctx, "pr_gate_create", l.total, g)) return rc;
   pr::GateView& v = g->v;
   memset(&v, 0, sizeof v);
   v.s_ij = src->edge_ij; v.s_Z = src->edge_Z; v.s_w = src->edge_w; v.s_state = src->state;
   v.d_ij = dst->edge_ij; v.d_Z = dst->edge_Z; v.d_w = dst->edge_w; v.d_state = dst->state;
   v.node_capacity = node_capacity; v.edge_capacity = edge_capacity;
   v.max_gap = params->max_gap; v.min_support = params->min_support; v.rounds = params->rounds;
-  const Layout l = layout_of(edge_capacity, params->max_gap);
-  hipError_t e = hipMalloc(&g->scratch, l.total);
-  if (e != hipSuccess) {
-    delete g;
-    return fail(ctx, e == hipErrorOutOfMemory ? PR_ENOMEM : PR_EHIP, "pr_gate_create: scratch of %zu bytes: %s", l.total, hipGetErrorString(e));
-  }
-  char* b = static_cast<char*>(g->scratch);
-  auto ip = [b](size_t o) { return reinterpret_cast<int*>(b + o); };
-  double* rot = reinterpret_cast<double*>(b + l.rot);
-  double* trans = reinterpret_cast<double*>(b + l.trans);
-  v.lmn = reinterpret_cast<double*>(b + l.lmn);
-  v.eij = ip(l.eij); v.valid = ip(l.valid); v.keep[0] = ip(l.keep0); v.keep[1] = ip(l.keep1); v.sup = ip(l.sup); v.map = ip(l.map);
-  v.rot_tab = rot; v.trans2_tab = trans; v.ctl = ip(l.ctl);
-  g->stage_keep = reinterpret_cast<uint8_t*>(b + l.s_keep);
-  g->stage_support = ip(l.s_support); g->stage_map = ip(l.s_map); g->stage_info = ip(l.s_info);
-  hipStream_t st = pr::ctx_stream(ctx);
+  void* b = g->scratch;
+  double* rot = at<double>(b, l.rot);
+  double* trans = at<double>(b, l.trans);
+  v.lmn = at<double>(b, l.lmn); v.eij = at<int>(b, l.eij); v.valid = at<int>(b, l.valid);
+  v.keep[0] = at<int>(b, l.keep0); v.keep[1] = at<int>(b, l.keep1); v.sup = at<int>(b, l.sup); v.map = at<int>(b, l.map);
+  v.rot_tab = rot; v.trans2_tab = trans; v.ctl = at<int>(b, l.ctl);
+  g->stage_keep = at<uint8_t>(b, l.s_keep); g->stage_support = at<int32_t>(b, l.s_support);
+  g->stage_map = at<int32_t>(b, l.s_map); g->stage_info = at<int32_t>(b, l.s_info);
   const size_t G = (size_t)params->max_gap + 1;
-  e = hipMemsetAsync(g->scratch, 0, l.total, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(rot, rot_tab, 8 * G, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(trans, trans2_tab, 8 * G, hipMemcpyHostToDevice, st);
-  const hipError_t es = hipStreamSynchronize(st);                // the host tables are in flight until here
-  if (e == hipSuccess) e = es;
-  if (e != hipSuccess) {
-    (void)hipFree(g->scratch);
-    delete g;
-    return fail(ctx, PR_EHIP, "pr_gate_create: clearing the scratch and uploading the tables failed: %s", hipGetErrorString(e));
-  }
-  *out = g;
-  return PR_OK;
+  pr::Transfer t(ctx);
+  t.fill(b, 0, l.total);
+  t.up(rot, rot_tab, 8 * G);
+  t.up(trans, trans2_tab, 8 * G);
+  return pr::commit(g, t, "pr_gate_create", out);
 }
 
-void pr_gate_destroy(pr_gate* g) {
-  if (!g) return;
-  (void)hipSetDevice(pr::ctx_device(g->ctx));
-  (void)hipStreamSynchronize(pr::ctx_stream(g->ctx));
-  (void)hipFree(g->scratch);          // the buffers of both logs are the caller's
-  delete g;
-}
+void pr_gate_destroy(pr_gate* g) { pr::destroy(g); }            // the buffers of both logs are the caller's
 
 int pr_gate_run_dev(pr_gate* g, const double* d_poses, const int32_t* d_n, uint8_t* d_keep, int32_t* d_support, int32_t* d_map, int32_t* d_info) {
   if (!g) return fail(nullptr, PR_EINVAL, "pr_gate_run_dev: gate is NULL");
@@ -152,19 +127,17 @@ int pr_gate_run(pr_gate* g, const double* d_poses, const int32_t* d_n, uint8_t* 
   if (!g) return fail(nullptr, PR_EINVAL, "pr_gate_run: gate is NULL");
   pr_ctx* ctx = g->ctx;
   if (!d_poses || !d_n || !info) return fail(ctx, PR_EINVAL, "pr_gate_run: a required pointer is NULL (d_poses, d_n, info)");
-  if (int rc = pr_gate_run_dev(g, d_poses, d_n, keep ? g->stage_keep : nullptr, support ? g->stage_support : nullptr,
-                               map ? g->stage_map : nullptr, g->stage_info))
-    return rc;
-  hipStream_t st = pr::ctx_stream(ctx);
   const size_t EC = (size_t)g->v.edge_capacity;
-  hipError_t e = hipMemcpyAsync(info, g->stage_info, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess && keep) e = hipMemcpyAsync(keep, g->stage_keep, EC, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess && support) e = hipMemcpyAsync(support, g->stage_support, 4 * EC, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess && map) e = hipMemcpyAsync(map, g->stage_map, 4 * EC, hipMemcpyDeviceToHost, st);
-  const hipError_t es = hipStreamSynchronize(st);                // the host arrays are in flight until here
-  if (e == hipSuccess) e = es;
-  if (e != hipSuccess) return fail(ctx, pr::hip_code(e), "pr_gate_run: %s", hipGetErrorString(e));
-  return PR_OK;
+  pr::Transfer t(ctx);
+  t.run([&] {
+    return pr_gate_run_dev(g, d_poses, d_n, keep ? g->stage_keep : nullptr, support ? g->stage_support : nullptr, map ? g->stage_map : nullptr,
+                           g->stage_info);
+  });
+  t.down(info, g->stage_info, 4 * sizeof(int32_t));
+  t.down(keep, g->stage_keep, EC);
+  t.down(support, g->stage_support, 4 * EC);
+  t.down(map, g->stage_map, 4 * EC);
+  return t.finish(ctx, "pr_gate_run");
 }
 
 }  // extern "C"

@@ -1,5 +1,6 @@
 // host_common.hpp — what the host files of the library share: an error return that leaves its text in the context, and the check of a
-// HIP call.  (pr_api.cpp's PR_HIP / PRE_HIP and pr_group.cpp's G_HIP report in other shapes and stay where they are.)
+// HIP call.  (pr_api.cpp's PR_HIP / PRE_HIP and pr_group.cpp's G_HIP report in other shapes and stay where they are.)  What the resident
+// handle families share on top of this - layout arena, handle base, create tail, transfer chain, state word - is handle_core.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -9,7 +9,7 @@
 #include <new>
 
 #include "../../include/place_recognition.h"
-#include "host_common.hpp"
+#include "handle_core.hpp"
 #include "kernels.hpp"
 
 static_assert(pr::MAP_OVERFLOW == PR_MAP_OVERFLOW && pr::MAP_DROPPED == PR_MAP_DROPPED, "flag bits");
@@ -21,6 +21,7 @@ struct pr_map {
 
 namespace {
 
+using pr::at;
 using pr::fail;
 
 // offs, frames and state to zero on the stream: what create and reset leave (the invariants of DESIGN.md 4.15)
@@ -38,8 +39,6 @@ struct Staging {
   void* p = nullptr;
   ~Staging() { if (p) (void)hipFree(p); }
 };
-
-size_t up16(size_t n) { return (n + 15) & ~(size_t)15; }
 
 }  // namespace
 
@@ -102,14 +101,12 @@ int pr_map_reset(pr_map* m) {
 int pr_map_count(pr_map* m, int32_t* keyframes, int64_t* points, int32_t* flags) {
   if (!m) return fail(nullptr, PR_EINVAL, "pr_map_count: map is NULL");
   if (!keyframes || !points || !flags) return fail(m->ctx, PR_EINVAL, "pr_map_count: a required pointer is NULL");
-  PR_CHECK_HIP(m->ctx, hipSetDevice(pr::ctx_device(m->ctx)));
-  hipStream_t st = pr::ctx_stream(m->ctx);
   int32_t s[4];
-  PR_CHECK_HIP(m->ctx, hipMemcpyAsync(s, m->v.state, sizeof s, hipMemcpyDeviceToHost, st));
-  PR_CHECK_HIP(m->ctx, hipStreamSynchronize(st));
+  if (int rc = pr::read_state(m->ctx, "pr_map_count", m->v.state, s)) return rc;
   const int32_t k = std::min(std::max(s[0], 0), m->v.kcap);
-  PR_CHECK_HIP(m->ctx, hipMemcpyAsync(points, m->v.offs + k, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-  PR_CHECK_HIP(m->ctx, hipStreamSynchronize(st));
+  pr::Transfer t(m->ctx);
+  t.down(points, m->v.offs + k, sizeof(int64_t));
+  if (int rc = t.finish(m->ctx, "pr_map_count")) return rc;
   *keyframes = s[0];
   *flags = s[1];
   return PR_OK;
@@ -147,45 +144,38 @@ int pr_map_append(pr_map* m, const double* xyz, const float* inten, const int64_
   const int64_t npts = hi - lo;
   if (npts > 0 && (!xyz || !inten)) return fail(ctx, PR_EINVAL, "pr_map_append: a required pointer is NULL");
   PR_CHECK_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
-  hipStream_t st = pr::ctx_stream(ctx);
   const size_t n = (size_t)N, np = (size_t)npts;
-  const size_t o_xyz = 0, o_int = o_xyz + up16(np * 24), o_offs = o_int + up16(np * 4), o_fr = o_offs + up16((n + 1) * 8),
-               o_pose = o_fr + up16(n * 128), o_ids = o_pose + up16(n * 96), o_emit = o_ids + up16(n * 4), o_info = o_emit + 16,
-               total = o_info + 16;
-  Staging s;
-  PR_CHECK_HIP(ctx, hipMalloc(&s.p, total));
-  char* b = static_cast<char*>(s.p);
-  if (np) {
-    PR_CHECK_HIP(ctx, hipMemcpyAsync(b + o_xyz, xyz + 3 * lo, np * 24, hipMemcpyHostToDevice, st));
-    PR_CHECK_HIP(ctx, hipMemcpyAsync(b + o_int, inten + lo, np * 4, hipMemcpyHostToDevice, st));
-  }
-  int64_t* rel = nullptr;                          // the offsets counted from the first uploaded point
+  pr::Arena a;
+  const size_t o_xyz = a.take(np * 24), o_int = a.take(np * 4), o_offs = a.take((n + 1) * 8), o_fr = a.take(n * 128), o_pose = a.take(n * 96),
+               o_ids = a.take(n * 4), o_emit = a.take(16), o_info = a.take(16);
+  std::unique_ptr<int64_t[]> rel;                  // the offsets counted from the first uploaded point
   if (N > 0) {
-    rel = new (std::nothrow) int64_t[n + 1];
+    rel.reset(new (std::nothrow) int64_t[n + 1]);
     if (!rel) return fail(ctx, PR_ENOMEM, "out of host memory");
     for (size_t i = 0; i <= n; i++) rel[i] = offs[i] - lo;
   }
-  hipError_t e = hipSuccess;
-  if (N > 0) {
-    e = hipMemcpyAsync(b + o_offs, rel, (n + 1) * 8, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(b + o_fr, frames, n * 128, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && poses) e = hipMemcpyAsync(b + o_pose, poses, n * 96, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && ids) e = hipMemcpyAsync(b + o_ids, ids, n * 4, hipMemcpyHostToDevice, st);
+  Staging s;                                       // (rel and the staging outlive the synchronise of finish)
+  PR_CHECK_HIP(ctx, hipMalloc(&s.p, a.total));
+  void* b = s.p;
+  pr::Transfer t(ctx);
+  if (np) {
+    t.up(at<double>(b, o_xyz), xyz + 3 * lo, np * 24);
+    t.up(at<float>(b, o_int), inten + lo, np * 4);
   }
-  if (e == hipSuccess && emitted) e = hipMemcpyAsync(b + o_emit, emitted, 4, hipMemcpyHostToDevice, st);
-  int rc = PR_OK;
-  if (e == hipSuccess)
-    rc = pr_map_append_dev(m, reinterpret_cast<double*>(b + o_xyz), reinterpret_cast<float*>(b + o_int), reinterpret_cast<int64_t*>(b + o_offs),
-                           reinterpret_cast<double*>(b + o_fr), poses ? reinterpret_cast<double*>(b + o_pose) : nullptr,
-                           ids ? reinterpret_cast<int32_t*>(b + o_ids) : nullptr, emitted ? reinterpret_cast<int32_t*>(b + o_emit) : nullptr, N,
-                           npts, reinterpret_cast<int32_t*>(b + o_info));
-  if (e == hipSuccess && rc == PR_OK) e = hipMemcpyAsync(info, b + o_info, 16, hipMemcpyDeviceToHost, st);
-  const hipError_t e2 = hipStreamSynchronize(st);   // rel and the staging are in flight until here
-  delete[] rel;
-  if (rc != PR_OK) return rc;
-  PR_CHECK_HIP(ctx, e);
-  PR_CHECK_HIP(ctx, e2);
-  return PR_OK;
+  if (N > 0) {
+    t.up(at<int64_t>(b, o_offs), rel.get(), (n + 1) * 8);
+    t.up(at<double>(b, o_fr), frames, n * 128);
+    t.up_opt(at<double>(b, o_pose), poses, n * 96);
+    t.up_opt(at<int32_t>(b, o_ids), ids, n * 4);
+  }
+  t.up_opt(at<int32_t>(b, o_emit), emitted, 4);
+  t.run([&] {
+    return pr_map_append_dev(m, at<double>(b, o_xyz), at<float>(b, o_int), at<int64_t>(b, o_offs), at<double>(b, o_fr),
+                             poses ? at<double>(b, o_pose) : nullptr, ids ? at<int32_t>(b, o_ids) : nullptr,
+                             emitted ? at<int32_t>(b, o_emit) : nullptr, N, npts, at<int32_t>(b, o_info));
+  });
+  t.down(info, at<int32_t>(b, o_info), 16);
+  return t.finish(ctx, "pr_map_append");
 }
 
 int pr_map_verify_dev(pr_map* m, int type, const double* d_xyz_q, const int64_t* d_offs_q, int32_t Nq, const double* d_frames_q, int32_t mq,

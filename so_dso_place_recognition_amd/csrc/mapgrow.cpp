@@ -1,24 +1,21 @@
 // mapgrow.cpp — host side of the incremental world map (mapgrow.hip): the opaque pr_mapgrow over a pr_worldmap and the
 // pr_maploc created over the same world buffer record, its ONE scratch allocation, the argument checks, the stream-ordered sync / extend /
-// normals and their host forms.
+// normals and their host forms, on the shared handle core (handle_core.hpp).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <new>
 #include <vector>
 
 #include "../../include/place_recognition.h"
-#include "host_common.hpp"
+#include "handle_core.hpp"
 #include "kernels.hpp"
 
 static_assert(pr::MAPGROW_ORDER == PR_MAPGROW_ORDER && pr::MAPGROW_STALE == PR_MAPGROW_STALE && pr::MAPGROW_FULL == PR_MAPGROW_FULL, "flag bits");
 
-struct pr_mapgrow {
-  pr_ctx* ctx = nullptr;
+struct pr_mapgrow : pr::Handle {     // scratch: everything MapGrowView names of its own and the staging of the host forms
   pr::MapGrowView v;
-  void* scratch = nullptr;            // one allocation: everything MapGrowView names of its own and the staging of the host forms
   double* stage_pose = nullptr;       // [12]: the call's pose row
   int32_t* stage_row = nullptr;       // [4]
   int64_t* stage_info = nullptr;      // [4]
@@ -29,19 +26,18 @@ struct pr_mapgrow {
 
 namespace {
 
+using pr::at;
 using pr::fail;
 
 // where the parts of the one scratch allocation lie (each on a 16-byte boundary); the formula of the header
-struct Layout { size_t ctl, slot_of, blk, s_pose, s_row, s_info, s_normals, s_ninfo, s_rows, total; };
+struct Layout : pr::Arena { size_t ctl, slot_of, blk, s_pose, s_row, s_info, s_normals, s_ninfo, s_rows; };
 
 Layout layout_of(int32_t mcp) {
   const size_t m = (size_t)mcp, nblk = (m + 255) / 256;
   Layout l;
-  l.total = 0;
-  auto take = [&l](size_t bytes) { const size_t o = l.total; l.total += (bytes + 15) & ~(size_t)15; return o; };
-  l.ctl = take(64); l.slot_of = take(4 * m); l.blk = take(8 * nblk);
-  l.s_pose = take(96); l.s_row = take(16); l.s_info = take(32);
-  l.s_normals = take(648 * m); l.s_ninfo = take(108 * m); l.s_rows = take(108 * m);
+  l.ctl = l.take(64); l.slot_of = l.take(4 * m); l.blk = l.take(8 * nblk);
+  l.s_pose = l.take(96); l.s_row = l.take(16); l.s_info = l.take(32);
+  l.s_normals = l.take(648 * m); l.s_ninfo = l.take(108 * m); l.s_rows = l.take(108 * m);
   return l;
 }
 
@@ -83,60 +79,35 @@ int pr_mapgrow_create(pr_ctx* ctx, pr_worldmap* wm, pr_maploc* ml, pr_mapgrow** 
     return fail(ctx, PR_EINVAL, "pr_mapgrow_create: the localiser was created over another world buffer record or out_capacity");
   const int32_t mcp = pr::worldmap_max_cloud(wm);
   if (!sizes_ok(mcp)) return fail(ctx, PR_EINVAL, "pr_mapgrow_create: the map's max_cloud_points=%d outside 1 .. 2^26", mcp);
-  PR_CHECK_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
-  pr_mapgrow* mg = new (std::nothrow) pr_mapgrow;
-  if (!mg) return fail(ctx, PR_ENOMEM, "out of host memory");
-  mg->ctx = ctx;
+  const Layout lay = layout_of(mcp);
+  pr::Owned<pr_mapgrow> mg;
+  if (int rc = pr::make(ctx, "pr_mapgrow_create", lay.total, mg)) return rc;
   pr::MapGrowView& v = mg->v;
   memset(&v, 0, sizeof v);
   v.w = w;
   v.table = l.table; v.ml_ctl = l.ctl; v.offs2 = l.offs2;
   v.cell = l.cell; v.log2T = l.log2T;
   v.mcp = mcp; v.nblk = (mcp + 255) / 256;
-  const Layout lay = layout_of(mcp);
-  hipError_t e = hipMalloc(&mg->scratch, lay.total);
-  if (e != hipSuccess) {
-    delete mg;
-    return fail(ctx, e == hipErrorOutOfMemory ? PR_ENOMEM : PR_EHIP, "pr_mapgrow_create: scratch of %zu bytes: %s", lay.total, hipGetErrorString(e));
-  }
-  char* b = static_cast<char*>(mg->scratch);
-  v.ctl = reinterpret_cast<int*>(b + lay.ctl);
-  v.slot_of = reinterpret_cast<int*>(b + lay.slot_of);
-  v.blk = reinterpret_cast<int*>(b + lay.blk);
-  mg->stage_pose = reinterpret_cast<double*>(b + lay.s_pose);
-  mg->stage_row = reinterpret_cast<int32_t*>(b + lay.s_row);
-  mg->stage_info = reinterpret_cast<int64_t*>(b + lay.s_info);
-  mg->stage_normals = reinterpret_cast<double*>(b + lay.s_normals);
-  mg->stage_ninfo = reinterpret_cast<int32_t*>(b + lay.s_ninfo);
-  mg->stage_rows = reinterpret_cast<int32_t*>(b + lay.s_rows);
-  hipStream_t st = pr::ctx_stream(ctx);
-  e = hipMemsetAsync(mg->scratch, 0, lay.total, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) {
-    (void)hipFree(mg->scratch);
-    delete mg;
-    return fail(ctx, PR_EHIP, "pr_mapgrow_create: clearing the scratch failed: %s", hipGetErrorString(e));
-  }
-  *out = mg;
-  return PR_OK;
+  void* b = mg->scratch;
+  v.ctl = at<int>(b, lay.ctl); v.slot_of = at<int>(b, lay.slot_of); v.blk = at<int>(b, lay.blk);
+  mg->stage_pose = at<double>(b, lay.s_pose); mg->stage_row = at<int32_t>(b, lay.s_row); mg->stage_info = at<int64_t>(b, lay.s_info);
+  mg->stage_normals = at<double>(b, lay.s_normals); mg->stage_ninfo = at<int32_t>(b, lay.s_ninfo); mg->stage_rows = at<int32_t>(b, lay.s_rows);
+  pr::Transfer t(ctx);
+  t.fill(b, 0, lay.total);
+  return pr::commit(mg, t, "pr_mapgrow_create", out);
 }
 
-void pr_mapgrow_destroy(pr_mapgrow* mg) {
-  if (!mg) return;
-  (void)hipSetDevice(pr::ctx_device(mg->ctx));
-  (void)hipStreamSynchronize(pr::ctx_stream(mg->ctx));
-  (void)hipFree(mg->scratch);         // the world map, the localiser and the world buffers are the caller's
-  delete mg;
-}
+// the world map, the localiser and the world buffers are the caller's
+void pr_mapgrow_destroy(pr_mapgrow* mg) { pr::destroy(mg); }
 
 int pr_mapgrow_count(pr_mapgrow* mg, int32_t* fused, int64_t* rows, int32_t* flags) {
   if (!mg) return fail(nullptr, PR_EINVAL, "pr_mapgrow_count: grower is NULL");
   if (!fused || !rows || !flags) return fail(mg->ctx, PR_EINVAL, "pr_mapgrow_count: a required pointer is NULL");
   PR_CHECK_HIP(mg->ctx, hipSetDevice(pr::ctx_device(mg->ctx)));
-  hipStream_t st = pr::ctx_stream(mg->ctx);
   int32_t s[8];
-  PR_CHECK_HIP(mg->ctx, hipMemcpyAsync(s, mg->v.ctl, sizeof s, hipMemcpyDeviceToHost, st));
-  PR_CHECK_HIP(mg->ctx, hipStreamSynchronize(st));
+  pr::Transfer t(mg->ctx);
+  t.down(s, mg->v.ctl, sizeof s);
+  if (int rc = t.finish(mg->ctx, "pr_mapgrow_count")) return rc;
   *fused = s[pr::MG_FUSED];
   *rows = s[pr::MG_SEEN];
   *flags = s[pr::MG_LAST];
@@ -178,21 +149,18 @@ int pr_mapgrow_extend(pr_mapgrow* mg, const double* poses, int32_t row, int64_t*
   if (!info) return fail(ctx, PR_EINVAL, "%s: info is NULL", fn);
   if (!mg) return fail(nullptr, PR_EINVAL, "%s: grower is NULL", fn);
   PR_CHECK_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
-  hipStream_t st = pr::ctx_stream(ctx);
   const pr::MapGrowView& v = mg->v;
   // the staging holds ONE pose row: the call's (a row outside the map is refused on the device and its pose never read)
   const bool own = poses && row >= 0 && row < v.w.kcap;
-  hipError_t e = hipMemcpyAsync(mg->stage_row, &row, sizeof row, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess && own) e = hipMemcpyAsync(mg->stage_pose, poses + 12 * (size_t)row, 96, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) {
-    pr::launch_mapgrow_extend(st, v, poses ? mg->stage_pose : v.w.m_poses, poses ? 1 : 0, mg->stage_row, mg->stage_info);
-    e = hipGetLastError();
+  pr::Transfer t(ctx);
+  t.up(mg->stage_row, &row, sizeof row);
+  if (own) t.up(mg->stage_pose, poses + 12 * (size_t)row, 96);
+  if (t.ok()) {
+    pr::launch_mapgrow_extend(t.st, v, poses ? mg->stage_pose : v.w.m_poses, poses ? 1 : 0, mg->stage_row, mg->stage_info);
+    t.note(hipGetLastError());
   }
-  if (e == hipSuccess) e = hipMemcpyAsync(info, mg->stage_info, 4 * sizeof(int64_t), hipMemcpyDeviceToHost, st);
-  const hipError_t es = hipStreamSynchronize(st);                 // the host words are in flight until here
-  if (e == hipSuccess) e = es;
-  if (e != hipSuccess) return fail(ctx, pr::hip_code(e), "%s: %s", fn, hipGetErrorString(e));
-  return PR_OK;
+  t.down(info, mg->stage_info, 4 * sizeof(int64_t));
+  return t.finish(ctx, fn);
 }
 
 int pr_mapgrow_normals(pr_mapgrow* mg, double radius, int32_t min_nbrs, double max_ratio, double* normals, int32_t* ninfo) {
@@ -200,15 +168,15 @@ int pr_mapgrow_normals(pr_mapgrow* mg, double radius, int32_t min_nbrs, double m
   if (int rc = check_normals(mg, fn, radius, min_nbrs, max_ratio, normals, ninfo)) return rc;
   pr_ctx* ctx = mg->ctx;
   PR_CHECK_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
-  hipStream_t st = pr::ctx_stream(ctx);
   const pr::MapGrowView& v = mg->v;
-  pr::launch_mapgrow_normals(st, v, radius * radius, min_nbrs, max_ratio, mg->stage_normals, mg->stage_ninfo, mg->stage_rows);
-  PR_CHECK_HIP(ctx, hipGetLastError());
+  pr::Transfer t(ctx);
+  pr::launch_mapgrow_normals(t.st, v, radius * radius, min_nbrs, max_ratio, mg->stage_normals, mg->stage_ninfo, mg->stage_rows);
+  t.note(hipGetLastError());
   int32_t s[4];
   int32_t state[4];
-  PR_CHECK_HIP(ctx, hipMemcpyAsync(s, v.ctl, sizeof s, hipMemcpyDeviceToHost, st));
-  PR_CHECK_HIP(ctx, hipMemcpyAsync(state, v.w.state, sizeof state, hipMemcpyDeviceToHost, st));
-  PR_CHECK_HIP(ctx, hipStreamSynchronize(st));
+  t.down(s, v.ctl, sizeof s);
+  t.down(state, v.w.state, sizeof state);
+  if (int rc = t.finish(ctx, fn)) return rc;
   // the kernel's own clamps: the range lies inside 0 .. R and holds at most max_cloud_points rows
   const int64_t R = std::min<int64_t>(std::max<int64_t>(state[0], 0), v.w.ocap);
   const int64_t a = std::min<int64_t>(std::max<int64_t>(s[pr::MG_A], 0), R), b = std::min<int64_t>(std::max<int64_t>(s[pr::MG_B], a), R);
@@ -216,10 +184,10 @@ int pr_mapgrow_normals(pr_mapgrow* mg, double radius, int32_t min_nbrs, double m
   if (!lanes) return PR_OK;
   std::vector<int32_t> rows(lanes), inf(lanes);
   std::vector<double> nrm(3 * lanes);
-  PR_CHECK_HIP(ctx, hipMemcpyAsync(rows.data(), mg->stage_rows, lanes * 4, hipMemcpyDeviceToHost, st));
-  PR_CHECK_HIP(ctx, hipMemcpyAsync(inf.data(), mg->stage_ninfo, lanes * 4, hipMemcpyDeviceToHost, st));
-  PR_CHECK_HIP(ctx, hipMemcpyAsync(nrm.data(), mg->stage_normals, lanes * 24, hipMemcpyDeviceToHost, st));
-  PR_CHECK_HIP(ctx, hipStreamSynchronize(st));
+  t.down(rows.data(), mg->stage_rows, lanes * 4);
+  t.down(inf.data(), mg->stage_ninfo, lanes * 4);
+  t.down(nrm.data(), mg->stage_normals, lanes * 24);
+  if (int rc = t.finish(ctx, fn)) return rc;
   for (size_t L = 0; L < lanes; L++) {
     const int32_t j = rows[L];
     if (j < 0 || j >= v.w.ocap) continue;

@@ -1,25 +1,23 @@
 // maploc.cpp — host side of the map localiser (maploc.hip): the opaque pr_maploc over three of a world map's caller-owned
-// buffers, its ONE scratch allocation, the argument checks, the stream-ordered index / seed / nn / refine and their host forms.
+// buffers, its ONE scratch allocation, the argument checks, the stream-ordered index / seed / nn / refine and their host forms, on the
+// shared handle core (handle_core.hpp).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
-#include <new>
 
 #include "../../include/place_recognition.h"
-#include "host_common.hpp"
+#include "handle_core.hpp"
 #include "kernels.hpp"
 
 static_assert(pr::MAPLOC_SKIPPED == PR_MAPLOC_SKIPPED && pr::MAPLOC_RANGE == PR_MAPLOC_RANGE && pr::MAPLOC_DUPLICATE == PR_MAPLOC_DUPLICATE &&
               pr::MAPLOC_TABLE == PR_MAPLOC_TABLE, "flag bits");
 static_assert(sizeof(pr::IcpStats) == sizeof(pr_icp_stats), "stats record");
 
-struct pr_maploc {
-  pr_ctx* ctx = nullptr;
+struct pr_maploc : pr::Handle {      // scratch: everything MapLocView names and the staging of the host forms
   pr::MapLocView v;
-  void* scratch = nullptr;            // one allocation: everything MapLocView names and the staging of the host forms
   double* stage_xyz = nullptr;        // [pair_capacity * ld][3]
   int64_t* stage_offs = nullptr;      // [pair_capacity + 1]
   int32_t* stage_src = nullptr;       // [pair_capacity]
@@ -32,24 +30,23 @@ struct pr_maploc {
 
 namespace {
 
+using pr::at;
 using pr::fail;
 
 // where the parts of the one scratch allocation lie (each on a 16-byte boundary); the formula of the header
-struct Layout {
+struct Layout : pr::Arena {
   size_t table, ctl, offs2, pair_dst, nn_d, nn_j, part, done, prev;
-  size_t s_xyz, s_offs, s_src, s_T, s_excl, s_out_offs, s_stats, s_info, total;
+  size_t s_xyz, s_offs, s_src, s_T, s_excl, s_out_offs, s_stats, s_info;
 };
 
 Layout layout_of(int64_t ocap, int32_t pcap, int32_t max_src) {
   const size_t T = (size_t)1 << pr::maploc_log2T(ocap), pc = (size_t)pcap, ld = (size_t)std::max(max_src, 1), nch = (ld + 255) / 256;
   Layout l;
-  l.total = 0;
-  auto take = [&l](size_t bytes) { const size_t o = l.total; l.total += (bytes + 15) & ~(size_t)15; return o; };
-  l.table = take(16 * T); l.ctl = take(16); l.offs2 = take(16); l.pair_dst = take(4 * pc);
-  l.nn_d = take(8 * pc * ld); l.nn_j = take(4 * pc * ld); l.part = take(8 * pc * nch * pr::ICP_PARTIAL);
-  l.done = take(4 * pc); l.prev = take(16 * pc);
-  l.s_xyz = take(24 * pc * ld); l.s_offs = take(8 * (pc + 1)); l.s_src = take(4 * pc); l.s_T = take(96 * pc); l.s_excl = take(8 * pc);
-  l.s_out_offs = take(8 * (pc + 1)); l.s_stats = take(32 * pc); l.s_info = take(32);
+  l.table = l.take(16 * T); l.ctl = l.take(16); l.offs2 = l.take(16); l.pair_dst = l.take(4 * pc);
+  l.nn_d = l.take(8 * pc * ld); l.nn_j = l.take(4 * pc * ld); l.part = l.take(8 * pc * nch * pr::ICP_PARTIAL);
+  l.done = l.take(4 * pc); l.prev = l.take(16 * pc);
+  l.s_xyz = l.take(24 * pc * ld); l.s_offs = l.take(8 * (pc + 1)); l.s_src = l.take(4 * pc); l.s_T = l.take(96 * pc); l.s_excl = l.take(8 * pc);
+  l.s_out_offs = l.take(8 * (pc + 1)); l.s_stats = l.take(32 * pc); l.s_info = l.take(32);
   return l;
 }
 
@@ -95,14 +92,13 @@ int host_shapes(pr_maploc* ml, const char* fn, const int64_t* offs_q, int32_t Nq
   return PR_OK;
 }
 
-hipError_t upload_pairs(pr_maploc* ml, hipStream_t st, const double* xyz_q, const int64_t* offs_q, int32_t Nq, const int32_t* pair_src, int32_t c,
-                        const double* T, const int32_t* excl) {
-  hipError_t e = hipMemcpyAsync(ml->stage_offs, offs_q, ((size_t)Nq + 1) * 8, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess && offs_q[Nq] > 0) e = hipMemcpyAsync(ml->stage_xyz, xyz_q, (size_t)offs_q[Nq] * 24, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess && c > 0) e = hipMemcpyAsync(ml->stage_src, pair_src, (size_t)c * 4, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess && c > 0) e = hipMemcpyAsync(ml->stage_T, T, (size_t)c * 96, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess && c > 0 && excl) e = hipMemcpyAsync(ml->stage_excl, excl, (size_t)c * 8, hipMemcpyHostToDevice, st);
-  return e;
+void upload_pairs(pr::Transfer& t, pr_maploc* ml, const double* xyz_q, const int64_t* offs_q, int32_t Nq, const int32_t* pair_src, int32_t c,
+                  const double* T, const int32_t* excl) {
+  t.up(ml->stage_offs, offs_q, ((size_t)Nq + 1) * 8);
+  t.up(ml->stage_xyz, xyz_q, (size_t)offs_q[Nq] * 24);
+  t.up(ml->stage_src, pair_src, (size_t)c * 4);
+  t.up(ml->stage_T, T, (size_t)c * 96);
+  t.up_opt(ml->stage_excl, excl, (size_t)c * 8);
 }
 
 }  // namespace
@@ -132,70 +128,36 @@ int pr_maploc_create(pr_ctx* ctx, const pr_worldmap_buffers* world, int64_t out_
   if (pair_capacity < 1 || pair_capacity > 65535) return fail(ctx, PR_EINVAL, "pr_maploc_create: pair_capacity=%d outside 1 .. 65535", pair_capacity);
   if (max_src_pts < 0 || max_src_pts > (1 << 26)) return fail(ctx, PR_EINVAL, "pr_maploc_create: max_src_pts=%d outside 0 .. 2^26", max_src_pts);
   if (!ctx) return fail(nullptr, PR_EINVAL, "pr_maploc_create: ctx is NULL");
-  PR_CHECK_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
-  pr_maploc* ml = new (std::nothrow) pr_maploc;
-  if (!ml) return fail(ctx, PR_ENOMEM, "out of host memory");
-  ml->ctx = ctx;
+  const Layout l = layout_of(out_capacity, pair_capacity, max_src_pts);
+  pr::Owned<pr_maploc> ml;
+  if (int rc = pr::make(ctx, "pr_maploc_create", l.total, ml)) return rc;
   pr::MapLocView& v = ml->v;
   memset(&v, 0, sizeof v);
   v.xyz = world->xyz; v.row = world->row; v.state = world->state;
   v.ocap = out_capacity; v.cell = cell;
   v.log2T = pr::maploc_log2T(out_capacity);
   v.pair_cap = pair_capacity; v.max_src = max_src_pts; v.ld = std::max(max_src_pts, 1); v.nchunks = (v.ld + 255) / 256;
-  const Layout l = layout_of(out_capacity, pair_capacity, max_src_pts);
-  hipError_t e = hipMalloc(&ml->scratch, l.total);
-  if (e != hipSuccess) {
-    delete ml;
-    return fail(ctx, e == hipErrorOutOfMemory ? PR_ENOMEM : PR_EHIP, "pr_maploc_create: scratch of %zu bytes: %s", l.total, hipGetErrorString(e));
-  }
-  char* b = static_cast<char*>(ml->scratch);
-  v.table = reinterpret_cast<unsigned long long*>(b + l.table);
-  v.ctl = reinterpret_cast<int*>(b + l.ctl);
-  v.offs2 = reinterpret_cast<int64_t*>(b + l.offs2);
-  v.pair_dst = reinterpret_cast<int*>(b + l.pair_dst);
-  v.nn_d = reinterpret_cast<double*>(b + l.nn_d);
-  v.nn_j = reinterpret_cast<int*>(b + l.nn_j);
-  v.part = reinterpret_cast<double*>(b + l.part);
-  v.done = reinterpret_cast<int*>(b + l.done);
-  v.prev = reinterpret_cast<double*>(b + l.prev);
-  ml->stage_xyz = reinterpret_cast<double*>(b + l.s_xyz);
-  ml->stage_offs = reinterpret_cast<int64_t*>(b + l.s_offs);
-  ml->stage_src = reinterpret_cast<int32_t*>(b + l.s_src);
-  ml->stage_T = reinterpret_cast<double*>(b + l.s_T);
-  ml->stage_excl = reinterpret_cast<int32_t*>(b + l.s_excl);
-  ml->stage_out_offs = reinterpret_cast<int64_t*>(b + l.s_out_offs);
-  ml->stage_stats = reinterpret_cast<pr_icp_stats*>(b + l.s_stats);
-  ml->stage_info = reinterpret_cast<int64_t*>(b + l.s_info);
-  hipStream_t st = pr::ctx_stream(ctx);
+  void* b = ml->scratch;
+  v.table = at<unsigned long long>(b, l.table); v.ctl = at<int>(b, l.ctl); v.offs2 = at<int64_t>(b, l.offs2); v.pair_dst = at<int>(b, l.pair_dst);
+  v.nn_d = at<double>(b, l.nn_d); v.nn_j = at<int>(b, l.nn_j); v.part = at<double>(b, l.part); v.done = at<int>(b, l.done);
+  v.prev = at<double>(b, l.prev);
+  ml->stage_xyz = at<double>(b, l.s_xyz); ml->stage_offs = at<int64_t>(b, l.s_offs); ml->stage_src = at<int32_t>(b, l.s_src);
+  ml->stage_T = at<double>(b, l.s_T); ml->stage_excl = at<int32_t>(b, l.s_excl); ml->stage_out_offs = at<int64_t>(b, l.s_out_offs);
+  ml->stage_stats = at<pr_icp_stats>(b, l.s_stats); ml->stage_info = at<int64_t>(b, l.s_info);
   // everything to zero (pair_dst stays zero for the handle's life; offs2 = {0, 0}: an empty target until the first index), the table empty
-  e = hipMemsetAsync(ml->scratch, 0, l.total, st);
-  if (e == hipSuccess) e = hipMemsetAsync(v.table, 0xFF, 16 * ((size_t)1 << v.log2T), st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) {
-    (void)hipFree(ml->scratch);
-    delete ml;
-    return fail(ctx, PR_EHIP, "pr_maploc_create: clearing the scratch failed: %s", hipGetErrorString(e));
-  }
-  *out = ml;
-  return PR_OK;
+  pr::Transfer t(ctx);
+  t.fill(b, 0, l.total);
+  t.fill(v.table, 0xFF, 16 * ((size_t)1 << v.log2T));
+  return pr::commit(ml, t, "pr_maploc_create", out);
 }
 
-void pr_maploc_destroy(pr_maploc* ml) {
-  if (!ml) return;
-  (void)hipSetDevice(pr::ctx_device(ml->ctx));
-  (void)hipStreamSynchronize(pr::ctx_stream(ml->ctx));
-  (void)hipFree(ml->scratch);         // the world buffers are the caller's
-  delete ml;
-}
+void pr_maploc_destroy(pr_maploc* ml) { pr::destroy(ml); }      // the world buffers are the caller's
 
 int pr_maploc_count(pr_maploc* ml, int64_t* rows_indexed, int32_t* flags) {
   if (!ml) return fail(nullptr, PR_EINVAL, "pr_maploc_count: localiser is NULL");
   if (!rows_indexed || !flags) return fail(ml->ctx, PR_EINVAL, "pr_maploc_count: a required pointer is NULL");
-  PR_CHECK_HIP(ml->ctx, hipSetDevice(pr::ctx_device(ml->ctx)));
-  hipStream_t st = pr::ctx_stream(ml->ctx);
   int32_t s[4];
-  PR_CHECK_HIP(ml->ctx, hipMemcpyAsync(s, ml->v.ctl, sizeof s, hipMemcpyDeviceToHost, st));
-  PR_CHECK_HIP(ml->ctx, hipStreamSynchronize(st));
+  if (int rc = pr::read_state(ml->ctx, "pr_maploc_count", ml->v.ctl, s)) return rc;
   *flags = s[0];
   *rows_indexed = s[1];
   return PR_OK;
@@ -214,11 +176,10 @@ int pr_maploc_index(pr_maploc* ml, int64_t* info) {
   if (!ml) return fail(nullptr, PR_EINVAL, "pr_maploc_index: localiser is NULL");
   pr_ctx* ctx = ml->ctx;
   if (!info) return fail(ctx, PR_EINVAL, "pr_maploc_index: info is NULL");
-  if (int rc = pr_maploc_index_dev(ml, ml->stage_info)) return rc;
-  hipStream_t st = pr::ctx_stream(ctx);
-  PR_CHECK_HIP(ctx, hipMemcpyAsync(info, ml->stage_info, 4 * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-  PR_CHECK_HIP(ctx, hipStreamSynchronize(st));
-  return PR_OK;
+  pr::Transfer t(ctx);
+  t.run([&] { return pr_maploc_index_dev(ml, ml->stage_info); });
+  t.down(info, ml->stage_info, 4 * sizeof(int64_t));
+  return t.finish(ctx, "pr_maploc_index");
 }
 
 int pr_maploc_seed_dev(pr_maploc* ml, const double* d_poses, const int32_t* d_n, int32_t keyframe_capacity, const int32_t* d_idx,
@@ -294,20 +255,17 @@ int pr_maploc_nn(pr_maploc* ml, const double* xyz_q, const int64_t* offs_q, int3
   if (offs_q[Nq] > 0 && !xyz_q) return fail(ctx, PR_EINVAL, "%s: a required pointer is NULL", fn);
   if (total > 0 && (!nn_idx || !nn_d2)) return fail(ctx, PR_EINVAL, "%s: a required pointer is NULL", fn);
   PR_CHECK_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
-  hipStream_t st = pr::ctx_stream(ctx);
-  hipError_t e = upload_pairs(ml, st, xyz_q, offs_q, Nq, pair_src, c, T, excl);
-  int rc = PR_OK;
+  pr::Transfer t(ctx);
+  upload_pairs(t, ml, xyz_q, offs_q, Nq, pair_src, c, T, excl);
   // (the compacted rows fit the handle's own [pair_capacity][ld] arrays, which a pass of its own does not use)
-  if (e == hipSuccess)
-    rc = pr_maploc_nn_dev(ml, ml->stage_xyz, ml->stage_offs, Nq, ml->stage_src, c, ml->stage_T, excl ? ml->stage_excl : nullptr, max_corr,
-                          ml->stage_out_offs, ml->v.nn_j, ml->v.nn_d);
-  if (rc == PR_OK && e == hipSuccess) e = hipMemcpyAsync(out_offs, ml->stage_out_offs, ((size_t)c + 1) * 8, hipMemcpyDeviceToHost, st);
-  if (rc == PR_OK && e == hipSuccess && total > 0) e = hipMemcpyAsync(nn_idx, ml->v.nn_j, (size_t)total * 4, hipMemcpyDeviceToHost, st);
-  if (rc == PR_OK && e == hipSuccess && total > 0) e = hipMemcpyAsync(nn_d2, ml->v.nn_d, (size_t)total * 8, hipMemcpyDeviceToHost, st);
-  const hipError_t es = hipStreamSynchronize(st);                 // the host arrays are in flight until here
-  if (e == hipSuccess) e = es;
-  if (rc == PR_OK && e != hipSuccess) rc = fail(ctx, pr::hip_code(e), "%s: %s", fn, hipGetErrorString(e));
-  return rc;
+  t.run([&] {
+    return pr_maploc_nn_dev(ml, ml->stage_xyz, ml->stage_offs, Nq, ml->stage_src, c, ml->stage_T, excl ? ml->stage_excl : nullptr, max_corr,
+                            ml->stage_out_offs, ml->v.nn_j, ml->v.nn_d);
+  });
+  t.down(out_offs, ml->stage_out_offs, ((size_t)c + 1) * 8);
+  t.down(nn_idx, ml->v.nn_j, (size_t)total * 4);
+  t.down(nn_d2, ml->v.nn_d, (size_t)total * 8);
+  return t.finish(ctx, fn);
 }
 
 int pr_maploc_refine(pr_maploc* ml, const double* xyz_q, const int64_t* offs_q, int32_t Nq, const int32_t* pair_src, int32_t c, const double* T0,
@@ -323,18 +281,15 @@ int pr_maploc_refine(pr_maploc* ml, const double* xyz_q, const int64_t* offs_q, 
   if (offs_q[Nq] > 0 && !xyz_q) return fail(ctx, PR_EINVAL, "%s: a required pointer is NULL", fn);
   if (c == 0) return PR_OK;
   PR_CHECK_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
-  hipStream_t st = pr::ctx_stream(ctx);
-  hipError_t e = upload_pairs(ml, st, xyz_q, offs_q, Nq, pair_src, c, T0, excl);
-  int rc = PR_OK;
-  if (e == hipSuccess)                                             // in place: d_T_out = d_T0
-    rc = pr_maploc_refine_dev(ml, ml->stage_xyz, ml->stage_offs, Nq, ml->stage_src, c, ml->stage_T, excl ? ml->stage_excl : nullptr, max_iter,
-                              max_corr, tol_rmse, tol_fitness, min_inliers, ml->stage_T, ml->stage_stats);
-  if (rc == PR_OK && e == hipSuccess) e = hipMemcpyAsync(T_out, ml->stage_T, (size_t)c * 96, hipMemcpyDeviceToHost, st);
-  if (rc == PR_OK && e == hipSuccess) e = hipMemcpyAsync(stats, ml->stage_stats, (size_t)c * sizeof(pr_icp_stats), hipMemcpyDeviceToHost, st);
-  const hipError_t es = hipStreamSynchronize(st);
-  if (e == hipSuccess) e = es;
-  if (rc == PR_OK && e != hipSuccess) rc = fail(ctx, pr::hip_code(e), "%s: %s", fn, hipGetErrorString(e));
-  return rc;
+  pr::Transfer t(ctx);
+  upload_pairs(t, ml, xyz_q, offs_q, Nq, pair_src, c, T0, excl);
+  t.run([&] {                                                      // in place: d_T_out = d_T0
+    return pr_maploc_refine_dev(ml, ml->stage_xyz, ml->stage_offs, Nq, ml->stage_src, c, ml->stage_T, excl ? ml->stage_excl : nullptr, max_iter,
+                                max_corr, tol_rmse, tol_fitness, min_inliers, ml->stage_T, ml->stage_stats);
+  });
+  t.down(T_out, ml->stage_T, (size_t)c * 96);
+  t.down(stats, ml->stage_stats, (size_t)c * sizeof(pr_icp_stats));
+  return t.finish(ctx, fn);
 }
 
 }  // extern "C"

@@ -1,21 +1,19 @@
 // mapplane.cpp — host side of the plane-metric map localiser (mapplane.hip): the opaque pr_mapplane over a pr_maploc,
-// its ONE scratch allocation, the argument checks, the stream-ordered normals / refine and their host forms.
+// its ONE scratch allocation, the argument checks, the stream-ordered normals / refine and their host forms, on the shared handle core
+// (handle_core.hpp).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <new>
 
 #include "../../include/place_recognition.h"
-#include "host_common.hpp"
+#include "handle_core.hpp"
 #include "kernels.hpp"
 
-struct pr_mapplane {
-  pr_ctx* ctx = nullptr;
+struct pr_mapplane : pr::Handle {    // scratch: the refinement's arrays and the staging of the host forms
   pr_maploc* ml = nullptr;
   const pr::MapLocView* v = nullptr;  // the localiser's: table, cell, out_capacity, world record, offs2 of the last index, the create sizes
-  void* scratch = nullptr;            // one allocation
   double* nn_d = nullptr;             // [pair_capacity][ld]
   int* nn_j = nullptr;                // [pair_capacity][ld]
   double* part = nullptr;             // [pair_capacity][nchunks][MAPPLANE_SUMS]
@@ -33,22 +31,21 @@ struct pr_mapplane {
 
 namespace {
 
+using pr::at;
 using pr::fail;
 
 // where the parts of the one scratch allocation lie (each on a 16-byte boundary); the formula of the header
-struct Layout {
-  size_t nn_d, nn_j, part, done, prev, s_xyz, s_offs, s_src, s_T, s_excl, s_stats, s_normals, s_ninfo, total;
+struct Layout : pr::Arena {
+  size_t nn_d, nn_j, part, done, prev, s_xyz, s_offs, s_src, s_T, s_excl, s_stats, s_normals, s_ninfo;
 };
 
 Layout layout_of(int32_t pcap, int32_t max_src) {
   const size_t pc = (size_t)pcap, ld = (size_t)std::max(max_src, 1), nch = (ld + 255) / 256;
   Layout l;
-  l.total = 0;
-  auto take = [&l](size_t bytes) { const size_t o = l.total; l.total += (bytes + 15) & ~(size_t)15; return o; };
-  l.nn_d = take(8 * pc * ld); l.nn_j = take(4 * pc * ld); l.part = take(8 * pc * nch * pr::MAPPLANE_SUMS);
-  l.done = take(4 * pc); l.prev = take(16 * pc);
-  l.s_xyz = take(24 * pc * ld); l.s_offs = take(8 * (pc + 1)); l.s_src = take(4 * pc); l.s_T = take(96 * pc); l.s_excl = take(8 * pc);
-  l.s_stats = take(32 * pc); l.s_normals = take(24 * pc * ld); l.s_ninfo = take(4 * pc * ld);
+  l.nn_d = l.take(8 * pc * ld); l.nn_j = l.take(4 * pc * ld); l.part = l.take(8 * pc * nch * pr::MAPPLANE_SUMS);
+  l.done = l.take(4 * pc); l.prev = l.take(16 * pc);
+  l.s_xyz = l.take(24 * pc * ld); l.s_offs = l.take(8 * (pc + 1)); l.s_src = l.take(4 * pc); l.s_T = l.take(96 * pc); l.s_excl = l.take(8 * pc);
+  l.s_stats = l.take(32 * pc); l.s_normals = l.take(24 * pc * ld); l.s_ninfo = l.take(4 * pc * ld);
   return l;
 }
 
@@ -112,49 +109,24 @@ int pr_mapplane_create(pr_ctx* ctx, pr_maploc* ml, pr_mapplane** out) {
   if (!ml) return fail(ctx, PR_EINVAL, "pr_mapplane_create: localiser is NULL");
   if (!ctx) return fail(nullptr, PR_EINVAL, "pr_mapplane_create: ctx is NULL");
   if (pr::maploc_ctx(ml) != ctx) return fail(ctx, PR_EINVAL, "pr_mapplane_create: the localiser belongs to another context");
-  PR_CHECK_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
-  pr_mapplane* mp = new (std::nothrow) pr_mapplane;
-  if (!mp) return fail(ctx, PR_ENOMEM, "out of host memory");
-  mp->ctx = ctx; mp->ml = ml; mp->v = pr::maploc_view(ml);
-  const Layout l = layout_of(mp->v->pair_cap, mp->v->max_src);
-  hipError_t e = hipMalloc(&mp->scratch, l.total);
-  if (e != hipSuccess) {
-    delete mp;
-    return fail(ctx, e == hipErrorOutOfMemory ? PR_ENOMEM : PR_EHIP, "pr_mapplane_create: scratch of %zu bytes: %s", l.total, hipGetErrorString(e));
-  }
-  char* b = static_cast<char*>(mp->scratch);
-  mp->nn_d = reinterpret_cast<double*>(b + l.nn_d);
-  mp->nn_j = reinterpret_cast<int*>(b + l.nn_j);
-  mp->part = reinterpret_cast<double*>(b + l.part);
-  mp->done = reinterpret_cast<int*>(b + l.done);
-  mp->prev = reinterpret_cast<double*>(b + l.prev);
-  mp->stage_xyz = reinterpret_cast<double*>(b + l.s_xyz);
-  mp->stage_offs = reinterpret_cast<int64_t*>(b + l.s_offs);
-  mp->stage_src = reinterpret_cast<int32_t*>(b + l.s_src);
-  mp->stage_T = reinterpret_cast<double*>(b + l.s_T);
-  mp->stage_excl = reinterpret_cast<int32_t*>(b + l.s_excl);
-  mp->stage_stats = reinterpret_cast<pr_icp_stats*>(b + l.s_stats);
-  mp->stage_normals = reinterpret_cast<double*>(b + l.s_normals);
-  mp->stage_ninfo = reinterpret_cast<int32_t*>(b + l.s_ninfo);
-  hipStream_t st = pr::ctx_stream(ctx);
-  e = hipMemsetAsync(mp->scratch, 0, l.total, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) {
-    (void)hipFree(mp->scratch);
-    delete mp;
-    return fail(ctx, PR_EHIP, "pr_mapplane_create: clearing the scratch failed: %s", hipGetErrorString(e));
-  }
-  *out = mp;
-  return PR_OK;
+  const pr::MapLocView* lv = pr::maploc_view(ml);
+  const Layout l = layout_of(lv->pair_cap, lv->max_src);
+  pr::Owned<pr_mapplane> mp;
+  if (int rc = pr::make(ctx, "pr_mapplane_create", l.total, mp)) return rc;
+  mp->ml = ml; mp->v = lv;
+  void* b = mp->scratch;
+  mp->nn_d = at<double>(b, l.nn_d); mp->nn_j = at<int>(b, l.nn_j); mp->part = at<double>(b, l.part); mp->done = at<int>(b, l.done);
+  mp->prev = at<double>(b, l.prev);
+  mp->stage_xyz = at<double>(b, l.s_xyz); mp->stage_offs = at<int64_t>(b, l.s_offs); mp->stage_src = at<int32_t>(b, l.s_src);
+  mp->stage_T = at<double>(b, l.s_T); mp->stage_excl = at<int32_t>(b, l.s_excl); mp->stage_stats = at<pr_icp_stats>(b, l.s_stats);
+  mp->stage_normals = at<double>(b, l.s_normals); mp->stage_ninfo = at<int32_t>(b, l.s_ninfo);
+  pr::Transfer t(ctx);
+  t.fill(b, 0, l.total);
+  return pr::commit(mp, t, "pr_mapplane_create", out);
 }
 
-void pr_mapplane_destroy(pr_mapplane* mp) {
-  if (!mp) return;
-  (void)hipSetDevice(pr::ctx_device(mp->ctx));
-  (void)hipStreamSynchronize(pr::ctx_stream(mp->ctx));
-  (void)hipFree(mp->scratch);         // the localiser and the world buffers are the caller's
-  delete mp;
-}
+// the localiser and the world buffers are the caller's
+void pr_mapplane_destroy(pr_mapplane* mp) { pr::destroy(mp); }
 
 int pr_mapplane_normals_dev(pr_mapplane* mp, double radius, int32_t min_nbrs, double max_ratio, double* d_normals, int32_t* d_ninfo) {
   const char* fn = "pr_mapplane_normals_dev";
@@ -201,14 +173,11 @@ int pr_mapplane_normals(pr_mapplane* mp, double radius, int32_t min_nbrs, double
   if (int rc = host_world(mp, fn)) return rc;
   pr_ctx* ctx = mp->ctx;
   const size_t oc = (size_t)mp->v->ocap;
-  if (int rc = pr_mapplane_normals_dev(mp, radius, min_nbrs, max_ratio, mp->stage_normals, mp->stage_ninfo)) return rc;
-  hipStream_t st = pr::ctx_stream(ctx);
-  hipError_t e = hipMemcpyAsync(normals, mp->stage_normals, oc * 24, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(ninfo, mp->stage_ninfo, oc * 4, hipMemcpyDeviceToHost, st);
-  const hipError_t es = hipStreamSynchronize(st);                 // the host arrays are in flight until here
-  if (e == hipSuccess) e = es;
-  if (e != hipSuccess) return fail(ctx, pr::hip_code(e), "%s: %s", fn, hipGetErrorString(e));
-  return PR_OK;
+  pr::Transfer t(ctx);
+  t.run([&] { return pr_mapplane_normals_dev(mp, radius, min_nbrs, max_ratio, mp->stage_normals, mp->stage_ninfo); });
+  t.down(normals, mp->stage_normals, oc * 24);
+  t.down(ninfo, mp->stage_ninfo, oc * 4);
+  return t.finish(ctx, fn);
 }
 
 int pr_mapplane_refine(pr_mapplane* mp, const double* xyz_q, const int64_t* offs_q, int32_t Nq, const int32_t* pair_src, int32_t c,
@@ -229,25 +198,22 @@ int pr_mapplane_refine(pr_mapplane* mp, const double* xyz_q, const int64_t* offs
   if (offs_q[Nq] > 0 && !xyz_q) return fail(ctx, PR_EINVAL, "%s: a required pointer is NULL", fn);
   if (c == 0) return PR_OK;
   PR_CHECK_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
-  hipStream_t st = pr::ctx_stream(ctx);
   const size_t oc = (size_t)v.ocap;
-  hipError_t e = hipMemcpyAsync(mp->stage_offs, offs_q, ((size_t)Nq + 1) * 8, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess && offs_q[Nq] > 0) e = hipMemcpyAsync(mp->stage_xyz, xyz_q, (size_t)offs_q[Nq] * 24, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(mp->stage_src, pair_src, (size_t)c * 4, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(mp->stage_T, T0, (size_t)c * 96, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess && excl) e = hipMemcpyAsync(mp->stage_excl, excl, (size_t)c * 8, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(mp->stage_normals, normals, oc * 24, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(mp->stage_ninfo, ninfo, oc * 4, hipMemcpyHostToDevice, st);
-  int rc = PR_OK;
-  if (e == hipSuccess)                                             // in place: d_T_out = d_T0
-    rc = pr_mapplane_refine_dev(mp, mp->stage_xyz, mp->stage_offs, Nq, mp->stage_src, c, mp->stage_T, excl ? mp->stage_excl : nullptr, max_iter,
-                                max_corr, tol_rmse, tol_fitness, min_inliers, mp->stage_normals, mp->stage_ninfo, mp->stage_T, mp->stage_stats);
-  if (rc == PR_OK && e == hipSuccess) e = hipMemcpyAsync(T_out, mp->stage_T, (size_t)c * 96, hipMemcpyDeviceToHost, st);
-  if (rc == PR_OK && e == hipSuccess) e = hipMemcpyAsync(stats, mp->stage_stats, (size_t)c * sizeof(pr_icp_stats), hipMemcpyDeviceToHost, st);
-  const hipError_t es = hipStreamSynchronize(st);
-  if (e == hipSuccess) e = es;
-  if (rc == PR_OK && e != hipSuccess) rc = fail(ctx, pr::hip_code(e), "%s: %s", fn, hipGetErrorString(e));
-  return rc;
+  pr::Transfer t(ctx);
+  t.up(mp->stage_offs, offs_q, ((size_t)Nq + 1) * 8);
+  t.up(mp->stage_xyz, xyz_q, (size_t)offs_q[Nq] * 24);
+  t.up(mp->stage_src, pair_src, (size_t)c * 4);
+  t.up(mp->stage_T, T0, (size_t)c * 96);
+  t.up_opt(mp->stage_excl, excl, (size_t)c * 8);
+  t.up(mp->stage_normals, normals, oc * 24);
+  t.up(mp->stage_ninfo, ninfo, oc * 4);
+  t.run([&] {                                                      // in place: d_T_out = d_T0
+    return pr_mapplane_refine_dev(mp, mp->stage_xyz, mp->stage_offs, Nq, mp->stage_src, c, mp->stage_T, excl ? mp->stage_excl : nullptr, max_iter,
+                                  max_corr, tol_rmse, tol_fitness, min_inliers, mp->stage_normals, mp->stage_ninfo, mp->stage_T, mp->stage_stats);
+  });
+  t.down(T_out, mp->stage_T, (size_t)c * 96);
+  t.down(stats, mp->stage_stats, (size_t)c * sizeof(pr_icp_stats));
+  return t.finish(ctx, fn);
 }
 
 }  // extern "C"

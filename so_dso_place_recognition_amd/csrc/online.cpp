@@ -1,14 +1,14 @@
 // online.cpp — host side of the online engine (online.hip): ONE core - the view over the caller's buffers, its scratch, match, append and
 // the host form of an append - behind two C families, pr_online (SC, M2DP) and pr_onlineset (FUSED, DELIGHT), whose entry points do their own argument checks.
+// Layout, create tail, destroy, the state word and the copy chain come from the shared handle core (handle_core.hpp).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstdio>
 #include <cstring>
-#include <new>
 
 #include "../../include/place_recognition.h"
-#include "host_common.hpp"
+#include "handle_core.hpp"
 #include "kernels.hpp"
 #include "online.hpp"
 
@@ -16,10 +16,8 @@ static_assert(pr::ONLINE_OVERFLOW == PR_ONLINE_OVERFLOW, "flag bit");
 static_assert(PR_TYPE_SC == pr::ONLINE_SC && PR_TYPE_M2DP == pr::ONLINE_M2DP, "pr_online_create passes its type on as the kind");
 static_assert(PR_ONLINESET_FUSED == 0 && PR_ONLINESET_DELIGHT == 1 && pr::ONLINE_DELIGHT == pr::ONLINE_FUSED + 1, "pr_onlineset_create adds ONLINE_FUSED");
 
-struct OnlineCore {
-  pr_ctx* ctx = nullptr;
+struct OnlineCore : pr::Handle {     // scratch: rows, partial, stats and the staging of the host form
   pr::OnlineView v;
-  void* scratch = nullptr;            // one allocation: rows, partial, stats and the staging of the host form
   double* stage_sig = nullptr;        // [len[0] + len[1]]: the parts, one behind the other
   int32_t* stage_info = nullptr;      // [4]
 };
@@ -28,9 +26,8 @@ struct pr_onlineset : OnlineCore {};
 
 namespace {
 
+using pr::at;
 using pr::fail;
-
-size_t up16(size_t n) { return (n + 15) & ~(size_t)15; }
 
 // Below, fn is the entry point's name and noun what it calls its handle ("database" / "set").  create: what is left once the entry point has
 // checked its own arguments - the checks both families share, the handle, the view over (p0, p1, state) and the scratch, from (kind, capacity) alone.
@@ -39,66 +36,40 @@ int create(pr_ctx* ctx, const char* fn, int kind, double* p0, double* p1, int32_
   if (capacity < 1 || capacity > PR_MAX_SIGS) return fail(ctx, PR_EINVAL, "%s: capacity=%d outside 1 .. PR_MAX_SIGS=%d", fn, capacity, PR_MAX_SIGS);
   if (max_k < 1 || max_k > pr::ONLINE_MAX_K) return fail(ctx, PR_EINVAL, "%s: max_k=%d outside 1 .. %d", fn, max_k, pr::ONLINE_MAX_K);
   if (!ctx) return fail(nullptr, PR_EINVAL, "%s: ctx is NULL", fn);
-  PR_CHECK_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
-  T* o = new (std::nothrow) T;
-  if (!o) return fail(ctx, PR_ENOMEM, "out of host memory");
-  o->ctx = ctx;
+  const int len0 = kind == pr::ONLINE_M2DP ? pr::ONLINE_M2DP_LEN : (kind == pr::ONLINE_DELIGHT ? pr::ONLINE_DELIGHT_LEN : pr::ONLINE_SC_LEN);
+  const int len1 = kind == pr::ONLINE_FUSED ? pr::ONLINE_M2DP_LEN : 0, NB = pr::online_blocks(kind, capacity);
+  const size_t C = (size_t)pr::online_channels(kind);
+  pr::Arena a;
+  const size_t o_rows = a.take(C * capacity * 8), o_part = a.take((size_t)NB * 2 * C * 8), o_stats = a.take(2 * C * 8),
+               o_sig = a.take((size_t)(len0 + len1) * 8), o_info = a.take(16);
+  pr::Owned<T> o;
+  if (int rc = pr::make(ctx, fn, a.total, o)) return rc;
   pr::OnlineView& v = o->v;
   memset(&v, 0, sizeof v);
   v.part[0] = p0; v.part[1] = p1; v.state = state;
-  v.len[0] = kind == pr::ONLINE_M2DP ? pr::ONLINE_M2DP_LEN : (kind == pr::ONLINE_DELIGHT ? pr::ONLINE_DELIGHT_LEN : pr::ONLINE_SC_LEN);
-  v.len[1] = kind == pr::ONLINE_FUSED ? pr::ONLINE_M2DP_LEN : 0;
-  v.kind = kind; v.capacity = capacity; v.max_k = max_k; v.NB = pr::online_blocks(kind, capacity);
-  const size_t C = (size_t)pr::online_channels(kind);
-  const size_t o_rows = 0, o_part = o_rows + up16(C * capacity * 8), o_stats = o_part + up16((size_t)v.NB * 2 * C * 8), o_sig = o_stats + 2 * C * 8,
-               o_info = o_sig + up16((size_t)(v.len[0] + v.len[1]) * 8), total = o_info + 16;
-  hipError_t e = hipMalloc(&o->scratch, total);
-  if (e != hipSuccess) {
-    delete o;
-    return fail(ctx, e == hipErrorOutOfMemory ? PR_ENOMEM : PR_EHIP, "%s: scratch: %s", fn, hipGetErrorString(e));
-  }
-  char* b = static_cast<char*>(o->scratch);
-  v.rows = reinterpret_cast<double*>(b + o_rows); v.partial = reinterpret_cast<double*>(b + o_part); v.stats = reinterpret_cast<double*>(b + o_stats);
-  o->stage_sig = reinterpret_cast<double*>(b + o_sig); o->stage_info = reinterpret_cast<int32_t*>(b + o_info);
-  hipStream_t st = pr::ctx_stream(ctx);
-  e = hipMemsetAsync(v.state, 0, 4 * sizeof(int32_t), st);
-  if (e == hipSuccess) e = hipMemsetAsync(o->scratch, 0, total, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) {
-    (void)hipFree(o->scratch);
-    delete o;
-    return fail(ctx, PR_EHIP, "%s: clearing the state failed: %s", fn, hipGetErrorString(e));
-  }
-  *out = o;
-  return PR_OK;
-}
-
-template <class T>
-void destroy(T* o) {
-  if (!o) return;
-  (void)hipSetDevice(pr::ctx_device(o->ctx));
-  (void)hipStreamSynchronize(pr::ctx_stream(o->ctx));
-  (void)hipFree(o->scratch);            // the buffers are the caller's
-  delete o;
+  v.len[0] = len0; v.len[1] = len1;
+  v.kind = kind; v.capacity = capacity; v.max_k = max_k; v.NB = NB;
+  void* b = o->scratch;
+  v.rows = at<double>(b, o_rows); v.partial = at<double>(b, o_part); v.stats = at<double>(b, o_stats);
+  o->stage_sig = at<double>(b, o_sig); o->stage_info = at<int32_t>(b, o_info);
+  pr::Transfer t(ctx);
+  t.fill(v.state, 0, 4 * sizeof(int32_t));
+  t.fill(b, 0, a.total);
+  return pr::commit(o, t, fn, out);
 }
 
 int no_handle(const char* fn, const char* noun) { return fail(nullptr, PR_EINVAL, "%s: %s is NULL", fn, noun); }
 
 int reset(OnlineCore* o, const char* fn, const char* noun) {
   if (!o) return no_handle(fn, noun);
-  PR_CHECK_HIP(o->ctx, hipSetDevice(pr::ctx_device(o->ctx)));
-  PR_CHECK_HIP(o->ctx, hipMemsetAsync(o->v.state, 0, 4 * sizeof(int32_t), pr::ctx_stream(o->ctx)));
-  return PR_OK;
+  return pr::clear_state(o->ctx, o->v.state);
 }
 
 int read_count(OnlineCore* o, const char* fn, const char* noun, int32_t* count, int32_t* flags) {
   if (!o) return no_handle(fn, noun);
   if (!count || !flags) return fail(o->ctx, PR_EINVAL, "%s: a required pointer is NULL", fn);
-  PR_CHECK_HIP(o->ctx, hipSetDevice(pr::ctx_device(o->ctx)));
-  hipStream_t st = pr::ctx_stream(o->ctx);
   int32_t s[4];
-  PR_CHECK_HIP(o->ctx, hipMemcpyAsync(s, o->v.state, sizeof s, hipMemcpyDeviceToHost, st));
-  PR_CHECK_HIP(o->ctx, hipStreamSynchronize(st));
+  if (int rc = pr::read_state(o->ctx, fn, o->v.state, s)) return rc;
   *count = s[0]; *flags = s[1];
   return PR_OK;
 }
@@ -130,21 +101,14 @@ int append_dev(OnlineCore* o, const pr::OnlineParts& src, const int32_t* d_emitt
 }
 
 // The host form: the parts through stage_sig, the device path, info back; synchronises.
-int append_host(OnlineCore* o, const pr::OnlineParts& src, int32_t* info) {
+int append_host(OnlineCore* o, const char* fn, const pr::OnlineParts& src, int32_t* info) {
   PR_CHECK_HIP(o->ctx, hipSetDevice(pr::ctx_device(o->ctx)));
-  hipStream_t st = pr::ctx_stream(o->ctx);
   double* const stage[2] = {o->stage_sig, o->v.len[1] ? o->stage_sig + o->v.len[0] : nullptr};
-  hipError_t e = hipSuccess;
-  for (int p = 0; p < 2 && o->v.len[p] && e == hipSuccess; p++)
-    e = hipMemcpyAsync(stage[p], src.p[p], (size_t)o->v.len[p] * sizeof(double), hipMemcpyHostToDevice, st);
-  int rc = PR_OK;
-  if (e == hipSuccess) rc = append_dev(o, {{stage[0], stage[1]}}, nullptr, o->stage_info);
-  if (e == hipSuccess && rc == PR_OK) e = hipMemcpyAsync(info, o->stage_info, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, st);
-  const hipError_t e2 = hipStreamSynchronize(st);    // the host arrays are in flight until here
-  if (rc != PR_OK) return rc;
-  PR_CHECK_HIP(o->ctx, e);
-  PR_CHECK_HIP(o->ctx, e2);
-  return PR_OK;
+  pr::Transfer t(o->ctx);
+  for (int p = 0; p < 2; p++) t.up(stage[p], src.p[p], (size_t)o->v.len[p] * sizeof(double));
+  t.run([&] { return append_dev(o, {{stage[0], stage[1]}}, nullptr, o->stage_info); });
+  t.down(info, o->stage_info, 4 * sizeof(int32_t));
+  return t.finish(o->ctx, fn);
 }
 
 // The parts a pr_onlineset call of this kind takes: FUSED needs sc and m2dp and no delight, DELIGHT the reverse.  0, or PR_EINVAL with the text set.
@@ -193,8 +157,8 @@ int pr_onlineset_create(pr_ctx* ctx, int kind, const pr_onlineset_buffers* buffe
                 buffers->state, capacity, max_k, out);
 }
 
-void pr_online_destroy(pr_online* o) { destroy(o); }
-void pr_onlineset_destroy(pr_onlineset* o) { destroy(o); }
+void pr_online_destroy(pr_online* o) { pr::destroy(o); }         // the buffers are the caller's
+void pr_onlineset_destroy(pr_onlineset* o) { pr::destroy(o); }
 
 int pr_online_reset(pr_online* o) { return reset(o, "pr_online_reset", "database"); }
 int pr_onlineset_reset(pr_onlineset* o) { return reset(o, "pr_onlineset_reset", "set"); }
@@ -234,14 +198,14 @@ int pr_onlineset_append_dev(pr_onlineset* o, const double* d_sc, const double* d
 int pr_online_append(pr_online* o, const double* sig, int32_t* info) {
   if (!o) return no_handle("pr_online_append", "database");
   if (!sig || !info) return fail(o->ctx, PR_EINVAL, "pr_online_append: a required pointer is NULL (sig, info)");
-  return append_host(o, {{sig, nullptr}}, info);
+  return append_host(o, "pr_online_append", {{sig, nullptr}}, info);
 }
 
 int pr_onlineset_append(pr_onlineset* o, const double* sc, const double* m2dp, const double* delight, int32_t* info) {
   if (!o) return no_handle("pr_onlineset_append", "set");
   if (int rc = check_parts(o->ctx, "pr_onlineset_append", o->v.kind, sc, m2dp, delight, "")) return rc;
   if (!info) return fail(o->ctx, PR_EINVAL, "pr_onlineset_append: a required pointer is NULL (info)");
-  return append_host(o, set_parts(sc, m2dp, delight), info);
+  return append_host(o, "pr_onlineset_append", set_parts(sc, m2dp, delight), info);
 }
 
 }  // extern "C"

@@ -1,24 +1,22 @@
 // posegraph.cpp — host side of the loop-closure log and the pose-graph relaxation (posegraph.hip): the opaque pr_posegraph
-// over the caller's four buffers with its scratch, the argument checks, the stream-ordered entry points and the host form of an add.
+// over the caller's four buffers with its scratch, the argument checks, the stream-ordered entry points and the host forms of an add, on
+// the shared handle core (handle_core.hpp).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstdio>
 #include <cstring>
-#include <new>
 
 #include "../../include/place_recognition.h"
-#include "host_common.hpp"
+#include "handle_core.hpp"
 #include "kernels.hpp"
 #include "posegraph.hpp"
 
 static_assert(pr::POSEGRAPH_OVERFLOW == PR_POSEGRAPH_OVERFLOW, "flag bit");
 static_assert(sizeof(pr_posegraph_params) == 32, "two int32 and three doubles, no padding");
 
-struct pr_posegraph {
-  pr_ctx* ctx = nullptr;
+struct pr_posegraph : pr::Handle {   // scratch: everything PoseGraphView names and the staging of the host form
   pr::PoseGraphView v;
-  void* scratch = nullptr;            // one allocation: everything PoseGraphView names and the staging of the host form
   int32_t* stage_idx = nullptr;       // [128]
   double* stage_T = nullptr;          // [128][12]
   uint8_t* stage_acc = nullptr;       // [128]
@@ -29,12 +27,21 @@ struct pr_posegraph {
 
 namespace {
 
+using pr::at;
 using pr::fail;
 
 constexpr int32_t MAX_NODES = 1 << 20, MAX_EDGES = 1 << 20, MAX_OUTER = 64, MAX_INNER = 1 << 16;
 constexpr int32_t MAX_BATCH = 65535;          // most slots of one batch add: pr_icp_pairs_dev's slot limit
 
 bool weight_ok(double w) { return std::isfinite(w) && w >= 0.0; }
+
+// the uploads the two single adds share: k slots and the four-word query row (the caller's, alive until its finish) into the create-time staging
+void stage_slots(pr::Transfer& t, pr_posegraph* g, const int32_t* idx, const double* T, const uint8_t* accepted, const int32_t* row, int32_t k) {
+  t.up(g->stage_idx, idx, (size_t)k * 4);
+  t.up(g->stage_T, T, (size_t)k * 12 * 8);
+  t.up(g->stage_acc, accepted, (size_t)k);
+  t.up(g->stage_row, row, 4 * sizeof(int32_t));
+}
 
 }  // namespace
 
@@ -55,73 +62,48 @@ int pr_posegraph_create(pr_ctx* ctx, const pr_posegraph_buffers* buffers, int32_
   if (max_outer < 1 || max_outer > MAX_OUTER) return fail(ctx, PR_EINVAL, "pr_posegraph_create: max_outer=%d outside 1 .. %d", max_outer, MAX_OUTER);
   if (max_inner < 1 || max_inner > MAX_INNER) return fail(ctx, PR_EINVAL, "pr_posegraph_create: max_inner=%d outside 1 .. %d", max_inner, MAX_INNER);
   if (!ctx) return fail(nullptr, PR_EINVAL, "pr_posegraph_create: ctx is NULL");
-  PR_CHECK_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
-  pr_posegraph* g = new (std::nothrow) pr_posegraph;
-  if (!g) return fail(ctx, PR_ENOMEM, "out of host memory");
-  g->ctx = ctx;
+  const size_t NC = (size_t)node_capacity, EC = (size_t)edge_capacity, S = NC - 1 + EC;
+  pr::Arena a;
+  const size_t o_X = a.take(NC * 12 * 8), o_zodo = a.take(NC * 12 * 8), o_jac = a.take(S * pr::PG_BLOCKS * 8), o_res = a.take(S * 6 * 8),
+               o_wgt = a.take(S * 2 * 8), o_cost = a.take(S * 8), o_u = a.take(S * 6 * 8), o_g = a.take(NC * 6 * 8), o_x = a.take(NC * 6 * 8),
+               o_r = a.take(NC * 6 * 8), o_z = a.take(NC * 6 * 8), o_p = a.take(NC * 6 * 8), o_q = a.take(NC * 6 * 8), o_dinv = a.take(NC * 36 * 8),
+               o_valid = a.take(S * 4), o_fin = a.take(NC * 4), o_deg = a.take(NC * 4), o_cur = a.take(NC * 4), o_off = a.take((NC + 1) * 4),
+               o_raw = a.take(2 * EC * 4), o_inc = a.take(2 * EC * 4), o_ctl = a.take(16), o_sidx = a.take(pr::POSEGRAPH_MAX_K * 4),
+               o_sT = a.take(pr::POSEGRAPH_MAX_K * 12 * 8), o_sacc = a.take(pr::POSEGRAPH_MAX_K), o_srow = a.take(16), o_sinfo = a.take(16),
+               o_sw = a.take(pr::POSEGRAPH_MAX_K * 2 * 8);
+  pr::Owned<pr_posegraph> g;
+  if (int rc = pr::make(ctx, "pr_posegraph_create", a.total, g)) return rc;
   pr::PoseGraphView& v = g->v;
   memset(&v, 0, sizeof v);
   v.edge_ij = buffers->edge_ij; v.edge_Z = buffers->edge_Z; v.edge_w = buffers->edge_w; v.state = buffers->state;
   v.node_capacity = node_capacity; v.edge_capacity = edge_capacity; v.max_outer = max_outer; v.max_inner = max_inner;
   v.S = node_capacity - 1 + edge_capacity;
-  const size_t NC = (size_t)node_capacity, EC = (size_t)edge_capacity, S = (size_t)v.S;
-  size_t total = 0;
-  auto take = [&total](size_t bytes) { const size_t o = total; total += (bytes + 15) & ~(size_t)15; return o; };
-  const size_t o_X = take(NC * 12 * 8), o_zodo = take(NC * 12 * 8), o_jac = take(S * pr::PG_BLOCKS * 8), o_res = take(S * 6 * 8),
-               o_wgt = take(S * 2 * 8), o_cost = take(S * 8), o_u = take(S * 6 * 8), o_g = take(NC * 6 * 8), o_x = take(NC * 6 * 8),
-               o_r = take(NC * 6 * 8), o_z = take(NC * 6 * 8), o_p = take(NC * 6 * 8), o_q = take(NC * 6 * 8), o_dinv = take(NC * 36 * 8),
-               o_valid = take(S * 4), o_fin = take(NC * 4), o_deg = take(NC * 4), o_cur = take(NC * 4), o_off = take((NC + 1) * 4),
-               o_raw = take(2 * EC * 4), o_inc = take(2 * EC * 4), o_ctl = take(16), o_sidx = take(pr::POSEGRAPH_MAX_K * 4), o_sT = take(pr::POSEGRAPH_MAX_K * 12 * 8),
-               o_sacc = take(pr::POSEGRAPH_MAX_K), o_srow = take(16), o_sinfo = take(16), o_sw = take(pr::POSEGRAPH_MAX_K * 2 * 8);
-  hipError_t e = hipMalloc(&g->scratch, total);
-  if (e != hipSuccess) {
-    delete g;
-    return fail(ctx, e == hipErrorOutOfMemory ? PR_ENOMEM : PR_EHIP, "pr_posegraph_create: scratch: %s", hipGetErrorString(e));
-  }
-  char* b = static_cast<char*>(g->scratch);
-  auto dp = [b](size_t o) { return reinterpret_cast<double*>(b + o); };
-  auto ip = [b](size_t o) { return reinterpret_cast<int*>(b + o); };
-  v.X = dp(o_X); v.zodo = dp(o_zodo); v.jac = dp(o_jac); v.res = dp(o_res); v.wgt = dp(o_wgt); v.cost = dp(o_cost); v.u = dp(o_u);
-  v.g = dp(o_g); v.x = dp(o_x); v.r = dp(o_r); v.z = dp(o_z); v.p = dp(o_p); v.q = dp(o_q); v.dinv = dp(o_dinv);
-  v.valid = ip(o_valid); v.finite = ip(o_fin); v.deg = ip(o_deg); v.cursor = ip(o_cur); v.inc_off = ip(o_off); v.inc_raw = ip(o_raw); v.inc = ip(o_inc); v.ctl = ip(o_ctl);
-  g->stage_idx = ip(o_sidx); g->stage_T = dp(o_sT); g->stage_acc = reinterpret_cast<uint8_t*>(b + o_sacc); g->stage_row = ip(o_srow);
-  g->stage_info = ip(o_sinfo); g->stage_w = dp(o_sw);
-  hipStream_t st = pr::ctx_stream(ctx);
-  e = hipMemsetAsync(v.state, 0, 4 * sizeof(int32_t), st);
-  if (e == hipSuccess) e = hipMemsetAsync(g->scratch, 0, total, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) {
-    (void)hipFree(g->scratch);
-    delete g;
-    return fail(ctx, PR_EHIP, "pr_posegraph_create: clearing the state failed: %s", hipGetErrorString(e));
-  }
-  *out = g;
-  return PR_OK;
+  void* b = g->scratch;
+  v.X = at<double>(b, o_X); v.zodo = at<double>(b, o_zodo); v.jac = at<double>(b, o_jac); v.res = at<double>(b, o_res);
+  v.wgt = at<double>(b, o_wgt); v.cost = at<double>(b, o_cost); v.u = at<double>(b, o_u); v.g = at<double>(b, o_g); v.x = at<double>(b, o_x);
+  v.r = at<double>(b, o_r); v.z = at<double>(b, o_z); v.p = at<double>(b, o_p); v.q = at<double>(b, o_q); v.dinv = at<double>(b, o_dinv);
+  v.valid = at<int>(b, o_valid); v.finite = at<int>(b, o_fin); v.deg = at<int>(b, o_deg); v.cursor = at<int>(b, o_cur);
+  v.inc_off = at<int>(b, o_off); v.inc_raw = at<int>(b, o_raw); v.inc = at<int>(b, o_inc); v.ctl = at<int>(b, o_ctl);
+  g->stage_idx = at<int32_t>(b, o_sidx); g->stage_T = at<double>(b, o_sT); g->stage_acc = at<uint8_t>(b, o_sacc);
+  g->stage_row = at<int32_t>(b, o_srow); g->stage_info = at<int32_t>(b, o_sinfo); g->stage_w = at<double>(b, o_sw);
+  pr::Transfer t(ctx);
+  t.fill(v.state, 0, 4 * sizeof(int32_t));
+  t.fill(b, 0, a.total);
+  return pr::commit(g, t, "pr_posegraph_create", out);
 }
 
-void pr_posegraph_destroy(pr_posegraph* g) {
-  if (!g) return;
-  (void)hipSetDevice(pr::ctx_device(g->ctx));
-  (void)hipStreamSynchronize(pr::ctx_stream(g->ctx));
-  (void)hipFree(g->scratch);          // the four buffers are the caller's
-  delete g;
-}
+void pr_posegraph_destroy(pr_posegraph* g) { pr::destroy(g); }  // the four buffers are the caller's
 
 int pr_posegraph_reset(pr_posegraph* g) {
   if (!g) return fail(nullptr, PR_EINVAL, "pr_posegraph_reset: graph is NULL");
-  PR_CHECK_HIP(g->ctx, hipSetDevice(pr::ctx_device(g->ctx)));
-  PR_CHECK_HIP(g->ctx, hipMemsetAsync(g->v.state, 0, 4 * sizeof(int32_t), pr::ctx_stream(g->ctx)));
-  return PR_OK;
+  return pr::clear_state(g->ctx, g->v.state);
 }
 
 int pr_posegraph_count(pr_posegraph* g, int32_t* edges, int32_t* flags) {
   if (!g) return fail(nullptr, PR_EINVAL, "pr_posegraph_count: graph is NULL");
   if (!edges || !flags) return fail(g->ctx, PR_EINVAL, "pr_posegraph_count: a required pointer is NULL");
-  PR_CHECK_HIP(g->ctx, hipSetDevice(pr::ctx_device(g->ctx)));
-  hipStream_t st = pr::ctx_stream(g->ctx);
   int32_t s[4];
-  PR_CHECK_HIP(g->ctx, hipMemcpyAsync(s, g->v.state, sizeof s, hipMemcpyDeviceToHost, st));
-  PR_CHECK_HIP(g->ctx, hipStreamSynchronize(st));
+  if (int rc = pr::read_state(g->ctx, "pr_posegraph_count", g->v.state, s)) return rc;
   *edges = s[0];
   *flags = s[1];
   return PR_OK;
@@ -150,20 +132,12 @@ int pr_posegraph_add(pr_posegraph* g, const int32_t* idx, const double* T, const
   if (!g) return fail(nullptr, PR_EINVAL, "pr_posegraph_add: graph is NULL");
   if (!idx || !T || !accepted || !info) return fail(ctx, PR_EINVAL, "pr_posegraph_add: a required pointer is NULL (idx, T, accepted, info)");
   PR_CHECK_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
-  hipStream_t st = pr::ctx_stream(ctx);
   const int32_t row[4] = {query_row, 0, 0, 0};
-  hipError_t e = hipMemcpyAsync(g->stage_idx, idx, (size_t)k * 4, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(g->stage_T, T, (size_t)k * 12 * 8, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(g->stage_acc, accepted, (size_t)k, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(g->stage_row, row, sizeof row, hipMemcpyHostToDevice, st);
-  int rc = PR_OK;
-  if (e == hipSuccess) rc = pr_posegraph_add_dev(g, g->stage_idx, g->stage_T, g->stage_acc, g->stage_row, k, w_rot, w_trans, g->stage_info);
-  if (e == hipSuccess && rc == PR_OK) e = hipMemcpyAsync(info, g->stage_info, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, st);
-  const hipError_t e2 = hipStreamSynchronize(st);     // the host arrays are in flight until here
-  if (rc != PR_OK) return rc;
-  PR_CHECK_HIP(ctx, e);
-  PR_CHECK_HIP(ctx, e2);
-  return PR_OK;
+  pr::Transfer t(ctx);
+  stage_slots(t, g, idx, T, accepted, row, k);
+  t.run([&] { return pr_posegraph_add_dev(g, g->stage_idx, g->stage_T, g->stage_acc, g->stage_row, k, w_rot, w_trans, g->stage_info); });
+  t.down(info, g->stage_info, 4 * sizeof(int32_t));
+  return t.finish(ctx, "pr_posegraph_add");
 }
 
 int pr_posegraphw_add_dev(pr_posegraph* g, const int32_t* d_idx, const double* d_T, const uint8_t* d_accepted, const int32_t* d_query_row,
@@ -187,21 +161,13 @@ int pr_posegraphw_add(pr_posegraph* g, const int32_t* idx, const double* T, cons
   if (!idx || !T || !accepted || !w || !info)
     return fail(ctx, PR_EINVAL, "pr_posegraphw_add: a required pointer is NULL (idx, T, accepted, w, info)");
   PR_CHECK_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
-  hipStream_t st = pr::ctx_stream(ctx);
   const int32_t row[4] = {query_row, 0, 0, 0};
-  hipError_t e = hipMemcpyAsync(g->stage_idx, idx, (size_t)k * 4, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(g->stage_T, T, (size_t)k * 12 * 8, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(g->stage_acc, accepted, (size_t)k, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(g->stage_row, row, sizeof row, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(g->stage_w, w, (size_t)k * 2 * 8, hipMemcpyHostToDevice, st);
-  int rc = PR_OK;
-  if (e == hipSuccess) rc = pr_posegraphw_add_dev(g, g->stage_idx, g->stage_T, g->stage_acc, g->stage_row, k, g->stage_w, g->stage_info);
-  if (e == hipSuccess && rc == PR_OK) e = hipMemcpyAsync(info, g->stage_info, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, st);
-  const hipError_t e2 = hipStreamSynchronize(st);     // the host arrays are in flight until here
-  if (rc != PR_OK) return rc;
-  PR_CHECK_HIP(ctx, e);
-  PR_CHECK_HIP(ctx, e2);
-  return PR_OK;
+  pr::Transfer t(ctx);
+  stage_slots(t, g, idx, T, accepted, row, k);
+  t.up(g->stage_w, w, (size_t)k * 2 * 8);
+  t.run([&] { return pr_posegraphw_add_dev(g, g->stage_idx, g->stage_T, g->stage_acc, g->stage_row, k, g->stage_w, g->stage_info); });
+  t.down(info, g->stage_info, 4 * sizeof(int32_t));
+  return t.finish(ctx, "pr_posegraphw_add");
 }
 
 int pr_posegraphb_add_dev(pr_posegraph* g, const int32_t* d_i, const int32_t* d_j, const double* d_T, const uint8_t* d_accepted, const double* d_w,
@@ -230,28 +196,24 @@ int pr_posegraphb_add(pr_posegraph* g, const int32_t* i, const int32_t* j, const
   if (!g) return fail(nullptr, PR_EINVAL, "pr_posegraphb_add: graph is NULL");
   if (!i || !j || !T || !accepted || !info) return fail(ctx, PR_EINVAL, "pr_posegraphb_add: a required pointer is NULL (i, j, T, accepted, info)");
   PR_CHECK_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
-  hipStream_t st = pr::ctx_stream(ctx);
   const size_t C = (size_t)c, o_T = 0, o_w = o_T + C * 96, o_i = o_w + C * 16, o_j = o_i + C * 4, o_info = o_j + C * 4, o_acc = o_info + 16;
-  char* b = nullptr;
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(&b), o_acc + C);
-  if (e != hipSuccess) return fail(ctx, e == hipErrorOutOfMemory ? PR_ENOMEM : PR_EHIP, "pr_posegraphb_add: staging: %s", hipGetErrorString(e));
-  e = hipMemcpyAsync(b + o_T, T, C * 96, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess && w) e = hipMemcpyAsync(b + o_w, w, C * 16, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(b + o_i, i, C * 4, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(b + o_j, j, C * 4, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(b + o_acc, accepted, C, hipMemcpyHostToDevice, st);
-  int rc = PR_OK;
-  if (e == hipSuccess)
-    rc = pr_posegraphb_add_dev(g, reinterpret_cast<int32_t*>(b + o_i), reinterpret_cast<int32_t*>(b + o_j), reinterpret_cast<double*>(b + o_T),
-                               reinterpret_cast<uint8_t*>(b + o_acc), w ? reinterpret_cast<double*>(b + o_w) : nullptr, w_rot, w_trans, c,
-                               reinterpret_cast<int32_t*>(b + o_info));
-  if (e == hipSuccess && rc == PR_OK) e = hipMemcpyAsync(info, b + o_info, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, st);
-  const hipError_t e2 = hipStreamSynchronize(st);     // the host arrays are in flight until here
-  (void)hipFree(b);
-  if (rc != PR_OK) return rc;
-  PR_CHECK_HIP(ctx, e);
-  PR_CHECK_HIP(ctx, e2);
-  return PR_OK;
+  void* b = nullptr;
+  const hipError_t e = hipMalloc(&b, o_acc + C);
+  if (e != hipSuccess) return fail(ctx, pr::hip_code(e), "pr_posegraphb_add: staging of %zu bytes: %s", o_acc + C, hipGetErrorString(e));
+  pr::Transfer t(ctx);
+  t.up(at<double>(b, o_T), T, C * 96);
+  t.up_opt(at<double>(b, o_w), w, C * 16);
+  t.up(at<int32_t>(b, o_i), i, C * 4);
+  t.up(at<int32_t>(b, o_j), j, C * 4);
+  t.up(at<uint8_t>(b, o_acc), accepted, C);
+  t.run([&] {
+    return pr_posegraphb_add_dev(g, at<int32_t>(b, o_i), at<int32_t>(b, o_j), at<double>(b, o_T), at<uint8_t>(b, o_acc),
+                                 w ? at<double>(b, o_w) : nullptr, w_rot, w_trans, c, at<int32_t>(b, o_info));
+  });
+  t.down(info, at<int32_t>(b, o_info), 4 * sizeof(int32_t));
+  const int rc = t.finish(ctx, "pr_posegraphb_add");
+  (void)hipFree(b);                                   // behind the synchronise
+  return rc;
 }
 
 int pr_posegraph_relax_dev(pr_posegraph* g, const double* d_poses_in, const int32_t* d_n, const pr_posegraph_params* params, double* d_poses_out,

@@ -1,48 +1,44 @@
 // proximity.cpp — host side of the pose-proximity candidate search (proximity.hip): the opaque pr_proximity, its ONE
-// scratch allocation, the argument checks, the stream-ordered search and its host form.
+// scratch allocation, the argument checks, the stream-ordered search and its host form, on the shared handle core (handle_core.hpp).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstdio>
 #include <cstring>
-#include <new>
 
 #include "../../include/place_recognition.h"
-#include "host_common.hpp"
+#include "handle_core.hpp"
 #include "kernels.hpp"
 #include "proximity.hpp"
 
 static_assert(pr::PROX_QRANGE_CLAMPED == PR_PROXIMITY_QRANGE_CLAMPED, "flag bit");
 static_assert(sizeof(pr_proximity_params) == 48, "four doubles and four int32, no padding");
 
-struct pr_proximity {
-  pr_ctx* ctx = nullptr;
+struct pr_proximity : pr::Handle {   // scratch: everything ProxView names and the staging of the host form
   pr::ProxView v;
-  void* scratch = nullptr;            // one allocation: everything ProxView names and the staging of the host form
   pr::ProxOut stage;                  // the staging of the host form, [query_capacity k_max] slots
 };
 
 namespace {
 
+using pr::at;
 using pr::fail;
 
 constexpr int32_t MAX_NODES = 1 << 20, MAX_SLOTS = 65535, MAX_LOG_EDGES = 1 << 20;
 
 // where the parts of the one scratch allocation lie (each on a 16-byte boundary); the formula of the header
-struct Layout {
-  size_t cen, axis, s, valid, part_d2, part_idx, s_idx, s_d2, s_T0, s_src, s_dst, s_known, s_info, total;
+struct Layout : pr::Arena {
+  size_t cen, axis, s, valid, part_d2, part_idx, s_idx, s_d2, s_T0, s_src, s_dst, s_known, s_info;
 };
 
 Layout layout_of(int32_t node_capacity, int32_t query_capacity, int32_t k_max) {
   const size_t NC = (size_t)node_capacity, QK = (size_t)query_capacity * (size_t)k_max;
   const size_t P = QK * (size_t)pr::prox_runs(node_capacity, query_capacity);
   Layout l;
-  l.total = 0;
-  auto take = [&l](size_t bytes) { const size_t o = l.total; l.total += (bytes + 15) & ~(size_t)15; return o; };
-  l.cen = take(24 * NC); l.axis = take(24 * NC); l.s = take(8 * NC); l.valid = take(4 * NC);
-  l.part_d2 = take(8 * P); l.part_idx = take(4 * P);
-  l.s_idx = take(4 * QK); l.s_d2 = take(8 * QK); l.s_T0 = take(96 * QK); l.s_src = take(4 * QK); l.s_dst = take(4 * QK); l.s_known = take(QK);
-  l.s_info = take(16);
+  l.cen = l.take(24 * NC); l.axis = l.take(24 * NC); l.s = l.take(8 * NC); l.valid = l.take(4 * NC);
+  l.part_d2 = l.take(8 * P); l.part_idx = l.take(4 * P);
+  l.s_idx = l.take(4 * QK); l.s_d2 = l.take(8 * QK); l.s_T0 = l.take(96 * QK); l.s_src = l.take(4 * QK); l.s_dst = l.take(4 * QK); l.s_known = l.take(QK);
+  l.s_info = l.take(16);
   return l;
 }
 
@@ -94,45 +90,25 @@ int pr_proximity_create(pr_ctx* ctx, int32_t node_capacity, int32_t query_capaci
   if (query_capacity < 1 || (int64_t)query_capacity * k_max > MAX_SLOTS)
     return fail(ctx, PR_EINVAL, "pr_proximity_create: query_capacity=%d is below 1 or query_capacity x k_max exceeds %d", query_capacity, MAX_SLOTS);
   if (!ctx) return fail(nullptr, PR_EINVAL, "pr_proximity_create: ctx is NULL");
-  PR_CHECK_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
-  pr_proximity* g = new (std::nothrow) pr_proximity;
-  if (!g) return fail(ctx, PR_ENOMEM, "out of host memory");
-  g->ctx = ctx;
+  const Layout l = layout_of(node_capacity, query_capacity, k_max);
+  pr::Owned<pr_proximity> g;
+  if (int rc = pr::make(ctx, "pr_proximity_create", l.total, g)) return rc;
   pr::ProxView& v = g->v;
   memset(&v, 0, sizeof v);
   memset(&g->stage, 0, sizeof g->stage);
   v.node_capacity = node_capacity; v.query_capacity = query_capacity; v.k_max = k_max; v.runs = pr::prox_runs(node_capacity, query_capacity);
-  const Layout l = layout_of(node_capacity, query_capacity, k_max);
-  hipError_t e = hipMalloc(&g->scratch, l.total);
-  if (e != hipSuccess) {
-    delete g;
-    return fail(ctx, e == hipErrorOutOfMemory ? PR_ENOMEM : PR_EHIP, "pr_proximity_create: scratch of %zu bytes: %s", l.total, hipGetErrorString(e));
-  }
-  char* b = static_cast<char*>(g->scratch);
-  auto ip = [b](size_t o) { return reinterpret_cast<int*>(b + o); };
-  auto dp = [b](size_t o) { return reinterpret_cast<double*>(b + o); };
-  v.cen = dp(l.cen); v.axis = dp(l.axis); v.s = dp(l.s); v.valid = ip(l.valid); v.part_d2 = dp(l.part_d2); v.part_idx = ip(l.part_idx);
-  g->stage.idx = ip(l.s_idx); g->stage.d2 = dp(l.s_d2); g->stage.T0 = dp(l.s_T0); g->stage.pair_src = ip(l.s_src); g->stage.pair_dst = ip(l.s_dst);
-  g->stage.known = reinterpret_cast<unsigned char*>(b + l.s_known); g->stage.info = ip(l.s_info);
-  hipStream_t st = pr::ctx_stream(ctx);
-  e = hipMemsetAsync(g->scratch, 0, l.total, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) {
-    (void)hipFree(g->scratch);
-    delete g;
-    return fail(ctx, PR_EHIP, "pr_proximity_create: clearing the scratch failed: %s", hipGetErrorString(e));
-  }
-  *out = g;
-  return PR_OK;
+  void* b = g->scratch;
+  v.cen = at<double>(b, l.cen); v.axis = at<double>(b, l.axis); v.s = at<double>(b, l.s); v.valid = at<int>(b, l.valid);
+  v.part_d2 = at<double>(b, l.part_d2); v.part_idx = at<int>(b, l.part_idx);
+  pr::ProxOut& s = g->stage;
+  s.idx = at<int>(b, l.s_idx); s.d2 = at<double>(b, l.s_d2); s.T0 = at<double>(b, l.s_T0); s.pair_src = at<int>(b, l.s_src);
+  s.pair_dst = at<int>(b, l.s_dst); s.known = at<unsigned char>(b, l.s_known); s.info = at<int>(b, l.s_info);
+  pr::Transfer t(ctx);
+  t.fill(b, 0, l.total);
+  return pr::commit(g, t, "pr_proximity_create", out);
 }
 
-void pr_proximity_destroy(pr_proximity* g) {
-  if (!g) return;
-  (void)hipSetDevice(pr::ctx_device(g->ctx));
-  (void)hipStreamSynchronize(pr::ctx_stream(g->ctx));
-  (void)hipFree(g->scratch);
-  delete g;
-}
+void pr_proximity_destroy(pr_proximity* g) { pr::destroy(g); }
 
 int pr_proximity_search_dev(pr_proximity* g, const double* d_poses, const int32_t* d_n, const int32_t* d_qrange, const pr_proximity_params* params,
                             const pr_posegraph_buffers* log, int32_t log_edge_capacity, int32_t* d_idx, double* d_d2, double* d_T0,
@@ -166,21 +142,15 @@ int pr_proximity_search(pr_proximity* g, const double* d_poses, const int32_t* d
   if (!d_poses || !d_n || !d_qrange || !idx || !d2 || !T0 || !pair_src || !pair_dst || !info)
     return fail(ctx, PR_EINVAL, "pr_proximity_search: a required pointer is NULL (d_poses, d_n, d_qrange, idx, d2, T0, pair_src, pair_dst, info)");
   const pr::ProxOut& s = g->stage;
-  if (int rc = pr_proximity_search_dev(g, d_poses, d_n, d_qrange, params, log, log_edge_capacity, s.idx, s.d2, s.T0, s.pair_src, s.pair_dst, s.known,
-                                       s.info))
-    return rc;
-  hipStream_t st = pr::ctx_stream(ctx);
   const size_t QK = (size_t)g->v.query_capacity * (size_t)params->k;
-  hipError_t e = hipSuccess;
-  auto back = [&e, st](void* dst, const void* src, size_t bytes) {
-    if (e == hipSuccess && dst && bytes) e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st);
-  };
-  back(idx, s.idx, 4 * QK); back(d2, s.d2, 8 * QK); back(T0, s.T0, 96 * QK); back(pair_src, s.pair_src, 4 * QK); back(pair_dst, s.pair_dst, 4 * QK);
-  back(known, s.known, QK); back(info, s.info, 16);
-  const hipError_t es = hipStreamSynchronize(st);                // the host arrays are in flight until here
-  if (e == hipSuccess) e = es;
-  if (e != hipSuccess) return fail(ctx, pr::hip_code(e), "pr_proximity_search: %s", hipGetErrorString(e));
-  return PR_OK;
+  pr::Transfer t(ctx);
+  t.run([&] {
+    return pr_proximity_search_dev(g, d_poses, d_n, d_qrange, params, log, log_edge_capacity, s.idx, s.d2, s.T0, s.pair_src, s.pair_dst, s.known,
+                                   s.info);
+  });
+  t.down(idx, s.idx, 4 * QK); t.down(d2, s.d2, 8 * QK); t.down(T0, s.T0, 96 * QK); t.down(pair_src, s.pair_src, 4 * QK);
+  t.down(pair_dst, s.pair_dst, 4 * QK); t.down(known, s.known, QK); t.down(info, s.info, 16);
+  return t.finish(ctx, "pr_proximity_search");
 }
 
 }  // extern "C"

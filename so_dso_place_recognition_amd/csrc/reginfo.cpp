@@ -1,14 +1,13 @@
 // reginfo.cpp — host side of the registration information (reginfo.hip): the opaque pr_reginfo, its ONE allocation, the
-// argument checks, the two stream-ordered calls and their host forms.
+// argument checks, the two stream-ordered calls and their host forms, on the shared handle core (handle_core.hpp).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <new>
 
 #include "../../include/place_recognition.h"
-#include "host_common.hpp"
+#include "handle_core.hpp"
 #include "kernels.hpp"
 #include "reginfo.hpp"
 
@@ -20,20 +19,18 @@ static_assert(pr::REGINFO_OFF == PR_REGINFO_OFF && pr::REGINFO_NONFINITE == PR_R
 namespace {
 
 // where the parts of the one allocation lie (each on a 16-byte boundary); the formula of the header
-struct Layout {
-  size_t part, s_xyz, s_offs, s_src, s_T, s_acc, s_ooffs, s_idx, s_d2, s_world, s_normals, s_ninfo, o_H, o_cov, o_spec, o_w, o_stat, o_ok, total;
+struct Layout : pr::Arena {
+  size_t part, s_xyz, s_offs, s_src, s_T, s_acc, s_ooffs, s_idx, s_d2, s_world, s_normals, s_ninfo, o_H, o_cov, o_spec, o_w, o_stat, o_ok;
 };
 
 Layout layout_of(int32_t pcap, int32_t max_src) {
   const size_t pc = (size_t)pcap, ld = (size_t)std::max(max_src, 1), nch = (ld + 255) / 256;
   Layout l;
-  l.total = 0;
-  auto take = [&l](size_t bytes) { const size_t o = l.total; l.total += (bytes + 15) & ~(size_t)15; return o; };
-  l.part = take(8 * pc * nch * pr::REGINFO_NS);
-  l.s_xyz = take(24 * pc * ld); l.s_offs = take(8 * (pc + 1)); l.s_src = take(4 * pc); l.s_T = take(96 * pc); l.s_acc = take(pc);
-  l.s_ooffs = take(8 * (pc + 1)); l.s_idx = take(4 * pc * ld); l.s_d2 = take(8 * pc * ld);
-  l.s_world = take(24 * pc * ld); l.s_normals = take(24 * pc * ld); l.s_ninfo = take(4 * pc * ld);
-  l.o_H = take(288 * pc); l.o_cov = take(288 * pc); l.o_spec = take(128 * pc); l.o_w = take(16 * pc); l.o_stat = take(16 * pc); l.o_ok = take(pc);
+  l.part = l.take(8 * pc * nch * pr::REGINFO_NS);
+  l.s_xyz = l.take(24 * pc * ld); l.s_offs = l.take(8 * (pc + 1)); l.s_src = l.take(4 * pc); l.s_T = l.take(96 * pc); l.s_acc = l.take(pc);
+  l.s_ooffs = l.take(8 * (pc + 1)); l.s_idx = l.take(4 * pc * ld); l.s_d2 = l.take(8 * pc * ld);
+  l.s_world = l.take(24 * pc * ld); l.s_normals = l.take(24 * pc * ld); l.s_ninfo = l.take(4 * pc * ld);
+  l.o_H = l.take(288 * pc); l.o_cov = l.take(288 * pc); l.o_spec = l.take(128 * pc); l.o_w = l.take(16 * pc); l.o_stat = l.take(16 * pc); l.o_ok = l.take(pc);
   return l;
 }
 
@@ -41,16 +38,15 @@ bool sizes_ok(int32_t pcap, int32_t max_src) { return pcap >= 1 && pcap <= 65535
 
 }  // namespace
 
-struct pr_reginfo {
-  pr_ctx* ctx = nullptr;
+struct pr_reginfo : pr::Handle {     // scratch: the partial sums and the staging of the host forms
   int32_t pair_cap = 0, max_src = 0, ld = 1, nchunks = 1;
-  void* scratch = nullptr;            // one allocation
   double* part = nullptr;             // [pair_capacity][nchunks][REGINFO_NS]
   Layout l;
 };
 
 namespace {
 
+using pr::at;
 using pr::fail;
 
 struct Outputs { double* H; double* cov; double* spec; double* w; int32_t* stat; uint8_t* ok; };
@@ -131,45 +127,39 @@ int run_host(pr_reginfo* ri, int plane, const double* xyz_q, const int64_t* offs
                 (long long)out_capacity);
   if (c == 0) return PR_OK;
   PR_CHECK_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
-  hipStream_t st = pr::ctx_stream(ctx);
-  char* b = static_cast<char*>(ri->scratch);
+  void* b = ri->scratch;
   const Layout& l = ri->l;
-  const size_t oc = (size_t)out_capacity, C = (size_t)c;
-  auto up = [&](size_t off, const void* src, size_t bytes) {
-    return bytes ? hipMemcpyAsync(b + off, src, bytes, hipMemcpyHostToDevice, st) : hipSuccess;
-  };
-  hipError_t e = up(l.s_offs, offs_q, ((size_t)Nq + 1) * 8);
-  if (e == hipSuccess) e = up(l.s_xyz, xyz_q, (size_t)offs_q[Nq] * 24);
-  if (e == hipSuccess) e = up(l.s_src, pair_src, C * 4);
-  if (e == hipSuccess) e = up(l.s_T, T, C * 96);
-  if (e == hipSuccess && accepted) e = up(l.s_acc, accepted, C);
-  if (e == hipSuccess) e = up(l.s_ooffs, out_offs, (C + 1) * 8);
-  if (e == hipSuccess) e = up(l.s_idx, nn_idx, (size_t)out_offs[c] * 4);
-  if (e == hipSuccess) e = up(l.s_d2, nn_d2, (size_t)out_offs[c] * 8);
-  if (e == hipSuccess && plane) e = up(l.s_world, world_xyz, oc * 24);
-  if (e == hipSuccess && plane) e = up(l.s_normals, normals, oc * 24);
-  if (e == hipSuccess && plane) e = up(l.s_ninfo, ninfo, oc * 4);
-  const Outputs d{reinterpret_cast<double*>(b + l.o_H), reinterpret_cast<double*>(b + l.o_cov), reinterpret_cast<double*>(b + l.o_spec),
-                  reinterpret_cast<double*>(b + l.o_w), reinterpret_cast<int32_t*>(b + l.o_stat), reinterpret_cast<uint8_t*>(b + l.o_ok)};
-  int rc = PR_OK;
-  if (e == hipSuccess)
-    rc = run_dev(ri, plane, reinterpret_cast<const double*>(b + l.s_xyz), reinterpret_cast<const int64_t*>(b + l.s_offs), Nq,
-                 reinterpret_cast<const int32_t*>(b + l.s_src), c, reinterpret_cast<const double*>(b + l.s_T),
-                 accepted ? reinterpret_cast<const uint8_t*>(b + l.s_acc) : nullptr, reinterpret_cast<const int64_t*>(b + l.s_ooffs),
-                 reinterpret_cast<const int32_t*>(b + l.s_idx), reinterpret_cast<const double*>(b + l.s_d2),
-                 reinterpret_cast<const double*>(b + l.s_world), out_capacity, reinterpret_cast<const double*>(b + l.s_normals),
-                 reinterpret_cast<const int32_t*>(b + l.s_ninfo), max_corr, min_inliers, min_ratio, sigma_min, w_max, d);
-  auto down = [&](void* dst, const void* src, size_t bytes) { return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st); };
-  if (rc == PR_OK && e == hipSuccess) e = down(o.H, d.H, C * 288);
-  if (rc == PR_OK && e == hipSuccess) e = down(o.cov, d.cov, C * 288);
-  if (rc == PR_OK && e == hipSuccess) e = down(o.spec, d.spec, C * 128);
-  if (rc == PR_OK && e == hipSuccess) e = down(o.w, d.w, C * 16);
-  if (rc == PR_OK && e == hipSuccess) e = down(o.stat, d.stat, C * 16);
-  if (rc == PR_OK && e == hipSuccess) e = down(o.ok, d.ok, C);
-  const hipError_t es = hipStreamSynchronize(st);                 // the host arrays are in flight until here
-  if (e == hipSuccess) e = es;
-  if (rc == PR_OK && e != hipSuccess) rc = fail(ctx, pr::hip_code(e), "%s: %s", fn, hipGetErrorString(e));
-  return rc;
+  const size_t oc = plane ? (size_t)out_capacity : 0, C = (size_t)c;
+  double *s_xyz = at<double>(b, l.s_xyz), *s_T = at<double>(b, l.s_T), *s_d2 = at<double>(b, l.s_d2), *s_world = at<double>(b, l.s_world),
+         *s_normals = at<double>(b, l.s_normals);
+  int64_t *s_offs = at<int64_t>(b, l.s_offs), *s_ooffs = at<int64_t>(b, l.s_ooffs);
+  int32_t *s_src = at<int32_t>(b, l.s_src), *s_idx = at<int32_t>(b, l.s_idx), *s_ninfo = at<int32_t>(b, l.s_ninfo);
+  uint8_t* s_acc = at<uint8_t>(b, l.s_acc);
+  const Outputs d{at<double>(b, l.o_H), at<double>(b, l.o_cov), at<double>(b, l.o_spec), at<double>(b, l.o_w), at<int32_t>(b, l.o_stat),
+                  at<uint8_t>(b, l.o_ok)};
+  pr::Transfer t(ctx);
+  t.up(s_offs, offs_q, ((size_t)Nq + 1) * 8);
+  t.up(s_xyz, xyz_q, (size_t)offs_q[Nq] * 24);
+  t.up(s_src, pair_src, C * 4);
+  t.up(s_T, T, C * 96);
+  t.up_opt(s_acc, accepted, C);
+  t.up(s_ooffs, out_offs, (C + 1) * 8);
+  t.up(s_idx, nn_idx, (size_t)out_offs[c] * 4);
+  t.up(s_d2, nn_d2, (size_t)out_offs[c] * 8);
+  t.up(s_world, world_xyz, oc * 24);                                // (the plane form's alone)
+  t.up(s_normals, normals, oc * 24);
+  t.up(s_ninfo, ninfo, oc * 4);
+  t.run([&] {
+    return run_dev(ri, plane, s_xyz, s_offs, Nq, s_src, c, s_T, accepted ? s_acc : nullptr, s_ooffs, s_idx, s_d2, s_world, out_capacity, s_normals,
+                   s_ninfo, max_corr, min_inliers, min_ratio, sigma_min, w_max, d);
+  });
+  t.down(o.H, d.H, C * 288);
+  t.down(o.cov, d.cov, C * 288);
+  t.down(o.spec, d.spec, C * 128);
+  t.down(o.w, d.w, C * 16);
+  t.down(o.stat, d.stat, C * 16);
+  t.down(o.ok, d.ok, C);
+  return t.finish(ctx, fn);
 }
 
 }  // namespace
@@ -187,38 +177,19 @@ int pr_reginfo_create(pr_ctx* ctx, int32_t pair_capacity, int32_t max_src_pts, p
   if (pair_capacity < 1 || pair_capacity > 65535) return fail(ctx, PR_EINVAL, "pr_reginfo_create: pair_capacity=%d outside 1 .. 65535", pair_capacity);
   if (max_src_pts < 0 || max_src_pts > (1 << 26)) return fail(ctx, PR_EINVAL, "pr_reginfo_create: max_src_pts=%d outside 0 .. 2^26", max_src_pts);
   if (!ctx) return fail(nullptr, PR_EINVAL, "pr_reginfo_create: ctx is NULL");
-  PR_CHECK_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
-  pr_reginfo* ri = new (std::nothrow) pr_reginfo;
-  if (!ri) return fail(ctx, PR_ENOMEM, "out of host memory");
-  ri->ctx = ctx; ri->pair_cap = pair_capacity; ri->max_src = max_src_pts;
+  const Layout l = layout_of(pair_capacity, max_src_pts);
+  pr::Owned<pr_reginfo> ri;
+  if (int rc = pr::make(ctx, "pr_reginfo_create", l.total, ri)) return rc;
+  ri->pair_cap = pair_capacity; ri->max_src = max_src_pts;
   ri->ld = std::max(max_src_pts, 1); ri->nchunks = (ri->ld + 255) / 256;
-  ri->l = layout_of(pair_capacity, max_src_pts);
-  hipError_t e = hipMalloc(&ri->scratch, ri->l.total);
-  if (e != hipSuccess) {
-    const size_t total = ri->l.total;
-    delete ri;
-    return fail(ctx, e == hipErrorOutOfMemory ? PR_ENOMEM : PR_EHIP, "pr_reginfo_create: scratch of %zu bytes: %s", total, hipGetErrorString(e));
-  }
-  ri->part = reinterpret_cast<double*>(static_cast<char*>(ri->scratch) + ri->l.part);
-  hipStream_t st = pr::ctx_stream(ctx);
-  e = hipMemsetAsync(ri->scratch, 0, ri->l.total, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) {
-    (void)hipFree(ri->scratch);
-    delete ri;
-    return fail(ctx, PR_EHIP, "pr_reginfo_create: clearing the scratch failed: %s", hipGetErrorString(e));
-  }
-  *out = ri;
-  return PR_OK;
+  ri->l = l;
+  ri->part = at<double>(ri->scratch, l.part);
+  pr::Transfer t(ctx);
+  t.fill(ri->scratch, 0, l.total);
+  return pr::commit(ri, t, "pr_reginfo_create", out);
 }
 
-void pr_reginfo_destroy(pr_reginfo* ri) {
-  if (!ri) return;
-  (void)hipSetDevice(pr::ctx_device(ri->ctx));
-  (void)hipStreamSynchronize(pr::ctx_stream(ri->ctx));
-  (void)hipFree(ri->scratch);
-  delete ri;
-}
+void pr_reginfo_destroy(pr_reginfo* ri) { pr::destroy(ri); }
 
 int pr_reginfo_point_dev(pr_reginfo* ri, const double* d_xyz_q, const int64_t* d_offs_q, int32_t Nq, const int32_t* d_pair_src, int32_t c,
                          const double* d_T, const uint8_t* d_accepted, const int64_t* d_out_offs, const int32_t* d_nn_idx, const double* d_nn_d2,

@@ -1,12 +1,12 @@
 // seqmatch.cpp — host side of the sequence matcher (seqmatch.hip): the tile constants, the argument checks and the
 // stream-ordered launch of the batch form.  The host-buffer form (pr_match_topk_seq_f64) lives with the shared top-k pipeline in pr_api.cpp.
+// The online form (pr_seqmatch, its ONE scratch allocation, push and read) stands on the shared handle core (handle_core.hpp).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <new>
 
 #include "../../include/place_recognition.h"
-#include "host_common.hpp"
+#include "handle_core.hpp"
 #include "kernels.hpp"
 #include "seqmatch.hpp"
 
@@ -14,6 +14,7 @@ static_assert(pr::SEQ_REACH == PR_SEQ_MAX_STEP && pr::SEQ_MAX_L == PR_SEQ_MAX_L 
               "the header's limits");
 static_assert(pr::SEQ_ONLINE_MAX_K == PR_SEQMATCH_MAX_K, "the header's limit of the online form");
 
+using pr::at;
 using pr::fail;
 
 extern "C" {
@@ -47,10 +48,8 @@ int pr_seq_select_dev(pr_ctx* ctx, const float* d_p, const float* d_i, int32_t m
 }  // extern "C"
 
 // ------------------------------------------------------------------------------------------------------------------ the online form
-struct pr_seqmatch {
-  pr_ctx* ctx = nullptr;
+struct pr_seqmatch : pr::Handle {    // scratch: everything SeqView names, then the staging of the host form
   pr::SeqView v;
-  void* block = nullptr;              // the one allocation: everything SeqView names, then the staging of the host form
   size_t state_bytes = 0;             // ring | ids | count: what reset clears
   double* stage_rows = nullptr;       // [channels][capacity]
   int32_t* stage_count = nullptr;     // [4]
@@ -64,21 +63,19 @@ namespace {
 
 constexpr int32_t SEQ_MAX_CAPACITY = 1 << 24;
 
-struct Layout {
-  size_t ring, ids, count, stats, ctl, steps, lscore, lj, lv, s_rows, s_count, s_score, s_idx, s_vel, s_info, total;
+struct Layout : pr::Arena {
+  size_t ring, ids, count, stats, ctl, steps, lscore, lj, lv, s_rows, s_count, s_score, s_idx, s_vel, s_info;
 };
 
 // where the parts of the one allocation lie (each on a 16-byte boundary); the formula of the header
 Layout layout_of(int32_t capacity, int32_t channels, int32_t V, int32_t L, int32_t max_k) {
   const size_t cap = (size_t)capacity, B = (cap + pr::SEQ_PUSH_COLS - 1) / pr::SEQ_PUSH_COLS, K = (size_t)max_k;
   Layout l;
-  l.total = 0;
-  auto take = [&l](size_t bytes) { const size_t o = l.total; l.total += (bytes + 15) & ~(size_t)15; return o; };
-  l.ring = take(8 * cap * L); l.ids = take(4 * (size_t)L); l.count = take(16);
-  l.stats = take(64); l.ctl = take(16); l.steps = take(4 * (size_t)V * L);
-  l.lscore = take(8 * B * K); l.lj = take(4 * B * K); l.lv = take(4 * B * K);
-  l.s_rows = take(8 * cap * channels); l.s_count = take(16); l.s_score = take(8 * K); l.s_idx = take(4 * K); l.s_vel = take(4 * K);
-  l.s_info = take(16);
+  l.ring = l.take(8 * cap * L); l.ids = l.take(4 * (size_t)L); l.count = l.take(16);
+  l.stats = l.take(64); l.ctl = l.take(16); l.steps = l.take(4 * (size_t)V * L);
+  l.lscore = l.take(8 * B * K); l.lj = l.take(4 * B * K); l.lv = l.take(4 * B * K);
+  l.s_rows = l.take(8 * cap * channels); l.s_count = l.take(16); l.s_score = l.take(8 * K); l.s_idx = l.take(4 * K); l.s_vel = l.take(4 * K);
+  l.s_info = l.take(16);
   return l;
 }
 
@@ -110,53 +107,30 @@ int pr_seqmatch_create(pr_ctx* ctx, int32_t capacity, int32_t channels, const in
   if (max_k < 1 || max_k > pr::SEQ_ONLINE_MAX_K)
     return fail(ctx, PR_EINVAL, "pr_seqmatch_create: max_k=%d outside 1 .. %d", max_k, pr::SEQ_ONLINE_MAX_K);
   if (!ctx) return fail(nullptr, PR_EINVAL, "pr_seqmatch_create: ctx is NULL");
-  PR_CHECK_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
-  pr_seqmatch* s = new (std::nothrow) pr_seqmatch;
-  if (!s) return fail(ctx, PR_ENOMEM, "out of host memory");
-  s->ctx = ctx;
   const Layout l = layout_of(capacity, channels, V, L, max_k);
-  hipError_t e = hipMalloc(&s->block, l.total);
-  if (e != hipSuccess) {
-    delete s;
-    return fail(ctx, pr::hip_code(e), "pr_seqmatch_create: allocation of %zu bytes: %s", l.total, hipGetErrorString(e));
-  }
-  char* b = static_cast<char*>(s->block);
-  auto dp = [b](size_t o) { return reinterpret_cast<double*>(b + o); };
-  auto ip = [b](size_t o) { return reinterpret_cast<int*>(b + o); };
+  pr::Owned<pr_seqmatch> s;
+  if (int rc = pr::make(ctx, "pr_seqmatch_create", l.total, s)) return rc;
+  void* b = s->scratch;
   pr::SeqView& v = s->v;
   v.capacity = capacity; v.channels = channels; v.V = V; v.L = L; v.max_k = max_k;
   v.blocks = (capacity + pr::SEQ_PUSH_COLS - 1) / pr::SEQ_PUSH_COLS;
-  v.ring = dp(l.ring); v.ids = ip(l.ids); v.count = ip(l.count); v.stats = dp(l.stats); v.ctl = ip(l.ctl); v.steps = ip(l.steps);
-  v.lscore = dp(l.lscore); v.lj = ip(l.lj); v.lv = ip(l.lv);
+  v.ring = at<double>(b, l.ring); v.ids = at<int>(b, l.ids); v.count = at<int>(b, l.count); v.stats = at<double>(b, l.stats);
+  v.ctl = at<int>(b, l.ctl); v.steps = at<int>(b, l.steps); v.lscore = at<double>(b, l.lscore); v.lj = at<int>(b, l.lj); v.lv = at<int>(b, l.lv);
   s->state_bytes = l.stats;                                       // ring | ids | count lie first
-  s->stage_rows = dp(l.s_rows); s->stage_count = ip(l.s_count); s->stage_score = dp(l.s_score);
-  s->stage_idx = ip(l.s_idx); s->stage_vel = ip(l.s_vel); s->stage_info = ip(l.s_info);
-  hipStream_t st = pr::ctx_stream(ctx);
-  e = hipMemsetAsync(s->block, 0, l.total, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(ip(l.steps), steps, 4 * (size_t)V * L, hipMemcpyHostToDevice, st);
-  const hipError_t es = hipStreamSynchronize(st);                 // the host table is in flight until here
-  if (e == hipSuccess) e = es;
-  if (e != hipSuccess) {
-    (void)hipFree(s->block);
-    delete s;
-    return fail(ctx, PR_EHIP, "pr_seqmatch_create: clearing the block and uploading the step table failed: %s", hipGetErrorString(e));
-  }
-  *out = s;
-  return PR_OK;
+  s->stage_rows = at<double>(b, l.s_rows); s->stage_count = at<int32_t>(b, l.s_count); s->stage_score = at<double>(b, l.s_score);
+  s->stage_idx = at<int32_t>(b, l.s_idx); s->stage_vel = at<int32_t>(b, l.s_vel); s->stage_info = at<int32_t>(b, l.s_info);
+  pr::Transfer t(ctx);
+  t.fill(b, 0, l.total);
+  t.up(at<int>(b, l.steps), steps, 4 * (size_t)V * L);
+  return pr::commit(s, t, "pr_seqmatch_create", out);
 }
 
-void pr_seqmatch_destroy(pr_seqmatch* s) {
-  if (!s) return;
-  (void)hipSetDevice(pr::ctx_device(s->ctx));
-  (void)hipStreamSynchronize(pr::ctx_stream(s->ctx));
-  (void)hipFree(s->block);
-  delete s;
-}
+void pr_seqmatch_destroy(pr_seqmatch* s) { pr::destroy(s); }
 
 int pr_seqmatch_reset(pr_seqmatch* s) {
   if (!s) return fail(nullptr, PR_EINVAL, "pr_seqmatch_reset: handle is NULL");
   PR_CHECK_HIP(s->ctx, hipSetDevice(pr::ctx_device(s->ctx)));
-  PR_CHECK_HIP(s->ctx, hipMemsetAsync(s->block, 0, s->state_bytes, pr::ctx_stream(s->ctx)));   // stream-ordered: ring, row ids, counter
+  PR_CHECK_HIP(s->ctx, hipMemsetAsync(s->scratch, 0, s->state_bytes, pr::ctx_stream(s->ctx)));   // stream-ordered: ring, row ids, counter
   return PR_OK;
 }
 
@@ -192,38 +166,29 @@ int pr_seqmatch_push(pr_seqmatch* s, const double* rows, int32_t count, const do
   if (int rc = push_checks(s, "pr_seqmatch_push", rows, &count, weights, normalize, mask_width, k, idx, score, vel, info)) return rc;
   pr_ctx* ctx = s->ctx;
   PR_CHECK_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
-  hipStream_t st = pr::ctx_stream(ctx);
-  const size_t rb = 8 * (size_t)s->v.capacity * s->v.channels;
-  hipError_t e = hipMemcpyAsync(s->stage_rows, rows, rb, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(s->stage_count, &count, 4, hipMemcpyHostToDevice, st);
-  int rc = PR_OK;
-  if (e == hipSuccess)
-    rc = pr_seqmatch_push_dev(s, s->stage_rows, s->stage_count, nullptr, weights, normalize, mask_width, k, s->stage_idx, s->stage_score,
-                              s->stage_vel, s->stage_info);
-  if (e == hipSuccess && rc == PR_OK) e = hipMemcpyAsync(idx, s->stage_idx, 4 * (size_t)k, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess && rc == PR_OK) e = hipMemcpyAsync(score, s->stage_score, 8 * (size_t)k, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess && rc == PR_OK) e = hipMemcpyAsync(vel, s->stage_vel, 4 * (size_t)k, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess && rc == PR_OK) e = hipMemcpyAsync(info, s->stage_info, 16, hipMemcpyDeviceToHost, st);
-  const hipError_t es = hipStreamSynchronize(st);                 // the host arrays are in flight until here
-  if (rc) return rc;
-  if (e == hipSuccess) e = es;
-  if (e != hipSuccess) return fail(ctx, pr::hip_code(e), "pr_seqmatch_push: %s", hipGetErrorString(e));
-  return PR_OK;
+  pr::Transfer t(ctx);
+  t.up(s->stage_rows, rows, 8 * (size_t)s->v.capacity * s->v.channels);
+  t.up(s->stage_count, &count, 4);
+  t.run([&] {
+    return pr_seqmatch_push_dev(s, s->stage_rows, s->stage_count, nullptr, weights, normalize, mask_width, k, s->stage_idx, s->stage_score,
+                                s->stage_vel, s->stage_info);
+  });
+  t.down(idx, s->stage_idx, 4 * (size_t)k);
+  t.down(score, s->stage_score, 8 * (size_t)k);
+  t.down(vel, s->stage_vel, 4 * (size_t)k);
+  t.down(info, s->stage_info, 16);
+  return t.finish(ctx, "pr_seqmatch_push");
 }
 
 int pr_seqmatch_read(pr_seqmatch* s, double* ring, int32_t* ids, int32_t* pushes) {
   if (!s) return fail(nullptr, PR_EINVAL, "pr_seqmatch_read: handle is NULL");
   pr_ctx* ctx = s->ctx;
   PR_CHECK_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
-  hipStream_t st = pr::ctx_stream(ctx);
-  hipError_t e = hipSuccess;
-  if (ring) e = hipMemcpyAsync(ring, s->v.ring, 8 * (size_t)s->v.capacity * s->v.L, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess && ids) e = hipMemcpyAsync(ids, s->v.ids, 4 * (size_t)s->v.L, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess && pushes) e = hipMemcpyAsync(pushes, s->v.count, 4, hipMemcpyDeviceToHost, st);
-  const hipError_t es = hipStreamSynchronize(st);
-  if (e == hipSuccess) e = es;
-  if (e != hipSuccess) return fail(ctx, pr::hip_code(e), "pr_seqmatch_read: %s", hipGetErrorString(e));
-  return PR_OK;
+  pr::Transfer t(ctx);
+  t.down(ring, s->v.ring, 8 * (size_t)s->v.capacity * s->v.L);
+  t.down(ids, s->v.ids, 4 * (size_t)s->v.L);
+  t.down(pushes, s->v.count, 4);
+  return t.finish(ctx, "pr_seqmatch_read");
 }
 
 }  // extern "C"

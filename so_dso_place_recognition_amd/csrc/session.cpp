@@ -1,15 +1,14 @@
 // session.cpp — host side of the drive sessions (session.hip): the opaque pr_session over the caller's two buffers, its ONE
 // scratch allocation, the argument checks, the stream-ordered entry points and their host forms, and the relaxation across breaks, which
-// fills the break array and hands it to the pose graph's own relaxation.
+// fills the break array and hands it to the pose graph's own relaxation.  Layout, create tail, destroy and copy chains: handle_core.hpp.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstdio>
 #include <cstring>
-#include <new>
 
 #include "../../include/place_recognition.h"
-#include "host_common.hpp"
+#include "handle_core.hpp"
 #include "kernels.hpp"
 #include "posegraph.hpp"
 #include "session.hpp"
@@ -22,10 +21,8 @@ static_assert(pr::SESSION_ALIGNED == PR_SESSION_ALIGNED && pr::SESSION_NO_TARGET
               pr::SESSION_NONFINITE == PR_SESSION_NONFINITE, "status values");
 static_assert(sizeof(pr_session_align_params) == 24, "two int32 and two doubles, no padding");
 
-struct pr_session {
-  pr_ctx* ctx = nullptr;
+struct pr_session : pr::Handle {     // scratch: everything SessionView names and the staging of the host forms
   pr::SessionView v;
-  void* scratch = nullptr;            // one allocation: everything SessionView names and the staging of the host forms
   double* stage_G = nullptr;          // [12]
   double* stage_hyp = nullptr;        // [edge_capacity][12]
   int32_t* stage_support = nullptr;   // [edge_capacity]
@@ -36,23 +33,22 @@ struct pr_session {
 
 namespace {
 
+using pr::at;
 using pr::fail;
 
 constexpr int32_t MAX_NODES = 1 << 20, MAX_EDGES = 65536, MAX_SESSIONS = pr::SESSION_MAX;
 
 // where the parts of the one scratch allocation lie (each on a 16-byte boundary); the formula of the header
-struct Layout {
-  size_t sid, brk, cand, q, hyp, c, p, sup, inl, gd, ctl, s_G, s_hyp, s_support, s_inlier, s_info, s_begin, total;
+struct Layout : pr::Arena {
+  size_t sid, brk, cand, q, hyp, c, p, sup, inl, gd, ctl, s_G, s_hyp, s_support, s_inlier, s_info, s_begin;
 };
 
 Layout layout_of(int32_t node_capacity, int32_t edge_capacity) {
   const size_t NC = (size_t)node_capacity, EC = (size_t)edge_capacity;
   Layout l;
-  l.total = 0;
-  auto take = [&l](size_t bytes) { const size_t o = l.total; l.total += (bytes + 15) & ~(size_t)15; return o; };
-  l.sid = take(4 * NC); l.brk = take(4 * NC); l.cand = take(4 * EC); l.q = take(4 * EC); l.hyp = take(96 * EC); l.c = take(24 * EC);
-  l.p = take(24 * EC); l.sup = take(4 * EC); l.inl = take(4 * EC); l.gd = take(192); l.ctl = take(48);
-  l.s_G = take(96); l.s_hyp = take(96 * EC); l.s_support = take(4 * EC); l.s_inlier = take(EC); l.s_info = take(32); l.s_begin = take(16);
+  l.sid = l.take(4 * NC); l.brk = l.take(4 * NC); l.cand = l.take(4 * EC); l.q = l.take(4 * EC); l.hyp = l.take(96 * EC); l.c = l.take(24 * EC);
+  l.p = l.take(24 * EC); l.sup = l.take(4 * EC); l.inl = l.take(4 * EC); l.gd = l.take(192); l.ctl = l.take(48);
+  l.s_G = l.take(96); l.s_hyp = l.take(96 * EC); l.s_support = l.take(4 * EC); l.s_inlier = l.take(EC); l.s_info = l.take(32); l.s_begin = l.take(16);
   return l;
 }
 
@@ -106,51 +102,29 @@ int pr_session_create(pr_ctx* ctx, const pr_session_buffers* buffers, int32_t no
   if (session_capacity < 1 || session_capacity > MAX_SESSIONS)
     return fail(ctx, PR_EINVAL, "pr_session_create: session_capacity=%d outside 1 .. %d", session_capacity, MAX_SESSIONS);
   if (!ctx) return fail(nullptr, PR_EINVAL, "pr_session_create: ctx is NULL");
-  PR_CHECK_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
-  pr_session* s = new (std::nothrow) pr_session;
-  if (!s) return fail(ctx, PR_ENOMEM, "out of host memory");
-  s->ctx = ctx;
+  const Layout l = layout_of(node_capacity, edge_capacity);
+  pr::Owned<pr_session> s;
+  if (int rc = pr::make(ctx, "pr_session_create", l.total, s)) return rc;
   pr::SessionView& v = s->v;
   memset(&v, 0, sizeof v);
   v.start = buffers->start; v.state = buffers->state;
   v.node_capacity = node_capacity; v.edge_capacity = edge_capacity; v.session_capacity = session_capacity;
-  const Layout l = layout_of(node_capacity, edge_capacity);
-  hipError_t e = hipMalloc(&s->scratch, l.total);
-  if (e != hipSuccess) {
-    delete s;
-    return fail(ctx, e == hipErrorOutOfMemory ? PR_ENOMEM : PR_EHIP, "pr_session_create: scratch of %zu bytes: %s", l.total, hipGetErrorString(e));
+  void* b = s->scratch;
+  v.sid = at<int>(b, l.sid); v.brk = at<int>(b, l.brk); v.cand = at<int>(b, l.cand); v.q = at<int>(b, l.q); v.hyp = at<double>(b, l.hyp);
+  v.c = at<double>(b, l.c); v.p = at<double>(b, l.p); v.sup = at<int>(b, l.sup); v.inl = at<int>(b, l.inl); v.gd = at<double>(b, l.gd);
+  v.ctl = at<int>(b, l.ctl);
+  s->stage_G = at<double>(b, l.s_G); s->stage_hyp = at<double>(b, l.s_hyp); s->stage_support = at<int32_t>(b, l.s_support);
+  s->stage_inlier = at<uint8_t>(b, l.s_inlier); s->stage_info = at<int32_t>(b, l.s_info); s->stage_begin = at<int32_t>(b, l.s_begin);
+  pr::Transfer t(ctx);
+  t.fill(b, 0, l.total);
+  if (t.ok()) {
+    pr::launch_session_reset(t.st, v);                           // S = 1, start[0] = 0
+    t.note(hipGetLastError());
   }
-  char* b = static_cast<char*>(s->scratch);
-  auto ip = [b](size_t o) { return reinterpret_cast<int*>(b + o); };
-  auto dp = [b](size_t o) { return reinterpret_cast<double*>(b + o); };
-  v.sid = ip(l.sid); v.brk = ip(l.brk); v.cand = ip(l.cand); v.q = ip(l.q); v.hyp = dp(l.hyp); v.c = dp(l.c); v.p = dp(l.p);
-  v.sup = ip(l.sup); v.inl = ip(l.inl); v.gd = dp(l.gd); v.ctl = ip(l.ctl);
-  s->stage_G = dp(l.s_G); s->stage_hyp = dp(l.s_hyp); s->stage_support = ip(l.s_support);
-  s->stage_inlier = reinterpret_cast<uint8_t*>(b + l.s_inlier); s->stage_info = ip(l.s_info); s->stage_begin = ip(l.s_begin);
-  hipStream_t st = pr::ctx_stream(ctx);
-  e = hipMemsetAsync(s->scratch, 0, l.total, st);
-  if (e == hipSuccess) {
-    pr::launch_session_reset(st, v);                             // S = 1, start[0] = 0
-    e = hipGetLastError();
-  }
-  const hipError_t es = hipStreamSynchronize(st);
-  if (e == hipSuccess) e = es;
-  if (e != hipSuccess) {
-    (void)hipFree(s->scratch);
-    delete s;
-    return fail(ctx, PR_EHIP, "pr_session_create: clearing the scratch and the table failed: %s", hipGetErrorString(e));
-  }
-  *out = s;
-  return PR_OK;
+  return pr::commit(s, t, "pr_session_create", out);
 }
 
-void pr_session_destroy(pr_session* s) {
-  if (!s) return;
-  (void)hipSetDevice(pr::ctx_device(s->ctx));
-  (void)hipStreamSynchronize(pr::ctx_stream(s->ctx));
-  (void)hipFree(s->scratch);          // the two buffers are the caller's
-  delete s;
-}
+void pr_session_destroy(pr_session* s) { pr::destroy(s); }      // the two buffers are the caller's
 
 int pr_session_reset(pr_session* s) {
   if (!s) return fail(nullptr, PR_EINVAL, "pr_session_reset: session table is NULL");
@@ -163,11 +137,8 @@ int pr_session_reset(pr_session* s) {
 int pr_session_count(pr_session* s, int32_t* sessions, int32_t* flags) {
   if (!s) return fail(nullptr, PR_EINVAL, "pr_session_count: session table is NULL");
   if (!sessions || !flags) return fail(s->ctx, PR_EINVAL, "pr_session_count: a required pointer is NULL");
-  PR_CHECK_HIP(s->ctx, hipSetDevice(pr::ctx_device(s->ctx)));
-  hipStream_t st = pr::ctx_stream(s->ctx);
   int32_t w[4];
-  PR_CHECK_HIP(s->ctx, hipMemcpyAsync(w, s->v.state, sizeof w, hipMemcpyDeviceToHost, st));
-  PR_CHECK_HIP(s->ctx, hipStreamSynchronize(st));
+  if (int rc = pr::read_state(s->ctx, "pr_session_count", s->v.state, w)) return rc;
   *sessions = w[0];
   *flags = w[1];
   return PR_OK;
@@ -187,13 +158,10 @@ int pr_session_begin(pr_session* s, const int32_t* d_n, int32_t* info) {
   if (!s) return fail(nullptr, PR_EINVAL, "pr_session_begin: session table is NULL");
   pr_ctx* ctx = s->ctx;
   if (!d_n || !info) return fail(ctx, PR_EINVAL, "pr_session_begin: a required pointer is NULL (d_n, info)");
-  if (int rc = pr_session_begin_dev(s, d_n, s->stage_begin)) return rc;
-  hipStream_t st = pr::ctx_stream(ctx);
-  hipError_t e = hipMemcpyAsync(info, s->stage_begin, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, st);
-  const hipError_t es = hipStreamSynchronize(st);                // the host array is in flight until here
-  if (e == hipSuccess) e = es;
-  if (e != hipSuccess) return fail(ctx, pr::hip_code(e), "pr_session_begin: %s", hipGetErrorString(e));
-  return PR_OK;
+  pr::Transfer t(ctx);
+  t.run([&] { return pr_session_begin_dev(s, d_n, s->stage_begin); });
+  t.down(info, s->stage_begin, 4 * sizeof(int32_t));
+  return t.finish(ctx, "pr_session_begin");
 }
 
 int pr_session_align_dev(pr_session* s, const pr_posegraph_buffers* log, int32_t log_edge_capacity, const double* d_poses_in, const int32_t* d_n,
@@ -214,20 +182,18 @@ int pr_session_align(pr_session* s, const pr_posegraph_buffers* log, int32_t log
                      int32_t* info) {
   if (int rc = align_check("pr_session_align", s, log, log_edge_capacity, d_poses_in, d_n, params, d_poses_out, G, info)) return rc;
   pr_ctx* ctx = s->ctx;
-  if (int rc = pr_session_align_dev(s, log, log_edge_capacity, d_poses_in, d_n, params, d_poses_out, s->stage_G, hyp ? s->stage_hyp : nullptr,
-                                    support ? s->stage_support : nullptr, inlier ? s->stage_inlier : nullptr, s->stage_info))
-    return rc;
-  hipStream_t st = pr::ctx_stream(ctx);
   const size_t EC = (size_t)s->v.edge_capacity;
-  hipError_t e = hipMemcpyAsync(info, s->stage_info, 8 * sizeof(int32_t), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(G, s->stage_G, 12 * sizeof(double), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess && hyp) e = hipMemcpyAsync(hyp, s->stage_hyp, 96 * EC, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess && support) e = hipMemcpyAsync(support, s->stage_support, 4 * EC, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess && inlier) e = hipMemcpyAsync(inlier, s->stage_inlier, EC, hipMemcpyDeviceToHost, st);
-  const hipError_t es = hipStreamSynchronize(st);                // the host arrays are in flight until here
-  if (e == hipSuccess) e = es;
-  if (e != hipSuccess) return fail(ctx, pr::hip_code(e), "pr_session_align: %s", hipGetErrorString(e));
-  return PR_OK;
+  pr::Transfer t(ctx);
+  t.run([&] {
+    return pr_session_align_dev(s, log, log_edge_capacity, d_poses_in, d_n, params, d_poses_out, s->stage_G, hyp ? s->stage_hyp : nullptr,
+                                support ? s->stage_support : nullptr, inlier ? s->stage_inlier : nullptr, s->stage_info);
+  });
+  t.down(info, s->stage_info, 8 * sizeof(int32_t));
+  t.down(G, s->stage_G, 12 * sizeof(double));
+  t.down(hyp, s->stage_hyp, 96 * EC);
+  t.down(support, s->stage_support, 4 * EC);
+  t.down(inlier, s->stage_inlier, EC);
+  return t.finish(ctx, "pr_session_align");
 }
 
 int pr_session_relax_dev(pr_session* s, pr_posegraph* g, const double* d_poses_in, const int32_t* d_n, const pr_posegraph_params* params,

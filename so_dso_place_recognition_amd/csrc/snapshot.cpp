@@ -6,11 +6,10 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <new>
 #include <string>
 
 #include "../../include/place_recognition.h"
-#include "host_common.hpp"
+#include "handle_core.hpp"
 #include "kernels.hpp"
 #include "snapshot.hpp"
 
@@ -24,10 +23,8 @@ static_assert(pr::SNAPSHOT_MAP == PR_SNAPSHOT_MAP && pr::SNAPSHOT_ONLINE == PR_S
 static_assert(sizeof(pr_snapshot_desc) == 112, "pointers, int32 pairs and one int64, no padding");
 static_assert(sizeof(pr::SnapshotView) <= 2048, "the view travels as a kernel argument");
 
-struct pr_snapshot {
-  pr_ctx* ctx = nullptr;
+struct pr_snapshot : pr::Handle {    // scratch: ctl | sums | the info of the host forms
   pr::SnapshotView v;
-  void* scratch = nullptr;            // one allocation: ctl | sums | the info of the host forms
   long long* stage_info = nullptr;    // [4]
   long long bound = 0;
 };
@@ -163,42 +160,21 @@ int pr_snapshot_create(pr_ctx* ctx, const pr_snapshot_desc* desc, pr_snapshot** 
   char why[256];
   if (!plan_of(desc, pl, why, sizeof why)) return fail(ctx, PR_EINVAL, "pr_snapshot_create: %s", why);
   if (!ctx) return fail(nullptr, PR_EINVAL, "pr_snapshot_create: ctx is NULL");
-  PR_CHECK_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
-  pr_snapshot* s = new (std::nothrow) pr_snapshot;
-  if (!s) return fail(ctx, PR_ENOMEM, "out of host memory");
-  s->ctx = ctx;
+  const size_t words = pr::SNAPSHOT_CTL_WORDS + pr::SNAPSHOT_MAX_SECTIONS + 4;
+  pr::Owned<pr_snapshot> s;
+  if (int rc = pr::make(ctx, "pr_snapshot_create", 8 * words, s)) return rc;
   s->v = pl.v;
   s->bound = pl.bound;
-  const size_t words = pr::SNAPSHOT_CTL_WORDS + pr::SNAPSHOT_MAX_SECTIONS + 4;
-  hipError_t e = hipMalloc(&s->scratch, 8 * words);
-  if (e != hipSuccess) {
-    delete s;
-    return fail(ctx, pr::hip_code(e), "pr_snapshot_create: %zu control bytes: %s", 8 * words, hipGetErrorString(e));
-  }
   long long* w = static_cast<long long*>(s->scratch);
   s->v.ctl = w;
   s->v.sums = reinterpret_cast<unsigned long long*>(w + pr::SNAPSHOT_CTL_WORDS);
   s->stage_info = w + pr::SNAPSHOT_CTL_WORDS + pr::SNAPSHOT_MAX_SECTIONS;
-  hipStream_t st = pr::ctx_stream(ctx);
-  e = hipMemsetAsync(s->scratch, 0, 8 * words, st);
-  const hipError_t es = hipStreamSynchronize(st);
-  if (e == hipSuccess) e = es;
-  if (e != hipSuccess) {
-    (void)hipFree(s->scratch);
-    delete s;
-    return fail(ctx, PR_EHIP, "pr_snapshot_create: clearing the control words failed: %s", hipGetErrorString(e));
-  }
-  *out = s;
-  return PR_OK;
+  pr::Transfer t(ctx);
+  t.fill(s->scratch, 0, 8 * words);
+  return pr::commit(s, t, "pr_snapshot_create", out);
 }
 
-void pr_snapshot_destroy(pr_snapshot* s) {
-  if (!s) return;
-  (void)hipSetDevice(pr::ctx_device(s->ctx));
-  (void)hipStreamSynchronize(pr::ctx_stream(s->ctx));
-  (void)hipFree(s->scratch);          // the buffers are the caller's
-  delete s;
-}
+void pr_snapshot_destroy(pr_snapshot* s) { pr::destroy(s); }    // the buffers are the caller's
 
 int pr_snapshot_desc_bound(const pr_snapshot_desc* desc, int64_t* bytes) {
   if (!bytes) return fail(nullptr, PR_EINVAL, "pr_snapshot_desc_bound: bytes is NULL");
@@ -239,18 +215,14 @@ int pr_snapshot_save(pr_snapshot* s, const char* path) {
   if (!path || !path[0]) return fail(ctx, PR_EINVAL, "pr_snapshot_save: path is NULL or empty");
   if (!s) return fail(nullptr, PR_EINVAL, "pr_snapshot_save: snapshot is NULL");
   PR_CHECK_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
-  hipStream_t st = pr::ctx_stream(ctx);
   void* d_stage = nullptr;
   PR_CHECK_HIP(ctx, hipMalloc(&d_stage, (size_t)s->bound));
   long long info[4] = {0, 0, 0, 0};
-  int rc = pr_snapshot_pack_dev(s, d_stage, s->bound, reinterpret_cast<int64_t*>(s->stage_info));
+  pr::Transfer t(ctx);
+  t.run([&] { return pr_snapshot_pack_dev(s, d_stage, s->bound, reinterpret_cast<int64_t*>(s->stage_info)); });
+  t.down(info, s->stage_info, sizeof info);
+  int rc = t.finish(ctx, "pr_snapshot_save");                    // the one synchronising read of info
   char* host = nullptr;
-  if (rc == PR_OK) {
-    hipError_t e = hipMemcpyAsync(info, s->stage_info, sizeof info, hipMemcpyDeviceToHost, st);
-    const hipError_t es = hipStreamSynchronize(st);              // the one synchronising read of info
-    if (e == hipSuccess) e = es;
-    if (e != hipSuccess) rc = fail(ctx, pr::hip_code(e), "pr_snapshot_save: %s", hipGetErrorString(e));
-  }
   if (rc == PR_OK && (info[2] != 0 || info[0] < pr::SNAPSHOT_HEADER_BYTES || info[0] > s->bound))
     rc = fail(ctx, PR_EHIP, "pr_snapshot_save: the pack reported %lld bytes, flags %lld", info[0], info[2]);
   if (rc == PR_OK) {
@@ -315,13 +287,11 @@ int pr_snapshot_load(pr_snapshot* s, const char* path, int64_t* info) {
     if (e == hipSuccess) e = hipMemcpy(d_stage, host, (size_t)size, hipMemcpyHostToDevice);
     if (e != hipSuccess) rc = fail(ctx, pr::hip_code(e), "pr_snapshot_load: staging %lld bytes: %s", size, hipGetErrorString(e));
   }
-  if (rc == PR_OK) rc = pr_snapshot_unpack_dev(s, d_stage, size, reinterpret_cast<int64_t*>(s->stage_info));
   if (rc == PR_OK) {
-    hipStream_t st = pr::ctx_stream(ctx);
-    hipError_t e = hipMemcpyAsync(info, s->stage_info, 4 * sizeof(int64_t), hipMemcpyDeviceToHost, st);
-    const hipError_t es = hipStreamSynchronize(st);
-    if (e == hipSuccess) e = es;
-    if (e != hipSuccess) rc = fail(ctx, pr::hip_code(e), "pr_snapshot_load: %s", hipGetErrorString(e));
+    pr::Transfer t(ctx);
+    t.run([&] { return pr_snapshot_unpack_dev(s, d_stage, size, reinterpret_cast<int64_t*>(s->stage_info)); });
+    t.down(info, s->stage_info, 4 * sizeof(int64_t));
+    rc = t.finish(ctx, "pr_snapshot_load");
   }
   if (d_stage) { if (s) (void)hipStreamSynchronize(pr::ctx_stream(ctx)); (void)hipFree(d_stage); }
   free(host);

@@ -1,13 +1,13 @@
 // submap.cpp — host side of the local submaps (submap.hip): the opaque pr_submap, its ONE scratch allocation, the argument
-// checks, the stream-ordered build and its host form (which stages in an allocation of its own for the call).
+// checks, the stream-ordered build and its host form (which stages in an allocation of its own for the call), on the shared handle core
+// (handle_core.hpp).
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
 #include <cstring>
-#include <new>
 
 #include "../../include/place_recognition.h"
-#include "host_common.hpp"
+#include "handle_core.hpp"
 #include "kernels.hpp"
 #include "submap.hpp"
 
@@ -15,29 +15,26 @@ static_assert(pr::SUBMAP_TRUNCATED == PR_SUBMAP_TRUNCATED && pr::SUBMAP_NO_CENTE
               "flag bits");
 static_assert(sizeof(pr_submap_params) == 16, "four int32, no padding");
 
-struct pr_submap {
-  pr_ctx* ctx = nullptr;
+struct pr_submap : pr::Handle {      // scratch: everything SubmapView names
   pr::SubmapView v;
-  void* scratch = nullptr;            // one allocation: everything SubmapView names
 };
 
 namespace {
 
+using pr::at;
 using pr::fail;
 
 constexpr int32_t MAX_SLOTS = 65535, MAX_CLOUD = 1 << 26, MAX_KEYFRAMES = 1 << 24;
 constexpr int64_t MAX_POINTS = (int64_t)1 << 40;
 
 // where the parts of the one scratch allocation lie (each on a 16-byte boundary); the formula of the header
-struct Layout { size_t row, dst, len, src, total, flags, taken, base, sum; };
+struct Layout : pr::Arena { size_t row, dst, len, src, tot, flags, taken, base; };
 
 Layout layout_of(int32_t slot_capacity, int32_t w_max) {
   const size_t S = (size_t)slot_capacity, SL = S * (size_t)(2 * w_max + 1);
   Layout l;
-  l.sum = 0;
-  auto take = [&l](size_t bytes) { const size_t o = l.sum; l.sum += (bytes + 15) & ~(size_t)15; return o; };
-  l.row = take(4 * SL); l.dst = take(4 * SL); l.len = take(4 * SL); l.src = take(8 * SL);
-  l.total = take(4 * S); l.flags = take(4 * S); l.taken = take(4 * S); l.base = take(8 * S);
+  l.row = l.take(4 * SL); l.dst = l.take(4 * SL); l.len = l.take(4 * SL); l.src = l.take(8 * SL);
+  l.tot = l.take(4 * S); l.flags = l.take(4 * S); l.taken = l.take(4 * S); l.base = l.take(8 * S);
   return l;
 }
 
@@ -60,7 +57,7 @@ extern "C" {
 
 int64_t pr_submap_scratch_bytes(int32_t slot_capacity, int32_t w_max) {
   if (!sizes_ok(slot_capacity, w_max)) return 0;
-  return (int64_t)layout_of(slot_capacity, w_max).sum;
+  return (int64_t)layout_of(slot_capacity, w_max).total;
 }
 
 int pr_submap_create(pr_ctx* ctx, int32_t slot_capacity, int32_t w_max, int64_t point_capacity, int32_t max_cloud_points, int32_t keyframe_capacity,
@@ -78,44 +75,22 @@ int pr_submap_create(pr_ctx* ctx, int32_t slot_capacity, int32_t w_max, int64_t 
   if (keyframe_capacity < 1 || keyframe_capacity > MAX_KEYFRAMES)
     return fail(ctx, PR_EINVAL, "pr_submap_create: keyframe_capacity=%d outside 1 .. %d", keyframe_capacity, MAX_KEYFRAMES);
   if (!ctx) return fail(nullptr, PR_EINVAL, "pr_submap_create: ctx is NULL");
-  PR_CHECK_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
-  pr_submap* g = new (std::nothrow) pr_submap;
-  if (!g) return fail(ctx, PR_ENOMEM, "out of host memory");
-  g->ctx = ctx;
+  const Layout l = layout_of(slot_capacity, w_max);
+  pr::Owned<pr_submap> g;
+  if (int rc = pr::make(ctx, "pr_submap_create", l.total, g)) return rc;
   pr::SubmapView& v = g->v;
   memset(&v, 0, sizeof v);
   v.slot_capacity = slot_capacity; v.w_max = w_max; v.L = 2 * w_max + 1; v.max_cloud_points = max_cloud_points;
   v.keyframe_capacity = keyframe_capacity; v.chunks = pr::submap_chunks(max_cloud_points); v.point_capacity = point_capacity;
-  const Layout l = layout_of(slot_capacity, w_max);
-  hipError_t e = hipMalloc(&g->scratch, l.sum);
-  if (e != hipSuccess) {
-    delete g;
-    return fail(ctx, e == hipErrorOutOfMemory ? PR_ENOMEM : PR_EHIP, "pr_submap_create: scratch of %zu bytes: %s", l.sum, hipGetErrorString(e));
-  }
-  char* b = static_cast<char*>(g->scratch);
-  auto ip = [b](size_t o) { return reinterpret_cast<int*>(b + o); };
-  auto lp = [b](size_t o) { return reinterpret_cast<long long*>(b + o); };
-  v.row = ip(l.row); v.dst = ip(l.dst); v.len = ip(l.len); v.src = lp(l.src); v.total = ip(l.total); v.flags = ip(l.flags); v.taken = ip(l.taken);
-  v.base = lp(l.base);
-  hipStream_t st = pr::ctx_stream(ctx);
-  e = hipMemsetAsync(g->scratch, 0, l.sum, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) {
-    (void)hipFree(g->scratch);
-    delete g;
-    return fail(ctx, PR_EHIP, "pr_submap_create: clearing the scratch failed: %s", hipGetErrorString(e));
-  }
-  *out = g;
-  return PR_OK;
+  void* b = g->scratch;
+  v.row = at<int>(b, l.row); v.dst = at<int>(b, l.dst); v.len = at<int>(b, l.len); v.src = at<long long>(b, l.src);
+  v.total = at<int>(b, l.tot); v.flags = at<int>(b, l.flags); v.taken = at<int>(b, l.taken); v.base = at<long long>(b, l.base);
+  pr::Transfer t(ctx);
+  t.fill(b, 0, l.total);
+  return pr::commit(g, t, "pr_submap_create", out);
 }
 
-void pr_submap_destroy(pr_submap* g) {
-  if (!g) return;
-  (void)hipSetDevice(pr::ctx_device(g->ctx));
-  (void)hipStreamSynchronize(pr::ctx_stream(g->ctx));
-  (void)hipFree(g->scratch);
-  delete g;
-}
+void pr_submap_destroy(pr_submap* g) { pr::destroy(g); }
 
 int pr_submap_build_dev(pr_submap* g, const pr_map_buffers* map, const double* d_poses, const int32_t* d_n, const int32_t* d_center,
                         const int32_t* d_avoid, int32_t c, const pr_submap_params* params, double* out_xyz, int64_t* out_offs, int32_t* out_rows,
@@ -148,35 +123,28 @@ int pr_submap_build(pr_submap* g, const pr_map_buffers* map, const double* d_pos
   if (!d_poses || !d_n || (!center && c > 0) || !out_xyz || !out_offs || !out_rows || !info)
     return fail(ctx, PR_EINVAL, "pr_submap_build: a required pointer is NULL (d_poses, d_n, center, out_xyz, out_offs, out_rows, info)");
   PR_CHECK_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
-  hipStream_t st = pr::ctx_stream(ctx);
   const size_t S = (size_t)g->v.slot_capacity, CB = ((size_t)c * 4 + 15) & ~(size_t)15;
   // the staging of this call: centre, avoid, offs, rows, info, then the points
   const size_t o_cen = 0, o_avoid = o_cen + CB, o_offs = o_avoid + CB, o_rows = o_offs + (((S + 1) * 8 + 15) & ~(size_t)15), o_info = o_rows + S * 8 + 8,
                o_xyz = o_info + 16, bytes = o_xyz + (size_t)g->v.point_capacity * 24;
-  char* b = nullptr;
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(&b), bytes);
+  void* b = nullptr;
+  hipError_t e = hipMalloc(&b, bytes);
   if (e != hipSuccess) return fail(ctx, pr::hip_code(e), "pr_submap_build: staging of %zu bytes: %s", bytes, hipGetErrorString(e));
-  int rc = PR_OK;
-  if (c > 0) e = hipMemcpyAsync(b + o_cen, center, (size_t)c * 4, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess && c > 0 && avoid) e = hipMemcpyAsync(b + o_avoid, avoid, (size_t)c * 4, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess)
-    rc = pr_submap_build_dev(g, map, d_poses, d_n, reinterpret_cast<int32_t*>(b + o_cen), avoid ? reinterpret_cast<int32_t*>(b + o_avoid) : nullptr, c,
-                             params, reinterpret_cast<double*>(b + o_xyz), reinterpret_cast<int64_t*>(b + o_offs),
-                             reinterpret_cast<int32_t*>(b + o_rows), reinterpret_cast<int32_t*>(b + o_info));
-  if (e == hipSuccess && rc == PR_OK) e = hipMemcpyAsync(out_offs, b + o_offs, (S + 1) * 8, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess && rc == PR_OK) e = hipMemcpyAsync(out_rows, b + o_rows, S * 8, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess && rc == PR_OK) e = hipMemcpyAsync(info, b + o_info, 16, hipMemcpyDeviceToHost, st);
-  hipError_t es = hipStreamSynchronize(st);                      // out_offs[c] says how many rows of out_xyz were written
-  if (e == hipSuccess) e = es;
-  if (e == hipSuccess && rc == PR_OK && out_offs[c] > 0) {
-    e = hipMemcpyAsync(out_xyz, b + o_xyz, (size_t)out_offs[c] * 24, hipMemcpyDeviceToHost, st);
-    es = hipStreamSynchronize(st);
-    if (e == hipSuccess) e = es;
-  }
+  pr::Transfer t(ctx);
+  t.up(at<int32_t>(b, o_cen), center, (size_t)c * 4);
+  t.up_opt(at<int32_t>(b, o_avoid), avoid, (size_t)c * 4);
+  t.run([&] {
+    return pr_submap_build_dev(g, map, d_poses, d_n, at<int32_t>(b, o_cen), avoid ? at<int32_t>(b, o_avoid) : nullptr, c, params,
+                               at<double>(b, o_xyz), at<int64_t>(b, o_offs), at<int32_t>(b, o_rows), at<int32_t>(b, o_info));
+  });
+  t.down(out_offs, at<int64_t>(b, o_offs), (S + 1) * 8);
+  t.down(out_rows, at<int32_t>(b, o_rows), S * 8);
+  t.down(info, at<int32_t>(b, o_info), 16);
+  t.sync();                                                      // out_offs[c] says how many rows of out_xyz were written
+  if (t.ok() && out_offs[c] > 0) t.down(out_xyz, at<double>(b, o_xyz), (size_t)out_offs[c] * 24);
+  const int rc = t.finish(ctx, "pr_submap_build");
   (void)hipFree(b);
-  if (rc != PR_OK) return rc;
-  if (e != hipSuccess) return fail(ctx, pr::hip_code(e), "pr_submap_build: %s", hipGetErrorString(e));
-  return PR_OK;
+  return rc;
 }
 
 }  // extern "C"

@@ -1,14 +1,13 @@
 // trajeval.cpp — host side of the trajectory evaluation (trajeval.hip): the opaque pr_trajeval, its ONE scratch allocation
-// with the two tables, the argument checks, the stream-ordered run and its host form.
+// with the two tables, the argument checks, the stream-ordered run and its host form, on the shared handle core (handle_core.hpp).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstdio>
 #include <cstring>
-#include <new>
 
 #include "../../include/place_recognition.h"
-#include "host_common.hpp"
+#include "handle_core.hpp"
 #include "kernels.hpp"
 #include "trajeval.hpp"
 
@@ -21,35 +20,32 @@ static_assert(pr::TRAJ_ATE == PR_TRAJ_ATE_STATS && pr::TRAJ_RPE == PR_TRAJ_RPE_S
 static_assert(sizeof(pr_trajeval_params) == 48, "eight int32 and two doubles, no padding");
 static_assert(sizeof(pr_trajeval_out) == 9 * sizeof(void*), "nine pointers");
 
-struct pr_trajeval {
-  pr_ctx* ctx = nullptr;
+struct pr_trajeval : pr::Handle {    // scratch: everything TrajView names and the staging of the host form
   pr::TrajView v;
-  void* scratch = nullptr;            // one allocation: everything TrajView names and the staging of the host form
   pr::TrajOut stage;                  // the staging of the host form
 };
 
 namespace {
 
+using pr::at;
 using pr::fail;
 
 constexpr int32_t MAX_NODES = 1 << 20, MAX_EDGES = 65536;
 
 // where the parts of the one scratch allocation lie (each on a 16-byte boundary); the formula of the header
-struct Layout {
-  size_t used, gtok, cen, prefix, S, segsum, deltas, lengths, s_ate, s_rpe, s_seg, s_clo, s_err, s_end, s_edge, total;
+struct Layout : pr::Arena {
+  size_t used, gtok, cen, prefix, S, segsum, deltas, lengths, s_ate, s_rpe, s_seg, s_clo, s_err, s_end, s_edge;
 };
 
 Layout layout_of(const pr_trajeval_params& p) {
   const size_t cap = (size_t)p.node_capacity, B = (size_t)p.batch, K = (size_t)p.n_deltas, L = (size_t)p.n_lengths, EC = (size_t)p.edge_capacity;
   const size_t slots = (size_t)pr::traj_slots(p.node_capacity, p.step);
   Layout l;
-  l.total = 0;
-  auto take = [&l](size_t bytes) { const size_t o = l.total; l.total += (bytes + 15) & ~(size_t)15; return o; };
-  l.used = take(4 * B * cap); l.gtok = take(4 * cap); l.cen = take(24 * (B + 1) * cap); l.prefix = take(16 * B * cap); l.S = take(128 * B);
-  l.segsum = take(32 * B * L);
-  l.deltas = take(32); l.lengths = take(64);
-  l.s_ate = take(8 * pr::TRAJ_ATE * B); l.s_rpe = take(8 * pr::TRAJ_RPE * B * K); l.s_seg = take(8 * pr::TRAJ_SEG * B * (L + 1));
-  l.s_clo = take(8 * pr::TRAJ_CLO); l.s_err = take(8 * B * cap); l.s_end = take(4 * B * slots * L); l.s_edge = take(16 * EC);
+  l.used = l.take(4 * B * cap); l.gtok = l.take(4 * cap); l.cen = l.take(24 * (B + 1) * cap); l.prefix = l.take(16 * B * cap); l.S = l.take(128 * B);
+  l.segsum = l.take(32 * B * L);
+  l.deltas = l.take(32); l.lengths = l.take(64);
+  l.s_ate = l.take(8 * pr::TRAJ_ATE * B); l.s_rpe = l.take(8 * pr::TRAJ_RPE * B * K); l.s_seg = l.take(8 * pr::TRAJ_SEG * B * (L + 1));
+  l.s_clo = l.take(8 * pr::TRAJ_CLO); l.s_err = l.take(8 * B * cap); l.s_end = l.take(4 * B * slots * L); l.s_edge = l.take(16 * EC);
   return l;
 }
 
@@ -110,51 +106,29 @@ int pr_trajeval_create(pr_ctx* ctx, const pr_trajeval_params* params, const int3
   if (int rc = check_sizes(ctx, params)) return rc;
   if (int rc = check_tables(ctx, params, deltas, lengths)) return rc;
   if (!ctx) return fail(nullptr, PR_EINVAL, "pr_trajeval_create: ctx is NULL");
-  PR_CHECK_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
-  pr_trajeval* g = new (std::nothrow) pr_trajeval;
-  if (!g) return fail(ctx, PR_ENOMEM, "out of host memory");
-  g->ctx = ctx;
+  const Layout l = layout_of(*params);
+  pr::Owned<pr_trajeval> g;
+  if (int rc = pr::make(ctx, "pr_trajeval_create", l.total, g)) return rc;
   pr::TrajView& v = g->v;
   memset(&v, 0, sizeof v);
   memset(&g->stage, 0, sizeof g->stage);
   v.cap = params->node_capacity; v.B = params->batch; v.align = params->align; v.gt_kind = params->gt_kind;
   v.K = params->n_deltas; v.L = params->n_lengths; v.step = params->step; v.slots = pr::traj_slots(v.cap, v.step);
   v.edge_capacity = params->edge_capacity; v.rot_thr = params->rot_thr; v.trans_thr = params->trans_thr;
-  const Layout l = layout_of(*params);
-  hipError_t e = hipMalloc(&g->scratch, l.total);
-  if (e != hipSuccess) {
-    delete g;
-    return fail(ctx, e == hipErrorOutOfMemory ? PR_ENOMEM : PR_EHIP, "pr_trajeval_create: scratch of %zu bytes: %s", l.total, hipGetErrorString(e));
-  }
-  char* b = static_cast<char*>(g->scratch);
-  auto ip = [b](size_t o) { return reinterpret_cast<int*>(b + o); };
-  auto dp = [b](size_t o) { return reinterpret_cast<double*>(b + o); };
-  v.used = ip(l.used); v.gtok = ip(l.gtok); v.cen = dp(l.cen); v.prefix = dp(l.prefix); v.S = dp(l.S); v.segsum = dp(l.segsum);
-  v.deltas = ip(l.deltas); v.lengths = dp(l.lengths);
-  g->stage.ate = dp(l.s_ate); g->stage.rpe = dp(l.s_rpe); g->stage.seg = dp(l.s_seg); g->stage.clo = dp(l.s_clo); g->stage.err = dp(l.s_err);
-  g->stage.seg_end = ip(l.s_end); g->stage.edge_err = dp(l.s_edge);
-  hipStream_t st = pr::ctx_stream(ctx);
-  e = hipMemsetAsync(g->scratch, 0, l.total, st);
-  if (e == hipSuccess && v.K > 0) e = hipMemcpyAsync(b + l.deltas, deltas, 4 * (size_t)v.K, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess && v.L > 0) e = hipMemcpyAsync(b + l.lengths, lengths, 8 * (size_t)v.L, hipMemcpyHostToDevice, st);
-  const hipError_t es = hipStreamSynchronize(st);                // the host tables are in flight until here
-  if (e == hipSuccess) e = es;
-  if (e != hipSuccess) {
-    (void)hipFree(g->scratch);
-    delete g;
-    return fail(ctx, PR_EHIP, "pr_trajeval_create: clearing the scratch and uploading the tables failed: %s", hipGetErrorString(e));
-  }
-  *out = g;
-  return PR_OK;
+  void* b = g->scratch;
+  v.used = at<int>(b, l.used); v.gtok = at<int>(b, l.gtok); v.cen = at<double>(b, l.cen); v.prefix = at<double>(b, l.prefix);
+  v.S = at<double>(b, l.S); v.segsum = at<double>(b, l.segsum); v.deltas = at<int>(b, l.deltas); v.lengths = at<double>(b, l.lengths);
+  pr::TrajOut& s = g->stage;
+  s.ate = at<double>(b, l.s_ate); s.rpe = at<double>(b, l.s_rpe); s.seg = at<double>(b, l.s_seg); s.clo = at<double>(b, l.s_clo);
+  s.err = at<double>(b, l.s_err); s.seg_end = at<int>(b, l.s_end); s.edge_err = at<double>(b, l.s_edge);
+  pr::Transfer t(ctx);
+  t.fill(b, 0, l.total);
+  t.up(at<int>(b, l.deltas), deltas, 4 * (size_t)v.K);           // (a table of no entries may be NULL)
+  t.up(at<double>(b, l.lengths), lengths, 8 * (size_t)v.L);
+  return pr::commit(g, t, "pr_trajeval_create", out);
 }
 
-void pr_trajeval_destroy(pr_trajeval* g) {
-  if (!g) return;
-  (void)hipSetDevice(pr::ctx_device(g->ctx));
-  (void)hipStreamSynchronize(pr::ctx_stream(g->ctx));
-  (void)hipFree(g->scratch);
-  delete g;
-}
+void pr_trajeval_destroy(pr_trajeval* g) { pr::destroy(g); }
 
 int pr_trajeval_run_dev(pr_trajeval* g, const double* d_est, const int32_t* d_n, const void* d_gt, const uint8_t* d_valid,
                         const pr_posegraph_buffers* log, const pr_trajeval_out* out) {
@@ -188,26 +162,19 @@ int pr_trajeval_run(pr_trajeval* g, const double* d_est, const int32_t* d_n, con
   d.ate = g->stage.ate; d.rpe = v.K > 0 ? g->stage.rpe : nullptr; d.seg = v.L > 0 ? g->stage.seg : nullptr; d.clo = log ? g->stage.clo : nullptr;
   d.err = out->err ? g->stage.err : nullptr; d.seg_end = out->seg_end && v.L > 0 ? g->stage.seg_end : nullptr;
   d.edge_err = out->edge_err && log ? g->stage.edge_err : nullptr;      // the centres and the prefixes are read from the scratch itself
-  if (int rc = pr_trajeval_run_dev(g, d_est, d_n, d_gt, d_valid, log, &d)) return rc;
-  hipStream_t st = pr::ctx_stream(ctx);
   const size_t cap = (size_t)v.cap, B = (size_t)v.B, K = (size_t)v.K, L = (size_t)v.L;
-  hipError_t e = hipSuccess;
-  auto back = [&e, st](void* dst, const void* src, size_t bytes) {
-    if (e == hipSuccess && dst && src && bytes) e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st);
-  };
-  back(out->ate, d.ate, 8 * pr::TRAJ_ATE * B);
-  back(out->rpe, d.rpe, 8 * pr::TRAJ_RPE * B * K);
-  back(out->seg, d.seg, 8 * pr::TRAJ_SEG * B * (L + 1));
-  back(out->clo, d.clo, 8 * pr::TRAJ_CLO);
-  back(out->err, d.err, 8 * B * cap);
-  back(out->seg_end, d.seg_end, 4 * B * (size_t)v.slots * L);
-  back(out->edge_err, d.edge_err, 16 * (size_t)v.edge_capacity);
-  back(out->centres, v.cen, 24 * (B + 1) * cap);
-  back(out->prefix, v.prefix, 16 * B * cap);
-  const hipError_t es = hipStreamSynchronize(st);                // the host arrays are in flight until here
-  if (e == hipSuccess) e = es;
-  if (e != hipSuccess) return fail(ctx, pr::hip_code(e), "pr_trajeval_run: %s", hipGetErrorString(e));
-  return PR_OK;
+  pr::Transfer t(ctx);
+  t.run([&] { return pr_trajeval_run_dev(g, d_est, d_n, d_gt, d_valid, log, &d); });
+  t.down(out->ate, d.ate, 8 * pr::TRAJ_ATE * B);
+  t.down(out->rpe, d.rpe, 8 * pr::TRAJ_RPE * B * K);
+  t.down(out->seg, d.seg, 8 * pr::TRAJ_SEG * B * (L + 1));
+  t.down(out->clo, d.clo, 8 * pr::TRAJ_CLO);
+  t.down(out->err, d.err, 8 * B * cap);
+  t.down(out->seg_end, d.seg_end, 4 * B * (size_t)v.slots * L);
+  t.down(out->edge_err, d.edge_err, 16 * (size_t)v.edge_capacity);
+  t.down(out->centres, v.cen, 24 * (B + 1) * cap);
+  t.down(out->prefix, v.prefix, 16 * B * cap);
+  return t.finish(ctx, "pr_trajeval_run");
 }
 
 }  // extern "C"

@@ -6,12 +6,11 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
-#include <new>
 #include <vector>
 
 #include "../../include/place_recognition.h"
 #include "hash_order.hpp"
-#include "host_common.hpp"
+#include "handle_core.hpp"
 #include "kernels.hpp"
 
 static_assert(pr::WIN_OVERFLOW == PR_WINDOW_OVERFLOW && pr::WIN_ORDER_GLOBAL == PR_WINDOW_ORDER_GLOBAL, "flag bits");
@@ -77,15 +76,14 @@ int build(pr_window* w, double range, int polar, int32_t cap, int32_t max_new, i
   WN_ALLOC(w->h_info, 4);
 #undef WN_ALLOC
   v.sched_cnt = d_scnt; v.sched_nb = d_snb;
-  hipStream_t st = pr::ctx_stream(w->ctx);
-  PR_CHECK_HIP(w->ctx, hipMemcpyAsync(d_scnt, scnt.data(), scnt.size() * sizeof(int), hipMemcpyHostToDevice, st));
-  PR_CHECK_HIP(w->ctx, hipMemcpyAsync(d_snb, snb.data(), snb.size() * sizeof(int), hipMemcpyHostToDevice, st));
-  PR_CHECK_HIP(w->ctx, hipMemsetAsync(v.st, 0, pr::WIN_STATE_WORDS * sizeof(int), st));
-  PR_CHECK_HIP(w->ctx, hipMemsetAsync(v.tval, 0xFF, (size_t)v.C * 8, st));      // "empty"; every push leaves the table so (win_clear_kernel)
-  PR_CHECK_HIP(w->ctx, hipMemsetAsync(v.tfirst, 0xFF, (size_t)v.C * 4, st));
-  PR_CHECK_HIP(w->ctx, hipMemsetAsync(v.tbest, 0xFF, (size_t)v.C * 4, st));
-  PR_CHECK_HIP(w->ctx, hipStreamSynchronize(st));                               // scnt / snb are this function's locals
-  return PR_OK;
+  pr::Transfer t(w->ctx);
+  t.up(d_scnt, scnt.data(), scnt.size() * sizeof(int));
+  t.up(d_snb, snb.data(), snb.size() * sizeof(int));
+  t.fill(v.st, 0, pr::WIN_STATE_WORDS * sizeof(int));
+  t.fill(v.tval, 0xFF, (size_t)v.C * 8);                   // "empty"; every push leaves the table so (win_clear_kernel)
+  t.fill(v.tfirst, 0xFF, (size_t)v.C * 4);
+  t.fill(v.tbest, 0xFF, (size_t)v.C * 4);
+  return t.finish(w->ctx, "pr_window_create");             // scnt / snb are this function's locals
 }
 
 }  // namespace
@@ -159,25 +157,24 @@ int pr_window_push(pr_window* w, const double* pose12, const double* xyz_new, co
   if (n_new < 0 || n_new > w->v.max_new)
     return fail(ctx, PR_EINVAL, "pr_window_push: n_new=%d outside 0 .. max_new_points=%d", n_new, w->v.max_new);
   PR_CHECK_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
-  hipStream_t st = pr::ctx_stream(ctx);
-  PR_CHECK_HIP(ctx, hipMemcpyAsync(w->h_pose, pose12, 12 * sizeof(double), hipMemcpyHostToDevice, st));
+  pr::Transfer t(ctx);
+  t.up(w->h_pose, pose12, 12 * sizeof(double));
   if (n_new > 0) {
-    PR_CHECK_HIP(ctx, hipMemcpyAsync(w->h_xyz, xyz_new, (size_t)n_new * 24, hipMemcpyHostToDevice, st));
-    PR_CHECK_HIP(ctx, hipMemcpyAsync(w->h_int, inten_new, (size_t)n_new * 4, hipMemcpyHostToDevice, st));
+    t.up(w->h_xyz, xyz_new, (size_t)n_new * 24);
+    t.up(w->h_int, inten_new, (size_t)n_new * 4);
   }
-  PR_CHECK_HIP(ctx, hipMemcpyAsync(w->h_n, &n_new, sizeof(int), hipMemcpyHostToDevice, st));
-  if (int rc = pr_window_push_dev(w, w->h_pose, w->h_xyz, w->h_int, w->h_n, w->v.max_new, w->h_oxyz, w->h_oint, w->h_offs, w->h_frame, w->h_info))
-    return rc;
-  PR_CHECK_HIP(ctx, hipMemcpyAsync(info, w->h_info, 4 * sizeof(int), hipMemcpyDeviceToHost, st));
-  PR_CHECK_HIP(ctx, hipMemcpyAsync(out_frame, w->h_frame, 16 * sizeof(double), hipMemcpyDeviceToHost, st));
-  PR_CHECK_HIP(ctx, hipStreamSynchronize(st));
+  t.up(w->h_n, &n_new, sizeof(int));
+  t.run([&] {
+    return pr_window_push_dev(w, w->h_pose, w->h_xyz, w->h_int, w->h_n, w->v.max_new, w->h_oxyz, w->h_oint, w->h_offs, w->h_frame, w->h_info);
+  });
+  t.down(info, w->h_info, 4 * sizeof(int));
+  t.down(out_frame, w->h_frame, 16 * sizeof(double));
+  if (int rc = t.finish(ctx, "pr_window_push")) return rc;
   *n_out = info[1];
-  if (*n_out > 0) {
-    PR_CHECK_HIP(ctx, hipMemcpyAsync(out_xyz, w->h_oxyz, (size_t)*n_out * 24, hipMemcpyDeviceToHost, st));
-    PR_CHECK_HIP(ctx, hipMemcpyAsync(out_inten, w->h_oint, (size_t)*n_out * 4, hipMemcpyDeviceToHost, st));
-    PR_CHECK_HIP(ctx, hipStreamSynchronize(st));
-  }
-  return PR_OK;
+  if (*n_out <= 0) return PR_OK;
+  t.down(out_xyz, w->h_oxyz, (size_t)*n_out * 24);
+  t.down(out_inten, w->h_oint, (size_t)*n_out * 4);
+  return t.finish(ctx, "pr_window_push");
 }
 
 }  // extern "C"

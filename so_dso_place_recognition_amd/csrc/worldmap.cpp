@@ -1,15 +1,15 @@
 // worldmap.cpp — host side of the world map (worldmap.hip): the opaque pr_worldmap over the caller's six output buffers and
-// a pr_map, its ONE scratch allocation, the argument checks, the stream-ordered fuse and its host form.
+// a pr_map, its ONE scratch allocation, the argument checks, the stream-ordered fuse and its host form, on the shared handle core
+// (handle_core.hpp).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
-#include <new>
 
 #include "../../include/place_recognition.h"
-#include "host_common.hpp"
+#include "handle_core.hpp"
 #include "kernels.hpp"
 
 static_assert(pr::WORLDMAP_OVERFLOW == PR_WORLDMAP_OVERFLOW && pr::WORLDMAP_SKIPPED == PR_WORLDMAP_SKIPPED &&
@@ -22,10 +22,8 @@ struct pr_map {
   pr::MapView v;
 };
 
-struct pr_worldmap {
-  pr_ctx* ctx = nullptr;
+struct pr_worldmap : pr::Handle {    // scratch: everything WorldMapView names and the staging of the host form
   pr::WorldMapView v;
-  void* scratch = nullptr;            // one allocation: everything WorldMapView names and the staging of the host form
   double* stage_poses = nullptr;      // [keyframe_capacity][12]
   int32_t* stage_n = nullptr;         // [4]
   int64_t* stage_info = nullptr;      // [4]
@@ -34,6 +32,7 @@ struct pr_worldmap {
 
 namespace {
 
+using pr::at;
 using pr::fail;
 
 // the value checks of a fuse, shared by both forms; they need no device
@@ -48,15 +47,13 @@ int check_fuse(pr_worldmap* wm, const char* who, double cell, int32_t min_count,
 
 // where the parts of the one scratch allocation lie (each on a 16-byte boundary): 20 T + 4 point_capacity + 8 nblk4 + 96 keyframe_capacity
 // + 64 bytes and what the rounding adds
-struct Layout { size_t slots, cnt, slot_of, blk, poses, n, info, total; };
+struct Layout : pr::Arena { size_t slots, cnt, slot_of, blk, poses, n, info; };
 
 Layout layout_of(int32_t kcap, int64_t pcap) {
   const size_t T = (size_t)1 << pr::worldmap_log2T(pcap), pc = (size_t)pcap, nblk4 = (((pc + 255) / 256) + 3) & ~(size_t)3;
   Layout l;
-  l.total = 0;
-  auto take = [&l](size_t bytes) { const size_t o = l.total; l.total += (bytes + 15) & ~(size_t)15; return o; };
-  l.slots = take(16 * T); l.cnt = take(4 * T + 16); l.slot_of = take(4 * pc); l.blk = take(8 * nblk4);
-  l.poses = take(96 * (size_t)kcap); l.n = take(16); l.info = take(32);
+  l.slots = l.take(16 * T); l.cnt = l.take(4 * T + 16); l.slot_of = l.take(4 * pc); l.blk = l.take(8 * nblk4);
+  l.poses = l.take(96 * (size_t)kcap); l.n = l.take(16); l.info = l.take(32);
   return l;
 }
 
@@ -89,10 +86,9 @@ int pr_worldmap_create(pr_ctx* ctx, pr_map* map, const pr_worldmap_buffers* buff
   const pr::MapView& m = map->v;
   if (m.pcap > pr::WORLDMAP_MAX_POINTS)
     return fail(ctx, PR_EINVAL, "pr_worldmap_create: the map's point_capacity=%lld exceeds 2^29 (slot indices are int32)", (long long)m.pcap);
-  PR_CHECK_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
-  pr_worldmap* wm = new (std::nothrow) pr_worldmap;
-  if (!wm) return fail(ctx, PR_ENOMEM, "out of host memory");
-  wm->ctx = ctx;
+  const Layout l = layout_of(m.kcap, m.pcap);
+  pr::Owned<pr_worldmap> wm;
+  if (int rc = pr::make(ctx, "pr_worldmap_create", l.total, wm)) return rc;
   wm->max_cloud = m.max_cloud;
   pr::WorldMapView& v = wm->v;
   memset(&v, 0, sizeof v);
@@ -102,51 +98,26 @@ int pr_worldmap_create(pr_ctx* ctx, pr_map* map, const pr_worldmap_buffers* buff
   v.log2T = pr::worldmap_log2T(m.pcap);
   v.nblk = (int)((m.pcap + 255) / 256);
   const size_t T = (size_t)1 << v.log2T;
-  const Layout l = layout_of(m.kcap, m.pcap);
-  const size_t total = l.total;
-  hipError_t e = hipMalloc(&wm->scratch, total);
-  if (e != hipSuccess) {
-    delete wm;
-    return fail(ctx, e == hipErrorOutOfMemory ? PR_ENOMEM : PR_EHIP, "pr_worldmap_create: scratch of %zu bytes: %s", total, hipGetErrorString(e));
-  }
-  char* b = static_cast<char*>(wm->scratch);
-  v.slots = reinterpret_cast<unsigned long long*>(b + l.slots);
-  v.cnt = reinterpret_cast<int*>(b + l.cnt);
+  void* b = wm->scratch;
+  v.slots = at<unsigned long long>(b, l.slots);
+  v.cnt = at<int>(b, l.cnt);
   v.ctl = v.cnt + T;                                      // behind the counts: one memset clears both
-  v.slot_of = reinterpret_cast<int*>(b + l.slot_of);
-  v.blk = reinterpret_cast<int*>(b + l.blk);
-  wm->stage_poses = reinterpret_cast<double*>(b + l.poses);
-  wm->stage_n = reinterpret_cast<int32_t*>(b + l.n);
-  wm->stage_info = reinterpret_cast<int64_t*>(b + l.info);
-  hipStream_t st = pr::ctx_stream(ctx);
-  e = hipMemsetAsync(v.state, 0, 4 * sizeof(int32_t), st);
-  if (e == hipSuccess) e = hipMemsetAsync(wm->scratch, 0, total, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) {
-    (void)hipFree(wm->scratch);
-    delete wm;
-    return fail(ctx, PR_EHIP, "pr_worldmap_create: clearing the state failed: %s", hipGetErrorString(e));
-  }
-  *out = wm;
-  return PR_OK;
+  v.slot_of = at<int>(b, l.slot_of); v.blk = at<int>(b, l.blk);
+  wm->stage_poses = at<double>(b, l.poses); wm->stage_n = at<int32_t>(b, l.n); wm->stage_info = at<int64_t>(b, l.info);
+  pr::Transfer t(ctx);
+  t.fill(v.state, 0, 4 * sizeof(int32_t));
+  t.fill(b, 0, l.total);
+  return pr::commit(wm, t, "pr_worldmap_create", out);
 }
 
-void pr_worldmap_destroy(pr_worldmap* wm) {
-  if (!wm) return;
-  (void)hipSetDevice(pr::ctx_device(wm->ctx));
-  (void)hipStreamSynchronize(pr::ctx_stream(wm->ctx));
-  (void)hipFree(wm->scratch);         // the six buffers are the caller's, the map is the caller's
-  delete wm;
-}
+// the six buffers are the caller's, the map is the caller's
+void pr_worldmap_destroy(pr_worldmap* wm) { pr::destroy(wm); }
 
 int pr_worldmap_count(pr_worldmap* wm, int64_t* rows, int32_t* flags) {
   if (!wm) return fail(nullptr, PR_EINVAL, "pr_worldmap_count: world map is NULL");
   if (!rows || !flags) return fail(wm->ctx, PR_EINVAL, "pr_worldmap_count: a required pointer is NULL");
-  PR_CHECK_HIP(wm->ctx, hipSetDevice(pr::ctx_device(wm->ctx)));
-  hipStream_t st = pr::ctx_stream(wm->ctx);
   int32_t s[4];
-  PR_CHECK_HIP(wm->ctx, hipMemcpyAsync(s, wm->v.state, sizeof s, hipMemcpyDeviceToHost, st));
-  PR_CHECK_HIP(wm->ctx, hipStreamSynchronize(st));
+  if (int rc = pr::read_state(wm->ctx, "pr_worldmap_count", wm->v.state, s)) return rc;
   *rows = s[0];
   *flags = s[1];
   return PR_OK;
@@ -173,27 +144,24 @@ int pr_worldmap_fuse(pr_worldmap* wm, const double* poses, const int32_t* n, dou
   if (!xyz || !inten || !src || !row || !count || !info)
     return fail(ctx, PR_EINVAL, "pr_worldmap_fuse: a required pointer is NULL (xyz, inten, src, row, count, info)");
   PR_CHECK_HIP(ctx, hipSetDevice(pr::ctx_device(ctx)));
-  hipStream_t st = pr::ctx_stream(ctx);
   const pr::WorldMapView& v = wm->v;
-  if (poses) PR_CHECK_HIP(ctx, hipMemcpyAsync(wm->stage_poses, poses, 96 * (size_t)v.kcap, hipMemcpyHostToDevice, st));
-  if (n) PR_CHECK_HIP(ctx, hipMemcpyAsync(wm->stage_n, n, sizeof(int32_t), hipMemcpyHostToDevice, st));
-  rc = pr_worldmap_fuse_dev(wm, poses ? wm->stage_poses : nullptr, n ? wm->stage_n : nullptr, cell, min_count, keep, wm->stage_info);
-  hipError_t e = hipSuccess;
-  if (rc == PR_OK) e = hipMemcpyAsync(info, wm->stage_info, 4 * sizeof(int64_t), hipMemcpyDeviceToHost, st);
-  const hipError_t e2 = hipStreamSynchronize(st);         // the host arrays are in flight until here
+  pr::Transfer t(ctx);
+  t.up_opt(wm->stage_poses, poses, 96 * (size_t)v.kcap);
+  t.up_opt(wm->stage_n, n, sizeof(int32_t));
+  t.run([&] {
+    return pr_worldmap_fuse_dev(wm, poses ? wm->stage_poses : nullptr, n ? wm->stage_n : nullptr, cell, min_count, keep, wm->stage_info);
+  });
+  t.down(info, wm->stage_info, 4 * sizeof(int64_t));
+  rc = t.finish(ctx, "pr_worldmap_fuse");                 // info[0] says how many rows were written
   if (rc != PR_OK) return rc;
-  PR_CHECK_HIP(ctx, e);
-  PR_CHECK_HIP(ctx, e2);
   const size_t rows = (size_t)std::min<int64_t>(std::max<int64_t>(info[0], 0), v.ocap);
-  if (rows) {
-    PR_CHECK_HIP(ctx, hipMemcpyAsync(xyz, v.xyz, rows * 24, hipMemcpyDeviceToHost, st));
-    PR_CHECK_HIP(ctx, hipMemcpyAsync(inten, v.inten, rows * 4, hipMemcpyDeviceToHost, st));
-    PR_CHECK_HIP(ctx, hipMemcpyAsync(src, v.src, rows * 8, hipMemcpyDeviceToHost, st));
-    PR_CHECK_HIP(ctx, hipMemcpyAsync(row, v.row, rows * 4, hipMemcpyDeviceToHost, st));
-    PR_CHECK_HIP(ctx, hipMemcpyAsync(count, v.count, rows * 4, hipMemcpyDeviceToHost, st));
-    PR_CHECK_HIP(ctx, hipStreamSynchronize(st));
-  }
-  return PR_OK;
+  if (!rows) return PR_OK;
+  t.down(xyz, v.xyz, rows * 24);
+  t.down(inten, v.inten, rows * 4);
+  t.down(src, v.src, rows * 8);
+  t.down(row, v.row, rows * 4);
+  t.down(count, v.count, rows * 4);
+  return t.finish(ctx, "pr_worldmap_fuse");
 }
 
 }  // extern "C"

@@ -311,6 +311,28 @@ def test_host_form_two_runs_and_one_capture_for_every_count(drive):
         rig.close(); g.close(); ctx.close()
 
 
+def test_host_form_without_known(drive):
+    """pr_proximity_search with known = NULL (allowed without a closure log): every output that was passed equals, byte for byte, that of
+    the call with all outputs, at the file's smallest rig"""
+    import ctypes as C
+    rig = Rig(15, 15, 4)
+    rig.load(drive[:15], 15, (0, 15))
+    full = rig.ps.search(rig.poses, rig.nd, rig.qr, **KW)
+    assert full.info[1] > 0
+    # ProximitySearch.search always allocates and passes every output, so known = NULL is reachable through the C entry point alone; the
+    # params record is built by the class's own helper so that it is the one search() passed above
+    k, prm, rec, ec = rig.ps._args("test", rig.poses, rig.nd, rig.qr, KW["radius"], KW["growth"], KW["radius_max"], -1.0, KW["min_gap"], KW["stride"],
+                                   KW["k"], None, 0)
+    got = {name: np.full(shape, GUARD % 256 if dt == np.uint8 else GUARD, dt) for name, (shape, dt) in rig.ps.shapes(k).items()}
+    p = lambda t: C.c_void_p(t.data_ptr())
+    outs = [None if name == "known" else got[name].ctypes.data_as(C.c_void_p) for name in NAMES]
+    rig.ctx.check(rig.ctx.lib.pr_proximity_search(rig.ps.h, p(rig.poses), p(rig.nd), p(rig.qr), C.byref(prm), None, ec, *outs))
+    for name in NAMES:
+        if name != "known":
+            assert same_bytes(got[name], np.asarray(getattr(full, name))), name
+    rig.close()
+
+
 # ------------------------------------------------------------------------------------------------ 9. the batch add
 def batch_inputs(c, seed):
     rng = np.random.default_rng(seed)

@@ -382,6 +382,25 @@ def test_online_host_form_large_k_and_refusals():
     rig.close()
 
 
+def test_online_read_with_null_outputs():
+    """pr_seqmatch_read with each output alone and with none: what was passed equals, byte for byte, that of the read with all three"""
+    L, cap = 4, 300
+    rig = OnlineRig(cap, 1, api.seq_steps(L, [1, -1, 0, 0.5]), 8)
+    for t, n in enumerate((40, 41)):
+        rig.push(rows_for(100 + t, n, cap, 1), n, (1.0,), False, 0, 2, what=("read", t))
+    ring, ids, pushes = rig.f.read()
+    assert pushes == 2
+    lib, h = rig.ctx.lib, rig.f.h
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    r2, i2, n2 = np.full_like(ring, GUARD), np.full_like(ids, GUARD), C.c_int32(GUARD)
+    rig.ctx.check(lib.pr_seqmatch_read(h, vp(r2), None, None))
+    rig.ctx.check(lib.pr_seqmatch_read(h, None, vp(i2), None))
+    rig.ctx.check(lib.pr_seqmatch_read(h, None, None, C.byref(n2)))
+    rig.ctx.check(lib.pr_seqmatch_read(h, None, None, None))
+    assert same_bytes(r2, ring) and same_bytes(i2, ids) and n2.value == pushes
+    rig.close()
+
+
 def test_the_drive_with_a_captured_sequence_push(seq07):
     """push -> SC generate -> match(rows=) -> SequenceFilter.push_torch(rows, db.state) -> append, per pose: eagerly, and as ONE graph
     captured behind the first eager step; the same bytes, and the restatement's over the rows the match wrote"""

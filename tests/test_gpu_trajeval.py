@@ -281,6 +281,24 @@ def test_host_form_two_runs_and_one_capture_for_every_count():
         rig.close(); g.close(); ctx.close()
 
 
+def test_host_form_without_optional_outputs():
+    """pr_trajeval_run with none and with some of err, seg_end, centres, prefix: every output that was passed equals, byte for byte, that of
+    the call with all of them, at the file's smallest rig"""
+    est, gt, valid = tn.case(65, cap=65, B=1, seed=9)
+    rig = Rig(est, gt, valid, align="se3", gt_kind="c2w", deltas=(1, 64), lengths=(10.0,), step=1)
+    rig.nd[0] = 65
+    full = rig.te.run(rig.est, rig.nd, rig.gt, valid=rig.valid)
+    assert all(getattr(full, name) is not None for name in ("ate", "rpe", "seg", "err", "seg_end", "centres", "prefix"))
+    for optional in ((), ("err", "prefix"), ("seg_end", "centres")):
+        part = rig.te.run(rig.est, rig.nd, rig.gt, valid=rig.valid, optional=optional)
+        for name in rig.te.NAMES:
+            if getattr(full, name) is not None and (name in ("ate", "rpe", "seg") or name in optional):
+                assert same_bytes(getattr(part, name), getattr(full, name)), (optional, name)
+            else:
+                assert getattr(part, name) is None, (optional, name)
+    rig.close()
+
+
 def test_relax_then_evaluate_as_one_graph_on_the_two_lap_circle():
     """test_gpu_posegraph.py's consistent graph: the relaxation recovers ground truth there, so the ATE after it is below the ATE before"""
     c = pg.consistent_case()
